@@ -11,11 +11,15 @@ Only Krylov-level work is counted: (iterations + 1) operator applications per CG
 
 The headline run is the FASTEST solver (time to solution): CG preconditioned by the block fast diagonalisation.  The metric's unit
 rewards operator applications, not solved steps - the polynomial (Chebyshev) preconditioner does 18 x more applications per step and
-therefore shows a 6 x higher `value` at 2.7 x the time per step - so the line also carries `best_ms_per_step` and, under
+therefore shows a 6 x higher `value` at 2.7 x the time per step - so with --full the line also carries `best_ms_per_step` and, under
 `time_to_solution`, the same step with the other preconditioners, and `config5`: 100 CONSECUTIVE steps of the transient (BASELINE config 5).
 
+A plain run (no --full) measures the headline alone: set-up, warm-up, the timed steps, the outputs of --dump-outputs and the JSON line.
+Everything else is measured with --full only: the other preconditioners, `config5`, the weak-scaled line, the rooflines (HIP events on the
+timed dispatches) and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64).
+
 Workload: 3D Q2/Q1 uniform box of 72^3 cells (N_u = 9 145 875: BASELINE config "3D Q2/Q1 ~10M DoF").  N > 1 cuts THAT mesh into N z-slabs
-(strong scaling: 9 cell layers per GPU at N = 8); the weak-scaled variant (72 layers per GPU, 72 x 72 x 72N box, same h) is measured
+(strong scaling: 9 cell layers per GPU at N = 8); with --full the weak-scaled variant (72 layers per GPU, 72 x 72 x 72N box, same h) is measured
 as well and reported under "weak_scaling_line".  `python bench.py --gpus N` starts its own N rank processes when it was not started by a launcher.
 Every timed step must do a real displacement solve: by default each timed step is time
 step 1 from the initial equilibrium (the device state is rolled back before every step - which also clears the solver's iteration-count history - so all
@@ -169,8 +173,9 @@ def committed_fdm_traffic():
         return None
 
 
-def run_case(args, scaling, steps, warmup, rank, world, local_rank, torch, dist, rccl_ids, prec=None, label="jacobi", transient=None, events=True):
-    """`warmup` untimed + `steps` timed time steps of one configuration; returns the measurements of this rank (elapsed = max over ranks)"""
+def run_case(args, scaling, steps, warmup, rank, world, local_rank, torch, dist, rccl_ids, prec=None, label="jacobi", transient=None, events=True, outputs=False):
+    """`warmup` untimed + `steps` timed time steps of one configuration; returns the measurements of this rank (elapsed = max over ranks);
+    outputs=True: also this rank's solution after the last timed step (read back after the timed region)"""
     dim, deg = args.dim, args.degree
     n, size = [args.n] * dim, [10.0] * dim
     if world > 1 and scaling == "weak":
@@ -244,8 +249,81 @@ def run_case(args, scaling, steps, warmup, rank, world, local_rank, torch, dist,
     out = {"n": n, "n_u_glob": n_u_glob, "n_p_glob": n_p_glob, "n_u_local": P.desc.n_dofs_u, "n_cells_local": n_cells, "elapsed": elapsed, "work": work,
            "updates": dof_updates(work, n_u_glob, n_p_glob, dim), "traces": traces, "step_seconds": step_seconds,
            "kernel_time": {k: G.timer(k) for k in families}}
+    if outputs:
+        out["outputs"] = {"u": G.get(pk.VEC_U), "p": G.get(pk.VEC_P), "volumetric_strain": G.get(pk.VEC_EPSV), "trace": traces[-1]}
     R.close(); P.close()
     return out
+
+
+def dump_outputs(path, outputs, rank, world):
+    """--dump-outputs: one float64 DIR/<name>.npy per array (N > 1: <name>_rank<r>.npy, this rank's slab).  An array of more than 2 M entries (divided
+    among the ranks) is written as a fixed seeded sample of 1 M entries, <name>_index.npy holds the sampled positions and <name>_norms.npy the
+    l2 / max-abs norms of the whole array: the files stay below 64 MB in all, whatever the mesh."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    whole, sample = (1 << 21) // world, (1 << 20) // world
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > whole:
+            idx = np.sort(np.random.default_rng(20240601).choice(a.size, sample, replace=False))
+            np.save(os.path.join(path, f"{name}_index{sfx}.npy"), idx.astype(np.float64))
+            np.save(os.path.join(path, f"{name}_norms{sfx}.npy"), np.array([np.linalg.norm(a), np.abs(a).max()]))
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+
+
+def rooflines(args, M, head, world):
+    """--full: the roofline of the dominant kernel of the headline run and of the operator application, from the HIP events of its timed steps"""
+    dim, deg = args.dim, args.degree
+    work, kernel_time = M["work"], M["kernel_time"]
+    # ---- rooflines (per launch, per GPU; kernel durations from HIP events attached to sampled dispatches inside the timed steps) ----
+    # operator y = A_u x (matrix-free, the kernel north_star names): HBM-bound, 16 N + 4 dpc n_cells algorithmic bytes (SURVEY 8d; the structured kernels read no index arrays:
+    # `frac_without_index_bytes`); with the Chebyshev preconditioner the polynomial update is fused into its stores (+ 8 N for the extra stream g).
+    t_plain, n_plain_launched = kernel_time["apply_u_matrix_free"]
+    t_cheb, n_cheb_launched = kernel_time["apply_u_chebyshev_fused"]
+    alg_plain = bytes_per_apply(dim, deg, M["n_u_local"], M["n_cells_local"], "matrix_free")
+    index_bytes = 4.0 * dim * (deg + 1) ** dim * M["n_cells_local"]
+    cg_total = int(work["cg_u"]); solves = int(work["asm_rhs_u"])
+    fused_cheb = n_cheb_launched > 0
+    n_plain_useful = (cg_total + solves) if (fused_cheb or head == "block_fdm") else (int(work["apply_u"]) or n_plain_launched)
+    avg_plain = t_plain / max(n_plain_useful, 1)
+    op_kernel = "k_kron3_q%d" % deg if dim == 3 else "k_kron2<%d>" % deg
+    roof_operator = {"bound": "hbm", "kernel": op_kernel + " (matrix-free y = A_u x, sum-factorised)", "achieved": alg_plain / avg_plain / 1e9 if (n_plain_useful and t_plain) else 0.0,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_launch": alg_plain, "avg_launch_us": 1e6 * avg_plain, "useful_launches": n_plain_useful,
+                     "traffic": committed_traffic(dim, deg, args.n, False) if world == 1 else None}
+    roof_operator["frac"] = roof_operator["achieved"] / HBM_PEAK_GBS
+    roof_operator["frac_without_index_bytes"] = (alg_plain - index_bytes) / avg_plain / 1e9 / HBM_PEAK_GBS if (n_plain_useful and t_plain) else 0.0
+    if fused_cheb:
+        n_cheb_useful = (args.cheb_degree + (args.cheb_degree & 1)) * (cg_total + solves)
+        avg_cheb = t_cheb / max(n_cheb_useful, 1); alg_cheb = alg_plain + 8.0 * M["n_u_local"]
+        roofline = {"bound": "hbm", "kernel": ("k_kron3_q%d_cheb" % deg if dim == 3 else "k_kron2<%d, true>" % deg) + " (matrix-free A_u z_j with the Chebyshev root-form update fused into the stores)",
+                    "achieved": alg_cheb / avg_cheb / 1e9 if avg_cheb > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": committed_traffic(dim, deg, args.n, True) if world == 1 else None,
+                    "algorithmic_bytes_per_launch": alg_cheb, "avg_launch_us": 1e6 * avg_cheb, "useful_launches": n_cheb_useful,
+                    "frac_without_index_bytes": (alg_cheb - index_bytes) / avg_cheb / 1e9 / HBM_PEAK_GBS if avg_cheb > 0 else 0.0}
+        roofline["frac"] = roofline["achieved"] / HBM_PEAK_GBS
+    elif head == "block_fdm" and kernel_time["fdm_u_pass1"][1] > 0:
+        # dominant kernel of the headline run: the transform pass of the block fast diagonalisation (3 launches per preconditioner application): GEMM-shaped, fp64 MFMA-bound.
+        # Algorithmic flops of one pass = 2 GEMMs per (component, octant, block) of the UNPADDED half-size problem: pass 1 / 3: 2 h_y h_x (h_x + h_y) per plane, pass 2: 4 h_z^2 per column.
+        nn = [deg * m + 1 for m in M["n"]]; h = [(v + 1) // 2 for v in nn]
+        flops_pass = [24.0 * h[2] * 2.0 * h[1] * h[0] * (h[0] + h[1]), 24.0 * h[0] * h[1] * 4.0 * h[2] * h[2], 24.0 * h[2] * 2.0 * h[1] * h[0] * (h[0] + h[1])]
+        t_pass = [kernel_time["fdm_u_pass%d" % (k + 1)][0] / max(kernel_time["fdm_u_pass%d" % (k + 1)][1], 1) for k in range(3)]
+        n_app = kernel_time["fdm_u_pass1"][1]
+        avg = sum(t_pass) / 3.0; fl = sum(flops_pass) / 3.0
+        n_oct_bytes = 8.0 * 24 * h[2] * h[1] * (h[0] + (h[0] & 1))
+        roofline = {"bound": "mfma", "kernel": "k_fdmo_pass<NT, MODE> (one sweep of the octant-form block fast diagonalisation: two chained half-size GEMMs per (component, octant, block) on v_mfma_f64_16x16x4_f64; 3 launches per preconditioner application)",
+                    "achieved": fl / avg / 1e12 if avg > 0 else 0.0, "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s", "algorithmic_flops_per_launch": fl, "avg_launch_us": 1e6 * avg,
+                    "avg_launch_us_by_pass": [1e6 * t for t in t_pass], "launches_enqueued": 3 * n_app,
+                    "traffic": committed_fdm_traffic() if world == 1 else None, "algorithmic_bytes_per_launch": 2.0 * n_oct_bytes,
+                    "hbm_frac_of_the_same_kernel": 2.0 * n_oct_bytes / avg / 1e9 / HBM_PEAK_GBS if avg > 0 else 0.0}
+        roofline["frac"] = roofline["achieved"] / MFMA_F64_PEAK_TFLOPS
+    else:
+        roofline = dict(roof_operator)
+    roofline["events_on_every_nth_launch"] = args.event_stride
+    roofline["note"] = ("kernel alone: HIP events attached to the dispatch itself (hipExtLaunchKernelGGL), as rocprofv3 reports it, on every events_on_every_nth_launch-th launch of the timed steps; "
+                        "`roofline` = the dominant kernel of the headline run, `roofline_operator` = the matrix-free operator application (HBM-bound; algorithmic bytes per SURVEY 8d, "
+                        "frac_without_index_bytes leaves out the element-index bytes the structured kernel does not read); traffic = PMC bytes per launch from profiles/, null unless measured on this kernel source")
+    return roofline, roof_operator
 
 
 def self_launch(args):
@@ -296,7 +374,14 @@ def main():
     ap.add_argument("--event-stride", type=int, default=8, help="attach HIP events to every n-th launch of each kernel family inside the timed region (1: every launch)")
     ap.add_argument("--no-kernel-events", action="store_true", help="diagnostic: do not attach HIP events to the kernel dispatches inside the timed region (no roofline figures)")
     ap.add_argument("--trace-out", default=None, help="write the per-step record of the config5 block (SURVEY 8d config 5: FSS / pressure / Krylov iteration counts, wall-clock) to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the other preconditioners (time_to_solution), config5, the weak-scaled line (N > 1), the rooflines "
+                         "(HIP events on the timed dispatches) and the CPU baseline; the --no-* / --config5-steps / --cpu-* / --event-stride / --trace-out options act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (displacement u, pressure p, volumetric strain, the step's trace) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.trace_out and not args.full:
+        ap.error("--trace-out records the config5 block, which runs with --full only")
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and args.gpus > 1:
@@ -327,9 +412,9 @@ def main():
     PREC = {"jacobi": pk.PREC_JACOBI, "chebyshev": pk.PREC_CHEBYSHEV, "block_fdm": pk.PREC_FDM}
     head = args.prec
     # one RCCL communicator per context: partitioned runs measure the headline solver (+ its weak-scaled and transient runs) only
-    others = [] if (args.no_variants or world > 1) else [k for k in ("block_fdm", "chebyshev", "jacobi") if k != head]
-    weak_line = world > 1 and args.scaling == "strong" and not args.no_weak_line
-    cfg5 = args.config5_steps > 0
+    others = [] if (not args.full or args.no_variants or world > 1) else [k for k in ("block_fdm", "chebyshev", "jacobi") if k != head]
+    weak_line = args.full and world > 1 and args.scaling == "strong" and not args.no_weak_line
+    cfg5 = args.full and args.config5_steps > 0
     rccl_ids = {}
     if world > 1 and not args.share_gpu:      # ids from rank 0
         labels = [head + args.scaling] + ([head + "weak"] if weak_line else []) + ([head + "config5" + args.scaling] if cfg5 else [])
@@ -351,57 +436,13 @@ def main():
             raise RuntimeError(err)
         return out
 
-    M = attempt(args, args.scaling, args.steps, args.warmup, rank, world, local_rank, torch, dist, rccl_ids, prec=PREC[head], label=head)
+    # the headline; HIP events on its timed dispatches only for the rooflines of --full
+    M = attempt(args, args.scaling, args.steps, args.warmup, rank, world, local_rank, torch, dist, rccl_ids, prec=PREC[head], label=head, events=args.full, outputs=bool(args.dump_outputs))
     work, elapsed, updates, traces, step_seconds = M["work"], M["elapsed"], M["updates"], M["traces"], M["step_seconds"]
     n, n_u_glob, n_p_glob = M["n"], M["n_u_glob"], M["n_p_glob"]
     kernel_time = M["kernel_time"]
-
-    # ---- rooflines (per launch, per GPU; kernel durations from HIP events attached to sampled dispatches inside the timed steps) ----
-    # operator y = A_u x (matrix-free, the kernel north_star names): HBM-bound, 16 N + 4 dpc n_cells algorithmic bytes (the structured kernels read no index arrays:
-    # `frac_without_index_bytes`); with the Chebyshev preconditioner the polynomial update is fused into its stores (+ 8 N for the extra stream g).
-    t_plain, n_plain_launched = kernel_time["apply_u_matrix_free"]
-    t_cheb, n_cheb_launched = kernel_time["apply_u_chebyshev_fused"]
-    alg_plain = bytes_per_apply(dim, deg, M["n_u_local"], M["n_cells_local"], "matrix_free")
-    index_bytes = 4.0 * dim * (deg + 1) ** dim * M["n_cells_local"]
-    cg_total = int(work["cg_u"]); solves = int(work["asm_rhs_u"])
-    fused_cheb = n_cheb_launched > 0
-    n_plain_useful = (cg_total + solves) if (fused_cheb or head == "block_fdm") else (int(work["apply_u"]) or n_plain_launched)
-    avg_plain = t_plain / max(n_plain_useful, 1)
-    op_kernel = "k_kron3_q%d" % deg if dim == 3 else "k_kron2<%d>" % deg
-    roof_operator = {"bound": "hbm", "kernel": op_kernel + " (matrix-free y = A_u x, sum-factorised)", "achieved": alg_plain / avg_plain / 1e9 if (n_plain_useful and t_plain) else 0.0,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_launch": alg_plain, "avg_launch_us": 1e6 * avg_plain, "useful_launches": n_plain_useful,
-                     "traffic": committed_traffic(dim, deg, args.n, False) if world == 1 else None}
-    roof_operator["frac"] = roof_operator["achieved"] / HBM_PEAK_GBS
-    roof_operator["frac_without_index_bytes"] = (alg_plain - index_bytes) / avg_plain / 1e9 / HBM_PEAK_GBS if (n_plain_useful and t_plain) else 0.0
-    if fused_cheb:
-        n_cheb_useful = (args.cheb_degree + (args.cheb_degree & 1)) * (cg_total + solves)
-        avg_cheb = t_cheb / max(n_cheb_useful, 1); alg_cheb = alg_plain + 8.0 * M["n_u_local"]
-        roofline = {"bound": "hbm", "kernel": ("k_kron3_q%d_cheb" % deg if dim == 3 else "k_kron2<%d, true>" % deg) + " (matrix-free A_u z_j with the Chebyshev root-form update fused into the stores)",
-                    "achieved": alg_cheb / avg_cheb / 1e9 if avg_cheb > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": committed_traffic(dim, deg, args.n, True) if world == 1 else None,
-                    "algorithmic_bytes_per_launch": alg_cheb, "avg_launch_us": 1e6 * avg_cheb, "useful_launches": n_cheb_useful,
-                    "frac_without_index_bytes": (alg_cheb - index_bytes) / avg_cheb / 1e9 / HBM_PEAK_GBS if avg_cheb > 0 else 0.0}
-        roofline["frac"] = roofline["achieved"] / HBM_PEAK_GBS
-    elif head == "block_fdm" and kernel_time["fdm_u_pass1"][1] > 0:
-        # dominant kernel of the headline run: the transform pass of the block fast diagonalisation (3 launches per preconditioner application): GEMM-shaped, fp64 MFMA-bound.
-        # Algorithmic flops of one pass = 2 GEMMs per (component, octant, block) of the UNPADDED half-size problem: pass 1 / 3: 2 h_y h_x (h_x + h_y) per plane, pass 2: 4 h_z^2 per column.
-        nn = [deg * m + 1 for m in M["n"]]; h = [(v + 1) // 2 for v in nn]
-        flops_pass = [24.0 * h[2] * 2.0 * h[1] * h[0] * (h[0] + h[1]), 24.0 * h[0] * h[1] * 4.0 * h[2] * h[2], 24.0 * h[2] * 2.0 * h[1] * h[0] * (h[0] + h[1])]
-        t_pass = [kernel_time["fdm_u_pass%d" % (k + 1)][0] / max(kernel_time["fdm_u_pass%d" % (k + 1)][1], 1) for k in range(3)]
-        n_app = kernel_time["fdm_u_pass1"][1]
-        avg = sum(t_pass) / 3.0; fl = sum(flops_pass) / 3.0
-        n_oct_bytes = 8.0 * 24 * h[2] * h[1] * (h[0] + (h[0] & 1))
-        roofline = {"bound": "mfma", "kernel": "k_fdmo_pass<NT, MODE> (one sweep of the octant-form block fast diagonalisation: two chained half-size GEMMs per (component, octant, block) on v_mfma_f64_16x16x4_f64; 3 launches per preconditioner application)",
-                    "achieved": fl / avg / 1e12 if avg > 0 else 0.0, "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s", "algorithmic_flops_per_launch": fl, "avg_launch_us": 1e6 * avg,
-                    "avg_launch_us_by_pass": [1e6 * t for t in t_pass], "launches_enqueued": 3 * n_app,
-                    "traffic": committed_fdm_traffic() if world == 1 else None, "algorithmic_bytes_per_launch": 2.0 * n_oct_bytes,
-                    "hbm_frac_of_the_same_kernel": 2.0 * n_oct_bytes / avg / 1e9 / HBM_PEAK_GBS if avg > 0 else 0.0}
-        roofline["frac"] = roofline["achieved"] / MFMA_F64_PEAK_TFLOPS
-    else:
-        roofline = dict(roof_operator)
-    roofline["events_on_every_nth_launch"] = args.event_stride
-    roofline["note"] = ("kernel alone: HIP events attached to the dispatch itself (hipExtLaunchKernelGGL), as rocprofv3 reports it, on every events_on_every_nth_launch-th launch of the timed steps; "
-                        "`roofline` = the dominant kernel of the headline run, `roofline_operator` = the matrix-free operator application (HBM-bound; algorithmic bytes per SURVEY 8d, "
-                        "frac_without_index_bytes leaves out the element-index bytes the structured kernel does not read); traffic = PMC bytes per launch from profiles/, null unless measured on this kernel source")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, M.pop("outputs"), rank, world)
 
     # ---- the same steps with the other preconditioners of the displacement CG ----
     def summary(V, prec_name):
@@ -452,19 +493,20 @@ def main():
                                    f"(pressure loop + matrix-free PCG displacement solve, preconditioner: {head}" + (f" degree {args.cheb_degree}" if head == "chebyshev" else "") + " + strain projection); input.data material/BCs, z-face BCs per SURVEY Q9",
                        "parallelism": f"z-slab x{world}" if world > 1 else "single GPU", "operator": "matrix_free",
                        "stopping_rule_u": stop_txt},
-            "best_ms_per_step": tts[best]["ms_per_step"], "best_preconditioner": best,
             "cg_iterations_u": cg_u,
-            "roofline": roofline, "roofline_operator": roof_operator,
             "work_per_step": {k: work[k] / args.steps for k in work},
-            "kernel_only": {"seconds_by_family": {k: v[0] for k, v in kernel_time.items()}, "launches_by_family": {k: v[1] for k, v in kernel_time.items()}},
             "fss_iterations_per_step": [int(len(t)) for t in traces],
         }
-        out["time_to_solution"] = tts
+        if args.full:
+            roofline, roof_operator = rooflines(args, M, head, world)
+            out.update({"best_ms_per_step": tts[best]["ms_per_step"], "best_preconditioner": best, "roofline": roofline, "roofline_operator": roof_operator,
+                        "kernel_only": {"seconds_by_family": {k: v[0] for k, v in kernel_time.items()}, "launches_by_family": {k: v[1] for k, v in kernel_time.items()}},
+                        "time_to_solution": tts})
         if config5 is not None:
             out["config5"] = config5
         if weak is not None:
             out["weak_scaling_line"] = weak
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dim, deg, args.cpu_n, args.rel_tol, args.stop == "reduction", args.cpu_csr_n)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -22,7 +22,7 @@ def _line(out):
 
 
 def test_single_rank_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--cells", "8", "--cpu-n", "3", "--cpu-csr-n", "4", "--config5-steps", "6"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--cells", "8", "--cpu-n", "3", "--cpu-csr-n", "4", "--config5-steps", "6"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert KEYS <= set(d) and "cpu_baseline" in d
@@ -48,8 +48,34 @@ def test_single_rank_line():
     assert c5["steps"] == 6 and len(c5["cg_iterations_u"]) == 6 and min(c5["cg_iterations_u"]) > 0 and c5["seconds"] > 0 and c5["fss_iterations"] == [1] * 6
 
 
+def test_plain_run_measures_the_headline_alone(tmp_path):
+    """without --full: the headline steps and nothing else (no other preconditioners, config5, rooflines or CPU baseline); --dump-outputs writes the solution of the last
+    timed step, and two runs with the same arguments write the same solution"""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cells", "8", "--dump-outputs", str(tmp_path / f"run{k}")],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_line(r.stdout))
+    for d in lines:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+        assert d["steps"] == 2 and d["warmup"] == 1 and len(d["cg_iterations_u"]) == 2 and min(min(t) for t in d["cg_iterations_u"]) > 0
+        assert not {"roofline", "roofline_operator", "kernel_only", "time_to_solution", "best_ms_per_step", "config5", "cpu_baseline"} & set(d), sorted(d)
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert names == ["p.npy", "trace.npy", "u.npy", "volumetric_strain.npy"] and sorted(os.listdir(tmp_path / "run1")) == names
+    a = {f: np.load(tmp_path / "run0" / f) for f in names}
+    b = {f: np.load(tmp_path / "run1" / f) for f in names}
+    assert a["u.npy"].shape == (3 * 17 ** 3,) and a["p.npy"].shape == a["volumetric_strain.npy"].shape == (9 ** 3,)
+    assert all(v.dtype == np.float64 for v in a.values()) and np.linalg.norm(a["u.npy"]) > 0
+    assert int(a["trace.npy"][-1, 6]) == lines[0]["cg_iterations_u"][-1][-1]     # the trace of the last timed step
+    assert np.array_equal(a["trace.npy"][:, :3], b["trace.npy"][:, :3])
+    for f in ("u.npy", "p.npy", "volumetric_strain.npy"):
+        assert np.linalg.norm(a[f] - b[f]) <= 1e-10 * np.linalg.norm(a[f]), f
+
+
 def test_chebyshev_headline_reports_the_fused_kernel():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--cells", "8", "--prec", "chebyshev", "--no-variants", "--no-cpu-baseline", "--config5-steps", "0"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--cells", "8", "--prec", "chebyshev", "--no-variants", "--no-cpu-baseline", "--config5-steps", "0"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert d["roofline"]["bound"] == "hbm" and "cheb" in d["roofline"]["kernel"] and d["roofline_operator"]["avg_launch_us"] > 0 and "config5" not in d
@@ -57,7 +83,7 @@ def test_chebyshev_headline_reports_the_fused_kernel():
 
 def test_gpus_flag_without_a_launcher_starts_its_own_ranks():
     """the driver's N = 1 command is plain `python bench.py --gpus 1`; the same form with N > 1 must start N rank processes itself"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "0", "--cells", "8", "--no-weak-line", "--config5-steps", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "0", "--cells", "8", "--no-weak-line", "--config5-steps", "2"],
                        capture_output=True, text=True, timeout=600, env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _line(r.stdout)
@@ -84,7 +110,7 @@ def test_dead_steps_fail_the_run():
 
 def test_two_rank_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--cells", "8", "--share-gpu", "--config5-steps", "3"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--cells", "8", "--share-gpu", "--config5-steps", "3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert len(r.stdout.strip().splitlines()) == 1, r.stdout[:500]      # stdout carries the one JSON line and nothing else (gloo's connection messages go to stderr)

@@ -21,9 +21,9 @@ json.dump(d, open("$OUT/${TAG}_pmc_traffic.json", "w"), indent=1)
 PY
 cp $OUT/${TAG}_pmc_traffic.json $ROOT/profiles/${TAG}_pmc_traffic.json
 # the bench line as the driver runs it (no profiler attached: HIP-event timings are inflated by ~5 % under rocprofv3)
-python3 $ROOT/bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_stderr.log || exit 1
+python3 $ROOT/bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_stderr.log || exit 1
 # kernel statistics of the headline run alone, many steady steps so that the few early-exit launches of the first solves do not weigh on the averages
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$TAG -- python3 $ROOT/bench.py --no-variants --no-cpu-baseline --steps 20 --warmup 1 > $OUT/${TAG}_bench_line_profiled.json 2>> $OUT/${TAG}_bench_stderr.log || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$TAG -- python3 $ROOT/bench.py --full --no-variants --no-cpu-baseline --steps 20 --warmup 1 > $OUT/${TAG}_bench_line_profiled.json 2>> $OUT/${TAG}_bench_stderr.log || exit 1
 cp $(ls $OUT/stats_$TAG/*/*kernel_stats.csv | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 python3 - <<PY
 import csv, glob, json, statistics

@@ -3,7 +3,7 @@
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$ROOT/gpurun_out/config5_probe; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-variants --no-cpu-baseline --config5-steps 100 --no-kernel-events "$@" > $OUT/line.json 2> $OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
+rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-variants --no-cpu-baseline --config5-steps 100 --no-kernel-events "$@" > $OUT/line.json 2> $OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
 T=$(ls $OUT/ktrace/*/*kernel_trace.csv | head -1)
 python3 $ROOT/tools/gap_analysis.py $T 15 > $OUT/gaps.txt
 python3 - $T > $OUT/kernels_steady.txt <<PY
