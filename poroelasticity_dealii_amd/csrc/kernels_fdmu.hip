@@ -127,7 +127,8 @@ k_fdmu_pass(FdmuPass P, const TIn *__restrict__ in, TOut *__restrict__ out) {
       for (int t = 0; t < MTH; ++t) { const TC a = (mh * MTH + t < P.MT) ? Ap[((int64_t)t * P.KK + kk) * 64] : (TC)0; acc[t] = Mfma<TC>::run(a, b, acc[t]); }
     }
   };
-  // D fragment -> LDS: register q of a lane holds row (lane >> 4) + 4 q of the tile, column lane & 15
+  // D fragment -> LDS, column lane & 15; the row of register q differs by MFMA: (lane >> 4) + 4 q for v_mfma_f64_16x16x4_f64, 4 (lane >> 4) + q for
+  // v_mfma_f32_16x16x4_f32 (fp32 transforms)
   auto acc_to_lds = [&](bool scale) {
     double base = 0; bool lvalid = true;
     if (scale) {
@@ -144,7 +145,7 @@ k_fdmu_pass(FdmuPass P, const TIn *__restrict__ in, TOut *__restrict__ out) {
       if (mt >= P.MT) continue;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int m = mt * 16 + kq + 4 * q;
+        const int m = mt * 16 + (std::is_same<TC, double>::value ? kq + 4 * q : 4 * kq + q);
         double v = (double)acc[t][q];
         if (scale) v = (lvalid && m < P.nK) ? v / (base + P.kd[c] * P.lam_d[c][m]) : 0.0;   // padded / constrained modes carry lam = inf
         L[(nt * 16 + i16) * s_n + m * s_k] = (TC)v;
