@@ -192,6 +192,7 @@ struct poro_ctx {
   poro::DevBuf<double> cell_X, tables;
   poro::DevBuf<double> cell_geo;          // 3D meshes whose cells are all parallelepipeds: J^-1 (9, row-major [b][d] = d xi_b / d x_d) and det J per cell (kernels_mfg.hip)
   poro::FeTablesDev fe{};
+  int mfg_sf = 0;                            // poro_desc.fe holds the Gauss(k+1) / equidistant-Lagrange tables the sum-factorised general kernels hard-code (kernels_mfg.hip)
   std::vector<int64_t> color_off;            // host offsets into color_cells
   poro::DevBuf<uint8_t> dir_mask, node_mask; poro::DevBuf<double> dir_val; poro::DevBuf<int32_t> dir_dofs;
   std::vector<int32_t> h_dir_dof; std::vector<double> h_dir_val;
@@ -317,6 +318,7 @@ struct AsmArgs {
   const uint8_t *dir_mask; const double *dir_val;
   poro_material mat;
   int interleaved_u;   // dof = node * dim + component everywhere (lets K-asm-u look CSR positions up per node pair)
+  int mfg_sf;          // poro_ctx::mfg_sf: the sum-factorised general kernels may stand in for the table-driven one
 };
 void asm_u_matrix(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *val, double *lift);
 void asm_u_element_matrix(hipStream_t s, const AsmArgs &a, int32_t cell, double *Ke);
@@ -328,6 +330,7 @@ void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t
                   double *const *rhs /*host array of device ptrs*/);
 
 // ---- kernels_mfg.hip: matrix-free operator on general meshes (one wave per cell, coloured scatter) ----------------
+bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k);
 void mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode);
 // ---- kernels_mf.hip -----------------------------------------------------------------------------
 struct MfArgs { int dim, k_u; BoxDev box; const double *Ke; const uint8_t *mask; const double *diag_local; double lam, G; int mask_anywhere; const uint8_t *nodemask; const int32_t *dirichlet_dofs; int64_t n_dirichlet; };

@@ -3,6 +3,7 @@
 #include <rccl/rccl.h>
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -188,11 +189,36 @@ void setup(poro_ctx *c, const poro_desc *d) {
   push(f.q1_qp, (size_t)f.nq_p * f.ns_p); push(f.dq1_qp, (size_t)f.nq_p * f.ns_p * dim); push(f.u_qf, (size_t)nf * f.nq_f * f.ns_u); push(f.dq1_qf, (size_t)nf * f.nq_f * f.ns_p * dim);
   c->tables.upload(T);
   const double *tb = c->tables.p;
+  c->mfg_sf = mfg_sf_tables_match(f, c->dim, c->k_u) ? 1 : 0;
   c->fe = FeTablesDev{f.nq_u, f.nq_p, f.nq_f, f.ns_u, f.ns_p, tb + off[0], tb + off[1], tb + off[2], tb + off[3], tb + off[4], tb + off[5], tb + off[6], tb + off[7], tb + off[8], tb + off[9], tb + off[10], tb + off[11]};
 
   c->cell_dofs_u.upload(d->cell_dofs_u, c->n_cells * c->dpc_u); c->cell_dofs_p.upload(d->cell_dofs_p, c->n_cells * c->dpc_p);
   { std::vector<double> X((size_t)c->n_cells * c->nv * dim);
     for (int64_t i = 0; i < c->n_cells * c->nv; ++i) for (int k = 0; k < dim; ++k) X[i * dim + k] = d->vertex_coords[(int64_t)d->cell_vertices[i] * dim + k];
+    // MappingQ1 must be orientation preserving: det J > 0 at the 2^dim corners and at the u-quadrature points of every cell (deal.II refuses such cells as well,
+    // Triangulation::DistortedCellList).  A mirrored or tangled cell would otherwise give a negative- or in-definite operator without any error.
+    { const int nv = c->nv, nq = f.nq_u; std::atomic<int64_t> bad{c->n_cells};
+      auto det_at = [&](const double *x, const double *dN) {   // dN: [nv][dim] reference gradients of the Q1 shape functions
+        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        for (int v = 0; v < nv; ++v) for (int r = 0; r < dim; ++r) for (int b = 0; b < dim; ++b) J[r][b] += x[v * dim + r] * dN[v * dim + b];
+        return dim == 2 ? J[0][0] * J[1][1] - J[0][1] * J[1][0]
+                        : J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+      };
+      std::vector<double> dNc((size_t)nv * nv * dim);            // Q1 gradients at the corners: corner w, vertex v, direction g
+      for (int w = 0; w < nv; ++w) for (int v = 0; v < nv; ++v) for (int g = 0; g < dim; ++g) {
+        double t = 1;
+        for (int e = 0; e < dim; ++e) { const int bw = (w >> e) & 1, bv = (v >> e) & 1; t *= e == g ? (bv ? 1.0 : -1.0) : (bv == bw ? 1.0 : 0.0); }
+        dNc[((size_t)w * nv + v) * dim + g] = t;
+      }
+      parallel_for(c->n_cells, [&](int64_t b, int64_t e) {
+        for (int64_t cell = b; cell < e; ++cell) {
+          const double *x = X.data() + cell * nv * dim; bool ok = true;
+          for (int w = 0; w < nv && ok; ++w) ok = det_at(x, dNc.data() + (size_t)w * nv * dim) > 0;
+          for (int q = 0; q < nq && ok; ++q) ok = det_at(x, f.dq1_qu + (size_t)q * nv * dim) > 0;
+          if (!ok) { int64_t cur = bad.load(); while (cell < cur && !bad.compare_exchange_weak(cur, cell)) {} return; }
+        }
+      });
+      if (bad.load() < c->n_cells) throw Error("cell " + std::to_string(bad.load()) + " is inverted or degenerate: det J <= 0 at a vertex or quadrature point (MappingQ1 needs positively oriented cells)"); }
     c->cell_X.upload(X);
     // affine cells (graded / locally refined boxes, lattice-like Gmsh grids): MappingQ1's Jacobian is one matrix per cell - the sum-factorised operator kernel reads
     // its inverse instead of forming it from the eight vertices at every quadrature point

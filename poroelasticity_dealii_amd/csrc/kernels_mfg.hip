@@ -9,6 +9,7 @@
 // a plain read-modify-write: no atomics, bitwise reproducible.  Dirichlet columns are masked on load; the Dirichlet ROWS are left to the
 // caller (inert inside PCG; poro_apply_operator finishes them from the constraint list).
 #include "common.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
@@ -140,6 +141,7 @@ k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
   const bool live = p < NP && slot < n_cells;
   const int64_t cell = slot < n_cells ? cells[slot] : cells[0];
   const int i = p % N1, j = (p / N1) % N1, k = p / (N1 * N1);
+  const int ti = live ? i : 0, tj = live ? j : 0, tk = live ? k : 0;   // point of the 1D tables: dead lanes (N1 = 3: p = 27..31 has k = 3) stay inside them
   const double lam = a.mat.lame_lambda, G = a.mat.shear_G;
   int32_t dof[3] = {0, 0, 0}; bool dir[3] = {true, true, true};
   if (live) {
@@ -193,9 +195,9 @@ k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
       for (int b = 0; b < 3; ++b)
 #pragma unroll
         for (int d = 0; d < 3; ++d) Ji[b][d] = live ? sX[cs][3 * b + d] : 0.0;
-      det = sX[cs][9];
+      det = live ? sX[cs][9] : 0.0;
     } else {
-    const double lx[2] = {1.0 - T.xi[i], T.xi[i]}, ly[2] = {1.0 - T.xi[j], T.xi[j]}, lz[2] = {1.0 - T.xi[k], T.xi[k]}, dl[2] = {-1.0, 1.0};
+    const double lx[2] = {1.0 - T.xi[ti], T.xi[ti]}, ly[2] = {1.0 - T.xi[tj], T.xi[tj]}, lz[2] = {1.0 - T.xi[tk], T.xi[tk]}, dl[2] = {-1.0, 1.0};
     double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 #pragma unroll
     for (int v = 0; v < 8; ++v) {
@@ -210,7 +212,7 @@ k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
     Ji[1][0] = c01 * id; Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
     Ji[2][0] = c02 * id; Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
     }
-    const double jxw = det * T.w[i] * T.w[j] * T.w[k];
+    const double jxw = det * T.w[ti] * T.w[tj] * T.w[tk];
     double g[3][3], tr = 0;                               // g[c][d] = d u_c / d x_d
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -395,12 +397,47 @@ Sf1D sf_tables(int k) {
 
 }  // namespace
 
+// does the descriptor carry the tables sf_tables(k) implies (tensor-product Gauss(k+1) points, x fastest; lexicographic equidistant Lagrange nodes)?
+// Only then may the sum-factorised kernels stand in for k_mfg, which reads poro_desc.fe like the assembly kernels do.
+bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k) {
+  if ((k != 1 && k != 2) || (dim != 2 && dim != 3)) return false;
+  const int n1 = k + 1, nq = dim == 3 ? n1 * n1 * n1 : n1 * n1, ns = nq, nv = 1 << dim;
+  if (f.nq_u != nq || f.ns_u != ns || !f.w_qu || !f.u_qu || !f.du_qu || !f.dq1_qu) return false;
+  const Sf1D T = sf_tables(k);
+  const double tol = 1e-14;
+  auto off = [&](double have, double want) { return !(std::fabs(have - want) <= tol * std::max(1.0, std::fabs(want))); };
+  for (int q = 0; q < nq; ++q) {
+    const int qi[3] = {q % n1, (q / n1) % n1, q / (n1 * n1)};
+    double w = 1;
+    for (int d = 0; d < dim; ++d) w *= T.w[qi[d]];
+    if (off(f.w_qu[q], w)) return false;
+    for (int s = 0; s < ns; ++s) {
+      const int si[3] = {s % n1, (s / n1) % n1, s / (n1 * n1)};
+      double v = 1;
+      for (int d = 0; d < dim; ++d) v *= T.N[qi[d]][si[d]];
+      if (off(f.u_qu[(size_t)q * ns + s], v)) return false;
+      for (int g = 0; g < dim; ++g) {
+        double t = 1;
+        for (int d = 0; d < dim; ++d) t *= d == g ? T.D[qi[d]][si[d]] : T.N[qi[d]][si[d]];
+        if (off(f.du_qu[((size_t)q * ns + s) * dim + g], t)) return false;
+      }
+    }
+    for (int v = 0; v < nv; ++v)           // MappingQ1 at the same points (the in-kernel Jacobian of k_mfg3_sf<N, false> / k_mfg2_sf)
+      for (int g = 0; g < dim; ++g) {
+        double t = 1;
+        for (int d = 0; d < dim; ++d) { const double x = T.xi[qi[d]]; const int b = (v >> d) & 1; t *= d == g ? (b ? 1.0 : -1.0) : (b ? x : 1.0 - x); }
+        if (off(f.dq1_qu[((size_t)q * nv + v) * dim + g], t)) return false;
+      }
+  }
+  return true;
+}
+
 // y = A_u x (mode 0) or y = diag(A_u) (mode 1) over the colour classes; y is zeroed here
 void mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode) {
   if (a.fe.nq_u > kMaxNq || a.dpc_u > kMaxDpc) throw Error("mfg_apply: element too large");
   PORO_HIP(hipMemsetAsync(y, 0, n_u * sizeof(double), s));
   static const bool no_sf = std::getenv("PORO_MFG_NO_SUMFAC") != nullptr;
-  const bool sf = (a.dim == 3 || a.dim == 2) && mode == 0 && !no_sf && (a.k_u == 1 || a.k_u == 2);
+  const bool sf = (a.dim == 3 || a.dim == 2) && mode == 0 && !no_sf && (a.k_u == 1 || a.k_u == 2) && a.mfg_sf;
   const Sf1D T = sf ? sf_tables(a.k_u) : Sf1D{};
   for (size_t k = 0; k + 1 < color_off.size(); ++k) {
     const int64_t nc = color_off[k + 1] - color_off[k];
