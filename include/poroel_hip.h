@@ -106,7 +106,15 @@ typedef struct poro_tensor_grid {
 /* Optional coarse space for the two-level preconditioner of the displacement system (PORO_PREC_TWO_LEVEL): the mesh is a refinement of a uniform box - a locally
  * refined hyper_rectangle (refine_mesh, PoroelasticityFSS.h:447-498) - whose own description is `box_problem` (same material and boundary conditions, box tag
  * set; it must stay alive until poro_ctx_create has returned), and every displacement NODE i of this mesh (= dof / dim: the numbering must be node-interleaved)
- * interpolates the box's FE functions: v_h(node i) = sum_k weight[k] * v_H(node[k]), k in ptr[i] .. ptr[i+1].  One rank. */
+ * interpolates the box's FE functions: v_h(node i) = sum_k weight[k] * v_H(node[k]), k in ptr[i] .. ptr[i+1].
+ * One rank, or a GENERAL partition (poro_partition.n_neighbours > 0; refused on slab partitions).  On a general partition:
+ *   - box_problem is the whole, unpartitioned box, the same on every rank (the coarse solve runs replicated on each rank);
+ *   - ptr / node / weight hold one row per LOCAL node (owned, shared and ghost alike), ptr_p / node_p / weight_p one per local pressure dof; the rows of a dof that
+ *     several ranks hold must be identical (same entries, same order) on all of them;
+ *   - the displacement numbering must keep whole nodes: node-interleaved incl. the ghost dofs, n_dofs_u and n_owned_u multiples of dim (owned nodes first);
+ *   - every rank passes a coarse space or none.  The library cannot check this at poro_ctx_create (no communicator exists yet): a rank without one would not join the
+ *     all-reduce that every application of PORO_PREC_TWO_LEVEL performs (the owned rows' restriction P^T g, 8 * dim * box nodes bytes; 8 * box vertices for the scalar
+ *     systems).  The host provider's pieces (poro_host_partition_ex with the coarse flag) satisfy all of this. */
 struct poro_desc;
 typedef struct poro_coarse_space {
   int32_t enabled;

@@ -183,6 +183,8 @@ def load_host():
         L.poro_host_tie_boundary.argtypes = [C.c_void_p, C.c_int, _ip, _ip]
         L.poro_host_partition.restype = C.c_void_p
         L.poro_host_partition.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.poro_host_partition_ex.restype = C.c_void_p
+        L.poro_host_partition_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.poro_host_local_to_global.restype = C.c_int64
         L.poro_host_local_to_global.argtypes = [C.c_void_p, C.c_int, _ip]
         L.poro_host_desc.restype = C.POINTER(Desc)
@@ -282,11 +284,12 @@ class Problem:
             return cls(load_host().poro_host_build_gmsh_refined(path.encode(), degree_u, int(refine), *args, C.byref(material)))
         return cls(load_host().poro_host_build_gmsh(path.encode(), degree_u, *args, C.byref(material)))
 
-    def partition(self, rank, n_ranks):
+    def partition(self, rank, n_ranks, coarse=False):
         """piece `rank` of a general partition of this (global) problem: contiguous ranges of the cells in Morton order + interface lists
-        (poro_partition.n_neighbours > 0); .local_to_global_u / _p map the piece's dofs back"""
+        (poro_partition.n_neighbours > 0); .local_to_global_u / _p map the piece's dofs back.  coarse=True: the piece also carries the
+        coarse space of PREC_TWO_LEVEL (poro_desc.coarse: its own copy of the whole box problem + the global interpolation rows of its nodes)"""
         H = load_host()
-        h = H.poro_host_partition(self.handle, rank, n_ranks)
+        h = H.poro_host_partition_ex(self.handle, rank, n_ranks, 1 if coarse else 0)
         if not h:
             raise RuntimeError(H.poro_host_last_error().decode())
         P = type(self)(h)

@@ -167,6 +167,8 @@ struct Comm {
   // host-staged callbacks (tests)
   poro_allreduce_fn ar = nullptr; poro_sendrecv_fn sr = nullptr; void *user = nullptr;
   DevBuf<double> recv_lo, recv_hi; std::vector<double> hsend, hrecv;
+  // pinned host staging of vector all-reduces through the callbacks (allreduce_sum_vec), grown on demand
+  struct Pinned { double *p = nullptr; size_t n = 0; Pinned() = default; Pinned(const Pinned &) = delete; Pinned &operator=(const Pinned &) = delete; ~Pinned() { if (p) (void)hipHostFree(p); } } hvec;
   bool force_multi = false;
   bool multi() const { return part.n_ranks > 1 || force_multi; }
 };

@@ -48,10 +48,15 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       if (!desc->coarse.box_problem || !desc->coarse.ptr || !desc->coarse.node || !desc->coarse.weight) throw Error("poro_desc.coarse: box_problem / ptr / node / weight missing");
       if (!desc->coarse.box_problem->box.enabled || desc->coarse.box_problem->coarse.enabled) throw Error("poro_desc.coarse.box_problem must be a uniform box (box.enabled) without a coarse space of its own");
       if (desc->coarse.box_problem->dim != desc->dim || desc->coarse.box_problem->degree_u != desc->degree_u) throw Error("poro_desc.coarse.box_problem: dimension / degree differ");
-      if (!c->interleaved_u || c->comm.multi()) throw Error("poro_desc.coarse needs node-interleaved displacement dofs on one rank");
+      if (!c->interleaved_u) throw Error("poro_desc.coarse needs node-interleaved displacement dofs");
+      if (c->comm.part.n_ranks > 1 && !c->comm.general) throw Error("poro_desc.coarse on a slab partition: not supported (general partitions only, poro_partition.n_neighbours > 0)");
+      // general partition: the interpolation rows are per local node, the restriction runs over the owned nodes [0, n_owned_u / dim)
+      if (c->comm.general && (c->n_u % c->dim || c->comm.ifc_u.n_owned % c->dim))
+        throw Error("poro_desc.coarse on a general partition needs whole displacement nodes: n_dofs_u and n_owned_u must be multiples of dim (node-interleaved numbering incl. ghost dofs)");
       poro_ctx *box = nullptr;
       if (poro_ctx_create(desc->coarse.box_problem, device, PORO_OP_MATRIX_FREE, &box) != 0) throw Error(std::string("poro_desc.coarse.box_problem: ") + poro_last_error());
       PORO_HIP(hipStreamSynchronize(box->stream)); (void)hipStreamDestroy(box->stream); box->stream = c->stream; box->borrowed_stream = true;
+      box->comm.force_multi = false;      // the box is solved whole on every rank (replicated coarse solve): never the partitioned code path
       c->two_level.box = box;
       setup_two_level(c.get(), desc);
     }

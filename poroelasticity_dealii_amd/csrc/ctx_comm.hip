@@ -188,6 +188,23 @@ void allreduce_sum(poro_ctx *c, double *dev, int n) {
     PORO_HIP(hipMemcpyAsync(dev, h, n * sizeof(double), hipMemcpyHostToDevice, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
   } else throw Error("partitioned context without a communicator");
 }
+// all-reduce (sum) of a device vector of any length: RCCL on the device buffer itself, the callbacks through a pinned staging buffer (not the scalar slots above)
+void allreduce_sum_vec(poro_ctx *c, double *dev, int64_t n, const char *timer) {
+  Comm &cm = c->comm;
+  if (!cm.multi() || n <= 0) return;
+  Timed tm(c, timer);
+  if (cm.nccl_comm) PORO_NCCL(g_rccl.AllReduce(dev, dev, (size_t)n, ncclFloat64, ncclSum, (ncclComm_t)cm.nccl_comm, c->stream));
+  else if (cm.ar) {
+    if (n > INT32_MAX) throw Error("allreduce_sum_vec: more than 2^31 - 1 entries for the callback communicator");
+    if (cm.hvec.n < (size_t)n) {
+      if (cm.hvec.p) { PORO_HIP(hipHostFree(cm.hvec.p)); cm.hvec.p = nullptr; cm.hvec.n = 0; }
+      void *p = nullptr; PORO_HIP(hipHostMalloc(&p, (size_t)n * sizeof(double), hipHostMallocDefault)); cm.hvec.p = static_cast<double *>(p); cm.hvec.n = (size_t)n;
+    }
+    PORO_HIP(hipMemcpyAsync(cm.hvec.p, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
+    cm.ar(cm.hvec.p, (int32_t)n, cm.user);
+    PORO_HIP(hipMemcpyAsync(dev, cm.hvec.p, n * sizeof(double), hipMemcpyHostToDevice, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
+  } else throw Error("partitioned context without a communicator");
+}
 int64_t owned(poro_ctx *c, int64_t n, int64_t plane) {
   if (c->comm.general) return n == c->n_u ? c->comm.ifc_u.n_owned : c->comm.ifc_p.n_owned;
   return (c->comm.multi() && c->comm.part.has_upper) ? n - plane : n;

@@ -52,7 +52,8 @@ void post_and_wait(poro_ctx *c, const double *dev_src, int n, const PcgScalars *
 void setup_general_partition(poro_ctx *c, const poro_desc *d);
 void exchange_planes(poro_ctx *c, const double *send_lo, const double *send_hi, int64_t plane);
 void exchange_add(poro_ctx *c, double *v, int64_t n, int64_t plane);
-void allreduce_sum(poro_ctx *c, double *dev, int n);
+void allreduce_sum(poro_ctx *c, double *dev, int n);                                          // a few scalars (at most kScalarSlots)
+void allreduce_sum_vec(poro_ctx *c, double *dev, int64_t n, const char *timer);              // a vector of any length, timed under `timer`
 int64_t owned(poro_ctx *c, int64_t n, int64_t plane);
 AsmArgs asm_args(poro_ctx *c);
 MfArgs mf_args(poro_ctx *c);

@@ -328,30 +328,38 @@ void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgS
   fdmo_slab_pass(s, O, 3, S.buf.p, z, gate);                                          // y, x backward, reading the received planes in place
 }
 // ---- additive two-level preconditioner on refinements of a uniform box (poro_desc.coarse) ----------------------------------------------------
-static void upload_interp(poro_ctx::Interp &T, int64_t n_fine, int64_t n_coarse, const int64_t *ptr, const int32_t *node, const double *weight, const char *what) {
+// P holds every local row (prolongation / combination); its transpose (restriction) only the owned rows [0, n_owned), so that the pieces of a general partition
+// sum every global row exactly once (one rank: n_owned = n_fine)
+// row_bound > 0 (general partitions): the lanes of P follow from the longest possible row instead of the piece's mean row length.  The lane count fixes the order in
+// which a row is summed, and the copies of a shared dof must come out bitwise equal on every rank that holds it
+static void upload_interp(poro_ctx::Interp &T, int64_t n_fine, int64_t n_owned, int64_t n_coarse, const int64_t *ptr, const int32_t *node, const double *weight, const char *what,
+                          int row_bound = 0) {
   T.n_fine = n_fine; T.n_coarse = n_coarse;
-  const int64_t nnz = ptr[n_fine];
+  const int64_t nnz = ptr[n_fine], nnz_t = ptr[n_owned];
   const auto lanes_for = [](int64_t nnz, int64_t rows) { return nnz >= 6 * rows ? 8 : nnz >= 3 * rows ? 4 : 1; };   // mean row length -> lanes per row
-  T.lanes = lanes_for(nnz, n_fine); T.lanes_t = lanes_for(nnz, n_coarse);
+  T.lanes = row_bound > 0 ? lanes_for(row_bound, 1) : lanes_for(nnz, n_fine); T.lanes_t = lanes_for(nnz_t, n_coarse);
+  for (int64_t k = 0; k < nnz; ++k) { const int32_t j = node[k]; if (j < 0 || j >= n_coarse) throw Error(std::string("poro_desc.coarse: ") + what + " node out of range"); }
   std::vector<int64_t> tp((size_t)n_coarse + 1, 0);
-  for (int64_t k = 0; k < nnz; ++k) { const int32_t j = node[k]; if (j < 0 || j >= n_coarse) throw Error(std::string("poro_desc.coarse: ") + what + " node out of range"); tp[j + 1]++; }
+  for (int64_t k = 0; k < nnz_t; ++k) tp[node[k] + 1]++;
   { int64_t longest = 0; for (int64_t j = 0; j < n_coarse; ++j) longest = std::max(longest, tp[j + 1]);      // restriction: a few very long rows (refined block) beside single-entry ones
     if (longest >= 48) T.lanes_t = std::max(T.lanes_t, 16); }                     // (measured on the refined 32^3 box and the Gmsh grid: 16 lanes 3 % ahead of 8, 32 lanes behind both)
   for (int64_t j = 0; j < n_coarse; ++j) tp[j + 1] += tp[j];
-  std::vector<int32_t> tc((size_t)nnz); std::vector<double> tw((size_t)nnz); std::vector<int64_t> pos(tp.begin(), tp.end() - 1);
+  std::vector<int32_t> tc((size_t)nnz_t); std::vector<double> tw((size_t)nnz_t); std::vector<int64_t> pos(tp.begin(), tp.end() - 1);
   for (int64_t i = 0; i < n_fine; ++i) {
     if (ptr[i + 1] < ptr[i]) throw Error("poro_desc.coarse: ptr not monotone");
-    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) { const int64_t at = pos[node[k]]++; tc[at] = (int32_t)i; tw[at] = weight[k]; }
+    if (i < n_owned) for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) { const int64_t at = pos[node[k]]++; tc[at] = (int32_t)i; tw[at] = weight[k]; }
   }
   T.p_ptr.upload(ptr, (size_t)n_fine + 1); T.p_col.upload(node, (size_t)nnz); T.p_w.upload(weight, (size_t)nnz);
   T.pt_ptr.upload(tp); T.pt_col.upload(tc); T.pt_w.upload(tw);
 }
 void setup_two_level(poro_ctx *c, const poro_desc *d) {
   auto &T = c->two_level; const int dim = c->dim;
-  upload_interp(T, c->n_u / dim, T.box->n_u / dim, d->coarse.ptr, d->coarse.node, d->coarse.weight, "displacement");
+  const bool general = c->comm.general;      // (rows of P interpolate the box's FE functions of one cell: at most (k + 1)^dim entries)
+  upload_interp(T, c->n_u / dim, general ? c->comm.ifc_u.n_owned / dim : c->n_u / dim, T.box->n_u / dim, d->coarse.ptr, d->coarse.node, d->coarse.weight, "displacement",
+                general ? ipow(c->k_u + 1, dim) : 0);
   if (d->coarse.ptr_p) {
     if (!d->coarse.node_p || !d->coarse.weight_p) throw Error("poro_desc.coarse: node_p / weight_p missing");
-    upload_interp(T.pressure, c->n_p, T.box->n_p, d->coarse.ptr_p, d->coarse.node_p, d->coarse.weight_p, "pressure");
+    upload_interp(T.pressure, c->n_p, general ? c->comm.ifc_p.n_owned : c->n_p, T.box->n_p, d->coarse.ptr_p, d->coarse.node_p, d->coarse.weight_p, "pressure", general ? 1 << dim : 0);
   }
 }
 bool two_level_supported(poro_ctx *c) {
@@ -368,6 +376,7 @@ void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double 
   if (!H->wz_p.p) H->wz_p.alloc(H->n_p);
   double *rc = H->wg_p.p, *zc = H->wz_p.p;
   la_nodal_interp(s, T.pt_ptr.p, T.pt_col.p, T.pt_w.p, T.n_coarse, 1, g, rc, T.lanes_t);
+  if (c->comm.multi()) allreduce_sum_vec(c, rc, T.n_coarse, "two_level_coarse_allreduce");      // partitioned: every rank restricted its owned rows; all hold P^T g after the sum
   const double kk[3] = {kappa, kappa, kappa};
   fdm_precondition_p(H, a, kk, rc, zc);
   la_two_level_combine(s, T.p_ptr.p, T.p_col.p, T.p_w.p, T.n_fine, 1, zc, g, dinv, (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr, omega, z, T.lanes);
@@ -378,6 +387,9 @@ void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double om
   build_fdm_u(H);
   double *rc = H->wg_u.p, *zc = H->wz_u.p;                                  // the box context's work vectors (it never solves anything itself)
   la_nodal_interp(s, T.pt_ptr.p, T.pt_col.p, T.pt_w.p, T.n_coarse, dim, g, rc, T.lanes_t);              // r_H = P^T g
+  // partitioned (general pieces): the owned rows' partial restriction, summed over the ranks.  The coarse solve then runs replicated on identical data and the
+  // combination below covers every local row, so the copies of a shared dof stay bitwise equal.  One all-reduce per application on every rank alike
+  if (c->comm.multi()) allreduce_sum_vec(c, rc, T.n_coarse * dim, "two_level_coarse_allreduce");
   FdmOct &O = H->fdm_oct;
   if (O.built) { fdmo_from_nodal(s, O, rc, O.g.p); if (O.planar) fdmo_apply_planar(s, O, O.g.p, O.z.p); else fdmo_apply(s, O, O.g.p, O.z.p, O.t.p); fdmo_to_nodal(s, O, O.z.p, zc); }
   else fdm_precondition_u(H, rc, zc);                                         // z_H = blockdiag(A_H)^-1 r_H (zero on the box's Dirichlet faces)

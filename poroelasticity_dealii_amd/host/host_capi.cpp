@@ -99,6 +99,12 @@ void *poro_host_partition(void *global, int rank, int n_ranks) {
   try { auto *L = new ProblemData(); try { partition_problem(*static_cast<ProblemData *>(global), rank, n_ranks, *L); } catch (...) { delete L; throw; } return L; }
   catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+// the same with options.  flags bit 0: the piece carries the coarse space of the two-level preconditioner (its own copy of the global box problem + the global
+// interpolation rows of its nodes; displacement ghosts and owners per node).  Refused when the global problem has no coarse space
+void *poro_host_partition_ex(void *global, int rank, int n_ranks, int flags) {
+  try { auto *L = new ProblemData(); try { partition_problem(*static_cast<ProblemData *>(global), rank, n_ranks, *L, (flags & 1) != 0); } catch (...) { delete L; throw; } return L; }
+  catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
 // local -> global dof map of a piece (space 0: displacement, 1: pressure); returns the length, copies when out != NULL
 int64_t poro_host_local_to_global(void *h, int space, int32_t *out) {
   auto &v = space == 0 ? static_cast<ProblemData *>(h)->local_to_global_u : static_cast<ProblemData *>(h)->local_to_global_p;

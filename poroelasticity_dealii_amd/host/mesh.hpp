@@ -410,6 +410,7 @@ struct ProblemData {
   // locally refined boxes: the underlying uniform box as a problem of its own + the interpolation from it (poro_coarse_space)
   std::unique_ptr<ProblemData> coarse; std::vector<int64_t> prol_ptr; std::vector<int32_t> prol_node; std::vector<double> prol_w;
   std::vector<int64_t> prol_ptr_p; std::vector<int32_t> prol_node_p; std::vector<double> prol_w_p;
+  int64_t n_dofs_p_global = 0;        // pieces of a general partition: the global problem's pressure dof count (0: this problem is not a piece)
   poro_desc d{};
 
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are
@@ -658,10 +659,23 @@ inline std::vector<int64_t> morton_cell_order(const Mesh &m) {
   return order;
 }
 
-inline void partition_problem(const ProblemData &G, int rank, int n_ranks, ProblemData &L) {
+// A copy of the uniform box problem behind a coarse space that owns its storage (finalize() points the copy's descriptor at the copy's arrays).
+inline void copy_box_problem(const ProblemData &S, ProblemData &D) {
+  D.mesh = S.mesh; D.dofs = S.dofs; D.bc = S.bc; D.mat = S.mat; D.part = S.part;
+  D.dirichlet_dof = S.dirichlet_dof; D.dirichlet_value = S.dirichlet_value; D.dirichlet_dof_p = S.dirichlet_dof_p; D.dirichlet_value_p = S.dirichlet_value_p;
+  D.cons_u = S.cons_u; D.cons_p = S.cons_p; D.dirichlet_given = true; D.ties_added = true;
+  D.finalize(S.dofs.k_u, true);
+}
+
+// with_coarse: the piece also carries the coarse space of the two-level preconditioner (poro_desc.coarse on a general partition): its own copy of the global box
+// problem, and for every local displacement node / pressure dof the interpolation row of its global counterpart (same entries, same order).  Ghosting and ownership then
+// work per displacement NODE, so all components of a node share one owner and the local numbering stays node-interleaved (a closed constraint list drops Dirichlet
+// components from the masters, so per-dof ghosting can split a master node's components between owners)
+inline void partition_problem(const ProblemData &G, int rank, int n_ranks, ProblemData &L, bool with_coarse = false) {
   if (n_ranks < 1 || rank < 0 || rank >= n_ranks) throw std::runtime_error("partition_problem: bad rank / n_ranks");
   if (G.part.n_ranks > 1) throw std::runtime_error("partition_problem: the problem is already a piece of a partition");
   if (!G.dirichlet_dof_p.empty()) throw std::runtime_error("partition_problem: prescribed pressures are implemented for one rank");
+  if (with_coarse && !(G.coarse && G.d.coarse.enabled)) throw std::runtime_error("partition_problem: coarse space requested, but the problem has none (poro_desc.coarse: locally refined boxes and Gmsh grids with an auxiliary box)");
   const Mesh &gm = G.mesh; const int dim = gm.dim, nv = 1 << dim, k_u = G.dofs.k_u, dpc = ipow(k_u + 1, dim) * dim; const int64_t nc = gm.n_cells();
   if (nc < n_ranks) throw std::runtime_error("partition_problem: fewer cells than ranks");
   const std::vector<int64_t> order = morton_cell_order(gm);
@@ -678,12 +692,14 @@ inline void partition_problem(const ProblemData &G, int rank, int n_ranks, Probl
   // constraint lists (hanging nodes, ties; closed): a rank that holds a constrained dof must hold all of its masters, or it could neither expand x nor fold the row.  Masters that
   // none of the rank's cells touch become GHOST dofs of the piece: local, shared with the ranks that do touch them (so the interface exchange keeps their values and row sums
   // consistent), part of no local cell.  Each rank then condenses with its own complete slice of the list; partial rows are folded BEFORE the interface sums (the library's order)
-  auto add_ghost_masters = [&](std::vector<std::vector<int32_t>> &t, const ConstraintList &cl) {
-    for (int64_t i = 0; i < cl.n(); ++i) for (int32_t r : std::vector<int32_t>(t[cl.dof[i]])) for (int64_t k = cl.ptr[i]; k < cl.ptr[i + 1]; ++k) {
-      auto &v = t[cl.master[k]]; auto it = std::lower_bound(v.begin(), v.end(), r); if (it == v.end() || *it != r) v.insert(it, r);
-    }
+  // (node_dofs > 1: every component of a master's node follows it)
+  auto add_ghost_masters = [&](std::vector<std::vector<int32_t>> &t, const ConstraintList &cl, int node_dofs) {
+    for (int64_t i = 0; i < cl.n(); ++i) for (int32_t r : std::vector<int32_t>(t[cl.dof[i]])) for (int64_t k = cl.ptr[i]; k < cl.ptr[i + 1]; ++k)
+      for (int32_t m = cl.master[k] / node_dofs * node_dofs, e = m + node_dofs; m < e; ++m) {
+        auto &v = t[m]; auto it = std::lower_bound(v.begin(), v.end(), r); if (it == v.end() || *it != r) v.insert(it, r);
+      }
   };
-  add_ghost_masters(tu, G.cons_u); add_ghost_masters(tp, G.cons_p);
+  add_ghost_masters(tu, G.cons_u, with_coarse ? dim : 1); add_ghost_masters(tp, G.cons_p, 1);
   auto has = [&](const std::vector<int32_t> &v) { return std::binary_search(v.begin(), v.end(), (int32_t)rank); };
   // local numbering: owned first, each group ascending in the global index
   auto number = [&](const std::vector<std::vector<int32_t>> &t, std::vector<int32_t> &l2g, std::vector<int32_t> &g2l, int64_t &n_owned) {
@@ -694,6 +710,12 @@ inline void partition_problem(const ProblemData &G, int rank, int n_ranks, Probl
   };
   std::vector<int32_t> g2l_u, g2l_p; int64_t own_u = 0, own_p = 0;
   number(tu, L.local_to_global_u, g2l_u, own_u); number(tp, L.local_to_global_p, g2l_p, own_p);
+  if (with_coarse) {      // per-node ghosting keeps the components of a node together: owned nodes first, every local node = dim consecutive dofs of one global node
+    const auto &l2g = L.local_to_global_u;
+    bool ok = own_u % dim == 0 && l2g.size() % dim == 0;
+    for (size_t i = 0; i < l2g.size() && ok; i += dim) for (int c = 0; c < dim; ++c) ok = ok && l2g[i] % dim == 0 && l2g[i + c] == l2g[i] + c;
+    if (!ok) throw std::runtime_error("partition_problem: the piece's displacement numbering is not node-interleaved (internal error)");
+  }
   // interface lists: for every other rank q the dofs both touch, ascending global index
   std::map<int32_t, std::vector<int32_t>> su, sp;
   for (size_t g = 0; g < tu.size(); ++g) if (has(tu[g])) for (int32_t q : tu[g]) if (q != rank) su[q].push_back(g2l_u[g]);
@@ -740,7 +762,29 @@ inline void partition_problem(const ProblemData &G, int rank, int n_ranks, Probl
   localise(G.cons_u, g2l_u, L.cons_u); localise(G.cons_p, g2l_p, L.cons_p);
   L.ties_added = true;
   L.part = poro_partition{}; L.part.rank = rank; L.part.n_ranks = n_ranks; L.part.n_owned_u = own_u; L.part.n_owned_p = own_p;
+  L.n_dofs_p_global = G.dofs.n_p;
+  L.coarse.reset(); L.prol_ptr.clear(); L.prol_node.clear(); L.prol_w.clear(); L.prol_ptr_p.clear(); L.prol_node_p.clear(); L.prol_w_p.clear();
+  if (with_coarse) {
+    // the whole box on every piece + the global interpolation rows of the local nodes / vertices
+    L.coarse.reset(new ProblemData()); copy_box_problem(*G.coarse, *L.coarse);
+    auto rows = [](const std::vector<int32_t> &l2g, int stride, const std::vector<int64_t> &gp, const std::vector<int32_t> &gn, const std::vector<double> &gw,
+                   std::vector<int64_t> &p, std::vector<int32_t> &nd, std::vector<double> &w) {
+      p.assign(1, 0);
+      for (size_t i = 0; i < l2g.size(); i += stride) {
+        const int64_t g = l2g[i] / stride;
+        nd.insert(nd.end(), gn.begin() + gp[g], gn.begin() + gp[g + 1]); w.insert(w.end(), gw.begin() + gp[g], gw.begin() + gp[g + 1]);
+        p.push_back((int64_t)nd.size());
+      }
+    };
+    rows(L.local_to_global_u, dim, G.prol_ptr, G.prol_node, G.prol_w, L.prol_ptr, L.prol_node, L.prol_w);
+    if (G.d.coarse.ptr_p) rows(L.local_to_global_p, 1, G.prol_ptr_p, G.prol_node_p, G.prol_w_p, L.prol_ptr_p, L.prol_node_p, L.prol_w_p);
+  }
   L.finalize(k_u, true);
+  if (with_coarse) {
+    L.d.coarse = poro_coarse_space{}; L.d.coarse.enabled = 1; L.d.coarse.box_problem = &L.coarse->d;
+    L.d.coarse.ptr = L.prol_ptr.data(); L.d.coarse.node = L.prol_node.data(); L.d.coarse.weight = L.prol_w.data();
+    if (!L.prol_ptr_p.empty()) { L.d.coarse.ptr_p = L.prol_ptr_p.data(); L.d.coarse.node_p = L.prol_node_p.data(); L.d.coarse.weight_p = L.prol_w_p.data(); }
+  }
 }
 
 }  // namespace poro_host
