@@ -22,6 +22,505 @@ template <class F> int guarded(F &&f) {
   catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// ---- pieces of poro_disp_assemble_system ------------------------------------------------------------------------------------------------
+// fn(cells, n_cells) once per colour of the cell colouring (one launch each: the cells of a colour share no dof)
+template <class F> void for_each_colour(poro_ctx *c, F &&fn) {
+  for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
+    fn(c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k]);
+}
+
+// lifting -(A_full g) on the free rows, from wh_u = A_full g (the unconstrained operator applied to the Dirichlet values)
+void lifting_from_wh(poro_ctx *c) {
+  la_fill(c->stream, c->lift_u.p, 0.0, c->n_u);
+  la_axpy(c->stream, c->lift_u.p, -1.0, c->wh_u.p, c->n_u);
+}
+
+// throws unless max |a - b| <= rel_tol max |b|; a is overwritten with a - b
+void throw_unless_close(poro_ctx *c, double *a, const double *b, int64_t n, double rel_tol, const char *what) {
+  hipStream_t s = c->stream;
+  la_axpy(s, a, -1.0, b, n);
+  la_norm_partials(s, a, n, c->partials.p, c->partials.p + kMaxPartials);
+  la_norm_partials(s, b, n, c->partials.p + 2 * kMaxPartials, c->partials.p + 3 * kMaxPartials);
+  la_reduce_finish(s, c->partials.p, 4, c->red.p, 2 | 8);
+  double h[4];
+  PORO_HIP(hipMemcpyAsync(h, c->red.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  PORO_HIP(hipStreamSynchronize(s));
+  if (!(h[1] <= rel_tol * h[3])) throw Error(std::string(what) + ": max diff " + std::to_string(h[1]) + " vs max " + std::to_string(h[3]));
+}
+
+// self-check of the structured CSR assembly (kernels_box.hip) against the coloured per-cell assembly
+void check_box_assembly(poro_ctx *c, const AsmArgs &a) {
+  hipStream_t s = c->stream;
+  DevBuf<double> ref, lift_ref;
+  ref.alloc(c->Au.nnz);
+  ref.zero(s);
+  lift_ref.alloc(c->n_u);
+  lift_ref.zero(s);
+  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_matrix(s, a, cells, n_cells, c->Au.rp.p, c->Au.col.p, ref.p, lift_ref.p); });
+  throw_unless_close(c, ref.p, c->Au_val.p, c->Au.nnz, 1e-12, "structured CSR assembly disagrees with the per-cell assembly");
+}
+
+// self-check of the sum-factorised operator against the element-matrix gather on a synthetic vector (guards the FE-table / numbering
+// assumptions of the structured path); both unconstrained
+void check_sum_factorised_operator(poro_ctx *c) {
+  hipStream_t s = c->stream;
+  std::vector<double> hx(c->n_u);
+  for (int64_t i = 0; i < c->n_u; ++i) hx[i] = std::sin(0.37 * (double)i);
+  DevBuf<double> tx, t1, t2;
+  tx.upload(hx);
+  t1.alloc(c->n_u);
+  t2.alloc(c->n_u);
+  kron_apply(s, mf_args(c), tx.p, t1.p, false, c->n_cus);
+  mf_apply(s, mf_args(c), tx.p, t2.p, false);
+  throw_unless_close(c, t1.p, t2.p, c->n_u, 1e-11, "sum-factorised operator disagrees with the element-matrix operator");
+}
+
+// dictionary form of the Jacobi diagonal: on a uniform box only a few dozen distinct per-node triples exist, so the PCG kernels
+// can read one class byte per node and a tiny table instead of 8 bytes per dof.  Built by de-duplicating the actual values of dinv_u;
+// with more than 255 classes there is no dictionary
+void build_diag_dictionary(poro_ctx *c) {
+  std::vector<double> hd(c->n_u);
+  PORO_HIP(hipMemcpyAsync(hd.data(), c->dinv_u.p, c->n_u * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PORO_HIP(hipStreamSynchronize(c->stream));
+  const int nc = c->dim;
+  const int64_t nnode = c->n_u / nc;
+  struct KeyHash {
+    size_t operator()(const std::array<double, 3> &k) const {
+      uint64_t h = 1469598103934665603ull;
+      for (double v : k) {
+        uint64_t b;
+        std::memcpy(&b, &v, 8);
+        h = (h ^ b) * 1099511628211ull;
+        h ^= h >> 29;
+      }
+      return (size_t)h;
+    }
+  };
+  std::unordered_map<std::array<double, 3>, int, KeyHash> dict;
+  std::vector<uint8_t> cls(nnode);
+  std::vector<double> tab;
+  for (int64_t nd = 0; nd < nnode; ++nd) {
+    std::array<double, 3> key{0, 0, 0};
+    for (int k = 0; k < nc; ++k) key[k] = hd[nd * nc + k];
+    auto it = dict.find(key);
+    if (it == dict.end()) {
+      if (dict.size() >= 255) return;
+      it = dict.emplace(key, (int)dict.size()).first;
+      for (int k = 0; k < nc; ++k) tab.push_back(key[k]);
+    }
+    cls[nd] = (uint8_t)it->second;
+  }
+  c->diag_u_cls.upload(cls);
+  c->diag_u_tab.upload(tab);
+}
+
+// ---- displacement solves: one function per preconditioner family ---------------------------------------------------------------------------
+// the operator of the displacement system, condensed on the fly where the mesh has constraint lists; apply(x, y, dot_partials) as apply_A_u
+ApplyFn operator_u(poro_ctx *c) {
+  return [c](const double *x, double *y, double *dp) {
+    const int mode = c->operator_mode;
+    if (!c->cons_u.n) return apply_A_u(c, x, y, mode, dp, false, dp ? c->scal.p : nullptr);
+    // C^T A C: the search direction's hanging entries follow their masters, the product's hanging rows fold into the masters' rows
+    la_cons_expand(c->stream, c->cons_u, const_cast<double *>(x), false);
+    apply_A_u(c, x, y, mode, nullptr, false, nullptr, false);                 // the rank's partial product ...
+    la_cons_reduce(c->stream, c->cons_u, y);                                   // ... folded ...
+    exchange_add(c, y, c->n_u, c->comm.part.plane_u);                          // ... then summed over the interface
+    return false;
+  };
+}
+
+// constraints.distribute (:306) on the solution: the Dirichlet values and, with `expand`, the hanging entries from their masters
+void finish_u(poro_ctx *c, bool expand) {
+  la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
+  if (expand) la_cons_expand(c->stream, c->cons_u, vec(c, PORO_VEC_U), true);
+}
+
+// the Jacobi diagonal of the displacement system; `dictionary`: in its class / table form where one was built
+DiagVec diag_u(poro_ctx *c, const uint8_t *inert, bool dictionary) {
+  DiagVec dv;
+  dv.full = c->dinv_u.p;
+  dv.ncomp = c->dim;
+  dv.inert = inert;
+  if (dictionary && c->diag_u_cls.p) {
+    dv.cls = c->diag_u_cls.p;
+    dv.tab = c->diag_u_tab.p;
+  }
+  return dv;
+}
+
+// lambda_max(D^-1 A): on a uniform box all cells share one element matrix and lambda_max <= lambda_max(diag(K_e)^-1 K_e) holds rigorously
+// (x^T A x = sum_e x_e^T K_e x_e <= mu sum_e x_e^T diag(K_e) x_e = mu x^T D x) but is loose (3.8 against 2.5 for Q2 hexahedra), so the working
+// value is the Lanczos estimate (+5 %) capped by it.  Cached in c->cheb_lmax until the matrix is rebuilt
+double chebyshev_lmax(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj) {
+  if (c->cheb_lmax > 0) return c->cheb_lmax;
+  const bool have_bound = c->box.enabled && c->Ke.p && !c->cons_u.n;
+  if (have_bound) {
+    std::vector<double> ke((size_t)c->dpc_u * c->dpc_u);
+    PORO_HIP(hipMemcpyAsync(ke.data(), c->Ke.p, ke.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    const double bound = jacobi_scaled_lambda_max(c->dpc_u, ke);              // rigorous but loose
+    c->cheb_lmax = std::min(bound, estimate_lmax_u(c, apply, dj));
+  } else {
+    c->cheb_lmax = estimate_lmax_u(c, apply, dj);
+  }
+  if (std::getenv("PORO_CHEB_VERBOSE")) std::fprintf(stderr, "[poro] lambda_max(D^-1 A_u) ~ %.6f\n", c->cheb_lmax);
+  return c->cheb_lmax;
+}
+
+// default interval ratio: a few times lambda_min, which scales with h^2 (calibrated on box runs of 8^3 .. 72^3 cells).  Cached in c->cheb_ratio_default
+double chebyshev_default_ratio(poro_ctx *c) {
+  if (c->cheb_ratio_default > 0) return c->cheb_ratio_default;
+  // from GLOBAL mesh sizes, so that every rank of a partitioned run builds the same polynomial (rank-local sizes gave uneven slabs different roots on
+  // either side of a shared plane): the cell layers of the partitioned direction (slabs) / the cell count (general partitions) are summed over the ranks
+  double h[2] = {(double)c->box.n[c->dim - 1], (double)c->n_cells};
+  if (c->comm.multi()) {
+    PORO_HIP(hipMemcpyAsync(c->red.p, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    allreduce_sum(c, c->red.p, 2);
+    PORO_HIP(hipMemcpyAsync(h, c->red.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PORO_HIP(hipStreamSynchronize(c->stream));
+  }
+  double nmax = 1;
+  if (c->box.enabled) {
+    for (int k = 0; k < c->dim; ++k) nmax = std::max(nmax, k == c->dim - 1 ? h[0] : (double)c->box.n[k]);
+  } else {
+    nmax = std::round(std::pow(h[1], 1.0 / c->dim));
+  }
+  c->cheb_ratio_default = std::min(400.0, std::max(10.0, (c->k_u == 2 ? 0.2 : 0.05) * nmax * nmax));
+  return c->cheb_ratio_default;
+}
+
+// The polynomial of the Chebyshev preconditioner z = q(D^-1 A) D^-1 g: q of degree m for the interval [lmax / ratio, lmax].
+// Only EVEN degrees are used: should an eigenvalue still exceed the assumed bound, it meets T_{m+1} outside [-1, 1], and q(lambda) lambda stays
+// positive (the preconditioner SPD) exactly when m + 1 is odd.
+// Root form: the residual polynomial of degree m + 1 is prod_i (1 - lambda / r_i) with the roots r_i of the Chebyshev polynomial shifted to
+// [lmax / ratio, lmax]; z_1 = D^-1 g / r_0, z_{j+1} = z_j + D^-1 (g - A z_j) / r_j.  Same polynomial as the three-term recurrence
+// (identical CG iteration counts in the prototype for every ordering at these degrees) with ONE extra stream per step (g) instead of two;
+// the roots are taken alternately from both ends so that no run of small roots inflates the intermediate iterates
+struct ChebPlan { int m; double lmax, ratio; std::vector<double> roots; };
+ChebPlan chebyshev_plan(poro_ctx *c, const poro_solver_opts *opts, const ApplyFn &apply, const DiagVec &dj) {
+  ChebPlan p;
+  p.m = opts->poly_degree > 0 ? opts->poly_degree : 6;
+  if (p.m & 1) ++p.m;
+  p.lmax = chebyshev_lmax(c, apply, dj);
+  // `omega` doubles as the interval ratio; anything below 4 (the SSOR relaxation 1.2 a caller may have left there, 0) means "default"
+  p.ratio = opts->omega >= 4.0 ? opts->omega : chebyshev_default_ratio(c);
+  const double lmin = p.lmax / p.ratio, theta = 0.5 * (p.lmax + lmin), delta = 0.5 * (p.lmax - lmin);
+  const int m = p.m;
+  std::vector<double> r(m + 1);
+  for (int i = 0; i <= m; ++i) r[i] = theta - delta * std::cos(3.14159265358979323846 * (2 * i + 1) / (2.0 * (m + 1)));
+  int lo = 0, hi = m;
+  while (lo <= hi) {
+    p.roots.push_back(r[hi--]);
+    if (lo <= hi) p.roots.push_back(r[lo++]);
+  }
+  return p;
+}
+
+// m operator applications without dot products; on 3D boxes (one rank) the recurrence runs inside the structured operator kernel
+int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+  hipStream_t s = c->stream;
+  const DiagVec dj = diag_u(c, c->cons_u.inert.p, true);
+  const ChebPlan plan = chebyshev_plan(c, opts, apply, dj);
+  const int m = plan.m;
+  const std::vector<double> &roots = plan.roots;
+  if (!c->cheb_z.p) {
+    c->cheb_z.alloc(c->n_u);
+    c->cheb_z.zero(s);
+    c->cheb_t.alloc(c->n_u);
+    c->cheb_t.zero(s);
+  }
+  if (!c->wz_u.p) {
+    c->wz_u.alloc(c->n_u);
+    c->wz_u.zero(s);
+  }
+  const bool fusable = c->operator_mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && c->box.enabled && kron_supported(c->dim, c->k_u) && c->diag_u_cls.p && !c->cons_u.n &&
+                       !std::getenv("PORO_CHEB_UNFUSED");
+  const bool fuse = fusable && !c->comm.multi();
+  // slab partitions (3D): the fused kernel runs on every rank with its LOCAL partial product; on the two shared node planes it also leaves the raw partial, the neighbours
+  // swap those planes and a plane-sized kernel redoes the update there with the complete sum (the same two numbers on both ranks: bitwise equal copies)
+  const bool fuse_multi = fusable && c->comm.multi() && !c->comm.general && c->dim == 3;
+  if (fuse_multi && c->cheb_side_lo.n < (size_t)c->comm.part.plane_u) {
+    c->cheb_side_lo.alloc(c->comm.part.plane_u);
+    c->cheb_side_hi.alloc(c->comm.part.plane_u);
+  }
+  const int64_t n_own = owned(c, c->n_u, c->comm.part.plane_u);
+
+  // One step zn = zj + omega D^-1 (g - A zj) in its three forms.  dp != null (the last step inside the iteration) asks for the block partials
+  // of g . zn; each form returns whether it has left them there
+  auto cheb_update = [&](const double *g, double *zn, double omega) {
+    KronCheb kc;
+    kc.g = g;
+    kc.znew = zn;
+    kc.omega = omega;
+    kc.cls = c->diag_u_cls.p;
+    kc.tab = c->diag_u_tab.p;
+    return kc;
+  };
+  auto fused_kernel = [&](const double *zj, const KronCheb &kc, double *dp, const PcgScalars *pstate) {
+    return sampled_dispatch(c, "apply_u_chebyshev_fused", [&](hipEvent_t e0, hipEvent_t e1) {
+      return kron_apply(s, mf_args(c), zj, nullptr, true, c->n_cus, dp, e0, e1, pstate, &kc);
+    });
+  };
+  auto step_fused_slabs = [&](const double *g, double *zj, double *zn, double omega, double *dp) {
+    const poro_partition &pt = c->comm.part;
+    const int64_t plane = pt.plane_u;
+    KronCheb kc = cheb_update(g, zn, omega);
+    kc.side_lo = pt.has_lower ? c->cheb_side_lo.p : nullptr;
+    kc.side_hi = pt.has_upper ? c->cheb_side_hi.p : nullptr;
+    (void)fused_kernel(zj, kc, nullptr, nullptr);
+    if (pt.has_lower || pt.has_upper) {
+      {
+        Timed te(c, "halo_exchange");
+        exchange_planes(c, c->cheb_side_lo.p, c->cheb_side_hi.p, plane);
+      }
+      la_cheb_fix_planes(s, zn, zj, g, kc.side_lo, c->comm.recv_lo.p, kc.side_hi, c->comm.recv_hi.p, dj, omega, c->n_u, plane);
+    }
+    if (dp) la_dot_partials(s, g, zn, n_own, dp);
+    return dp != nullptr;
+  };
+  auto step_fused = [&](const double *g, double *zj, double *zn, double omega, double *dp, const PcgScalars *pstate) {
+    const KronCheb kc = cheb_update(g, zn, omega);
+    if (dp) PORO_HIP(hipMemsetAsync(dp, 0, kMaxPartials * sizeof(double), s));
+    const int slots = fused_kernel(zj, kc, dp, pstate);
+    return dp && slots > 0;
+  };
+  auto step_unfused = [&](const double *g, double *zj, double *zn, double omega, double *dp) {
+    apply(zj, c->cheb_t.p, nullptr);
+    la_cheb_step(s, zn, zj, g, c->cheb_t.p, dj, omega, c->n_u, n_own, dp);
+    return dp != nullptr;
+  };
+  const ApplyFn P = [&](const double *g, double *z, double *gz_partials) {
+    Timed tm(c, "precondition_u_chebyshev");
+    double *X[2] = {(m % 2 == 0) ? z : c->cheb_z.p, (m % 2 == 0) ? c->cheb_z.p : z};   // z_{j+1} lands in X[j & 1]; the last one (j = m) in z
+    if (!gz_partials && !c->cheb_z1_ready) la_cheb_first(s, X[0], g, dj, 1.0 / roots[0], c->n_u);   // inside the iteration z_1 = D^-1 g / r_0 was stored by the residual update (DiagVec::z1_out)
+    c->cheb_z1_ready = false;
+    bool dot_done = false;
+    // (the device-side "solve finished" flag may only gate launches inside the iteration: before pcg_scalars_start it still holds the previous solve's state)
+    const PcgScalars *pstate = gz_partials ? c->scal.p : nullptr;
+    for (int j = 1; j <= m; ++j) {
+      const double omega = 1.0 / roots[j];
+      double *zj = X[(j - 1) & 1], *zn = X[j & 1];
+      double *dp = j == m ? gz_partials : nullptr;
+      if (fuse_multi) dot_done = step_fused_slabs(g, zj, zn, omega, dp);
+      else if (fuse) dot_done = step_fused(g, zj, zn, omega, dp, pstate);
+      else dot_done = step_unfused(g, zj, zn, omega, dp);
+      ++c->cheb_applies;
+    }
+    return dot_done;
+  };
+  DiagVec dz = dj;
+  dz.z = c->wz_u.p;
+  dz.z1_out = (m % 2 == 0) ? c->wz_u.p : c->cheb_z.p;
+  dz.z1_scale = 1.0 / roots[0];
+  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
+                     c->pcg_hint_cheb_u, fuse);
+  // useful operator applications: one per CG iteration + the initial residual, and m per preconditioner call (one call per iteration + the first direction)
+  if (info) info->operator_applications = (int64_t)info->iterations + 1 + (int64_t)m * (info->iterations + 1);
+  finish_u(c, true);
+  return rc;   // (stream-ordered: pcg() returned after the finishing iteration, `distribute` follows in the stream)
+}
+
+// The three transform dispatches of the octant form.  A sampled call times them one by one (per-kernel roofline of the bench): the sampling runs on
+// fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
+void fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, const PcgScalars *gate) {
+  Timed tm(c, "precondition_u_fdm");
+  const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
+  if (!begin_sampled_dispatch(c, names[0])) {
+    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate);
+    return;
+  }
+  c->timers[names[1]].enqueued++;
+  c->timers[names[2]].enqueued++;
+  hipEvent_t ev[6];
+  for (auto &e : ev) e = event_get(c);
+  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev);
+  for (int k = 0; k < 3; ++k) {
+    Timer &t = c->timers[names[k]];
+    t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
+    t.launches++;
+  }
+}
+
+// z = blockdiag(A_cc)^-1 g by fast diagonalisation: the same device-controlled SolverCG recurrence with an explicit preconditioner vector
+int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+  build_fdm_u(c);
+  const FdmOct *oct = c->fdm_oct.built ? &c->fdm_oct : nullptr;
+  const ApplyFn P = [&](const double *g, double *z, double *in_iteration) {
+    // g, z in octant form: three contiguous sweeps; inside the iteration the launches are gated on the device-side "solve finished" flag (before
+    // pcg_scalars_start it still holds the previous solve's state)
+    const PcgScalars *gate = in_iteration ? c->scal.p : nullptr;
+    if (!oct) {
+      fdm_precondition_u(c, g, z);
+    } else if (oct->slab.on) {
+      fdm_precondition_u_slab(c, g, z, gate);
+    } else if (oct->planar) {
+      Timed tm(c, "precondition_u_fdm");
+      fdmo_apply_planar(c->stream, *oct, g, z, gate);
+    } else {
+      fdm_u_octant_passes(c, *oct, g, z, gate);
+    }
+    return false;
+  };
+  DiagVec dz = diag_u(c, c->dir_mask.p, false);
+  dz.z = c->wz_u.p;
+  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
+                     c->pcg_hint_fdm_u, oct != nullptr /* every launch of an iteration is gated: overshooting is cheap */, oct);
+  finish_u(c, false);
+  return rc;
+}
+
+// z = omega D^-1 g + P B_H^-1 P^T g: Jacobi on this mesh + the block fast diagonalisation of the underlying uniform box; SolverCG's recurrence with an
+// explicit preconditioner vector
+int solve_u_two_level(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+  if (!two_level_supported(c)) throw Error("PORO_PREC_TWO_LEVEL needs poro_desc.coarse (a refinement of a uniform box whose Dirichlet conditions cover whole faces)");
+  const double om = opts->omega > 0 ? opts->omega : 1.0;
+  if (!c->wz_u.p) {
+    c->wz_u.alloc(c->n_u);
+    c->wz_u.zero(c->stream);
+  }
+  const ApplyFn P = [&](const double *g, double *z, double *) {
+    two_level_precondition_u(c, g, z, om);
+    return false;
+  };
+  DiagVec dz = diag_u(c, c->cons_u.inert.p, false);
+  dz.z = c->wz_u.p;
+  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
+                     c->pcg_hint_u);
+  finish_u(c, true);
+  return rc;
+}
+
+int solve_u_jacobi(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+  const DiagVec dv = diag_u(c, c->cons_u.inert.p, true);
+  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dv, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, nullptr,
+                     c->pcg_hint_u);
+  finish_u(c, true);
+  return rc;
+}
+
+// ---- the scalar Q1 systems (a M + kappa K) x = b on the pattern Ap: the pressure Jacobian and the projection mass matrix ---------------------
+struct Q1System {
+  double a, kappa;                    // (1 / (M_b dt), k / mu) or (1, 0)
+  const double *val;                  // CSR values
+  const double *dinv;                 // reciprocal diagonal, zero on the inert dofs
+  DevBuf<double> *ilu;                // ILU(0) factor and whether it belongs to the present values
+  bool *ilu_valid;
+  double *x;
+  const double *b;
+  int *hint;                          // iteration counts of the last two solves
+  const uint8_t *inert_two_level;     // the inert mask handed to PCG per branch (FDM: none); null selects the kernel form without a mask
+  const uint8_t *inert_jacobi;
+};
+
+// uniform box, matrix-free: both matrices are constant-coefficient stencils
+bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled; }
+
+// Direct solve of n <= 3 systems that share (a, kappa) where the fast diagonalisation is the exact inverse (uniform box, slab partitions included: the
+// distributed form is the same inverse): x_e = (a M + kappa K)^-1 b_e, then the residuals are checked against the reference's stopping rule with one poll
+// for all norms.  info[e].iterations = 0 marks a directly solved system; returns whether every system met the rule (if not, x_e is a good start for CG).
+// y: scratch of n vectors.  batched: all right-hand sides in one set of launches (c->fdm_p_fused)
+bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *const *b, double *const *x, double *y_scratch, bool batched,
+                     const poro_solver_opts *opts, poro_solve_info *info) {
+  hipStream_t s = c->stream;
+  const double *y[3];
+  for (int e = 0; e < n; ++e) y[e] = y_scratch + (size_t)e * c->n_p;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (batched) {
+    Timed tm(c, "precondition_p_fdm");
+    fdmo_scalar_apply_many(s, c->fdm_p_fused, a, kappa, n, b, x);
+  } else {
+    const double kk[3] = {kappa, kappa, kappa};
+    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e]);
+  }
+  for (int e = 0; e < n; ++e) {
+    {
+      Timed tm(c, "apply_p_stencil");
+      p_stencil_apply(s, c->dim, c->box, a, kappa, x[e], const_cast<double *>(y[e]));
+    }
+    exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p);
+  }
+  la_residual_norms_many(s, n, y, b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p);
+  pcg_scalars_sum(s, c->partials.p, 2 * n, c->red.p);
+  allreduce_sum(c, c->red.p, 2 * n);
+  post_and_wait(c, c->red.p, 2 * n);
+  bool all = true;
+  for (int e = 0; e < n; ++e) {
+    const double res = std::sqrt(c->mailbox->vals[2 * e]), bn = std::sqrt(c->mailbox->vals[2 * e + 1]);
+    const bool ok = res <= std::max(opts->abs_tol, opts->rel_tol * bn);
+    all = all && ok;
+    if (!info) continue;
+    info[e] = poro_solve_info{};
+    info[e].iterations = 0;
+    info[e].converged = ok ? 1 : 0;
+    info[e].initial_residual = bn;
+    info[e].final_residual = res;
+    info[e].operator_applications = 1;
+    info[e].seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / n;
+  }
+  return all;
+}
+
+// ILU(0) / SSOR / fast-diagonalisation / two-level / Jacobi PCG on one system.  direct_first (FDM only): try the direct solve, whose result is the
+// start of the iteration where its check fails
+int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_solve_info *info, bool direct_first = false) {
+  double *g = c->wg_p.p, *d = c->wd_p.p, *h = c->wh_p.p;
+  if (opts->preconditioner == PORO_PREC_ILU0) return pcg_ilu0(c, c->Ap, q.val, *q.ilu, *q.ilu_valid, q.x, q.b, g, d, h, opts, info);
+  if (opts->preconditioner == PORO_PREC_SSOR) return pcg_ssor(c, c->Ap, q.val, q.x, q.b, g, d, h, opts, info);
+  const bool stencil = q1_stencil(c);
+  const int64_t n = c->n_p, plane = c->comm.part.plane_p;
+  // the condensed matrix C^T (a M + kappa K) C (:168, StrainProjector.h:104-105)
+  const ApplyFn apply = [&](const double *x, double *y, double *) {
+    la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);
+    if (stencil) {
+      Timed tm(c, "apply_p_stencil");
+      p_stencil_apply(c->stream, c->dim, c->box, q.a, q.kappa, x, y);
+    } else {
+      Timed tm(c, "apply_p_csr");
+      la_csr_spmv(c->stream, c->Ap, q.val, x, y);
+    }
+    la_cons_reduce(c->stream, c->cons_p, y);
+    exchange_add(c, y, n, plane);
+    return false;
+  };
+  DiagVec dz;
+  dz.full = q.dinv;
+  if (opts->preconditioner == PORO_PREC_FDM) {
+    build_fdm_p(c);
+    const double kk[3] = {q.kappa, q.kappa, q.kappa};
+    if (!c->wz_p.p) c->wz_p.alloc(n);
+    if (direct_first) {
+      poro_solve_info direct;
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct)) {
+        if (info) *info = direct;
+        return 0;
+      }
+    }
+    const ApplyFn P = [&](const double *gg, double *z, double *) {
+      fdm_precondition_p(c, q.a, kk, gg, z);
+      return false;
+    };
+    dz.z = c->wz_p.p;
+    return pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, &P, q.hint);
+  }
+  int rc;
+  if (opts->preconditioner == PORO_PREC_TWO_LEVEL) {
+    if (!c->wz_p.p) c->wz_p.alloc(n);
+    const double om = opts->omega > 0 ? opts->omega : 1.0;
+    const ApplyFn P = [&](const double *gg, double *z, double *) {
+      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om);
+      return false;
+    };
+    dz.z = c->wz_p.p;
+    dz.inert = q.inert_two_level;
+    rc = pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, &P, q.hint);
+  } else {
+    dz.inert = q.inert_jacobi;
+    rc = pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, nullptr, q.hint);
+  }
+  la_cons_expand(c->stream, c->cons_p, q.x, true);                              // constraints.distribute (:180, StrainProjector.h:216)
+  return rc;
+}
+
 }  // namespace
 
 // ======================================= extern "C" ================================================================
@@ -196,73 +695,37 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         if (!c->Ke.p) c->Ke.alloc((size_t)c->dpc_u * c->dpc_u);
         asm_u_element_matrix(s, a, 0, c->Ke.p);
         box_asm_u_matrix(s, c->dim, c->k_u, c->box, c->Ke.p, c->Au, c->dir_mask.p, c->Au_val.p);
-        if (!c->box_asm_checked && c->Au.nnz <= 60000000 && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) {   // once, against the coloured per-cell assembly
-          DevBuf<double> ref, lift_ref; ref.alloc(c->Au.nnz); ref.zero(s); lift_ref.alloc(c->n_u); lift_ref.zero(s);
-          for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
-            asm_u_matrix(s, a, c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k], c->Au.rp.p, c->Au.col.p, ref.p, lift_ref.p);
-          la_axpy(s, ref.p, -1.0, c->Au_val.p, c->Au.nnz);
-          la_norm_partials(s, ref.p, c->Au.nnz, c->partials.p, c->partials.p + kMaxPartials); la_norm_partials(s, c->Au_val.p, c->Au.nnz, c->partials.p + 2 * kMaxPartials, c->partials.p + 3 * kMaxPartials);
-          la_reduce_finish(s, c->partials.p, 4, c->red.p, 2 | 8);
-          double h[4]; PORO_HIP(hipMemcpyAsync(h, c->red.p, sizeof(h), hipMemcpyDeviceToHost, s)); PORO_HIP(hipStreamSynchronize(s));
-          if (!(h[1] <= 1e-12 * h[3])) throw Error("structured CSR assembly disagrees with the per-cell assembly: max diff " + std::to_string(h[1]) + " vs max " + std::to_string(h[3]));
-        }
+        if (!c->box_asm_checked && c->Au.nnz <= 60000000 && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) check_box_assembly(c, a);   // once
         c->box_asm_checked = true;
         mf_operator(c, c->dir_val.p, c->wh_u.p, false);
-        la_fill(s, c->lift_u.p, 0.0, c->n_u); la_axpy(s, c->lift_u.p, -1.0, c->wh_u.p, c->n_u);
+        lifting_from_wh(c);
         la_csr_diag(s, c->Au, c->Au_val.p, c->diag_u_local.p);
       } else if (c->operator_mode == PORO_OP_CSR) {
         c->Au_val.zero(s);
-        for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
-          asm_u_matrix(s, a, c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k], c->Au.rp.p, c->Au.col.p, c->Au_val.p, c->lift_u.p);
+        for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_matrix(s, a, cells, n_cells, c->Au.rp.p, c->Au.col.p, c->Au_val.p, c->lift_u.p); });
         la_csr_diag(s, c->Au, c->Au_val.p, c->diag_u_local.p);
       } else if (!c->box.enabled) {
         // general mesh, matrix-free: the diagonal and the lifting -(A_full g) come from the same quadrature-level cell loop
         mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, nullptr, c->diag_u_local.p, false, 1);
         mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->dir_val.p, c->wh_u.p, false, 0);
-        la_fill(s, c->lift_u.p, 0.0, c->n_u); la_axpy(s, c->lift_u.p, -1.0, c->wh_u.p, c->n_u);
+        lifting_from_wh(c);
       } else {
         asm_u_element_matrix(s, a, 0, c->Ke.p);
         mf_diag(s, mf_args(c), c->diag_u_local.p);
         // lifting: -(A_full g) on the free rows, through the unconstrained operator
         mf_operator(c, c->dir_val.p, c->wh_u.p, false);
-        if (c->mf_variant == 1 && kron_supported(c->dim, c->k_u) && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) {
-          // self-check of the sum-factorised operator against the element-matrix gather on a synthetic vector (guards the
-          // FE-table / numbering assumptions of the structured path); both unconstrained
-          std::vector<double> hx(c->n_u); for (int64_t i = 0; i < c->n_u; ++i) hx[i] = std::sin(0.37 * (double)i);
-          DevBuf<double> tx, t1, t2; tx.upload(hx); t1.alloc(c->n_u); t2.alloc(c->n_u);
-          kron_apply(s, mf_args(c), tx.p, t1.p, false, c->n_cus); mf_apply(s, mf_args(c), tx.p, t2.p, false);
-          la_axpy(s, t1.p, -1.0, t2.p, c->n_u);
-          la_norm_partials(s, t1.p, c->n_u, c->partials.p, c->partials.p + kMaxPartials); la_norm_partials(s, t2.p, c->n_u, c->partials.p + 2 * kMaxPartials, c->partials.p + 3 * kMaxPartials);
-          la_reduce_finish(s, c->partials.p, 4, c->red.p, 2 | 8);
-          double h[4]; PORO_HIP(hipMemcpyAsync(h, c->red.p, sizeof(h), hipMemcpyDeviceToHost, s)); PORO_HIP(hipStreamSynchronize(s));
-          if (!(h[1] <= 1e-11 * h[3])) throw Error("sum-factorised operator disagrees with the element-matrix operator: max diff " + std::to_string(h[1]) + " vs max " + std::to_string(h[3]));
-        }
-        la_fill(s, c->lift_u.p, 0.0, c->n_u); la_axpy(s, c->lift_u.p, -1.0, c->wh_u.p, c->n_u);
+        if (c->mf_variant == 1 && kron_supported(c->dim, c->k_u) && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) check_sum_factorised_operator(c);
+        lifting_from_wh(c);
       }
       asm_u_neumann(s, a, c->n_bfaces, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
       if (!c->diag_u.p) c->diag_u.alloc(c->n_u);
       la_copy(s, c->diag_u.p, c->diag_u_local.p, c->n_u);
       exchange_add(c, c->diag_u.p, c->n_u, c->comm.part.plane_u);
-      // dictionary form of the Jacobi diagonal: on a uniform box only a few dozen distinct per-node triples exist, so the PCG kernels
-      // can read one class byte per node and a tiny table instead of 8 bytes per dof.  Built by de-duplicating the actual values.
       c->diag_u_cls.release(); c->diag_u_tab.release();
       if (!c->dinv_u.p) c->dinv_u.alloc(c->n_u);
       la_reciprocal(s, c->dinv_u.p, c->diag_u.p, c->n_u);
       la_mask_zero(s, c->dinv_u.p, c->cons_u.inert.p, c->n_u);                   // zero reciprocal = inert (Dirichlet or hanging) dof (DiagVec)
-      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
-        std::vector<double> hd(c->n_u);
-        PORO_HIP(hipMemcpyAsync(hd.data(), c->dinv_u.p, c->n_u * sizeof(double), hipMemcpyDeviceToHost, s)); PORO_HIP(hipStreamSynchronize(s));
-        const int nc = c->dim; const int64_t nnode = c->n_u / nc;
-        struct KeyHash { size_t operator()(const std::array<double, 3> &k) const { uint64_t h = 1469598103934665603ull; for (double v : k) { uint64_t b; std::memcpy(&b, &v, 8); h = (h ^ b) * 1099511628211ull; h ^= h >> 29; } return (size_t)h; } };
-        std::unordered_map<std::array<double, 3>, int, KeyHash> dict; std::vector<uint8_t> cls(nnode); std::vector<double> tab; bool ok = true;
-        for (int64_t nd = 0; nd < nnode && ok; ++nd) {
-          std::array<double, 3> key{0, 0, 0}; for (int k = 0; k < nc; ++k) key[k] = hd[nd * nc + k];
-          auto it = dict.find(key);
-          if (it == dict.end()) { if (dict.size() >= 255) { ok = false; break; } it = dict.emplace(key, (int)dict.size()).first; for (int k = 0; k < nc; ++k) tab.push_back(key[k]); }
-          cls[nd] = (uint8_t)it->second;
-        }
-        if (ok) { c->diag_u_cls.upload(cls); c->diag_u_tab.upload(tab); }
-      }
+      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) build_diag_dictionary(c);
       c->matrix_built = true; c->ilu_u_valid = false; c->cheb_lmax = 0;
     }
     {
@@ -271,8 +734,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
       if (c->box_asm) box_rhs_u(s, c->dim, c->box_cpl, c->mat.biot_alpha, vec(c, PORO_VEC_P), c->lift_u.p, c->neumann_u.p, c->dir_mask.p, rhs);
       else {
         la_fill(s, rhs, 0.0, c->n_u);                                            // rhs_vector = 0 (:204)
-        for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
-          asm_u_rhs(s, a, c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k], vec(c, PORO_VEC_P), rhs);
+        for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_rhs(s, a, cells, n_cells, vec(c, PORO_VEC_P), rhs); });
         la_rhs_u_finish(s, rhs, c->lift_u.p, c->neumann_u.p, c->dir_mask.p, c->n_u);
       }
     }
@@ -311,185 +773,28 @@ int poro_disp_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     if (!c->matrix_built) throw Error("disp_solve before disp_assemble_system");
-    const int mode = c->operator_mode;
-    if (c->cons_u.n && opts->preconditioner != PORO_PREC_JACOBI && opts->preconditioner != PORO_PREC_NONE && opts->preconditioner != PORO_PREC_CHEBYSHEV && opts->preconditioner != PORO_PREC_TWO_LEVEL)
+    const int prec = opts->preconditioner;
+    if (c->cons_u.n && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && prec != PORO_PREC_CHEBYSHEV && prec != PORO_PREC_TWO_LEVEL)
       throw Error("meshes with constraint lists: PORO_PREC_JACOBI / CHEBYSHEV / TWO_LEVEL / NONE only (the operator is condensed on the fly)");
-    if (opts->preconditioner == PORO_PREC_ILU0) {
-      if (mode != PORO_OP_CSR) throw Error("PORO_PREC_ILU0 needs the assembled CSR operator");
+    if (prec == PORO_PREC_ILU0) {
+      if (c->operator_mode != PORO_OP_CSR) throw Error("PORO_PREC_ILU0 needs the assembled CSR operator");
       const int rc = pcg_ilu0(c, c->Au, c->Au_val.p, c->ilu_u, c->ilu_u_valid, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
-      la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
+      finish_u(c, false);
       PORO_HIP(hipStreamSynchronize(c->stream));
       return rc;
     }
-    if (opts->preconditioner == PORO_PREC_SSOR) {
-      if (mode != PORO_OP_CSR) throw Error("PORO_PREC_SSOR needs the assembled CSR operator");
+    if (prec == PORO_PREC_SSOR) {
+      if (c->operator_mode != PORO_OP_CSR) throw Error("PORO_PREC_SSOR needs the assembled CSR operator");
       const int rc = pcg_ssor(c, c->Au, c->Au_val.p, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
-      la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
+      finish_u(c, false);
       PORO_HIP(hipStreamSynchronize(c->stream));
       return rc;
     }
-    const std::function<bool(const double *, double *, double *)> apply = [&](const double *x, double *y, double *dp) {
-      if (!c->cons_u.n) return apply_A_u(c, x, y, mode, dp, false, dp ? c->scal.p : nullptr);
-      // C^T A C: the search direction's hanging entries follow their masters, the product's hanging rows fold into the masters' rows
-      la_cons_expand(c->stream, c->cons_u, const_cast<double *>(x), false);
-      apply_A_u(c, x, y, mode, nullptr, false, nullptr, false);                 // the rank's partial product ...
-      la_cons_reduce(c->stream, c->cons_u, y);                                   // ... folded ...
-      exchange_add(c, y, c->n_u, c->comm.part.plane_u);                          // ... then summed over the interface
-      return false;
-    };
-    if (opts->preconditioner == PORO_PREC_CHEBYSHEV) {
-      // z = q(D^-1 A) D^-1 g with the Chebyshev polynomial q of degree m for the interval [lambda_max / ratio, lambda_max]: m operator applications
-      // without dot products; on 3D boxes (one rank) the recurrence runs inside the structured operator kernel
-      int m = opts->poly_degree > 0 ? opts->poly_degree : 6;
-      DiagVec dj; dj.full = c->dinv_u.p; dj.ncomp = c->dim; dj.inert = c->cons_u.inert.p;
-      if (c->diag_u_cls.p) { dj.cls = c->diag_u_cls.p; dj.tab = c->diag_u_tab.p; }
-      // lambda_max(D^-1 A): on a uniform box all cells share one element matrix and lambda_max <= lambda_max(diag(K_e)^-1 K_e) holds rigorously
-      // (x^T A x = sum_e x_e^T K_e x_e <= mu sum_e x_e^T diag(K_e) x_e = mu x^T D x) but is loose (3.8 against 2.5 for Q2 hexahedra), so the working
-      // value is the Lanczos estimate (+5 %) capped by it.  Only EVEN degrees are used: should an eigenvalue still exceed the assumed bound, it meets
-      // T_{m+1} outside [-1, 1], and q(lambda) lambda stays positive (the preconditioner SPD) exactly when m + 1 is odd
-      const bool have_bound = c->box.enabled && c->Ke.p && !c->cons_u.n;
-      if (m & 1) ++m;
-      if (!(c->cheb_lmax > 0)) {
-        if (have_bound) {
-          std::vector<double> ke((size_t)c->dpc_u * c->dpc_u);
-          PORO_HIP(hipMemcpyAsync(ke.data(), c->Ke.p, ke.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
-          c->cheb_lmax = std::min(jacobi_scaled_lambda_max(c->dpc_u, ke), estimate_lmax_u(c, apply, dj));   // the element bound is rigorous but loose
-        } else c->cheb_lmax = estimate_lmax_u(c, apply, dj); if (std::getenv("PORO_CHEB_VERBOSE")) std::fprintf(stderr, "[poro] lambda_max(D^-1 A_u) ~ %.6f\n", c->cheb_lmax); }
-      // `omega` doubles as the interval ratio; anything below 4 (the SSOR relaxation 1.2 a caller may have left there, 0) means "default"
-      double ratio = opts->omega;
-      if (!(ratio >= 4.0)) {   // default: a few times lambda_min, which scales with h^2 (calibrated on box runs of 8^3 .. 72^3 cells)
-        if (!(c->cheb_ratio_default > 0)) {
-          // from GLOBAL mesh sizes, so that every rank of a partitioned run builds the same polynomial (rank-local sizes gave uneven slabs different roots on
-          // either side of a shared plane): the cell layers of the partitioned direction (slabs) / the cell count (general partitions) are summed over the ranks
-          double h[2] = {(double)c->box.n[c->dim - 1], (double)c->n_cells};
-          if (c->comm.multi()) {
-            PORO_HIP(hipMemcpyAsync(c->red.p, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-            allreduce_sum(c, c->red.p, 2);
-            PORO_HIP(hipMemcpyAsync(h, c->red.p, sizeof(h), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
-          }
-          double nmax = 1;
-          if (c->box.enabled) { for (int k = 0; k < c->dim; ++k) nmax = std::max(nmax, k == c->dim - 1 ? h[0] : (double)c->box.n[k]); }
-          else nmax = std::round(std::pow(h[1], 1.0 / c->dim));
-          c->cheb_ratio_default = std::min(400.0, std::max(10.0, (c->k_u == 2 ? 0.2 : 0.05) * nmax * nmax));
-        }
-        ratio = c->cheb_ratio_default;
-      }
-      // root form: the residual polynomial of degree m + 1 is prod_i (1 - lambda / r_i) with the roots r_i of the Chebyshev polynomial shifted to
-      // [lambda_max / ratio, lambda_max]; z_1 = D^-1 g / r_0, z_{j+1} = z_j + D^-1 (g - A z_j) / r_j.  Same polynomial as the three-term recurrence
-      // (identical CG iteration counts in the prototype for every ordering at these degrees) with ONE extra stream per step (g) instead of two;
-      // the roots are taken alternately from both ends so that no run of small roots inflates the intermediate iterates
-      const double lmax = c->cheb_lmax, lmin = lmax / ratio, theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-      std::vector<double> roots;
-      { std::vector<double> r(m + 1); for (int i = 0; i <= m; ++i) r[i] = theta - delta * std::cos(3.14159265358979323846 * (2 * i + 1) / (2.0 * (m + 1)));
-        int lo = 0, hi = m; while (lo <= hi) { roots.push_back(r[hi--]); if (lo <= hi) roots.push_back(r[lo++]); } }
-      if (!c->cheb_z.p) { c->cheb_z.alloc(c->n_u); c->cheb_z.zero(c->stream); c->cheb_t.alloc(c->n_u); c->cheb_t.zero(c->stream); }
-      if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }
-      const bool fusable = mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && c->box.enabled && kron_supported(c->dim, c->k_u) && c->diag_u_cls.p && !c->cons_u.n && !std::getenv("PORO_CHEB_UNFUSED");
-      const bool fuse = fusable && !c->comm.multi();
-      // slab partitions (3D): the fused kernel runs on every rank with its LOCAL partial product; on the two shared node planes it also leaves the raw partial, the neighbours
-      // swap those planes and a plane-sized kernel redoes the update there with the complete sum (the same two numbers on both ranks: bitwise equal copies)
-      const bool fuse_multi = fusable && c->comm.multi() && !c->comm.general && c->dim == 3;
-      if (fuse_multi && c->cheb_side_lo.n < (size_t)c->comm.part.plane_u) { c->cheb_side_lo.alloc(c->comm.part.plane_u); c->cheb_side_hi.alloc(c->comm.part.plane_u); }
-      const int64_t n_own = owned(c, c->n_u, c->comm.part.plane_u);
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *gz_partials) {
-        Timed tm(c, "precondition_u_chebyshev");
-        hipStream_t s = c->stream;
-        double *X[2] = {(m % 2 == 0) ? z : c->cheb_z.p, (m % 2 == 0) ? c->cheb_z.p : z};   // z_{j+1} lands in X[j & 1]; the last one (j = m) in z
-        if (!gz_partials && !c->cheb_z1_ready) la_cheb_first(s, X[0], g, dj, 1.0 / roots[0], c->n_u);   // inside the iteration z_1 = D^-1 g / r_0 was stored by the residual update (DiagVec::z1_out)
-        c->cheb_z1_ready = false;
-        bool dot_done = false;
-        // (the device-side "solve finished" flag may only gate launches inside the iteration: before pcg_scalars_start it still holds the previous solve's state)
-        const PcgScalars *pstate = gz_partials ? c->scal.p : nullptr;
-        for (int j = 1; j <= m; ++j) {
-          const double omega = 1.0 / roots[j];
-          double *zj = X[(j - 1) & 1], *zn = X[j & 1];
-          const bool last = j == m;
-          if (fuse_multi) {
-            const poro_partition &pt = c->comm.part; const int64_t plane = pt.plane_u;
-            KronCheb kc; kc.g = g; kc.znew = zn; kc.omega = omega; kc.cls = c->diag_u_cls.p; kc.tab = c->diag_u_tab.p;
-            kc.side_lo = pt.has_lower ? c->cheb_side_lo.p : nullptr; kc.side_hi = pt.has_upper ? c->cheb_side_hi.p : nullptr;
-            if (c->timing && c->timers["apply_u_chebyshev_fused"].sample(c->timing_stride)) { isolate_sampled_dispatch(c); Timer &t = c->timers["apply_u_chebyshev_fused"]; hipEvent_t e0 = event_get(c), e1 = event_get(c);
-                                                                                           (void)kron_apply(s, mf_args(c), zj, nullptr, true, c->n_cus, nullptr, e0, e1, nullptr, &kc); t.pending.emplace_back(e0, e1); t.launches++; }
-            else (void)kron_apply(s, mf_args(c), zj, nullptr, true, c->n_cus, nullptr, nullptr, nullptr, nullptr, &kc);
-            if (pt.has_lower || pt.has_upper) {
-              { Timed te(c, "halo_exchange"); exchange_planes(c, c->cheb_side_lo.p, c->cheb_side_hi.p, plane); }
-              la_cheb_fix_planes(s, zn, zj, g, kc.side_lo, c->comm.recv_lo.p, kc.side_hi, c->comm.recv_hi.p, dj, omega, c->n_u, plane);
-            }
-            if (last && gz_partials) { la_dot_partials(s, g, zn, n_own, gz_partials); dot_done = true; }
-          } else if (fuse) {
-            KronCheb kc; kc.g = g; kc.znew = zn; kc.omega = omega; kc.cls = c->diag_u_cls.p; kc.tab = c->diag_u_tab.p;
-            double *dp = (last && gz_partials) ? gz_partials : nullptr;
-            if (dp) PORO_HIP(hipMemsetAsync(dp, 0, kMaxPartials * sizeof(double), s));
-            int slots;
-            if (c->timing && c->timers["apply_u_chebyshev_fused"].sample(c->timing_stride)) { isolate_sampled_dispatch(c); Timer &t = c->timers["apply_u_chebyshev_fused"]; hipEvent_t e0 = event_get(c), e1 = event_get(c);
-                             slots = kron_apply(s, mf_args(c), zj, nullptr, true, c->n_cus, dp, e0, e1, pstate, &kc); t.pending.emplace_back(e0, e1); t.launches++; }
-            else slots = kron_apply(s, mf_args(c), zj, nullptr, true, c->n_cus, dp, nullptr, nullptr, pstate, &kc);
-            if (dp && slots > 0) dot_done = true;
-          } else {
-            apply(zj, c->cheb_t.p, nullptr);
-            la_cheb_step(s, zn, zj, g, c->cheb_t.p, dj, omega, c->n_u, n_own, (last && gz_partials) ? gz_partials : nullptr);
-            if (last && gz_partials) dot_done = true;
-          }
-          ++c->cheb_applies;
-        }
-        return dot_done;
-      };
-      DiagVec dz = dj; dz.z = c->wz_u.p;
-      dz.z1_out = (m % 2 == 0) ? c->wz_u.p : c->cheb_z.p; dz.z1_scale = 1.0 / roots[0];
-      const int64_t applies0 = c->cheb_applies;
-      const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P, c->pcg_hint_cheb_u, fuse);
-      // useful operator applications: one per CG iteration + the initial residual, and m per preconditioner call (one call per iteration + the first direction)
-      if (info) info->operator_applications = (int64_t)info->iterations + 1 + (int64_t)m * (info->iterations + 1);
-      (void)applies0;
-      la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
-      la_cons_expand(c->stream, c->cons_u, vec(c, PORO_VEC_U), true);
-      return rc;   // (stream-ordered: pcg() returned after the finishing iteration, `distribute` follows in the stream)
-    }
-    if (opts->preconditioner == PORO_PREC_FDM) {
-      // z = blockdiag(A_cc)^-1 g by fast diagonalisation: the same device-controlled SolverCG recurrence with an explicit preconditioner vector
-      build_fdm_u(c);
-      const FdmOct *oct = c->fdm_oct.built ? &c->fdm_oct : nullptr;
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *in_iteration) {
-        // g, z in octant form: three contiguous sweeps; inside the iteration the launches are gated on the device-side "solve finished" flag (before
-        // pcg_scalars_start it still holds the previous solve's state)
-        if (oct && oct->slab.on) fdm_precondition_u_slab(c, g, z, in_iteration ? c->scal.p : nullptr);
-        else if (oct && oct->planar) { Timed tm(c, "precondition_u_fdm"); fdmo_apply_planar(c->stream, *oct, g, z, in_iteration ? c->scal.p : nullptr); }
-        else if (oct) {
-          Timed tm(c, "precondition_u_fdm");
-          if (c->timing && c->timers["fdm_u_pass1"].sample(c->timing_stride)) {     // the three transform dispatches individually (per-kernel roofline of the bench)
-            c->timers["fdm_u_pass2"].enqueued++; c->timers["fdm_u_pass3"].enqueued++;
-            isolate_sampled_dispatch(c);
-            hipEvent_t ev[6]; for (auto &e : ev) e = event_get(c);
-            fdmo_apply(c->stream, *oct, g, z, c->fdm_oct.t.p, in_iteration ? c->scal.p : nullptr, ev);
-            const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
-            for (int k = 0; k < 3; ++k) { Timer &t = c->timers[names[k]]; t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]); t.launches++; }
-          } else fdmo_apply(c->stream, *oct, g, z, c->fdm_oct.t.p, in_iteration ? c->scal.p : nullptr);
-        }
-        else fdm_precondition_u(c, g, z);
-        return false; };
-      DiagVec dz; dz.full = c->dinv_u.p; dz.ncomp = c->dim; dz.inert = c->dir_mask.p; dz.z = c->wz_u.p;
-      const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P, c->pcg_hint_fdm_u, oct != nullptr /* every launch of an iteration is gated: overshooting is cheap */, oct);
-      la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
-      return rc;
-    }
-    if (opts->preconditioner == PORO_PREC_TWO_LEVEL) {
-      // z = omega D^-1 g + P B_H^-1 P^T g: Jacobi on this mesh + the block fast diagonalisation of the underlying uniform box; SolverCG's recurrence with an explicit preconditioner vector
-      if (!two_level_supported(c)) throw Error("PORO_PREC_TWO_LEVEL needs poro_desc.coarse (a refinement of a uniform box whose Dirichlet conditions cover whole faces)");
-      const double om = opts->omega > 0 ? opts->omega : 1.0;
-      if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *) { two_level_precondition_u(c, g, z, om); return false; };
-      DiagVec dz; dz.full = c->dinv_u.p; dz.ncomp = c->dim; dz.inert = c->cons_u.inert.p; dz.z = c->wz_u.p;
-      const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P, c->pcg_hint_u);
-      la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);
-      la_cons_expand(c->stream, c->cons_u, vec(c, PORO_VEC_U), true);
-      return rc;
-    }
-    DiagVec dv; dv.full = c->dinv_u.p; dv.ncomp = c->dim; dv.inert = c->cons_u.inert.p;
-    if (c->diag_u_cls.p) { dv.cls = c->diag_u_cls.p; dv.tab = c->diag_u_tab.p; }
-    const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dv, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, nullptr, c->pcg_hint_u);
-    la_set_constrained(c->stream, vec(c, PORO_VEC_U), c->dir_mask.p, c->dir_val.p, c->n_u);   // constraints.distribute (:306)
-    la_cons_expand(c->stream, c->cons_u, vec(c, PORO_VEC_U), true);
-    return rc;
+    const ApplyFn apply = operator_u(c);
+    if (prec == PORO_PREC_CHEBYSHEV) return solve_u_chebyshev(c, apply, opts, info);
+    if (prec == PORO_PREC_FDM) return solve_u_fdm(c, apply, opts, info);
+    if (prec == PORO_PREC_TWO_LEVEL) return solve_u_two_level(c, apply, opts, info);
+    return solve_u_jacobi(c, apply, opts, info);
   });
 }
 
@@ -545,62 +850,31 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     if (c->jac_dt < 0) throw Error("pres_solve before pres_assemble_jacobian");
-    if ((c->cons_p.n || c->n_pdir) && opts->preconditioner != PORO_PREC_JACOBI && opts->preconditioner != PORO_PREC_NONE && !(opts->preconditioner == PORO_PREC_TWO_LEVEL && !c->n_pdir)) throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL) only");
-    if (opts->preconditioner == PORO_PREC_ILU0) {
-      return pcg_ilu0(c, c->Ap, c->Jp.p, c->ilu_J, c->ilu_J_valid, vec(c, PORO_VEC_DP), vec(c, PORO_VEC_RESIDUAL_P), c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info);
-    }
-    if (opts->preconditioner == PORO_PREC_SSOR) return pcg_ssor(c, c->Ap, c->Jp.p, vec(c, PORO_VEC_DP), vec(c, PORO_VEC_RESIDUAL_P), c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info);
-    const bool stencil = c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled;   // uniform box: J is a constant-coefficient stencil
-    const double ja = 1. / c->mat.biot_M / c->jac_dt, jk = c->mat.k_over_mu;
-    auto apply = [&](const double *x, double *y, double *) {
-      la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);      // condensed Jacobian C^T J C (:168)
-      if (stencil) { Timed tm(c, "apply_p_stencil"); p_stencil_apply(c->stream, c->dim, c->box, ja, jk, x, y); }
-      else { Timed tm(c, "apply_p_csr"); la_csr_spmv(c->stream, c->Ap, c->Jp.p, x, y); }
-      la_cons_reduce(c->stream, c->cons_p, y);
-      exchange_add(c, y, c->n_p, c->comm.part.plane_p); return false;
-    };
-    if (opts->preconditioner == PORO_PREC_FDM) {
-      build_fdm_p(c);
-      const double kk[3] = {jk, jk, jk};
-      if (!c->wz_p.p) c->wz_p.alloc(c->n_p);
-      // one rank, uniform box (2D or 3D): the fast diagonalisation is the exact inverse of J, so the update is computed directly and its residual checked against
-      // the reference's stopping rule (:175) with one poll; info->iterations = 0 marks a directly solved system.  A failed check falls through to CG with that update as start
+    const int prec = opts->preconditioner;
+    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && !c->n_pdir))
+      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL) only");
+    if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c))
+      throw Error("PORO_PREC_TWO_LEVEL (pressure): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)");
+    Q1System J;
+    J.a = 1. / c->mat.biot_M / c->jac_dt;
+    J.kappa = c->mat.k_over_mu;
+    J.val = c->Jp.p;
+    J.dinv = c->dinv_J.p;
+    J.ilu = &c->ilu_J;
+    J.ilu_valid = &c->ilu_J_valid;
+    J.x = vec(c, PORO_VEC_DP);
+    J.b = vec(c, PORO_VEC_RESIDUAL_P);
+    J.hint = c->pcg_hint_p;
+    J.inert_two_level = c->cons_p.n ? c->cons_p.inert.p : nullptr;
+    J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;
+    // one rank or slabs, uniform box (2D or 3D): the fast diagonalisation is the exact inverse of J, so the update is computed directly and its residual checked
+    // against the reference's stopping rule (:175); a failed check goes on to CG with that update as start
+    bool direct_first = false;
+    if (prec == PORO_PREC_FDM) {
       static const bool iterative = std::getenv("PORO_PRES_ITERATIVE") != nullptr;
-      if (!iterative && opts->stop_rule == PORO_STOP_RHS && stencil) {            // (slab partitions too: the distributed fast diagonalisation is the same exact inverse)
-        hipStream_t s = c->stream; double *x = vec(c, PORO_VEC_DP); const double *b = vec(c, PORO_VEC_RESIDUAL_P); const double *y = c->wh_p.p;
-        const auto t0 = std::chrono::steady_clock::now();
-        fdm_precondition_p(c, ja, kk, b, x);
-        { Timed tm(c, "apply_p_stencil"); p_stencil_apply(s, c->dim, c->box, ja, jk, x, c->wh_p.p); }
-        exchange_add(c, c->wh_p.p, c->n_p, c->comm.part.plane_p);
-        la_residual_norms_many(s, 1, &y, &b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p);
-        pcg_scalars_sum(s, c->partials.p, 2, c->red.p);
-        allreduce_sum(c, c->red.p, 2);
-        post_and_wait(c, c->red.p, 2);
-        const double res = std::sqrt(c->mailbox->vals[0]), bn = std::sqrt(c->mailbox->vals[1]);
-        if (res <= std::max(opts->abs_tol, opts->rel_tol * bn)) {
-          if (info) { *info = poro_solve_info{}; info->iterations = 0; info->converged = 1; info->initial_residual = bn; info->final_residual = res; info->operator_applications = 1;
-                      info->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-          return 0;
-        }
-      }
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *) { fdm_precondition_p(c, ja, kk, g, z); return false; };
-      DiagVec dz; dz.full = c->dinv_J.p; dz.z = c->wz_p.p;
-      return pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_DP), vec(c, PORO_VEC_RESIDUAL_P), dz, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, &P, c->pcg_hint_p);
+      direct_first = !iterative && opts->stop_rule == PORO_STOP_RHS && q1_stencil(c);
     }
-    if (opts->preconditioner == PORO_PREC_TWO_LEVEL) {
-      if (!two_level_supported_p(c)) throw Error("PORO_PREC_TWO_LEVEL (pressure): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)");
-      if (!c->wz_p.p) c->wz_p.alloc(c->n_p);
-      const double om = opts->omega > 0 ? opts->omega : 1.0;
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *) { two_level_precondition_p(c, ja, jk, c->dinv_J.p, g, z, om); return false; };
-      DiagVec dz; dz.full = c->dinv_J.p; dz.z = c->wz_p.p; dz.inert = c->cons_p.n ? c->cons_p.inert.p : nullptr;
-      const int rc = pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_DP), vec(c, PORO_VEC_RESIDUAL_P), dz, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, &P, c->pcg_hint_p);
-      la_cons_expand(c->stream, c->cons_p, vec(c, PORO_VEC_DP), true);
-      return rc;
-    }
-    DiagVec dv; dv.full = c->dinv_J.p; dv.inert = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;
-    const int rc = pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_DP), vec(c, PORO_VEC_RESIDUAL_P), dv, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, nullptr, c->pcg_hint_p);
-    la_cons_expand(c->stream, c->cons_p, vec(c, PORO_VEC_DP), true);              // constraints.distribute(solution_update) (:180)
-    return rc;
+    return solve_q1(c, J, opts, info, direct_first);
   });
 }
 
@@ -636,8 +910,7 @@ int poro_proj_assemble_rhs(poro_ctx *c, const int32_t *tensor_components, int32_
       if (c->box_asm) box_proj_rhs(c->stream, c->dim, c->box_cpl, vec(c, PORO_VEC_U), n_comp, tensor_components, rhs);
       else {
         const AsmArgs a = asm_args(c);
-        for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
-          asm_proj_rhs(c->stream, a, c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k], vec(c, PORO_VEC_U), n_comp, tensor_components, rhs);
+        for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_proj_rhs(c->stream, a, cells, n_cells, vec(c, PORO_VEC_U), n_comp, tensor_components, rhs); });
       }
     }
     for (int k = 0; k < n_comp; ++k) { la_cons_reduce(c->stream, c->cons_p, rhs[k]); exchange_add(c, rhs[k], c->n_p, c->comm.part.plane_p); }   // StrainProjector.h:191-194 (partial rows folded, then the interface sums)
@@ -650,48 +923,27 @@ int poro_proj_solve(poro_ctx *c, int32_t entry, const poro_solver_opts *opts, po
     PORO_HIP(hipSetDevice(c->device));
     if (!c->projection_matrix_ready) throw Error("proj_solve before proj_assemble_matrix");
     if (entry < 0 || entry >= c->dim * (c->dim + 1) / 2) throw Error("rhs_entry out of range");
-    if (c->cons_p.n && opts->preconditioner != PORO_PREC_JACOBI && opts->preconditioner != PORO_PREC_NONE && opts->preconditioner != PORO_PREC_TWO_LEVEL) throw Error("meshes with hanging-node constraints: PORO_PREC_JACOBI / TWO_LEVEL / NONE only");
-    if (opts->preconditioner == PORO_PREC_ILU0) {
-      return pcg_ilu0(c, c->Ap, c->Mp.p, c->ilu_M, c->ilu_M_valid, vec(c, PORO_VEC_STRAIN0 + entry), vec(c, PORO_VEC_PROJ_RHS0 + entry), c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info);
-    }
-    if (opts->preconditioner == PORO_PREC_SSOR) return pcg_ssor(c, c->Ap, c->Mp.p, vec(c, PORO_VEC_STRAIN0 + entry), vec(c, PORO_VEC_PROJ_RHS0 + entry), c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info);
-    const bool stencil = c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled;
-    auto apply = [&](const double *x, double *y, double *) {
-      la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);      // condensed projection matrix (StrainProjector.h:104-105)
-      if (stencil) { Timed tm(c, "apply_p_stencil"); p_stencil_apply(c->stream, c->dim, c->box, 1.0, 0.0, x, y); }
-      else { Timed tm(c, "apply_p_csr"); la_csr_spmv(c->stream, c->Ap, c->Mp.p, x, y); }
-      la_cons_reduce(c->stream, c->cons_p, y);
-      exchange_add(c, y, c->n_p, c->comm.part.plane_p); return false;
-    };
-    if (opts->preconditioner == PORO_PREC_FDM) {
-      build_fdm_p(c);
-      const double kk[3] = {0, 0, 0};
-      if (!c->wz_p.p) c->wz_p.alloc(c->n_p);
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *) { fdm_precondition_p(c, 1.0, kk, g, z); return false; };
-      DiagVec dz; dz.full = c->dinv_M.p; dz.z = c->wz_p.p;
-      return pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_STRAIN0 + entry), vec(c, PORO_VEC_PROJ_RHS0 + entry), dz, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, &P, c->pcg_hint_proj);
-    }
-    if (opts->preconditioner == PORO_PREC_TWO_LEVEL) {
-      if (!two_level_supported_p(c)) throw Error("PORO_PREC_TWO_LEVEL (projection): needs poro_desc.coarse with the pressure interpolation");
-      if (!c->wz_p.p) c->wz_p.alloc(c->n_p);
-      const double om = opts->omega > 0 ? opts->omega : 1.0;
-      const std::function<bool(const double *, double *, double *)> P = [&](const double *g, double *z, double *) { two_level_precondition_p(c, 1.0, 0.0, c->dinv_M.p, g, z, om); return false; };
-      DiagVec dz; dz.full = c->dinv_M.p; dz.z = c->wz_p.p; dz.inert = c->cons_p.n ? c->cons_p.inert.p : nullptr;
-      const int rc = pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_STRAIN0 + entry), vec(c, PORO_VEC_PROJ_RHS0 + entry), dz, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, &P, c->pcg_hint_proj);
-      la_cons_expand(c->stream, c->cons_p, vec(c, PORO_VEC_STRAIN0 + entry), true);
-      return rc;
-    }
-    DiagVec dv; dv.full = c->dinv_M.p; dv.inert = c->cons_p.n ? c->cons_p.inert.p : nullptr;
-    const int rc = pcg(c, apply, c->n_p, c->comm.part.plane_p, vec(c, PORO_VEC_STRAIN0 + entry), vec(c, PORO_VEC_PROJ_RHS0 + entry), dv, c->wg_p.p, c->wd_p.p, c->wh_p.p, opts, info, nullptr, c->pcg_hint_proj);
-    la_cons_expand(c->stream, c->cons_p, vec(c, PORO_VEC_STRAIN0 + entry), true);   // constraints.distribute (StrainProjector.h:216)
-    return rc;
+    const int prec = opts->preconditioner;
+    if (c->cons_p.n && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && prec != PORO_PREC_TWO_LEVEL) throw Error("meshes with hanging-node constraints: PORO_PREC_JACOBI / TWO_LEVEL / NONE only");
+    if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c)) throw Error("PORO_PREC_TWO_LEVEL (projection): needs poro_desc.coarse with the pressure interpolation");
+    Q1System M;                                                                  // projection_matrix = mass_matrix (StrainProjector.h:104)
+    M.a = 1.0;
+    M.kappa = 0.0;
+    M.val = c->Mp.p;
+    M.dinv = c->dinv_M.p;
+    M.ilu = &c->ilu_M;
+    M.ilu_valid = &c->ilu_M_valid;
+    M.x = vec(c, PORO_VEC_STRAIN0 + entry);
+    M.b = vec(c, PORO_VEC_PROJ_RHS0 + entry);
+    M.hint = c->pcg_hint_proj;
+    M.inert_two_level = M.inert_jacobi = c->cons_p.n ? c->cons_p.inert.p : nullptr;
+    return solve_q1(c, M, opts, info);
   });
 }
 
 // Several projection systems at once (the three normal strains of a time step, PoroelasticityFSS.h:153-164).  Where the fast diagonalisation is the EXACT inverse of the
-// projection mass matrix (uniform box or tensor grid, one rank, no constraint lists) the systems are solved directly: x_e = M^-1 b_e for all of them in one set of three
-// launches, then ||M x_e - b_e|| is checked against the stopping rule of the reference's CG (SolverControl, StrainProjector.h:209) and one poll returns all norms.
-// Otherwise - or if a check fails - every entry goes through poro_proj_solve.  info[e].iterations = 0 marks a directly solved entry.
+// projection mass matrix (uniform box or tensor grid, no constraint lists) the systems are solved directly (solve_q1_direct; stopping rule of the reference's CG:
+// SolverControl, StrainProjector.h:209).  Otherwise - or if a check fails - every entry goes through poro_proj_solve.  info[e].iterations = 0 marks a directly solved entry.
 int poro_proj_solve_many(poro_ctx *c, const int32_t *entries, int32_t n_entries, const poro_solver_opts *opts, poro_solve_info *info) {
   if (!c || !entries || !opts || n_entries < 0) { g_err = "null argument"; return -1; }
   int done_direct = 0;
@@ -700,30 +952,17 @@ int poro_proj_solve_many(poro_ctx *c, const int32_t *entries, int32_t n_entries,
     if (!c->projection_matrix_ready) throw Error("proj_solve before proj_assemble_matrix");
     for (int e = 0; e < n_entries; ++e) if (entries[e] < 0 || entries[e] >= c->dim * (c->dim + 1) / 2) throw Error("rhs_entry out of range");
     static const bool iterative = std::getenv("PORO_PROJ_ITERATIVE") != nullptr;
-    const bool stencil = c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled;
-    if (iterative || opts->preconditioner != PORO_PREC_FDM || opts->stop_rule != PORO_STOP_RHS || c->cons_p.n || !stencil || n_entries < 1 || n_entries > 3 || !fdm_p_supported(c)) return 0;
+    if (iterative || opts->preconditioner != PORO_PREC_FDM || opts->stop_rule != PORO_STOP_RHS || c->cons_p.n || !q1_stencil(c) || n_entries < 1 || n_entries > 3 || !fdm_p_supported(c)) return 0;
     build_fdm_p(c);
     const bool batched = !c->comm.multi() && c->fdm_p_fused.built && !c->fdm_p_fused.slab.on;      // one rank, 3D, lines of <= 128 vertices: all right-hand sides in one set of launches
-    hipStream_t s = c->stream; const double *b[3]; double *x[3]; const double *y[3];
     if (c->proj_y.n < (size_t)3 * c->n_p) c->proj_y.alloc((size_t)3 * c->n_p);
-    for (int e = 0; e < n_entries; ++e) { b[e] = vec(c, PORO_VEC_PROJ_RHS0 + entries[e]); x[e] = vec(c, PORO_VEC_STRAIN0 + entries[e]); y[e] = c->proj_y.p + (size_t)e * c->n_p; }
-    const auto t0 = std::chrono::steady_clock::now();
-    if (batched) { Timed tm(c, "precondition_p_fdm"); fdmo_scalar_apply_many(s, c->fdm_p_fused, 1.0, 0.0, n_entries, b, x); }
-    else { const double kk[3] = {0, 0, 0}; for (int e = 0; e < n_entries; ++e) fdm_precondition_p(c, 1.0, kk, b[e], x[e]); }
-    for (int e = 0; e < n_entries; ++e) { { Timed tm(c, "apply_p_stencil"); p_stencil_apply(s, c->dim, c->box, 1.0, 0.0, x[e], const_cast<double *>(y[e])); } exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p); }
-    la_residual_norms_many(s, n_entries, y, b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p);
-    pcg_scalars_sum(s, c->partials.p, 2 * n_entries, c->red.p);
-    allreduce_sum(c, c->red.p, 2 * n_entries);
-    post_and_wait(c, c->red.p, 2 * n_entries);
-    bool all = true;
+    const double *b[3];
+    double *x[3];
     for (int e = 0; e < n_entries; ++e) {
-      const double res = std::sqrt(c->mailbox->vals[2 * e]), bn = std::sqrt(c->mailbox->vals[2 * e + 1]);
-      const bool ok = res <= std::max(opts->abs_tol, opts->rel_tol * bn);
-      all = all && ok;
-      if (info) { info[e] = poro_solve_info{}; info[e].iterations = 0; info[e].converged = ok ? 1 : 0; info[e].initial_residual = bn; info[e].final_residual = res; info[e].operator_applications = 1;
-                  info[e].seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / n_entries; }
+      b[e] = vec(c, PORO_VEC_PROJ_RHS0 + entries[e]);
+      x[e] = vec(c, PORO_VEC_STRAIN0 + entries[e]);
     }
-    done_direct = all ? 1 : 0;     // (a failed check leaves x_e = M^-1 b_e as the warm start of the iterative solve below)
+    done_direct = solve_q1_direct(c, 1.0, 0.0, n_entries, b, x, c->proj_y.p, batched, opts, info) ? 1 : 0;     // (a failed check leaves x_e = M^-1 b_e as the warm start of the iterative solve below)
     return 0;
   });
   if (rc0 != 0) return rc0;

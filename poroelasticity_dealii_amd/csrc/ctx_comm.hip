@@ -59,9 +59,16 @@ void timers_collect(poro_ctx *c) {
 }
 // before a dispatch that carries start / stop events in a stream whose other dispatches carry none: a marker that drains the stream, so that the bracket holds the kernel
 // alone (otherwise its first workgroups share the chip with the tail of the previous kernel and the bracket reads a few microseconds long)
-void isolate_sampled_dispatch(poro_ctx *c) {
+static void isolate_sampled_dispatch(poro_ctx *c) {
   if (c->timing_stride <= 1) return;
   hipEvent_t m = event_get(c); (void)hipEventRecord(m, c->stream); c->event_pool.push_back(m);
+}
+Timer *begin_sampled_dispatch(poro_ctx *c, const char *family) {
+  if (!c->timing) return nullptr;
+  Timer *t = &c->timers[family];
+  if (!t->sample(c->timing_stride)) return nullptr;
+  isolate_sampled_dispatch(c);
+  return t;
 }
 
 
@@ -246,13 +253,9 @@ bool is_u_vec(int which) { return which == PORO_VEC_U || which == PORO_VEC_RHS_U
 bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_partials, bool fix_rows, const PcgScalars *pcg_state, bool exchange) {
   bool fused = false;
   if (mode == PORO_OP_MATRIX_FREE && c->box.enabled && c->mf_variant == 1 && kron_supported(c->dim, c->k_u)) {
-    int slots;
-    if (c->timing && c->timers["apply_u_matrix_free"].sample(c->timing_stride)) {   // events attached to the dispatch itself: the kernel's own duration, without the gaps to its neighbours in the stream
-      isolate_sampled_dispatch(c);
-      Timer &t = c->timers["apply_u_matrix_free"]; hipEvent_t e0 = event_get(c), e1 = event_get(c);
-      slots = kron_apply(c->stream, mf_args(c), x, y, true, c->n_cus, dot_partials, e0, e1, pcg_state);
-      t.pending.emplace_back(e0, e1); t.launches++;
-    } else slots = kron_apply(c->stream, mf_args(c), x, y, true, c->n_cus, dot_partials, nullptr, nullptr, pcg_state);
+    const int slots = sampled_dispatch(c, "apply_u_matrix_free", [&](hipEvent_t e0, hipEvent_t e1) {
+      return kron_apply(c->stream, mf_args(c), x, y, true, c->n_cus, dot_partials, e0, e1, pcg_state);
+    });
     // inside PCG the Dirichlet rows are inert (zero residual and direction), so what the structured kernel leaves there is never read
     fused = dot_partials != nullptr && slots > 0;   // slots < 0: too many workgroups for the partial slots, the kernel ran without the fused x.y
     if (fix_rows) { Timed tm(c, "apply_u_dirichlet_rows"); kron_fix_constrained(c->stream, mf_args(c), x, y, fused ? dot_partials : nullptr, slots > 0 ? slots : -slots); }

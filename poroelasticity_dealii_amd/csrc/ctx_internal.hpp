@@ -37,7 +37,19 @@ struct Timed {
   ~Timed();
 };
 void timers_collect(poro_ctx *c);
-void isolate_sampled_dispatch(poro_ctx *c);
+// A dispatch that carries its own start / stop events (the kernel's own duration, without the gaps to its neighbours in the stream).
+// begin_sampled_dispatch counts one dispatch of `family` (only while timing is on) and returns its timer when this one is to carry events,
+// with the stream already drained for it; null otherwise.  sampled_dispatch calls launch(e0, e1) with such events or with (nullptr, nullptr).
+Timer *begin_sampled_dispatch(poro_ctx *c, const char *family);
+template <class Launch> auto sampled_dispatch(poro_ctx *c, const char *family, Launch &&launch) {
+  Timer *t = begin_sampled_dispatch(c, family);
+  if (!t) return launch(nullptr, nullptr);
+  hipEvent_t e0 = event_get(c), e1 = event_get(c);
+  auto r = launch(e0, e1);
+  t->pending.emplace_back(e0, e1);
+  t->launches++;
+  return r;
+}
 // a start / stop event pair that is returned to the context's pool on every exit path
 struct EventPair {
   poro_ctx *c; hipEvent_t e0, e1;

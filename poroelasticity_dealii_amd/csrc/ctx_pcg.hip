@@ -23,9 +23,9 @@ namespace ctx_detail {
 // costs ONE all-reduce: z = P^-1 g, w = A z, then {g.z, w.z, g.g} in one reduction, then d = -z + beta d, s = -w + beta s (= A d), x += alpha d,
 // g += alpha s.  Per iteration: 1 operator application (1 grouped neighbour exchange) + the exchanges inside P^-1 + 1 all-reduce of 4 doubles.
 // The price is two more vector passes than pcg(), which is why single-rank runs keep the three-kernel recurrence.
-int pcg_single_reduction(poro_ctx *c, const std::function<bool(const double *, double *, double *)> &apply, int64_t n, int64_t plane, double *x, const double *b,
+int pcg_single_reduction(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, const double *b,
                          const DiagVec &diag, double *g, double *d, double *sv, const poro_solver_opts *opts, poro_solve_info *info,
-                         const std::function<bool(const double *, double *, double *)> *precond, int *its_hint) {
+                         const ApplyFn *precond, int *its_hint) {
   hipStream_t s = c->stream;
   const int which = n == c->n_u ? 0 : 1;
   if (c->cg1_w[which].n < (size_t)n) { c->cg1_w[which].alloc(n); c->cg1_z[which].alloc(n); }
@@ -78,9 +78,9 @@ int pcg_single_reduction(poro_ctx *c, const std::function<bool(const double *, d
 // precond != null: explicit preconditioner z = P^-1 g (a sequence of launches on the stream, e.g. the fast diagonalisation) written into
 // diag.z between the two update kernels; the scalars stay on the device exactly as in the Jacobi case.  precond(g, z, gz_partials) returns true
 // when it has already left the block partials of g . z (over the owned rows) in gz_partials.
-int pcg(poro_ctx *c, const std::function<bool(const double *, double *, double *)> &apply, int64_t n, int64_t plane, double *x, const double *b,
+int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, const double *b,
         const DiagVec &diag, double *g, double *d, double *h, const poro_solver_opts *opts, poro_solve_info *info,
-        const std::function<bool(const double *, double *, double *)> *precond, int *its_hint, bool precond_gated,
+        const ApplyFn *precond, int *its_hint, bool precond_gated,
         const FdmOct *oct /* single rank, explicit preconditioner: the residual and z = P^-1 g live in octant form (kernels_fdmo.hip), `g` is unused */) {
   static const bool two_reductions = std::getenv("PORO_TWO_REDUCTION_CG") != nullptr;    // A/B hook: the three-kernel recurrence on partitioned runs too
   if (c->comm.multi() && !two_reductions && !oct) return pcg_single_reduction(c, apply, n, plane, x, b, diag, g, d, h, opts, info, precond, its_hint);
@@ -245,7 +245,7 @@ int pcg_ilu0(poro_ctx *c, CsrDev &A, const double *val, DevBuf<double> &lu, bool
 
 // lambda_max(D^-1 A_u) from the Lanczos tridiagonal of 25 Jacobi-preconditioned CG steps on a synthetic right-hand side (the constrained rows are
 // inert): the largest Ritz value approaches lambda_max from below within a fraction of a percent, far faster than a power iteration
-double estimate_lmax_u(poro_ctx *c, const std::function<bool(const double *, double *, double *)> &apply, const DiagVec &dj) {
+double estimate_lmax_u(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj) {
   hipStream_t s = c->stream; const int64_t n = c->n_u, n_own = owned(c, n, c->comm.part.plane_u);
   std::vector<double> hv(n); for (int64_t i = 0; i < n; ++i) hv[i] = std::sin(0.731 * (double)i) + 0.3 * std::cos(0.013 * (double)i * (double)(i % 7));
   DevBuf<double> r, z, p, ap; r.upload(hv); z.alloc(n); p.alloc(n); ap.alloc(n);
