@@ -104,6 +104,7 @@ struct FdmOct {
   double coef[3][3] = {};
   DevBuf<double> fwd[3][3][2], bwd[3][3][2], lam[3][3][2];   // [component][direction][parity]: half-size transforms in MFMA fragment order [tile][4 nt][64], eigenvalues (inf = no such mode)
   DevBuf<double> g, z, t;                         // residual, preconditioned residual, scratch - all in octant form
+  DevBuf<double> gz_part; int gz_n = 0;           // octant form on one rank: per-workgroup partial sums of g . z left by transform pass 2 (one slot per workgroup of that launch)
   std::vector<double> h_lam[3][3][2];             // host copies of the eigenvalues
   DevBuf<double> bxy;                             // [component][py][px][my][mx] = coef_x lam_x[mx] + coef_y lam_y[my]: the part of the eigenvalue sum a z line shares (pass 2 reads it per column)
   // slab-partitioned form ("quadrant form"): only x and y are split into parities in the CG vectors, Q[c][q = 2 py + px][kz local][ky][kx] (no = 4 blocks per component);
@@ -377,7 +378,8 @@ void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t 
 void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int rank, const std::vector<int> &node_layers, bool has_upper, hipStream_t s);
 bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn);
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
-void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing
+void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
+                double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing
 // the same transform kernel for the scalar Q1 systems of a 3D box (nodal layout, one block set, no octants): 3 launches instead of 6
 bool fdmo_scalar_usable(int dim, const int nn[3]);
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s);
@@ -401,7 +403,8 @@ void fdmo_init_residual(hipStream_t s, const FdmOct &O, double *g_oct, const dou
 void fdmo_first_direction(hipStream_t s, const FdmOct &O, double *d, const double *g_oct, const double *z_oct, double *partials /*2 sets: gg, gz*/);
 // red != null (partitioned runs): the all-reduced d.h (update_g: red[0]) / g.g and g.z (update_d: red[0], red[1]) instead of the block partials
 void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, double *g_oct, const double *h, const uint8_t *inert, const double *partials_dh, double *partials_out /*gg*/, const double *red = nullptr);
-void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z_oct, const double *partials_in /*2 sets*/, const double *red = nullptr);
+void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z_oct, const double *partials_in /*2 sets*/, const double *red = nullptr,
+                   bool gz_from_pass = false /* g . z from O.gz_part (left by fdmo_apply) instead of the second set of partials_in */);
 void fdmo_dot_owned(hipStream_t s, const FdmOct &O, const double *a_oct, const double *b_oct, double *partials, const PcgScalars *gate);   // block partials of a.b over the planes this rank owns
 // slab form: the pieces of one application around the two all-to-alls (ctx_prec.hip drives them)
 void fdmo_slab_pass(hipStream_t s, const FdmOct &O, int pass /*1, 2, 3*/, const double *in, double *out, const PcgScalars *gate, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

@@ -322,29 +322,32 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
 
 // The three transform dispatches of the octant form.  A sampled call times them one by one (per-kernel roofline of the bench): the sampling runs on
 // fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
-void fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, const PcgScalars *gate) {
+// gz_part != null: pass 2 also leaves the partial sums of g . z there (returns true: no separate dot kernel)
+bool fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, const PcgScalars *gate, double *gz_part) {
   Timed tm(c, "precondition_u_fdm");
   const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
   if (!begin_sampled_dispatch(c, names[0])) {
-    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate);
-    return;
+    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, nullptr, gz_part);
+    return gz_part != nullptr;
   }
   c->timers[names[1]].enqueued++;
   c->timers[names[2]].enqueued++;
   hipEvent_t ev[6];
   for (auto &e : ev) e = event_get(c);
-  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev);
+  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev, gz_part);
   for (int k = 0; k < 3; ++k) {
     Timer &t = c->timers[names[k]];
     t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
     t.launches++;
   }
+  return gz_part != nullptr;
 }
 
 // z = blockdiag(A_cc)^-1 g by fast diagonalisation: the same device-controlled SolverCG recurrence with an explicit preconditioner vector
 int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
   build_fdm_u(c);
   const FdmOct *oct = c->fdm_oct.built ? &c->fdm_oct : nullptr;
+  const bool separate_gz = std::getenv("PORO_FDMO_SEPARATE_GZ") != nullptr;    // A/B hook, read once per solve: g . z by its own dot kernel, as before pass 2 produced it
   const ApplyFn P = [&](const double *g, double *z, double *in_iteration) {
     // g, z in octant form: three contiguous sweeps; inside the iteration the launches are gated on the device-side "solve finished" flag (before
     // pcg_scalars_start it still holds the previous solve's state)
@@ -357,7 +360,8 @@ int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts,
       Timed tm(c, "precondition_u_fdm");
       fdmo_apply_planar(c->stream, *oct, g, z, gate);
     } else {
-      fdm_u_octant_passes(c, *oct, g, z, gate);
+      // inside the iteration pass 2 leaves g . z (in oct->gz_part, which k_fdmo_update_d reads); the first application of a solve keeps k_fdmo_first_direction's dot
+      return fdm_u_octant_passes(c, *oct, g, z, gate, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
     }
     return false;
   };

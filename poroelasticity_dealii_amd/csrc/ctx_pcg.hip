@@ -77,7 +77,7 @@ int pcg_single_reduction(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t p
 // block partials (single rank, 3 launches per iteration incl. the operator) or from the all-reduced scalars (partitioned).
 // precond != null: explicit preconditioner z = P^-1 g (a sequence of launches on the stream, e.g. the fast diagonalisation) written into
 // diag.z between the two update kernels; the scalars stay on the device exactly as in the Jacobi case.  precond(g, z, gz_partials) returns true
-// when it has already left the block partials of g . z (over the owned rows) in gz_partials.
+// when it has already left the block partials of g . z (over the owned rows) in gz_partials (octant form on one rank: in oct->gz_part, see fdmo_update_d).
 int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, const double *b,
         const DiagVec &diag, double *g, double *d, double *h, const poro_solver_opts *opts, poro_solve_info *info,
         const ApplyFn *precond, int *its_hint, bool precond_gated,
@@ -129,12 +129,14 @@ int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, 
       if (multi) { pcg_scalars_sum(s, part_dh, 1, red); allreduce_sum(c, red, 1); }
       if (oct) fdmo_update_g(s, *oct, sc, (it - 1) & 1, g, h, diag.inert, part_dh, part, multi ? red : nullptr);
       else pcg_update_g_fused(s, sc, (it - 1) & 1, g, h, diag, prec, n, n_own, part_dh, multi ? red : nullptr, part);
-      if (precond && !(*precond)(g, zbuf, part + kMaxPartials)) {
+      const bool gz_left = precond && (*precond)(g, zbuf, part + kMaxPartials);
+      if (precond && !gz_left) {
         if (oct && multi) fdmo_dot_owned(s, *oct, g, zbuf, part + kMaxPartials, precond_gated ? sc : nullptr);
         else la_dot_partials(s, g, zbuf, oct ? oct->n_oct : n_own, part + kMaxPartials, precond_gated ? sc : nullptr);
       }
       if (multi) { pcg_scalars_sum(s, part, 2, red + 1); allreduce_sum(c, red + 1, 2); }
-      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr);
+      // (octant form: the transform passes leave their g . z partials in oct->gz_part - one per workgroup of pass 2, more than kMaxPartials - not in `part`)
+      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz_left);
       else pcg_update_d_fused(s, sc, (it - 1) & 1, it, x, d, g, diag, prec, n, part, multi ? red + 1 : nullptr);
     }
     post_and_wait(c, nullptr, 0, sc); hs = c->mailbox->sc;

@@ -60,10 +60,10 @@ __device__ inline void store_partial(double *partials, double v) {
   }
 }
 
-// sum of kMaxPartials block partials in a fixed order, broadcast to every thread of the block (identical bits in every block)
-__device__ inline double sum_partials(const double *p, double *sh /*[5]*/) {
+// sum of n block partials (default: the kMaxPartials slots of a capped grid) in a fixed order, broadcast to every thread of the block (identical bits in every block)
+__device__ inline double sum_partials(const double *p, double *sh /*[5]*/, int n = kMaxPartials) {
   double v = 0;
-  for (int i = threadIdx.x; i < kMaxPartials; i += kBlock) v += p[i];
+  for (int i = threadIdx.x; i < n; i += kBlock) v += p[i];
   v = block_sum(v, sh);
   if (threadIdx.x == 0) sh[4] = v;
   __syncthreads();

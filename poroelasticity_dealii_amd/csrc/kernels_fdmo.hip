@@ -200,10 +200,12 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
   if (blockIdx.x == 0 && threadIdx.x == 0) { sc->dh = dh; sc->alpha = alpha; }
 }
 // x += alpha d, then d = beta d - H' z unless the solve just finished (k_pcg_update_d_fused with the explicit z in octant form)
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red) {
+// g . z: the gz_n per-workgroup partials of transform pass 2 (gz_part != null), else the second set of partials_in (separate dot kernel)
+template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
+                                                                            const double *gz_part, int gz_n) {
   __shared__ double sh[5];
   if (sc->done) return;
-  const double gg = red ? red[0] : sum_partials(partials_in, sh), gz = red ? red[1] : sum_partials(partials_in + kMaxPartials, sh);
+  const double gg = red ? red[0] : sum_partials(partials_in, sh), gz = red ? red[1] : gz_part ? sum_partials(gz_part, sh, gz_n) : sum_partials(partials_in + kMaxPartials, sh);
   const double res = sqrt(gg), gh_old = sc->gh2[parity], alpha = sc->alpha;
   const bool conv = res <= sc->tol, fail = !conv && it >= sc->max_iter;
   if (blockIdx.x == 0 && threadIdx.x == 0) { sc->gg = gg; sc->gz = gz; sc->res = res; sc->it = it; }
@@ -285,6 +287,7 @@ struct OctPass {
   // global plane in the gathered buffer - the block is loaded as even / odd combination of a plane and its mirror image
   int slab_io, store_planes, ng, scols, col_unit, rank; float inv_scols; int64_t dest_stride, recv_off; const int64_t *row_in;
   int vec2;                     // rows are 16-byte aligned (even pitch, even chunk offsets): 16-byte block loads; 0: 8-byte loads (the scalar Q1 systems keep their nodal layout)
+  double *gz_part;              // octant form, pass 2 (GZ instantiations): one partial sum of g . z per workgroup, see the epilogue of the first GEMM
   const PcgScalars *gate;       // inside a PCG iteration: the launch is a no-op once the solve has finished (the host enqueues iterations ahead of the device-side stopping test)
   unsigned long long *stamps;   // diagnostic (PORO_FDMO_STAMPS): per block 8 words: 100 MHz time at start / block in LDS / GEMM 1 done / intermediate in LDS / GEMM 2 done / stored, HW_ID, XCC_ID
 };
@@ -309,9 +312,14 @@ template <int NT> struct PassGeom {
 // VAR = 0: the octant form on one rank (24 blocks, aligned rows, no exchange buffer, no per-block offsets) with those switches folded at compile time;
 // VAR = 1: the quadrant form of the displacement system on slabs (pass 1 stores into / pass 3 loads from the exchange buffer, pass 2 forms the parity parts on load), likewise;
 // VAR = 2: everything else by run-time switches (scalar systems, batched right-hand sides)
-template <int NT, int MODE, int VAR>
+// GZ (MODE = 1, VAR = 0 only): the pass also leaves g . z.  Per block z = B Lambda^-1 F g with B = F^T (fdmo_upload_dir), so sum Q_g Q_z = sum over the modes of
+// ghat^2 / den with ghat = (F x F x F) Q_g - which is what the accumulators hold after the first GEMM, next to the 1 / den that scales them.  Removed modes give
+// 1 / den = 0, pads are exact zeros and every tile of pass 2 belongs to one wave, so the workgroup's sum is its share of g . z: two FMAs per entry and one
+// 8-byte store, no extra load, no extra launch (P.gz_part[blockIdx.x]; k_fdmo_update_d adds the slots up in a fixed order)
+template <int NT, int MODE, int VAR, bool GZ = false>
 __global__ void __launch_bounds__(64 * pass_waves<NT>())
 k_fdmo_pass(OctPass P, const double *in, double *out) {
+  static_assert(!GZ || (MODE == 1 && VAR == 0), "g . z comes out of pass 2 of the single-rank octant form only");
   // (the kernel argument stays in the kernarg segment - a modified copy would live in scratch because of its dynamically indexed members)
   constexpr bool GENERAL = VAR == 2, SLAB = VAR == 1;
   const int f_vec2 = GENERAL ? P.vec2 : 1, f_slab_z = GENERAL ? P.slab_z : (SLAB && MODE == 1 ? 2 : 0), f_slab_io = GENERAL ? P.slab_io : (SLAB && MODE == 0 ? 1 : SLAB && MODE == 2 ? 2 : 0),
@@ -329,6 +337,7 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   constexpr int NS = EXTRA ? 2 : 1;                          // fragment streams per wave: its own tile row of T (and the shared one)
   constexpr int PADC = 16 * NL;                              // padded block columns
   extern __shared__ double L[];                              // PADN x LDMAX doubles (dynamic: more than 64 KB from NT = 6 on)
+  __shared__ double gz_wave[GZ ? NW : 1];                    // (referenced by the GZ instantiations only: the others allocate nothing for it)
   if (P.gate && (P.gate->done | P.gate->finishing)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
@@ -456,6 +465,7 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
     double lzw[4], lzx[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { lzw[q] = czc * lamz[16 * w + 4 * q + kq]; lzx[q] = EXTRA ? czc * lamz[16 * XT + 4 * q + kq] : 0.0; }
+    double gz = 0;                      // GZ: this thread's share of g . z
 #pragma unroll
     for (int a = 0; a < NACC; ++a) {
       int tr, tc; tile_of(a, tr, tc, false);
@@ -466,9 +476,15 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
         const double den = (a < NL ? lzw[q] : lzx[q]) + bxy;
         double r = __builtin_amdgcn_rcp(den);
         r = den < 1e300 ? fma(r, fma(-den, r, 1.0), r) : 0.0;
-        L[(16 * tr + 4 * q + kq) * LD2 + 16 * tc + j] = acc[a][q] * r;
+        const double zh = acc[a][q] * r;
+        L[(16 * tr + 4 * q + kq) * LD2 + 16 * tc + j] = zh;
+        if constexpr (GZ) gz = fma(acc[a][q], zh, gz);
         __builtin_amdgcn_sched_barrier(0);
       }
+    }
+    if constexpr (GZ) {                 // wave sums -> LDS; the barrier in front of the second GEMM publishes them
+      gz = wave_sum(gz);
+      if (lane == 0) gz_wave[w] = gz;
     }
   } else {
 #pragma unroll
@@ -482,6 +498,9 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   zero_acc();
   __syncthreads();
   stamp(3);
+  if constexpr (GZ) {
+    if (tid == 0) { double t = 0; for (int k = 0; k < NW; ++k) t += gz_wave[k]; P.gz_part[blockIdx.x] = t; }   // fixed order: bitwise reproducible
+  }
   if (heavy) gemm(CS{}, L2c{}, S1c{}, std::integral_constant<bool, CORNER>{}, P.kk2); else gemm(CS{}, L2c{}, S1c{}, std::false_type{}, P.kk2);
   if (P.stamps) { __syncthreads(); stamp(4); }
   // ---- store ----
@@ -734,9 +753,9 @@ template <int NT> void launch_zpass_both(hipStream_t s, const OctPass &P, const 
 }
 
 // one instantiation: dynamic LDS (more than 64 KB from NT = 6 on: opted in once per device), events attached to the dispatch itself (the kernel's own duration, as rocprofv3 reports it)
-template <int NT, int MODE, int VAR> void launch_one(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+template <int NT, int MODE, int VAR, bool GZ = false> void launch_one(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
   constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(double));
-  auto kernel = k_fdmo_pass<NT, MODE, VAR>;
+  auto kernel = k_fdmo_pass<NT, MODE, VAR, GZ>;
   if (lds > 64 * 1024) {
     static std::mutex mu; static std::set<int> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
@@ -749,7 +768,9 @@ template <int NT> void launch_pass(hipStream_t s, const OctPass &P, int n_items,
   const bool oct = plain && P.slab_z == 0 && P.slab_io == 0 && !P.row_in && P.no_shift == 3;
   const bool slab_u = plain && P.no_shift == 2 && ((P.mode == 0 && P.slab_io == 1 && !P.slab_z) || (P.mode == 1 && P.slab_z == 2 && P.row_in && !P.slab_io) || (P.mode == 2 && P.slab_io == 2 && !P.slab_z));
   if (oct) {
-    if (P.mode == 0) launch_one<NT, 0, 0>(s, n_items, P, in, out, e0, e1); else if (P.mode == 1) launch_one<NT, 1, 0>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 2, 0>(s, n_items, P, in, out, e0, e1);
+    if (P.mode == 0) launch_one<NT, 0, 0>(s, n_items, P, in, out, e0, e1);
+    else if (P.mode == 1) { if (P.gz_part) launch_one<NT, 1, 0, true>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 1, 0>(s, n_items, P, in, out, e0, e1); }
+    else launch_one<NT, 2, 0>(s, n_items, P, in, out, e0, e1);
   } else if (slab_u) {
     if (P.mode == 0) launch_one<NT, 0, 1>(s, n_items, P, in, out, e0, e1); else if (P.mode == 1) launch_one<NT, 1, 1>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 2, 1>(s, n_items, P, in, out, e0, e1);
   } else {
@@ -791,6 +812,9 @@ void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t 
   O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = 24 * O.co_stride; O.no = 8; O.own_z = O.n[2];
   O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct);
   O.g.zero(s); O.z.zero(s); O.t.zero(s);
+  const int cw = pass2_chunk(O.nt);
+  O.gz_n = 24 * ((O.hxp * O.h[1] + cw - 1) / cw);       // workgroups of pass 2: one g . z partial each (grows with the box - not bounded by kMaxPartials)
+  O.gz_part.alloc(O.gz_n); O.gz_part.zero(s);
 }
 // chunks, shares, plane tables and buffers of the slab form, after n / h / hxp / nt / co_stride are set: nb blocks per plane position set, np parity parts of a z line
 static void slab_layout(FdmOct &O, int nb, int np, int rank, const std::vector<int> &node_layers, hipStream_t s) {
@@ -882,7 +906,7 @@ void fdmo_finalize(FdmOct &O) {
   O.bxy.upload(B);
 }
 
-void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev) {
+void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part) {
   static int stamp_calls = 0; const char *stamp_path = std::getenv("PORO_FDMO_STAMPS");
   const bool stamping = stamp_path && ++stamp_calls == 3;          // diagnostic: the third application of the process writes its per-block time stamps
   DevBuf<unsigned long long> stamps; std::vector<std::pair<int, int64_t>> stamp_off;
@@ -904,7 +928,10 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
   P.mode = 1; P.R = hz; P.C = cw; P.nt_r = tiles(hz); P.nt_c = cw / 16; P.kk1 = ksteps(hz); P.kk2 = ksteps(hz); P.nblk = (hxp * hy + cw - 1) / cw; P.blk_stride = cw; P.row_stride = (int64_t)hxp * hy; P.bit1 = 2; P.bit2 = 2;
   for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.fwd[c][2][p].p; P.T2[c][p] = O.bwd[c][2][p].p; }
   if (stamping) P.stamps = stamps.p + 8 * (int64_t)(24 * hz); stamp_off.push_back({24 * P.nblk, 8 * (int64_t)(24 * hz)});
+  if (gz_part && 24 * P.nblk != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
+  P.gz_part = gz_part;
   launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, scratch, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
+  P.gz_part = nullptr;
   // pass 3: per z-plane, X[my][mx] -> (By X) Bx^T
   P.mode = 2; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hy); P.kk2 = ksteps(hx); P.nblk = hz; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp; P.bit1 = 1; P.bit2 = 0;
   for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.bwd[c][1][p].p; P.T2[c][p] = O.bwd[c][0][p].p; }
@@ -1124,8 +1151,8 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
   if (single) PORO_OCT_LAUNCH(k_fdmo_update_g, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
   else PORO_OCT_LAUNCH(k_fdmo_update_g2, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
 }
-void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red) {
-  PORO_OCT_LAUNCH(k_fdmo_update_d, O, sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red);
+void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass) {
+  PORO_OCT_LAUNCH(k_fdmo_update_d, O, sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red, gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0);
 }
 
 }  // namespace poro

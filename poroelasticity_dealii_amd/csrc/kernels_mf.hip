@@ -204,7 +204,9 @@ k_p_residual_stencil(int n0, int n1, int n2, double h0, double h1, double h2, do
                      const double *__restrict__ src, double *__restrict__ R) {
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= (int64_t)n0 * n1 * n2) return;
-  const double s1 = p_stencil_row<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, t), s2 = p_stencil_row<DIM>(n0, n1, n2, h0, h1, h2, 0.0, 1.0, node, p);
+  PStencilTaps<DIM> Tt, Tp;               // the loads of both stencils are in flight before either is summed
+  p_stencil_load<DIM>(n0, n1, n2, node, t, Tt); p_stencil_load<DIM>(n0, n1, n2, node, p, Tp);
+  const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 0.0, 1.0, node, Tp);
   R[node] = -((s1 + s2 * kappa) + src[node]);
 }
 void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R) {
