@@ -276,6 +276,20 @@ void poro_ctx_destroy(poro_ctx *ctx);
 /* wait until the device has finished everything the context has enqueued (see the note on synchronisation at the top) */
 int  poro_ctx_synchronize(poro_ctx *ctx);
 
+/* Scatter mode of the matrix-free operator on GENERAL meshes (no box tag): how the cell loop adds its contributions into y = A_u x.
+ *   PORO_SCATTER_COLOURED (default): one launch per colour class (2^dim), plain read-modify-write, bitwise reproducible.
+ *   PORO_SCATTER_ATOMIC:             ONE launch over all cells, fp64 atomic adds; the results differ in the last bits from run to run.
+ * May be changed between any two calls; governs every application of the operator (Krylov operator, Chebyshev polynomial, two-level fine-level products, partitions,
+ * condensation, poro_apply_operator / poro_bench_operator).  The set-up quantities (diagonal, lifting vector, the product with the constraints' inhomogeneities in the
+ * condensed right-hand side, self-checks) stay coloured in both modes: PORO_VEC_DIAG_U and PORO_VEC_RHS_U do not depend on the mode, bit for bit.  The cell list of
+ * the single launch (4 bytes per cell) is built on the host from the cell vertices when a context enters the atomic mode for the first time (a stream synchronise, a
+ * device-to-host copy of the vertices and a sort: call it outside timed regions; under the environment variable below the first operator application pays for it).  On a box-tagged
+ * context the call succeeds and changes nothing (the structured kernels have no scatter).  An unknown mode returns < 0.  The environment variable
+ * PORO_MFG_SCATTER=atomic|coloured (diagnostic) is read once, at context creation, as the initial mode. */
+enum { PORO_SCATTER_COLOURED = 0, PORO_SCATTER_ATOMIC = 1 };
+int  poro_ctx_set_scatter_mode(poro_ctx *ctx, int32_t mode);
+int  poro_ctx_get_scatter_mode(poro_ctx *ctx, int32_t *mode);
+
 /* multi-GPU wiring.  id is the 128-byte ncclUniqueId from rank 0. */
 int  poro_comm_unique_id(void *id128);
 int  poro_ctx_comm_init_rccl(poro_ctx *ctx, const void *id128);

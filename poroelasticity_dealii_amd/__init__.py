@@ -17,6 +17,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 PREC_NONE, PREC_JACOBI, PREC_SSOR, PREC_FDM, PREC_ILU0, PREC_CHEBYSHEV, PREC_TWO_LEVEL = 0, 1, 2, 3, 4, 5, 6
 STOP_RHS, STOP_REDUCTION = 0, 1
 OP_CSR, OP_MATRIX_FREE = 0, 1
+SCATTER_COLOURED, SCATTER_ATOMIC = 0, 1
 MAT_A_U, MAT_MASS_P, MAT_LAPLACE_P, MAT_JACOBIAN_P = 0, 1, 2, 3
 VEC_U, VEC_RHS_U, VEC_P, VEC_P_OLD, VEC_DP, VEC_RESIDUAL_P, VEC_EPSV, VEC_EPSV0, VEC_SOURCE_P = range(9)
 VEC_STRAIN0, VEC_PROJ_RHS0, VEC_DIAG_U, VEC_STRESS0 = 16, 32, 48, 64
@@ -98,7 +99,7 @@ SENDRECV_FN = C.CFUNCTYPE(None, _dp, _dp, C.c_int64, C.c_int32, C.c_void_p)
 
 # every symbol include/poroel_hip.h declares (checked by the CPU test-suite against the built library)
 HIP_SYMBOLS = [
-    "poro_last_error", "poro_abi_version", "poro_ctx_create", "poro_ctx_destroy", "poro_ctx_synchronize", "poro_comm_unique_id", "poro_ctx_comm_init_rccl",
+    "poro_last_error", "poro_abi_version", "poro_ctx_create", "poro_ctx_destroy", "poro_ctx_synchronize", "poro_ctx_set_scatter_mode", "poro_ctx_get_scatter_mode", "poro_comm_unique_id", "poro_ctx_comm_init_rccl",
     "poro_ctx_comm_init_callbacks", "poro_vec_set", "poro_vec_get", "poro_vec_fill", "poro_vec_copy", "poro_vec_axpy", "poro_vec_norm",
     "poro_state_save", "poro_state_restore", "poro_disp_assemble_system", "poro_disp_solve", "poro_supports_preconditioner", "poro_pres_assemble_residual", "poro_pres_apply_boundary_values", "poro_pres_assemble_jacobian", "poro_pres_solve",
     "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
@@ -124,6 +125,8 @@ def load_hip():
         L.poro_ctx_destroy.argtypes = [C.c_void_p]
         L.poro_ctx_destroy.restype = None
         L.poro_ctx_synchronize.argtypes = [C.c_void_p]
+        L.poro_ctx_set_scatter_mode.argtypes = [C.c_void_p, C.c_int32]
+        L.poro_ctx_get_scatter_mode.argtypes = [C.c_void_p, _ip]
         L.poro_comm_unique_id.argtypes = [C.c_void_p]
         L.poro_ctx_comm_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
         L.poro_ctx_comm_init_callbacks.argtypes = [C.c_void_p, ALLREDUCE_FN, SENDRECV_FN, C.c_void_p]
@@ -354,6 +357,16 @@ class Context:
         """wait for everything the context has enqueued (device-only entry points are stream-ordered)"""
         self._chk(self.L.poro_ctx_synchronize(self.ptr))
 
+    def set_scatter_mode(self, mode):
+        """SCATTER_COLOURED (default: one launch per colour class, bitwise reproducible) or SCATTER_ATOMIC (one launch, fp64 atomic adds, last bits differ from run
+        to run) for the matrix-free operator on general meshes; a no-op on box-tagged contexts"""
+        self._chk(self.L.poro_ctx_set_scatter_mode(self.ptr, int(mode)))
+
+    def get_scatter_mode(self):
+        m = C.c_int32()
+        self._chk(self.L.poro_ctx_get_scatter_mode(self.ptr, C.byref(m)))
+        return m.value
+
     def _len(self, which):
         return self.n_u if which in (VEC_U, VEC_RHS_U, VEC_DIAG_U) else self.n_p
 
@@ -509,13 +522,14 @@ def rccl_unique_id():
 
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
-                abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False):
+                abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
+                atomic_scatter=False):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context)."""
     H = load_host()
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
-    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                            trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
     if rows < 0:
         raise RuntimeError(H.poro_host_last_error().decode())
@@ -529,10 +543,11 @@ class Runner:
     """Steppable PoroElasticProblem<dim> (C++ host driver): initialize() = PoroelasticityFSS.h:308-317, step() = one pass of :328-407."""
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
-                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False):
+                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
+                 atomic_scatter=False):
         self.H = load_host()
         self.max_fss = max_fss
-        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
+        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
         if not h:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         self.h = C.c_void_p(h)

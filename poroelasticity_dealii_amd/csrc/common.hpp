@@ -197,6 +197,9 @@ struct poro_ctx {
   poro::FeTablesDev fe{};
   int mfg_sf = 0;                            // poro_desc.fe holds the Gauss(k+1) / equidistant-Lagrange tables the sum-factorised general kernels hard-code (kernels_mfg.hip)
   std::vector<int64_t> color_off;            // host offsets into color_cells
+  // scatter mode of the general cell-loop operator (poro_ctx_set_scatter_mode).  spatial_cells: all cells in Morton order of their centroids, built the first time the
+  // context enters the atomic mode
+  int scatter_mode = 0; poro::DevBuf<int32_t> spatial_cells;
   poro::DevBuf<uint8_t> dir_mask, node_mask; poro::DevBuf<double> dir_val; poro::DevBuf<int32_t> dir_dofs;
   std::vector<int32_t> h_dir_dof; std::vector<double> h_dir_val;
   poro::ConsDev cons_u, cons_p;
@@ -332,9 +335,10 @@ void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *u, int n_comp, const int32_t *comps /*host*/,
                   double *const *rhs /*host array of device ptrs*/);
 
-// ---- kernels_mfg.hip: matrix-free operator on general meshes (one wave per cell, coloured scatter) ----------------
+// ---- kernels_mfg.hip: matrix-free operator on general meshes (one wave per cell; coloured scatter, or one launch with an atomic scatter) ----------------
 bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k);
-void mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode);
+int mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
+              const int32_t *all_cells = nullptr /* non-null: ONE launch over this list of all cells with an atomic scatter (mode 0) */);
 // ---- kernels_mf.hip -----------------------------------------------------------------------------
 struct MfArgs { int dim, k_u; BoxDev box; const double *Ke; const uint8_t *mask; const double *diag_local; double lam, G; int mask_anywhere; const uint8_t *nodemask; const int32_t *dirichlet_dofs; int64_t n_dirichlet; };
 void mf_apply(hipStream_t s, const MfArgs &a, const double *x, double *y, bool constrained, double *dot_partials = nullptr);

@@ -563,9 +563,30 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       c->two_level.box = box;
       setup_two_level(c.get(), desc);
     }
+    // diagnostic switch, read once here: the initial scatter mode of the general operator
+    if (const char *v = std::getenv("PORO_MFG_SCATTER")) {
+      const std::string m(v);
+      if (m != "atomic" && m != "coloured") throw Error("PORO_MFG_SCATTER: atomic or coloured");
+      if (m == "atomic" && !c->box.enabled) c->scatter_mode = PORO_SCATTER_ATOMIC;
+    }
     *out = c.release();
     return 0;
   });
+}
+
+int poro_ctx_set_scatter_mode(poro_ctx *c, int32_t mode) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    if (mode != PORO_SCATTER_COLOURED && mode != PORO_SCATTER_ATOMIC) throw Error("poro_ctx_set_scatter_mode: unknown mode " + std::to_string(mode) + " (PORO_SCATTER_COLOURED or PORO_SCATTER_ATOMIC)");
+    if (c->box.enabled) return 0;   // the structured kernels have no scatter: nothing to select
+    PORO_HIP(hipSetDevice(c->device));
+    if (mode == PORO_SCATTER_ATOMIC && c->operator_mode == PORO_OP_MATRIX_FREE) build_spatial_cells(c);   // (a CSR context that applies the matrix-free operator builds it then)
+    c->scatter_mode = mode;
+    return 0;
+  });
+}
+int poro_ctx_get_scatter_mode(poro_ctx *c, int32_t *mode) {
+  return guarded([&] { if (!c || !mode) throw Error("null argument"); *mode = c->scatter_mode; return 0; });
 }
 
 void poro_ctx_destroy(poro_ctx *c) {
@@ -710,8 +731,9 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         la_csr_diag(s, c->Au, c->Au_val.p, c->diag_u_local.p);
       } else if (!c->box.enabled) {
         // general mesh, matrix-free: the diagonal and the lifting -(A_full g) come from the same quadrature-level cell loop
-        mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, nullptr, c->diag_u_local.p, false, 1);
-        mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->dir_val.p, c->wh_u.p, false, 0);
+        // (coloured in either scatter mode: assembled data stay bitwise stable)
+        count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, nullptr, c->diag_u_local.p, false, 1));
+        count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->dir_val.p, c->wh_u.p, false, 0));
         lifting_from_wh(c);
       } else {
         asm_u_element_matrix(s, a, 0, c->Ke.p);
@@ -749,7 +771,11 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
       if (c->cons_u.any_inhom) {
         la_fill(s, c->wd_u.p, 0.0, c->n_u); la_cons_expand(s, c->cons_u, c->wd_u.p, true);
         if (c->operator_mode == PORO_OP_CSR) la_csr_spmv(s, c->Au, c->Au_val.p, c->wd_u.p, c->wh_u.p);
-        else mf_operator(c, c->wd_u.p, c->wh_u.p, true);
+        else if (!c->box.enabled) {
+          // general mesh: a set-up quantity like the lifting above, so coloured in either scatter mode (VEC_RHS_U stays bitwise stable); otherwise as mf_operator
+          count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->wd_u.p, c->wh_u.p, true, 0));
+          kron_fix_constrained(s, mf_args(c), c->wd_u.p, c->wh_u.p, nullptr, 0);
+        } else mf_operator(c, c->wd_u.p, c->wh_u.p, true);
         la_mask_zero(s, c->wh_u.p, c->dir_mask.p, c->n_u);
         la_axpy(s, rhs, -1.0, c->wh_u.p, c->n_u);
       }

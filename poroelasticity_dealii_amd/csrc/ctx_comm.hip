@@ -229,10 +229,52 @@ MfArgs mf_args(poro_ctx *c) {
   a.lam = c->mat.lame_lambda; a.G = c->mat.shear_G; a.mask_anywhere = c->mask_anywhere;
   a.nodemask = c->node_mask.p; a.dirichlet_dofs = c->dir_dofs.p; a.n_dirichlet = (int64_t)c->dir_dofs.n; return a;
 }
+// all cells in Morton order of their (quantised) centroids: a workgroup of the single atomic launch then holds neighbouring cells, whose shared nodes meet in L2.
+// 4 bytes per cell, built from cell_X the first time the context enters the atomic mode: poro_ctx_set_scatter_mode builds it; under PORO_MFG_SCATTER=atomic the first
+// operator application does, and so carries a stream synchronise, the copy of cell_X to the host (192 bytes per 3D cell) and a host sort
+void build_spatial_cells(poro_ctx *c) {
+  if (c->spatial_cells.p || !c->n_cells) return;
+  const int dim = c->dim, nv = c->nv; const int64_t nc = c->n_cells;
+  std::vector<double> X((size_t)nc * nv * dim), ctr((size_t)nc * dim);
+  PORO_HIP(hipStreamSynchronize(c->stream));
+  PORO_HIP(hipMemcpy(X.data(), c->cell_X.p, X.size() * sizeof(double), hipMemcpyDeviceToHost));
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (int64_t k = 0; k < nc; ++k)
+    for (int d = 0; d < dim; ++d) {
+      double m = 0; for (int v = 0; v < nv; ++v) m += X[((size_t)k * nv + v) * dim + d];
+      m /= nv; ctr[(size_t)k * dim + d] = m; lo[d] = std::min(lo[d], m); hi[d] = std::max(hi[d], m);
+    }
+  const int bits = dim == 3 ? 21 : 31;
+  std::vector<std::pair<uint64_t, int32_t>> key(nc);
+  for (int64_t k = 0; k < nc; ++k) {
+    uint64_t q[3] = {0, 0, 0}, m = 0;
+    for (int d = 0; d < dim; ++d) { const double w = hi[d] - lo[d]; q[d] = w > 0 ? (uint64_t)((ctr[(size_t)k * dim + d] - lo[d]) / w * (double)((1ull << bits) - 1)) : 0; }
+    for (int b = 0; b < bits; ++b) for (int d = 0; d < dim; ++d) m |= ((q[d] >> b) & 1ull) << (b * dim + d);
+    key[k] = {m, (int32_t)k};
+  }
+  std::sort(key.begin(), key.end());
+  std::vector<int32_t> cells(nc);
+  for (int64_t k = 0; k < nc; ++k) cells[k] = key[k].second;
+  c->spatial_cells.upload(cells);
+}
+
+// the general cell-loop operator y = A_u x in the context's scatter mode (set-up quantities call mfg_apply directly and stay coloured)
+void mfg_operator(poro_ctx *c, const double *x, double *y, bool constrained) {
+  const int32_t *all = nullptr;
+  if (c->scatter_mode == PORO_SCATTER_ATOMIC) {
+    // diagnostic PORO_MFG_ATOMIC_ORDER=colour: the single launch over the colour-sorted list instead (A/B of the cell order, profiles/mfg_atomic_scatter.json)
+    static const bool colour_order = std::getenv("PORO_MFG_ATOMIC_ORDER") && std::string(std::getenv("PORO_MFG_ATOMIC_ORDER")) == "colour";
+    if (colour_order && !c->color_off.empty()) all = c->color_cells.p + c->color_off.front();
+    else { build_spatial_cells(c); all = c->spatial_cells.p; }
+  }
+  count_mfg_launches(c, mfg_apply(c->stream, asm_args(c), c->color_cells.p, c->color_off, c->n_u, x, y, constrained, 0, all));
+}
+void count_mfg_launches(poro_ctx *c, int n) { if (c->timing) c->timers["mfg_cell_kernels"].enqueued += n; }
+
 // y = A_u x without forming A_u: sum-factorised sweeps where available, element-matrix gather otherwise
 void mf_operator(poro_ctx *c, const double *x, double *y, bool constrained) {
   if (!c->box.enabled) {   // general mesh: quadrature-level cell loop; the Dirichlet rows from the constraint list as for the structured kernels
-    mfg_apply(c->stream, asm_args(c), c->color_cells.p, c->color_off, c->n_u, x, y, constrained, 0);
+    mfg_operator(c, x, y, constrained);
     if (constrained) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, 0);
     return;
   }
@@ -261,7 +303,7 @@ bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_pa
     if (fix_rows) { Timed tm(c, "apply_u_dirichlet_rows"); kron_fix_constrained(c->stream, mf_args(c), x, y, fused ? dot_partials : nullptr, slots > 0 ? slots : -slots); }
   } else if (mode == PORO_OP_MATRIX_FREE && !c->box.enabled) {
     Timed tm(c, "apply_u_matrix_free");
-    mfg_apply(c->stream, asm_args(c), c->color_cells.p, c->color_off, c->n_u, x, y, true, 0);
+    mfg_operator(c, x, y, true);
     if (fix_rows) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, 0);
   } else {
     Timed tm(c, mode == PORO_OP_MATRIX_FREE ? "apply_u_matrix_free" : "apply_u_csr");

@@ -70,6 +70,9 @@ int64_t owned(poro_ctx *c, int64_t n, int64_t plane);
 AsmArgs asm_args(poro_ctx *c);
 MfArgs mf_args(poro_ctx *c);
 void mf_operator(poro_ctx *c, const double *x, double *y, bool constrained);
+void mfg_operator(poro_ctx *c, const double *x, double *y, bool constrained);   // general cell loop, mode 0, in the context's scatter mode
+void build_spatial_cells(poro_ctx *c);
+void count_mfg_launches(poro_ctx *c, int n);                                   // timer family "mfg_cell_kernels": cell-loop kernel launches of mfg_apply (a count, no time)
 double *vec(poro_ctx *c, int which);
 int64_t vec_len(poro_ctx *c, int which);
 bool is_u_vec(int which);

@@ -8,6 +8,8 @@
 // matrix, no element matrix in memory.  Cells are processed colour by colour (no two cells of a colour share a dof), so the scatter is
 // a plain read-modify-write: no atomics, bitwise reproducible.  Dirichlet columns are masked on load; the Dirichlet ROWS are left to the
 // caller (inert inside PCG; poro_apply_operator finishes them from the constraint list).
+// Second scatter mode (opt-in, poro_ctx_set_scatter_mode): ONE launch over all cells, the final y[dof] += v a relaxed agent-scope fp64 atomic add
+// (global_atomic_add_f64).  Everything before the scatter is the same code; the sums then differ in the last bits from run to run.
 #include "common.hpp"
 #include <algorithm>
 #include <cmath>
@@ -42,8 +44,14 @@ template <int DIM> __device__ inline double jac_inv(const double *X, const doubl
 
 constexpr int kMaxNq = 27, kMaxDpc = 81;
 
-// mode 0: y += A x (cells of one colour); mode 1: y += diag(A)
-template <int DIM> __global__ void __launch_bounds__(64)
+// scatter forms of the cell kernels: the coloured read-modify-write; the atomic add, each lane adding its own node's components (lanes 8 * dim bytes apart)
+// (kScatterAtomicTransposed, 3D sum-factorised kernels only, diagnostic PORO_MFG_ATOMIC_SHAPE=transposed: node-major, component-minor through LDS, lanes 8 bytes apart
+// within a node; measured against the direct form in profiles/mfg_atomic_scatter.json)
+enum { kScatterColoured = 0, kScatterAtomic = 1, kScatterAtomicTransposed = 2 };
+__device__ __forceinline__ void atomic_add_f64(double *p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// mode 0: y += A x (cells of one colour; ATOMIC: any cells); mode 1: y += diag(A).  Lane i holds entry i of the cell's dof list, so the atomic form is already dof-list ordered
+template <int DIM, bool ATOMIC = false> __global__ void __launch_bounds__(64)
 k_mfg(AsmArgs a, const int32_t *__restrict__ cells, const double *__restrict__ x, double *__restrict__ y, int constrained, int mode) {
   constexpr int NV = 1 << DIM;
   __shared__ double sX[NV * DIM], sU[kMaxDpc], sJi[kMaxNq * DIM * DIM], sJxW[kMaxNq], sS[kMaxNq * DIM * DIM];
@@ -117,7 +125,7 @@ k_mfg(AsmArgs a, const int32_t *__restrict__ cells, const double *__restrict__ x
         acc = fma(sJxW[q], lam * gx[c] * gx[c] + G * (n2 + gx[c] * gx[c]), acc);
       }
     }
-    y[sDof[i]] += acc;
+    if constexpr (ATOMIC) atomic_add_f64(&y[sDof[i]], acc); else y[sDof[i]] += acc;
   }
 }
 
@@ -131,7 +139,7 @@ struct Sf1D { double N[3][3], D[3][3], w[3], xi[3]; };   // [quadrature point][n
 // every exchange of the sum-factorised kernel stays inside one cell's lanes, i.e. inside one wavefront (32 or 8 lanes per cell): LDS operations of a wave complete in
 // issue order, so a compiler-level fence replaces the workgroup barrier and the four waves of a workgroup drift apart freely (645 -> 626 us at 72^3 cells)
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-template <int N1, bool AFFINE>
+template <int N1, bool AFFINE, int SC = kScatterColoured>
 __global__ void __launch_bounds__(256)
 k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, const double *__restrict__ x, double *__restrict__ y, int constrained) {
   constexpr int NP = N1 * N1 * N1, LPC = N1 == 3 ? 32 : 8, CPW = 256 / LPC;
@@ -276,14 +284,21 @@ k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
       double v = 0;
 #pragma unroll
       for (int m = 0; m < N1; ++m) { const int at = m + N1 * (j + N1 * k); v = fma(T.D[m][i], sA[cs][2 * c][at], v); v = fma(T.N[m][i], sA[cs][2 * c + 1][at], v); }
-      if (!dir[c]) y[dof[c]] += v;
+      if constexpr (SC == kScatterColoured) { if (!dir[c]) y[dof[c]] += v; }
+      else if constexpr (SC == kScatterAtomic) { if (!dir[c]) atomic_add_f64(&y[dof[c]], v); }
+      else { (&sU[cs][0][0])[3 * p + c] = v; reinterpret_cast<int32_t *>(&sB[cs][0][0])[3 * p + c] = dir[c] ? -1 : dof[c]; }   // sU, sB: free since the sweeps
     }
+  }
+  if constexpr (SC == kScatterAtomicTransposed) {          // through the cell's LDS rows: consecutive lanes add consecutive entries of the cell's dof list
+    wave_sync();
+    if (slot < n_cells)
+      for (int e = p; e < 3 * NP; e += LPC) { const int32_t d = reinterpret_cast<const int32_t *>(&sB[cs][0][0])[e]; if (d >= 0) atomic_add_f64(&y[d], (&sU[cs][0][0])[e]); }
   }
 }
 
 
 // ---- the same for quadrilaterals (2D, Q1 / Q2): 16 lanes per Q2 cell (9 points), 4 per Q1 cell; 16 / 64 cells per workgroup -----------------------------------------
-template <int N1>
+template <int N1, int SC = kScatterColoured>
 __global__ void __launch_bounds__(256)
 k_mfg2_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, const double *__restrict__ x, double *__restrict__ y, int constrained) {
   constexpr int NP = N1 * N1, LPC = N1 == 3 ? 16 : 4, CPW = 256 / LPC;
@@ -377,7 +392,8 @@ k_mfg2_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
       double v = 0;
 #pragma unroll
       for (int m = 0; m < N1; ++m) { v = fma(T.D[m][i], sA[cs][2 * c][m + N1 * j], v); v = fma(T.N[m][i], sA[cs][2 * c + 1][m + N1 * j], v); }
-      if (!dir[c]) y[dof[c]] += v;
+      if constexpr (SC == kScatterColoured) { if (!dir[c]) y[dof[c]] += v; }
+      else if (!dir[c]) atomic_add_f64(&y[dof[c]], v);
     }
   }
 }
@@ -432,33 +448,52 @@ bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k) {
   return true;
 }
 
-// y = A_u x (mode 0) or y = diag(A_u) (mode 1) over the colour classes; y is zeroed here
-void mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode) {
+namespace {
+// one launch of the cell kernel that fits the mesh over `nc` cells of the list `cells`
+template <int SC>
+void launch_cells(hipStream_t s, const AsmArgs &a, bool sf, const Sf1D &T, const int32_t *cells, int64_t nc, const double *x, double *y, int constrained, int mode) {
+  if (sf && a.dim == 2) {
+    constexpr int SC2 = SC == kScatterAtomicTransposed ? kScatterAtomic : SC;
+    const int cpw = a.k_u == 2 ? 16 : 64; const unsigned grid = (unsigned)((nc + cpw - 1) / cpw);
+    if (a.k_u == 2) hipLaunchKernelGGL((k_mfg2_sf<3, SC2>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+    else hipLaunchKernelGGL((k_mfg2_sf<2, SC2>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+  } else if (sf) {
+    const int cpw = a.k_u == 2 ? 8 : 32; const unsigned grid = (unsigned)((nc + cpw - 1) / cpw);
+    if (a.k_u == 2 && a.cell_geo) hipLaunchKernelGGL((k_mfg3_sf<3, true, SC>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+    else if (a.k_u == 2) hipLaunchKernelGGL((k_mfg3_sf<3, false, SC>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+    else if (a.cell_geo) hipLaunchKernelGGL((k_mfg3_sf<2, true, SC>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+    else hipLaunchKernelGGL((k_mfg3_sf<2, false, SC>), grid, 256, 0, s, a, T, cells, (int)nc, x, y, constrained);
+  } else if (a.dim == 2) hipLaunchKernelGGL((k_mfg<2, SC != kScatterColoured>), (unsigned)nc, 64, 0, s, a, cells, x, y, constrained, mode);
+  else hipLaunchKernelGGL((k_mfg<3, SC != kScatterColoured>), (unsigned)nc, 64, 0, s, a, cells, x, y, constrained, mode);
+}
+}  // namespace
+
+// y = A_u x (mode 0) or y = diag(A_u) (mode 1); y is zeroed here.  all_cells == null: over the colour classes, one launch each (bitwise reproducible).
+// all_cells != null (mode 0 only): one launch over that list of all cells in any order, atomic scatter.  Returns the cell-kernel launches
+int mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
+              const int32_t *all_cells) {
   if (a.fe.nq_u > kMaxNq || a.dpc_u > kMaxDpc) throw Error("mfg_apply: element too large");
+  if (all_cells && mode != 0) throw Error("mfg_apply: the atomic scatter is for mode 0");
   PORO_HIP(hipMemsetAsync(y, 0, n_u * sizeof(double), s));
   static const bool no_sf = std::getenv("PORO_MFG_NO_SUMFAC") != nullptr;
   const bool sf = (a.dim == 3 || a.dim == 2) && mode == 0 && !no_sf && (a.k_u == 1 || a.k_u == 2) && a.mfg_sf;
   const Sf1D T = sf ? sf_tables(a.k_u) : Sf1D{};
+  if (all_cells) {
+    const int64_t nc = color_off.empty() ? 0 : color_off.back() - color_off.front();
+    if (!nc) return 0;
+    static const bool transposed = std::getenv("PORO_MFG_ATOMIC_SHAPE") && std::string(std::getenv("PORO_MFG_ATOMIC_SHAPE")) == "transposed";
+    if (transposed && sf && a.dim == 3) launch_cells<kScatterAtomicTransposed>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);
+    else launch_cells<kScatterAtomic>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);
+    return 1;
+  }
+  int launches = 0;
   for (size_t k = 0; k + 1 < color_off.size(); ++k) {
     const int64_t nc = color_off[k + 1] - color_off[k];
     if (!nc) continue;
-    if (sf && a.dim == 2) {
-      const int cpw = a.k_u == 2 ? 16 : 64;
-      if (a.k_u == 2) hipLaunchKernelGGL(k_mfg2_sf<3>, (unsigned)((nc + cpw - 1) / cpw), 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      else hipLaunchKernelGGL(k_mfg2_sf<2>, (unsigned)((nc + cpw - 1) / cpw), 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      continue;
-    }
-    if (sf) {
-      const int cpw = a.k_u == 2 ? 8 : 32; const unsigned grid = (unsigned)((nc + cpw - 1) / cpw);
-      if (a.k_u == 2 && a.cell_geo) hipLaunchKernelGGL((k_mfg3_sf<3, true>), grid, 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      else if (a.k_u == 2) hipLaunchKernelGGL((k_mfg3_sf<3, false>), grid, 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      else if (a.cell_geo) hipLaunchKernelGGL((k_mfg3_sf<2, true>), grid, 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      else hipLaunchKernelGGL((k_mfg3_sf<2, false>), grid, 256, 0, s, a, T, color_cells + color_off[k], (int)nc, x, y, constrained ? 1 : 0);
-      continue;
-    }
-    if (a.dim == 2) hipLaunchKernelGGL(k_mfg<2>, (unsigned)nc, 64, 0, s, a, color_cells + color_off[k], x, y, constrained ? 1 : 0, mode);
-    else hipLaunchKernelGGL(k_mfg<3>, (unsigned)nc, 64, 0, s, a, color_cells + color_off[k], x, y, constrained ? 1 : 0, mode);
+    launch_cells<kScatterColoured>(s, a, sf, T, color_cells + color_off[k], nc, x, y, constrained ? 1 : 0, mode);
+    ++launches;
   }
+  return launches;
 }
 
 }  // namespace poro
