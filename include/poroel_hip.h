@@ -290,6 +290,26 @@ enum { PORO_SCATTER_COLOURED = 0, PORO_SCATTER_ATOMIC = 1 };
 int  poro_ctx_set_scatter_mode(poro_ctx *ctx, int32_t mode);
 int  poro_ctx_get_scatter_mode(poro_ctx *ctx, int32_t *mode);
 
+/* Transform precision of PORO_PREC_FDM for the DISPLACEMENT system, where it runs in the single-rank 3D octant form (one rank, 3D, every Dirichlet condition on a pair of
+ * opposite faces, half lines of at most 128 nodes).
+ *   PORO_FDM_FP64 (default): the three transform passes on the fp64 matrix instruction.
+ *   PORO_FDM_FP32:           the same passes on the fp32 matrix instruction, fp32 transform matrices and an fp32 intermediate array; the residual, the preconditioned
+ *                            residual, g . z, the operator, the iterate and the stopping test stay fp64 (a lower-precision preconditioner inside an fp64 CG).
+ * Governs poro_disp_solve and poro_apply_preconditioner_u (its `reps` timing included).  Everything else stays fp64 in both modes: the scalar Q1 systems (there the fast
+ * diagonalisation is an exact direct solve), the planar 2D form, the slab / quadrant form of partitioned runs, the nodal fallback kernels and the coarse box of
+ * PORO_PREC_TWO_LEVEL.  On a context that does not run the octant form the setter succeeds, `effective` reports PORO_FDM_FP64 and nothing changes bit for bit.
+ * May be changed between any two calls, at no cost: the fp32 copies of the transform matrices are uploaded next to the fp64 ones when the block FDM is built (the first
+ * solve with PORO_PREC_FDM, or the getter below).  `effective` is final only once the block FDM has been built (the build checks the eigenvectors' mirror symmetry numerically),
+ * so poro_ctx_get_fdm_precision BUILDS it when fp32 is requested on a single-rank 3D context that can use PORO_PREC_FDM: host eigenproblems, uploads and a stream
+ * synchronise - call it outside timed regions.  With PORO_FDM_FP64 requested the getter builds nothing.
+ * Range: the fp32 mode needs |g| and |g| / den (den = the eigenvalue sums of the blocks, of the size of the moduli / h) to be fp32-normal, roughly 1e-38 .. 3e38; with GPa
+ * moduli and the reference's tolerances the residual at the end of a solve sits near 1e-25.  Nothing checks this at run time.
+ * The mode is never chosen automatically.  An unknown value returns < 0 with a message.  The environment variable PORO_FDMO_PRECISION=fp32|fp64 is read once, at context
+ * creation, as the initial mode (so that unchanged drivers can run it); PORO_FDMU_SINGLE keeps its own meaning (fp32 nodal transforms, octant form off). */
+enum { PORO_FDM_FP64 = 0, PORO_FDM_FP32 = 1 };
+int  poro_ctx_set_fdm_precision(poro_ctx *ctx, int32_t precision);
+int  poro_ctx_get_fdm_precision(poro_ctx *ctx, int32_t *requested, int32_t *effective);
+
 /* multi-GPU wiring.  id is the 128-byte ncclUniqueId from rank 0. */
 int  poro_comm_unique_id(void *id128);
 int  poro_ctx_comm_init_rccl(poro_ctx *ctx, const void *id128);

@@ -103,7 +103,8 @@ struct FdmOct {
   int64_t co_stride = 0, n_oct = 0;               // entries per (component, octant) = hxp h[1] h[2]; 24 co_stride
   double coef[3][3] = {};
   DevBuf<double> fwd[3][3][2], bwd[3][3][2], lam[3][3][2];   // [component][direction][parity]: half-size transforms in MFMA fragment order [tile][4 nt][64], eigenvalues (inf = no such mode)
-  DevBuf<double> g, z, t;                         // residual, preconditioned residual, scratch - all in octant form
+  DevBuf<float> fwd32[3][3][2], bwd32[3][3][2];   // single-rank octant form: the same fragments rounded to fp32 (PORO_FDM_FP32; bwd32 is the exact transpose of fwd32)
+  DevBuf<double> g, z, t;                         // residual, preconditioned residual, scratch - all in octant form (PORO_FDM_FP32: t holds the intermediate array as floats, half of it used)
   DevBuf<double> gz_part; int gz_n = 0;           // octant form on one rank: per-workgroup partial sums of g . z left by transform pass 2 (one slot per workgroup of that launch)
   std::vector<double> h_lam[3][3][2];             // host copies of the eigenvalues
   DevBuf<double> bxy;                             // [component][py][px][my][mx] = coef_x lam_x[mx] + coef_y lam_y[my]: the part of the eigenvalue sum a z line shares (pass 2 reads it per column)
@@ -200,6 +201,8 @@ struct poro_ctx {
   // scatter mode of the general cell-loop operator (poro_ctx_set_scatter_mode).  spatial_cells: all cells in Morton order of their centroids, built the first time the
   // context enters the atomic mode
   int scatter_mode = 0; poro::DevBuf<int32_t> spatial_cells;
+  // transform precision of the displacement system's block FDM where it runs in the single-rank 3D octant form (poro_ctx_set_fdm_precision); every other form ignores it
+  int fdm_precision = 0;
   poro::DevBuf<uint8_t> dir_mask, node_mask; poro::DevBuf<double> dir_val; poro::DevBuf<int32_t> dir_dofs;
   std::vector<int32_t> h_dir_dof; std::vector<double> h_dir_val;
   poro::ConsDev cons_u, cons_p;
@@ -383,7 +386,8 @@ void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int ran
 bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn);
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
-                double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing
+                double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr,
+                int precision /* PORO_FDM_FP32: the three passes on the fp32 MFMA with an fp32 intermediate array; g_oct, z_oct and g . z stay fp64 */ = PORO_FDM_FP64);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing
 // the same transform kernel for the scalar Q1 systems of a 3D box (nodal layout, one block set, no octants): 3 launches instead of 6
 bool fdmo_scalar_usable(int dim, const int nn[3]);
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s);

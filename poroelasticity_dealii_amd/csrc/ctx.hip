@@ -327,14 +327,14 @@ bool fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double
   Timed tm(c, "precondition_u_fdm");
   const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
   if (!begin_sampled_dispatch(c, names[0])) {
-    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, nullptr, gz_part);
+    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, nullptr, gz_part, c->fdm_precision);
     return gz_part != nullptr;
   }
   c->timers[names[1]].enqueued++;
   c->timers[names[2]].enqueued++;
   hipEvent_t ev[6];
   for (auto &e : ev) e = event_get(c);
-  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev, gz_part);
+  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev, gz_part, c->fdm_precision);
   for (int k = 0; k < 3; ++k) {
     Timer &t = c->timers[names[k]];
     t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
@@ -569,6 +569,12 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       if (m != "atomic" && m != "coloured") throw Error("PORO_MFG_SCATTER: atomic or coloured");
       if (m == "atomic" && !c->box.enabled) c->scatter_mode = PORO_SCATTER_ATOMIC;
     }
+    // read once here as well: the initial transform precision of the displacement system's octant-form block FDM (so that unchanged drivers can run the fp32 mode)
+    if (const char *v = std::getenv("PORO_FDMO_PRECISION")) {
+      const std::string m(v);
+      if (m != "fp32" && m != "fp64") throw Error("PORO_FDMO_PRECISION: fp32 or fp64");
+      c->fdm_precision = m == "fp32" ? PORO_FDM_FP32 : PORO_FDM_FP64;
+    }
     *out = c.release();
     return 0;
   });
@@ -587,6 +593,34 @@ int poro_ctx_set_scatter_mode(poro_ctx *c, int32_t mode) {
 }
 int poro_ctx_get_scatter_mode(poro_ctx *c, int32_t *mode) {
   return guarded([&] { if (!c || !mode) throw Error("null argument"); *mode = c->scatter_mode; return 0; });
+}
+
+// true where PORO_PREC_FDM of the displacement system runs in the single-rank 3D octant form.  Builds the block FDM where that is possible at all (one rank, 3D, separable
+// Dirichlet faces) - the numerical symmetry check of the eigenvectors is part of the build, so only then is the answer final
+static bool fdm_u_runs_octant(poro_ctx *c) {
+  if (!c->fdm_u.built) {
+    if (c->dim != 3 || c->comm.multi()) return false;
+    analyse_fdm_u(c);
+    if (c->fdm_u_state != 1) return false;
+    build_fdm_u(c);
+  }
+  return c->fdm_oct.built && !c->fdm_oct.planar && !c->fdm_oct.slab.on;
+}
+int poro_ctx_set_fdm_precision(poro_ctx *c, int32_t precision) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    if (precision != PORO_FDM_FP64 && precision != PORO_FDM_FP32) throw Error("poro_ctx_set_fdm_precision: unknown precision " + std::to_string(precision) + " (PORO_FDM_FP64 or PORO_FDM_FP32)");
+    c->fdm_precision = precision;   // (the fp32 fragments are uploaded with the fp64 ones when the block FDM is built: nothing to do here, and forms without fp32 kernels never look at it)
+    return 0;
+  });
+}
+int poro_ctx_get_fdm_precision(poro_ctx *c, int32_t *requested, int32_t *effective) {
+  return guarded([&] {
+    if (!c || !requested || !effective) throw Error("null argument");
+    *requested = c->fdm_precision; *effective = PORO_FDM_FP64;
+    if (c->fdm_precision == PORO_FDM_FP32) { PORO_HIP(hipSetDevice(c->device)); if (fdm_u_runs_octant(c)) *effective = PORO_FDM_FP32; }
+    return 0;
+  });
 }
 
 void poro_ctx_destroy(poro_ctx *c) {
@@ -1063,7 +1097,7 @@ int poro_apply_preconditioner_u(poro_ctx *c, int32_t preconditioner, const doubl
       build_fdm_u(c);
       FdmOct &O = c->fdm_oct;
       // octant form where the solver uses it: butterflies outside (H, H'), the three transform passes in between - the timed part, as inside PCG
-      auto once = [&]() { if (O.built && O.slab.on) fdm_precondition_u_slab(c, O.g.p, O.z.p, nullptr); else if (O.built && O.planar) fdmo_apply_planar(s, O, O.g.p, O.z.p); else if (O.built) fdmo_apply(s, O, O.g.p, O.z.p, O.t.p); else fdm_precondition_u(c, g.p, z.p); };
+      auto once = [&]() { if (O.built && O.slab.on) fdm_precondition_u_slab(c, O.g.p, O.z.p, nullptr); else if (O.built && O.planar) fdmo_apply_planar(s, O, O.g.p, O.z.p); else if (O.built) fdmo_apply(s, O, O.g.p, O.z.p, O.t.p, nullptr, nullptr, nullptr, c->fdm_precision); else fdm_precondition_u(c, g.p, z.p); };
       if (O.built) fdmo_from_nodal(s, O, g.p, O.g.p);
       once();
       if (O.built) fdmo_to_nodal(s, O, O.z.p, z.p);

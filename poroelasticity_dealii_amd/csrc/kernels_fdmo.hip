@@ -34,6 +34,7 @@ namespace poro {
 namespace {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct OctDims { int nx, ny, nz, hx, hy, hz, hxp; int64_t co; int no, own_z, nc; };   // nodes and half lengths per direction; hxp = row pitch (hx rounded up to even: 16-byte aligned rows, the pad entry stays zero); co = hxp hy hz entries per (component, octant)
 // no = 8: octant form.  no = 4 (slab partitions): z is not split - every z index is "its own mirror image" (hz = nz, parity blocks 0..3 only); own_z = planes that count in dot products
@@ -275,7 +276,7 @@ struct OctPass {
   int64_t co_stride, blk_stride, row_stride;
   int bit1, bit2;           // octant bit that selects the parity of the matrices of GEMM 1 / 2
   int hx, pl;               // mode 1: columns of a plane = hx hy; a column's plane offset -> (my, mx)
-  const double *T1[3][2], *T2[3][2];                     // [component][parity], MFMA fragment order [tile][4 NT][64]
+  const void *T1[3][2], *T2[3][2];                       // [component][parity], MFMA fragment order [tile][4 NT][64]: doubles (k_fdmo_pass, k_fdmo_zpass_both) or floats (k_fdmo_pass_f32)
   const double *lam_z[3][2]; double cz[3]; const double *bxy;   // mode 1: eigenvalues of the line direction; bxy[(4 c + (o & 3)) pl + column] = the other two directions' share
   const double *in_blk[3]; double *out_blk[3]; int use_in_off, use_out_off;   // batched scalar systems (no_shift = 0, up to 3 blocks = right-hand sides in separate vectors): every block's own vector instead of `in` / `out` + block * co_stride
   int bxy_cmul;                 // bxy table: blocks per component (4: displacement system; 0: the scalar systems share one table)
@@ -299,6 +300,13 @@ template <int NT> struct PassGeom {
   static constexpr int LDA = PADN + 2;                       // data as the A operand: lane (i, kq) reads [16 t + i][4 kk + kq]; LD = 2 * odd (mod 32) keeps a 32-lane group on 32 bank pairs
   static constexpr int LDB = PADN + ((NT & 1) ? 0 : 16);     // data as the B operand: lane (j, kq) reads [4 kk + kq][16 w + j]; LD = 16 (mod 32)
   static constexpr int LDMAX = LDA > LDB ? LDA : LDB;
+  // Both leading dimensions count ELEMENTS and serve the 8-byte elements of k_fdmo_pass and the 4-byte ones of k_fdmo_pass_f32 alike.  A fragment read is serviced in two
+  // groups of 32 lanes (kq = 0, 1 and kq = 2, 3).  Doubles (ds_read_b64): bank = (byte address / 4) mod 64 - an element is a bank PAIR, 32 pairs.  Floats (ds_read_b32):
+  // bank = (byte address / 4) mod 32 - an element is a bank, 32 banks.  Either way a group is conflict-free iff its 32 element offsets differ mod 32.
+  //   A role: offsets i LD + kq (i < 16, kq in {0, 1}); LD = 2 * odd (mod 32) -> (2 i * odd + kq) mod 32 takes every value once.
+  //   B role: offsets kq LD + j (j < 16); LD = 16 (mod 32) -> j and j + 16.
+  // fp32 accumulator stores (one register of all lanes: rows 4 kq + q, element offsets j + 4 kq LD): 4 LD = 0 or 8 (mod 32), two lanes per bank in a group of 32 - the 2-way
+  // conflict that ds_write_b32 absorbs in its own issue cycles.  LD is even: the float2 stores of the staged block are 8-byte aligned.
 };
 
 // One item (= one (component, octant, block)) per workgroup; the hardware dispatcher balances the items over the CUs.
@@ -355,7 +363,7 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   if (f_use_out) out = P.out_blk[co];
   const bool heavy = CORNER && w == (int)(blockIdx.x & (NW - 1));   // this wave also computes tile (XT, XT)
   const int R = P.R, C = MODE == 1 ? min(P.C, P.pl - b * P.C) : P.C;
-  const double *__restrict__ T1 = P.T1[c][(o >> P.bit1) & 1] + lane, *__restrict__ T2 = P.T2[c][(o >> P.bit2) & 1] + lane;
+  const double *__restrict__ T1 = static_cast<const double *>(P.T1[c][(o >> P.bit1) & 1]) + lane, *__restrict__ T2 = static_cast<const double *>(P.T2[c][(o >> P.bit2) & 1]) + lane;
   // slab form: address of plane position `col` of this block in the exchange buffer
   // (a block's columns lie in at most two shares when a share is at least a block long - up to 12 ranks: the two bases are wave-uniform scalars)
   int slab_q0 = 0, slab_sw = 0; int64_t slab_base[2] = {0, 0};
@@ -521,6 +529,171 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   }
 }
 
+
+// ---- the transform pass with fp32 transforms (opt-in: poro_ctx_set_fdm_precision, PORO_FDM_FP32) ---------------------------------------------------------------------
+// The single-rank octant form only (VAR = 0 of k_fdmo_pass: 24 blocks, aligned rows, no exchange buffer), with the same workgroup shapes, tile ownership, fragment streams
+// and chunking, on v_mfma_f32_16x16x4_f32.  A kernel of its own rather than a compute-type parameter of k_fdmo_pass: as a parameter it moved the register allocation of
+// eight fp64 instantiations by 2-4 VGPRs, and the fp64 path is to stay what it was.
+//   pass 1 (MODE 0) reads the fp64 octant array g and converts on the way into LDS; it stores FLOATS into the scratch array (reinterpreted, same indices: half of it is used);
+//   pass 2 (MODE 1) reads and writes floats, in place; between its GEMMs it multiplies by an fp32 reciprocal of the fp64 eigenvalue sum;
+//   pass 3 (MODE 2) reads floats and stores the fp64 octant array z.
+// Rows of the float array start at even indices (even pitch, even chunk offsets): 8-byte aligned, float2 accesses - for odd and even half lines alike (hxp padding).
+// The MFMA takes one A and one B value per lane exactly as the fp64 one (A[l & 15][l >> 4], B[l >> 4][l & 15]), but its four accumulators are the rows 4 kq + q of column j
+// (fp64: 4 q + kq): `arow`.  Its dependent latency (40 cycles) exceeds its issue slot (32); every wave carries >= 4 independent accumulators at NT >= 4 and the accumulator
+// loop is innermost, as in the fp64 kernel.  Padding: converted zeros are zeros; removed modes (lam = inf) give exactly 0 as in fp64 (guard on the fp64 sum).
+// GZ: g . z in fp64 from the fp32 values the pass holds - ghat and the rounded ghat / den it stores; they have the same sign, so every term is >= 0.
+// Range: |g| and |g| / den must be fp32-normal (include/poroel_hip.h).
+template <int NT, int MODE, bool GZ = false>
+__global__ void __launch_bounds__(64 * pass_waves<NT>())
+k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
+  static_assert(!GZ || MODE == 1, "g . z comes out of pass 2");
+  typedef PassGeom<NT> Gm;
+  constexpr int NW = pass_waves<NT>();
+  constexpr bool EXTRA = NT > NW;
+  constexpr int XT = NT - 1;
+  constexpr int NL = (MODE == 1 && EXTRA) ? NW : NT;
+  constexpr bool CORNER = EXTRA && MODE != 1;
+  constexpr int NACC = NL + (EXTRA ? 1 : 0) + (CORNER ? 1 : 0);
+  constexpr bool kColsFirst = MODE == 0, kColsSecond = MODE == 2;
+  constexpr int LD1 = kColsFirst ? Gm::LDA : Gm::LDB, LD2 = kColsSecond ? Gm::LDA : Gm::LDB;
+  constexpr int NS = EXTRA ? 2 : 1;
+  constexpr int PADC = 16 * NL;
+  extern __shared__ float Lf[];                              // PADN x LDMAX floats (dynamic: more than 64 KB at NT = 8 only)
+  __shared__ double gz_wave[GZ ? NW : 1];
+  if (P.gate && (P.gate->done | P.gate->finishing)) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, kq = lane >> 4;
+  auto arow = [&](int q) { return 4 * kq + q; };             // row of accumulator register q inside its tile
+  const int co = blockIdx.x / P.nblk, b = blockIdx.x % P.nblk, c = co >> 3, o = co & 7;
+  const int64_t base = (int64_t)co * P.co_stride + (int64_t)b * P.blk_stride;
+  const bool heavy = CORNER && w == (int)(blockIdx.x & (NW - 1));
+  const int R = P.R, C = MODE == 1 ? min(P.C, P.pl - b * P.C) : P.C;
+  const float *__restrict__ T1 = static_cast<const float *>(P.T1[c][(o >> P.bit1) & 1]) + lane, *__restrict__ T2 = static_cast<const float *>(P.T2[c][(o >> P.bit2) & 1]) + lane;
+  const float *inf = reinterpret_cast<const float *>(in); float *outf = reinterpret_cast<float *>(out);
+  // ---- block -> LDS, zero padded to PADN x PADC; all loads in flight before the first LDS store ----
+  {
+    constexpr int HP = PADC / 2, TOT = Gm::PADN * HP, PER = (TOT + 64 * NW - 1) / (64 * NW);
+    float2 stage[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP);
+      const bool ok = e < TOT && r < R && c2 < C; const int64_t at = base + (int64_t)r * P.row_stride + c2;      // (even: base, row_stride and c2 are)
+      if constexpr (MODE == 0) { const double2 v = ok ? *reinterpret_cast<const double2 *>(in + at) : double2{0.0, 0.0}; stage[u] = float2{(float)v.x, (float)v.y}; }
+      else stage[u] = ok ? *reinterpret_cast<const float2 *>(inf + at) : float2{0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP); if (e < TOT) *reinterpret_cast<float2 *>(&Lf[r * LD1 + c2]) = stage[u]; }
+  }
+  constexpr int CHK = EXTRA ? 2 : 4, NCH = Gm::KKP / CHK;
+  float tf[2][NS][CHK];
+  auto load_chunk = [&](int buf, int step) {
+    const float *__restrict__ T = step < NCH ? T1 : T2; const int ch = step < NCH ? step : step - NCH;
+#pragma unroll
+    for (int k = 0; k < CHK; ++k) {
+      tf[buf][0][k] = T[((int64_t)w * Gm::KKP + CHK * ch + k) * 64];
+      if constexpr (EXTRA) tf[buf][1][k] = T[((int64_t)XT * Gm::KKP + CHK * ch + k) * 64];
+    }
+  };
+  v4f acc[NACC];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int t = 0; t < NACC; ++t) acc[t] = v4f{0, 0, 0, 0};
+  };
+  // (tile ownership as in k_fdmo_pass)
+  auto gemm = [&](auto contract_cols, auto ld_c, auto first_step_c, auto corner_c, int kk_n) {
+    constexpr bool kCols = decltype(contract_cols)::value, kCorner = decltype(corner_c)::value; constexpr int LD = decltype(ld_c)::value, S0 = decltype(first_step_c)::value;
+    const float *La = kCols ? Lf + j * LD + kq : Lf + kq * LD + j;
+    const float *Lw = kCols ? La + 16 * w * LD : La + 16 * w;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int buf = (S0 + ch) & 1;
+#pragma unroll
+      for (int k = 0; k < CHK; ++k) {
+        const int kk = CHK * ch + k;
+        if (kk < Gm::KKP - 3 || kk < kk_n) {
+          float d[NT];
+#pragma unroll
+          for (int t = 0; t < NT; ++t) if (t < NL || (kCorner && t == XT)) d[t] = kCols ? La[16 * t * LD + 4 * kk] : La[4 * kk * LD + 16 * t];
+          float dw = 0; if constexpr (EXTRA) dw = kCols ? Lw[4 * kk] : Lw[4 * kk * LD];
+#pragma unroll
+          for (int t = 0; t < NL; ++t) acc[t] = kCols ? __builtin_amdgcn_mfma_f32_16x16x4f32(d[t], tf[buf][0][k], acc[t], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(tf[buf][0][k], d[t], acc[t], 0, 0, 0);
+          if constexpr (EXTRA) acc[NL] = kCols ? __builtin_amdgcn_mfma_f32_16x16x4f32(dw, tf[buf][1][k], acc[NL], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(tf[buf][1][k], dw, acc[NL], 0, 0, 0);
+          if constexpr (kCorner) acc[NL + 1] = kCols ? __builtin_amdgcn_mfma_f32_16x16x4f32(d[XT], tf[buf][1][k], acc[NL + 1], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(tf[buf][1][k], d[XT], acc[NL + 1], 0, 0, 0);
+        }
+      }
+      if (S0 + ch + 2 < 2 * NCH) load_chunk(buf, S0 + ch + 2);
+    }
+  };
+  auto tile_of = [&](int a, int &tr, int &tc, bool cols) {
+    if (a < NL) { tr = cols ? a : w; tc = cols ? w : a; }
+    else if (a == NL) { tr = cols ? w : XT; tc = cols ? XT : w; }
+    else { tr = XT; tc = XT; }
+  };
+  typedef std::integral_constant<bool, kColsFirst> CF; typedef std::integral_constant<int, LD1> L1c;
+  typedef std::integral_constant<bool, kColsSecond> CS; typedef std::integral_constant<int, LD2> L2c;
+  typedef std::integral_constant<int, 0> S0c; typedef std::integral_constant<int, NCH> S1c;
+  __builtin_amdgcn_s_setprio(3);
+  load_chunk(0, 0); load_chunk(1, 1);
+  zero_acc();
+  __builtin_amdgcn_s_setprio(0);
+  __syncthreads();
+  if (heavy) gemm(CF{}, L1c{}, S0c{}, std::integral_constant<bool, CORNER>{}, P.kk1); else gemm(CF{}, L1c{}, S0c{}, std::false_type{}, P.kk1);
+  __syncthreads();
+  // ---- first result -> LDS in the layout of the second GEMM (MODE 1: divided by the eigenvalue sums on the way) ----
+  if constexpr (MODE == 1) {
+    const double *lamz = P.lam_z[c][(o >> 2) & 1], *bx = P.bxy + (int64_t)(4 * c + (o & 3)) * P.pl;
+    const double czc = P.cz[c];
+    double lzw[4], lzx[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { lzw[q] = czc * lamz[16 * w + arow(q)]; lzx[q] = EXTRA ? czc * lamz[16 * XT + arow(q)] : 0.0; }
+    double gz = 0;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int tr, tc; tile_of(a, tr, tc, false);
+      const double bxy = bx[min(b * P.C + 16 * tc + j, P.pl - 1)];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        // the fp64 eigenvalue sum, rounded once, then v_rcp_f32 (1 ulp); modes that do not exist (lam = inf) and sums beyond the fp32 range give exactly 0
+        const double den = (a < NL ? lzw[q] : lzx[q]) + bxy;
+        const float r = den < 1e300 ? __builtin_amdgcn_rcpf((float)den) : 0.f;
+        const float zh = acc[a][q] * r;
+        Lf[(16 * tr + arow(q)) * LD2 + 16 * tc + j] = zh;
+        if constexpr (GZ) gz = fma((double)acc[a][q], (double)zh, gz);
+        __builtin_amdgcn_sched_barrier(0);       // one entry at a time, as in k_fdmo_pass: otherwise the conversions and reciprocals of all entries pile up in registers
+      }
+    }
+    if constexpr (GZ) {
+      gz = wave_sum(gz);
+      if (lane == 0) gz_wave[w] = gz;
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int tr, tc; tile_of(a, tr, tc, kColsFirst);
+      if (a == NL + 1 && !heavy) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Lf[(16 * tr + arow(q)) * LD2 + 16 * tc + j] = acc[a][q];
+    }
+  }
+  zero_acc();
+  __syncthreads();
+  if constexpr (GZ) {
+    if (tid == 0) { double t = 0; for (int k = 0; k < NW; ++k) t += gz_wave[k]; P.gz_part[blockIdx.x] = t; }   // fixed order: reproducible
+  }
+  if (heavy) gemm(CS{}, L2c{}, S1c{}, std::integral_constant<bool, CORNER>{}, P.kk2); else gemm(CS{}, L2c{}, S1c{}, std::false_type{}, P.kk2);
+  // ---- store: floats (passes 1, 2) or the fp64 octant array (pass 3) ----
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) {
+    int tr, tc; tile_of(a, tr, tc, kColsSecond);
+    if (a == NL + 1 && !heavy) continue;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = 16 * tr + arow(q), cc = 16 * tc + j;
+      if (r < R && cc < C) { const int64_t at = base + (int64_t)r * P.row_stride + cc; if constexpr (MODE == 2) out[at] = (double)acc[a][q]; else outf[at] = acc[a][q]; }
+    }
+  }
+}
+
 // ---- planar (2D) form: the blocks are whole (component, quadrant) planes of up to ~350 x 350 entries - too large for one workgroup's LDS, so each of the four
 //      1D transforms is a batched tiled GEMM of its own: C_b (M x N) = A_b (M x K) B_b (K x N), 64 x 64 tiles, 16-deep LDS stages (double buffered), 4 waves x (2 x 2) MFMA tiles.
 //      An operand whose unit stride runs along K is staged "m-major" ([64][16 + 2]), one whose unit stride runs along M / N "k-major" ([16][64 + 16]): both give
@@ -650,7 +823,7 @@ k_fdmo_zpass_both(OctPass P, const int64_t *__restrict__ dst /* [ng][2]: offsets
   }
   constexpr int CHK = 2, NCH = Gm::KKP / CHK;
   double tf[2][NS][CHK];
-  const double *__restrict__ T1e = P.T1[c][0] + lane, *__restrict__ T1o = P.T1[c][1] + lane, *__restrict__ T2e = P.T2[c][0] + lane, *__restrict__ T2o = P.T2[c][1] + lane;
+  const double *__restrict__ T1e = static_cast<const double *>(P.T1[c][0]) + lane, *__restrict__ T1o = static_cast<const double *>(P.T1[c][1]) + lane, *__restrict__ T2e = static_cast<const double *>(P.T2[c][0]) + lane, *__restrict__ T2o = static_cast<const double *>(P.T2[c][1]) + lane;
   auto load_chunk = [&](int buf, int step) {
     const bool first = step < NCH; const int ch = first ? step : step - NCH;
     const double *__restrict__ Te = first ? T1e : T2e, *__restrict__ To = first ? T1o : T2o;
@@ -763,11 +936,26 @@ template <int NT, int MODE, int VAR, bool GZ = false> void launch_one(hipStream_
   }
   hipExtLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
 }
-template <int NT> void launch_pass(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+template <int NT, int MODE, bool GZ = false> void launch_one_f32(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(float));
+  auto kernel = k_fdmo_pass_f32<NT, MODE, GZ>;
+  if (lds > 64 * 1024) {
+    static std::mutex mu; static std::set<int> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done.count(dev)) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert(dev); }
+  }
+  hipExtLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
+}
+template <int NT> void launch_pass(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1, bool f32) {
   const bool plain = P.vec2 == 1 && !P.use_in_off && !P.use_out_off && P.bxy_cmul == 4;
   const bool oct = plain && P.slab_z == 0 && P.slab_io == 0 && !P.row_in && P.no_shift == 3;
   const bool slab_u = plain && P.no_shift == 2 && ((P.mode == 0 && P.slab_io == 1 && !P.slab_z) || (P.mode == 1 && P.slab_z == 2 && P.row_in && !P.slab_io) || (P.mode == 2 && P.slab_io == 2 && !P.slab_z));
-  if (oct) {
+  if (f32) {       // fp32 mode: P.T1 / P.T2 hold float fragments, the intermediate array is float
+    if (!oct) throw Error("fdmo: fp32 transforms exist for the single-rank octant form only");
+    if (P.mode == 0) launch_one_f32<NT, 0>(s, n_items, P, in, out, e0, e1);
+    else if (P.mode == 1) { if (P.gz_part) launch_one_f32<NT, 1, true>(s, n_items, P, in, out, e0, e1); else launch_one_f32<NT, 1>(s, n_items, P, in, out, e0, e1); }
+    else launch_one_f32<NT, 2>(s, n_items, P, in, out, e0, e1);
+  } else if (oct) {
     if (P.mode == 0) launch_one<NT, 0, 0>(s, n_items, P, in, out, e0, e1);
     else if (P.mode == 1) { if (P.gz_part) launch_one<NT, 1, 0, true>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 1, 0>(s, n_items, P, in, out, e0, e1); }
     else launch_one<NT, 2, 0>(s, n_items, P, in, out, e0, e1);
@@ -777,16 +965,16 @@ template <int NT> void launch_pass(hipStream_t s, const OctPass &P, int n_items,
     if (P.mode == 0) launch_one<NT, 0, 2>(s, n_items, P, in, out, e0, e1); else if (P.mode == 1) launch_one<NT, 1, 2>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 2, 2>(s, n_items, P, in, out, e0, e1);
   }
 }
-void launch_pass_nt(hipStream_t s, int nt, const OctPass &P, int n_blocks, const double *in, double *out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+void launch_pass_nt(hipStream_t s, int nt, const OctPass &P, int n_blocks, const double *in, double *out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, bool f32 = false) {
   switch (nt) {
-    case 1: launch_pass<1>(s, P, n_blocks, in, out, e0, e1); break;
-    case 2: launch_pass<2>(s, P, n_blocks, in, out, e0, e1); break;
-    case 3: launch_pass<3>(s, P, n_blocks, in, out, e0, e1); break;
-    case 4: launch_pass<4>(s, P, n_blocks, in, out, e0, e1); break;
-    case 5: launch_pass<5>(s, P, n_blocks, in, out, e0, e1); break;
-    case 6: launch_pass<6>(s, P, n_blocks, in, out, e0, e1); break;
-    case 7: launch_pass<7>(s, P, n_blocks, in, out, e0, e1); break;
-    case 8: launch_pass<8>(s, P, n_blocks, in, out, e0, e1); break;
+    case 1: launch_pass<1>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 2: launch_pass<2>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 3: launch_pass<3>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 4: launch_pass<4>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 5: launch_pass<5>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 6: launch_pass<6>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 7: launch_pass<7>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 8: launch_pass<8>(s, P, n_blocks, in, out, e0, e1, f32); break;
     default: throw Error("fdmo: half lines of more than 128 entries");
   }
 }
@@ -894,6 +1082,9 @@ bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S,
     for (int m = 0; m < ng; ++m) lp[m] = lam[grp[p][m]];
     O.h_lam[comp][dir][p] = lp;
     O.fwd[comp][dir][p].upload(F); O.bwd[comp][dir][p].upload(B); O.lam[comp][dir][p].upload(lp);
+    if (!O.slab.on) {   // fp32 mode of the octant form: both matrices rounded entry by entry from the same S, so the backward one is the exact transpose of the rounded forward one
+      O.fwd32[comp][dir][p].upload(std::vector<float>(F.begin(), F.end())); O.bwd32[comp][dir][p].upload(std::vector<float>(B.begin(), B.end()));
+    }
   }
   return true;
 }
@@ -906,7 +1097,11 @@ void fdmo_finalize(FdmOct &O) {
   O.bxy.upload(B);
 }
 
-void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part) {
+void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part, int precision) {
+  const bool f32 = precision == PORO_FDM_FP32;     // fp32 transforms: float fragments, `scratch` holds the intermediate array as floats (g_oct, z_oct stay fp64)
+  if (f32 && (O.slab.on || O.planar || !O.fwd32[0][0][0].p)) throw Error("fdmo_apply: fp32 transforms exist for the single-rank octant form only");
+  auto fw = [&](int c, int d, int p) -> const void * { return f32 ? (const void *)O.fwd32[c][d][p].p : (const void *)O.fwd[c][d][p].p; };
+  auto bw = [&](int c, int d, int p) -> const void * { return f32 ? (const void *)O.bwd32[c][d][p].p : (const void *)O.bwd[c][d][p].p; };
   static int stamp_calls = 0; const char *stamp_path = std::getenv("PORO_FDMO_STAMPS");
   const bool stamping = stamp_path && ++stamp_calls == 3;          // diagnostic: the third application of the process writes its per-block time stamps
   DevBuf<unsigned long long> stamps; std::vector<std::pair<int, int64_t>> stamp_off;
@@ -919,24 +1114,24 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
   for (int c = 0; c < 3; ++c) { P.cz[c] = O.coef[c][2]; for (int p = 0; p < 2; ++p) P.lam_z[c][p] = O.lam[c][2][p].p; }
   // pass 1: per z-plane, X[ky][kx] -> Fy (X Fx^T)
   P.mode = 0; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hx); P.kk2 = ksteps(hy); P.nblk = hz; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp; P.bit1 = 0; P.bit2 = 1;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.fwd[c][0][p].p; P.T2[c][p] = O.fwd[c][1][p].p; }
+  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = fw(c, 0, p); P.T2[c][p] = fw(c, 1, p); }
   if (stamping) { stamps.alloc((size_t)8 * 24 * (O.h[2] + (hxp * hy + pass2_chunk(nt) - 1) / pass2_chunk(nt) + O.h[2])); stamps.zero(s); }
   P.stamps = stamping ? stamps.p : nullptr; stamp_off.push_back({24 * P.nblk, 0});
-  launch_pass_nt(s, nt, P, 24 * P.nblk, g_oct, scratch, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
+  launch_pass_nt(s, nt, P, 24 * P.nblk, g_oct, scratch, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, f32);
   // pass 2: per chunk of 16 NT columns of a (component, octant) block, X[kz][col] -> Bz scale (Fz X), in place
   const int cw = pass2_chunk(nt);                 // chunk width of pass 2: one column tile per wave (NT = 5: 5 x 4 tiles for the four waves of the workgroup)
   P.mode = 1; P.R = hz; P.C = cw; P.nt_r = tiles(hz); P.nt_c = cw / 16; P.kk1 = ksteps(hz); P.kk2 = ksteps(hz); P.nblk = (hxp * hy + cw - 1) / cw; P.blk_stride = cw; P.row_stride = (int64_t)hxp * hy; P.bit1 = 2; P.bit2 = 2;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.fwd[c][2][p].p; P.T2[c][p] = O.bwd[c][2][p].p; }
+  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = fw(c, 2, p); P.T2[c][p] = bw(c, 2, p); }
   if (stamping) P.stamps = stamps.p + 8 * (int64_t)(24 * hz); stamp_off.push_back({24 * P.nblk, 8 * (int64_t)(24 * hz)});
   if (gz_part && 24 * P.nblk != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
   P.gz_part = gz_part;
-  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, scratch, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
+  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, scratch, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, f32);
   P.gz_part = nullptr;
   // pass 3: per z-plane, X[my][mx] -> (By X) Bx^T
   P.mode = 2; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hy); P.kk2 = ksteps(hx); P.nblk = hz; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp; P.bit1 = 1; P.bit2 = 0;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.bwd[c][1][p].p; P.T2[c][p] = O.bwd[c][0][p].p; }
+  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = bw(c, 1, p); P.T2[c][p] = bw(c, 0, p); }
   if (stamping) P.stamps = stamps.p + 8 * (int64_t)(24 * hz + stamp_off[1].first); stamp_off.push_back({24 * P.nblk, 8 * (int64_t)(24 * hz + stamp_off[1].first)});
-  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, z_oct, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr);
+  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, z_oct, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr, f32);
   if (stamping) {
     PORO_HIP(hipStreamSynchronize(s));
     std::vector<unsigned long long> h(stamps.n); PORO_HIP(hipMemcpy(h.data(), stamps.p, stamps.n * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -51,6 +51,7 @@ struct RunControls {
   std::string output_dir;                                           // "" = no files; the reference always writes ./solution/solution-NNNN.vtk (:285-290)
   int chebyshev_degree = 0; double chebyshev_ratio = 0.0;           // PORO_PREC_CHEBYSHEV: 0 = the library's defaults
   int preconditioner_p = -1;                                        // pressure / projection solves; -1 = fast diagonalisation where the context supports it, else the two-level form, else Jacobi
+  bool fdm_fp32 = false;                                            // PORO_FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (elsewhere no effect).  Never chosen automatically
   bool atomic_scatter = false;                                      // general meshes, matrix-free: PORO_SCATTER_ATOMIC (one launch per operator application; not bitwise reproducible).  Never chosen automatically
 };
 
@@ -256,6 +257,7 @@ template <int dim> class PoroElasticProblem {
   // trace rows: [step, fss_iteration, pressure_iterations, inner pressure error, |p|_inf, error after displacement, u CG its, p CG its]
   void initialize(const RunControls &rc) {
     if (rc.atomic_scatter) check(poro_ctx_set_scatter_mode(context(), PORO_SCATTER_ATOMIC), "ctx_set_scatter_mode");
+    if (rc.fdm_fp32) check(poro_ctx_set_fdm_precision(context(), PORO_FDM_FP32), "ctx_set_fdm_precision");
     displacement_solver.control.abs_tol = rc.abs_tol_u; displacement_solver.control.rel_tol = rc.rel_tol_u; displacement_solver.control.stop_rule = rc.stop_rule_u;
     displacement_solver.control.max_iter = pressure_solver.control.max_iter = strain_projector.control.max_iter = rc.max_iter;
     // rc.preconditioner < 0: the strongest displacement preconditioner this mesh supports

@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--atomic-scatter]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--atomic-scatter] [--fdm-fp32]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -16,7 +16,7 @@ using namespace poro_host;
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl; return 1; }   // parse_command_line.h:9-13
-  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false;
+  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -32,9 +32,11 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--block-fdm")) prec = PORO_PREC_FDM;         // block fast diagonalisation (uniform boxes with face-wise Dirichlet data)
     else if (!std::strcmp(argv[i], "--two-level")) prec = PORO_PREC_TWO_LEVEL;   // Jacobi + block fast diagonalisation of the underlying / auxiliary box (refined boxes, rectangle-filling Gmsh meshes)
     else if (!std::strcmp(argv[i], "--atomic-scatter")) atomic_scatter = true;   // general meshes, --matrix-free: one launch per operator application with fp64 atomic adds (last bits differ from run to run)
+    else if (!std::strcmp(argv[i], "--fdm-fp32")) fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
+  if (fdm_fp32 && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
   try {
     input_data::InputDataPoroel data;
     data.read_input_file(argv[1]);
@@ -52,7 +54,7 @@ int main(int argc, char **argv) {
       for (int d = 0; d < data.dim; ++d) { n[d] = 1 << data.initial_refinement_level; size[d] = data.domain_size.at(d); }
       build_box_problem(P, data.dim, n, size, degree);
     }
-    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter;
+    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
     int n_steps = 0; for (double t = 0; t < data.t_max; t += data.time_step) ++n_steps;   // while (time < t_max) (:327)
