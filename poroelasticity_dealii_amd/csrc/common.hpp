@@ -97,6 +97,7 @@ struct FdmU { int dim = 0; int nn[3] = {1, 1, 1}; double coef[3][3] = {}; FdmuDi
 // part o_k = v_k - v_k' of the pair k < h, k' = n - 1 - k; the centre node of an odd line is its own mirror: e = v, o = 0), h = (n + 1) / 2 entries per
 // direction.  Each of the 24 (component, octant) blocks is then an independent half-size 3D transform, done in three passes (x y fused per plane, z
 // forward + eigenvalue scaling + z backward, y x fused per plane); the butterflies ride in the CG update kernels, which touch every entry anyway.
+struct FdmoPlans;
 struct FdmOct {
   bool built = false; int nt = 0;                 // 16-wide MFMA tiles per half line (max over the directions), 1..8
   int n[3] = {1, 1, 1}, h[3] = {1, 1, 1}; int hxp = 2;   // hxp: row pitch = h[0] rounded up to even (16-byte aligned rows; the pad entry is zero and stays zero)
@@ -127,6 +128,7 @@ struct FdmOct {
     DevBuf<int64_t> row_out; DevBuf<int32_t> row_kz;   // [rows_back]: offset (in buf) of a row of the scattering all-to-all, global plane of that row
     DevBuf<double> buf, tz;                       // all-to-all buffers; transposed array [chunk][pz][hzg][cw]
   } slab;
+  std::shared_ptr<FdmoPlans> plans;              // displacement forms: the launch descriptors of the three passes, planned once by fdmo_finalize (kernels_fdmo.hip)
   struct ScalarTable { double a, kappa; DevBuf<double> t; };
   std::list<ScalarTable> scalar_tables;           // scalar form: a + kappa (lam_x + lam_y) per plane position, one table per (a, kappa) seen (pressure Jacobian, mass matrix)
 };

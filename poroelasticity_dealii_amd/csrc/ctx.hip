@@ -1097,10 +1097,8 @@ int poro_apply_preconditioner_u(poro_ctx *c, int32_t preconditioner, const doubl
       build_fdm_u(c);
       FdmOct &O = c->fdm_oct;
       // octant form where the solver uses it: butterflies outside (H, H'), the three transform passes in between - the timed part, as inside PCG
-      auto once = [&]() { if (O.built && O.slab.on) fdm_precondition_u_slab(c, O.g.p, O.z.p, nullptr); else if (O.built && O.planar) fdmo_apply_planar(s, O, O.g.p, O.z.p); else if (O.built) fdmo_apply(s, O, O.g.p, O.z.p, O.t.p, nullptr, nullptr, nullptr, c->fdm_precision); else fdm_precondition_u(c, g.p, z.p); };
-      if (O.built) fdmo_from_nodal(s, O, g.p, O.g.p);
-      once();
-      if (O.built) fdmo_to_nodal(s, O, O.z.p, z.p);
+      fdm_precondition_u_nodal(c, g.p, z.p, c->fdm_precision);
+      auto once = [&]() { if (O.built) fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, c->fdm_precision); else fdm_precondition_u(c, g.p, z.p); };
       if (reps > 0 && seconds_per_apply) {
         EventPair ev(c); PORO_HIP(hipEventRecord(ev.e0, s));
         for (int k = 0; k < reps; ++k) once();

@@ -98,6 +98,8 @@ bool two_level_supported_p(poro_ctx *c);
 void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega);   // z = omega D^-1 g + P B_H^-1 P^T g
 void fdm_precondition_u_slab(poro_ctx *c, const double *g_quadrant, double *z_quadrant, const PcgScalars *gate);
+void fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision: of the octant form's transforms
+void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision);   // nodal g -> the form that is built (or the nodal kernels of fdm_precondition_u) -> nodal z
 void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z);
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);

@@ -327,6 +327,19 @@ void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgS
   alltoall_blocks(c, send, recv, (int64_t)S.max_nl * S.scols, true);
   fdmo_slab_pass(s, O, 3, S.buf.p, z, gate);                                          // y, x backward, reading the received planes in place
 }
+// g, z in the layout of the form that is built (c->fdm_oct.built): quadrants on slabs, the planar form in 2D, octants on one rank
+void fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgScalars *gate, int precision) {
+  FdmOct &O = c->fdm_oct;
+  if (O.slab.on) fdm_precondition_u_slab(c, g, z, gate);
+  else if (O.planar) fdmo_apply_planar(c->stream, O, g, z, gate);
+  else fdmo_apply(c->stream, O, g, z, O.t.p, gate, nullptr, nullptr, precision);
+}
+// nodal g -> whichever form of the block FDM is built -> nodal z
+void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision) {
+  FdmOct &O = c->fdm_oct;
+  if (!O.built) { fdm_precondition_u(c, g, z); return; }
+  fdmo_from_nodal(c->stream, O, g, O.g.p); fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, precision); fdmo_to_nodal(c->stream, O, O.z.p, z);
+}
 // ---- additive two-level preconditioner on refinements of a uniform box (poro_desc.coarse) ----------------------------------------------------
 // P holds every local row (prolongation / combination); its transpose (restriction) only the owned rows [0, n_owned), so that the pieces of a general partition
 // sum every global row exactly once (one rank: n_owned = n_fine)
@@ -390,9 +403,7 @@ void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double om
   // partitioned (general pieces): the owned rows' partial restriction, summed over the ranks.  The coarse solve then runs replicated on identical data and the
   // combination below covers every local row, so the copies of a shared dof stay bitwise equal.  One all-reduce per application on every rank alike
   if (c->comm.multi()) allreduce_sum_vec(c, rc, T.n_coarse * dim, "two_level_coarse_allreduce");
-  FdmOct &O = H->fdm_oct;
-  if (O.built) { fdmo_from_nodal(s, O, rc, O.g.p); if (O.planar) fdmo_apply_planar(s, O, O.g.p, O.z.p); else fdmo_apply(s, O, O.g.p, O.z.p, O.t.p); fdmo_to_nodal(s, O, O.z.p, zc); }
-  else fdm_precondition_u(H, rc, zc);                                         // z_H = blockdiag(A_H)^-1 r_H (zero on the box's Dirichlet faces)
+  fdm_precondition_u_nodal(H, rc, zc, PORO_FDM_FP64);                         // z_H = blockdiag(A_H)^-1 r_H (zero on the box's Dirichlet faces)
   la_two_level_combine(s, T.p_ptr.p, T.p_col.p, T.p_w.p, T.n_fine, dim, zc, g, c->dinv_u.p, c->cons_u.inert.p, omega, z, T.lanes);
 }
 

@@ -270,12 +270,11 @@ __global__ void __launch_bounds__(256) k_fdmo_slab_scatter_pack(SlabGeo S, int r
 struct OctPass {
   int mode;                 // 0: contract columns, then rows (pass 1); 1: rows, eigenvalue scaling, rows (pass 2); 2: rows, then columns (pass 3)
   int R, C;                 // valid rows / columns of a block (mode 1: C = columns of a full chunk, the last chunk has fewer)
-  int nt_r, nt_c;           // 16-wide tiles covering them
   int kk1, kk2;             // k-steps (of 4) of the two GEMMs
   int nblk;                 // blocks per (component, octant)
   int64_t co_stride, blk_stride, row_stride;
   int bit1, bit2;           // octant bit that selects the parity of the matrices of GEMM 1 / 2
-  int hx, pl;               // mode 1: columns of a plane = hx hy; a column's plane offset -> (my, mx)
+  int pl;                   // mode 1: columns of a plane = row pitch x hy
   const void *T1[3][2], *T2[3][2];                       // [component][parity], MFMA fragment order [tile][4 NT][64]: doubles (k_fdmo_pass, k_fdmo_zpass_both) or floats (k_fdmo_pass_f32)
   const double *lam_z[3][2]; double cz[3]; const double *bxy;   // mode 1: eigenvalues of the line direction; bxy[(4 c + (o & 3)) pl + column] = the other two directions' share
   const double *in_blk[3]; double *out_blk[3]; int use_in_off, use_out_off;   // batched scalar systems (no_shift = 0, up to 3 blocks = right-hand sides in separate vectors): every block's own vector instead of `in` / `out` + block * co_stride
@@ -317,6 +316,7 @@ template <int NT> struct PassGeom {
 //     mod 4, so that over the items every SIMD gets the same share (6.25 tiles per wave on average; the two GEMM bodies - with and without the seventh tile - are
 //     separate branch-free instruction streams);
 //   pass 2 (lines are independent): chunks of 64 columns = 5 x 4 tiles, wave w owns (w, 0..3) and (4, w): five tiles each, nothing left over.
+// VAR is stated by the host code that builds the descriptor (PassVariant; launch_pass_nt rejects a descriptor whose flags contradict it):
 // VAR = 0: the octant form on one rank (24 blocks, aligned rows, no exchange buffer, no per-block offsets) with those switches folded at compile time;
 // VAR = 1: the quadrant form of the displacement system on slabs (pass 1 stores into / pass 3 loads from the exchange buffer, pass 2 forms the parity parts on load), likewise;
 // VAR = 2: everything else by run-time switches (scalar systems, batched right-hand sides)
@@ -925,66 +925,179 @@ template <int NT> void launch_zpass_both(hipStream_t s, const OctPass &P, const 
   hipExtLaunchKernelGGL((k_fdmo_zpass_both<NT>), dim3((unsigned)n_items), dim3(64 * (NT < 4 ? NT : 4)), 0, s, e0, e1, 0, P, dst, in, out);
 }
 
-// one instantiation: dynamic LDS (more than 64 KB from NT = 6 on: opted in once per device), events attached to the dispatch itself (the kernel's own duration, as rocprofv3 reports it)
-template <int NT, int MODE, int VAR, bool GZ = false> void launch_one(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
-  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(double));
-  auto kernel = k_fdmo_pass<NT, MODE, VAR, GZ>;
+// one instantiation: dynamic LDS of PADN x LDMAX elements (more than 64 KB from NT = 6 on in fp64: opted in once per device and instantiation), events attached to the
+// dispatch itself (the kernel's own duration, as rocprofv3 reports it)
+template <auto Kernel, int NT, class Elem> void launch_one(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(Elem));
   if (lds > 64 * 1024) {
     static std::mutex mu; static std::set<int> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert(dev); }
+    if (!done.count(dev)) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert(dev); }
   }
-  hipExtLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
+  hipExtLaunchKernelGGL(Kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
 }
-template <int NT, int MODE, bool GZ = false> void launch_one_f32(hipStream_t s, int n_items, const OctPass &P, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
-  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(float));
-  auto kernel = k_fdmo_pass_f32<NT, MODE, GZ>;
-  if (lds > 64 * 1024) {
-    static std::mutex mu; static std::set<int> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert(dev); }
-  }
-  hipExtLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
-}
-template <int NT> void launch_pass(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1, bool f32) {
+// The kernel variant of a pass is stated by whoever builds the descriptor.  Octant / SlabU (VAR = 0 / 1 of k_fdmo_pass) fold the flags below at compile time and never read
+// them, General (VAR = 2) reads them, OctantF32 is k_fdmo_pass_f32 (float fragments in P.T1 / P.T2, float intermediate array; it folds what Octant folds)
+enum class PassVariant { Octant, SlabU, General, OctantF32 };
+constexpr const char *kVariantName[] = {"Octant", "SlabU", "General", "OctantF32"};
+PassVariant variant_of_flags(const OctPass &P) {       // the variant whose folded switches equal the descriptor's flags
   const bool plain = P.vec2 == 1 && !P.use_in_off && !P.use_out_off && P.bxy_cmul == 4;
   const bool oct = plain && P.slab_z == 0 && P.slab_io == 0 && !P.row_in && P.no_shift == 3;
   const bool slab_u = plain && P.no_shift == 2 && ((P.mode == 0 && P.slab_io == 1 && !P.slab_z) || (P.mode == 1 && P.slab_z == 2 && P.row_in && !P.slab_io) || (P.mode == 2 && P.slab_io == 2 && !P.slab_z));
-  if (f32) {       // fp32 mode: P.T1 / P.T2 hold float fragments, the intermediate array is float
-    if (!oct) throw Error("fdmo: fp32 transforms exist for the single-rank octant form only");
-    if (P.mode == 0) launch_one_f32<NT, 0>(s, n_items, P, in, out, e0, e1);
-    else if (P.mode == 1) { if (P.gz_part) launch_one_f32<NT, 1, true>(s, n_items, P, in, out, e0, e1); else launch_one_f32<NT, 1>(s, n_items, P, in, out, e0, e1); }
-    else launch_one_f32<NT, 2>(s, n_items, P, in, out, e0, e1);
-  } else if (oct) {
-    if (P.mode == 0) launch_one<NT, 0, 0>(s, n_items, P, in, out, e0, e1);
-    else if (P.mode == 1) { if (P.gz_part) launch_one<NT, 1, 0, true>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 1, 0>(s, n_items, P, in, out, e0, e1); }
-    else launch_one<NT, 2, 0>(s, n_items, P, in, out, e0, e1);
-  } else if (slab_u) {
-    if (P.mode == 0) launch_one<NT, 0, 1>(s, n_items, P, in, out, e0, e1); else if (P.mode == 1) launch_one<NT, 1, 1>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 2, 1>(s, n_items, P, in, out, e0, e1);
-  } else {
-    if (P.mode == 0) launch_one<NT, 0, 2>(s, n_items, P, in, out, e0, e1); else if (P.mode == 1) launch_one<NT, 1, 2>(s, n_items, P, in, out, e0, e1); else launch_one<NT, 2, 2>(s, n_items, P, in, out, e0, e1);
+  return oct ? PassVariant::Octant : slab_u ? PassVariant::SlabU : PassVariant::General;
+}
+template <int NT, int VAR> void launch_modes(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+  if (P.mode == 0) launch_one<k_fdmo_pass<NT, 0, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
+  else if (P.mode == 2) launch_one<k_fdmo_pass<NT, 2, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
+  else if (VAR == 0 && P.gz_part) launch_one<k_fdmo_pass<NT, 1, 0, true>, NT, double>(s, n_items, P, in, out, e0, e1);
+  else launch_one<k_fdmo_pass<NT, 1, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
+}
+template <int NT> void launch_pass(hipStream_t s, PassVariant v, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+  switch (v) {
+    case PassVariant::Octant: launch_modes<NT, 0>(s, P, n_items, in, out, e0, e1); break;
+    case PassVariant::SlabU: launch_modes<NT, 1>(s, P, n_items, in, out, e0, e1); break;
+    case PassVariant::General: launch_modes<NT, 2>(s, P, n_items, in, out, e0, e1); break;
+    case PassVariant::OctantF32:
+      if (P.mode == 0) launch_one<k_fdmo_pass_f32<NT, 0>, NT, float>(s, n_items, P, in, out, e0, e1);
+      else if (P.mode == 2) launch_one<k_fdmo_pass_f32<NT, 2>, NT, float>(s, n_items, P, in, out, e0, e1);
+      else if (P.gz_part) launch_one<k_fdmo_pass_f32<NT, 1, true>, NT, float>(s, n_items, P, in, out, e0, e1);
+      else launch_one<k_fdmo_pass_f32<NT, 1>, NT, float>(s, n_items, P, in, out, e0, e1);
+      break;
   }
 }
-void launch_pass_nt(hipStream_t s, int nt, const OctPass &P, int n_blocks, const double *in, double *out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, bool f32 = false) {
+void launch_pass_nt(hipStream_t s, int nt, PassVariant v, const OctPass &P, int n_blocks, const double *in, double *out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  const PassVariant flags = variant_of_flags(P);
+  if (flags != (v == PassVariant::OctantF32 ? PassVariant::Octant : v)) throw Error(std::string("fdmo: pass stated as ") + kVariantName[(int)v] + ", the flags of its descriptor are those of " + kVariantName[(int)flags]);
   switch (nt) {
-    case 1: launch_pass<1>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 2: launch_pass<2>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 3: launch_pass<3>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 4: launch_pass<4>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 5: launch_pass<5>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 6: launch_pass<6>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 7: launch_pass<7>(s, P, n_blocks, in, out, e0, e1, f32); break;
-    case 8: launch_pass<8>(s, P, n_blocks, in, out, e0, e1, f32); break;
+    case 1: launch_pass<1>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 2: launch_pass<2>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 3: launch_pass<3>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 4: launch_pass<4>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 5: launch_pass<5>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 6: launch_pass<6>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 7: launch_pass<7>(s, v, P, n_blocks, in, out, e0, e1); break;
+    case 8: launch_pass<8>(s, v, P, n_blocks, in, out, e0, e1); break;
     default: throw Error("fdmo: half lines of more than 128 entries");
   }
 }
 // columns of a pass-2 chunk: one 16-wide tile per wave (NT = 5: four waves)
 inline int pass2_chunk(int nt) { return nt == 5 ? 64 : 16 * nt; }
+inline int pass2_chunks(int pl, int nt) { return (pl + pass2_chunk(nt) - 1) / pass2_chunk(nt); }   // chunks of a plane of pl positions = workgroups of pass 2 per block (one rank)
 inline int oct_grid(int64_t co, int nc = 3) { return (int)std::min<int64_t>((nc * co + kBlock - 1) / kBlock, kMaxPartials); }   // threads = positions x components, as many per thread as the partial slots demand
 OctDims dims_of(const FdmOct &O) { return OctDims{O.n[0], O.n[1], O.n[2], O.h[0], O.h[1], O.h[2], O.hxp, O.co_stride, O.no, O.own_z, O.nc}; }
 SlabGeo geo_of(const FdmOct &O) { const auto &S = O.slab; return SlabGeo{S.cw, S.nchunk, S.cps, S.nb * S.nchunk, S.rank, S.my_chunks, S.hzg, S.ng, S.np, S.scols, (int64_t)O.hxp * O.h[1], O.co_stride}; }
 
+// ---- the pass plan: one description of a form, one builder of the three launch descriptors ---------------------------------------------------------------------------
+// A form = what the passes need to know about the arrays they sweep: `blocks` blocks of planes() z-planes of hy() rows of `pitch` entries, hx() of them transformed.  Pass 2
+// takes lines of zlen() entries in chunks of cw() columns: the z lines of the blocks themselves (one rank) or blocks [zlen][cw] of the transposed array (slabs: global lines)
+struct Form {
+  const FdmOct &O; bool scalar, f32;   // scalar: every block = a right-hand side of one scalar Q1 system (one set of matrices); f32: the float fragments
+  int pitch, blocks, no_shift;         // blocks of the arrays = components (right-hand sides) x parity parts; log2 of the parity parts
+  int nc, np, vec2, bxy_cmul;          // components and parities that have matrices
+  double kappa; const double *bxy;     // scalar: the z coefficient; x / y share of the eigenvalue sums
+  int hx() const { return O.h[0]; } int hy() const { return O.h[1]; } int planes() const { return O.h[2]; }
+  int zlen() const { return O.slab.on ? O.slab.hzg : O.h[2]; } int cw() const { return O.slab.on ? O.slab.cw : pass2_chunk(O.nt); }
+  const void *fwd(int c, int d, int p) const { c = scalar ? 0 : c; return f32 ? (const void *)O.fwd32[c][d][p].p : (const void *)O.fwd[c][d][p].p; }
+  const void *bwd(int c, int d, int p) const { c = scalar ? 0 : c; return f32 ? (const void *)O.bwd32[c][d][p].p : (const void *)O.bwd[c][d][p].p; }
+  const double *lam_z(int c, int p) const { return O.lam[scalar ? 0 : c][2][p].p; } double cz(int c) const { return scalar ? kappa : O.coef[c][2]; }
+};
+// displacement system (octants on one rank, quadrants on slabs; rows padded to even length) / nb right-hand sides of the scalar Q1 system a M + kappa K (nodal layout)
+Form disp_form(const FdmOct &O, bool f32) { return Form{O, false, f32, O.hxp, 3 * O.no, O.slab.on ? 2 : 3, 3, 2, 1, 4, 0.0, O.bxy.p}; }
+Form scalar_form(const FdmOct &O, int nb, double kappa, const double *table) { return Form{O, true, false, O.h[0], nb, 0, nb, 1, 0, 0, kappa, table}; }
+// pass 1: per z-plane X[ky][kx] -> Fy (X Fx^T); pass 2: per chunk of cw columns X[kz][col] -> Bz scale (Fz X); pass 3: per z-plane X[my][mx] -> (By X) Bx^T.
+// Everything but the per-call fields (gate, gz_part, in_blk / out_blk, stamps) and the slab extras (plan_slab_pass)
+OctPass plan_pass(const Form &F, int pass) {
+  auto ksteps = [](int n) { return (n + 3) / 4; };
+  const int hx = F.hx(), hy = F.hy(), zlen = F.zlen(), cw = F.cw(), pl = F.pitch * hy; const bool first = pass == 1, transposed = F.O.slab.on;
+  OctPass P{};
+  P.co_stride = F.O.co_stride; P.pl = pl; P.bxy = F.bxy; P.vec2 = F.vec2; P.no_shift = F.no_shift; P.bxy_cmul = F.bxy_cmul;
+  if (pass == 2) {       // (transposed: one block [zlen][cw] per workgroup instead of cw columns of a block of the array)
+    P.mode = 1; P.R = zlen; P.C = cw; P.kk1 = P.kk2 = ksteps(zlen); P.bit1 = P.bit2 = 2;
+    P.nblk = transposed ? 1 : pass2_chunks(pl, F.O.nt); P.blk_stride = transposed ? (int64_t)zlen * cw : cw; P.row_stride = transposed ? cw : pl;
+  } else {
+    P.mode = first ? 0 : 2; P.R = hy; P.C = F.pitch; P.kk1 = ksteps(first ? hx : hy); P.kk2 = ksteps(first ? hy : hx); P.bit1 = first ? 0 : 1; P.bit2 = first ? 1 : 0;
+    P.nblk = F.planes(); P.blk_stride = pl; P.row_stride = F.pitch;
+  }
+  for (int c = 0; c < F.nc; ++c) {
+    P.cz[c] = F.cz(c);
+    for (int p = 0; p < F.np; ++p) {
+      P.lam_z[c][p] = F.lam_z(c, p);
+      if (pass == 1) { P.T1[c][p] = F.fwd(c, 0, p); P.T2[c][p] = F.fwd(c, 1, p); }
+      else if (pass == 2) { P.T1[c][p] = F.fwd(c, 2, p); P.T2[c][p] = F.bwd(c, 2, p); }
+      else { P.T1[c][p] = F.bwd(c, 1, p); P.T2[c][p] = F.bwd(c, 0, p); }
+    }
+  }
+  return P;
+}
+// slab form: the same plan + where the pass meets the exchange buffer (see OctPass): pass 1 stores into it, pass 3 loads from it, pass 2 gathers whole lines from it
+OctPass plan_slab_pass(const Form &F, int pass) {
+  const auto &S = F.O.slab;
+  OctPass P = plan_pass(F, pass);
+  if (pass == 2) {
+    P.slab_z = S.np; P.chunk0 = S.chunk0; P.chunk_total = S.nb * S.nchunk; P.nchunk = S.nchunk; P.row_in = S.row_in.p; P.ng = S.ng;
+    P.vec2 = 1;                              // (the planes in the exchange buffer are 16-byte aligned whatever the layout of the form's own vectors)
+  } else {
+    const bool first = pass == 1;
+    P.slab_io = first ? 1 : 2; P.store_planes = S.own; P.scols = (int)S.scols; P.inv_scols = 1.0f / (float)S.scols; P.col_unit = S.nchunk * S.cw; P.rank = S.rank;
+    P.dest_stride = (int64_t)((first ? S.max_own : S.max_nl) - 1) * S.scols; P.recv_off = S.recv_off;
+  }
+  return P;
+}
+// diagnostic (PORO_FDMO_STAMPS = file name): the third application of the process records the per-block time stamps of its three passes (OctPass::stamps) and
+// writes them as lines "pass block t0 .. t5 hw_id xcc_id" (tools/fdmo_stamps.py)
+struct PassStamps {
+  bool on = false; DevBuf<unsigned long long> buf; int items[3] = {0, 0, 0};
+  static const char *path() { static const char *p = std::getenv("PORO_FDMO_STAMPS"); return p; }
+  PassStamps() { static int calls = 0; on = path() && ++calls == 3; }
+  void attach(hipStream_t s, OctPass (&P)[3], const int (&n_items)[3]) {
+    if (!on) return;
+    buf.alloc((size_t)8 * (n_items[0] + n_items[1] + n_items[2])); buf.zero(s);
+    for (int k = 0, at = 0; k < 3; at += n_items[k++]) { items[k] = n_items[k]; P[k].stamps = buf.p + 8 * (int64_t)at; }
+  }
+  void dump(hipStream_t s) {
+    if (!on) return;
+    PORO_HIP(hipStreamSynchronize(s));
+    std::vector<unsigned long long> h(buf.n); PORO_HIP(hipMemcpy(h.data(), buf.p, buf.n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    FILE *f = std::fopen(path(), "w"); const unsigned long long *r = h.data();
+    for (int pass = 0; f && pass < 3; ++pass) for (int b = 0; b < items[pass]; ++b, r += 8) std::fprintf(f, "%d %d %llu %llu %llu %llu %llu %llu %llu %llu\n", pass, b, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+    if (f) std::fclose(f);
+  }
+};
+// a rows x cols matrix el(r, c) in MFMA fragment order [tile][4 NT][64]: lane l of fragment (tile, kk) holds element (16 tile + (l & 15), 4 kk + (l >> 4)); zero beyond
+template <class El> std::vector<double> pack_fragments(int nt, int rows, int cols, El el) {
+  const int kkp = 4 * nt;
+  std::vector<double> M((size_t)nt * kkp * 64, 0.0);
+  for (int t = 0; t < nt; ++t) for (int kk = 0; kk < kkp; ++kk) for (int l = 0; l < 64; ++l) {
+    const int r = 16 * t + (l & 15), c = 4 * kk + (l >> 4);
+    if (r < rows && c < cols) M[((size_t)t * kkp + kk) * 64 + l] = el(r, c);
+  }
+  return M;
+}
+// sizes of a 3D form: half lines in the first `nsplit` directions (parity split, `no` parity parts), whole lines in the others; rows padded to even length where x is split.
+// On slabs (slab_prologue first) the transformed z line is the global one, split in parities whenever x and y are.  coef != null (displacement system): g, z, t in the form's layout
+void form_geometry(FdmOct &O, const int nn[3], const double (*coef)[3], int nsplit, int no, hipStream_t s) {
+  const int zline = O.slab.on ? O.slab.ng : nn[2]; int hmax = nsplit ? (zline + 1) / 2 : zline;
+  for (int d = 0; d < 3; ++d) {
+    O.n[d] = nn[d]; O.h[d] = d < nsplit ? (nn[d] + 1) / 2 : nn[d];
+    if (d < 2) hmax = std::max(hmax, O.h[d]);
+    for (int c = 0; coef && c < 3; ++c) O.coef[c][d] = coef[c][d];
+  }
+  O.nt = (hmax + 15) / 16; O.hxp = nsplit ? (O.h[0] + 1) & ~1 : O.h[0]; O.no = no;
+  O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = (coef ? 3 : 1) * no * O.co_stride;
+  if (coef) { O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct); O.g.zero(s); O.z.zero(s); O.t.zero(s); }
+}
+// slab forms: the ranks' layers -> global line length; this rank's planes must match its entry
+void slab_prologue(FdmOct &O, const int nn[3], int rank, const std::vector<int> &node_layers, const char *who) {
+  auto &S = O.slab; const int N = (int)node_layers.size();
+  S.on = true; S.n_ranks = N; S.rank = rank;
+  S.ng = 1; for (int q = 0; q < N; ++q) S.ng += node_layers[q];
+  if (nn[2] != node_layers[rank] + 1) throw Error(std::string(who) + ": local planes do not match the layer table");
+}
+
 }  // namespace
+
+// everything of the three passes of a displacement form that does not change from one application to the next: [fp64 / fp32 fragments][pass]
+struct FdmoPlans { OctPass pass[2][3]; int n_items[3]; };
 
 bool fdmo_usable(int dim, const int nn[3]) {
   if (dim != 3) return false;
@@ -993,15 +1106,9 @@ bool fdmo_usable(int dim, const int nn[3]) {
 }
 
 void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s) {
-  int hmax = 1;
-  for (int d = 0; d < 3; ++d) { O.n[d] = nn[d]; O.h[d] = (nn[d] + 1) / 2; hmax = std::max(hmax, O.h[d]); for (int c = 0; c < 3; ++c) O.coef[c][d] = coef[c][d]; }
-  O.nt = (hmax + 15) / 16;
-  O.hxp = (O.h[0] + 1) & ~1;
-  O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = 24 * O.co_stride; O.no = 8; O.own_z = O.n[2];
-  O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct);
-  O.g.zero(s); O.z.zero(s); O.t.zero(s);
-  const int cw = pass2_chunk(O.nt);
-  O.gz_n = 24 * ((O.hxp * O.h[1] + cw - 1) / cw);       // workgroups of pass 2: one g . z partial each (grows with the box - not bounded by kMaxPartials)
+  form_geometry(O, nn, coef, 3, 8, s);
+  O.own_z = O.n[2];
+  O.gz_n = 24 * pass2_chunks(O.hxp * O.h[1], O.nt);   // workgroups of pass 2: one g . z partial each (grows with the box - not bounded by kMaxPartials)
   O.gz_part.alloc(O.gz_n); O.gz_part.zero(s);
 }
 // chunks, shares, plane tables and buffers of the slab form, after n / h / hxp / nt / co_stride are set: nb blocks per plane position set, np parity parts of a z line
@@ -1031,34 +1138,20 @@ static void slab_layout(FdmOct &O, int nb, int np, int rank, const std::vector<i
   if (!S.zboth) { S.tz.alloc((size_t)np * S.cps * S.hzg * S.cw); S.tz.zero(s); }      // (the both-parity z pass goes from the gathered planes straight to the scattered ones)
 }
 void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int rank, const std::vector<int> &node_layers, bool has_upper, hipStream_t s) {
-  auto &S = O.slab; const int N = (int)node_layers.size();
-  S.on = true; S.n_ranks = N; S.rank = rank;
-  S.ng = 1; for (int q = 0; q < N; ++q) S.ng += node_layers[q];
-  if (nn[2] != node_layers[rank] + 1) throw Error("fdmo_init_slab: local planes do not match the layer table");
-  int hmax = (S.ng + 1) / 2;
-  for (int d = 0; d < 3; ++d) { O.n[d] = nn[d]; O.h[d] = d < 2 ? (nn[d] + 1) / 2 : nn[d]; if (d < 2) hmax = std::max(hmax, O.h[d]); for (int c = 0; c < 3; ++c) O.coef[c][d] = coef[c][d]; }
-  O.nt = (hmax + 15) / 16;
-  O.hxp = (O.h[0] + 1) & ~1; O.no = 4; O.own_z = has_upper ? nn[2] - 1 : nn[2];
-  O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = 12 * O.co_stride;
-  O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct);
-  O.g.zero(s); O.z.zero(s); O.t.zero(s);
+  slab_prologue(O, nn, rank, node_layers, "fdmo_init_slab");
+  form_geometry(O, nn, coef, 2, 4, s);
+  O.own_z = has_upper ? nn[2] - 1 : nn[2];
   slab_layout(O, 12, 2, rank, node_layers, s);
 }
 // scalar Q1 system on a slab: nodal layout [local plane][y][x], whole-length lines everywhere (no parity split)
 void fdmo_scalar_init_slab(FdmOct &O, const int nn[3], int rank, const std::vector<int> &node_layers, hipStream_t s) {
-  auto &S = O.slab; const int N = (int)node_layers.size();
-  S.on = true; S.n_ranks = N; S.rank = rank;
-  S.ng = 1; for (int q = 0; q < N; ++q) S.ng += node_layers[q];
-  if (nn[2] != node_layers[rank] + 1) throw Error("fdmo_scalar_init_slab: local planes do not match the layer table");
-  int hmax = S.ng;
-  for (int d = 0; d < 3; ++d) { O.n[d] = nn[d]; O.h[d] = nn[d]; if (d < 2) hmax = std::max(hmax, nn[d]); }
-  O.nt = (hmax + 15) / 16; O.hxp = nn[0]; O.no = 1;
-  O.co_stride = (int64_t)nn[0] * nn[1] * nn[2]; O.n_oct = O.co_stride;
+  slab_prologue(O, nn, rank, node_layers, "fdmo_scalar_init_slab");
+  form_geometry(O, nn, nullptr, 0, 1, s);
   slab_layout(O, 1, 1, rank, node_layers, s);
 }
 
 bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn) {
-  const int h = (nn + 1) / 2, nt = O.nt, kkp = 4 * nt, padn = 16 * nt;
+  const int h = (nn + 1) / 2, nt = O.nt, padn = 16 * nt;
   if (nn != (O.slab.on && dir == 2 ? O.slab.ng : O.n[dir])) throw Error("fdmo_upload_dir: line length mismatch");
   std::vector<int> grp[2];
   for (int m = 0; m < nn; ++m) {
@@ -1069,16 +1162,10 @@ bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S,
   }
   for (int p = 0; p < 2; ++p) {
     if ((int)grp[p].size() > h) return false;
-    // forward F[m][k] = S[k][mode m] (rows = modes of the parity group, columns = lower-half nodes), backward B[k][m] = S[k][mode m]; both as [tile][4 NT][64]:
-    // lane l of fragment (tile, kk) holds element (16 tile + (l & 15), 4 kk + (l >> 4))
-    std::vector<double> F((size_t)nt * kkp * 64, 0.0), B((size_t)nt * kkp * 64, 0.0), lp(padn + 16, std::numeric_limits<double>::infinity());
+    // forward F[m][k] = S[k][mode m] (rows = modes of the parity group, columns = lower-half nodes), backward B[k][m] = S[k][mode m]
     const int ng = (int)grp[p].size();
-    for (int t = 0; t < nt; ++t) for (int kk = 0; kk < kkp; ++kk) for (int l = 0; l < 64; ++l) {
-      const int r = 16 * t + (l & 15), cc = 4 * kk + (l >> 4);
-      const size_t at = ((size_t)t * kkp + kk) * 64 + l;
-      if (r < ng && cc < h) F[at] = S[(size_t)cc * nn + grp[p][r]];
-      if (r < h && cc < ng) B[at] = S[(size_t)r * nn + grp[p][cc]];
-    }
+    const std::vector<double> F = pack_fragments(nt, ng, h, [&](int r, int cc) { return S[(size_t)cc * nn + grp[p][r]]; }), B = pack_fragments(nt, h, ng, [&](int r, int cc) { return S[(size_t)r * nn + grp[p][cc]]; });
+    std::vector<double> lp(padn + 16, std::numeric_limits<double>::infinity());
     for (int m = 0; m < ng; ++m) lp[m] = lam[grp[p][m]];
     O.h_lam[comp][dir][p] = lp;
     O.fwd[comp][dir][p].upload(F); O.bwd[comp][dir][p].upload(B); O.lam[comp][dir][p].upload(lp);
@@ -1095,87 +1182,41 @@ void fdmo_finalize(FdmOct &O) {
   for (int c = 0; c < 3; ++c) for (int py = 0; py < 2; ++py) for (int px = 0; px < 2; ++px) for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx)
     B[(size_t)(4 * c + 2 * py + px) * pl + (size_t)my * hxp + mx] = O.coef[c][0] * O.h_lam[c][0][px][mx] + O.coef[c][1] * O.h_lam[c][1][py][my];
   O.bxy.upload(B);
+  auto plans = std::make_shared<FdmoPlans>();
+  for (int f32 = 0; f32 < (O.slab.on ? 1 : 2); ++f32) for (int k = 0; k < 3; ++k) {
+    const Form F = disp_form(O, f32 != 0);
+    plans->pass[f32][k] = O.slab.on ? plan_slab_pass(F, k + 1) : plan_pass(F, k + 1);
+    plans->n_items[k] = F.blocks * plans->pass[f32][k].nblk;
+  }
+  O.plans = plans;
 }
 
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part, int precision) {
   const bool f32 = precision == PORO_FDM_FP32;     // fp32 transforms: float fragments, `scratch` holds the intermediate array as floats (g_oct, z_oct stay fp64)
   if (f32 && (O.slab.on || O.planar || !O.fwd32[0][0][0].p)) throw Error("fdmo_apply: fp32 transforms exist for the single-rank octant form only");
-  auto fw = [&](int c, int d, int p) -> const void * { return f32 ? (const void *)O.fwd32[c][d][p].p : (const void *)O.fwd[c][d][p].p; };
-  auto bw = [&](int c, int d, int p) -> const void * { return f32 ? (const void *)O.bwd32[c][d][p].p : (const void *)O.bwd[c][d][p].p; };
-  static int stamp_calls = 0; const char *stamp_path = std::getenv("PORO_FDMO_STAMPS");
-  const bool stamping = stamp_path && ++stamp_calls == 3;          // diagnostic: the third application of the process writes its per-block time stamps
-  DevBuf<unsigned long long> stamps; std::vector<std::pair<int, int64_t>> stamp_off;
-  const int nt = O.nt, hx = O.h[0], hy = O.h[1], hz = O.h[2], hxp = O.hxp;
-  auto tiles = [](int n) { return (n + 15) / 16; };
-  auto ksteps = [](int n) { return (n + 3) / 4; };
-  OctPass P{};
-  P.co_stride = O.co_stride; P.hx = hxp; P.pl = hxp * hy;
-  P.bxy = O.bxy.p; P.gate = gate; P.vec2 = 1; P.no_shift = 3; P.bxy_cmul = 4;
-  for (int c = 0; c < 3; ++c) { P.cz[c] = O.coef[c][2]; for (int p = 0; p < 2; ++p) P.lam_z[c][p] = O.lam[c][2][p].p; }
-  // pass 1: per z-plane, X[ky][kx] -> Fy (X Fx^T)
-  P.mode = 0; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hx); P.kk2 = ksteps(hy); P.nblk = hz; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp; P.bit1 = 0; P.bit2 = 1;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = fw(c, 0, p); P.T2[c][p] = fw(c, 1, p); }
-  if (stamping) { stamps.alloc((size_t)8 * 24 * (O.h[2] + (hxp * hy + pass2_chunk(nt) - 1) / pass2_chunk(nt) + O.h[2])); stamps.zero(s); }
-  P.stamps = stamping ? stamps.p : nullptr; stamp_off.push_back({24 * P.nblk, 0});
-  launch_pass_nt(s, nt, P, 24 * P.nblk, g_oct, scratch, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, f32);
-  // pass 2: per chunk of 16 NT columns of a (component, octant) block, X[kz][col] -> Bz scale (Fz X), in place
-  const int cw = pass2_chunk(nt);                 // chunk width of pass 2: one column tile per wave (NT = 5: 5 x 4 tiles for the four waves of the workgroup)
-  P.mode = 1; P.R = hz; P.C = cw; P.nt_r = tiles(hz); P.nt_c = cw / 16; P.kk1 = ksteps(hz); P.kk2 = ksteps(hz); P.nblk = (hxp * hy + cw - 1) / cw; P.blk_stride = cw; P.row_stride = (int64_t)hxp * hy; P.bit1 = 2; P.bit2 = 2;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = fw(c, 2, p); P.T2[c][p] = bw(c, 2, p); }
-  if (stamping) P.stamps = stamps.p + 8 * (int64_t)(24 * hz); stamp_off.push_back({24 * P.nblk, 8 * (int64_t)(24 * hz)});
-  if (gz_part && 24 * P.nblk != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
-  P.gz_part = gz_part;
-  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, scratch, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, f32);
-  P.gz_part = nullptr;
-  // pass 3: per z-plane, X[my][mx] -> (By X) Bx^T
-  P.mode = 2; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hy); P.kk2 = ksteps(hx); P.nblk = hz; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp; P.bit1 = 1; P.bit2 = 0;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = bw(c, 1, p); P.T2[c][p] = bw(c, 0, p); }
-  if (stamping) P.stamps = stamps.p + 8 * (int64_t)(24 * hz + stamp_off[1].first); stamp_off.push_back({24 * P.nblk, 8 * (int64_t)(24 * hz + stamp_off[1].first)});
-  launch_pass_nt(s, nt, P, 24 * P.nblk, scratch, z_oct, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr, f32);
-  if (stamping) {
-    PORO_HIP(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h(stamps.n); PORO_HIP(hipMemcpy(h.data(), stamps.p, stamps.n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (FILE *f = std::fopen(stamp_path, "w")) {
-      for (int pass = 0; pass < 3; ++pass) for (int b = 0; b < stamp_off[pass].first; ++b) {
-        const unsigned long long *r = h.data() + stamp_off[pass].second + 8 * (int64_t)b;
-        std::fprintf(f, "%d %d %llu %llu %llu %llu %llu %llu %llu %llu\n", pass, b, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
-      }
-      std::fclose(f);
-    }
-  }
+  OctPass P[3]; const int (&n_items)[3] = O.plans->n_items;
+  for (int k = 0; k < 3; ++k) { P[k] = O.plans->pass[f32][k]; P[k].gate = gate; }
+  if (gz_part && n_items[1] != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
+  P[1].gz_part = gz_part;
+  PassStamps stamps; stamps.attach(s, P, n_items);
+  const double *const in[3] = {g_oct, scratch, scratch}; double *const out[3] = {scratch, scratch, z_oct};      // (pass 2 works in place)
+  for (int k = 0; k < 3; ++k) launch_pass_nt(s, O.nt, f32 ? PassVariant::OctantF32 : PassVariant::Octant, P[k], n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
+  stamps.dump(s);
 }
 
 // ---- slab form: the three sweeps as separate entry points (two all-to-alls sit between them, ctx_prec.hip) ----
 void fdmo_slab_pass(hipStream_t s, const FdmOct &O, int pass, const double *in, double *out, const PcgScalars *gate, hipEvent_t e0, hipEvent_t e1) {
-  const auto &S = O.slab; const int nt = O.nt, hx = O.h[0], hy = O.h[1], nzl = O.h[2], hxp = O.hxp;
-  auto tiles = [](int n) { return (n + 15) / 16; };
-  auto ksteps = [](int n) { return (n + 3) / 4; };
-  OctPass P{};
-  P.co_stride = O.co_stride; P.hx = hxp; P.pl = hxp * hy; P.bxy = O.bxy.p; P.gate = gate; P.vec2 = 1; P.no_shift = 2; P.bxy_cmul = 4;
-  for (int c = 0; c < 3; ++c) { P.cz[c] = O.coef[c][2]; for (int p = 0; p < 2; ++p) P.lam_z[c][p] = O.lam[c][2][p].p; }
-  if (pass == 2) {
-    P.mode = 1; P.R = S.hzg; P.C = S.cw; P.nt_r = tiles(S.hzg); P.nt_c = S.cw / 16; P.kk1 = P.kk2 = ksteps(S.hzg); P.nblk = 1; P.blk_stride = (int64_t)S.hzg * S.cw; P.row_stride = S.cw; P.bit1 = P.bit2 = 2;
-    P.slab_z = 2; P.chunk0 = S.chunk0; P.chunk_total = 12 * S.nchunk; P.nchunk = S.nchunk; P.row_in = S.row_in.p; P.ng = S.ng;
-    for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = O.fwd[c][2][p].p; P.T2[c][p] = O.bwd[c][2][p].p; }
-    if (S.zboth) {       // both parity parts per workgroup: `in` and `out` are the exchange buffer (gathered planes in, scattered planes out)
-      if (S.my_chunks > 0) switch (nt) {
-        case 2: launch_zpass_both<2>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
-        case 4: launch_zpass_both<4>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
-        case 5: launch_zpass_both<5>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
-        default: throw Error("fdmo: both-parity z pass needs 2, 4 or 5 tiles per half line");
-      }
-      return;
-    }
-    if (S.my_chunks > 0) launch_pass_nt(s, nt, P, 2 * S.my_chunks, in, out, e0, e1);
-    return;
+  const auto &S = O.slab;
+  OctPass P = O.plans->pass[0][pass - 1]; P.gate = gate;
+  if (pass != 2) launch_pass_nt(s, O.nt, PassVariant::SlabU, P, O.plans->n_items[pass - 1], in, out, e0, e1);
+  else if (S.my_chunks <= 0) return;
+  else if (!S.zboth) launch_pass_nt(s, O.nt, PassVariant::SlabU, P, 2 * S.my_chunks, in, out, e0, e1);
+  else switch (O.nt) {       // both parity parts per workgroup: `in` and `out` are the exchange buffer (gathered planes in, scattered planes out)
+    case 2: launch_zpass_both<2>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
+    case 4: launch_zpass_both<4>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
+    case 5: launch_zpass_both<5>(s, P, S.dst2.p, S.my_chunks, in, out, e0, e1); break;
+    default: throw Error("fdmo: both-parity z pass needs 2, 4 or 5 tiles per half line");
   }
-  const bool first = pass == 1;
-  P.mode = first ? 0 : 2; P.R = hy; P.C = hxp; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(first ? hx : hy); P.kk2 = ksteps(first ? hy : hx); P.nblk = nzl; P.blk_stride = (int64_t)hxp * hy; P.row_stride = hxp;
-  P.bit1 = first ? 0 : 1; P.bit2 = first ? 1 : 0;
-  for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) { P.T1[c][p] = first ? O.fwd[c][0][p].p : O.bwd[c][1][p].p; P.T2[c][p] = first ? O.fwd[c][1][p].p : O.bwd[c][0][p].p; }
-  P.slab_io = first ? 1 : 2; P.store_planes = S.own; P.scols = (int)S.scols; P.inv_scols = 1.0f / (float)S.scols; P.col_unit = S.nchunk * S.cw; P.rank = S.rank;
-  P.dest_stride = (int64_t)((first ? S.max_own : S.max_nl) - 1) * S.scols; P.recv_off = S.recv_off;
-  launch_pass_nt(s, nt, P, 12 * P.nblk, in, out, e0, e1);
 }
 static int copy_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096)); }
 void fdmo_slab_scatter_pack(hipStream_t s, const FdmOct &O, const PcgScalars *gate) {
@@ -1190,22 +1231,15 @@ void fdmo_dot_owned(hipStream_t s, const FdmOct &O, const double *a, const doubl
 // vectors keep their nodal layout [z][y][x] (full-length lines, odd pitch: 8-byte block loads).  Replaces six single-direction launches of kernels_fdm.hip.
 bool fdmo_scalar_usable(int dim, const int nn[3]) { if (dim != 3) return false; for (int d = 0; d < 3; ++d) if (nn[d] > 16 * kFdmoMaxTiles || nn[d] < 2) return false; return true; }
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s) {
-  int hmax = 1;
-  for (int d = 0; d < 3; ++d) { O.n[d] = nn[d]; O.h[d] = nn[d]; hmax = std::max(hmax, nn[d]); }
-  O.nt = (hmax + 15) / 16; O.hxp = nn[0];
-  O.co_stride = (int64_t)nn[0] * nn[1] * nn[2]; O.n_oct = O.co_stride;
+  form_geometry(O, nn, nullptr, 0, 1, s);
   O.t.alloc(3 * O.n_oct); O.t.zero(s);      // (scratch for up to three right-hand sides at once)
 }
 void fdmo_scalar_upload_dir(FdmOct &O, int dir, const std::vector<double> &S, const std::vector<double> &lam, int n) {   // S: n x n row-major, columns = M-orthonormal eigenvectors
   if (n != (O.slab.on && dir == 2 ? O.slab.ng : O.n[dir])) throw Error("fdmo_scalar_upload_dir: line length mismatch");
-  const int nt = O.nt, kkp = 4 * nt, padn = 16 * nt;
-  std::vector<double> F((size_t)nt * kkp * 64, 0.0), B((size_t)nt * kkp * 64, 0.0), lp(padn + 16, std::numeric_limits<double>::infinity());
-  for (int t = 0; t < nt; ++t) for (int kk = 0; kk < kkp; ++kk) for (int l = 0; l < 64; ++l) {
-    const int r = 16 * t + (l & 15), cc = 4 * kk + (l >> 4);
-    if (r < n && cc < n) { F[((size_t)t * kkp + kk) * 64 + l] = S[(size_t)cc * n + r]; B[((size_t)t * kkp + kk) * 64 + l] = S[(size_t)r * n + cc]; }
-  }
+  std::vector<double> lp(16 * O.nt + 16, std::numeric_limits<double>::infinity());
   for (int m = 0; m < n; ++m) lp[m] = lam[m];
-  O.h_lam[0][dir][0] = lp; O.fwd[0][dir][0].upload(F); O.bwd[0][dir][0].upload(B); O.lam[0][dir][0].upload(lp);
+  O.h_lam[0][dir][0] = lp; O.lam[0][dir][0].upload(lp);
+  O.fwd[0][dir][0].upload(pack_fragments(O.nt, n, n, [&](int r, int cc) { return S[(size_t)cc * n + r]; })); O.bwd[0][dir][0].upload(pack_fragments(O.nt, n, n, [&](int r, int cc) { return S[(size_t)r * n + cc]; }));
 }
 static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kappa);
 // z = (a M + kappa K)^-1 g; the x / y share a + kappa (lam_x + lam_y) of the eigenvalue sums is tabulated per plane position, one table per (a, kappa)
@@ -1216,26 +1250,15 @@ void fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const d
 // the same for up to three right-hand sides in separate vectors: one set of three launches with 3 x the workgroups (the Q1 systems of config 4 fill less than a third of the chip)
 void fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate) {
   if (nb < 1 || nb > 3) throw Error("fdmo_scalar_apply_many: 1..3 right-hand sides");
-  const int nt = O.nt, hx = O.h[0], hy = O.h[1], hz = O.h[2];
-  const double *table = scalar_table(s, O, a, kappa);
-  auto tiles = [](int n) { return (n + 15) / 16; };
-  auto ksteps = [](int n) { return (n + 3) / 4; };
-  OctPass P{};
-  P.co_stride = O.co_stride; P.hx = hx; P.pl = hx * hy; P.bxy = table; P.gate = gate; P.vec2 = 0; P.no_shift = 0; P.bxy_cmul = 0;
-  for (int c = 0; c < nb; ++c) { P.cz[c] = kappa; P.lam_z[c][0] = O.lam[0][2][0].p; P.in_blk[c] = g[c]; P.out_blk[c] = z[c]; }
-  P.mode = 0; P.R = hy; P.C = hx; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hx); P.kk2 = ksteps(hy); P.nblk = hz; P.blk_stride = (int64_t)hx * hy; P.row_stride = hx; P.bit1 = 0; P.bit2 = 1;
-  for (int c = 0; c < nb; ++c) { P.T1[c][0] = O.fwd[0][0][0].p; P.T2[c][0] = O.fwd[0][1][0].p; }
-  P.use_in_off = 1; P.use_out_off = 0;
-  launch_pass_nt(s, nt, P, nb * P.nblk, g[0], O.t.p);
-  const int cw = pass2_chunk(nt);
-  P.mode = 1; P.R = hz; P.C = cw; P.nt_r = tiles(hz); P.nt_c = cw / 16; P.kk1 = ksteps(hz); P.kk2 = ksteps(hz); P.nblk = (hx * hy + cw - 1) / cw; P.blk_stride = cw; P.row_stride = (int64_t)hx * hy; P.bit1 = 2; P.bit2 = 2;
-  for (int c = 0; c < nb; ++c) { P.T1[c][0] = O.fwd[0][2][0].p; P.T2[c][0] = O.bwd[0][2][0].p; }
-  P.use_in_off = 0;
-  launch_pass_nt(s, nt, P, nb * P.nblk, O.t.p, O.t.p);
-  P.mode = 2; P.R = hy; P.C = hx; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(hy); P.kk2 = ksteps(hx); P.nblk = hz; P.blk_stride = (int64_t)hx * hy; P.row_stride = hx; P.bit1 = 1; P.bit2 = 0;
-  for (int c = 0; c < nb; ++c) { P.T1[c][0] = O.bwd[0][1][0].p; P.T2[c][0] = O.bwd[0][0][0].p; }
-  P.use_out_off = 1;
-  launch_pass_nt(s, nt, P, nb * P.nblk, O.t.p, z[0]);
+  const Form F = scalar_form(O, nb, kappa, scalar_table(s, O, a, kappa));
+  const double *const in[3] = {g[0], O.t.p, O.t.p}; double *const out[3] = {O.t.p, O.t.p, z[0]};
+  for (int k = 0; k < 3; ++k) {
+    OctPass P = plan_pass(F, k + 1);
+    P.gate = gate;
+    for (int c = 0; c < nb; ++c) { P.in_blk[c] = g[c]; P.out_blk[c] = z[c]; }
+    P.use_in_off = k == 0; P.use_out_off = k == 2;           // pass 1 reads, pass 3 writes every right-hand side's own vector; in between they sit side by side in O.t
+    launch_pass_nt(s, O.nt, PassVariant::General, P, nb * P.nblk, in[k], out[k]);
+  }
 }
 
 static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kappa) {
@@ -1247,26 +1270,10 @@ static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kap
   O.scalar_tables.emplace_back(); auto &T = O.scalar_tables.back(); T.a = a; T.kappa = kappa; T.t.upload(Bt); return T.t.p;
 }
 void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double kappa, const double *in, double *out) {
-  const auto &S = O.slab; const int nt = O.nt, hx = O.h[0], hy = O.h[1], nzl = O.h[2];
-  auto tiles = [](int n) { return (n + 15) / 16; };
-  auto ksteps = [](int n) { return (n + 3) / 4; };
-  OctPass P{};
-  P.co_stride = O.co_stride; P.hx = hx; P.pl = hx * hy; P.bxy = scalar_table(s, O, a, kappa); P.vec2 = 0; P.no_shift = 0; P.bxy_cmul = 0;
-  P.cz[0] = kappa; P.lam_z[0][0] = O.lam[0][2][0].p;
-  if (pass == 2) {
-    P.mode = 1; P.R = S.ng; P.C = S.cw; P.nt_r = tiles(S.ng); P.nt_c = S.cw / 16; P.kk1 = P.kk2 = ksteps(S.ng); P.nblk = 1; P.blk_stride = (int64_t)S.hzg * S.cw; P.row_stride = S.cw; P.bit1 = P.bit2 = 2;
-    P.slab_z = 1; P.chunk0 = S.chunk0; P.chunk_total = S.nchunk; P.nchunk = S.nchunk; P.row_in = S.row_in.p; P.ng = S.ng; P.vec2 = 1;
-    P.T1[0][0] = O.fwd[0][2][0].p; P.T2[0][0] = O.bwd[0][2][0].p;
-    if (S.my_chunks > 0) launch_pass_nt(s, nt, P, S.my_chunks, in, out);
-    return;
-  }
-  const bool first = pass == 1;
-  P.mode = first ? 0 : 2; P.R = hy; P.C = hx; P.nt_r = tiles(hy); P.nt_c = tiles(hx); P.kk1 = ksteps(first ? hx : hy); P.kk2 = ksteps(first ? hy : hx); P.nblk = nzl; P.blk_stride = (int64_t)hx * hy; P.row_stride = hx;
-  P.bit1 = first ? 0 : 1; P.bit2 = first ? 1 : 0;
-  P.T1[0][0] = first ? O.fwd[0][0][0].p : O.bwd[0][1][0].p; P.T2[0][0] = first ? O.fwd[0][1][0].p : O.bwd[0][0][0].p;
-  P.slab_io = first ? 1 : 2; P.store_planes = S.own; P.scols = (int)S.scols; P.inv_scols = 1.0f / (float)S.scols; P.col_unit = S.nchunk * S.cw; P.rank = S.rank;
-  P.dest_stride = (int64_t)((first ? S.max_own : S.max_nl) - 1) * S.scols; P.recv_off = S.recv_off;
-  launch_pass_nt(s, nt, P, P.nblk, in, out);
+  const Form F = scalar_form(O, 1, kappa, scalar_table(s, O, a, kappa));
+  const OctPass P = plan_slab_pass(F, pass);
+  const int n_items = pass == 2 ? O.slab.my_chunks : P.nblk;
+  if (n_items > 0) launch_pass_nt(s, O.nt, PassVariant::General, P, n_items, in, out);
 }
 
 #define PORO_OCT_LAUNCH(kernel, O, ...) do { if ((O).nc == 2) hipLaunchKernelGGL(kernel<2>, oct_grid((O).co_stride, 2), kBlock, 0, s, dims_of(O), __VA_ARGS__); \

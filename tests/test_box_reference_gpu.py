@@ -135,7 +135,7 @@ def test_block_fdm_on_a_graded_box_equals_the_exact_block_inverse():
 
 
 # ---- (c) pressure and projection direct solves ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dim,n", [(3, 72), (3, 99), (2, 336)], ids=str)
+@pytest.mark.parametrize("dim,n", [(3, 72), (3, 99), (2, 336), (3, (9, 5, 2))], ids=str)   # the last: Q1 lines of 10 / 6 / 3 nodes = 3 / 2 / 1 MFMA k-steps in one tile, a direction mix-up truncates a contraction
 def test_pressure_and_projection_fdm_solves_are_the_exact_inverses(dim, n):
     P = box_problem(dim, n, 1)
     G = pk.Context(P, 0, pk.OP_MATRIX_FREE)

@@ -22,9 +22,9 @@ def check(rec, its_slack):
     assert rec["rel_diff_u_vs_single_rank"] <= 1e-7 and rec["rel_diff_p_vs_single_rank"] <= 1e-9, rec
 
 
-@pytest.mark.parametrize("world,n,prec", [(3, 8, "block_fdm"), (4, 8, "chebyshev"), (5, 10, "jacobi"), (2, 24, "block_fdm"), (3, 48, "block_fdm")])   # (24 / 48 cells: 2 / 4 tiles per half line = the both-parity z pass at its other sizes; 72 cells: 5 tiles)
+@pytest.mark.parametrize("world,n,prec", [(3, 8, "block_fdm"), (4, 8, "chebyshev"), (5, 10, "jacobi"), (2, 24, "block_fdm"), (3, 48, "block_fdm"), (3, (10, 9, 24), "block_fdm")])   # (24 / 48 cells: 2 / 4 tiles per half line = the both-parity z pass at its other sizes; 72 cells: 5 tiles; 10 x 9 x 24: hx != hy != local planes in the both-parity z stage and the fused scalar slab passes)
 def test_rank_threads_small(world, n, prec):
-    check(rank_threads.rehearse(world, 3, [n, n, n], 2, prec, 2), its_slack=2)
+    check(rank_threads.rehearse(world, 3, list(n) if isinstance(n, tuple) else [n, n, n], 2, prec, 2), its_slack=2)
 
 
 def test_config4_partition_8_slabs_of_9_layers():
