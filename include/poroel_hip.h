@@ -367,6 +367,34 @@ int  poro_get_volumetric_strain(poro_ctx *ctx);
  * (ConstitutiveModel.h:45-57); PORO_VEC_STRAIN0+e -> PORO_VEC_STRESS0+e */
 int  poro_get_effective_stresses(poro_ctx *ctx);
 
+/* Mesh adaptation (refine_mesh, PoroelasticityFSS.h:447-498; appended entry points, no struct changes: PORO_ABI_VERSION stays 4).
+ *
+ * KellyErrorEstimator<dim>::estimate of PoroelasticityFSS.h:452-458 for the pressure-space vector `which_vec` (PORO_VEC_P, or any other vector of that space):
+ * eta_host[n_cells], one indicator per cell.  THE DEFINITION BELOW IS THIS PROJECT'S (it follows deal.II's cell_diameter_over_24 strategy with coefficient 1 and an
+ * empty Neumann map; deal.II itself was not available to compare against, so this text is what the tests pin):
+ *   - for every interior face F shared by the cells K and K':  J_F = int_F [n . (grad p_h|_K - grad p_h|_K')]^2 dS, with the tensorised Gauss(2) rule on the face
+ *     (QGauss<dim-1>(fe.degree + 1)) mapped with MappingQ1; surface element and normal from the face's own map (the convention of the Neumann term);
+ *   - boundary faces contribute 0;
+ *   - a hanging face is a coarse face of K against the 2^(dim-1) faces of its fine neighbours K'_s: one J_s per subface, integrated ON THE SUBFACE with Gauss(2), the
+ *     coarse side's gradient evaluated at the matching reference points; the coarse cell receives the sum of the J_s, each fine neighbour its own J_s;
+ *   - eta_K = sqrt(sum over the faces F of K of c_F J_F), c_F = h_K / 24 on regular faces and h_coarse / 24 for BOTH sides of a hanging face (deal.II takes the
+ *     factor from the coarse cell); h = the cell diameter = the longest of the 2 (2D) or 4 (3D) vertex diagonals.
+ * The face tables are built on the host at the first call (from the cells' pressure dofs, the boundary-face list and cons_p: a face of one cell only that is not in
+ * the boundary-face list must pair with a coarse face through the masters of its hanging vertices - meshes with ONE level of hanging nodes; anything else returns
+ * < 0 with a message) and stay on the device.  Two kernels, no atomics: the result is bitwise the same from call to call.  The call synchronises (it returns host
+ * data), leaves every vector unchanged, works in both operator modes and on every single-rank mesh (box-tagged, tensor, refined, Gmsh; 2D and 3D); on a partitioned
+ * context (n_ranks > 1) it returns < 0.  Timer family: "kelly". */
+int  poro_pres_estimate_error(poro_ctx *ctx, int which_vec, double *eta_host /* [n_cells] */);
+/* SolutionTransfer<dim>::interpolate of PoroelasticityFSS.h:474-497: PORO_VEC_P, PORO_VEC_EPSV, PORO_VEC_EPSV0 of `from` -> `to`, one launch:
+ *   to[i] = sum_{k in ptr[i] .. ptr[i+1]} weight[k] * from[node[k]]   for every pressure dof i of `to` (the sum runs in the row's entry order).
+ * The rows (ptr[to.n_dofs_p + 1], node, weight; host arrays) evaluate the old FE function at the new dofs; the host provider builds them for its refined boxes, a
+ * caller with its own triangulation takes them from its SolutionTransfer.  They are checked on the host first (ptr[0] == 0, ptr ascending, nodes in range): a
+ * malformed row, contexts on different devices or a partitioned context return < 0 and leave `to` untouched.  The launch is ordered after everything `from` has
+ * enqueued and runs on `to`'s stream; the call returns when it has finished.  Every other vector of `to` is left as it is - zero on a new context, as after every
+ * reinit of the reference (so the displacement warm start is lost across a refinement, as there).  Prescribed pressures of `to` are re-imposed by the caller with
+ * poro_pres_apply_boundary_values. */
+int  poro_state_transfer_p(poro_ctx *from, poro_ctx *to, const int64_t *ptr, const int32_t *node, const double *weight);
+
 /* parity / measurement hooks */
 int  poro_export_csr_size(poro_ctx *ctx, int which, int64_t *n_rows, int64_t *nnz);
 int  poro_export_csr(poro_ctx *ctx, int which, int64_t *row_ptr, int32_t *col, double *val);

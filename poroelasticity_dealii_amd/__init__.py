@@ -104,6 +104,7 @@ HIP_SYMBOLS = [
     "poro_ctx_comm_init_callbacks", "poro_vec_set", "poro_vec_get", "poro_vec_fill", "poro_vec_copy", "poro_vec_axpy", "poro_vec_norm",
     "poro_state_save", "poro_state_restore", "poro_disp_assemble_system", "poro_disp_solve", "poro_supports_preconditioner", "poro_pres_assemble_residual", "poro_pres_apply_boundary_values", "poro_pres_assemble_jacobian", "poro_pres_solve",
     "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
+    "poro_pres_estimate_error", "poro_state_transfer_p",
     "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get"]
 
 _hip = None
@@ -155,6 +156,8 @@ def load_hip():
         L.poro_proj_solve_many.argtypes = [C.c_void_p, _ip, C.c_int32, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]
         L.poro_get_volumetric_strain.argtypes = [C.c_void_p]
         L.poro_get_effective_stresses.argtypes = [C.c_void_p]
+        L.poro_pres_estimate_error.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.poro_state_transfer_p.argtypes = [C.c_void_p, C.c_void_p, _lp, _ip, _dp]
         L.poro_export_csr_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.poro_export_csr.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _dp]
         L.poro_apply_operator.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
@@ -181,6 +184,22 @@ def load_host():
         L.poro_host_build_box.argtypes = [C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int] + bc
         L.poro_host_build_refined_box.restype = C.c_void_p
         L.poro_host_build_refined_box.argtypes = [C.c_int, _ip, _dp, C.c_int, _ip, _ip] + bc
+        L.poro_host_build_refined_box_mask.restype = C.c_void_p
+        L.poro_host_build_refined_box_mask.argtypes = [C.c_int, _ip, _dp, C.c_int, _ip] + bc
+        L.poro_host_refine_mask.restype = C.c_int64
+        L.poro_host_refine_mask.argtypes = [C.c_void_p, _ip]
+        L.poro_host_cell_parents.restype = C.c_int64
+        L.poro_host_cell_parents.argtypes = [C.c_void_p, _ip, _ip]
+        L.poro_host_mark_fixed_fraction.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, _ip]
+        L.poro_host_transfer_rows_p.restype = C.c_int64
+        L.poro_host_transfer_rows_p.argtypes = [C.c_void_p, C.c_void_p, _lp, _ip, _dp]
+        L.poro_host_run_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.poro_host_runner_adapt.argtypes = [C.c_void_p, C.c_double, C.c_double, _lp]
+        L.poro_host_runner_problem.restype = C.c_void_p
+        L.poro_host_runner_problem.argtypes = [C.c_void_p]
+        L.poro_host_kelly_tables.restype = C.c_int64
+        L.poro_host_kelly_tables.argtypes = [C.c_void_p, _lp, _ip, _ip, _ip, _lp, _ip, _ip]
         L.poro_host_build_gmsh.restype = C.c_void_p
         L.poro_host_build_gmsh.argtypes = [C.c_char_p, C.c_int] + bc
         L.poro_host_build_gmsh_refined.restype = C.c_void_p
@@ -238,10 +257,11 @@ def read_input(path=None):
 class Problem:
     """Mesh + DoFs + FE tables + constraints = everything poro_desc points at (owned by the C++ host layer)."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, owned=True):
         if not handle:
             raise RuntimeError(load_host().poro_host_last_error().decode())
         self.handle = C.c_void_p(handle)
+        self.owned = owned                      # False: the C++ side (a Runner that adapted its mesh) frees it
         self.desc_ptr = load_host().poro_host_desc(self.handle)
         self.desc = self.desc_ptr.contents
 
@@ -280,6 +300,74 @@ class Problem:
         lo, plo = _arr_i(list(refine_lo) + [0] * (3 - len(refine_lo)))
         hi, phi = _arr_i(list(refine_hi) + [1] * (3 - len(refine_hi)))
         return cls(load_host().poro_host_build_refined_box(dim, pn, ps, degree_u, plo, phi, *args, C.byref(material)))
+
+    @classmethod
+    def refined_box_mask(cls, dim, n, size, degree_u, material, dirichlet, mask, neumann=()):
+        """the same mesh class from a mask: mask[c] != 0 splits coarse cell c (lexicographic, x fastest; any array with prod(n) entries).  The block form is this
+        with the block's mask.  An all-zero mask gives the uniform box as a GENERAL mesh with the coarse space of PREC_TWO_LEVEL and no box tag - the starting
+        point of an adaptive run; `box` is the way to the structured kernels"""
+        keep, args = cls._bc(dirichlet, neumann)
+        n3, pn = _arr_i(list(n) + [1] * (3 - len(n)))
+        s3, ps = _arr_d(list(size) + [1.0] * (3 - len(size)))
+        m, pm = _arr_i(np.asarray(mask).reshape(-1) != 0)
+        if m.size != int(np.prod(n3)):
+            raise ValueError("refined_box_mask: the mask needs one entry per coarse cell")
+        return cls(load_host().poro_host_build_refined_box_mask(dim, pn, ps, degree_u, pm, *args, C.byref(material)))
+
+    def refine_mask(self):
+        """the refinement mask of a refined box (one int32 per coarse cell)"""
+        H = load_host()
+        n = H.poro_host_refine_mask(self.handle, None)
+        if n < 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        m = np.zeros(n, dtype=np.int32)
+        H.poro_host_refine_mask(self.handle, m.ctypes.data_as(_ip))
+        return m
+
+    def cell_parents(self):
+        """(coarse cell, child number) of every cell of a refined box; child = cx + 2 cy + 4 cz, -1 for an unrefined coarse cell"""
+        H = load_host()
+        n = H.poro_host_cell_parents(self.handle, None, None)
+        if n < 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        a, b = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        H.poro_host_cell_parents(self.handle, a.ctypes.data_as(_ip), b.ctypes.data_as(_ip))
+        return a, b
+
+    def mark_fixed_fraction(self, eta, refine_fraction=0.6, coarsen_fraction=0.4):
+        """refine_and_coarsen_fixed_fraction on the criteria eta[n_cells] + the level limits of refine_mesh (PoroelasticityFSS.h:460-472): the mask of the next mesh"""
+        H = load_host()
+        e, pe = _arr_d(eta)
+        if e.size != self.desc.n_cells:
+            raise ValueError("mark_fixed_fraction: one eta per cell")
+        m = np.zeros(len(self.refine_mask()), dtype=np.int32)
+        if H.poro_host_mark_fixed_fraction(self.handle, pe, refine_fraction, coarsen_fraction, m.ctypes.data_as(_ip)) != 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        return m
+
+    def kelly_tables(self):
+        """the face tables Context.pres_estimate_error builds for this mesh (the same host code, without a GPU): dict of cell_a, cell_b, code [n_faces], ent_ptr [n_cells + 1],
+        ent_face, ent_hcell [n_entries]; layout in csrc/kelly_tables.hpp and csrc/kernels_kelly.hip"""
+        H = load_host()
+        ne = C.c_int64()
+        nf = H.poro_host_kelly_tables(self.handle, C.byref(ne), None, None, None, None, None, None)
+        if nf < 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        T = dict(cell_a=np.zeros(nf, np.int32), cell_b=np.zeros(nf, np.int32), code=np.zeros(nf, np.int32), ent_ptr=np.zeros(self.desc.n_cells + 1, np.int64),
+                 ent_face=np.zeros(ne.value, np.int32), ent_hcell=np.zeros(ne.value, np.int32))
+        H.poro_host_kelly_tables(self.handle, None, *(T[k].ctypes.data_as(_lp if k == "ent_ptr" else _ip) for k in ("cell_a", "cell_b", "code", "ent_ptr", "ent_face", "ent_hcell")))
+        return T
+
+    def transfer_rows_p(self, new):
+        """(ptr, node, weight): row i evaluates this (old) problem's pressure FE function at vertex i of `new` (both refined boxes over the same coarse box)"""
+        H = load_host()
+        ptr = np.zeros(new.desc.n_dofs_p + 1, dtype=np.int64)
+        nnz = H.poro_host_transfer_rows_p(self.handle, new.handle, ptr.ctypes.data_as(_lp), None, None)
+        if nnz < 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        node, w = np.zeros(nnz, dtype=np.int32), np.zeros(nnz)
+        H.poro_host_transfer_rows_p(self.handle, new.handle, ptr.ctypes.data_as(_lp), node.ctypes.data_as(_ip), w.ctypes.data_as(_dp))
+        return ptr, node, w
 
     @classmethod
     def gmsh(cls, path, degree_u, material, dirichlet, neumann=(), refine=0):
@@ -324,7 +412,8 @@ class Problem:
 
     def close(self):
         if self.handle:
-            load_host().poro_host_free(self.handle)
+            if self.owned:
+                load_host().poro_host_free(self.handle)
             self.handle = None
 
     def array(self, name, shape, dtype=np.float64):
@@ -406,6 +495,20 @@ class Context:
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.poro_vec_norm(self.ptr, which, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def pres_estimate_error(self, which=VEC_P):
+        """Kelly error indicator of a pressure-space vector, one value per cell (definition: include/poroel_hip.h)"""
+        eta = np.empty(self.problem.desc.n_cells)
+        self._chk(self.L.poro_pres_estimate_error(self.ptr, int(which), eta.ctypes.data_as(_dp)))
+        return eta
+
+    def transfer_p_from(self, other, rows):
+        """VEC_P, VEC_EPSV, VEC_EPSV0 of `other` (the context of the previous mesh) -> this context through rows = (ptr, node, weight), e.g. other.problem.transfer_rows_p(self.problem)"""
+        ptr = np.ascontiguousarray(rows[0], dtype=np.int64)
+        node, pn = _arr_i(rows[1]); w, pw = _arr_d(rows[2])
+        if ptr.size != self.n_p + 1:
+            raise ValueError("transfer_p_from: ptr needs n_dofs_p + 1 entries")
+        self._chk(self.L.poro_state_transfer_p(other.ptr, self.ptr, ptr.ctypes.data_as(_lp), pn, pw))
 
     def state_save(self):
         self._chk(self.L.poro_state_save(self.ptr))
@@ -537,12 +640,21 @@ def rccl_unique_id():
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False):
-    """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context)."""
+                atomic_scatter=False, fdm_fp32=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
+    """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
+    refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
+    Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once)."""
     H = load_host()
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
+    if refine_every is not None:
+        last = C.c_void_p()
+        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+                                        int(refine_every), refine_fraction, coarsen_fraction, trace.ctypes.data_as(_dp), max_rows, C.byref(ctx), C.byref(last))
+        if rows < 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        return trace[:rows], Context(Problem(last.value) if last.value else problem, ptr=ctx)
     rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                            trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
     if rows < 0:
@@ -565,6 +677,7 @@ class Runner:
         if not h:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         self.h = C.c_void_p(h)
+        self.problem = problem
         self.ctx = Context(problem, ptr=C.c_void_p(self.H.poro_host_runner_ctx(self.h)))
 
     def initialize(self):
@@ -579,6 +692,17 @@ class Runner:
         if rows < 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         return trace[:rows], dict(zip(WORK_FIELDS, list(work)))
+
+    def adapt(self, refine_fraction=0.6, coarsen_fraction=0.4):
+        """refine_mesh (PoroelasticityFSS.h:447-498) + the re-assembly of :338-339 between two steps: estimate, mark, new mesh, new context, transfer.  Returns the
+        cell counts (before, after); .problem / .ctx then refer to the new mesh, which the runner owns and frees (the problem handed to the constructor stays the caller's)"""
+        cells = (C.c_int64 * 2)()
+        if self.H.poro_host_runner_adapt(self.h, refine_fraction, coarsen_fraction, cells) != 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
+        self.ctx.ptr = None                      # destroyed by the runner
+        self.problem = Problem(self.H.poro_host_runner_problem(self.h), owned=False)
+        self.ctx = Context(self.problem, ptr=C.c_void_p(self.H.poro_host_runner_ctx(self.h)))
+        return cells[0], cells[1]
 
     def save_state(self):
         """device-side snapshot of every solver vector (and the step counter)"""

@@ -177,6 +177,10 @@ struct Comm {
   bool multi() const { return part.n_ranks > 1 || force_multi; }
 };
 
+// face tables of the Kelly error indicator (ctx_adapt.hip), built at the first poro_pres_estimate_error: interior (sub)faces sorted by their first cell, and per cell
+// the list of its faces with the cell whose diameter scales them
+struct KellyDev { bool built = false; int64_t n_faces = 0; DevBuf<int32_t> cell_a, cell_b, code, ent_face, ent_hcell; DevBuf<int64_t> ent_ptr; DevBuf<double> jump, eta; };
+
 struct BoxDev { int enabled = 0; int n[3] = {1, 1, 1}; int nn[3] = {1, 1, 1}; double h[3] = {1, 1, 1}; };
 
 }  // namespace poro
@@ -253,6 +257,7 @@ struct poro_ctx {
   // timing
   bool timing = false; std::map<std::string, poro::Timer> timers; std::vector<hipEvent_t> event_pool;
   double jac_dt = -1;
+  poro::KellyDev kelly;
 };
 
 namespace poro {
@@ -319,6 +324,12 @@ void pcg_update_g_fused(hipStream_t s, PcgScalars *sc, int parity, double *g, co
                         const double *partials_dh, const double *red /*null: single rank*/, double *partials_out /*2 sets*/);
 void pcg_update_d_fused(hipStream_t s, PcgScalars *sc, int parity, int it, double *x, double *d, const double *g, const DiagVec &diag, int prec, int64_t n,
                         const double *partials_in /*2 sets*/, const double *red /*null: single rank*/);
+
+// ---- kernels_kelly.hip: mesh adaptation (Kelly indicator, transfer of the pressure-space vectors) ----
+void kelly_faces(hipStream_t s, int dim, int64_t n_faces, const int32_t *cell_a, const int32_t *cell_b, const int32_t *code, const double *cell_X, const int32_t *cell_dofs_p,
+                 const double *p, double *jump);
+void kelly_cells(hipStream_t s, int dim, int64_t n_cells, const int64_t *ent_ptr, const int32_t *ent_face, const int32_t *ent_hcell, const double *cell_X, const double *jump, double *eta);
+void transfer_rows3(hipStream_t s, int64_t n_rows, const int64_t *ptr, const int32_t *col, const double *w, const double *const in[3], double *const out[3]);
 
 // ---- kernels_asm.hip ----------------------------------------------------------------------------
 struct AsmArgs {

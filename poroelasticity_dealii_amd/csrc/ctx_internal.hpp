@@ -105,6 +105,11 @@ void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);
 
+// ---- mesh adaptation (ctx_adapt.hip) ------------------------------------------------------------------------------------------------------
+// rows a caller hands in (interpolation / transfer): ptr[0] == 0, ptr ascending over n_rows rows, every column in [0, n_cols); throws before anything is uploaded
+void validate_rows(const int64_t *ptr, const int32_t *col, const double *weight, int64_t n_rows, int64_t n_cols, const std::string &what);
+void build_kelly_tables(poro_ctx *c);
+
 // ---- set-up (ctx_setup.hip) -------------------------------------------------------------------------------------------------------------
 void setup(poro_ctx *c, const poro_desc *d);
 void sync_source_vector(poro_ctx *c);

@@ -348,10 +348,10 @@ void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int preci
 static void upload_interp(poro_ctx::Interp &T, int64_t n_fine, int64_t n_owned, int64_t n_coarse, const int64_t *ptr, const int32_t *node, const double *weight, const char *what,
                           int row_bound = 0) {
   T.n_fine = n_fine; T.n_coarse = n_coarse;
+  validate_rows(ptr, node, weight, n_fine, n_coarse, std::string("poro_desc.coarse: ") + what);   // before ptr[n_fine] is used or a row is walked
   const int64_t nnz = ptr[n_fine], nnz_t = ptr[n_owned];
   const auto lanes_for = [](int64_t nnz, int64_t rows) { return nnz >= 6 * rows ? 8 : nnz >= 3 * rows ? 4 : 1; };   // mean row length -> lanes per row
   T.lanes = row_bound > 0 ? lanes_for(row_bound, 1) : lanes_for(nnz, n_fine); T.lanes_t = lanes_for(nnz_t, n_coarse);
-  for (int64_t k = 0; k < nnz; ++k) { const int32_t j = node[k]; if (j < 0 || j >= n_coarse) throw Error(std::string("poro_desc.coarse: ") + what + " node out of range"); }
   std::vector<int64_t> tp((size_t)n_coarse + 1, 0);
   for (int64_t k = 0; k < nnz_t; ++k) tp[node[k] + 1]++;
   { int64_t longest = 0; for (int64_t j = 0; j < n_coarse; ++j) longest = std::max(longest, tp[j + 1]);      // restriction: a few very long rows (refined block) beside single-entry ones
@@ -359,7 +359,6 @@ static void upload_interp(poro_ctx::Interp &T, int64_t n_fine, int64_t n_owned, 
   for (int64_t j = 0; j < n_coarse; ++j) tp[j + 1] += tp[j];
   std::vector<int32_t> tc((size_t)nnz_t); std::vector<double> tw((size_t)nnz_t); std::vector<int64_t> pos(tp.begin(), tp.end() - 1);
   for (int64_t i = 0; i < n_fine; ++i) {
-    if (ptr[i + 1] < ptr[i]) throw Error("poro_desc.coarse: ptr not monotone");
     if (i < n_owned) for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) { const int64_t at = pos[node[k]]++; tc[at] = (int32_t)i; tw[at] = weight[k]; }
   }
   T.p_ptr.upload(ptr, (size_t)n_fine + 1); T.p_col.upload(node, (size_t)nnz); T.p_w.upload(weight, (size_t)nnz);

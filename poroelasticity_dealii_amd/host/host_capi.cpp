@@ -1,10 +1,12 @@
 // C entry points of the host layer (mesh / DoF / FE-table provider, parameter file front end and the
 // run() driver), so tests and bench.py can reach the C++ host code through ctypes.
 #include <cstring>
+#include <memory>
 #include <string>
 #include "input_data.hpp"
 #include "mesh.hpp"
 #include "problem.hpp"
+#include "../csrc/kelly_tables.hpp"
 
 using namespace poro_host;
 
@@ -62,6 +64,79 @@ void *poro_host_build_refined_box(int dim, const int32_t *n, const double *size,
     build_refined_box_problem(*P, dim, nn, sz, k_u, l3, h3);
     return P;
   } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+
+// the same mesh class from a mask: mask[c] != 0 = coarse cell c (lexicographic, x fastest) is split once.  The block form above is this with the block's mask (same
+// numbering).  An all-zero mask gives the uniform box as a GENERAL mesh with the coarse space and no box tag (the starting point of an adaptive run); the structured
+// kernels need poro_host_build_box.
+void *poro_host_build_refined_box_mask(int dim, const int32_t *n, const double *size, int k_u, const int32_t *mask,
+                                       int n_dir, const int32_t *dl, const int32_t *dc, const double *dv,
+                                       int n_neu, const int32_t *nl, const int32_t *nc, const double *nv, const poro_material *mat) {
+  try {
+    std::unique_ptr<ProblemData> P(new ProblemData());
+    fill_bc(P->bc, n_dir, dl, dc, dv, n_neu, nl, nc, nv);
+    P->mat = *mat;
+    int nn[3] = {n[0], n[1], dim == 3 ? n[2] : 1}; double sz[3] = {size[0], size[1], dim == 3 ? size[2] : 1};
+    if (nn[0] < 1 || nn[1] < 1 || nn[2] < 1) throw std::runtime_error("refined_box_mask: n must be positive");
+    std::vector<uint8_t> m((size_t)nn[0] * nn[1] * nn[2]);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = mask[i] ? 1 : 0;
+    build_refined_box_problem_mask(*P, dim, nn, sz, k_u, m);
+    return P.release();
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+// what a refined box keeps for adaptation.  Both return the length (n_coarse_cells / n_cells), or -1 when the problem is no refined box; they copy when the pointers are given
+int64_t poro_host_refine_mask(void *h, int32_t *mask) {
+  auto *P = static_cast<ProblemData *>(h);
+  if (!P->refined_box) { g_err = "not a mask- or block-refined box"; return -1; }
+  if (mask) for (size_t i = 0; i < P->refine_mask.size(); ++i) mask[i] = P->refine_mask[i];
+  return (int64_t)P->refine_mask.size();
+}
+// per cell of the mesh: its coarse cell and its child number (cx + 2 cy + 4 cz; -1 = the coarse cell itself)
+int64_t poro_host_cell_parents(void *h, int32_t *coarse, int32_t *child) {
+  auto *P = static_cast<ProblemData *>(h);
+  if (!P->refined_box) { g_err = "not a mask- or block-refined box"; return -1; }
+  if (coarse) std::memcpy(coarse, P->cell_coarse.data(), P->cell_coarse.size() * sizeof(int32_t));
+  if (child) std::memcpy(child, P->cell_child.data(), P->cell_child.size() * sizeof(int32_t));
+  return (int64_t)P->cell_coarse.size();
+}
+// refine_and_coarsen_fixed_fraction + the level limits of refine_mesh (PoroelasticityFSS.h:460-472) as the mask of the next mesh; the rule is stated at mark_fixed_fraction (mesh.hpp)
+int poro_host_mark_fixed_fraction(void *h, const double *eta /* [n_cells] */, double refine_fraction, double coarsen_fraction, int32_t *new_mask /* [n_coarse_cells] */) {
+  try {
+    std::vector<uint8_t> m;
+    mark_fixed_fraction(*static_cast<ProblemData *>(h), eta, refine_fraction, coarsen_fraction, m);
+    for (size_t i = 0; i < m.size(); ++i) new_mask[i] = m[i];
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// SolutionTransfer::interpolate (:474-497) for the pressure space as rows: new dof i = sum weight * old dof node (see transfer_rows_p, mesh.hpp).  Two calls as for
+// poro_host_local_to_global: with node == NULL it fills ptr[n_new + 1] (when given) and returns the entry count, with node / weight it fills those too.  < 0: error
+int64_t poro_host_transfer_rows_p(void *old_problem, void *new_problem, int64_t *ptr, int32_t *node, double *weight) {
+  try {
+    std::vector<int64_t> p; std::vector<int32_t> nd; std::vector<double> w;
+    transfer_rows_p(*static_cast<ProblemData *>(old_problem), *static_cast<ProblemData *>(new_problem), p, nd, w);
+    if (ptr) std::memcpy(ptr, p.data(), p.size() * sizeof(int64_t));
+    if (node) std::memcpy(node, nd.data(), nd.size() * sizeof(int32_t));
+    if (weight) std::memcpy(weight, w.data(), w.size() * sizeof(double));
+    return (int64_t)nd.size();
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// the face tables poro_pres_estimate_error builds for this problem's descriptor (csrc/kelly_tables.hpp; the same code, run on the descriptor's host arrays), so that
+// they can be checked without a GPU.  Returns the face count and *n_entries (< 0: error); fills the arrays that are given: per face cell_a / cell_b / code, per cell
+// ent_ptr[n_cells + 1], per entry ent_face / ent_hcell
+int64_t poro_host_kelly_tables(void *h, int64_t *n_entries, int32_t *cell_a, int32_t *cell_b, int32_t *code, int64_t *ent_ptr, int32_t *ent_face, int32_t *ent_hcell) {
+  try {
+    const poro_desc &d = static_cast<ProblemData *>(h)->d;
+    const int nv = 1 << d.dim; const poro_constraints &c = d.cons_p; const int64_t nm = c.n ? c.ptr[c.n] : 0;
+    const poro::KellyTables T = poro::build_kelly_tables_host(d.dim, d.n_cells, d.n_dofs_p, std::vector<int32_t>(d.cell_dofs_p, d.cell_dofs_p + d.n_cells * nv), d.n_bfaces,
+        std::vector<int32_t>(d.bface_cell, d.bface_cell + d.n_bfaces), std::vector<int32_t>(d.bface_local, d.bface_local + d.n_bfaces), c.n,
+        std::vector<int32_t>(c.dof, c.dof + c.n), c.n ? std::vector<int64_t>(c.ptr, c.ptr + c.n + 1) : std::vector<int64_t>(1, 0), std::vector<int32_t>(c.master, c.master + nm),
+        std::vector<double>(c.weight, c.weight + nm));
+    auto put = [](auto *dst, const auto &src) { if (dst) std::copy(src.begin(), src.end(), dst); };
+    put(cell_a, T.cell_a); put(cell_b, T.cell_b); put(code, T.code); put(ent_ptr, T.ent_ptr); put(ent_face, T.ent_face); put(ent_hcell, T.ent_hcell);
+    if (n_entries) *n_entries = (int64_t)T.ent_face.size();
+    return (int64_t)T.cell_a.size();
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
 // Gmsh 2.2 mesh (GridIn::read_msh, PoroelasticityFSS.h:438-445)
@@ -189,6 +264,28 @@ int poro_host_run(void *problem_data, int device, int operator_mode, double p_in
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// The same with mesh adaptation (refine_mesh every refine_every-th step, PoroelasticityFSS.h:333-340; 0 = never: the run of poro_host_run).  `flags` as for poro_host_run.
+// The problem must be a mask- or block-refined box.  *problem_out receives the mesh the run ended on when it was refined at least once (the caller frees it with
+// poro_host_free; the context in *ctx_out belongs to it), else NULL (the context belongs to `problem_data`).
+int poro_host_run_adaptive(void *problem_data, int device, int operator_mode, double p_init, double dt, int n_steps,
+                           double fss_tol, double pressure_tol, int max_fss, int max_pres,
+                           double abs_u, double rel_u, int max_it, int preconditioner, int flags, int refine_every, double refine_fraction, double coarsen_fraction,
+                           double *trace, int max_rows, poro_ctx **ctx_out, void **problem_out) {
+  try {
+    auto *P = static_cast<ProblemData *>(problem_data);
+    RunControls rc; rc.p_init = p_init; rc.time_step = dt; rc.n_steps = n_steps; rc.fss_tol = fss_tol; rc.pressure_tol = pressure_tol;
+    rc.max_fss_iterations = max_fss; rc.max_pressure_iterations = max_pres; rc.abs_tol_u = abs_u; rc.rel_tol_u = rel_u; rc.max_iter = max_it; rc.preconditioner = preconditioner; rc.coupled_fss = (flags & 1) != 0; rc.incremental_strain = (flags & 2) != 0; rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) rc.preconditioner_p = PORO_PREC_TWO_LEVEL; rc.atomic_scatter = (flags & 32) != 0; rc.fdm_fp32 = (flags & 64) != 0; rc.chebyshev_degree = (flags >> 8) & 0xff; rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
+    if (refine_every < 0) throw std::runtime_error("run_adaptive: refine_every must be >= 0");
+    rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
+    int rows = 0;
+    if (problem_out) *problem_out = nullptr;
+    auto go = [&](auto &prob) { rows = prob.run(rc, trace, max_rows); if (problem_out) *problem_out = prob.release_problem(); if (ctx_out) *ctx_out = prob.release(); };
+    if (P->mesh.dim == 2) { PoroElasticProblem<2> prob(*P, device, operator_mode); go(prob); }
+    else { PoroElasticProblem<3> prob(*P, device, operator_mode); go(prob); }
+    return rows;
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
 // Steppable driver for bench.py: the same PoroElasticProblem object, one time step per call.
 struct HostRunner {
   int dim; RunControls rc; PoroElasticProblem<2> *p2 = nullptr; PoroElasticProblem<3> *p3 = nullptr;
@@ -205,6 +302,18 @@ void *poro_host_runner_create(void *problem_data, int device, int operator_mode,
     return R;
   } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
+// refine_mesh + the two calls of PoroelasticityFSS.h:338-339 between two steps; cells[2] = cell counts before and after.  Afterwards poro_host_runner_ctx and
+// poro_host_runner_problem give the new context and mesh, both owned (and freed) by the runner
+int poro_host_runner_adapt(void *r, double refine_fraction, double coarsen_fraction, int64_t *cells) {
+  try {
+    auto *R = static_cast<HostRunner *>(r);
+    RunControls rc = R->rc; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
+    const std::pair<int64_t, int64_t> n = R->dim == 2 ? R->p2->refine_mesh(rc) : R->p3->refine_mesh(rc);
+    if (cells) { cells[0] = n.first; cells[1] = n.second; }
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+void *poro_host_runner_problem(void *r) { auto *R = static_cast<HostRunner *>(r); return const_cast<ProblemData *>(R->dim == 2 ? R->p2->problem() : R->p3->problem()); }
 poro_ctx *poro_host_runner_ctx(void *r) { auto *R = static_cast<HostRunner *>(r); return R->dim == 2 ? R->p2->context() : R->p3->context(); }
 int poro_host_runner_initialize(void *r) {
   try { auto *R = static_cast<HostRunner *>(r); if (R->dim == 2) R->p2->initialize(R->rc); else R->p3->initialize(R->rc); return 0; }

@@ -263,11 +263,19 @@ struct RefinedBox {
   // interpolation from the underlying uniform box: displacement node i = sum of weight * box node (lexicographic box numbering), rows by prol_ptr
   std::vector<int64_t> prol_ptr; std::vector<int32_t> prol_node; std::vector<double> prol_w;
   std::vector<int64_t> prol_ptr_p; std::vector<int32_t> prol_node_p; std::vector<double> prol_w_p;     // the same for the pressure space (vertices)
+  // what mesh adaptation needs: the refinement mask (one byte per coarse cell, lexicographic), per cell of the mesh its coarse cell and child number
+  // (cx + 2 cy + 4 cz; -1: the coarse cell itself), per vertex its half-lattice coordinates (units h / 2)
+  std::vector<uint8_t> mask; std::vector<int32_t> cell_coarse, cell_child; std::vector<std::array<int, 3>> lattice_p;
 };
-inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[3], const double h[3], int k_u, const int lo[3], const int hi[3]) {
+// mask[c] != 0: coarse cell c (lexicographic, x fastest) is replaced by its children.  Any mask is a valid one-level mesh (neighbours differ by at most one level).
+// In 3D a refined and an unrefined cell may meet along an edge only (the other two cells around it refined): the edge midpoint hangs on that edge, and the search
+// below finds it, because it goes through every coarse cell whose closure contains the node, whatever the contact.
+inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[3], const double h[3], int k_u, const std::vector<uint8_t> &mask) {
   RefinedBox R; Mesh &m = R.mesh; m.dim = dim;
   const int nc[3] = {n[0], n[1], dim == 3 ? n[2] : 1};
-  auto refined = [&](const int c[3]) { for (int d = 0; d < dim; ++d) if (c[d] < lo[d] || c[d] >= hi[d]) return false; return true; };
+  if ((int64_t)mask.size() != (int64_t)nc[0] * nc[1] * nc[2]) throw std::runtime_error("make_refined_box: the mask needs one entry per coarse cell");
+  R.mask = mask; for (auto &b : R.mask) b = b ? 1 : 0;
+  auto refined = [&](const int c[3]) { return R.mask[((size_t)c[2] * nc[1] + c[1]) * nc[0] + c[0]] != 0; };
   struct Cell { int c[3]; int child[3]; bool fine; };
   std::vector<Cell> cells;
   for (int k = 0; k < nc[2]; ++k) for (int j = 0; j < nc[1]; ++j) for (int i = 0; i < nc[0]; ++i) {
@@ -275,6 +283,7 @@ inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[
     if (!refined(c)) { cells.push_back(Cell{{i, j, k}, {0, 0, 0}, false}); continue; }
     for (int cz = 0; cz < (dim == 3 ? 2 : 1); ++cz) for (int cy = 0; cy < 2; ++cy) for (int cx = 0; cx < 2; ++cx) cells.push_back(Cell{{i, j, k}, {cx, cy, cz}, true});
   }
+  for (const Cell &C : cells) { R.cell_coarse.push_back((int32_t)(((int64_t)C.c[2] * nc[1] + C.c[1]) * nc[0] + C.c[0])); R.cell_child.push_back(C.fine ? C.child[0] + 2 * C.child[1] + 4 * C.child[2] : -1); }
   // lattice numbering of one scalar space of degree k: key = lattice coordinates in units h / (2k)
   auto key_of = [&](int k, const int X[3]) { const int64_t L1 = 2 * k * nc[0] + 1, L2 = 2 * k * nc[1] + 1; return ((int64_t)(dim == 3 ? X[2] : 0) * L2 + X[1]) * L1 + X[0]; };
   auto number_space = [&](int k, std::vector<int32_t> &cell_nodes, std::map<int64_t, int32_t> &id, std::vector<std::array<int, 3>> &coord) {
@@ -319,6 +328,7 @@ inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[
   std::map<int64_t, int32_t> idp, idu; std::vector<std::array<int, 3>> cp, cu; std::vector<int32_t> nodes_p, nodes_u;
   number_space(1, nodes_p, idp, cp);
   number_space(k_u, nodes_u, idu, cu);
+  R.lattice_p = cp;
   m.vertices.resize(cp.size() * dim);
   for (size_t v = 0; v < cp.size(); ++v) for (int d = 0; d < dim; ++d) m.vertices[v * dim + d] = origin[d] + 0.5 * h[d] * cp[v][d];
   m.cells = nodes_p;
@@ -379,6 +389,17 @@ inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[
   }
   return R;
 }
+// the block form: the coarse cells with index lo[d] <= i_d < hi[d] are refined
+inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[3], const double h[3], int k_u, const int lo[3], const int hi[3]) {
+  const int nc[3] = {n[0], n[1], dim == 3 ? n[2] : 1};
+  std::vector<uint8_t> mask((size_t)nc[0] * nc[1] * nc[2], 0);
+  for (int k = 0; k < nc[2]; ++k) for (int j = 0; j < nc[1]; ++j) for (int i = 0; i < nc[0]; ++i) {
+    const int c[3] = {i, j, k}; bool in = true;
+    for (int d = 0; d < dim; ++d) if (c[d] < lo[d] || c[d] >= hi[d]) in = false;
+    mask[((size_t)k * nc[1] + j) * nc[0] + i] = in ? 1 : 0;
+  }
+  return make_refined_box(dim, n, origin, h, k_u, mask);
+}
 
 // extension: prescribed pressure on the faces carrying the given labels (first condition wins, like the displacement conditions)
 inline void make_dirichlet_p(const Mesh &m, const DoFs &D, const BoundaryConditions &bc, std::vector<int32_t> &dofs, std::vector<double> &values) {
@@ -411,6 +432,9 @@ struct ProblemData {
   std::unique_ptr<ProblemData> coarse; std::vector<int64_t> prol_ptr; std::vector<int32_t> prol_node; std::vector<double> prol_w;
   std::vector<int64_t> prol_ptr_p; std::vector<int32_t> prol_node_p; std::vector<double> prol_w_p;
   int64_t n_dofs_p_global = 0;        // pieces of a general partition: the global problem's pressure dof count (0: this problem is not a piece)
+  // one-level refined boxes (block or mask form) keep what mesh adaptation needs, see RefinedBox; refined_box tells whether this problem is one
+  bool refined_box = false; int box_n[3] = {1, 1, 1}; double box_size[3] = {1, 1, 1}; int box_k_u = 0;
+  std::vector<uint8_t> refine_mask; std::vector<int32_t> cell_coarse, cell_child; std::vector<std::array<int, 3>> lattice_p;
   poro_desc d{};
 
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are
@@ -616,10 +640,12 @@ inline void build_graded_box_problem(ProblemData &P, int dim, const int n[3], co
   }
 }
 
-inline void build_refined_box_problem(ProblemData &P, int dim, const int n[3], const double size[3], int k_u, const int lo[3], const int hi[3]) {
-  double origin[3] = {0, 0, 0}, h[3] = {1, 1, 1};
-  for (int d = 0; d < dim; ++d) { h[d] = size[d] / n[d]; origin[d] = -size[d] / 2; }
-  RefinedBox R = make_refined_box(dim, n, origin, h, k_u, lo, hi);
+// the refined box `R` (over n coarse cells, extent `size`) as a problem with the coarse space of the two-level preconditioner.  An all-zero mask gives the uniform box
+// as a GENERAL mesh (no box tag, so the general kernels run) that still has the coarse space: the starting point of an adaptive run.  Problem.box is the way to the structured kernels.
+inline void adopt_refined_box(ProblemData &P, RefinedBox &&R, int dim, const int n[3], const double size[3], int k_u) {
+  P.refined_box = true; P.box_k_u = k_u;
+  for (int d = 0; d < 3; ++d) { P.box_n[d] = d < dim ? n[d] : 1; P.box_size[d] = d < dim ? size[d] : 1; }
+  P.refine_mask = std::move(R.mask); P.cell_coarse = std::move(R.cell_coarse); P.cell_child = std::move(R.cell_child); P.lattice_p = std::move(R.lattice_p);
   P.mesh = std::move(R.mesh); P.dofs = std::move(R.dofs); P.cons_u = std::move(R.cons_u); P.cons_p = std::move(R.cons_p);
   P.prol_ptr = std::move(R.prol_ptr); P.prol_node = std::move(R.prol_node); P.prol_w = std::move(R.prol_w);
   P.prol_ptr_p = std::move(R.prol_ptr_p); P.prol_node_p = std::move(R.prol_node_p); P.prol_w_p = std::move(R.prol_w_p);
@@ -631,6 +657,94 @@ inline void build_refined_box_problem(ProblemData &P, int dim, const int n[3], c
   P.d.coarse = poro_coarse_space{}; P.d.coarse.enabled = 1; P.d.coarse.box_problem = &P.coarse->d;
   P.d.coarse.ptr = P.prol_ptr.data(); P.d.coarse.node = P.prol_node.data(); P.d.coarse.weight = P.prol_w.data();
   P.d.coarse.ptr_p = P.prol_ptr_p.data(); P.d.coarse.node_p = P.prol_node_p.data(); P.d.coarse.weight_p = P.prol_w_p.data();
+}
+inline void build_refined_box_problem(ProblemData &P, int dim, const int n[3], const double size[3], int k_u, const int lo[3], const int hi[3]) {
+  double origin[3] = {0, 0, 0}, h[3] = {1, 1, 1};
+  for (int d = 0; d < dim; ++d) { h[d] = size[d] / n[d]; origin[d] = -size[d] / 2; }
+  adopt_refined_box(P, make_refined_box(dim, n, origin, h, k_u, lo, hi), dim, n, size, k_u);
+}
+inline void build_refined_box_problem_mask(ProblemData &P, int dim, const int n[3], const double size[3], int k_u, const std::vector<uint8_t> &mask) {
+  double origin[3] = {0, 0, 0}, h[3] = {1, 1, 1};
+  for (int d = 0; d < dim; ++d) { h[d] = size[d] / n[d]; origin[d] = -size[d] / 2; }
+  adopt_refined_box(P, make_refined_box(dim, n, origin, h, k_u, mask), dim, n, size, k_u);
+}
+
+// ---- mesh adaptation on one-level refined boxes (refine_mesh, PoroelasticityFSS.h:447-498) -----------------------------------------------
+// GridRefinement::refine_and_coarsen_fixed_fraction(refine_fraction, coarsen_fraction) on the criteria `eta` (one per cell of P's mesh) + the level limits of
+// refine_mesh (:463-472) with Max refinement level = 1, as the mask of the next mesh:
+//   - cells sorted by eta descending: the refine set is the shortest prefix whose running sum of eta (of eta, not eta^2) reaches refine_fraction * sum(eta),
+//     extended by every cell tied with its last member; sums run sequentially in the sorted order;
+//   - the coarsen set is the same from the ascending end with coarsen_fraction, minus the cells of the refine set;  an all-zero eta flags nothing;
+//   - a refine flag on a child is dropped (maximum level), a coarsen flag on a box cell is dropped (minimum level), a refined coarse cell is coarsened only if
+//     ALL its 2^dim children carry the coarsen flag;
+//   - new_mask[c] = 1 if c was unrefined and is flagged for refinement, or if c was refined and is not coarsened.
+inline void mark_fixed_fraction(const ProblemData &P, const double *eta, double refine_fraction, double coarsen_fraction, std::vector<uint8_t> &new_mask) {
+  if (!P.refined_box) throw std::runtime_error("mark_fixed_fraction: the problem is not a mask- or block-refined box");
+  const int64_t nc = P.mesh.n_cells(); const int nchild = 1 << P.mesh.dim;
+  for (int64_t i = 0; i < nc; ++i) if (!(eta[i] >= 0.0) || !std::isfinite(eta[i])) throw std::runtime_error("mark_fixed_fraction: eta must be finite and non-negative");
+  std::vector<double> s(eta, eta + nc);
+  std::vector<uint8_t> refine(nc, 0), coarsen(nc, 0);
+  auto threshold = [&](double fraction, bool &any) {       // s is sorted from the end the set starts at
+    double total = 0; for (double v : s) total += v;
+    const double target = fraction * total; double run = 0; int64_t m = 0;
+    while (m < nc && !(run >= target)) run += s[m++];
+    any = m > 0; return any ? s[m - 1] : 0.0;
+  };
+  bool any = false;
+  std::sort(s.begin(), s.end(), [](double a, double b) { return a > b; });
+  const double t_ref = threshold(refine_fraction, any);
+  if (any) for (int64_t i = 0; i < nc; ++i) refine[i] = eta[i] >= t_ref;
+  std::sort(s.begin(), s.end());
+  const double t_crs = threshold(coarsen_fraction, any);
+  if (any) for (int64_t i = 0; i < nc; ++i) coarsen[i] = eta[i] <= t_crs && !refine[i];
+  new_mask = P.refine_mask;
+  std::vector<int> flagged(new_mask.size(), 0);
+  for (int64_t i = 0; i < nc; ++i) {
+    const int32_t c = P.cell_coarse[i];
+    if (P.cell_child[i] < 0) { if (refine[i]) new_mask[c] = 1; }
+    else if (coarsen[i]) flagged[c]++;
+  }
+  for (size_t c = 0; c < new_mask.size(); ++c) if (P.refine_mask[c] && flagged[c] == nchild) new_mask[c] = 0;
+}
+
+// SolutionTransfer<dim>::interpolate for the pressure space between two refined boxes over the same coarse box: row i evaluates the OLD finite-element function at
+// new vertex i.  A point that is a vertex of the old mesh takes that value (one entry, weight 1: kept nodes, coarsening by injection; an old hanging node carries
+// its distributed value); any other point lies in the closure of an old UNREFINED coarse cell and takes that cell's Q1 shape values (entries below 1e-13 dropped).
+// Entries of a row are in ascending old-node order.
+inline void transfer_rows_p(const ProblemData &O, const ProblemData &N, std::vector<int64_t> &ptr, std::vector<int32_t> &node, std::vector<double> &weight) {
+  if (!O.refined_box || !N.refined_box) throw std::runtime_error("transfer_rows_p: both problems must be mask- or block-refined boxes");
+  if (O.mesh.dim != N.mesh.dim) throw std::runtime_error("transfer_rows_p: the problems differ in dimension");
+  for (int d = 0; d < 3; ++d) if (O.box_n[d] != N.box_n[d] || O.box_size[d] != N.box_size[d]) throw std::runtime_error("transfer_rows_p: the problems are not refinements of the same box (n, size)");
+  const int dim = O.mesh.dim, nv = 1 << dim; const int *nc = O.box_n;
+  auto key_of = [&](const int X[3]) { const int64_t L1 = 2 * nc[0] + 1, L2 = 2 * nc[1] + 1; return ((int64_t)(dim == 3 ? X[2] : 0) * L2 + X[1]) * L1 + X[0]; };
+  std::unordered_map<int64_t, int32_t> old_id; old_id.reserve(O.lattice_p.size() * 2);
+  for (size_t v = 0; v < O.lattice_p.size(); ++v) old_id.emplace(key_of(O.lattice_p[v].data()), (int32_t)v);
+  ptr.assign(1, 0); node.clear(); weight.clear();
+  std::vector<double> val(nv), grad((size_t)nv * dim);
+  for (size_t i = 0; i < N.lattice_p.size(); ++i) {
+    const int *X = N.lattice_p[i].data();
+    auto it = old_id.find(key_of(X));
+    if (it != old_id.end()) { node.push_back(it->second); weight.push_back(1.0); ptr.push_back((int64_t)node.size()); continue; }
+    int c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
+    for (int d = 0; d < dim; ++d) { const int q = X[d] / 2, r = X[d] % 2; c1[d] = std::min(q, nc[d] - 1); c0[d] = (r == 0 && q > 0) ? q - 1 : c1[d]; }
+    bool done = false;
+    for (int ck = c0[2]; ck <= c1[2] && !done; ++ck) for (int cj = c0[1]; cj <= c1[1] && !done; ++cj) for (int ci = c0[0]; ci <= c1[0] && !done; ++ci) {
+      if (O.refine_mask[((size_t)ck * nc[1] + cj) * nc[0] + ci]) continue;
+      const int c[3] = {ci, cj, ck}; double xi[3] = {0, 0, 0};
+      for (int d = 0; d < dim; ++d) xi[d] = (double)(X[d] - 2 * c[d]) / 2;
+      shape_at(dim, 1, xi, val.data(), grad.data());
+      std::vector<std::pair<int32_t, double>> row;
+      for (int s = 0; s < nv; ++s) if (std::fabs(val[s]) > 1e-13) {
+        int Y[3] = {0, 0, 0}; for (int d = 0; d < dim; ++d) Y[d] = 2 * (c[d] + ((s >> d) & 1));
+        row.emplace_back(old_id.at(key_of(Y)), val[s]);
+      }
+      std::sort(row.begin(), row.end());
+      for (auto &e : row) { node.push_back(e.first); weight.push_back(e.second); }
+      done = true;
+    }
+    if (!done) throw std::runtime_error("transfer_rows_p: a new vertex lies in no cell of the old mesh");
+    ptr.push_back((int64_t)node.size());
+  }
 }
 
 // ---- general partition (last sentence): contiguous ranges of the cells in Morton order + indexed interface lists --------------

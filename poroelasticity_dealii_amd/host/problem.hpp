@@ -53,6 +53,8 @@ struct RunControls {
   int preconditioner_p = -1;                                        // pressure / projection solves; -1 = fast diagonalisation where the context supports it, else the two-level form, else Jacobi
   bool fdm_fp32 = false;                                            // PORO_FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (elsewhere no effect).  Never chosen automatically
   bool atomic_scatter = false;                                      // general meshes, matrix-free: PORO_SCATTER_ATOMIC (one launch per operator application; not bitwise reproducible).  Never chosen automatically
+  int refine_every = 0;                                             // refine_mesh when time_step_number % refine_every == 0 (the reference hard-wires 5, PoroelasticityFSS.h:333); 0 = never
+  double refine_fraction = 0.6, coarsen_fraction = 0.4;             // refine_and_coarsen_fixed_fraction (:460-462)
 };
 
 }  // namespace poro_host
@@ -66,6 +68,7 @@ template <int dim> class PoroElasticDisplacementSolver {
   poro_solver_opts control{1e-12, 0.0, 1000, PORO_PREC_JACOBI, 1.2, PORO_STOP_RHS, 0};   // :298-299, omega :303 (Jacobi is the fast default; PORO_PREC_SSOR = the reference's)
   poro_solve_info  last{};
   explicit PoroElasticDisplacementSolver(poro_ctx *c) : ctx(c) { solution.ctx = c; solution.id = PORO_VEC_U; }
+  void rebind(poro_ctx *c) { ctx = c; solution.ctx = c; rebuild_system_matrix = true; }   // a new mesh (refine_mesh): the solver follows the problem to its new context
   void setup_dofs() { rebuild_system_matrix = true; }      // :106-153 (pattern / constraints are built by poro_ctx_create)
   // :155-291 — pressure_solution must be the pressure solver's `solution`
   void assemble_system(DeviceVector &pressure_solution) {
@@ -91,6 +94,7 @@ template <int dim> class PoroElasticPressureSolver {
     solution.ctx = solution_update.ctx = old_solution.ctx = residual.ctx = c;
     solution.id = PORO_VEC_P; solution_update.id = PORO_VEC_DP; old_solution.id = PORO_VEC_P_OLD; residual.id = PORO_VEC_RESIDUAL_P;
   }
+  void rebind(poro_ctx *c) { ctx = c; solution.ctx = solution_update.ctx = old_solution.ctx = residual.ctx = c; }
   void setup_dofs() {}                                     // :68-111 (mass / Laplace matrices are built by poro_ctx_create)
   void assemble_jacobian(double time_step) { poro_host::check(poro_pres_assemble_jacobian(ctx, time_step), "pres_assemble_jacobian"); }   // :158-169
   // :113-155 — the strains must be the problem's volumetric_strain / initial_volumetric_strain
@@ -157,11 +161,13 @@ template <int dim> class TensorIndexer {
 namespace poro_host {
 
 // PoroElasticProblem<dim> (PoroelasticityFSS.h:42-90): owns the context and reproduces run()'s call sequence
-// (:294-415) with mesh creation, AMR (:333-340) and output (:409-411) removed.
+// (:294-415) with mesh creation left to the caller.  Mesh adaptation (:333-340, refine_mesh :447-498) is there for the mesh class the host provider
+// can rebuild - boxes with ONE level of refinement (mask- or block-refined, the analogue of `Max refinement level = 1`), one rank: estimate on the device,
+// mark and rebuild on the host, new context, transfer on the device.  Off unless RunControls::refine_every is set or refine_mesh is called.
 template <int dim> class PoroElasticProblem {
   poro_ctx *ctx;   // declared first: the solver members below are constructed from it
  public:
-  PoroElasticProblem(ProblemData &P, int device, int operator_mode) : ctx(make_ctx(P, device, operator_mode)), pressure_solver(ctx), displacement_solver(ctx), pd(&P) {
+  PoroElasticProblem(ProblemData &P, int device, int operator_mode) : ctx(make_ctx(P, device, operator_mode)), pressure_solver(ctx), displacement_solver(ctx), pd(&P), device_(device), operator_mode_(operator_mode) {
     volumetric_strain.ctx = initial_volumetric_strain.ctx = ctx;
     volumetric_strain.id = PORO_VEC_EPSV; initial_volumetric_strain.id = PORO_VEC_EPSV0;
     if (dim == 2) { strain_tensor_volumetric_components = {0, 3}; strain_tensor_shear_components = {1}; }
@@ -170,6 +176,50 @@ template <int dim> class PoroElasticProblem {
   ~PoroElasticProblem() { if (ctx) poro_ctx_destroy(ctx); }
   poro_ctx *context() { return ctx; }
   poro_ctx *release() { poro_ctx *c = ctx; ctx = nullptr; return c; }
+  const ProblemData *problem() const { return pd; }                    // the mesh the context currently belongs to (the caller's, or the last one refine_mesh built)
+  ProblemData *release_problem() { return adapted.release(); }        // the mesh refine_mesh built last, handed to the caller (null: never refined)
+
+  // refine_mesh (:447-498) on one-level refined boxes, followed by the two calls of :338-339.  Sequence: estimate (KellyErrorEstimator on the device) -> mark
+  // (fixed fraction + level limits, mesh.hpp) -> the new ProblemData from the mask -> a new context in the same operator mode, scatter mode and FDM precision ->
+  // setup_dofs -> transfer of p, eps_v, eps_v0 on the device -> swap, the old context is destroyed.  The preconditioner choice of initialize() is made again on the
+  // new context (rc.preconditioner < 0 lands on the two-level form once hanging nodes exist).  Work counters carry over; the displacement warm start is lost (every
+  // reinit of the reference leaves zero vectors).  Returns the cell counts before and after.
+  std::pair<int64_t, int64_t> refine_mesh(const RunControls &rc) {
+    const ProblemData &O = *pd;
+    if (!O.refined_box) throw std::runtime_error("refine_mesh: the problem is not a mask- or block-refined box (the host provider adapts boxes with one level of refinement)");
+    if (O.part.n_ranks > 1) throw std::runtime_error("refine_mesh: implemented for one rank");
+    std::vector<double> eta((size_t)O.d.n_cells);
+    check(poro_pres_estimate_error(ctx, PORO_VEC_P, eta.data()), "pres_estimate_error");     // :452-458
+    std::vector<uint8_t> mask;
+    mark_fixed_fraction(O, eta.data(), rc.refine_fraction, rc.coarsen_fraction, mask);       // :460-472
+    std::unique_ptr<ProblemData> N(new ProblemData());
+    N->bc = O.bc; N->mat = O.mat;
+    build_refined_box_problem_mask(*N, O.mesh.dim, O.box_n, O.box_size, O.box_k_u, mask);    // :481-483
+    std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
+    transfer_rows_p(O, *N, ptr, node, weight);
+    int32_t scatter = PORO_SCATTER_COLOURED, fdm_req = PORO_FDM_FP64;
+    check(poro_ctx_get_scatter_mode(ctx, &scatter), "ctx_get_scatter_mode");
+    if (rc.fdm_fp32) fdm_req = PORO_FDM_FP32;
+    struct Guard { poro_ctx *c; ~Guard() { if (c) poro_ctx_destroy(c); } } fresh{make_ctx(*N, device_, operator_mode_)};
+    if (scatter != PORO_SCATTER_COLOURED || rc.atomic_scatter) check(poro_ctx_set_scatter_mode(fresh.c, rc.atomic_scatter ? PORO_SCATTER_ATOMIC : scatter), "ctx_set_scatter_mode");
+    if (fdm_req != PORO_FDM_FP64) check(poro_ctx_set_fdm_precision(fresh.c, fdm_req), "ctx_set_fdm_precision");
+    poro_ctx *old = ctx;
+    const std::pair<int64_t, int64_t> counts(O.d.n_cells, N->d.n_cells);
+    rebind(fresh.c);
+    try {
+      setup_dofs();                                                                          // :485
+      check(poro_state_transfer_p(old, ctx, ptr.data(), node.data(), weight.data()), "state_transfer_p");   // :488-497
+      check(poro_pres_apply_boundary_values(ctx), "pres_apply_boundary_values");
+    } catch (...) { rebind(old); throw; }
+    fresh.c = nullptr;
+    poro_ctx_destroy(old);
+    adapted = std::move(N); pd = adapted.get();                                              // (the previous adapted mesh, if any, goes with its context)
+    choose_preconditioners(rc);
+    first_assembly = true; jacobian_dt = -1;
+    assemble_displacement();                                                                 // :338
+    strain_projector.assemble_projection_matrix();                                           // :339
+    return counts;
+  }
 
   void setup_dofs() {                                      // :131-151
     pressure_solver.setup_dofs(); displacement_solver.setup_dofs();
@@ -254,10 +304,8 @@ template <int dim> class PoroElasticProblem {
   struct Work { int64_t apply_u = 0, apply_p = 0, asm_rhs_u = 0, asm_matrix_u = 0, residual_p = 0, jacobian_p = 0, proj_rhs = 0;
                 int64_t cg_u = 0, cg_p = 0, cg_proj = 0; double seconds_solve_u = 0; } work;
 
-  // trace rows: [step, fss_iteration, pressure_iterations, inner pressure error, |p|_inf, error after displacement, u CG its, p CG its]
-  void initialize(const RunControls &rc) {
-    if (rc.atomic_scatter) check(poro_ctx_set_scatter_mode(context(), PORO_SCATTER_ATOMIC), "ctx_set_scatter_mode");
-    if (rc.fdm_fp32) check(poro_ctx_set_fdm_precision(context(), PORO_FDM_FP32), "ctx_set_fdm_precision");
+  // the solver controls and the preconditioner choice from rc and from what the CURRENT context supports (initialize, and again after every refine_mesh)
+  void choose_preconditioners(const RunControls &rc) {
     displacement_solver.control.abs_tol = rc.abs_tol_u; displacement_solver.control.rel_tol = rc.rel_tol_u; displacement_solver.control.stop_rule = rc.stop_rule_u;
     displacement_solver.control.max_iter = pressure_solver.control.max_iter = strain_projector.control.max_iter = rc.max_iter;
     // rc.preconditioner < 0: the strongest displacement preconditioner this mesh supports
@@ -274,6 +322,12 @@ template <int dim> class PoroElasticProblem {
     const int64_t n_dofs_p = pd->n_dofs_p_global > 0 ? pd->n_dofs_p_global : pd->d.n_dofs_p;
     if (rc.preconditioner != PORO_PREC_SSOR && rc.preconditioner_p < 0 && pressure_solver.control.preconditioner == PORO_PREC_JACOBI && n_dofs_p >= 4096 && poro_supports_preconditioner(context(), 1, PORO_PREC_TWO_LEVEL))
       pressure_solver.control.preconditioner = PORO_PREC_TWO_LEVEL;
+  }
+  // trace rows: [step, fss_iteration, pressure_iterations, inner pressure error, |p|_inf, error after displacement, u CG its, p CG its]
+  void initialize(const RunControls &rc) {
+    if (rc.atomic_scatter) check(poro_ctx_set_scatter_mode(context(), PORO_SCATTER_ATOMIC), "ctx_set_scatter_mode");
+    if (rc.fdm_fp32) check(poro_ctx_set_fdm_precision(context(), PORO_FDM_FP32), "ctx_set_fdm_precision");
+    choose_preconditioners(rc);
     setup_dofs();                                          // :308
     pressure_solver.solution = rc.p_init;                  // :311
     check(poro_pres_apply_boundary_values(ctx), "pres_apply_boundary_values");   // (extension: prescribed pressures; no-op for the reference's problems)
@@ -289,6 +343,7 @@ template <int dim> class PoroElasticProblem {
   int time_step(const RunControls &rc, double *trace, int max_rows) {
     int rows = 0;
     time_step_number++;                                    // :329
+    if (rc.refine_every > 0 && time_step_number % rc.refine_every == 0) refine_mesh(rc);   // :333-340
     pressure_solver.old_solution = pressure_solver.solution;   // :342
     if (rc.incremental_strain && time_step_number > 1) initial_volumetric_strain = volumetric_strain;
     double pressure_error = rc.pressure_tol * 2; int fss_iteration = 0;   // :345-346
@@ -325,6 +380,7 @@ template <int dim> class PoroElasticProblem {
   void restore_state() { check(poro_state_restore(ctx), "state_restore"); time_step_number = saved_step_number; }
   int run(const RunControls &rc, double *trace, int max_rows) {
     int rows = 0;
+    if (rc.refine_every > 0 && !pd->refined_box) throw std::runtime_error("run: refine_every needs a mask- or block-refined box (the mesh class the host provider can adapt)");
     initialize(rc);
     if (rows < max_rows) { double *r = trace + 8 * rows++; for (int i = 0; i < 8; ++i) r[i] = 0; r[6] = displacement_solver.last.iterations; }
     for (int s = 1; s <= rc.n_steps; ++s) { rows += time_step(rc, trace + 8 * rows, max_rows - rows); if (!rc.output_dir.empty()) postprocess(rc); }   // :327, :409-411
@@ -347,8 +403,14 @@ template <int dim> class PoroElasticProblem {
   void normal_strains() {
     get_normal_strain_components(); work.proj_rhs++;
   }
+  // the problem and its solver members move to another context (refine_mesh); the caller looks after the context left behind
+  void rebind(poro_ctx *c) {
+    ctx = c; pressure_solver.rebind(c); displacement_solver.rebind(c); strain_projector.set_solvers(c);
+    volumetric_strain.ctx = initial_volumetric_strain.ctx = c;
+  }
   bool first_assembly = true; int time_step_number = 0, saved_step_number = 0; double jacobian_dt = -1;
-  const ProblemData *pd;
+  const ProblemData *pd; int device_, operator_mode_;
+  std::unique_ptr<ProblemData> adapted;   // the mesh the last refine_mesh built (the first mesh belongs to the caller)
   static poro_ctx *make_ctx(ProblemData &P, int device, int operator_mode) {
     poro_ctx *c = nullptr;
     check(poro_ctx_create(&P.d, device, operator_mode, &c), "poro_ctx_create");

@@ -1,8 +1,10 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--atomic-scatter] [--fdm-fp32]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--atomic-scatter] [--fdm-fp32] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
-// (read_mesh, :438-445).  --output DIR writes DIR/solution-NNNN.vtk after every step like output_results (:227-291); AMR is out of scope.
+// (read_mesh, :438-445).  --output DIR writes DIR/solution-NNNN.vtk after every step like output_results (:227-291).
+// --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
+// (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -17,6 +19,7 @@ using namespace poro_host;
 int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl; return 1; }   // parse_command_line.h:9-13
   std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false;
+  int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -33,10 +36,15 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--two-level")) prec = PORO_PREC_TWO_LEVEL;   // Jacobi + block fast diagonalisation of the underlying / auxiliary box (refined boxes, rectangle-filling Gmsh meshes)
     else if (!std::strcmp(argv[i], "--atomic-scatter")) atomic_scatter = true;   // general meshes, --matrix-free: one launch per operator application with fp64 atomic adds (last bits differ from run to run)
     else if (!std::strcmp(argv[i], "--fdm-fp32")) fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) refine_every = std::atoi(argv[++i]);            // 0 = never (default)
+    else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
+    else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) coarsen_fraction = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
   if (fdm_fp32 && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
+  if (refine_every < 0) { std::cerr << "--refine-every needs a non-negative step count" << std::endl; return 1; }
+  if (refine_every > 0 && !mesh_file.empty()) { std::cerr << "--refine-every adapts boxes only (not --mesh)" << std::endl; return 1; }
   try {
     input_data::InputDataPoroel data;
     data.read_input_file(argv[1]);
@@ -52,11 +60,13 @@ int main(int argc, char **argv) {
     else {
       int n[3] = {1, 1, 1}; double size[3] = {1, 1, 1};
       for (int d = 0; d < data.dim; ++d) { n[d] = 1 << data.initial_refinement_level; size[d] = data.domain_size.at(d); }
-      build_box_problem(P, data.dim, n, size, degree);
+      if (refine_every > 0) build_refined_box_problem_mask(P, data.dim, n, size, degree, std::vector<uint8_t>((size_t)n[0] * n[1] * n[2], 0));
+      else build_box_problem(P, data.dim, n, size, degree);
     }
     RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
+    rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
     int n_steps = 0; for (double t = 0; t < data.t_max; t += data.time_step) ++n_steps;   // while (time < t_max) (:327)
     rc.n_steps = steps >= 0 ? steps : n_steps;
     std::vector<double> trace(8 * (size_t)(1 + rc.n_steps * rc.max_fss_iterations));
