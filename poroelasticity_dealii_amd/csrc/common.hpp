@@ -425,7 +425,8 @@ void fdmo_first_direction(hipStream_t s, const FdmOct &O, double *d, const doubl
 // red != null (partitioned runs): the all-reduced d.h (update_g: red[0]) / g.g and g.z (update_d: red[0], red[1]) instead of the block partials
 void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, double *g_oct, const double *h, const uint8_t *inert, const double *partials_dh, double *partials_out /*gg*/, const double *red = nullptr);
 void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z_oct, const double *partials_in /*2 sets*/, const double *red = nullptr,
-                   bool gz_from_pass = false /* g . z from O.gz_part (left by fdmo_apply) instead of the second set of partials_in */);
+                   bool gz_from_pass = false /* g . z from O.gz_part (left by fdmo_apply) instead of the second set of partials_in */,
+                   bool stream_x = false /* three components: non-temporal accesses to x (the caller keeps h in z's allocation, see pcg) */);
 void fdmo_dot_owned(hipStream_t s, const FdmOct &O, const double *a_oct, const double *b_oct, double *partials, const PcgScalars *gate);   // block partials of a.b over the planes this rank owns
 // slab form: the pieces of one application around the two all-to-alls (ctx_prec.hip drives them)
 void fdmo_slab_pass(hipStream_t s, const FdmOct &O, int pass /*1, 2, 3*/, const double *in, double *out, const PcgScalars *gate, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

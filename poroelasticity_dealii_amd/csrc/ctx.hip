@@ -323,18 +323,19 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
 // The three transform dispatches of the octant form.  A sampled call times them one by one (per-kernel roofline of the bench): the sampling runs on
 // fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
 // gz_part != null: pass 2 also leaves the partial sums of g . z there (returns true: no separate dot kernel)
-bool fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, const PcgScalars *gate, double *gz_part) {
+// scratch == null: the passes work on z itself (fp64 transforms only)
+bool fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, double *scratch, const PcgScalars *gate, double *gz_part) {
   Timed tm(c, "precondition_u_fdm");
   const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
   if (!begin_sampled_dispatch(c, names[0])) {
-    fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, nullptr, gz_part, c->fdm_precision);
+    fdmo_apply(c->stream, oct, g, z, scratch, gate, nullptr, gz_part, c->fdm_precision);
     return gz_part != nullptr;
   }
   c->timers[names[1]].enqueued++;
   c->timers[names[2]].enqueued++;
   hipEvent_t ev[6];
   for (auto &e : ev) e = event_get(c);
-  fdmo_apply(c->stream, oct, g, z, c->fdm_oct.t.p, gate, ev, gz_part, c->fdm_precision);
+  fdmo_apply(c->stream, oct, g, z, scratch, gate, ev, gz_part, c->fdm_precision);
   for (int k = 0; k < 3; ++k) {
     Timer &t = c->timers[names[k]];
     t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
@@ -348,6 +349,16 @@ int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts,
   build_fdm_u(c);
   const FdmOct *oct = c->fdm_oct.built ? &c->fdm_oct : nullptr;
   const bool separate_gz = std::getenv("PORO_FDMO_SEPARATE_GZ") != nullptr;    // A/B hook, read once per solve: g . z by its own dot kernel, as before pass 2 produced it
+  // Single-rank octant form: the iteration's live set is d + g + ONE octant-sized array that is h and z in turn, and x streams past the cache.
+  //   h | z: the operator writes h and the residual update is its only reader; then transform pass 1 (fp32 mode: pass 3) rewrites the whole array as z, whose last reader is the
+  //          direction update; then the operator writes h again.  The prologue has the same order (apply -> init_residual -> preconditioner -> first_direction).
+  //   fp64 transforms run on z itself, without the scratch array (k_fdmo_pass: "in place"); the fp32 mode keeps its float scratch array.
+  // PORO_FDMO_SEPARATE_BUFFERS (A/B hook, read once per solve): h in wh_u, the scratch array between the passes, plain accesses to x.  The timer family
+  // "fdm_u_shared_buffers" counts the solves that ran on the shared layout (a count, no time; it counts whether or not the context's timing is on).  pcg sees the
+  // layout from h == oct->z and tells the direction update to stream x.
+  const bool shared = oct && !oct->slab.on && !oct->planar && std::getenv("PORO_FDMO_SEPARATE_BUFFERS") == nullptr;
+  if (shared) c->timers["fdm_u_shared_buffers"].enqueued++;
+  double *const scratch = shared && c->fdm_precision != PORO_FDM_FP32 ? nullptr : c->fdm_oct.t.p;
   const ApplyFn P = [&](const double *g, double *z, double *in_iteration) {
     // g, z in octant form: three contiguous sweeps; inside the iteration the launches are gated on the device-side "solve finished" flag (before
     // pcg_scalars_start it still holds the previous solve's state)
@@ -361,13 +372,13 @@ int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts,
       fdmo_apply_planar(c->stream, *oct, g, z, gate);
     } else {
       // inside the iteration pass 2 leaves g . z (in oct->gz_part, which k_fdmo_update_d reads); the first application of a solve keeps k_fdmo_first_direction's dot
-      return fdm_u_octant_passes(c, *oct, g, z, gate, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
+      return fdm_u_octant_passes(c, *oct, g, z, scratch, gate, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
     }
     return false;
   };
   DiagVec dz = diag_u(c, c->dir_mask.p, false);
   dz.z = c->wz_u.p;
-  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
+  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, shared ? c->fdm_oct.z.p : c->wh_u.p, opts, info, &P,
                      c->pcg_hint_fdm_u, oct != nullptr /* every launch of an iteration is gated: overshooting is cheap */, oct);
   finish_u(c, false);
   return rc;

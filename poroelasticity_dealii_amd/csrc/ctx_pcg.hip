@@ -91,6 +91,7 @@ int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, 
   if (precond && !zbuf) throw Error("pcg: explicit preconditioner without a z vector");
   const int64_t n_own = owned(c, n, plane);
   const bool multi = c->comm.multi();
+  const bool stream_x = oct && h == oct->z.p;     // the caller put h into z's allocation (solve_u_fdm: the shared layout): x then streams past the cache in the direction update
   double *part = c->partials.p, *red = c->red.p; PcgScalars *sc = c->scal.p;
   double *part_dh = part + 3 * (size_t)kMaxPartials;      // slots of the fused / separate d.h partials
   const auto t_start = std::chrono::steady_clock::now();
@@ -136,7 +137,7 @@ int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, 
       }
       if (multi) { pcg_scalars_sum(s, part, 2, red + 1); allreduce_sum(c, red + 1, 2); }
       // (octant form: the transform passes leave their g . z partials in oct->gz_part - one per workgroup of pass 2, more than kMaxPartials - not in `part`)
-      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz_left);
+      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz_left, stream_x);
       else pcg_update_d_fused(s, sc, (it - 1) & 1, it, x, d, g, diag, prec, n, part, multi ? red + 1 : nullptr);
     }
     post_and_wait(c, nullptr, 0, sc); hs = c->mailbox->sc;

@@ -202,7 +202,10 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
 }
 // x += alpha d, then d = beta d - H' z unless the solve just finished (k_pcg_update_d_fused with the explicit z in octant form)
 // g . z: the gz_n per-workgroup partials of transform pass 2 (gz_part != null), else the second set of partials_in (separate dot kernel)
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
+// XNT: x is touched once per iteration and nowhere else: non-temporal accesses keep it from evicting d, g and the shared h | z array (224.6 MB at 72^3 Q2), which then
+// stay in the 256 MiB memory-side cache from one kernel of the iteration to the next (as in k_pcg_update_d_fused).  d and z keep plain accesses, and so does the
+// finishing branch below on purpose: it runs once per solve, after the last use of d, g and z.
+template <int NC, bool XNT> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
                                                                             const double *gz_part, int gz_n) {
   __shared__ double sh[5];
   if (sc->done) return;
@@ -216,7 +219,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctD
     return;
   }
   const double beta = gz / gh_old;
-  PORO_OCT_LOOP(D) {          // (two positions per thread, as in k_fdmo_update_g2, were measured here too: 72 instead of 59 us - the paired read-modify-writes of the nodal vectors cost more than the 16-byte octant reads save)
+  PORO_OCT_LOOP(D) {          // (two positions per thread, as in k_fdmo_update_g2, were measured here too: 72 instead of 59 us, and 111 instead of 70 us with d resident and x streamed - the paired read-modify-writes of the nodal vectors cost more than the 16-byte octant reads save)
     PORO_OCT_DECODE(D)
     double w[8];
 #pragma unroll
@@ -225,8 +228,9 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctD
 #pragma unroll
     for (int m = 0; m < 8; ++m) if (P.live[m]) {
       const int64_t dof = P.node[m] * NC + c;
-      const double dv = d[dof], xv = x[dof];
-      x[dof] = fma(alpha, dv, xv); d[dof] = fma(beta, dv, -w[m]);
+      const double dv = d[dof], xv = XNT ? __builtin_nontemporal_load(&x[dof]) : x[dof];
+      if (XNT) __builtin_nontemporal_store(fma(alpha, dv, xv), &x[dof]); else x[dof] = fma(alpha, dv, xv);
+      d[dof] = fma(beta, dv, -w[m]);
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) { sc->beta = beta; sc->gh2[parity ^ 1] = gz; }
@@ -324,6 +328,12 @@ template <int NT> struct PassGeom {
 // ghat^2 / den with ghat = (F x F x F) Q_g - which is what the accumulators hold after the first GEMM, next to the 1 / den that scales them.  Removed modes give
 // 1 / den = 0, pads are exact zeros and every tile of pass 2 belongs to one wave, so the workgroup's sum is its share of g . z: two FMAs per entry and one
 // 8-byte store, no extra load, no extra launch (P.gz_part[blockIdx.x]; k_fdmo_update_d adds the slots up in a fixed order)
+// In place (in == out; `in` and `out` carry no __restrict__): every workgroup loads exactly the R x C entries of its block that it stores, blocks of different workgroups are
+// disjoint, and the block is staged in full before the first store - all global loads of the input sit in the staging loop, whose values are in LDS by the barrier in front
+// of the first GEMM, and nothing but LDS and the transform matrices is read after it.  So pass 2 AND passes 1 / 3 may overwrite their input; the single-rank octant form in
+// fp64 runs g -> z, z -> z, z -> z without a scratch array (fdmo_apply).  Pad column: passes 1 and 3 of the displacement forms store it too (C = the row pitch, plan_pass) -
+// exact zeros, because the pad rows of the transform matrices are zero (pack_fragments) and the staged data are finite.  Pass 1 therefore rewrites every entry of the
+// array it stores into, pads included, whatever that array held before (the octant form's z doubles as the operator's output h, ctx.hip: solve_u_fdm).
 template <int NT, int MODE, int VAR, bool GZ = false>
 __global__ void __launch_bounds__(64 * pass_waves<NT>())
 k_fdmo_pass(OctPass P, const double *in, double *out) {
@@ -543,6 +553,8 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
 // loop is innermost, as in the fp64 kernel.  Padding: converted zeros are zeros; removed modes (lam = inf) give exactly 0 as in fp64 (guard on the fp64 sum).
 // GZ: g . z in fp64 from the fp32 values the pass holds - ghat and the rounded ghat / den it stores; they have the same sign, so every term is >= 0.
 // Range: |g| and |g| / den must be fp32-normal (include/poroel_hip.h).
+// Here pass 3 is the first writer of z, and it stores every entry of it, pad column included (C = the row pitch; the pad rows of the float matrices are zero, the float
+// intermediate is finite): z may hold anything before - it doubles as the operator's output h (ctx.hip: solve_u_fdm).
 template <int NT, int MODE, bool GZ = false>
 __global__ void __launch_bounds__(64 * pass_waves<NT>())
 k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
@@ -1107,6 +1119,9 @@ bool fdmo_usable(int dim, const int nn[3]) {
 
 void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s) {
   form_geometry(O, nn, coef, 3, 8, s);
+  // z doubles as the operator's nodal output h inside PCG (h and z are never live together, ctx.hip: solve_u_fdm): the octant array is the larger of the two (24 co >= n_u: 2 h >= n in every direction), checked here
+  const int64_t n_u = (int64_t)3 * nn[0] * nn[1] * nn[2];
+  if (n_u > O.n_oct) throw Error("fdmo_init: the octant array is smaller than the nodal vector");
   O.own_z = O.n[2];
   O.gz_n = 24 * pass2_chunks(O.hxp * O.h[1], O.nt);   // workgroups of pass 2: one g . z partial each (grows with the box - not bounded by kMaxPartials)
   O.gz_part.alloc(O.gz_n); O.gz_part.zero(s);
@@ -1199,7 +1214,10 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
   if (gz_part && n_items[1] != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
   P[1].gz_part = gz_part;
   PassStamps stamps; stamps.attach(s, P, n_items);
-  const double *const in[3] = {g_oct, scratch, scratch}; double *const out[3] = {scratch, scratch, z_oct};      // (pass 2 works in place)
+  // scratch == null (fp64 only): all three passes on z_oct itself, see "in place" at k_fdmo_pass.  The float intermediate of the fp32 mode needs its own array
+  if (f32 && !scratch) throw Error("fdmo_apply: the fp32 transforms need the scratch array");
+  double *const mid = scratch ? scratch : z_oct;
+  const double *const in[3] = {g_oct, mid, mid}; double *const out[3] = {mid, mid, z_oct};      // (pass 2 works in place)
   for (int k = 0; k < 3; ++k) launch_pass_nt(s, O.nt, f32 ? PassVariant::OctantF32 : PassVariant::Octant, P[k], n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
   stamps.dump(s);
 }
@@ -1353,8 +1371,14 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
   if (single) PORO_OCT_LAUNCH(k_fdmo_update_g, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
   else PORO_OCT_LAUNCH(k_fdmo_update_g2, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
 }
-void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass) {
-  PORO_OCT_LAUNCH(k_fdmo_update_d, O, sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red, gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0);
+template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass) {
+  hipLaunchKernelGGL((k_fdmo_update_d<NC, XNT>), oct_grid(O.co_stride, NC), kBlock, 0, s, dims_of(O), sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red,
+                     gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0);
+}
+void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x) {
+  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);       // (planar form)
+  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);
+  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);
 }
 
 }  // namespace poro
