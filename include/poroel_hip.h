@@ -290,6 +290,30 @@ enum { PORO_SCATTER_COLOURED = 0, PORO_SCATTER_ATOMIC = 1 };
 int  poro_ctx_set_scatter_mode(poro_ctx *ctx, int32_t mode);
 int  poro_ctx_get_scatter_mode(poro_ctx *ctx, int32_t *mode);
 
+/* Operator form of the matrix-free operator on REFINED BOXES (a uniform box with some cells split once, poro_desc.coarse = the uniform box; no box tag).
+ *   PORO_OPFORM_GENERAL (default): the general cell kernels over every cell.
+ *   PORO_OPFORM_HYBRID:            A x = S (A_box x_box - sum_{refined box cells c} K_c x_box) + sum_{fine cells f} K_f x,  x_box = S^T x, S = the injection box node ->
+ *                                  mesh node: the box's structured kernel over the whole box, the element matrix on the refined box cells (subtracted, owner computes), the
+ *                                  general cell kernels over the children only.  The results differ from the general form's by rounding (a few ulps of the sum of the
+ *                                  contributions); in PORO_SCATTER_COLOURED they are bitwise reproducible from call to call.
+ * May be changed between any two calls; governs the same applications as the scatter mode (Krylov operator, Chebyshev polynomial, two-level fine-level products,
+ * condensation, poro_apply_operator / poro_bench_operator) and composes with it: the fine-cell launches run in the context's scatter mode.  The set-up quantities
+ * (diagonal, lifting vector, the product with the constraints' inhomogeneities, self-checks) keep the general coloured form: PORO_VEC_DIAG_U and PORO_VEC_RHS_U do
+ * not depend on the form, bit for bit.
+ * The library derives everything itself from what the context holds, at the FIRST enable: the injection from the interpolation rows (box node b <-> the mesh node whose
+ * row is the single entry (b, 1.0)), the unrefined cells (dof list = the injected dof list of a box cell), the refined box cells (matched by none) and the fine cells (the
+ * rest: 2^dim per refined box cell), then compares one hybrid product with the general one (skipped under PORO_DIAG_SKIP_SELFCHECK=1).  That first enable costs
+ * device-to-host copies of the cell lists and vertices, host work, uploads, two box-sized device vectors and a stream synchronise: call it outside timed regions.
+ * Returns < 0 with a message, the form staying as it was, on: no coarse space; a partitioned context; a context not created with PORO_OP_MATRIX_FREE; a dimension /
+ * degree without structured kernel; a box node without injected image (an auxiliary box); unmatched cells; vertices of a matched cell more than 1e-12 of the box
+ * extent off the box cell's (a mapped mesh); a Dirichlet mask that differs from the box's at the injected dofs; different material constants; a failed self-check;
+ * an unknown form.  On a box-tagged context the call succeeds and changes nothing.  The form is never chosen automatically.
+ * The getter also reports the cells the general kernels run over per application (all cells in the general form, the fine cells in the hybrid one, 0 on a box-tagged
+ * context) and the refined box cells whose element products are subtracted (0 in the general form); either pointer may be NULL. */
+enum { PORO_OPFORM_GENERAL = 0, PORO_OPFORM_HYBRID = 1 };
+int  poro_ctx_set_operator_form(poro_ctx *ctx, int32_t form);
+int  poro_ctx_get_operator_form(poro_ctx *ctx, int32_t *form, int64_t *general_cells /* cells the general kernel runs over per application */, int64_t *removed_box_cells);
+
 /* Transform precision of PORO_PREC_FDM for the DISPLACEMENT system, where it runs in the single-rank 3D octant form (one rank, 3D, every Dirichlet condition on a pair of
  * opposite faces, half lines of at most 128 nodes).
  *   PORO_FDM_FP64 (default): the three transform passes on the fp64 matrix instruction.

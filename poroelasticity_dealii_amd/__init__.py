@@ -18,6 +18,7 @@ PREC_NONE, PREC_JACOBI, PREC_SSOR, PREC_FDM, PREC_ILU0, PREC_CHEBYSHEV, PREC_TWO
 STOP_RHS, STOP_REDUCTION = 0, 1
 OP_CSR, OP_MATRIX_FREE = 0, 1
 SCATTER_COLOURED, SCATTER_ATOMIC = 0, 1
+OPFORM_GENERAL, OPFORM_HYBRID = 0, 1
 FDM_FP64, FDM_FP32 = 0, 1
 MAT_A_U, MAT_MASS_P, MAT_LAPLACE_P, MAT_JACOBIAN_P = 0, 1, 2, 3
 VEC_U, VEC_RHS_U, VEC_P, VEC_P_OLD, VEC_DP, VEC_RESIDUAL_P, VEC_EPSV, VEC_EPSV0, VEC_SOURCE_P = range(9)
@@ -100,7 +101,7 @@ SENDRECV_FN = C.CFUNCTYPE(None, _dp, _dp, C.c_int64, C.c_int32, C.c_void_p)
 
 # every symbol include/poroel_hip.h declares (checked by the CPU test-suite against the built library)
 HIP_SYMBOLS = [
-    "poro_last_error", "poro_abi_version", "poro_ctx_create", "poro_ctx_destroy", "poro_ctx_synchronize", "poro_ctx_set_scatter_mode", "poro_ctx_get_scatter_mode", "poro_ctx_set_fdm_precision", "poro_ctx_get_fdm_precision", "poro_comm_unique_id", "poro_ctx_comm_init_rccl",
+    "poro_last_error", "poro_abi_version", "poro_ctx_create", "poro_ctx_destroy", "poro_ctx_synchronize", "poro_ctx_set_scatter_mode", "poro_ctx_get_scatter_mode", "poro_ctx_set_operator_form", "poro_ctx_get_operator_form", "poro_ctx_set_fdm_precision", "poro_ctx_get_fdm_precision", "poro_comm_unique_id", "poro_ctx_comm_init_rccl",
     "poro_ctx_comm_init_callbacks", "poro_vec_set", "poro_vec_get", "poro_vec_fill", "poro_vec_copy", "poro_vec_axpy", "poro_vec_norm",
     "poro_state_save", "poro_state_restore", "poro_disp_assemble_system", "poro_disp_solve", "poro_supports_preconditioner", "poro_pres_assemble_residual", "poro_pres_apply_boundary_values", "poro_pres_assemble_jacobian", "poro_pres_solve",
     "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
@@ -129,6 +130,8 @@ def load_hip():
         L.poro_ctx_synchronize.argtypes = [C.c_void_p]
         L.poro_ctx_set_scatter_mode.argtypes = [C.c_void_p, C.c_int32]
         L.poro_ctx_get_scatter_mode.argtypes = [C.c_void_p, _ip]
+        L.poro_ctx_set_operator_form.argtypes = [C.c_void_p, C.c_int32]
+        L.poro_ctx_get_operator_form.argtypes = [C.c_void_p, _ip, _lp, _lp]
         L.poro_ctx_set_fdm_precision.argtypes = [C.c_void_p, C.c_int32]
         L.poro_ctx_get_fdm_precision.argtypes = [C.c_void_p, _ip, _ip]
         L.poro_comm_unique_id.argtypes = [C.c_void_p]
@@ -459,6 +462,19 @@ class Context:
         self._chk(self.L.poro_ctx_get_scatter_mode(self.ptr, C.byref(m)))
         return m.value
 
+    def set_operator_form(self, form):
+        """OPFORM_GENERAL (default: the general cell kernels over every cell) or OPFORM_HYBRID for the matrix-free operator on refined boxes: the coarse box's structured
+        kernel over the whole box, minus the element products of the refined box cells, plus the general kernels over the fine cells only.  The first enable derives the
+        plan on the host and checks one product (outside timed regions); raises where the mesh cannot take the form, which then stays as it was.  A no-op on
+        box-tagged contexts"""
+        self._chk(self.L.poro_ctx_set_operator_form(self.ptr, int(form)))
+
+    def get_operator_form(self):
+        """(form, cells the general kernels run over per application, refined box cells whose element products are subtracted)"""
+        f, g, r = C.c_int32(), C.c_int64(), C.c_int64()
+        self._chk(self.L.poro_ctx_get_operator_form(self.ptr, C.byref(f), C.byref(g), C.byref(r)))
+        return f.value, g.value, r.value
+
     def set_fdm_precision(self, precision):
         """FDM_FP64 (default) or FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (the CG around it
         stays fp64); no effect on any other form"""
@@ -640,22 +656,23 @@ def rccl_unique_id():
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
+                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
-    Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once)."""
+    Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
+    hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it)."""
     H = load_host()
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
     if refine_every is not None:
         last = C.c_void_p()
-        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                                         int(refine_every), refine_fraction, coarsen_fraction, trace.ctypes.data_as(_dp), max_rows, C.byref(ctx), C.byref(last))
         if rows < 0:
             raise RuntimeError(H.poro_host_last_error().decode())
         return trace[:rows], Context(Problem(last.value) if last.value else problem, ptr=ctx)
-    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                            trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
     if rows < 0:
         raise RuntimeError(H.poro_host_last_error().decode())
@@ -670,10 +687,10 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False):
         self.H = load_host()
         self.max_fss = max_fss
-        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
+        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
         if not h:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         self.h = C.c_void_p(h)

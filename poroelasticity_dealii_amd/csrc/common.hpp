@@ -181,6 +181,20 @@ struct Comm {
 // the list of its faces with the cell whose diameter scales them
 struct KellyDev { bool built = false; int64_t n_faces = 0; DevBuf<int32_t> cell_a, cell_b, code, ent_face, ent_hcell; DevBuf<int64_t> ent_ptr; DevBuf<double> jump, eta; };
 
+// hybrid operator form on refined boxes (poro_ctx_set_operator_form; kernels_hyb.hip, ctx_hybrid.hip): everything derived on the host at the first enable
+struct HybridPlan {
+  bool built = false;
+  int64_t n_box_nodes = 0, n_fine_cells = 0, n_removed = 0, n_chunks = 0;
+  DevBuf<int64_t> inj;                                            // [box node] -> mesh node
+  DevBuf<int32_t> color_cells; std::vector<int64_t> color_off;    // the context's colour classes restricted to the fine cells (offsets from 0)
+  DevBuf<int32_t> spatial_cells;                                  // the fine cells in the Morton order of the atomic scatter mode
+  DevBuf<int32_t> removed_cells, slot;                            // the refined box cells; [box cell] -> its position in that list or -1
+  DevBuf<uint8_t> touched;                                        // [box node]: belongs to a refined cell (handled by the listed-node kernel)
+  DevBuf<double> Ke_t, V;                                         // the box's element matrix transposed; slab [refined cell][dofs per cell] of Ke x_box|_c
+  DevBuf<int64_t> nodes; DevBuf<int32_t> chunk_cls;               // the touched nodes sorted by position class, every class padded with -1 to whole waves; class of every 64-node chunk
+  DevBuf<double> x_box, y_box;                                    // box-sized work vectors of the plan (the box context's own belong to the two-level preconditioner)
+};
+
 struct BoxDev { int enabled = 0; int n[3] = {1, 1, 1}; int nn[3] = {1, 1, 1}; double h[3] = {1, 1, 1}; };
 
 }  // namespace poro
@@ -207,6 +221,8 @@ struct poro_ctx {
   // scatter mode of the general cell-loop operator (poro_ctx_set_scatter_mode).  spatial_cells: all cells in Morton order of their centroids, built the first time the
   // context enters the atomic mode
   int scatter_mode = 0; poro::DevBuf<int32_t> spatial_cells;
+  // operator form of the general matrix-free operator (poro_ctx_set_operator_form): PORO_OPFORM_GENERAL, or the hybrid of the box's structured kernel and the fine cells
+  int operator_form = 0; poro::HybridPlan hyb;
   // transform precision of the displacement system's block FDM where it runs in the single-rank 3D octant form (poro_ctx_set_fdm_precision); every other form ignores it
   int fdm_precision = 0;
   poro::DevBuf<uint8_t> dir_mask, node_mask; poro::DevBuf<double> dir_val; poro::DevBuf<int32_t> dir_dofs;
@@ -437,5 +453,12 @@ int kron_apply(hipStream_t s, const MfArgs &a, const double *x, double *y, bool 
                const PcgScalars *pcg = nullptr /* launch becomes a no-op once pcg->done / finishing is set */,
                const KronCheb *cheb = nullptr /* 3D only: store the Chebyshev update instead of the product (y is not written) */);   // returns the workgroup count (= partial slots used)
 void kron_fix_constrained(hipStream_t s, const MfArgs &a, const double *x, double *y, double *dot_partials, int slot_base);
+// ---- kernels_hyb.hip: the pieces of the hybrid operator form between the fine-cell launches and the box product ------------------
+void hyb_gather(hipStream_t s, int dim, int64_t n_box_nodes, const int64_t *inj, const double *x, double *x_box);   // x_box[b] = x[inj[b]], node-wise
+// y[inj[b]] += y_box[b] - sum over the refined box cells around b of (Ke x_box)'s row of b; `box` = mf_args of the box context (geometry, nodemask: Dirichlet columns zeroed
+// when constrained), Ke_t = its element matrix transposed; the pointers of HybridPlan
+struct HybCombine { int64_t n_box_nodes, n_removed, n_chunks; const int64_t *inj; const uint8_t *touched; const int32_t *removed_cells, *slot, *chunk_cls; const int64_t *nodes;
+                    const double *x_box, *y_box; double *V; };
+void hyb_combine(hipStream_t s, const MfArgs &box, const double *Ke_t, bool constrained, const HybCombine &h, double *y);
 
 }  // namespace poro

@@ -606,6 +606,28 @@ int poro_ctx_get_scatter_mode(poro_ctx *c, int32_t *mode) {
   return guarded([&] { if (!c || !mode) throw Error("null argument"); *mode = c->scatter_mode; return 0; });
 }
 
+int poro_ctx_set_operator_form(poro_ctx *c, int32_t form) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    if (form != PORO_OPFORM_GENERAL && form != PORO_OPFORM_HYBRID) throw Error("poro_ctx_set_operator_form: unknown form " + std::to_string(form) + " (PORO_OPFORM_GENERAL or PORO_OPFORM_HYBRID)");
+    if (c->box.enabled) return 0;   // the structured kernels already run on every cell: nothing to select
+    PORO_HIP(hipSetDevice(c->device));
+    if (form == PORO_OPFORM_HYBRID) hybrid_enable(c);   // throws where the mesh cannot take it: the form stays as it was (GENERAL, or a HYBRID that was accepted before)
+    c->operator_form = form;
+    return 0;
+  });
+}
+int poro_ctx_get_operator_form(poro_ctx *c, int32_t *form, int64_t *general_cells, int64_t *removed_box_cells) {
+  return guarded([&] {
+    if (!c || !form) throw Error("null argument");
+    const bool hybrid = c->operator_form == PORO_OPFORM_HYBRID;
+    *form = c->operator_form;
+    if (general_cells) *general_cells = c->box.enabled ? 0 : hybrid ? c->hyb.n_fine_cells : c->n_cells;
+    if (removed_box_cells) *removed_box_cells = hybrid ? c->hyb.n_removed : 0;
+    return 0;
+  });
+}
+
 // true where PORO_PREC_FDM of the displacement system runs in the single-rank 3D octant form.  Builds the block FDM where that is possible at all (one rank, 3D, separable
 // Dirichlet faces) - the numerical symmetry check of the eigenvectors is part of the build, so only then is the answer final
 static bool fdm_u_runs_octant(poro_ctx *c) {

@@ -258,8 +258,9 @@ void build_spatial_cells(poro_ctx *c) {
   c->spatial_cells.upload(cells);
 }
 
-// the general cell-loop operator y = A_u x in the context's scatter mode (set-up quantities call mfg_apply directly and stay coloured)
+// the general cell-loop operator y = A_u x in the context's scatter mode and operator form (set-up quantities call mfg_apply directly: coloured, over all cells)
 void mfg_operator(poro_ctx *c, const double *x, double *y, bool constrained) {
+  if (c->operator_form == PORO_OPFORM_HYBRID) { hybrid_operator(c, x, y, constrained); return; }
   const int32_t *all = nullptr;
   if (c->scatter_mode == PORO_SCATTER_ATOMIC) {
     // diagnostic PORO_MFG_ATOMIC_ORDER=colour: the single launch over the colour-sorted list instead (A/B of the cell order, profiles/mfg_atomic_scatter.json)

@@ -53,6 +53,7 @@ struct RunControls {
   int preconditioner_p = -1;                                        // pressure / projection solves; -1 = fast diagonalisation where the context supports it, else the two-level form, else Jacobi
   bool fdm_fp32 = false;                                            // PORO_FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (elsewhere no effect).  Never chosen automatically
   bool atomic_scatter = false;                                      // general meshes, matrix-free: PORO_SCATTER_ATOMIC (one launch per operator application; not bitwise reproducible).  Never chosen automatically
+  bool hybrid_operator = false;                                     // refined boxes, matrix-free: PORO_OPFORM_HYBRID (structured kernel on the coarse box + general kernels on the fine cells); a no-op on box-tagged meshes, an error on meshes that cannot take it.  Never chosen automatically
   int refine_every = 0;                                             // refine_mesh when time_step_number % refine_every == 0 (the reference hard-wires 5, PoroelasticityFSS.h:333); 0 = never
   double refine_fraction = 0.6, coarsen_fraction = 0.4;             // refine_and_coarsen_fixed_fraction (:460-462)
 };
@@ -180,7 +181,7 @@ template <int dim> class PoroElasticProblem {
   ProblemData *release_problem() { return adapted.release(); }        // the mesh refine_mesh built last, handed to the caller (null: never refined)
 
   // refine_mesh (:447-498) on one-level refined boxes, followed by the two calls of :338-339.  Sequence: estimate (KellyErrorEstimator on the device) -> mark
-  // (fixed fraction + level limits, mesh.hpp) -> the new ProblemData from the mask -> a new context in the same operator mode, scatter mode and FDM precision ->
+  // (fixed fraction + level limits, mesh.hpp) -> the new ProblemData from the mask -> a new context in the same operator mode, scatter mode, FDM precision and operator form ->
   // setup_dofs -> transfer of p, eps_v, eps_v0 on the device -> swap, the old context is destroyed.  The preconditioner choice of initialize() is made again on the
   // new context (rc.preconditioner < 0 lands on the two-level form once hanging nodes exist).  Work counters carry over; the displacement warm start is lost (every
   // reinit of the reference leaves zero vectors).  Returns the cell counts before and after.
@@ -203,6 +204,9 @@ template <int dim> class PoroElasticProblem {
     struct Guard { poro_ctx *c; ~Guard() { if (c) poro_ctx_destroy(c); } } fresh{make_ctx(*N, device_, operator_mode_)};
     if (scatter != PORO_SCATTER_COLOURED || rc.atomic_scatter) check(poro_ctx_set_scatter_mode(fresh.c, rc.atomic_scatter ? PORO_SCATTER_ATOMIC : scatter), "ctx_set_scatter_mode");
     if (fdm_req != PORO_FDM_FP64) check(poro_ctx_set_fdm_precision(fresh.c, fdm_req), "ctx_set_fdm_precision");
+    int32_t form = PORO_OPFORM_GENERAL;
+    check(poro_ctx_get_operator_form(ctx, &form, nullptr, nullptr), "ctx_get_operator_form");
+    if (form != PORO_OPFORM_GENERAL || rc.hybrid_operator) check(poro_ctx_set_operator_form(fresh.c, rc.hybrid_operator ? PORO_OPFORM_HYBRID : form), "ctx_set_operator_form");
     poro_ctx *old = ctx;
     const std::pair<int64_t, int64_t> counts(O.d.n_cells, N->d.n_cells);
     rebind(fresh.c);
@@ -327,6 +331,7 @@ template <int dim> class PoroElasticProblem {
   void initialize(const RunControls &rc) {
     if (rc.atomic_scatter) check(poro_ctx_set_scatter_mode(context(), PORO_SCATTER_ATOMIC), "ctx_set_scatter_mode");
     if (rc.fdm_fp32) check(poro_ctx_set_fdm_precision(context(), PORO_FDM_FP32), "ctx_set_fdm_precision");
+    if (rc.hybrid_operator) check(poro_ctx_set_operator_form(context(), PORO_OPFORM_HYBRID), "ctx_set_operator_form");
     choose_preconditioners(rc);
     setup_dofs();                                          // :308
     pressure_solver.solution = rc.p_init;                  // :311
