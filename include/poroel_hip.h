@@ -197,7 +197,13 @@ typedef struct poro_desc {
   poro_constraints cons_p;   /* pressure space; also used by the strain projection (StrainProjector.h:191-194) */
   /* EXTENSION (not in the reference, whose pressure space has "no dirichlet pressure BC's", PoroElasticPressureSolver.h:69-70): prescribed pressures,
    * e.g. a drained boundary p = 0.  Needed to validate the corrected-physics switches on Terzaghi's consolidation problem.  The rows are
-   * taken out of the pressure Newton system (residual 0, update 0); poro_pres_apply_boundary_values writes the values into PORO_VEC_P. */
+   * taken out of the pressure Newton system (residual 0, update 0); poro_pres_apply_boundary_values writes the values into PORO_VEC_P.
+   * One rank; not together with hanging pressure nodes; not with PORO_PREC_TWO_LEVEL.  Preconditioners of poro_pres_solve: PORO_PREC_JACOBI / NONE for any set.
+   * Where the set is exactly a union of whole faces of a uniform box (box.enabled) or tensor-product grid (tensor) - the values may differ from node to node -
+   * also PORO_PREC_FDM: the free block of a M + kappa K is then a Kronecker sum of the 1D matrices without those end nodes and has its own exact fast
+   * diagonalisation (direct solve on matrix-free boxes, info.iterations = 0; preconditioner of CG on tensor grids and CSR contexts); the update is exactly 0
+   * on the prescribed rows (that path first zeroes PORO_VEC_RESIDUAL_P and PORO_VEC_DP there: the rows are not part of the system, whatever a caller stored in them).
+   * poro_supports_preconditioner(ctx, 1, PORO_PREC_FDM) tells.  The projection (which_system = 2) is not affected by the list. */
   int64_t n_dirichlet_p;
   const int32_t *dirichlet_dof_p;
   const double  *dirichlet_value_p;
@@ -243,7 +249,7 @@ enum { PORO_STOP_RHS = 0, PORO_STOP_REDUCTION = 1 };
  * preconditioner z = omega D^-1 g + P B_H^-1 P^T g: Jacobi on the refined mesh plus the BLOCK fast diagonalisation of the underlying uniform box as coarse solve (P = the
  * FE interpolation of poro_coarse_space).  The CG iteration count stays bounded under uniform refinement of the whole configuration.  With poro_coarse_space.ptr_p ...
  * also for poro_pres_solve (a M + kappa K: Jacobi + the box's exact scalar fast diagonalisation through the vertex interpolation; hanging nodes allowed, prescribed
- * pressures not) and poro_proj_solve (accepted; Jacobi alone is already mesh-independent on the mass matrix and needs fewer iterations). */
+ * pressures not: those have PORO_PREC_FDM where they cover whole faces, see poro_desc.dirichlet_dof_p) and poro_proj_solve (accepted; Jacobi alone is already mesh-independent on the mass matrix and needs fewer iterations). */
 enum { PORO_PREC_NONE = 0, PORO_PREC_JACOBI = 1, PORO_PREC_SSOR = 2, PORO_PREC_FDM = 3, PORO_PREC_ILU0 = 4, PORO_PREC_CHEBYSHEV = 5, PORO_PREC_TWO_LEVEL = 6 };
 enum { PORO_OP_CSR = 0, PORO_OP_MATRIX_FREE = 1 };
 enum { PORO_MAT_A_U = 0, PORO_MAT_MASS_P = 1, PORO_MAT_LAPLACE_P = 2, PORO_MAT_JACOBIAN_P = 3 };
@@ -362,7 +368,8 @@ int  poro_state_restore(poro_ctx *ctx);
 int  poro_disp_assemble_system(poro_ctx *ctx, int rebuild_matrix);
 /* PoroElasticDisplacementSolver<dim>::solve (:294-307): PCG, warm start from PORO_VEC_U, then constraints.distribute. */
 int  poro_disp_solve(poro_ctx *ctx, const poro_solver_opts *opts, poro_solve_info *info);
-/* 1 if `preconditioner` can be used by poro_pres_solve / poro_proj_solve (which_system = 1) or poro_disp_solve (which_system = 0) on this context, else 0 */
+/* 1 if `preconditioner` can be used by poro_pres_solve / poro_proj_solve (which_system = 1) or poro_disp_solve (which_system = 0) on this context, else 0.
+ * which_system = 2: poro_proj_solve / poro_proj_solve_many alone (the mass matrix: prescribed pressures do not restrict it; they do restrict which_system = 1) */
 int  poro_supports_preconditioner(poro_ctx *ctx, int32_t which_system, int32_t preconditioner);
 
 /* PoroElasticPressureSolver<dim>::assemble_residual (:113-155) from PORO_VEC_{P,P_OLD,EPSV,EPSV0}; l2 = residual.l2_norm() (PoroelasticityFSS.h:364) */

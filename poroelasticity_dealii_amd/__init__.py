@@ -540,7 +540,7 @@ class Context:
         return SolverOpts(abs_tol, rel_tol, max_iter, prec, omega, stop_rule, poly_degree)
 
     def supports_preconditioner(self, which_system, prec):
-        """which_system: 0 displacement, 1 pressure / projection."""
+        """which_system: 0 displacement, 1 pressure / projection, 2 projection alone (prescribed pressures restrict 1, not 2)."""
         return bool(self.L.poro_supports_preconditioner(self.ptr, which_system, prec))
 
     def disp_solve(self, abs_tol=1e-12, rel_tol=0.0, max_iter=1000, prec=PREC_JACOBI, omega=1.2, reduction=False, poly_degree=0):

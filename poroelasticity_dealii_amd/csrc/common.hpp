@@ -229,6 +229,9 @@ struct poro_ctx {
   std::vector<int32_t> h_dir_dof; std::vector<double> h_dir_val;
   poro::ConsDev cons_u, cons_p;
   poro::DevBuf<uint8_t> pdir_mask; poro::DevBuf<double> pdir_val; int64_t n_pdir = 0;   // extension: prescribed pressures
+  // the prescribed set is exactly a union of whole faces (direction, side) of `lines` (face analysis at set-up): deleting those rows and columns leaves a Kronecker sum of
+  // 1D matrices without their end nodes, which the second table set below diagonalises
+  bool pdir_faces_ok = false; int pdir_face[3][2] = {{0, 0}, {0, 0}, {0, 0}};
   poro::DevBuf<int32_t> bface_cell, bface_local, bface_id, neu_label, neu_comp; poro::DevBuf<double> neu_val;
   int64_t n_bfaces = 0; int n_neumann = 0;
   // matrices
@@ -252,6 +255,9 @@ struct poro_ctx {
   poro::DevBuf<double> cheb_z, cheb_t;
   poro::FdmOct fdm_oct;
   poro::FdmOct fdm_p_fused;          // the scalar Q1 systems through the same transform kernel (3D boxes, lines of <= 128 vertices)
+  // second table set of the Q1 systems: the pressure Jacobian with the prescribed faces' end nodes removed (built only when n_pdir != 0; fdm_p / fdm_p_fused stay the
+  // projection mass matrix's, which has no fixed ends).  fdm_t1 / fdm_t2 are shared
+  poro::FdmScalar fdm_pj; poro::FdmOct fdm_pj_fused;
   // two-level preconditioner (poro_desc.coarse): the underlying uniform box as a context of its own (same device and stream) + the node-wise interpolation P and its transpose
   struct Interp { int64_t n_fine = 0, n_coarse = 0; int lanes = 1, lanes_t = 1;   /* lanes per row of the interpolation kernels, from the mean row length */ poro::DevBuf<int64_t> p_ptr, pt_ptr; poro::DevBuf<int32_t> p_col, pt_col; poro::DevBuf<double> p_w, pt_w; };   // P (rows = fine) and its transpose as CSR
   struct TwoLevel : Interp { poro_ctx *box = nullptr; Interp pressure; } two_level;   // (the base part: displacement nodes; .pressure: pressure dofs, optional)
@@ -424,7 +430,8 @@ void fdmo_scalar_upload_dir(FdmOct &O, int dir, const std::vector<double> &S, co
 void fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate = nullptr);
 void fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate = nullptr);   // up to 3 right-hand sides in one set of launches
 // block partials of |y_e - b_e|^2 and |b_e|^2 for up to three (y, b) pairs: sets 2e and 2e + 1 of `partials`
-void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials);
+// mask != null: rows with mask[i] != 0 count in neither norm (prescribed rows of a system solved on its free rows)
+void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask = nullptr);
 // slab partitions: nn = LOCAL vertices, the last direction's matrices are uploaded for the GLOBAL line; the three sweeps separately (all-to-alls in between, ctx_prec.hip)
 void fdmo_scalar_init_slab(FdmOct &O, const int nn[3], int rank, const std::vector<int> &node_layers, hipStream_t s);
 void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double kappa, const double *in, double *out);

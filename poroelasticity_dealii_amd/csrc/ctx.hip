@@ -423,8 +423,10 @@ struct Q1System {
   double *x;
   const double *b;
   int *hint;                          // iteration counts of the last two solves
-  const uint8_t *inert_two_level;     // the inert mask handed to PCG per branch (FDM: none); null selects the kernel form without a mask
+  const uint8_t *inert_two_level;     // the inert mask handed to PCG per branch; null selects the kernel form without a mask
   const uint8_t *inert_jacobi;
+  const uint8_t *inert_fdm = nullptr; // FDM: none, except with prescribed pressures on whole faces (the free-row system: residual norm and g . z see free rows only)
+  bool fixed_ends = false;            // FDM: the table set without the prescribed faces' end nodes (c->fdm_pj) instead of c->fdm_p
 };
 
 // uniform box, matrix-free: both matrices are constant-coefficient stencils
@@ -434,8 +436,10 @@ bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE &&
 // distributed form is the same inverse): x_e = (a M + kappa K)^-1 b_e, then the residuals are checked against the reference's stopping rule with one poll
 // for all norms.  info[e].iterations = 0 marks a directly solved system; returns whether every system met the rule (if not, x_e is a good start for CG).
 // y: scratch of n vectors.  batched: all right-hand sides in one set of launches (c->fdm_p_fused)
+// fixed_ends + mask (prescribed pressures on whole faces): x_e = J_ff^-1 b_e on the free rows and exactly 0 on the masked ones; the check leaves the masked rows out,
+// where (J x)_i is the coupling to the free neighbours and not part of the system
 bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *const *b, double *const *x, double *y_scratch, bool batched,
-                     const poro_solver_opts *opts, poro_solve_info *info) {
+                     const poro_solver_opts *opts, poro_solve_info *info, bool fixed_ends = false, const uint8_t *mask = nullptr) {
   hipStream_t s = c->stream;
   const double *y[3];
   for (int e = 0; e < n; ++e) y[e] = y_scratch + (size_t)e * c->n_p;
@@ -445,7 +449,7 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
     fdmo_scalar_apply_many(s, c->fdm_p_fused, a, kappa, n, b, x);
   } else {
     const double kk[3] = {kappa, kappa, kappa};
-    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e]);
+    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e], fixed_ends);
   }
   for (int e = 0; e < n; ++e) {
     {
@@ -454,7 +458,7 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
     }
     exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p);
   }
-  la_residual_norms_many(s, n, y, b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p);
+  la_residual_norms_many(s, n, y, b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p, mask);
   pcg_scalars_sum(s, c->partials.p, 2 * n, c->red.p);
   allreduce_sum(c, c->red.p, 2 * n);
   post_and_wait(c, c->red.p, 2 * n);
@@ -500,21 +504,22 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
   DiagVec dz;
   dz.full = q.dinv;
   if (opts->preconditioner == PORO_PREC_FDM) {
-    build_fdm_p(c);
+    if (q.fixed_ends) build_fdm_pj(c); else build_fdm_p(c);
     const double kk[3] = {q.kappa, q.kappa, q.kappa};
     if (!c->wz_p.p) c->wz_p.alloc(n);
     if (direct_first) {
       poro_solve_info direct;
-      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct)) {
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct, q.fixed_ends, q.inert_fdm)) {
         if (info) *info = direct;
         return 0;
       }
     }
     const ApplyFn P = [&](const double *gg, double *z, double *) {
-      fdm_precondition_p(c, q.a, kk, gg, z);
+      fdm_precondition_p(c, q.a, kk, gg, z, q.fixed_ends);
       return false;
     };
     dz.z = c->wz_p.p;
+    dz.inert = q.inert_fdm;
     return pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, &P, q.hint);
   }
   int rc;
@@ -859,6 +864,12 @@ int poro_supports_preconditioner(poro_ctx *c, int32_t which_system, int32_t prec
   if (prec == PORO_PREC_NONE || prec == PORO_PREC_JACOBI) return 1;
   if (prec == PORO_PREC_TWO_LEVEL) return which_system == 0 ? two_level_supported(c) : (two_level_supported_p(c) && !c->n_pdir);
   if (which_system == 0 && c->cons_u.n) return prec == PORO_PREC_CHEBYSHEV;      // condensed operators exist at operator level only: Jacobi, the polynomial built on it, the two-level form above
+  if (which_system == 2) {                                                        // the projection's mass matrix has no prescribed rows
+    if (c->cons_p.n) return 0;
+    if (prec == PORO_PREC_SSOR || prec == PORO_PREC_ILU0) return !c->comm.multi();
+    return prec == PORO_PREC_FDM ? fdm_p_supported(c) : 0;
+  }
+  if (which_system == 1 && c->n_pdir && !c->cons_p.n) return prec == PORO_PREC_FDM && fdm_pj_supported(c);   // prescribed pressures: whole faces of a box / tensor grid on one rank
   if (which_system == 1 && (c->cons_p.n || c->n_pdir)) return 0;
   if (prec == PORO_PREC_SSOR || prec == PORO_PREC_ILU0) return !c->comm.multi() && (which_system == 1 || c->operator_mode == PORO_OP_CSR);
   if (prec == PORO_PREC_CHEBYSHEV) return which_system == 0;
@@ -948,8 +959,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     PORO_HIP(hipSetDevice(c->device));
     if (c->jac_dt < 0) throw Error("pres_solve before pres_assemble_jacobian");
     const int prec = opts->preconditioner;
-    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && !c->n_pdir))
-      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL) only");
+    const bool fdm_fixed_ends = prec == PORO_PREC_FDM && fdm_pj_supported(c);      // prescribed pressures on whole faces of a box / tensor grid, one rank
+    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && !c->n_pdir) && !fdm_fixed_ends)
+      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL) only; prescribed pressures that cover whole faces of a uniform box or tensor-product grid on one rank: also PORO_PREC_FDM");
     if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c))
       throw Error("PORO_PREC_TWO_LEVEL (pressure): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)");
     Q1System J;
@@ -964,6 +976,12 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     J.hint = c->pcg_hint_p;
     J.inert_two_level = c->cons_p.n ? c->cons_p.inert.p : nullptr;
     J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;
+    if (fdm_fixed_ends) {
+      J.fixed_ends = true;
+      J.inert_fdm = c->pdir_mask.p;
+      la_mask_zero(c->stream, vec(c, PORO_VEC_RESIDUAL_P), c->pdir_mask.p, c->n_p);   // R_f: poro_pres_assemble_residual leaves zeros there already; a caller's own right-hand side may not
+      la_mask_zero(c->stream, vec(c, PORO_VEC_DP), c->pdir_mask.p, c->n_p);           // the update is 0 there: CG never touches an inert row of its start vector, the direct solve writes 0 itself
+    }
     // one rank or slabs, uniform box (2D or 3D): the fast diagonalisation is the exact inverse of J, so the update is computed directly and its residual checked
     // against the reference's stopping rule (:175); a failed check goes on to CG with that update as start
     bool direct_first = false;

@@ -94,6 +94,8 @@ double estimate_lmax_u(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj);
 // ---- fast-diagonalisation preconditioners (ctx_prec.hip) ------------------------------------------------------------------------------
 bool fdm_p_supported(poro_ctx *c);
 void build_fdm_p(poro_ctx *c);
+bool fdm_pj_supported(poro_ctx *c);      // prescribed pressures on whole faces of a box / tensor grid, one rank
+void build_fdm_pj(poro_ctx *c);          // the Q1 tables of the pressure Jacobian with those faces' end nodes removed (never built without prescribed pressures)
 void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool self_in_place = false /* the caller has already put its own block into recv */);
 void setup_two_level(poro_ctx *c, const poro_desc *d);                // uploads P and its transpose (poro_desc.coarse)
 bool two_level_supported(poro_ctx *c);
@@ -103,7 +105,7 @@ void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double om
 void fdm_precondition_u_slab(poro_ctx *c, const double *g_quadrant, double *z_quadrant, const PcgScalars *gate);
 void fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision: of the octant form's transforms
 void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision);   // nodal g -> the form that is built (or the nodal kernels of fdm_precondition_u) -> nodal z
-void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z);
+void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, bool fixed_ends = false /* the table set of build_fdm_pj */);
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);

@@ -95,6 +95,35 @@ void build_fdm_p(poro_ctx *c) {
   }
   c->fdm_p.built = true;
 }
+// ---- the second table set: the pressure Jacobian with whole prescribed faces (one rank) ---------------------------------------------------------------------------
+// Deleting the rows and columns of a face from a M + kappa K deletes the end node of that direction's 1D matrices; fdmu_eig_1d gives their eigenpairs in full-length
+// storage (zero rows of S at removed nodes, zero columns and lam = inf behind the free modes), so the transform kernels run unchanged and return exactly 0 there.
+bool fdm_pj_supported(poro_ctx *c) { return c->n_pdir && c->pdir_faces_ok && !c->comm.multi() && fdm_p_supported(c); }
+void build_fdm_pj(poro_ctx *c) {
+  if (c->fdm_pj.built) return;
+  if (!fdm_pj_supported(c)) throw Error("PORO_PREC_FDM with prescribed pressures needs a uniform box or tensor-product grid on one rank whose prescribed set is a union of whole faces");
+  if (c->timing) c->timers["fdm_pj_build"].enqueued += 1;          // (a count, no time: contexts without prescribed pressures never get here)
+  FdmScalar &F = c->fdm_pj; F.dim = c->dim;
+  int np3[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, c->dim == 3 ? c->lines.n[2] + 1 : 1};
+  const bool fused = fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
+  if (fused) fdmo_scalar_init(c->fdm_pj_fused, np3, c->stream);
+  for (int d = 0; d < c->dim; ++d) {
+    const std::vector<double> &hcell = c->lines.hcell[d]; const int n = (int)hcell.size() + 1;
+    const bool lo = c->pdir_face[d][0] != 0, hi = c->pdir_face[d][1] != 0;
+    std::vector<double> S, lam;
+    if (!lo && !hi && c->lines.uniform) q1_eig(n - 1, hcell[0], S, lam); else fdmu_eig_1d(1, hcell, lo, hi, S, lam);   // (free directions: the tables of fdm_p)
+    if (fused) fdmo_scalar_upload_dir(c->fdm_pj_fused, d, S, lam, n);
+    std::vector<double> St((size_t)n * n);
+    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
+    // six-launch form: its kernel divides by a + sum k_d lam_d.  A removed mode's coefficient is exactly 0 (zero row of S^T), so any finite positive eigenvalue in its
+    // place gives the 0 that lam = inf gives, without inf * 0 where a coefficient k_d is 0
+    for (double &l : lam) if (!(l < 1e300)) l = 1e300;
+    FdmDir &D = F.dir[d]; D.n = n; D.S.upload(S); D.St.upload(St); D.lam.upload(lam);
+  }
+  c->fdm_pj_fused.built = fused;
+  if (c->fdm_t1.n < (size_t)c->n_p) { c->fdm_t1.alloc(c->n_p); c->fdm_t2.alloc(c->n_p); }
+  F.built = true;
+}
 // every rank sends block q of `send` (blk doubles) to rank q and receives block q of `recv` from it
 void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool self_in_place) {
   Comm &cm = c->comm; const int N = cm.part.n_ranks, r = cm.part.rank;
@@ -121,9 +150,16 @@ void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool 
   } else throw Error("partitioned context without a communicator");
 }
 // z = (a M + sum_d k_d K_d)^-1 g for the Q1 space of the (global) box
-void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z) {
+// fixed_ends: the second table set (whole prescribed faces removed, one rank): z = J_ff^-1 g_f on the free rows, exactly 0 on the prescribed ones whatever g holds there
+void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, bool fixed_ends) {
   Timed tm(c, "precondition_p_fdm");
   hipStream_t s = c->stream;
+  if (fixed_ends) {
+    Timed tf(c, "precondition_p_fdm_fixed_ends");
+    if (c->fdm_pj_fused.built && k[0] == k[1] && k[1] == k[2]) fdmo_scalar_apply(s, c->fdm_pj_fused, a, k[0], g, z);
+    else fdm_apply(s, c->fdm_pj, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);
+    return;
+  }
   if (!c->comm.multi()) {
     if (c->fdm_p_fused.built && k[0] == k[1] && k[1] == k[2]) fdmo_scalar_apply(s, c->fdm_p_fused, a, k[0], g, z);
     else fdm_apply(s, c->fdm_p, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);

@@ -121,6 +121,32 @@ void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, c
   C.inert.upload(inert);
 }
 
+// Is the prescribed-pressure set exactly a union of whole faces (direction, side) of the line structure?  Then the free block of a M + kappa K is the Kronecker sum of
+// the 1D matrices without those end nodes (ctx_prec.hip: build_fdm_pj).  The prescribed VALUES may differ from node to node: they never enter the Newton matrix.
+static void analyse_pdir_faces(poro_ctx *c, const std::vector<uint8_t> &pm) {
+  c->pdir_faces_ok = false;
+  for (int d = 0; d < 3; ++d) c->pdir_face[d][0] = c->pdir_face[d][1] = 0;
+  if (!c->n_pdir || !c->lines.on || c->comm.multi() || c->cons_p.n) return;
+  const int dim = c->dim; const int64_t np[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, dim == 3 ? c->lines.n[2] + 1 : 1};
+  if (np[0] * np[1] * np[2] != c->n_p) return;
+  auto node = [&](int64_t i, int64_t j, int64_t k) { return (k * np[1] + j) * np[0] + i; };
+  for (int d = 0; d < dim; ++d) for (int side = 0; side < 2; ++side) {
+    bool all = true; const int64_t fixed = side ? np[d] - 1 : 0; const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
+    for (int64_t a = 0; a < np[d1] && all; ++a) for (int64_t b = 0; b < np[d2]; ++b) {
+      int64_t ix[3]; ix[d] = fixed; ix[d1] = a; ix[d2] = b;
+      if (!pm[node(ix[0], ix[1], ix[2])]) { all = false; break; }
+    }
+    c->pdir_face[d][side] = all ? 1 : 0;
+  }
+  for (int64_t k = 0; k < np[2]; ++k) for (int64_t j = 0; j < np[1]; ++j) for (int64_t i = 0; i < np[0]; ++i) {
+    const int64_t ix[3] = {i, j, k}; bool on = false;
+    for (int d = 0; d < dim; ++d) on = on || (ix[d] == 0 && c->pdir_face[d][0]) || (ix[d] == np[d] - 1 && c->pdir_face[d][1]);
+    if (on != (pm[node(i, j, k)] != 0)) return;          // partial faces, interior nodes: the Jacobi path as before
+  }
+  for (int d = 0; d < dim; ++d) if (np[d] - c->pdir_face[d][0] - c->pdir_face[d][1] < 1) return;   // (a direction without a free node: nothing to solve)
+  c->pdir_faces_ok = true;
+}
+
 void setup(poro_ctx *c, const poro_desc *d) {
   if (d->abi_version != PORO_ABI_VERSION) throw Error("poro_desc.abi_version mismatch");
   if (d->dim != 2 && d->dim != 3) throw Error("dim must be 2 or 3");
@@ -256,9 +282,10 @@ void setup(poro_ctx *c, const poro_desc *d) {
       if (d->n_dirichlet_p < 0 || (d->n_dirichlet_p && (!d->dirichlet_dof_p || !d->dirichlet_value_p))) throw Error("bad prescribed-pressure list");
       for (int64_t i = 0; i < d->n_dirichlet_p; ++i) { const int32_t dof = d->dirichlet_dof_p[i]; if (dof < 0 || dof >= c->n_p) throw Error("dirichlet_dof_p out of range"); pm[dof] = 1; pv[dof] = d->dirichlet_value_p[i]; }
       c->n_pdir = d->n_dirichlet_p;
-      if (c->n_pdir) { if (c->comm.part.n_ranks > 1) throw Error("prescribed pressures are implemented for one rank"); c->pdir_mask.upload(pm); c->pdir_val.upload(pv); }
+      if (c->n_pdir) { if (c->comm.part.n_ranks > 1) throw Error("prescribed pressures are implemented for one rank (there: PORO_PREC_JACOBI for any set, PORO_PREC_FDM where they cover whole faces of a uniform box or tensor-product grid)"); c->pdir_mask.upload(pm); c->pdir_val.upload(pv); }
       upload_constraints(c->cons_p, d->cons_p, c->n_p, &pm, "cons_p");
-      if (c->cons_p.n && c->n_pdir) throw Error("prescribed pressures together with hanging pressure nodes are not supported"); }
+      if (c->cons_p.n && c->n_pdir) throw Error("prescribed pressures together with hanging pressure nodes are not supported (prescribed pressures: meshes without constraint lists in the pressure space, one rank)");
+      analyse_pdir_faces(c, pm); }
     { std::vector<uint8_t> nm((size_t)(c->n_u / c->dim), 0); for (int64_t i = 0; i < d->n_dirichlet; ++i) nm[d->dirichlet_dof[i] / c->dim] |= (uint8_t)(1u << (d->dirichlet_dof[i] % c->dim)); c->node_mask.upload(nm); c->h_node_mask = std::move(nm); }
     if (d->n_dirichlet) c->dir_dofs.upload(d->dirichlet_dof, d->n_dirichlet);
     if (d->box.enabled) {   // are all constrained dofs on the box boundary?  (lets the matrix-free kernels skip mask loads in the interior)

@@ -1284,7 +1284,13 @@ static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kap
   const int hx = O.h[0], hy = O.h[1];
   if (O.scalar_tables.size() >= 8) { PORO_HIP(hipStreamSynchronize(s)); O.scalar_tables.pop_front(); }   // (a changing coefficient, e.g. a varying time step: drop the oldest)
   std::vector<double> Bt((size_t)hx * hy);
-  for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx) Bt[(size_t)my * hx + mx] = a + kappa * (O.h_lam[0][0][0][mx] + O.h_lam[0][1][0][my]);
+  // a removed mode (lam = inf: a line whose end node is prescribed) is marked inf outright - pass 2 then multiplies its coefficient by exactly 0 - instead of a + kappa inf,
+  // which is NaN where kappa = 0
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx) {
+    const double lx = O.h_lam[0][0][0][mx], ly = O.h_lam[0][1][0][my];
+    Bt[(size_t)my * hx + mx] = (lx < 1e300 && ly < 1e300) ? a + kappa * (lx + ly) : inf;
+  }
   O.scalar_tables.emplace_back(); auto &T = O.scalar_tables.back(); T.a = a; T.kappa = kappa; T.t.upload(Bt); return T.t.p;
 }
 void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double kappa, const double *in, double *out) {

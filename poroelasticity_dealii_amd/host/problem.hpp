@@ -316,9 +316,14 @@ template <int dim> class PoroElasticProblem {
     displacement_solver.control.preconditioner = rc.preconditioner >= 0 ? rc.preconditioner
         : poro_supports_preconditioner(context(), 0, PORO_PREC_FDM) ? PORO_PREC_FDM : poro_supports_preconditioner(context(), 0, PORO_PREC_TWO_LEVEL) ? PORO_PREC_TWO_LEVEL : PORO_PREC_CHEBYSHEV;
     if (displacement_solver.control.preconditioner == PORO_PREC_CHEBYSHEV) { displacement_solver.control.omega = rc.chebyshev_ratio; displacement_solver.control.poly_degree = rc.chebyshev_degree; }
-    pressure_solver.control.preconditioner = strain_projector.control.preconditioner =
-        rc.preconditioner == PORO_PREC_SSOR ? PORO_PREC_SSOR : rc.preconditioner_p >= 0 ? rc.preconditioner_p
-        : poro_supports_preconditioner(context(), 1, PORO_PREC_FDM) ? PORO_PREC_FDM : PORO_PREC_JACOBI;
+    // the pressure Jacobian and the projection's mass matrix are asked separately: prescribed pressures take rows out of the former only, so the projection keeps the
+    // fast diagonalisation (and its batched direct solve) whatever the prescribed set looks like
+    const auto q1_choice = [&](int which_system) {
+      return rc.preconditioner == PORO_PREC_SSOR ? (int)PORO_PREC_SSOR : rc.preconditioner_p >= 0 ? rc.preconditioner_p
+          : poro_supports_preconditioner(context(), which_system, PORO_PREC_FDM) ? (int)PORO_PREC_FDM : (int)PORO_PREC_JACOBI;
+    };
+    pressure_solver.control.preconditioner = q1_choice(1);
+    strain_projector.control.preconditioner = q1_choice(2);
     // the pressure Jacobian's stiffness part makes Jacobi-CG grow with 1/h: the two-level form where the mesh carries a coarse space.  (The projection's mass matrix
     // is well conditioned under Jacobi on any mesh: 12-15 iterations, fewer than the additive two-level form needs; below ~4k pressure dofs a CG iteration is
     // launch-bound and the two-level form's extra launches cost more than the iterations it saves - profiles/r03_refined_box_step.json.)

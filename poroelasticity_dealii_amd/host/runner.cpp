@@ -1,12 +1,15 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
 // (read_mesh, :438-445).  --output DIR writes DIR/solution-NNNN.vtk after every step like output_results (:227-291).
+// --pressure-bc LABEL=VALUE (repeatable; an extension, the reference has no pressure boundary conditions) prescribes the pressure on a boundary label, e.g. a drained face
+// `--pressure-bc 3=0`; the run then also prints which preconditioners the pressure and projection systems got.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
@@ -20,6 +23,7 @@ int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl; return 1; }   // parse_command_line.h:9-13
   std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false;
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
+  std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -40,6 +44,12 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) refine_every = std::atoi(argv[++i]);            // 0 = never (default)
     else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) coarsen_fraction = std::atof(argv[++i]);
+    else if (!std::strcmp(argv[i], "--pressure-bc") && i + 1 < argc) {           // prescribed pressure VALUE on the boundary LABEL (one rank; boxes: whole faces, which keeps the fast diagonalisation)
+      const char *arg = argv[++i], *eq = std::strchr(arg, '='); char *end = nullptr, *end2 = nullptr;
+      const long label = std::strtol(arg, &end, 10); const double value = eq ? std::strtod(eq + 1, &end2) : 0.0;
+      if (!eq || end != eq || eq == arg || !end2 || end2 == eq + 1 || *end2 || label < 0) { std::cerr << "--pressure-bc needs LABEL=VALUE, got " << arg << std::endl; return 1; }
+      pressure_labels.push_back((int32_t)label); pressure_values.push_back(value);
+    }
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
@@ -56,6 +66,7 @@ int main(int argc, char **argv) {
     P.bc.neumann_labels.assign(data.stress_boundary_labels.begin(), data.stress_boundary_labels.end());
     P.bc.neumann_components.assign(data.stress_boundary_components.begin(), data.stress_boundary_components.end());
     P.bc.neumann_values = data.stress_boundary_values;
+    P.bc.pressure_labels = pressure_labels; P.bc.pressure_values = pressure_values;
     P.mat = data.material();
     if (!mesh_file.empty()) { P.mesh = read_gmsh22(mesh_file); P.finalize(degree); attach_auxiliary_box(P, degree); }   // (coarse space of --two-level / --fastest where the mesh fills a rectangle)
     else {
@@ -73,8 +84,15 @@ int main(int argc, char **argv) {
     std::vector<double> trace(8 * (size_t)(1 + rc.n_steps * rc.max_fss_iterations));
     int rows;
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
-    if (data.dim == 2) { PoroElasticProblem<2> prob(P, device, op); rows = prob.run(rc, trace.data(), (int)trace.size() / 8); }
-    else { PoroElasticProblem<3> prob(P, device, op); rows = prob.run(rc, trace.data(), (int)trace.size() / 8); }
+    static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
+    auto go = [&](auto &prob) {
+      rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
+      if (!pressure_labels.empty())        // (only with the extension, so the reference's log stays as it is)
+        std::cout << "prescribed pressures: " << P.d.n_dirichlet_p << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner]
+                  << ", projection preconditioner: " << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
+    };
+    if (data.dim == 2) { PoroElasticProblem<2> prob(P, device, op); go(prob); }
+    else { PoroElasticProblem<3> prob(P, device, op); go(prob); }
     for (int r = 1; r < rows; ++r) {
       const double *t = &trace[8 * r];
       if (t[1] == 1) std::cout << "Time: " << t[0] * rc.time_step << std::endl;                  // :330
