@@ -198,12 +198,20 @@ typedef struct poro_desc {
   /* EXTENSION (not in the reference, whose pressure space has "no dirichlet pressure BC's", PoroElasticPressureSolver.h:69-70): prescribed pressures,
    * e.g. a drained boundary p = 0.  Needed to validate the corrected-physics switches on Terzaghi's consolidation problem.  The rows are
    * taken out of the pressure Newton system (residual 0, update 0); poro_pres_apply_boundary_values writes the values into PORO_VEC_P.
-   * One rank; not together with hanging pressure nodes; not with PORO_PREC_TWO_LEVEL.  Preconditioners of poro_pres_solve: PORO_PREC_JACOBI / NONE for any set.
+   * One rank.  Preconditioners of poro_pres_solve: PORO_PREC_JACOBI / NONE for any set.
    * Where the set is exactly a union of whole faces of a uniform box (box.enabled) or tensor-product grid (tensor) - the values may differ from node to node -
    * also PORO_PREC_FDM: the free block of a M + kappa K is then a Kronecker sum of the 1D matrices without those end nodes and has its own exact fast
    * diagonalisation (direct solve on matrix-free boxes, info.iterations = 0; preconditioner of CG on tensor grids and CSR contexts); the update is exactly 0
    * on the prescribed rows (that path first zeroes PORO_VEC_RESIDUAL_P and PORO_VEC_DP there: the rows are not part of the system, whatever a caller stored in them).
-   * poro_supports_preconditioner(ctx, 1, PORO_PREC_FDM) tells.  The projection (which_system = 2) is not affected by the list. */
+   * poro_supports_preconditioner(ctx, 1, PORO_PREC_FDM) tells.  The projection (which_system = 2) is not affected by the list.
+   * Together with hanging pressure nodes (cons_p; a drained face on a locally refined mesh) the two lists are analysed at set-up.  A hanging dof may have prescribed
+   * masters (the normal case; its row then reads their values).  A dof may be in BOTH lists only if all its masters are prescribed and its value is
+   * sum w * value(master) + inhomogeneity, to 1e-12 of the largest prescribed magnitude (1e-12 absolute if that is 0); any other overlap is refused with the dof
+   * named.  The Newton system is C^T J C without the prescribed rows: residual condensed first, then zeroed on the prescribed rows; the update is 0 on the prescribed
+   * rows and distributed homogeneously, so a dof in both lists gets 0.  PORO_PREC_FDM is not available there (hanging nodes).  PORO_PREC_TWO_LEVEL, with or
+   * without hanging nodes: where poro_desc.coarse.box_problem carries a prescribed set of its own that covers whole faces, and every dof of this mesh whose
+   * interpolation row is a single entry of weight 1 on a prescribed coarse dof is prescribed here too; the coarse solve is then the box's matrix without those
+   * faces, z = omega D^-1 g + P (J_H)_ff^-1 P^T g.  poro_supports_preconditioner(ctx, 1, PORO_PREC_TWO_LEVEL) tells. */
   int64_t n_dirichlet_p;
   const int32_t *dirichlet_dof_p;
   const double  *dirichlet_value_p;
@@ -249,7 +257,7 @@ enum { PORO_STOP_RHS = 0, PORO_STOP_REDUCTION = 1 };
  * preconditioner z = omega D^-1 g + P B_H^-1 P^T g: Jacobi on the refined mesh plus the BLOCK fast diagonalisation of the underlying uniform box as coarse solve (P = the
  * FE interpolation of poro_coarse_space).  The CG iteration count stays bounded under uniform refinement of the whole configuration.  With poro_coarse_space.ptr_p ...
  * also for poro_pres_solve (a M + kappa K: Jacobi + the box's exact scalar fast diagonalisation through the vertex interpolation; hanging nodes allowed, prescribed
- * pressures not: those have PORO_PREC_FDM where they cover whole faces, see poro_desc.dirichlet_dof_p) and poro_proj_solve (accepted; Jacobi alone is already mesh-independent on the mass matrix and needs fewer iterations). */
+ * pressures where the coarse box carries them as whole faces, see poro_desc.dirichlet_dof_p) and poro_proj_solve (accepted; Jacobi alone is already mesh-independent on the mass matrix and needs fewer iterations). */
 enum { PORO_PREC_NONE = 0, PORO_PREC_JACOBI = 1, PORO_PREC_SSOR = 2, PORO_PREC_FDM = 3, PORO_PREC_ILU0 = 4, PORO_PREC_CHEBYSHEV = 5, PORO_PREC_TWO_LEVEL = 6 };
 enum { PORO_OP_CSR = 0, PORO_OP_MATRIX_FREE = 1 };
 enum { PORO_MAT_A_U = 0, PORO_MAT_MASS_P = 1, PORO_MAT_LAPLACE_P = 2, PORO_MAT_JACOBIAN_P = 3 };
@@ -374,7 +382,10 @@ int  poro_supports_preconditioner(poro_ctx *ctx, int32_t which_system, int32_t p
 
 /* PoroElasticPressureSolver<dim>::assemble_residual (:113-155) from PORO_VEC_{P,P_OLD,EPSV,EPSV0}; l2 = residual.l2_norm() (PoroelasticityFSS.h:364) */
 int  poro_pres_assemble_residual(poro_ctx *ctx, double time_step, double *l2);
-/* extension: PORO_VEC_P[dof] = value on the prescribed-pressure dofs of the descriptor; a no-op without any; call after setting the initial pressure */
+/* extension: PORO_VEC_P[dof] = value on the prescribed-pressure dofs of the descriptor; a no-op without any; call after setting the initial pressure (and after
+ * poro_state_transfer_p).  On a context that also has hanging pressure nodes (cons_p) the pressure constraints are then distributed WITH their inhomogeneities,
+ * p[h] = sum w p[master] + b, so that a hanging row with a prescribed master is conforming from the start: only updates are distributed afterwards, homogeneously,
+ * and would carry a violation along for ever.  The prescribed dofs hold their listed values exactly.  Contexts without cons_p: unchanged, bit for bit. */
 int  poro_pres_apply_boundary_values(poro_ctx *ctx);
 /* PoroElasticPressureSolver<dim>::assemble_jacobian (:158-169) */
 int  poro_pres_assemble_jacobian(poro_ctx *ctx, double time_step);

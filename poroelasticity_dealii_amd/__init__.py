@@ -233,6 +233,8 @@ def load_host():
         L.poro_host_runner_work.restype = None
         L.poro_host_runner_postprocess.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.poro_host_runner_state.argtypes = [C.c_void_p, C.c_int]
+        L.poro_host_runner_preconditioners.argtypes = [C.c_void_p, _ip]
+        L.poro_host_runner_preconditioners.restype = None
         L.poro_host_runner_free.argtypes = [C.c_void_p]
         L.poro_host_runner_free.restype = None
         _host = L
@@ -406,7 +408,10 @@ class Problem:
         return self
 
     def set_pressure_bc(self, conditions):
-        """extension (the reference has no pressure boundary conditions): prescribed pressure [(boundary label, value)], e.g. a drained face p = 0"""
+        """extension (the reference has no pressure boundary conditions): prescribed pressure [(boundary label, value)], e.g. a drained face p = 0.  One rank.  Also on
+        meshes with hanging nodes (refined boxes, adapted meshes): every vertex of the labelled faces is listed, a hanging one among them with the value its (listed)
+        masters give.  The coarse problem of PREC_TWO_LEVEL (refined boxes: same labels; Gmsh grids with an auxiliary box: the labels translated to the box's sides)
+        gets the same condition, also when it was built before this call"""
         lab, pl = _arr_i([c[0] for c in conditions]); val, pv = _arr_d([c[1] for c in conditions])
         if load_host().poro_host_set_pressure_bc(self.handle, len(conditions), pl, pv) != 0:
             raise RuntimeError(load_host().poro_host_last_error().decode())
@@ -560,6 +565,8 @@ class Context:
         self._chk(self.L.poro_pres_assemble_jacobian(self.ptr, dt))
 
     def pres_apply_boundary_values(self):
+        """VEC_P = listed value on the prescribed dofs; with hanging pressure nodes as well the constraints are then distributed, p[h] = sum w p[master] + b, so that
+        the pressure is conforming beside a prescribed master (no-op without prescribed pressures)"""
         self._chk(self.L.poro_pres_apply_boundary_values(self.ptr))
 
     def pres_solve(self, abs_tol=0.0, rel_tol=1e-8, max_iter=1000, prec=PREC_JACOBI, omega=1.0):
@@ -712,7 +719,9 @@ class Runner:
 
     def adapt(self, refine_fraction=0.6, coarsen_fraction=0.4):
         """refine_mesh (PoroelasticityFSS.h:447-498) + the re-assembly of :338-339 between two steps: estimate, mark, new mesh, new context, transfer.  Returns the
-        cell counts (before, after); .problem / .ctx then refer to the new mesh, which the runner owns and frees (the problem handed to the constructor stays the caller's)"""
+        cell counts (before, after); .problem / .ctx then refer to the new mesh, which the runner owns and frees (the problem handed to the constructor stays the caller's).
+        Prescribed pressures (Problem.set_pressure_bc) are carried to every new mesh and re-imposed on the transferred pressure, which is conforming afterwards;
+        the preconditioners are chosen again for the new context"""
         cells = (C.c_int64 * 2)()
         if self.H.poro_host_runner_adapt(self.h, refine_fraction, coarsen_fraction, cells) != 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
@@ -734,6 +743,12 @@ class Runner:
         """PoroelasticityFSS.h:409-411: shear strains, effective stresses (PORO_VEC_STRESS0+e) and, with a directory, solution-NNNN.vtk"""
         if self.H.poro_host_runner_postprocess(self.h, output_dir.encode() if output_dir else None, int(corrected)) < 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
+
+    def preconditioners(self):
+        """(displacement, pressure, projection): the PREC_* the driver chose for the current context (made in initialize(), and again after every adapt())"""
+        out = (C.c_int32 * 3)()
+        self.H.poro_host_runner_preconditioners(self.h, out)
+        return tuple(out)
 
     def work(self):
         """cumulative work counters since creation"""

@@ -148,6 +148,7 @@ struct ConsDev {
   DevBuf<int32_t> dof, master; DevBuf<int64_t> ptr; DevBuf<double> weight, inhom;
   DevBuf<int32_t> t_master, t_dof; DevBuf<int64_t> t_ptr; DevBuf<double> t_weight;
   DevBuf<uint8_t> inert;   // byte mask: constrained (Dirichlet or hanging) dofs stay out of the Krylov system
+  DevBuf<uint8_t> hanging; // pressure space with both lists only: the hanging dofs alone (the projection's mass matrix has no prescribed rows)
   bool any_inhom = false;
 };
 
@@ -233,6 +234,7 @@ struct poro_ctx {
   // 1D matrices without their end nodes, which the second table set below diagonalises
   bool pdir_faces_ok = false; int pdir_face[3][2] = {{0, 0}, {0, 0}, {0, 0}};
   poro::DevBuf<int32_t> bface_cell, bface_local, bface_id, neu_label, neu_comp; poro::DevBuf<double> neu_val;
+  poro::DevBuf<int32_t> bface_order; std::vector<int64_t> bface_group_off;   // boundary faces sorted by (colour of the cell, local face): the groups of asm_u_neumann
   int64_t n_bfaces = 0; int n_neumann = 0;
   // matrices
   poro::CsrDev Ap, Au;                       // pressure pattern (mass, Laplace, Jacobian share it), displacement pattern
@@ -260,7 +262,7 @@ struct poro_ctx {
   poro::FdmScalar fdm_pj; poro::FdmOct fdm_pj_fused;
   // two-level preconditioner (poro_desc.coarse): the underlying uniform box as a context of its own (same device and stream) + the node-wise interpolation P and its transpose
   struct Interp { int64_t n_fine = 0, n_coarse = 0; int lanes = 1, lanes_t = 1;   /* lanes per row of the interpolation kernels, from the mean row length */ poro::DevBuf<int64_t> p_ptr, pt_ptr; poro::DevBuf<int32_t> p_col, pt_col; poro::DevBuf<double> p_w, pt_w; };   // P (rows = fine) and its transpose as CSR
-  struct TwoLevel : Interp { poro_ctx *box = nullptr; Interp pressure; } two_level;   // (the base part: displacement nodes; .pressure: pressure dofs, optional)
+  struct TwoLevel : Interp { poro_ctx *box = nullptr; Interp pressure; bool pdir_nested = false; /* prescribed pressures: every fine dof on a prescribed coarse dof is prescribed */ } two_level;   // (the base part: displacement nodes; .pressure: pressure dofs, optional)
   bool borrowed_stream = false;     // (the box context of a two-level preconditioner runs on its parent's stream)
   poro::FdmU fdm_u; poro::DevBuf<double> fdmu_t1, fdmu_t2, wz_u; int fdm_u_state = 0 /* 0 unknown, 1 usable, -1 not separable */; std::string fdm_u_why;
   std::vector<uint8_t> h_node_mask;
@@ -367,7 +369,8 @@ struct AsmArgs {
 void asm_u_matrix(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *val, double *lift);
 void asm_u_element_matrix(hipStream_t s, const AsmArgs &a, int32_t cell, double *Ke);
 void asm_u_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *p, double *rhs);
-void asm_u_neumann(hipStream_t s, const AsmArgs &a, int64_t n_bfaces, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id,
+// order / group_off: the boundary faces grouped by (colour of the cell, local face number), one launch per group (no atomics, fixed summation order)
+void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const std::vector<int64_t> &group_off, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id,
                    int n_neu, const int32_t *label, const int32_t *comp, const double *value, double *rhs);
 void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *M, double *K, double *src);
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *u, int n_comp, const int32_t *comps /*host*/,

@@ -427,7 +427,12 @@ struct Q1System {
   const uint8_t *inert_jacobi;
   const uint8_t *inert_fdm = nullptr; // FDM: none, except with prescribed pressures on whole faces (the free-row system: residual norm and g . z see free rows only)
   bool fixed_ends = false;            // FDM: the table set without the prescribed faces' end nodes (c->fdm_pj) instead of c->fdm_p
+  bool coarse_fixed_ends = false;     // two-level: the same table set of the coarse box, (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
+  bool distribute_inhom = true;       // constraints.distribute with the inhomogeneities; an UPDATE of a vector that already carries them (dp beside prescribed pressures) is distributed without
 };
+
+// the projection's mass matrix has no prescribed rows: where the pressure space has both lists its inert rows are the hanging ones alone
+const uint8_t *proj_inert(poro_ctx *c) { return c->cons_p.hanging.p ? c->cons_p.hanging.p : c->cons_p.inert.p; }
 
 // uniform box, matrix-free: both matrices are constant-coefficient stencils
 bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled; }
@@ -527,7 +532,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     if (!c->wz_p.p) c->wz_p.alloc(n);
     const double om = opts->omega > 0 ? opts->omega : 1.0;
     const ApplyFn P = [&](const double *gg, double *z, double *) {
-      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om);
+      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om, q.inert_two_level, q.coarse_fixed_ends);
       return false;
     };
     dz.z = c->wz_p.p;
@@ -537,7 +542,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     dz.inert = q.inert_jacobi;
     rc = pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, nullptr, q.hint);
   }
-  la_cons_expand(c->stream, c->cons_p, q.x, true);                              // constraints.distribute (:180, StrainProjector.h:216)
+  la_cons_expand(c->stream, c->cons_p, q.x, q.distribute_inhom);                // constraints.distribute (:180, StrainProjector.h:216)
   return rc;
 }
 
@@ -815,7 +820,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         if (c->mf_variant == 1 && kron_supported(c->dim, c->k_u) && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) check_sum_factorised_operator(c);
         lifting_from_wh(c);
       }
-      asm_u_neumann(s, a, c->n_bfaces, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
+      asm_u_neumann(s, a, c->bface_order.p, c->bface_group_off, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
       if (!c->diag_u.p) c->diag_u.alloc(c->n_u);
       la_copy(s, c->diag_u.p, c->diag_u_local.p, c->n_u);
       exchange_add(c, c->diag_u.p, c->n_u, c->comm.part.plane_u);
@@ -862,7 +867,8 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
 int poro_supports_preconditioner(poro_ctx *c, int32_t which_system, int32_t prec) {
   if (!c) return 0;
   if (prec == PORO_PREC_NONE || prec == PORO_PREC_JACOBI) return 1;
-  if (prec == PORO_PREC_TWO_LEVEL) return which_system == 0 ? two_level_supported(c) : (two_level_supported_p(c) && !c->n_pdir);
+  // (pressure Jacobian with prescribed rows: the coarse box must carry the condition as whole faces, see two_level_supported_pj; the projection has no such rows)
+  if (prec == PORO_PREC_TWO_LEVEL) return which_system == 0 ? two_level_supported(c) : (which_system == 1 && c->n_pdir) ? two_level_supported_pj(c) : two_level_supported_p(c);
   if (which_system == 0 && c->cons_u.n) return prec == PORO_PREC_CHEBYSHEV;      // condensed operators exist at operator level only: Jacobi, the polynomial built on it, the two-level form above
   if (which_system == 2) {                                                        // the projection's mass matrix has no prescribed rows
     if (c->cons_p.n) return 0;
@@ -932,6 +938,12 @@ int poro_pres_apply_boundary_values(poro_ctx *c) {
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     if (c->n_pdir) la_set_constrained(c->stream, vec(c, PORO_VEC_P), c->pdir_mask.p, c->pdir_val.p, c->n_p);
+    if (c->n_pdir && c->cons_p.n) {
+      // hanging nodes beside the prescribed set: p[h] = sum w p[m] + b, so that a row with a prescribed master is conforming from the start (only updates are
+      // distributed afterwards, homogeneously).  A dof in both lists reproduces its value up to rounding; the second pass makes it the listed value exactly
+      la_cons_expand(c->stream, c->cons_p, vec(c, PORO_VEC_P), true);
+      la_set_constrained(c->stream, vec(c, PORO_VEC_P), c->pdir_mask.p, c->pdir_val.p, c->n_p);
+    }
     return 0;
   });
 }
@@ -960,8 +972,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     if (c->jac_dt < 0) throw Error("pres_solve before pres_assemble_jacobian");
     const int prec = opts->preconditioner;
     const bool fdm_fixed_ends = prec == PORO_PREC_FDM && fdm_pj_supported(c);      // prescribed pressures on whole faces of a box / tensor grid, one rank
-    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && !c->n_pdir) && !fdm_fixed_ends)
-      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL) only; prescribed pressures that cover whole faces of a uniform box or tensor-product grid on one rank: also PORO_PREC_FDM");
+    const bool two_level_pdir = prec == PORO_PREC_TWO_LEVEL && c->n_pdir && two_level_supported_pj(c);   // the coarse box carries the prescribed set as whole faces
+    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && (!c->n_pdir || two_level_pdir)) && !fdm_fixed_ends)
+      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL; with prescribed pressures where the coarse box carries them as whole faces) only; prescribed pressures that cover whole faces of a uniform box or tensor-product grid on one rank: also PORO_PREC_FDM");
     if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c))
       throw Error("PORO_PREC_TWO_LEVEL (pressure): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)");
     Q1System J;
@@ -974,8 +987,13 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     J.x = vec(c, PORO_VEC_DP);
     J.b = vec(c, PORO_VEC_RESIDUAL_P);
     J.hint = c->pcg_hint_p;
-    J.inert_two_level = c->cons_p.n ? c->cons_p.inert.p : nullptr;
-    J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;
+    J.inert_two_level = J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;     // hanging and prescribed rows alike (the union where both lists are present)
+    J.coarse_fixed_ends = two_level_pdir;
+    if (c->n_pdir && (c->cons_p.n || two_level_pdir)) {
+      J.distribute_inhom = false;
+      la_mask_zero(c->stream, vec(c, PORO_VEC_RESIDUAL_P), c->pdir_mask.p, c->n_p);   // as on the fixed-ends path below: the prescribed rows are not part of the system, and the update is 0 there,
+      la_mask_zero(c->stream, vec(c, PORO_VEC_DP), c->pdir_mask.p, c->n_p);           // so that a hanging row beside them (expanded homogeneously) gets its free masters' share alone
+    }
     if (fdm_fixed_ends) {
       J.fixed_ends = true;
       J.inert_fdm = c->pdir_mask.p;
@@ -1004,7 +1022,7 @@ int poro_proj_assemble_matrix(poro_ctx *c) {
     exchange_add(c, c->diag_M.p, c->n_p, c->comm.part.plane_p);
     if (!c->dinv_M.p) c->dinv_M.alloc(c->n_p);
     la_reciprocal(c->stream, c->dinv_M.p, c->diag_M.p, c->n_p);
-    if (c->cons_p.n) la_mask_zero(c->stream, c->dinv_M.p, c->cons_p.inert.p, c->n_p);
+    if (c->cons_p.n) la_mask_zero(c->stream, c->dinv_M.p, proj_inert(c), c->n_p);
     c->projection_matrix_ready = true; return 0;
   });
 }
@@ -1051,7 +1069,7 @@ int poro_proj_solve(poro_ctx *c, int32_t entry, const poro_solver_opts *opts, po
     M.x = vec(c, PORO_VEC_STRAIN0 + entry);
     M.b = vec(c, PORO_VEC_PROJ_RHS0 + entry);
     M.hint = c->pcg_hint_proj;
-    M.inert_two_level = M.inert_jacobi = c->cons_p.n ? c->cons_p.inert.p : nullptr;
+    M.inert_two_level = M.inert_jacobi = c->cons_p.n ? proj_inert(c) : nullptr;
     return solve_q1(c, M, opts, info);
   });
 }

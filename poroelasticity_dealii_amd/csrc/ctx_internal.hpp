@@ -100,7 +100,8 @@ void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool 
 void setup_two_level(poro_ctx *c, const poro_desc *d);                // uploads P and its transpose (poro_desc.coarse)
 bool two_level_supported(poro_ctx *c);
 bool two_level_supported_p(poro_ctx *c);
-void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g
+bool two_level_supported_pj(poro_ctx *c);  // ... for the pressure Jacobian with prescribed rows: the coarse box carries them as whole faces (its second table set is the coarse solve)
+void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, bool coarse_fixed_ends = false);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g, 0 on the inert rows; coarse_fixed_ends: the coarse matrix without its prescribed rows
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega);   // z = omega D^-1 g + P B_H^-1 P^T g
 void fdm_precondition_u_slab(poro_ctx *c, const double *g_quadrant, double *z_quadrant, const PcgScalars *gate);
 void fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision: of the octant form's transforms

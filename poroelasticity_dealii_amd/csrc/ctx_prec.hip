@@ -408,6 +408,21 @@ void setup_two_level(poro_ctx *c, const poro_desc *d) {
   if (d->coarse.ptr_p) {
     if (!d->coarse.node_p || !d->coarse.weight_p) throw Error("poro_desc.coarse: node_p / weight_p missing");
     upload_interp(T.pressure, c->n_p, general ? c->comm.ifc_p.n_owned : c->n_p, T.box->n_p, d->coarse.ptr_p, d->coarse.node_p, d->coarse.weight_p, "pressure", general ? 1 << dim : 0);
+    // prescribed pressures: a fine dof that IS a coarse dof (one entry of weight 1) with a prescribed coarse value must be prescribed here as well, or the coarse
+    // space would lack the function the fine space has there
+    T.pdir_nested = false;
+    const poro_desc *H = d->coarse.box_problem;
+    if (c->n_pdir && H->n_dirichlet_p > 0 && H->dirichlet_dof_p) {
+      std::vector<uint8_t> fine(c->n_p, 0), coarse(T.box->n_p, 0);
+      for (int64_t i = 0; i < d->n_dirichlet_p; ++i) fine[d->dirichlet_dof_p[i]] = 1;
+      for (int64_t i = 0; i < H->n_dirichlet_p; ++i) coarse[H->dirichlet_dof_p[i]] = 1;      // (range-checked when the box's context was created)
+      bool ok = true;
+      for (int64_t i = 0; i < c->n_p && ok; ++i) {
+        const int64_t k = d->coarse.ptr_p[i];
+        if (d->coarse.ptr_p[i + 1] - k == 1 && std::fabs(d->coarse.weight_p[k] - 1.0) <= 1e-12 && coarse[d->coarse.node_p[k]] && !fine[i]) ok = false;
+      }
+      T.pdir_nested = ok;
+    }
   }
 }
 bool two_level_supported(poro_ctx *c) {
@@ -416,18 +431,25 @@ bool two_level_supported(poro_ctx *c) {
   return c->two_level.box->fdm_u_state == 1;
 }
 bool two_level_supported_p(poro_ctx *c) { return c->two_level.box && c->two_level.pressure.n_fine == c->n_p && fdm_p_supported(c->two_level.box); }
+// the pressure Jacobian with prescribed rows: the coarse solve is (J_H)_ff^-1, the box's second table set, so the box must carry a prescribed set of whole faces itself,
+// and the fine mesh must prescribe every dof that sits on a prescribed coarse dof (setup_two_level: pdir_nested)
+bool two_level_supported_pj(poro_ctx *c) {
+  return c->n_pdir && two_level_supported_p(c) && c->two_level.pdir_nested && c->two_level.box->n_pdir && fdm_pj_supported(c->two_level.box);
+}
 // the scalar analogue for the pressure Jacobian a M + kappa K and the projection mass matrix (a = 1, kappa = 0): Jacobi on this mesh + the box's exact fast diagonalisation
-void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega) {
+// inert: the rows of z left 0 (hanging rows; for the Jacobian also the prescribed ones).  coarse_fixed_ends: z = omega D^-1 g + P (J_H)_ff^-1 P^T g, the coarse box's
+// table set without its prescribed faces' end nodes - whatever P^T g holds on those coarse rows, the coarse correction is exactly 0 there
+void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, bool coarse_fixed_ends) {
   Timed tm(c, "precondition_p_two_level");
   auto &T = c->two_level.pressure; poro_ctx *H = c->two_level.box; hipStream_t s = c->stream;
-  build_fdm_p(H);
+  if (coarse_fixed_ends) build_fdm_pj(H); else build_fdm_p(H);
   if (!H->wz_p.p) H->wz_p.alloc(H->n_p);
   double *rc = H->wg_p.p, *zc = H->wz_p.p;
   la_nodal_interp(s, T.pt_ptr.p, T.pt_col.p, T.pt_w.p, T.n_coarse, 1, g, rc, T.lanes_t);
   if (c->comm.multi()) allreduce_sum_vec(c, rc, T.n_coarse, "two_level_coarse_allreduce");      // partitioned: every rank restricted its owned rows; all hold P^T g after the sum
   const double kk[3] = {kappa, kappa, kappa};
-  fdm_precondition_p(H, a, kk, rc, zc);
-  la_two_level_combine(s, T.p_ptr.p, T.p_col.p, T.p_w.p, T.n_fine, 1, zc, g, dinv, (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr, omega, z, T.lanes);
+  fdm_precondition_p(H, a, kk, rc, zc, coarse_fixed_ends);
+  la_two_level_combine(s, T.p_ptr.p, T.p_col.p, T.p_w.p, T.n_fine, 1, zc, g, dinv, inert, omega, z, T.lanes);
 }
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega) {
   Timed tm(c, "precondition_u_two_level");

@@ -83,7 +83,11 @@ void colour_cells(int64_t n_cells, int64_t n_vertices, int nv, const int32_t *cv
 }
 
 // poro_constraints -> device lists (+ transposed lists for the gather form of C^T y); `fixed` = byte mask of the Dirichlet dofs of the same space (or null)
-void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, const std::vector<uint8_t> *fixed, const char *what) {
+// fixed_value (pressure space with prescribed pressures; null elsewhere): the lists are analysed together instead of being kept apart.  A master may be prescribed
+// (the normal case next to a drained face: the row reads the prescribed value when p is distributed, and 0 when an update is).  A dof may be in both lists only if ALL
+// its masters are prescribed and its value is what they give, sum w * value(master) + inhomogeneity, to 1e-12 of the largest prescribed magnitude (1e-12 absolute if
+// that is 0); it stays in the device list - its row then reproduces its own value, and 0 for an update.  Anything else is refused with the dof named
+void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, const std::vector<uint8_t> *fixed, const char *what, const std::vector<double> *fixed_value = nullptr) {
   C.n = h.n;
   std::vector<uint8_t> inert(n_dofs, 0);
   if (fixed) inert = *fixed;
@@ -95,20 +99,31 @@ void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, c
     const int32_t dof = h.dof[i];
     if (dof < 0 || dof >= n_dofs) throw Error(std::string(what) + ": constrained dof out of range");
     if (hanging[dof]) throw Error(std::string(what) + ": dof constrained twice");
-    if (fixed && (*fixed)[dof]) throw Error(std::string(what) + ": dof is both in the Dirichlet list and in the constraint list");
+    if (fixed && !fixed_value && (*fixed)[dof]) throw Error(std::string(what) + ": dof is both in the Dirichlet list and in the constraint list");
     hanging[dof] = 1;
   }
   const int64_t nm = h.ptr[h.n];
   if (h.ptr[0] != 0 || nm < 0 || (nm && (!h.master || !h.weight))) throw Error(std::string(what) + ": bad constraint offsets");
+  double fixed_tol = 0;
+  if (fixed_value) { for (int64_t i = 0; i < n_dofs; ++i) if ((*fixed)[i]) fixed_tol = std::max(fixed_tol, std::fabs((*fixed_value)[i])); fixed_tol = fixed_tol > 0 ? 1e-12 * fixed_tol : 1e-12; }
   std::map<int32_t, std::vector<std::pair<int32_t, double>>> tr;
   for (int64_t i = 0; i < h.n; ++i) {
     if (h.ptr[i + 1] < h.ptr[i]) throw Error(std::string(what) + ": constraint offsets not ascending");
+    const bool both = fixed_value && (*fixed)[h.dof[i]];
+    double from_masters = h.inhomogeneity[i];
     for (int64_t k = h.ptr[i]; k < h.ptr[i + 1]; ++k) {
       const int32_t m = h.master[k];
       if (m < 0 || m >= n_dofs) throw Error(std::string(what) + ": master dof out of range");
-      if (hanging[m] || (fixed && (*fixed)[m])) throw Error(std::string(what) + ": constraints are not closed (a master is itself constrained)");
+      if (hanging[m] || (fixed && !fixed_value && (*fixed)[m])) throw Error(std::string(what) + ": constraints are not closed (a master is itself constrained)");
+      if (both) {
+        if (!(*fixed)[m]) throw Error(std::string(what) + ": dof " + std::to_string(h.dof[i]) + " is both hanging and prescribed, but its master " + std::to_string(m) + " is not prescribed");
+        from_masters += h.weight[k] * (*fixed_value)[m];
+      }
       tr[m].emplace_back(h.dof[i], h.weight[k]);
     }
+    if (both && !(std::fabs((*fixed_value)[h.dof[i]] - from_masters) <= fixed_tol))
+      throw Error(std::string(what) + ": dof " + std::to_string(h.dof[i]) + " is both hanging and prescribed, but its prescribed value " + std::to_string((*fixed_value)[h.dof[i]]) +
+                  " is not what its (prescribed) masters give, " + std::to_string(from_masters));
     if (h.inhomogeneity[i] != 0.0) C.any_inhom = true;
   }
   C.dof.upload(h.dof, h.n); C.ptr.upload(h.ptr, h.n + 1); C.inhom.upload(h.inhomogeneity, h.n);
@@ -119,6 +134,7 @@ void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, c
   if (C.n_masters) { C.t_master.upload(tm); C.t_dof.upload(td); C.t_ptr.upload(tp); C.t_weight.upload(tw); }
   for (int64_t i = 0; i < n_dofs; ++i) inert[i] = inert[i] | hanging[i];
   C.inert.upload(inert);
+  if (fixed_value) C.hanging.upload(hanging);
 }
 
 // Is the prescribed-pressure set exactly a union of whole faces (direction, side) of the line structure?  Then the free block of a M + kappa K is the Kronecker sum of
@@ -267,7 +283,22 @@ void setup(poro_ctx *c, const poro_desc *d) {
       static const bool no_affine = std::getenv("PORO_MFG_NO_AFFINE") != nullptr;
       if (affine && !no_affine) c->cell_geo.upload(geo);
     } }
-  { std::vector<int32_t> cells; colour_cells(c->n_cells, d->n_vertices, c->nv, d->cell_vertices, cells, c->color_off); c->color_cells.upload(cells); }
+  { std::vector<int32_t> cells; colour_cells(c->n_cells, d->n_vertices, c->nv, d->cell_vertices, cells, c->color_off); c->color_cells.upload(cells);
+    // the boundary faces by (colour of their cell, local face number): faces of one group share no dof, so the traction load is assembled group by group without atomics
+    if (d->n_bfaces) {
+      const int nf = 2 * c->dim; const int ncol = (int)c->color_off.size() - 1;
+      std::vector<int> colour_of((size_t)c->n_cells, 0);
+      for (int k = 0; k < ncol; ++k) for (int64_t i = c->color_off[k]; i < c->color_off[k + 1]; ++i) colour_of[cells[i]] = k;
+      std::vector<int64_t> off((size_t)ncol * nf + 1, 0);
+      for (int64_t b = 0; b < d->n_bfaces; ++b) {
+        if (d->bface_cell[b] < 0 || d->bface_cell[b] >= c->n_cells || d->bface_local[b] < 0 || d->bface_local[b] >= nf) throw Error("bface_cell / bface_local out of range");
+        off[(size_t)colour_of[d->bface_cell[b]] * nf + d->bface_local[b] + 1]++;
+      }
+      for (size_t g = 0; g + 1 < off.size(); ++g) off[g + 1] += off[g];
+      std::vector<int32_t> order((size_t)d->n_bfaces); std::vector<int64_t> pos(off.begin(), off.end() - 1);
+      for (int64_t b = 0; b < d->n_bfaces; ++b) order[pos[(size_t)colour_of[d->bface_cell[b]] * nf + d->bface_local[b]]++] = (int32_t)b;
+      c->bface_order.upload(order); c->bface_group_off = std::move(off);
+    } }
   { std::vector<uint8_t> m(c->n_u, 0); std::vector<double> v(c->n_u, 0.0);
     for (int64_t i = 0; i < d->n_dirichlet; ++i) { const int32_t dof = d->dirichlet_dof[i]; if (dof < 0 || dof >= c->n_u) throw Error("dirichlet_dof out of range"); m[dof] = 1; v[dof] = d->dirichlet_value[i]; }
     c->dir_mask.upload(m); c->dir_val.upload(v);
@@ -283,8 +314,8 @@ void setup(poro_ctx *c, const poro_desc *d) {
       for (int64_t i = 0; i < d->n_dirichlet_p; ++i) { const int32_t dof = d->dirichlet_dof_p[i]; if (dof < 0 || dof >= c->n_p) throw Error("dirichlet_dof_p out of range"); pm[dof] = 1; pv[dof] = d->dirichlet_value_p[i]; }
       c->n_pdir = d->n_dirichlet_p;
       if (c->n_pdir) { if (c->comm.part.n_ranks > 1) throw Error("prescribed pressures are implemented for one rank (there: PORO_PREC_JACOBI for any set, PORO_PREC_FDM where they cover whole faces of a uniform box or tensor-product grid)"); c->pdir_mask.upload(pm); c->pdir_val.upload(pv); }
-      upload_constraints(c->cons_p, d->cons_p, c->n_p, &pm, "cons_p");
-      if (c->cons_p.n && c->n_pdir) throw Error("prescribed pressures together with hanging pressure nodes are not supported (prescribed pressures: meshes without constraint lists in the pressure space, one rank)");
+      // both lists at once (a drained face on a locally refined mesh): analysed together, see upload_constraints.  cons_p.inert is then the union of the two sets
+      upload_constraints(c->cons_p, d->cons_p, c->n_p, &pm, "cons_p", c->n_pdir ? &pv : nullptr);
       analyse_pdir_faces(c, pm); }
     { std::vector<uint8_t> nm((size_t)(c->n_u / c->dim), 0); for (int64_t i = 0; i < d->n_dirichlet; ++i) nm[d->dirichlet_dof[i] / c->dim] |= (uint8_t)(1u << (d->dirichlet_dof[i] % c->dim)); c->node_mask.upload(nm); c->h_node_mask = std::move(nm); }
     if (d->n_dirichlet) c->dir_dofs.upload(d->dirichlet_dof, d->n_dirichlet);

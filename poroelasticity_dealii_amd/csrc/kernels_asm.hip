@@ -217,19 +217,26 @@ k_asm_u_rhs(AsmArgs a, const int32_t *__restrict__ cells, const double *__restri
   }
 }
 
-// ---- Neumann faces: b_i += phi_i t_l n_c JxW_f (:249-277); few faces, constant in time -> float atomics are fine ----
-template <int DIM> __global__ void k_asm_u_neumann(AsmArgs a, int64_t n_bf, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id, int n_neu,
-                                                   const int32_t *label, const int32_t *comp, const double *value, double *rhs) {
+// ---- Neumann faces: b_i += phi_i t_l n_c JxW_f (:249-277); few faces, constant in time ----
+// One lane per boundary face of ONE group (cells of one colour, one local face number: `order` lists the group's faces), the conditions in list order inside the
+// lane.  Faces of a group share no dof (cells of a colour share none, a cell has one face per local number), so the adds need no atomics and the groups, launched one
+// after the other, sum every dof in a fixed order: the load is bitwise the same in every context of a mesh.  (It used to be one launch with fp64 atomic adds; with
+// up to four faces meeting in a dof in 3D the sum then differed in the last bit from context to context, which a laterally symmetric adaptive run turns into
+// different marked cells.)
+template <int DIM> __global__ void k_asm_u_neumann(AsmArgs a, int64_t n_group, const int32_t *__restrict__ order, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id,
+                                                   int n_neu, const int32_t *label, const int32_t *comp, const double *value, double *rhs) {
   const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= n_bf * n_neu) return;
-  const int64_t bf = item / n_neu; const int l = (int)(item % n_neu);
-  if (bf_id[bf] != label[l]) return;
+  if (item >= n_group) return;
+  const int64_t bf = order[item];
   constexpr int NV = 1 << DIM;
   const int64_t cell = bf_cell[bf];
-  const int f = bf_local[bf], nd = f / 2, side = f % 2, ci = comp[l];
+  const int f = bf_local[bf], nd = f / 2, side = f % 2;
   double X[NV * DIM];
   for (int i = 0; i < NV * DIM; ++i) X[i] = a.cell_X[cell * NV * DIM + i];
   const int nqf = a.fe.nq_f, ns = a.ns_u, dpc = a.dpc_u;
+  for (int l = 0; l < n_neu; ++l) {
+  if (bf_id[bf] != label[l]) continue;
+  const int ci = comp[l];
   for (int q = 0; q < nqf; ++q) {
     const double *dN = a.fe.dq1_qf + (size_t)(f * nqf + q) * NV * DIM;
     double J[DIM][DIM];
@@ -242,8 +249,9 @@ template <int DIM> __global__ void k_asm_u_neumann(AsmArgs a, int64_t n_bf, cons
     const double neumann_value = value[l] * (sgn * cof[ci] / len), jxwf = len * a.fe.w_qf[q];
     for (int s = 0; s < ns; ++s) {
       const double phi = a.fe.u_qf[(size_t)(f * nqf + q) * ns + s];
-      if (phi != 0.0) atomicAdd(&rhs[a.cell_dofs_u[cell * dpc + s * DIM + ci]], phi * neumann_value * jxwf);
+      if (phi != 0.0) rhs[a.cell_dofs_u[cell * dpc + s * DIM + ci]] += phi * neumann_value * jxwf;
     }
+  }
   }
 }
 
@@ -386,13 +394,16 @@ void asm_u_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n,
   if (!n) return;
   PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL(k_asm_u_rhs<2>, (unsigned)n, 64, 0, s, a, cells, p, rhs), hipLaunchKernelGGL(k_asm_u_rhs<3>, (unsigned)n, 64, 0, s, a, cells, p, rhs));
 }
-void asm_u_neumann(hipStream_t s, const AsmArgs &a, int64_t n_bf, const int32_t *bc, const int32_t *bl, const int32_t *bi, int n_neu, const int32_t *label,
-                   const int32_t *comp, const double *value, double *rhs) {
-  const int64_t items = n_bf * n_neu;
-  if (!items) return;
-  const unsigned grid = (unsigned)((items + 63) / 64);
-  PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL(k_asm_u_neumann<2>, grid, 64, 0, s, a, n_bf, bc, bl, bi, n_neu, label, comp, value, rhs),
-                    hipLaunchKernelGGL(k_asm_u_neumann<3>, grid, 64, 0, s, a, n_bf, bc, bl, bi, n_neu, label, comp, value, rhs));
+void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const std::vector<int64_t> &group_off, const int32_t *bc, const int32_t *bl, const int32_t *bi, int n_neu,
+                   const int32_t *label, const int32_t *comp, const double *value, double *rhs) {
+  if (!n_neu) return;
+  for (size_t g = 0; g + 1 < group_off.size(); ++g) {
+    const int64_t n = group_off[g + 1] - group_off[g];
+    if (!n) continue;
+    const unsigned grid = (unsigned)((n + 63) / 64); const int32_t *o = order + group_off[g];
+    PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL(k_asm_u_neumann<2>, grid, 64, 0, s, a, n, o, bc, bl, bi, n_neu, label, comp, value, rhs),
+                      hipLaunchKernelGGL(k_asm_u_neumann<3>, grid, 64, 0, s, a, n, o, bc, bl, bi, n_neu, label, comp, value, rhs));
+  }
 }
 void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const int64_t *rp, const int32_t *col, double *M, double *K, double *src) {
   if (!n) return;

@@ -362,6 +362,12 @@ void poro_host_runner_work(void *r, int64_t *work) {
                              work[6] = w.proj_rhs; work[7] = w.cg_u; work[8] = w.cg_p; work[9] = w.cg_proj; work[10] = (int64_t)(w.seconds_solve_u * 1e6); };
   if (R->dim == 2) fill(R->p2->work); else fill(R->p3->work);
 }
+// the preconditioners the driver chose for the current context (initialize, and again after every adapt): out[3] = displacement, pressure, projection (PORO_PREC_*)
+void poro_host_runner_preconditioners(void *r, int32_t *out) {
+  auto *R = static_cast<HostRunner *>(r);
+  auto fill = [&](auto &p) { out[0] = p.displacement_solver.control.preconditioner; out[1] = p.pressure_solver.control.preconditioner; out[2] = p.strain_projector.control.preconditioner; };
+  if (R->dim == 2) fill(*R->p2); else fill(*R->p3);
+}
 void poro_host_runner_free(void *r) { delete static_cast<HostRunner *>(r); }
 
 }  // extern "C"

@@ -430,6 +430,7 @@ struct ProblemData {
   std::vector<double> tensor_grid[3]; // vertex planes per direction of a tensor-product grid without the box tag (graded boxes)
   // locally refined boxes: the underlying uniform box as a problem of its own + the interpolation from it (poro_coarse_space)
   std::unique_ptr<ProblemData> coarse; std::vector<int64_t> prol_ptr; std::vector<int32_t> prol_node; std::vector<double> prol_w;
+  std::map<int, int> coarse_side_of_id; bool coarse_is_auxiliary = false;   // auxiliary box (attach_auxiliary_box): the mesh's boundary ids -> the box's own
   std::vector<int64_t> prol_ptr_p; std::vector<int32_t> prol_node_p; std::vector<double> prol_w_p;
   int64_t n_dofs_p_global = 0;        // pieces of a general partition: the global problem's pressure dof count (0: this problem is not a piece)
   // one-level refined boxes (block or mask form) keep what mesh adaptation needs, see RefinedBox; refined_box tells whether this problem is one
@@ -503,9 +504,19 @@ struct ProblemData {
     d.cons_u = cons_u.c_view(); d.cons_p = cons_p.c_view();
     set_pressure_bc();
   }
+  // ids no face of the mesh carries go to ids the auxiliary box does not have
+  void translate_to_coarse(std::vector<int32_t> &labels) const { for (auto &l : labels) { auto it = coarse_side_of_id.find(l); l = it == coarse_side_of_id.end() ? -1 - l : it->second; } }
   void set_pressure_bc() {
     if (!dirichlet_given) make_dirichlet_p(mesh, dofs, bc, dirichlet_dof_p, dirichlet_value_p);
     d.n_dirichlet_p = (int64_t)dirichlet_dof_p.size(); d.dirichlet_dof_p = dirichlet_dof_p.data(); d.dirichlet_value_p = dirichlet_value_p.data();
+    // the coarse space of the two-level preconditioner carries the same condition (a refined box's coarse problem has the mesh's own labels, an auxiliary box its own
+    // ids): a coarse problem built before the condition was set learns of it here.  Pieces of a partition: their copy of the coarse problem has its lists given
+    // (dirichlet_given, copy_box_problem) and is left alone; partition_problem copies the translation all the same
+    if (coarse && !coarse->dirichlet_given) {
+      coarse->bc.pressure_labels = bc.pressure_labels; coarse->bc.pressure_values = bc.pressure_values;
+      if (coarse_is_auxiliary) translate_to_coarse(coarse->bc.pressure_labels);
+      coarse->set_pressure_bc();
+    }
   }
 };
 
@@ -561,7 +572,8 @@ inline bool attach_auxiliary_box(ProblemData &P, int k_u) {
     auto it = side_of_id.find(m.bface_id[f]);
     if (it == side_of_id.end()) side_of_id[m.bface_id[f]] = side; else if (it->second != side) return false;
   }
-  auto translate = [&](std::vector<int32_t> &labels) { for (auto &l : labels) { auto it = side_of_id.find(l); l = it == side_of_id.end() ? -1 - l : it->second; } };   // (ids no edge carries: to ids the box does not have)
+  P.coarse_side_of_id = side_of_id; P.coarse_is_auxiliary = true;
+  auto translate = [&](std::vector<int32_t> &labels) { P.translate_to_coarse(labels); };   // (ids no edge carries: to ids the box does not have)
   // resolution of the auxiliary box: as many cells as the mesh, divided by coarsen^2 (the spaces need not be nested; a coarser box makes the coarse solve cheaper
   // - its transforms cost O(n^3) per application - at the price of a few CG iterations; PORO_AUX_BOX_COARSEN overrides the default)
   // measured on the bundled grid (profiles/r03_gmsh_step.json): half the resolution costs 5 of 51 CG iterations per step and saves 12 % of the step at 102 400 cells;
@@ -881,6 +893,7 @@ inline void partition_problem(const ProblemData &G, int rank, int n_ranks, Probl
   if (with_coarse) {
     // the whole box on every piece + the global interpolation rows of the local nodes / vertices
     L.coarse.reset(new ProblemData()); copy_box_problem(*G.coarse, *L.coarse);
+    L.coarse_side_of_id = G.coarse_side_of_id; L.coarse_is_auxiliary = G.coarse_is_auxiliary;
     auto rows = [](const std::vector<int32_t> &l2g, int stride, const std::vector<int64_t> &gp, const std::vector<int32_t> &gn, const std::vector<double> &gw,
                    std::vector<int64_t> &p, std::vector<int32_t> &nd, std::vector<double> &w) {
       p.assign(1, 0);

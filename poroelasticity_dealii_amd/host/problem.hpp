@@ -5,6 +5,7 @@
 // device-resident vectors; nothing here computes on the CPU.
 #pragma once
 #include <cmath>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -353,7 +354,10 @@ template <int dim> class PoroElasticProblem {
   int time_step(const RunControls &rc, double *trace, int max_rows) {
     int rows = 0;
     time_step_number++;                                    // :329
-    if (rc.refine_every > 0 && time_step_number % rc.refine_every == 0) refine_mesh(rc);   // :333-340
+    if (rc.refine_every > 0 && time_step_number % rc.refine_every == 0) {                  // :333-340
+      const std::pair<int64_t, int64_t> cells = refine_mesh(rc);
+      if (on_adapt) on_adapt(time_step_number, cells.first, cells.second);
+    }
     pressure_solver.old_solution = pressure_solver.solution;   // :342
     if (rc.incremental_strain && time_step_number > 1) initial_volumetric_strain = volumetric_strain;
     double pressure_error = rc.pressure_tol * 2; int fss_iteration = 0;   // :345-346
@@ -397,6 +401,7 @@ template <int dim> class PoroElasticProblem {
     return rows;
   }
 
+  std::function<void(int step, int64_t cells_before, int64_t cells_after)> on_adapt;   // called after every refine_mesh of time_step (the driver's log); unset: nothing
   solvers::PoroElasticPressureSolver<dim>     pressure_solver;     // :77
   solvers::PoroElasticDisplacementSolver<dim> displacement_solver; // :78
   projection::StrainProjector<dim>            strain_projector;    // :79

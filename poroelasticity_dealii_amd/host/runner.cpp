@@ -86,9 +86,15 @@ int main(int argc, char **argv) {
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
     static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
     auto go = [&](auto &prob) {
-      rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
       if (!pressure_labels.empty())        // (only with the extension, so the reference's log stays as it is)
-        std::cout << "prescribed pressures: " << P.d.n_dirichlet_p << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner]
+        prob.on_adapt = [&](int step, int64_t before, int64_t after) {     // the choice is made again on every adapted mesh
+          std::cout << "adapted before step " << step << ": " << before << " -> " << after << " cells; prescribed pressures: " << prob.problem()->d.n_dirichlet_p
+                    << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << ", projection preconditioner: "
+                    << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
+        };
+      rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
+      if (!pressure_labels.empty())
+        std::cout << "prescribed pressures: " << prob.problem()->d.n_dirichlet_p << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner]
                   << ", projection preconditioner: " << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
     };
     if (data.dim == 2) { PoroElasticProblem<2> prob(P, device, op); go(prob); }
