@@ -72,12 +72,16 @@ struct FdmScalar { int dim = 0; FdmDir dir[3]; bool built = false; };
 struct FdmScale { const double *lam[3]; int n[3]; double a, k[3]; int64_t ncol, col0, col_total; };   // divide by a + k0 lam0[i] + k1 lam1[j] + k2 lam2[k] at grid node (i, j, k); ncol > 0: column-distributed layout
 // partitioned (slab) form: the transforms of the leading directions are local, the last direction runs on columns gathered by an all-to-all
 struct FdmWindow { int n_planes; int64_t ncols_valid, grid_col0, grid_plane0; };   // one peer's share of a window copy (fdm_window_batch)
-struct FdmDist {
-  bool built = false; int n_ranks = 1, rank = 0;
-  std::vector<int> layers, off;                 // cell layers and first global plane of every rank
+// what every rank of a slab partition knows about all slabs (ctx_prec.hip: slab_layout), in node planes of the space it was filled for (Q1, or the displacement space)
+struct SlabLayout {
+  int n_ranks = 1, rank = 0;
+  std::vector<int> layers, off;                 // cell layers and first global node plane of every rank
   int ng = 0;                                   // global node planes of the last direction
   int64_t ncol_total = 0, C = 0;                // columns (nodes of one plane) and columns per rank
   int max_own = 0, max_nl = 0;                  // padded plane counts of the two exchanges
+};
+struct FdmDist : SlabLayout {
+  bool built = false;
   FdmDir last;                                  // global eigenvectors of the last direction
   DevBuf<double> sendbuf, recvbuf, tz1, tz2; std::vector<double> hsend, hrecv;
   DevBuf<FdmWindow> windows;                    // [4][n_ranks]: the per-peer windows of the four copies around the two all-to-alls (one launch each)
@@ -86,11 +90,11 @@ struct FdmDist {
 // block fast diagonalisation of the displacement system (kernels_fdmu.hip): per (component, direction) the transform matrices S^T (fwd) and
 // S (bwd) in MFMA fragment order and the eigenvalues (inf marks removed modes); coef[c][d] = lambda + 2G (d == c) | G
 struct FdmuDir { int n = 0; bool reg_form = false, split = false, blk = false; int n_even = 0; int blk_kk[2] = {0, 0}, blk_nch[2] = {0, 0}, blk_mb[2] = {0, 0} /* [forward, backward] */; DevBuf<double> fwd, bwd, lam; };
-struct FdmU { int dim = 0; int nn[3] = {1, 1, 1}; double coef[3][3] = {}; FdmuDir dir[3][3]; FdmuDir last_global[3]; bool built = false, single = false;
+struct FdmU : SlabLayout {
+              int dim = 0; int nn[3] = {1, 1, 1}; double coef[3][3] = {}; FdmuDir dir[3][3]; FdmuDir last_global[3]; bool built = false, single = false;
               int fix[3][3][2] = {};
               // slab-partitioned form: node planes of the last direction are gathered per column group by an all-to-all (as FdmDist for the Q1 systems)
-              bool dist = false; int n_ranks = 1, rank = 0; std::vector<int> layers, off /* first global node plane of every rank */; int ng = 0; int64_t ncol_total = 0, C = 0;
-              int max_own = 0, max_nl = 0; DevBuf<double> sendbuf, recvbuf, tz1, tz2; };
+              bool dist = false; DevBuf<double> sendbuf, recvbuf, tz1, tz2; };
 // octant form of the block fast diagonalisation (kernels_fdmo.hip; 3D boxes, one rank, every direction mirror-symmetric for every component).
 // The even / odd butterflies of the three directions commute with everything inside the preconditioner, so they are hoisted out of it: the CG residual g and
 // the preconditioned residual z live as 8 octants per component, Q[c][o][kz][ky][kx] with o = 4 pz + 2 py + px (p = 0: even part e_k = v_k + v_k', 1: odd
@@ -132,6 +136,9 @@ struct FdmOct {
   struct ScalarTable { double a, kappa; DevBuf<double> t; };
   std::list<ScalarTable> scalar_tables;           // scalar form: a + kappa (lam_x + lam_y) per plane position, one table per (a, kappa) seen (pressure Jacobian, mass matrix)
 };
+// one table set of the scalar Q1 systems: the six-launch form (kernels_fdm.hip) and, where usable, the same tables for the three-launch transform kernel
+// (kernels_fdmo.hip: 3D boxes, lines of at most 80 vertices)
+struct FdmQ1 { FdmScalar nodal; FdmOct fused; };
 // dependency levels of the lower / upper triangle in natural row order (rows of one level can be swept concurrently)
 struct SsorLevels { DevBuf<int32_t> fwd_rows, bwd_rows; std::vector<int64_t> fwd_off, bwd_off; bool built = false; };
 struct CsrDev {
@@ -231,7 +238,7 @@ struct poro_ctx {
   poro::ConsDev cons_u, cons_p;
   poro::DevBuf<uint8_t> pdir_mask; poro::DevBuf<double> pdir_val; int64_t n_pdir = 0;   // extension: prescribed pressures
   // the prescribed set is exactly a union of whole faces (direction, side) of `lines` (face analysis at set-up): deleting those rows and columns leaves a Kronecker sum of
-  // 1D matrices without their end nodes, which the second table set below diagonalises
+  // 1D matrices without their end nodes, which the table set q1_fixed below diagonalises
   bool pdir_faces_ok = false; int pdir_face[3][2] = {{0, 0}, {0, 0}, {0, 0}};
   poro::DevBuf<int32_t> bface_cell, bface_local, bface_id, neu_label, neu_comp; poro::DevBuf<double> neu_val;
   poro::DevBuf<int32_t> bface_order; std::vector<int64_t> bface_group_off;   // boundary faces sorted by (colour of the cell, local face): the groups of asm_u_neumann
@@ -251,15 +258,14 @@ struct poro_ctx {
   int box_asm = 0 /* 0 off, 1 unchecked, 2 checked against the per-cell kernels */; poro::BoxCoupling box_cpl{};
   poro::DevBuf<double> ilu_u, ilu_J, ilu_M; bool ilu_u_valid = false, ilu_J_valid = false, ilu_M_valid = false;   // ILU(0) factors on the CSR patterns
   poro::DevBuf<double> wz_p;   // z = P^-1 g of an explicit preconditioner (pressure-sized systems)
-  poro::FdmScalar fdm_p; poro::FdmDist fdm_dist; poro::DevBuf<double> fdm_t1, fdm_t2;   // fast diagonalisation of the Q1 box operators
+  // fast diagonalisation of the Q1 box operators, two table sets (ctx_prec.hip: build_fdm_q1).  q1_free: a M + kappa K on the whole grid - the projection mass matrix,
+  // the pressure Jacobian without prescribed rows; slab partitions (fdm_dist) use this set alone.  q1_fixed: the pressure Jacobian with the prescribed faces' end nodes
+  // removed (built only when n_pdir != 0, one rank).  fdm_t1 / fdm_t2 are shared
+  poro::FdmQ1 q1_free, q1_fixed; poro::FdmDist fdm_dist; poro::DevBuf<double> fdm_t1, fdm_t2;
   double cheb_lmax = 0;   // estimate of lambda_max(D^-1 A_u) (Lanczos at matrix build; 0 = not yet computed)
   double cheb_ratio_default = 0;   // default interval ratio of the Chebyshev preconditioner, from the GLOBAL mesh size (0 = not yet computed)
   poro::DevBuf<double> cheb_z, cheb_t;
   poro::FdmOct fdm_oct;
-  poro::FdmOct fdm_p_fused;          // the scalar Q1 systems through the same transform kernel (3D boxes, lines of <= 128 vertices)
-  // second table set of the Q1 systems: the pressure Jacobian with the prescribed faces' end nodes removed (built only when n_pdir != 0; fdm_p / fdm_p_fused stay the
-  // projection mass matrix's, which has no fixed ends).  fdm_t1 / fdm_t2 are shared
-  poro::FdmScalar fdm_pj; poro::FdmOct fdm_pj_fused;
   // two-level preconditioner (poro_desc.coarse): the underlying uniform box as a context of its own (same device and stream) + the node-wise interpolation P and its transpose
   struct Interp { int64_t n_fine = 0, n_coarse = 0; int lanes = 1, lanes_t = 1;   /* lanes per row of the interpolation kernels, from the mean row length */ poro::DevBuf<int64_t> p_ptr, pt_ptr; poro::DevBuf<int32_t> p_col, pt_col; poro::DevBuf<double> p_w, pt_w; };   // P (rows = fine) and its transpose as CSR
   struct TwoLevel : Interp { poro_ctx *box = nullptr; Interp pressure; bool pdir_nested = false; /* prescribed pressures: every fine dof on a prescribed coarse dof is prescribed */ } two_level;   // (the base part: displacement nodes; .pressure: pressure dofs, optional)

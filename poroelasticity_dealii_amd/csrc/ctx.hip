@@ -320,30 +320,6 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
   return rc;   // (stream-ordered: pcg() returned after the finishing iteration, `distribute` follows in the stream)
 }
 
-// The three transform dispatches of the octant form.  A sampled call times them one by one (per-kernel roofline of the bench): the sampling runs on
-// fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
-// gz_part != null: pass 2 also leaves the partial sums of g . z there (returns true: no separate dot kernel)
-// scratch == null: the passes work on z itself (fp64 transforms only)
-bool fdm_u_octant_passes(poro_ctx *c, const FdmOct &oct, const double *g, double *z, double *scratch, const PcgScalars *gate, double *gz_part) {
-  Timed tm(c, "precondition_u_fdm");
-  const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
-  if (!begin_sampled_dispatch(c, names[0])) {
-    fdmo_apply(c->stream, oct, g, z, scratch, gate, nullptr, gz_part, c->fdm_precision);
-    return gz_part != nullptr;
-  }
-  c->timers[names[1]].enqueued++;
-  c->timers[names[2]].enqueued++;
-  hipEvent_t ev[6];
-  for (auto &e : ev) e = event_get(c);
-  fdmo_apply(c->stream, oct, g, z, scratch, gate, ev, gz_part, c->fdm_precision);
-  for (int k = 0; k < 3; ++k) {
-    Timer &t = c->timers[names[k]];
-    t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
-    t.launches++;
-  }
-  return gz_part != nullptr;
-}
-
 // z = blockdiag(A_cc)^-1 g by fast diagonalisation: the same device-controlled SolverCG recurrence with an explicit preconditioner vector
 int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
   build_fdm_u(c);
@@ -360,21 +336,15 @@ int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts,
   if (shared) c->timers["fdm_u_shared_buffers"].enqueued++;
   double *const scratch = shared && c->fdm_precision != PORO_FDM_FP32 ? nullptr : c->fdm_oct.t.p;
   const ApplyFn P = [&](const double *g, double *z, double *in_iteration) {
-    // g, z in octant form: three contiguous sweeps; inside the iteration the launches are gated on the device-side "solve finished" flag (before
+    // g, z in the layout of the form that is built (octants: three contiguous sweeps); inside the iteration the launches are gated on the device-side "solve finished" flag (before
     // pcg_scalars_start it still holds the previous solve's state)
     const PcgScalars *gate = in_iteration ? c->scal.p : nullptr;
     if (!oct) {
       fdm_precondition_u(c, g, z);
-    } else if (oct->slab.on) {
-      fdm_precondition_u_slab(c, g, z, gate);
-    } else if (oct->planar) {
-      Timed tm(c, "precondition_u_fdm");
-      fdmo_apply_planar(c->stream, *oct, g, z, gate);
-    } else {
-      // inside the iteration pass 2 leaves g . z (in oct->gz_part, which k_fdmo_update_d reads); the first application of a solve keeps k_fdmo_first_direction's dot
-      return fdm_u_octant_passes(c, *oct, g, z, scratch, gate, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
+      return false;
     }
-    return false;
+    // octant form: inside the iteration pass 2 leaves g . z (in oct->gz_part, which k_fdmo_update_d reads); the first application of a solve keeps k_fdmo_first_direction's dot
+    return fdm_precondition_u_form(c, g, z, gate, c->fdm_precision, scratch, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
   };
   DiagVec dz = diag_u(c, c->dir_mask.p, false);
   dz.z = c->wz_u.p;
@@ -426,8 +396,8 @@ struct Q1System {
   const uint8_t *inert_two_level;     // the inert mask handed to PCG per branch; null selects the kernel form without a mask
   const uint8_t *inert_jacobi;
   const uint8_t *inert_fdm = nullptr; // FDM: none, except with prescribed pressures on whole faces (the free-row system: residual norm and g . z see free rows only)
-  bool fixed_ends = false;            // FDM: the table set without the prescribed faces' end nodes (c->fdm_pj) instead of c->fdm_p
-  bool coarse_fixed_ends = false;     // two-level: the same table set of the coarse box, (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
+  Q1Set set = Q1Set::free_ends;       // FDM: the table set; fixed_ends = without the prescribed faces' end nodes
+  Q1Set coarse_set = Q1Set::free_ends; // two-level: the coarse box's table set; fixed_ends = (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
   bool distribute_inhom = true;       // constraints.distribute with the inhomogeneities; an UPDATE of a vector that already carries them (dp beside prescribed pressures) is distributed without
 };
 
@@ -440,21 +410,21 @@ bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE &&
 // Direct solve of n <= 3 systems that share (a, kappa) where the fast diagonalisation is the exact inverse (uniform box, slab partitions included: the
 // distributed form is the same inverse): x_e = (a M + kappa K)^-1 b_e, then the residuals are checked against the reference's stopping rule with one poll
 // for all norms.  info[e].iterations = 0 marks a directly solved system; returns whether every system met the rule (if not, x_e is a good start for CG).
-// y: scratch of n vectors.  batched: all right-hand sides in one set of launches (c->fdm_p_fused)
-// fixed_ends + mask (prescribed pressures on whole faces): x_e = J_ff^-1 b_e on the free rows and exactly 0 on the masked ones; the check leaves the masked rows out,
+// y: scratch of n vectors.  batched: all right-hand sides in one set of launches (c->q1_free.fused)
+// Q1Set::fixed_ends + mask (prescribed pressures on whole faces): x_e = J_ff^-1 b_e on the free rows and exactly 0 on the masked ones; the check leaves the masked rows out,
 // where (J x)_i is the coupling to the free neighbours and not part of the system
 bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *const *b, double *const *x, double *y_scratch, bool batched,
-                     const poro_solver_opts *opts, poro_solve_info *info, bool fixed_ends = false, const uint8_t *mask = nullptr) {
+                     const poro_solver_opts *opts, poro_solve_info *info, Q1Set set = Q1Set::free_ends, const uint8_t *mask = nullptr) {
   hipStream_t s = c->stream;
   const double *y[3];
   for (int e = 0; e < n; ++e) y[e] = y_scratch + (size_t)e * c->n_p;
   const auto t0 = std::chrono::steady_clock::now();
   if (batched) {
     Timed tm(c, "precondition_p_fdm");
-    fdmo_scalar_apply_many(s, c->fdm_p_fused, a, kappa, n, b, x);
+    fdmo_scalar_apply_many(s, c->q1_free.fused, a, kappa, n, b, x);
   } else {
     const double kk[3] = {kappa, kappa, kappa};
-    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e], fixed_ends);
+    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e], set);
   }
   for (int e = 0; e < n; ++e) {
     {
@@ -509,18 +479,18 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
   DiagVec dz;
   dz.full = q.dinv;
   if (opts->preconditioner == PORO_PREC_FDM) {
-    if (q.fixed_ends) build_fdm_pj(c); else build_fdm_p(c);
+    build_fdm_q1(c, q.set);
     const double kk[3] = {q.kappa, q.kappa, q.kappa};
     if (!c->wz_p.p) c->wz_p.alloc(n);
     if (direct_first) {
       poro_solve_info direct;
-      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct, q.fixed_ends, q.inert_fdm)) {
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct, q.set, q.inert_fdm)) {
         if (info) *info = direct;
         return 0;
       }
     }
     const ApplyFn P = [&](const double *gg, double *z, double *) {
-      fdm_precondition_p(c, q.a, kk, gg, z, q.fixed_ends);
+      fdm_precondition_p(c, q.a, kk, gg, z, q.set);
       return false;
     };
     dz.z = c->wz_p.p;
@@ -532,7 +502,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     if (!c->wz_p.p) c->wz_p.alloc(n);
     const double om = opts->omega > 0 ? opts->omega : 1.0;
     const ApplyFn P = [&](const double *gg, double *z, double *) {
-      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om, q.inert_two_level, q.coarse_fixed_ends);
+      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om, q.inert_two_level, q.coarse_set);
       return false;
     };
     dz.z = c->wz_p.p;
@@ -864,41 +834,20 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
   });
 }
 
-int poro_supports_preconditioner(poro_ctx *c, int32_t which_system, int32_t prec) {
-  if (!c) return 0;
-  if (prec == PORO_PREC_NONE || prec == PORO_PREC_JACOBI) return 1;
-  // (pressure Jacobian with prescribed rows: the coarse box must carry the condition as whole faces, see two_level_supported_pj; the projection has no such rows)
-  if (prec == PORO_PREC_TWO_LEVEL) return which_system == 0 ? two_level_supported(c) : (which_system == 1 && c->n_pdir) ? two_level_supported_pj(c) : two_level_supported_p(c);
-  if (which_system == 0 && c->cons_u.n) return prec == PORO_PREC_CHEBYSHEV;      // condensed operators exist at operator level only: Jacobi, the polynomial built on it, the two-level form above
-  if (which_system == 2) {                                                        // the projection's mass matrix has no prescribed rows
-    if (c->cons_p.n) return 0;
-    if (prec == PORO_PREC_SSOR || prec == PORO_PREC_ILU0) return !c->comm.multi();
-    return prec == PORO_PREC_FDM ? fdm_p_supported(c) : 0;
-  }
-  if (which_system == 1 && c->n_pdir && !c->cons_p.n) return prec == PORO_PREC_FDM && fdm_pj_supported(c);   // prescribed pressures: whole faces of a box / tensor grid on one rank
-  if (which_system == 1 && (c->cons_p.n || c->n_pdir)) return 0;
-  if (prec == PORO_PREC_SSOR || prec == PORO_PREC_ILU0) return !c->comm.multi() && (which_system == 1 || c->operator_mode == PORO_OP_CSR);
-  if (prec == PORO_PREC_CHEBYSHEV) return which_system == 0;
-  if (prec == PORO_PREC_FDM && which_system == 1) return fdm_p_supported(c);
-  if (prec == PORO_PREC_FDM) { analyse_fdm_u(c); return c->fdm_u_state == 1; }
-  return 0;
-}
+int poro_supports_preconditioner(poro_ctx *c, int32_t which_system, int32_t prec) { return c && !prec_refusal(c, which_system, prec); }
 int poro_disp_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     if (!c->matrix_built) throw Error("disp_solve before disp_assemble_system");
     const int prec = opts->preconditioner;
-    if (c->cons_u.n && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && prec != PORO_PREC_CHEBYSHEV && prec != PORO_PREC_TWO_LEVEL)
-      throw Error("meshes with constraint lists: PORO_PREC_JACOBI / CHEBYSHEV / TWO_LEVEL / NONE only (the operator is condensed on the fly)");
+    if (const char *why = prec_refusal(c, 0, prec, true)) throw Error(why);
     if (prec == PORO_PREC_ILU0) {
-      if (c->operator_mode != PORO_OP_CSR) throw Error("PORO_PREC_ILU0 needs the assembled CSR operator");
       const int rc = pcg_ilu0(c, c->Au, c->Au_val.p, c->ilu_u, c->ilu_u_valid, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
       finish_u(c, false);
       PORO_HIP(hipStreamSynchronize(c->stream));
       return rc;
     }
     if (prec == PORO_PREC_SSOR) {
-      if (c->operator_mode != PORO_OP_CSR) throw Error("PORO_PREC_SSOR needs the assembled CSR operator");
       const int rc = pcg_ssor(c, c->Au, c->Au_val.p, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
       finish_u(c, false);
       PORO_HIP(hipStreamSynchronize(c->stream));
@@ -971,12 +920,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     PORO_HIP(hipSetDevice(c->device));
     if (c->jac_dt < 0) throw Error("pres_solve before pres_assemble_jacobian");
     const int prec = opts->preconditioner;
-    const bool fdm_fixed_ends = prec == PORO_PREC_FDM && fdm_pj_supported(c);      // prescribed pressures on whole faces of a box / tensor grid, one rank
-    const bool two_level_pdir = prec == PORO_PREC_TWO_LEVEL && c->n_pdir && two_level_supported_pj(c);   // the coarse box carries the prescribed set as whole faces
-    if ((c->cons_p.n || c->n_pdir) && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && !(prec == PORO_PREC_TWO_LEVEL && (!c->n_pdir || two_level_pdir)) && !fdm_fixed_ends)
-      throw Error("meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL; with prescribed pressures where the coarse box carries them as whole faces) only; prescribed pressures that cover whole faces of a uniform box or tensor-product grid on one rank: also PORO_PREC_FDM");
-    if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c))
-      throw Error("PORO_PREC_TWO_LEVEL (pressure): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)");
+    if (const char *why = prec_refusal(c, 1, prec, true)) throw Error(why);
+    const bool fdm_fixed_ends = prec == PORO_PREC_FDM && c->n_pdir;                 // prescribed pressures on whole faces of a box / tensor grid, one rank (the verdict has checked fdm_pj_supported)
+    const bool two_level_pdir = prec == PORO_PREC_TWO_LEVEL && c->n_pdir;           // the coarse box carries the prescribed set as whole faces (two_level_supported_pj)
     Q1System J;
     J.a = 1. / c->mat.biot_M / c->jac_dt;
     J.kappa = c->mat.k_over_mu;
@@ -988,14 +934,14 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     J.b = vec(c, PORO_VEC_RESIDUAL_P);
     J.hint = c->pcg_hint_p;
     J.inert_two_level = J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;     // hanging and prescribed rows alike (the union where both lists are present)
-    J.coarse_fixed_ends = two_level_pdir;
+    if (two_level_pdir) J.coarse_set = Q1Set::fixed_ends;
     if (c->n_pdir && (c->cons_p.n || two_level_pdir)) {
       J.distribute_inhom = false;
       la_mask_zero(c->stream, vec(c, PORO_VEC_RESIDUAL_P), c->pdir_mask.p, c->n_p);   // as on the fixed-ends path below: the prescribed rows are not part of the system, and the update is 0 there,
       la_mask_zero(c->stream, vec(c, PORO_VEC_DP), c->pdir_mask.p, c->n_p);           // so that a hanging row beside them (expanded homogeneously) gets its free masters' share alone
     }
     if (fdm_fixed_ends) {
-      J.fixed_ends = true;
+      J.set = Q1Set::fixed_ends;
       J.inert_fdm = c->pdir_mask.p;
       la_mask_zero(c->stream, vec(c, PORO_VEC_RESIDUAL_P), c->pdir_mask.p, c->n_p);   // R_f: poro_pres_assemble_residual leaves zeros there already; a caller's own right-hand side may not
       la_mask_zero(c->stream, vec(c, PORO_VEC_DP), c->pdir_mask.p, c->n_p);           // the update is 0 there: CG never touches an inert row of its start vector, the direct solve writes 0 itself
@@ -1057,8 +1003,7 @@ int poro_proj_solve(poro_ctx *c, int32_t entry, const poro_solver_opts *opts, po
     if (!c->projection_matrix_ready) throw Error("proj_solve before proj_assemble_matrix");
     if (entry < 0 || entry >= c->dim * (c->dim + 1) / 2) throw Error("rhs_entry out of range");
     const int prec = opts->preconditioner;
-    if (c->cons_p.n && prec != PORO_PREC_JACOBI && prec != PORO_PREC_NONE && prec != PORO_PREC_TWO_LEVEL) throw Error("meshes with hanging-node constraints: PORO_PREC_JACOBI / TWO_LEVEL / NONE only");
-    if (prec == PORO_PREC_TWO_LEVEL && !two_level_supported_p(c)) throw Error("PORO_PREC_TWO_LEVEL (projection): needs poro_desc.coarse with the pressure interpolation");
+    if (const char *why = prec_refusal(c, 2, prec, true)) throw Error(why);
     Q1System M;                                                                  // projection_matrix = mass_matrix (StrainProjector.h:104)
     M.a = 1.0;
     M.kappa = 0.0;
@@ -1085,9 +1030,11 @@ int poro_proj_solve_many(poro_ctx *c, const int32_t *entries, int32_t n_entries,
     if (!c->projection_matrix_ready) throw Error("proj_solve before proj_assemble_matrix");
     for (int e = 0; e < n_entries; ++e) if (entries[e] < 0 || entries[e] >= c->dim * (c->dim + 1) / 2) throw Error("rhs_entry out of range");
     static const bool iterative = std::getenv("PORO_PROJ_ITERATIVE") != nullptr;
-    if (iterative || opts->preconditioner != PORO_PREC_FDM || opts->stop_rule != PORO_STOP_RHS || c->cons_p.n || !q1_stencil(c) || n_entries < 1 || n_entries > 3 || !fdm_p_supported(c)) return 0;
-    build_fdm_p(c);
-    const bool batched = !c->comm.multi() && c->fdm_p_fused.built && !c->fdm_p_fused.slab.on;      // one rank, 3D, lines of <= 128 vertices: all right-hand sides in one set of launches
+    if (n_entries < 1) return 0;
+    if (const char *why = prec_refusal(c, 2, opts->preconditioner, true)) throw Error(why);      // (FDM past this line: no constraint list, fdm_p_supported)
+    if (iterative || opts->preconditioner != PORO_PREC_FDM || opts->stop_rule != PORO_STOP_RHS || !q1_stencil(c) || n_entries > 3) return 0;
+    build_fdm_q1(c, Q1Set::free_ends);
+    const bool batched = !c->comm.multi() && c->q1_free.fused.built && !c->q1_free.fused.slab.on;      // one rank, 3D, lines of <= 128 vertices: all right-hand sides in one set of launches
     if (c->proj_y.n < (size_t)3 * c->n_p) c->proj_y.alloc((size_t)3 * c->n_p);
     const double *b[3];
     double *x[3];
@@ -1167,7 +1114,7 @@ int poro_apply_preconditioner_u(poro_ctx *c, int32_t preconditioner, const doubl
       FdmOct &O = c->fdm_oct;
       // octant form where the solver uses it: butterflies outside (H, H'), the three transform passes in between - the timed part, as inside PCG
       fdm_precondition_u_nodal(c, g.p, z.p, c->fdm_precision);
-      auto once = [&]() { if (O.built) fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, c->fdm_precision); else fdm_precondition_u(c, g.p, z.p); };
+      auto once = [&]() { if (O.built) fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, c->fdm_precision, O.t.p); else fdm_precondition_u(c, g.p, z.p); };
       if (reps > 0 && seconds_per_apply) {
         EventPair ev(c); PORO_HIP(hipEventRecord(ev.e0, s));
         for (int k = 0; k < reps; ++k) once();

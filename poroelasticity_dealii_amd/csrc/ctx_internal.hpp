@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "common.hpp"
+#include "whole_faces.hpp"
 
 namespace poro {
 namespace ctx_detail {
@@ -93,20 +94,23 @@ double estimate_lmax_u(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj);
 
 // ---- fast-diagonalisation preconditioners (ctx_prec.hip) ------------------------------------------------------------------------------
 bool fdm_p_supported(poro_ctx *c);
-void build_fdm_p(poro_ctx *c);
 bool fdm_pj_supported(poro_ctx *c);      // prescribed pressures on whole faces of a box / tensor grid, one rank
-void build_fdm_pj(poro_ctx *c);          // the Q1 tables of the pressure Jacobian with those faces' end nodes removed (never built without prescribed pressures)
+// the two table sets of the Q1 systems (poro_ctx::q1_free, q1_fixed): every end free | the ends of the prescribed faces removed (never built without prescribed pressures)
+enum class Q1Set { free_ends, fixed_ends };
+inline FdmQ1 &q1_set(poro_ctx *c, Q1Set which) { return which == Q1Set::fixed_ends ? c->q1_fixed : c->q1_free; }
+void build_fdm_q1(poro_ctx *c, Q1Set which);
+int slab_layout(poro_ctx *c, SlabLayout &L, int nodes_per_cell, int64_t ncol_total);
+const char *prec_refusal(poro_ctx *c, int which_system, int prec, bool solving = false);   // null: usable; else why not (valid until the thread's next call)
 void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool self_in_place = false /* the caller has already put its own block into recv */);
 void setup_two_level(poro_ctx *c, const poro_desc *d);                // uploads P and its transpose (poro_desc.coarse)
 bool two_level_supported(poro_ctx *c);
 bool two_level_supported_p(poro_ctx *c);
 bool two_level_supported_pj(poro_ctx *c);  // ... for the pressure Jacobian with prescribed rows: the coarse box carries them as whole faces (its second table set is the coarse solve)
-void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, bool coarse_fixed_ends = false);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g, 0 on the inert rows; coarse_fixed_ends: the coarse matrix without its prescribed rows
+void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, Q1Set coarse_set = Q1Set::free_ends);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g, 0 on the inert rows; Q1Set::fixed_ends: the coarse matrix without its prescribed rows
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega);   // z = omega D^-1 g + P B_H^-1 P^T g
-void fdm_precondition_u_slab(poro_ctx *c, const double *g_quadrant, double *z_quadrant, const PcgScalars *gate);
-void fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision: of the octant form's transforms
+bool fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision, double *scratch, double *gz_part = nullptr);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision, scratch, gz_part: of the octant form's passes
 void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision);   // nodal g -> the form that is built (or the nodal kernels of fdm_precondition_u) -> nodal z
-void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, bool fixed_ends = false /* the table set of build_fdm_pj */);
+void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which = Q1Set::free_ends);
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <optional>
 #include <thread>
 #include <unordered_map>
 #include "common.hpp"
@@ -25,104 +26,99 @@ bool fdm_p_supported(poro_ctx *c) {
   if (c->comm.multi() && !(c->comm.nccl_comm || (c->comm.ar && c->comm.sr))) return false;
   return true;
 }
-static void upload_dir(FdmDir &D, const std::vector<double> &hcell, bool uniform, FdmOct *fused = nullptr, int dir = 0) {
-  const int n_cells = (int)hcell.size();
+// the second table set: the pressure Jacobian with whole prescribed faces (one rank)
+bool fdm_pj_supported(poro_ctx *c) { return c->n_pdir && c->pdir_faces_ok && !c->comm.multi() && fdm_p_supported(c); }
+// The 1D tables of one direction, with or without its end nodes.  Deleting the rows and columns of a face from a M + kappa K deletes the end node of that direction's 1D
+// matrices; fdmu_eig_1d gives their eigenpairs in full-length storage (zero rows of S at removed nodes, zero columns and lam = inf behind the free modes), so the
+// transform kernels run unchanged and return exactly 0 there.
+static void upload_dir(FdmDir &D, const std::vector<double> &hcell, bool uniform, bool fix_lo, bool fix_hi, FdmOct *fused = nullptr, int dir = 0) {
+  const int n = (int)hcell.size() + 1;
   std::vector<double> S, lam;
-  if (uniform) q1_eig(n_cells, hcell[0], S, lam); else fdmu_eig_1d(1, hcell, false, false, S, lam);   // (closed form on a uniform line)
-  if (fused) fdmo_scalar_upload_dir(*fused, dir, S, lam, n_cells + 1);
-  const int n = n_cells + 1;
+  if (uniform && !fix_lo && !fix_hi) q1_eig(n - 1, hcell[0], S, lam); else fdmu_eig_1d(1, hcell, fix_lo, fix_hi, S, lam);   // (closed form on a uniform line with free ends)
+  if (fused) fdmo_scalar_upload_dir(*fused, dir, S, lam, n);
   std::vector<double> St((size_t)n * n);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
+  // six-launch form: its kernel divides by a + sum k_d lam_d.  A removed mode's coefficient is exactly 0 (zero row of S^T), so any finite positive eigenvalue in its
+  // place gives the 0 that lam = inf gives, without inf * 0 where a coefficient k_d is 0
+  if (fix_lo || fix_hi) for (double &l : lam) if (!(l < 1e300)) l = 1e300;
   D.n = n; D.S.upload(S); D.St.upload(St); D.lam.upload(lam);
 }
-void build_fdm_p(poro_ctx *c) {
-  if (c->fdm_p.built) return;
-  if (!fdm_p_supported(c)) throw Error("PORO_PREC_FDM needs a uniform box (poro_desc.box.enabled) and, when partitioned, an initialised communicator");
-  c->fdm_p.dim = c->dim;
+// every rank learns all slab thicknesses through the existing all-reduce.  nodes_per_cell: 1 for the Q1 space, k_u for the displacement space; ncol_total: the nodes of one
+// plane.  Returns the global number of cell layers
+int slab_layout(poro_ctx *c, SlabLayout &L, int nodes_per_cell, int64_t ncol_total) {
+  const int N = std::max(1, c->comm.part.n_ranks), r = c->comm.part.rank, last = c->dim - 1;
+  L.n_ranks = N; L.rank = r;
+  std::vector<double> lay(N, 0.0); lay[r] = c->box.n[last];
+  DevBuf<double> tmp; tmp.upload(lay);
+  for (int base = 0; base < N; base += kScalarSlots) {
+    const int m = std::min(kScalarSlots, N - base);
+    PORO_HIP(hipMemcpyAsync(c->red.p, tmp.p + base, m * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    allreduce_sum(c, c->red.p, m);
+    PORO_HIP(hipMemcpyAsync(lay.data() + base, c->red.p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
+  }
+  L.layers.resize(N); L.off.resize(N); int acc = 0;
+  for (int q = 0; q < N; ++q) { L.layers[q] = (int)std::lround(lay[q]); L.off[q] = nodes_per_cell * acc; acc += L.layers[q]; }
+  L.ng = nodes_per_cell * acc + 1;
+  L.ncol_total = ncol_total;
+  L.C = (L.ncol_total + N - 1) / N;
+  L.max_own = 0; L.max_nl = 0;
+  for (int q = 0; q < N; ++q) { L.max_own = std::max(L.max_own, nodes_per_cell * L.layers[q] + (q == N - 1 ? 1 : 0)); L.max_nl = std::max(L.max_nl, nodes_per_cell * L.layers[q] + 1); }
+  return acc;
+}
+// the slab-partitioned part of the free table set: the global line of the last direction, the exchange buffers and windows, the slab form of the fused kernels
+static void build_fdm_dist(poro_ctx *c, const int np3[3]) {
+  FdmDist &F = c->fdm_dist; FdmOct &fused = c->q1_free.fused; const int last = c->dim - 1;
+  int64_t ncol_total = 1; for (int d = 0; d < last; ++d) ncol_total *= c->box.n[d] + 1;
+  const int acc = slab_layout(c, F, 1, ncol_total), N = F.n_ranks, r = F.rank;
+  // slab form of the same three-launch kernels (kernels_fdmo.hip): 3D, local planes and the global line of at most 80 vertices
+  { int g3[3] = {np3[0], np3[1], acc + 1};
+    const bool fused_slab = c->dim == 3 && fdmo_scalar_usable(3, np3) && fdmo_scalar_usable(3, g3) && !std::getenv("PORO_FDM_P_UNFUSED");
+    if (fused_slab) {
+      fdmo_scalar_init_slab(fused, np3, r, F.layers, c->stream);
+      for (int d = 0; d < 2; ++d) { std::vector<double> S, lam; q1_eig(c->box.n[d], c->box.h[d], S, lam); fdmo_scalar_upload_dir(fused, d, S, lam, c->box.n[d] + 1); }
+      std::vector<double> S, lam; q1_eig(acc, c->box.h[last], S, lam); fdmo_scalar_upload_dir(fused, 2, S, lam, acc + 1);
+      fused.built = true;
+    } }
+  upload_dir(F.last, std::vector<double>((size_t)acc, c->box.h[last]), true, false, false);
+  const size_t blk = (size_t)std::max(F.max_own, F.max_nl) * F.C;
+  F.sendbuf.alloc(blk * N); F.recvbuf.alloc(blk * N); F.tz1.alloc((size_t)F.ng * F.C); F.tz2.alloc((size_t)F.ng * F.C);
+  F.sendbuf.zero(c->stream); F.recvbuf.zero(c->stream); F.tz1.zero(c->stream); F.tz2.zero(c->stream);
+  // the four window copies of an application, one entry per peer: local grid -> send blocks (own planes), gathered blocks -> whole lines, whole lines -> send blocks
+  // (every rank's planes incl. the shared ones), scattered blocks -> local grid
+  std::vector<FdmWindow> W((size_t)4 * N);
+  auto ncols_of = [&](int q) { return std::max<int64_t>(0, std::min<int64_t>(F.C, F.ncol_total - (int64_t)q * F.C)); };
+  const int own_r = F.layers[r] + (r == N - 1 ? 1 : 0), nl_r = c->box.n[last] + 1;
+  for (int q = 0; q < N; ++q) {
+    W[q] = FdmWindow{own_r, ncols_of(q), (int64_t)q * F.C, 0};
+    W[N + q] = FdmWindow{F.layers[q] + (q == N - 1 ? 1 : 0), F.C, 0, F.off[q]};
+    W[2 * N + q] = FdmWindow{F.layers[q] + 1, F.C, 0, F.off[q]};
+    W[3 * N + q] = FdmWindow{nl_r, ncols_of(q), (int64_t)q * F.C, 0};
+  }
+  F.windows.upload(W);
+  F.built = true;
+}
+// One builder for both table sets.  Q1Set::free_ends: every end free (the projection mass matrix, the pressure Jacobian without prescribed rows), on slab partitions with
+// the distributed part.  Q1Set::fixed_ends: the ends of c->pdir_face removed; built lazily by the first solve that needs it, never without prescribed pressures
+void build_fdm_q1(poro_ctx *c, Q1Set which) {
+  const bool fixed = which == Q1Set::fixed_ends;
+  FdmQ1 &T = q1_set(c, which);
+  if (T.nodal.built) return;
+  if (fixed) {
+    if (!fdm_pj_supported(c)) throw Error("PORO_PREC_FDM with prescribed pressures needs a uniform box or tensor-product grid on one rank whose prescribed set is a union of whole faces");
+    if (c->timing) c->timers["fdm_pj_build"].enqueued += 1;          // (a count, no time: contexts without prescribed pressures never get here)
+  } else if (!fdm_p_supported(c)) throw Error("PORO_PREC_FDM needs a uniform box (poro_desc.box.enabled) and, when partitioned, an initialised communicator");
+  T.nodal.dim = c->dim;
+  const bool multi = !fixed && c->comm.multi();                      // (the fixed-ends set: one rank, see fdm_pj_supported)
   // one rank, 3D, lines of at most 80 nodes: the three-launch form through the block-FDM transform kernel (kernels_fdmo.hip) instead of six single-direction launches
   int np3[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, c->dim == 3 ? c->lines.n[2] + 1 : 1};
-  const bool fused = !c->comm.multi() && fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
-  if (fused) fdmo_scalar_init(c->fdm_p_fused, np3, c->stream);
-  bool fused_slab = false;   // decided below, once the global line length is known
-  for (int d = 0; d < c->dim; ++d) upload_dir(c->fdm_p.dir[d], c->lines.hcell[d], c->lines.uniform, fused ? &c->fdm_p_fused : nullptr, d);   // local slab; the last direction is replaced below when partitioned
-  if (!c->comm.multi()) c->fdm_p_fused.built = fused;
-  c->fdm_t1.alloc(c->n_p); c->fdm_t2.alloc(c->n_p);
-  if (c->comm.multi()) {
-    FdmDist &F = c->fdm_dist; const int N = std::max(1, c->comm.part.n_ranks), r = c->comm.part.rank, last = c->dim - 1;
-    F.n_ranks = N; F.rank = r;
-    // every rank learns all slab thicknesses through the existing all-reduce
-    std::vector<double> lay(N, 0.0); lay[r] = c->box.n[last];
-    DevBuf<double> tmp; tmp.upload(lay);
-    for (int base = 0; base < N; base += kScalarSlots) {
-      const int m = std::min(kScalarSlots, N - base);
-      PORO_HIP(hipMemcpyAsync(c->red.p, tmp.p + base, m * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      allreduce_sum(c, c->red.p, m);
-      PORO_HIP(hipMemcpyAsync(lay.data() + base, c->red.p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
-    }
-    F.layers.resize(N); F.off.resize(N); int acc = 0;
-    for (int q = 0; q < N; ++q) { F.layers[q] = (int)std::lround(lay[q]); F.off[q] = acc; acc += F.layers[q]; }
-    F.ng = acc + 1;
-    F.ncol_total = 1; for (int d = 0; d < last; ++d) F.ncol_total *= c->box.n[d] + 1;
-    F.C = (F.ncol_total + N - 1) / N;
-    F.max_own = 0; F.max_nl = 0;
-    for (int q = 0; q < N; ++q) { F.max_own = std::max(F.max_own, F.layers[q] + (q == N - 1 ? 1 : 0)); F.max_nl = std::max(F.max_nl, F.layers[q] + 1); }
-    // slab form of the same three-launch kernels (kernels_fdmo.hip): 3D, local planes and the global line of at most 80 vertices
-    { int g3[3] = {np3[0], np3[1], acc + 1};
-      fused_slab = c->dim == 3 && fdmo_scalar_usable(3, np3) && fdmo_scalar_usable(3, g3) && !std::getenv("PORO_FDM_P_UNFUSED");
-      if (fused_slab) {
-        fdmo_scalar_init_slab(c->fdm_p_fused, np3, r, F.layers, c->stream);
-        for (int d = 0; d < 2; ++d) { std::vector<double> S, lam; q1_eig(c->box.n[d], c->box.h[d], S, lam); fdmo_scalar_upload_dir(c->fdm_p_fused, d, S, lam, c->box.n[d] + 1); }
-        std::vector<double> S, lam; q1_eig(acc, c->box.h[last], S, lam); fdmo_scalar_upload_dir(c->fdm_p_fused, 2, S, lam, acc + 1);
-        c->fdm_p_fused.built = true;
-      } }
-    upload_dir(F.last, std::vector<double>((size_t)acc, c->box.h[last]), true);
-    const size_t blk = (size_t)std::max(F.max_own, F.max_nl) * F.C;
-    F.sendbuf.alloc(blk * N); F.recvbuf.alloc(blk * N); F.tz1.alloc((size_t)F.ng * F.C); F.tz2.alloc((size_t)F.ng * F.C);
-    F.sendbuf.zero(c->stream); F.recvbuf.zero(c->stream); F.tz1.zero(c->stream); F.tz2.zero(c->stream);
-    // the four window copies of an application, one entry per peer: local grid -> send blocks (own planes), gathered blocks -> whole lines, whole lines -> send blocks
-    // (every rank's planes incl. the shared ones), scattered blocks -> local grid
-    std::vector<FdmWindow> W((size_t)4 * N);
-    auto ncols_of = [&](int q) { return std::max<int64_t>(0, std::min<int64_t>(F.C, F.ncol_total - (int64_t)q * F.C)); };
-    const int own_r = F.layers[r] + (r == N - 1 ? 1 : 0), nl_r = c->box.n[last] + 1;
-    for (int q = 0; q < N; ++q) {
-      W[q] = FdmWindow{own_r, ncols_of(q), (int64_t)q * F.C, 0};
-      W[N + q] = FdmWindow{F.layers[q] + (q == N - 1 ? 1 : 0), F.C, 0, F.off[q]};
-      W[2 * N + q] = FdmWindow{F.layers[q] + 1, F.C, 0, F.off[q]};
-      W[3 * N + q] = FdmWindow{nl_r, ncols_of(q), (int64_t)q * F.C, 0};
-    }
-    F.windows.upload(W);
-    F.built = true;
-  }
-  c->fdm_p.built = true;
-}
-// ---- the second table set: the pressure Jacobian with whole prescribed faces (one rank) ---------------------------------------------------------------------------
-// Deleting the rows and columns of a face from a M + kappa K deletes the end node of that direction's 1D matrices; fdmu_eig_1d gives their eigenpairs in full-length
-// storage (zero rows of S at removed nodes, zero columns and lam = inf behind the free modes), so the transform kernels run unchanged and return exactly 0 there.
-bool fdm_pj_supported(poro_ctx *c) { return c->n_pdir && c->pdir_faces_ok && !c->comm.multi() && fdm_p_supported(c); }
-void build_fdm_pj(poro_ctx *c) {
-  if (c->fdm_pj.built) return;
-  if (!fdm_pj_supported(c)) throw Error("PORO_PREC_FDM with prescribed pressures needs a uniform box or tensor-product grid on one rank whose prescribed set is a union of whole faces");
-  if (c->timing) c->timers["fdm_pj_build"].enqueued += 1;          // (a count, no time: contexts without prescribed pressures never get here)
-  FdmScalar &F = c->fdm_pj; F.dim = c->dim;
-  int np3[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, c->dim == 3 ? c->lines.n[2] + 1 : 1};
-  const bool fused = fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
-  if (fused) fdmo_scalar_init(c->fdm_pj_fused, np3, c->stream);
-  for (int d = 0; d < c->dim; ++d) {
-    const std::vector<double> &hcell = c->lines.hcell[d]; const int n = (int)hcell.size() + 1;
-    const bool lo = c->pdir_face[d][0] != 0, hi = c->pdir_face[d][1] != 0;
-    std::vector<double> S, lam;
-    if (!lo && !hi && c->lines.uniform) q1_eig(n - 1, hcell[0], S, lam); else fdmu_eig_1d(1, hcell, lo, hi, S, lam);   // (free directions: the tables of fdm_p)
-    if (fused) fdmo_scalar_upload_dir(c->fdm_pj_fused, d, S, lam, n);
-    std::vector<double> St((size_t)n * n);
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
-    // six-launch form: its kernel divides by a + sum k_d lam_d.  A removed mode's coefficient is exactly 0 (zero row of S^T), so any finite positive eigenvalue in its
-    // place gives the 0 that lam = inf gives, without inf * 0 where a coefficient k_d is 0
-    for (double &l : lam) if (!(l < 1e300)) l = 1e300;
-    FdmDir &D = F.dir[d]; D.n = n; D.S.upload(S); D.St.upload(St); D.lam.upload(lam);
-  }
-  c->fdm_pj_fused.built = fused;
+  const bool fused = !multi && fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
+  if (fused) fdmo_scalar_init(T.fused, np3, c->stream);
+  for (int d = 0; d < c->dim; ++d)                                   // (partitioned: the local slab; the last direction is replaced by fdm_dist.last)
+    upload_dir(T.nodal.dir[d], c->lines.hcell[d], c->lines.uniform, fixed && c->pdir_face[d][0], fixed && c->pdir_face[d][1], fused ? &T.fused : nullptr, d);
+  if (!multi) T.fused.built = fused;
   if (c->fdm_t1.n < (size_t)c->n_p) { c->fdm_t1.alloc(c->n_p); c->fdm_t2.alloc(c->n_p); }
-  F.built = true;
+  if (multi) build_fdm_dist(c, np3);
+  T.nodal.built = true;
 }
 // every rank sends block q of `send` (blk doubles) to rank q and receives block q of `recv` from it
 void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool self_in_place) {
@@ -149,25 +145,22 @@ void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool 
     }
   } else throw Error("partitioned context without a communicator");
 }
-// z = (a M + sum_d k_d K_d)^-1 g for the Q1 space of the (global) box
-// fixed_ends: the second table set (whole prescribed faces removed, one rank): z = J_ff^-1 g_f on the free rows, exactly 0 on the prescribed ones whatever g holds there
-void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, bool fixed_ends) {
+// z = (a M + sum_d k_d K_d)^-1 g for the Q1 space of the (global) box, from the table set `which`
+// Q1Set::fixed_ends (whole prescribed faces removed, one rank): z = J_ff^-1 g_f on the free rows, exactly 0 on the prescribed ones whatever g holds there
+void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which) {
   Timed tm(c, "precondition_p_fdm");
   hipStream_t s = c->stream;
-  if (fixed_ends) {
-    Timed tf(c, "precondition_p_fdm_fixed_ends");
-    if (c->fdm_pj_fused.built && k[0] == k[1] && k[1] == k[2]) fdmo_scalar_apply(s, c->fdm_pj_fused, a, k[0], g, z);
-    else fdm_apply(s, c->fdm_pj, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);
+  const bool fixed = which == Q1Set::fixed_ends, isotropic = k[0] == k[1] && k[1] == k[2];
+  FdmQ1 &T = q1_set(c, which);
+  if (fixed || !c->comm.multi()) {
+    std::optional<Timed> tf; if (fixed) tf.emplace(c, "precondition_p_fdm_fixed_ends");
+    if (T.fused.built && isotropic) fdmo_scalar_apply(s, T.fused, a, k[0], g, z);
+    else fdm_apply(s, T.nodal, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);
     return;
   }
-  if (!c->comm.multi()) {
-    if (c->fdm_p_fused.built && k[0] == k[1] && k[1] == k[2]) fdmo_scalar_apply(s, c->fdm_p_fused, a, k[0], g, z);
-    else fdm_apply(s, c->fdm_p, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);
-    return;
-  }
-  if (c->fdm_p_fused.built && c->fdm_p_fused.slab.on && k[0] == k[1] && k[1] == k[2]) {
+  if (T.fused.built && T.fused.slab.on && isotropic) {
     // the slab form of the fused kernels: x / y sweeps on the local planes straight into the exchange buffer, whole z lines per column share, scatter, y / x sweeps
-    FdmOct &O = c->fdm_p_fused; auto &S = O.slab; double *send = S.buf.p, *recv = S.buf.p + S.recv_off;
+    FdmOct &O = T.fused; auto &S = O.slab; double *send = S.buf.p, *recv = S.buf.p + S.recv_off;
     fdmo_scalar_slab_pass(s, O, 1, a, k[0], g, S.buf.p);
     alltoall_blocks(c, send, recv, (int64_t)S.max_own * S.scols, true);
     fdmo_scalar_slab_pass(s, O, 2, a, k[0], S.buf.p, S.tz.p);
@@ -176,7 +169,7 @@ void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *
     fdmo_scalar_slab_pass(s, O, 3, a, k[0], S.buf.p, z);
     return;
   }
-  FdmDist &F = c->fdm_dist; const FdmScalar &L = c->fdm_p;
+  FdmDist &F = c->fdm_dist; const FdmScalar &L = T.nodal;
   const int dim = c->dim, N = F.n_ranks, r = F.rank, last = dim - 1;
   const int n0 = L.dir[0].n, nl = c->box.n[last] + 1;             // local planes incl. the shared ones
   const int64_t SIp = F.ncol_total;
@@ -221,26 +214,11 @@ void analyse_fdm_u(poro_ctx *c) {
   }
   if (why.empty()) {
     const std::vector<uint8_t> &nm = c->h_node_mask;
-    auto node = [&](int64_t i, int64_t j, int64_t k) { return (k * nn[1] + j) * nn[0] + i; };
     // a face of the partitioned direction is a physical boundary only at the first / last rank
-    auto physical = [&](int d, int side) { return !(multi && d == last && (side == 0 ? c->comm.part.has_lower : c->comm.part.has_upper)); };
-    for (int comp = 0; comp < dim && why.empty(); ++comp) {
-      for (int d = 0; d < dim; ++d) for (int side = 0; side < 2; ++side) {
-        bool all = physical(d, side);
-        const int64_t fixed = side ? nn[d] - 1 : 0;
-        const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-        for (int64_t a = 0; a < nn[d1] && all; ++a) for (int64_t b = 0; b < nn[d2]; ++b) {
-          int64_t ix[3]; ix[d] = fixed; ix[d1] = a; ix[d2] = b;
-          if (!(nm[node(ix[0], ix[1], ix[2])] >> comp & 1)) { all = false; break; }
-        }
-        F.fix[comp][d][side] = all ? 1 : 0;
-      }
-      for (int64_t k = 0; k < nn[2] && why.empty(); ++k) for (int64_t j = 0; j < nn[1] && why.empty(); ++j) for (int64_t i = 0; i < nn[0]; ++i) {
-        const int64_t ix[3] = {i, j, k}; bool on = false;
-        for (int d = 0; d < dim; ++d) on = on || (ix[d] == 0 && F.fix[comp][d][0]) || (ix[d] == nn[d] - 1 && F.fix[comp][d][1]);
-        if (on != (bool)(nm[node(i, j, k)] >> comp & 1)) { why = "Dirichlet dofs are not a union of whole faces per component"; break; }
-      }
-    }
+    int physical[3][2] = {{1, 1}, {1, 1}, {1, 1}};
+    if (multi) { physical[last][0] = !c->comm.part.has_lower; physical[last][1] = !c->comm.part.has_upper; }
+    for (int comp = 0; comp < dim && why.empty(); ++comp)
+      if (!whole_faces(nn, dim, nm.data(), comp, physical, F.fix[comp])) why = "Dirichlet dofs are not a union of whole faces per component";
   }
   // ranks agree on the verdict and on the face flags (the end faces of the partitioned direction live on the first / last rank only)
   if (multi) {
@@ -281,25 +259,10 @@ void build_fdm_u(poro_ctx *c) {
   for (int comp = 0; comp < dim; ++comp) for (int d = 0; d < dim; ++d) F.coef[comp][d] = d == comp ? l2g : G;
   int n_cells_last = c->lines.n[last];
   if (multi) {
-    // every rank learns all slab thicknesses through the existing all-reduce
-    const int N = std::max(1, c->comm.part.n_ranks), r = c->comm.part.rank;
-    F.dist = true; F.n_ranks = N; F.rank = r;
-    std::vector<double> lay(N, 0.0); lay[r] = c->box.n[last];
-    DevBuf<double> tmp; tmp.upload(lay);
-    for (int base = 0; base < N; base += kScalarSlots) {
-      const int m = std::min(kScalarSlots, N - base);
-      PORO_HIP(hipMemcpyAsync(c->red.p, tmp.p + base, m * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      allreduce_sum(c, c->red.p, m);
-      PORO_HIP(hipMemcpyAsync(lay.data() + base, c->red.p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream)); PORO_HIP(hipStreamSynchronize(c->stream));
-    }
-    F.layers.resize(N); F.off.resize(N); int acc = 0;
-    for (int q = 0; q < N; ++q) { F.layers[q] = (int)std::lround(lay[q]); F.off[q] = ku * acc; acc += F.layers[q]; }
-    n_cells_last = acc; F.ng = ku * acc + 1;
+    int64_t ncol_total = 1; for (int d = 0; d < last; ++d) ncol_total *= F.nn[d];
+    F.dist = true; n_cells_last = slab_layout(c, F, ku, ncol_total);
     if (F.ng > 4096) throw Error("PORO_PREC_FDM (displacement): more than 4096 nodes per global grid line");
-    F.ncol_total = 1; for (int d = 0; d < last; ++d) F.ncol_total *= F.nn[d];
-    F.C = (F.ncol_total + N - 1) / N;
-    F.max_own = 0; F.max_nl = 0;
-    for (int q = 0; q < N; ++q) { F.max_own = std::max(F.max_own, ku * F.layers[q] + (q == N - 1 ? 1 : 0)); F.max_nl = std::max(F.max_nl, ku * F.layers[q] + 1); }
+    const int N = F.n_ranks;
     const size_t blk = (size_t)dim * std::max(F.max_own, F.max_nl) * F.C;
     F.sendbuf.alloc(blk * N); F.recvbuf.alloc(blk * N); F.tz1.alloc((size_t)dim * F.ng * F.C); F.tz2.alloc((size_t)dim * F.ng * F.C);
     F.sendbuf.zero(c->stream); F.recvbuf.zero(c->stream); F.tz1.zero(c->stream); F.tz2.zero(c->stream);
@@ -349,8 +312,7 @@ void build_fdm_u(poro_ctx *c) {
   F.built = true;
 }
 // slab form of the octant kernels: g, z in quadrant layout.  x / y sweeps on the local planes, whole z lines per column share between two all-to-alls
-void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgScalars *gate) {
-  Timed tm(c, "precondition_u_fdm");
+static void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgScalars *gate) {
   hipStream_t s = c->stream; FdmOct &O = c->fdm_oct; auto &S = O.slab;
   double *send = S.buf.p, *recv = S.buf.p + S.recv_off;
   fdmo_slab_pass(s, O, 1, g, S.buf.p, gate);                                          // x, y forward on the local planes; the owned planes go straight into the exchange buffer
@@ -363,18 +325,38 @@ void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgS
   alltoall_blocks(c, send, recv, (int64_t)S.max_nl * S.scols, true);
   fdmo_slab_pass(s, O, 3, S.buf.p, z, gate);                                          // y, x backward, reading the received planes in place
 }
-// g, z in the layout of the form that is built (c->fdm_oct.built): quadrants on slabs, the planar form in 2D, octants on one rank
-void fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgScalars *gate, int precision) {
-  FdmOct &O = c->fdm_oct;
-  if (O.slab.on) fdm_precondition_u_slab(c, g, z, gate);
-  else if (O.planar) fdmo_apply_planar(c->stream, O, g, z, gate);
-  else fdmo_apply(c->stream, O, g, z, O.t.p, gate, nullptr, nullptr, precision);
+// g, z in the layout of the form that is built (c->fdm_oct.built): quadrants on slabs, the planar form in 2D, octants on one rank - the one place that switches between them.
+// The octant form runs as three transform dispatches.  A sampled call times them one by one (per-kernel roofline of the bench): the sampling runs on
+// fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
+// gz_part != null (octant form; the others ignore it): pass 2 also leaves the partial sums of g . z there (returns true: no separate dot kernel)
+// scratch == null (octant form): the passes work on z itself (fp64 transforms only)
+bool fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgScalars *gate, int precision, double *scratch, double *gz_part) {
+  Timed tm(c, "precondition_u_fdm");
+  const FdmOct &O = c->fdm_oct;
+  if (O.slab.on) { fdm_precondition_u_slab(c, g, z, gate); return false; }
+  if (O.planar) { fdmo_apply_planar(c->stream, O, g, z, gate); return false; }
+  const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
+  if (!begin_sampled_dispatch(c, names[0])) {
+    fdmo_apply(c->stream, O, g, z, scratch, gate, nullptr, gz_part, precision);
+    return gz_part != nullptr;
+  }
+  c->timers[names[1]].enqueued++;
+  c->timers[names[2]].enqueued++;
+  hipEvent_t ev[6];
+  for (auto &e : ev) e = event_get(c);
+  fdmo_apply(c->stream, O, g, z, scratch, gate, ev, gz_part, precision);
+  for (int k = 0; k < 3; ++k) {
+    Timer &t = c->timers[names[k]];
+    t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);
+    t.launches++;
+  }
+  return gz_part != nullptr;
 }
 // nodal g -> whichever form of the block FDM is built -> nodal z
 void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision) {
   FdmOct &O = c->fdm_oct;
   if (!O.built) { fdm_precondition_u(c, g, z); return; }
-  fdmo_from_nodal(c->stream, O, g, O.g.p); fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, precision); fdmo_to_nodal(c->stream, O, O.z.p, z);
+  fdmo_from_nodal(c->stream, O, g, O.g.p); fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, precision, O.t.p); fdmo_to_nodal(c->stream, O, O.z.p, z);
 }
 // ---- additive two-level preconditioner on refinements of a uniform box (poro_desc.coarse) ----------------------------------------------------
 // P holds every local row (prolongation / combination); its transpose (restriction) only the owned rows [0, n_owned), so that the pieces of a general partition
@@ -437,18 +419,18 @@ bool two_level_supported_pj(poro_ctx *c) {
   return c->n_pdir && two_level_supported_p(c) && c->two_level.pdir_nested && c->two_level.box->n_pdir && fdm_pj_supported(c->two_level.box);
 }
 // the scalar analogue for the pressure Jacobian a M + kappa K and the projection mass matrix (a = 1, kappa = 0): Jacobi on this mesh + the box's exact fast diagonalisation
-// inert: the rows of z left 0 (hanging rows; for the Jacobian also the prescribed ones).  coarse_fixed_ends: z = omega D^-1 g + P (J_H)_ff^-1 P^T g, the coarse box's
+// inert: the rows of z left 0 (hanging rows; for the Jacobian also the prescribed ones).  coarse_set = Q1Set::fixed_ends: z = omega D^-1 g + P (J_H)_ff^-1 P^T g, the coarse box's
 // table set without its prescribed faces' end nodes - whatever P^T g holds on those coarse rows, the coarse correction is exactly 0 there
-void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, bool coarse_fixed_ends) {
+void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, Q1Set coarse_set) {
   Timed tm(c, "precondition_p_two_level");
   auto &T = c->two_level.pressure; poro_ctx *H = c->two_level.box; hipStream_t s = c->stream;
-  if (coarse_fixed_ends) build_fdm_pj(H); else build_fdm_p(H);
+  build_fdm_q1(H, coarse_set);
   if (!H->wz_p.p) H->wz_p.alloc(H->n_p);
   double *rc = H->wg_p.p, *zc = H->wz_p.p;
   la_nodal_interp(s, T.pt_ptr.p, T.pt_col.p, T.pt_w.p, T.n_coarse, 1, g, rc, T.lanes_t);
   if (c->comm.multi()) allreduce_sum_vec(c, rc, T.n_coarse, "two_level_coarse_allreduce");      // partitioned: every rank restricted its owned rows; all hold P^T g after the sum
   const double kk[3] = {kappa, kappa, kappa};
-  fdm_precondition_p(H, a, kk, rc, zc, coarse_fixed_ends);
+  fdm_precondition_p(H, a, kk, rc, zc, coarse_set);
   la_two_level_combine(s, T.p_ptr.p, T.p_col.p, T.p_w.p, T.n_fine, 1, zc, g, dinv, inert, omega, z, T.lanes);
 }
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega) {
@@ -487,6 +469,48 @@ void fdm_precondition_u(poro_ctx *c, const double *g, double *z) {
   alltoall_blocks(c, F.sendbuf.p, F.recvbuf.p, blk2);
   for (int q = 0; q < N; ++q) fdmu_window(s, cur, F.recvbuf.p + (size_t)q * blk2, false, dim, nl, F.max_nl, F.C, ncols_of(q), F.ncol_total, nl, (int64_t)q * F.C, 0);
   fdmu_apply(s, F, g, z, c->fdmu_t1.p, c->fdmu_t2.p, 1);
+}
+
+// ---- what a context supports: the one verdict behind poro_supports_preconditioner and the three solve entry points ------------------------------------------------
+// null where the preconditioner `prec` is usable on system `which_system` (0 displacement, 1 pressure Jacobian, 2 projection mass matrix), else the reason.  The
+// per-feature predicates stay where their features are; the refusals inside the builders and solves remain as checks for internal callers.
+// solving: asked by a solve entry point.  The one difference: a value that has no implementation on the system runs there as PORO_PREC_NONE does - CG without a
+// preconditioner, the Krylov driver applies the diagonal for PORO_PREC_JACOBI alone (see the two marked lines)
+const char *prec_refusal(poro_ctx *c, int which_system, int prec, bool solving) {
+  static thread_local std::string why;
+  if (prec == PORO_PREC_NONE || prec == PORO_PREC_JACOBI) return nullptr;
+  const bool multi = c->comm.multi(), sweeps = prec == PORO_PREC_SSOR || prec == PORO_PREC_ILU0;
+  const char *one_rank = prec == PORO_PREC_SSOR ? "PORO_PREC_SSOR is a single-rank fidelity mode (the sweeps are order dependent)"
+                                                : "PORO_PREC_ILU0 is implemented for one rank (the factorisation is sequential in the row order)";
+  if (which_system == 0) {
+    if (prec == PORO_PREC_TWO_LEVEL)
+      return two_level_supported(c) ? nullptr : "PORO_PREC_TWO_LEVEL needs poro_desc.coarse (a refinement of a uniform box whose Dirichlet conditions cover whole faces)";
+    // condensed operators exist at operator level only: Jacobi, the polynomial built on it, the two-level form above
+    if (c->cons_u.n && prec != PORO_PREC_CHEBYSHEV) return "meshes with constraint lists: PORO_PREC_JACOBI / CHEBYSHEV / TWO_LEVEL / NONE only (the operator is condensed on the fly)";
+    if (prec == PORO_PREC_CHEBYSHEV) return nullptr;
+    if (sweeps) return c->operator_mode != PORO_OP_CSR ? (prec == PORO_PREC_SSOR ? "PORO_PREC_SSOR needs the assembled CSR operator" : "PORO_PREC_ILU0 needs the assembled CSR operator") : multi ? one_rank : nullptr;
+    if (prec == PORO_PREC_FDM) {
+      analyse_fdm_u(c);                                      // (state 0, a partitioned context without a communicator yet: unsupported, and asked again next time)
+      if (c->fdm_u_state == 1) return nullptr;
+      why = "PORO_PREC_FDM (displacement): " + c->fdm_u_why;
+      return why.c_str();
+    }
+    return solving ? nullptr : "unknown preconditioner";      // asymmetry kept: disp_solve runs an unknown value as PORO_PREC_NONE
+  }
+  if (which_system != 1 && which_system != 2) return "unknown system (0 displacement, 1 pressure, 2 projection)";
+  if (which_system == 1 && (c->cons_p.n || c->n_pdir)) {
+    // hanging rows: the two-level form.  Prescribed rows: two-level where the coarse box carries the condition as whole faces (two_level_supported_pj), the
+    // fixed-ends table set where they cover whole faces of a box / tensor grid on one rank (fdm_pj_supported: never with hanging rows)
+    const bool ok = prec == PORO_PREC_TWO_LEVEL ? (!c->n_pdir || two_level_supported_pj(c)) : prec == PORO_PREC_FDM && fdm_pj_supported(c);
+    if (!ok) return "meshes with hanging-node constraints or prescribed pressures: PORO_PREC_JACOBI / NONE (hanging nodes: also TWO_LEVEL; with prescribed pressures where the coarse box carries them as whole faces) only; prescribed pressures that cover whole faces of a uniform box or tensor-product grid on one rank: also PORO_PREC_FDM";
+  }
+  // (the projection's mass matrix has no prescribed rows)
+  if (which_system == 2 && c->cons_p.n && prec != PORO_PREC_TWO_LEVEL) return "meshes with hanging-node constraints: PORO_PREC_JACOBI / TWO_LEVEL / NONE only";
+  if (prec == PORO_PREC_TWO_LEVEL)
+    return two_level_supported_p(c) ? nullptr : "PORO_PREC_TWO_LEVEL (pressure / projection): needs poro_desc.coarse with the pressure interpolation (ptr_p / node_p / weight_p)";
+  if (sweeps) return multi ? one_rank : nullptr;
+  if (prec == PORO_PREC_FDM) return fdm_p_supported(c) ? nullptr : "PORO_PREC_FDM needs a uniform box (poro_desc.box.enabled) and, when partitioned, an initialised communicator";
+  return solving ? nullptr : "PORO_PREC_CHEBYSHEV (and unknown values) have no form on the Q1 systems";   // asymmetry kept: the Q1 solves run these as PORO_PREC_NONE; an error is a later issue
 }
 
 }  // namespace ctx_detail

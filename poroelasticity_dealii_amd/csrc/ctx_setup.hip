@@ -138,27 +138,15 @@ void upload_constraints(ConsDev &C, const poro_constraints &h, int64_t n_dofs, c
 }
 
 // Is the prescribed-pressure set exactly a union of whole faces (direction, side) of the line structure?  Then the free block of a M + kappa K is the Kronecker sum of
-// the 1D matrices without those end nodes (ctx_prec.hip: build_fdm_pj).  The prescribed VALUES may differ from node to node: they never enter the Newton matrix.
+// the 1D matrices without those end nodes (ctx_prec.hip: build_fdm_q1, Q1Set::fixed_ends).  The prescribed VALUES may differ from node to node: they never enter the Newton matrix.
 static void analyse_pdir_faces(poro_ctx *c, const std::vector<uint8_t> &pm) {
   c->pdir_faces_ok = false;
   for (int d = 0; d < 3; ++d) c->pdir_face[d][0] = c->pdir_face[d][1] = 0;
   if (!c->n_pdir || !c->lines.on || c->comm.multi() || c->cons_p.n) return;
   const int dim = c->dim; const int64_t np[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, dim == 3 ? c->lines.n[2] + 1 : 1};
   if (np[0] * np[1] * np[2] != c->n_p) return;
-  auto node = [&](int64_t i, int64_t j, int64_t k) { return (k * np[1] + j) * np[0] + i; };
-  for (int d = 0; d < dim; ++d) for (int side = 0; side < 2; ++side) {
-    bool all = true; const int64_t fixed = side ? np[d] - 1 : 0; const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-    for (int64_t a = 0; a < np[d1] && all; ++a) for (int64_t b = 0; b < np[d2]; ++b) {
-      int64_t ix[3]; ix[d] = fixed; ix[d1] = a; ix[d2] = b;
-      if (!pm[node(ix[0], ix[1], ix[2])]) { all = false; break; }
-    }
-    c->pdir_face[d][side] = all ? 1 : 0;
-  }
-  for (int64_t k = 0; k < np[2]; ++k) for (int64_t j = 0; j < np[1]; ++j) for (int64_t i = 0; i < np[0]; ++i) {
-    const int64_t ix[3] = {i, j, k}; bool on = false;
-    for (int d = 0; d < dim; ++d) on = on || (ix[d] == 0 && c->pdir_face[d][0]) || (ix[d] == np[d] - 1 && c->pdir_face[d][1]);
-    if (on != (pm[node(i, j, k)] != 0)) return;          // partial faces, interior nodes: the Jacobi path as before
-  }
+  const int every_face[3][2] = {{1, 1}, {1, 1}, {1, 1}};
+  if (!whole_faces(np, dim, pm.data(), 0, every_face, c->pdir_face)) return;          // partial faces, interior nodes: the Jacobi path as before
   for (int d = 0; d < dim; ++d) if (np[d] - c->pdir_face[d][0] - c->pdir_face[d][1] < 1) return;   // (a direction without a free node: nothing to solve)
   c->pdir_faces_ok = true;
 }

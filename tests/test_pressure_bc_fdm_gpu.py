@@ -1,7 +1,7 @@
 """Prescribed pressures on the fast-diagonalisation path (uniform boxes and tensor-product grids, one rank).
 
 Where the prescribed set is a union of whole faces, deleting those rows and columns from a M + kappa K leaves a Kronecker sum of 1D matrices without their end nodes, which
-has its own exact fast diagonalisation (the second table set, ctx_prec.hip: build_fdm_pj).  Checked here: the exact inverse against a sparse direct solve of the deleted
+has its own exact fast diagonalisation (the second table set, ctx_prec.hip: build_fdm_q1).  Checked here: the exact inverse against a sparse direct solve of the deleted
 system, the direct path (no CG iteration) on matrix-free boxes, CG + FDM on tensor grids and CSR contexts, the projection's untouched direct solve, the support queries,
 Terzaghi's column end to end, the CLI, and that contexts without prescribed pressures compute what they computed before (stored results of the previous code).
 
