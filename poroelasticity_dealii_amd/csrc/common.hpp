@@ -12,10 +12,9 @@
 #include <list>
 #include <vector>
 #include "../../include/poroel_hip.h"
+#include "fdm_tables.hpp"      // poro::Error (declared there: that header compiles without this one) and LineTables, the 1D tables of a grid line
 
 namespace poro {
-
-struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 
 #define PORO_HIP(x)                                                                                   \
   do { hipError_t e_ = (x); if (e_ != hipSuccess) throw poro::Error(std::string(#x) + " -> " + hipGetErrorString(e_)); } while (0)
@@ -405,18 +404,13 @@ BoxCoupling box_coupling(int dim, int k_u, const BoxDev &box);
 void box_rhs_u(hipStream_t s, int dim, const BoxCoupling &B, double alpha, const double *p, const double *lift, const double *neu, const uint8_t *mask, double *rhs);
 void box_asm_u_matrix(hipStream_t s, int dim, int k_u, const BoxDev &box, const double *Ke, const CsrDev &A, const uint8_t *mask, double *val);
 void box_proj_rhs(hipStream_t s, int dim, const BoxCoupling &B, const double *u, int n_comp, const int32_t *tensor_components, double *const *rhs);
-void q1_eig(int n_cells, double h, std::vector<double> &S, std::vector<double> &lam);   // host: generalised eigenpairs of the 1D Q1 stiffness / mass matrices
 // all peers' windows in one launch: block q of the dense side is dense + q blk (to_block: peer `self` goes to dense_self instead - its own block of the receive buffer)
 void fdm_window_batch(hipStream_t s, double *grid, double *dense, double *dense_self, int self, bool to_block, const FdmWindow *win, int n_peers, int n_planes_pad, int64_t C, int64_t grid_stride, int64_t blk);
 void fdm_window(hipStream_t s, double *dst, const double *src, bool to_block, int n_planes, int n_planes_pad, int64_t C, int64_t ncols_valid, int64_t grid_stride, int64_t grid_col0, int64_t grid_plane0);
 void fdm_transform(hipStream_t s, const double *T, int n_l, int64_t SI, int64_t n_outer, const double *in, double *out, const FdmScale *scale);
 void fdm_apply(hipStream_t s, const FdmScalar &F, double a, const double k[3], const double *g, double *z, double *t1, double *t2);
 // ---- kernels_fdmu.hip ---------------------------------------------------------------------------
-double jacobi_scaled_lambda_max(int n, const std::vector<double> &A);
-double sym_lambda_max(int n, const std::vector<double> &A);   // largest eigenvalue of a small dense symmetric matrix
-void fdmu_eig_1d(int k, int n_cells, double h, bool fix_lo, bool fix_hi, std::vector<double> &S, std::vector<double> &lam);
-void fdmu_eig_1d(int k, const std::vector<double> &cell_sizes, bool fix_lo, bool fix_hi, std::vector<double> &S, std::vector<double> &lam);   // the same on a non-uniform 1D grid
-void fdmu_upload_dir(FdmuDir &D, const std::vector<double> &S, const std::vector<double> &lam, int nn, bool single, bool allow_split);   // D.split tells whether the even / odd form was taken
+void fdmu_upload_dir(FdmuDir &D, const LineTables &T, bool single, bool split);   // split: the even / odd form (T.parity required) unless a switch or `single` rules it out; D.split tells
 // stage 2: the whole application (single rank); 0 / 1: the passes of the leading directions before / after the caller's distributed last direction
 void fdmu_apply(hipStream_t s, const FdmU &F, const double *g, double *z, void *t1, void *t2, int stage);
 void fdmu_window(hipStream_t s, double *dst, const double *src, bool to_block, int ncomp, int n_planes, int n_planes_pad, int64_t C, int64_t ncols_valid,
@@ -427,7 +421,7 @@ bool fdmo_usable(int dim, const int nn[3]);          // 3D, half lines of at mos
 void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s);   // sizes + buffers
 // slab-partitioned form: nn = LOCAL nodes; layers[q] = node planes rank q holds minus one (its cell layers x degree); the last direction's matrices are uploaded for the GLOBAL line
 void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int rank, const std::vector<int> &node_layers, bool has_upper, hipStream_t s);
-bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn);
+void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
                 double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr,
@@ -435,7 +429,7 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
 // the same transform kernel for the scalar Q1 systems of a 3D box (nodal layout, one block set, no octants): 3 launches instead of 6
 bool fdmo_scalar_usable(int dim, const int nn[3]);
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s);
-void fdmo_scalar_upload_dir(FdmOct &O, int dir, const std::vector<double> &S, const std::vector<double> &lam, int n);
+void fdmo_scalar_upload_dir(FdmOct &O, int dir, const LineTables &T);
 void fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate = nullptr);
 void fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate = nullptr);   // up to 3 right-hand sides in one set of launches
 // block partials of |y_e - b_e|^2 and |b_e|^2 for up to three (y, b) pairs: sets 2e and 2e + 1 of `partials`
@@ -447,7 +441,7 @@ void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double 
 // planar (2D) form: quadrant layout with one plane and 2 components; four batched GEMM launches per application
 bool fdmo_planar_usable(int dim, const int nn[3]);
 void fdmo_init_planar(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s, bool split = true /* false: different conditions at the two ends of some line - no parity split, full-length transforms */);
-bool fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn);
+void fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required by the split form
 void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g_q, double *z_q, const PcgScalars *gate = nullptr);
 void fdmo_from_nodal(hipStream_t s, const FdmOct &O, const double *v_nodal, double *q_oct);   // q = H v (node-interleaved vector -> octant form)
 void fdmo_to_nodal(hipStream_t s, const FdmOct &O, const double *r_oct, double *v_nodal);     // v = H^-1-form of the backward transform: v_k = a + b, v_k' = a - b

@@ -6,6 +6,7 @@
 #include <vector>
 #include "common.hpp"
 #include "whole_faces.hpp"
+#include "fdm_tables.hpp"
 
 namespace poro {
 namespace ctx_detail {

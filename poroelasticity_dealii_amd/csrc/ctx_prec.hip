@@ -29,18 +29,16 @@ bool fdm_p_supported(poro_ctx *c) {
 // the second table set: the pressure Jacobian with whole prescribed faces (one rank)
 bool fdm_pj_supported(poro_ctx *c) { return c->n_pdir && c->pdir_faces_ok && !c->comm.multi() && fdm_p_supported(c); }
 // The 1D tables of one direction, with or without its end nodes.  Deleting the rows and columns of a face from a M + kappa K deletes the end node of that direction's 1D
-// matrices; fdmu_eig_1d gives their eigenpairs in full-length storage (zero rows of S at removed nodes, zero columns and lam = inf behind the free modes), so the
-// transform kernels run unchanged and return exactly 0 there.
-static void upload_dir(FdmDir &D, const std::vector<double> &hcell, bool uniform, bool fix_lo, bool fix_hi, FdmOct *fused = nullptr, int dir = 0) {
-  const int n = (int)hcell.size() + 1;
-  std::vector<double> S, lam;
-  if (uniform && !fix_lo && !fix_hi) q1_eig(n - 1, hcell[0], S, lam); else fdmu_eig_1d(1, hcell, fix_lo, fix_hi, S, lam);   // (closed form on a uniform line with free ends)
-  if (fused) fdmo_scalar_upload_dir(*fused, dir, S, lam, n);
-  std::vector<double> St((size_t)n * n);
+// matrices; line_tables (fdm_tables.hpp) gives their eigenpairs in full-length storage (zero rows of S at removed nodes, zero columns and lam = inf behind the free
+// modes), so the transform kernels run unchanged and return exactly 0 there.
+static void upload_dir(FdmDir &D, const LineTables &T, FdmOct *fused = nullptr, int dir = 0) {
+  const int n = T.n; const std::vector<double> &S = T.S;
+  if (fused) fdmo_scalar_upload_dir(*fused, dir, T);
+  std::vector<double> St((size_t)n * n), lam = T.lam;
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) St[(size_t)j * n + i] = S[(size_t)i * n + j];
   // six-launch form: its kernel divides by a + sum k_d lam_d.  A removed mode's coefficient is exactly 0 (zero row of S^T), so any finite positive eigenvalue in its
   // place gives the 0 that lam = inf gives, without inf * 0 where a coefficient k_d is 0
-  if (fix_lo || fix_hi) for (double &l : lam) if (!(l < 1e300)) l = 1e300;
+  for (double &l : lam) if (!(l < 1e300)) l = 1e300;
   D.n = n; D.S.upload(S); D.St.upload(St); D.lam.upload(lam);
 }
 // every rank learns all slab thicknesses through the existing all-reduce.  nodes_per_cell: 1 for the Q1 space, k_u for the displacement space; ncol_total: the nodes of one
@@ -75,11 +73,11 @@ static void build_fdm_dist(poro_ctx *c, const int np3[3]) {
     const bool fused_slab = c->dim == 3 && fdmo_scalar_usable(3, np3) && fdmo_scalar_usable(3, g3) && !std::getenv("PORO_FDM_P_UNFUSED");
     if (fused_slab) {
       fdmo_scalar_init_slab(fused, np3, r, F.layers, c->stream);
-      for (int d = 0; d < 2; ++d) { std::vector<double> S, lam; q1_eig(c->box.n[d], c->box.h[d], S, lam); fdmo_scalar_upload_dir(fused, d, S, lam, c->box.n[d] + 1); }
-      std::vector<double> S, lam; q1_eig(acc, c->box.h[last], S, lam); fdmo_scalar_upload_dir(fused, 2, S, lam, acc + 1);
+      for (int d = 0; d < 2; ++d) fdmo_scalar_upload_dir(fused, d, q1_eig(c->box.n[d], c->box.h[d]));
+      fdmo_scalar_upload_dir(fused, 2, q1_eig(acc, c->box.h[last]));
       fused.built = true;
     } }
-  upload_dir(F.last, std::vector<double>((size_t)acc, c->box.h[last]), true, false, false);
+  upload_dir(F.last, q1_eig(acc, c->box.h[last]));
   const size_t blk = (size_t)std::max(F.max_own, F.max_nl) * F.C;
   F.sendbuf.alloc(blk * N); F.recvbuf.alloc(blk * N); F.tz1.alloc((size_t)F.ng * F.C); F.tz2.alloc((size_t)F.ng * F.C);
   F.sendbuf.zero(c->stream); F.recvbuf.zero(c->stream); F.tz1.zero(c->stream); F.tz2.zero(c->stream);
@@ -113,8 +111,10 @@ void build_fdm_q1(poro_ctx *c, Q1Set which) {
   int np3[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, c->dim == 3 ? c->lines.n[2] + 1 : 1};
   const bool fused = !multi && fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
   if (fused) fdmo_scalar_init(T.fused, np3, c->stream);
-  for (int d = 0; d < c->dim; ++d)                                   // (partitioned: the local slab; the last direction is replaced by fdm_dist.last)
-    upload_dir(T.nodal.dir[d], c->lines.hcell[d], c->lines.uniform, fixed && c->pdir_face[d][0], fixed && c->pdir_face[d][1], fused ? &T.fused : nullptr, d);
+  for (int d = 0; d < c->dim; ++d) {                                 // (partitioned: the local slab; the last direction is replaced by fdm_dist.last)
+    const std::vector<double> &hcell = c->lines.hcell[d]; const bool lo = fixed && c->pdir_face[d][0], hi = fixed && c->pdir_face[d][1];
+    upload_dir(T.nodal.dir[d], c->lines.uniform && !lo && !hi ? q1_eig((int)hcell.size(), hcell[0]) : line_tables(1, hcell, lo, hi), fused ? &T.fused : nullptr, d);   // (closed form on a uniform line with free ends)
+  }
   if (!multi) T.fused.built = fused;
   if (c->fdm_t1.n < (size_t)c->n_p) { c->fdm_t1.alloc(c->n_p); c->fdm_t2.alloc(c->n_p); }
   if (multi) build_fdm_dist(c, np3);
@@ -267,43 +267,43 @@ void build_fdm_u(poro_ctx *c) {
     F.sendbuf.alloc(blk * N); F.recvbuf.alloc(blk * N); F.tz1.alloc((size_t)dim * F.ng * F.C); F.tz2.alloc((size_t)dim * F.ng * F.C);
     F.sendbuf.zero(c->stream); F.recvbuf.zero(c->stream); F.tz1.zero(c->stream); F.tz2.zero(c->stream);
   }
+  // eigenpairs per (direction, end conditions); components with the same end conditions share the host work.  same_ends[d]: every component has the same condition at
+  // both ends of direction d; parity[d]: every component's eigenvectors came out even or odd there (they do on a uniform line with the same ends, not on a graded one)
+  LineTables tables[3][4]; bool same_ends[3], parity[3];
+  const auto key_of = [&](int comp, int d) { return F.fix[comp][d][0] * 2 + F.fix[comp][d][1]; };
+  for (int d = 0; d < dim; ++d) {
+    const bool global_dir = multi && d == last;
+    const std::vector<double> hcell = global_dir ? std::vector<double>((size_t)n_cells_last, c->box.h[d]) : c->lines.hcell[d];
+    same_ends[d] = parity[d] = true;
+    for (int comp = 0; comp < dim; ++comp) {
+      LineTables &T = tables[d][key_of(comp, d)];
+      if (!T.n) T = line_tables(ku, hcell, F.fix[comp][d][0], F.fix[comp][d][1]);
+      same_ends[d] = same_ends[d] && F.fix[comp][d][0] == F.fix[comp][d][1]; parity[d] = parity[d] && T.parity;
+    }
+  }
   // octant form (kernels_fdmo.hip): one rank, 3D, every direction mirror-symmetric for every component, half lines of at most 128 entries
   // slab partitions: the quadrant form (x, y split locally; the z butterfly next to the all-to-all) under the same conditions on the GLOBAL line
   bool oct_ok = !F.single && !std::getenv("PORO_FDMU_NO_OCT");
-  bool planar = false, planar_split = true;     // 2D, one rank: the quadrant form with a single plane, transforms as batched GEMMs (lines of any length; without the parity split where the end conditions differ)
+  bool planar = false;     // 2D, one rank: the quadrant form with a single plane, transforms as batched GEMMs (lines of any length; without the parity split where the end conditions differ)
   { int nn3[3] = {F.nn[0], F.nn[1], F.nn[2]}, sym3[3] = {F.nn[0], F.nn[1], multi ? F.ng : F.nn[2]};
     planar = dim == 2 && !multi && fdmo_planar_usable(dim, nn3);
     oct_ok = oct_ok && (planar || fdmo_usable(dim, sym3));
-    bool symmetric = true;
-    for (int d = 0; d < dim; ++d) for (int comp = 0; comp < dim; ++comp) symmetric = symmetric && F.fix[comp][d][0] == F.fix[comp][d][1];
-    planar_split = symmetric;
-    if (!planar) oct_ok = oct_ok && symmetric;      // (the planar form also runs without the parity split; the 3D forms need it)
-    if (oct_ok && planar) fdmo_init_planar(c->fdm_oct, nn3, F.coef, c->stream, planar_split);
+    bool symmetric = true, all_parity = true;
+    for (int d = 0; d < dim; ++d) { symmetric = symmetric && same_ends[d]; all_parity = all_parity && parity[d]; }
+    // the planar form also runs without the parity split; its split form and the 3D forms need the same ends everywhere and eigenvectors that are all even or odd
+    oct_ok = oct_ok && ((planar && !symmetric) || (symmetric && all_parity));
+    if (oct_ok && planar) fdmo_init_planar(c->fdm_oct, nn3, F.coef, c->stream, symmetric);
     else if (oct_ok && !multi) fdmo_init(c->fdm_oct, nn3, F.coef, c->stream);
     if (oct_ok && multi) { std::vector<int> node_layers(F.n_ranks); for (int q = 0; q < F.n_ranks; ++q) node_layers[q] = ku * F.layers[q];
                            fdmo_init_slab(c->fdm_oct, nn3, F.coef, F.rank, node_layers, c->comm.part.has_upper != 0, c->stream); } }
-  // eigenpairs per (direction, end conditions); components with the same end conditions share the host work.  A direction takes the even / odd
-  // form (half the MFMA work) when every component has the same condition at both ends there - all components of a pass share one kernel
-  for (int d = 0; d < dim; ++d) {
-    std::vector<double> S[4], lam[4]; bool have[4] = {false, false, false, false};
+  // A direction takes the even / odd form of the nodal kernels (half the MFMA work) when it has the same ends and the parity for every component - all components
+  // of a pass share one kernel
+  for (int d = 0; d < dim; ++d) for (int comp = 0; comp < dim; ++comp) {
     const bool global_dir = multi && d == last;
-    const int ncell = global_dir ? n_cells_last : c->lines.n[d], nnode = ku * ncell + 1;
-    const std::vector<double> hcell = global_dir ? std::vector<double>((size_t)ncell, c->box.h[d]) : c->lines.hcell[d];
-    bool allow_split = true;
-    for (int comp = 0; comp < dim; ++comp) allow_split = allow_split && F.fix[comp][d][0] == F.fix[comp][d][1];
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      bool all_split = true;
-      for (int comp = 0; comp < dim; ++comp) {
-        const int key = F.fix[comp][d][0] * 2 + F.fix[comp][d][1];
-        if (!have[key]) { fdmu_eig_1d(ku, hcell, F.fix[comp][d][0], F.fix[comp][d][1], S[key], lam[key]); have[key] = true; }
-        FdmuDir &D = global_dir ? F.last_global[comp] : F.dir[comp][d];
-        if (!(planar && oct_ok && nnode > 320 && !allow_split)) fdmu_upload_dir(D, S[key], lam[key], nnode, global_dir ? false : F.single, allow_split);   // (the nodal kernels have no full-length form beyond 320 points; the planar form does not need them)
-        all_split = all_split && D.split;
-        if (oct_ok && attempt == 0) oct_ok = planar ? fdmo_upload_dir_planar(c->fdm_oct, comp, d, S[key], lam[key], nnode) : fdmo_upload_dir(c->fdm_oct, comp, d, S[key], lam[key], nnode);
-      }
-      if (!allow_split || all_split) break;
-      allow_split = false;                       // the numerical symmetry check failed for some component: the whole direction in the full form
-    }
+    const LineTables &T = tables[d][key_of(comp, d)];
+    FdmuDir &D = global_dir ? F.last_global[comp] : F.dir[comp][d];
+    if (!(planar && oct_ok && T.n > 320 && !same_ends[d])) fdmu_upload_dir(D, T, global_dir ? false : F.single, same_ends[d] && parity[d]);   // (the nodal kernels have no full-length form beyond 320 points; the planar form does not need them)
+    if (oct_ok) { if (planar) fdmo_upload_dir_planar(c->fdm_oct, comp, d, T); else fdmo_upload_dir(c->fdm_oct, comp, d, T); }
   }
   c->fdmu_t1.alloc(c->n_u); c->fdmu_t2.alloc(c->n_u); c->fdmu_t1.zero(c->stream); c->fdmu_t2.zero(c->stream);   // (only finite values ever live in the scratch arrays)
   if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }

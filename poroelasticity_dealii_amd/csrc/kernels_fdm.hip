@@ -191,27 +191,5 @@ void fdm_apply(hipStream_t s, const FdmScalar &F, double a, const double k[3], c
   }
 }
 
-// ---- host side: K1 s = lam M1 s for the 1D Q1 matrices on n cells of size h (natural boundary conditions) ---------------------------
-// M1 = h/6 tridiag(1 4 1) (corners 2), K1 = 1/h tridiag(-1 2 -1) (corners 1): the eigenvectors are the cosines s_j(i) = cos(j pi i / n),
-// lam_j = 6/h^2 (1 - cos t)/(2 + cos t), t = j pi / n (insert into an interior and a boundary row); columns scaled to s^T M1 s = 1.
-void q1_eig(int n_cells, double h, std::vector<double> &S, std::vector<double> &lam) {
-  const int n = n_cells + 1; const double pi = 3.14159265358979323846;
-  S.assign((size_t)n * n, 0.0); lam.assign(n, 0.0);
-  std::vector<double> v(n);
-  for (int j = 0; j < n; ++j) {
-    const double t = j * pi / n_cells, ct = std::cos(t);
-    lam[j] = 6.0 / (h * h) * (1.0 - ct) / (2.0 + ct);
-    for (int i = 0; i < n; ++i) v[i] = std::cos(t * i);
-    double m = 0;
-    for (int i = 0; i < n; ++i) {
-      double Mv = (i > 0 && i < n - 1 ? 4.0 : 2.0) * v[i];
-      if (i > 0) Mv += v[i - 1];
-      if (i < n - 1) Mv += v[i + 1];
-      m += v[i] * Mv * h / 6.0;
-    }
-    const double sc = 1.0 / std::sqrt(m);
-    for (int i = 0; i < n; ++i) S[(size_t)i * n + j] = v[i] * sc;
-  }
-}
 
 }  // namespace poro

@@ -21,6 +21,7 @@
 // Y = T X, wave s owns output row tile s, data = B operand; either way the accumulator of tile (T, W) holds element (16 T + 4 q + kq, 16 W + j) in
 // register q of lane j + 16 kq, so one store routine serves both.
 #include "common.hpp"
+#include "fdm_tables.hpp"
 #include "device_reduce.hpp"
 #include <hip/hip_ext.h>
 #include <cmath>
@@ -1075,16 +1076,6 @@ struct PassStamps {
     if (f) std::fclose(f);
   }
 };
-// a rows x cols matrix el(r, c) in MFMA fragment order [tile][4 NT][64]: lane l of fragment (tile, kk) holds element (16 tile + (l & 15), 4 kk + (l >> 4)); zero beyond
-template <class El> std::vector<double> pack_fragments(int nt, int rows, int cols, El el) {
-  const int kkp = 4 * nt;
-  std::vector<double> M((size_t)nt * kkp * 64, 0.0);
-  for (int t = 0; t < nt; ++t) for (int kk = 0; kk < kkp; ++kk) for (int l = 0; l < 64; ++l) {
-    const int r = 16 * t + (l & 15), c = 4 * kk + (l >> 4);
-    if (r < rows && c < cols) M[((size_t)t * kkp + kk) * 64 + l] = el(r, c);
-  }
-  return M;
-}
 // sizes of a 3D form: half lines in the first `nsplit` directions (parity split, `no` parity parts), whole lines in the others; rows padded to even length where x is split.
 // On slabs (slab_prologue first) the transformed z line is the global one, split in parities whenever x and y are.  coef != null (displacement system): g, z, t in the form's layout
 void form_geometry(FdmOct &O, const int nn[3], const double (*coef)[3], int nsplit, int no, hipStream_t s) {
@@ -1165,30 +1156,24 @@ void fdmo_scalar_init_slab(FdmOct &O, const int nn[3], int rank, const std::vect
   slab_layout(O, 1, 1, rank, node_layers, s);
 }
 
-bool fdmo_upload_dir(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn) {
-  const int h = (nn + 1) / 2, nt = O.nt, padn = 16 * nt;
+void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T) {
+  const int nn = T.n, h = (nn + 1) / 2, nt = O.nt, padn = 16 * nt;
+  const std::vector<double> &S = T.S, &lam = T.lam;
   if (nn != (O.slab.on && dir == 2 ? O.slab.ng : O.n[dir])) throw Error("fdmo_upload_dir: line length mismatch");
-  std::vector<int> grp[2];
-  for (int m = 0; m < nn; ++m) {
-    if (!(lam[m] < 1e300)) continue;              // removed modes
-    double ds = 0, da = 0, nrm = 0;
-    for (int k = 0; k < nn; ++k) { const double a = S[(size_t)k * nn + m], b = S[(size_t)(nn - 1 - k) * nn + m]; ds += (a - b) * (a - b); da += (a + b) * (a + b); nrm += a * a; }
-    if (ds <= 1e-20 * nrm) grp[0].push_back(m); else if (da <= 1e-20 * nrm) grp[1].push_back(m); else return false;
-  }
+  if (!T.parity) throw Error("fdmo_upload_dir: tables whose modes are not all even or odd");      // (the caller decides the form from T.parity before any upload)
+  const std::vector<int> *const grp[2] = {&T.even, &T.odd};
   for (int p = 0; p < 2; ++p) {
-    if ((int)grp[p].size() > h) return false;
     // forward F[m][k] = S[k][mode m] (rows = modes of the parity group, columns = lower-half nodes), backward B[k][m] = S[k][mode m]
-    const int ng = (int)grp[p].size();
-    const std::vector<double> F = pack_fragments(nt, ng, h, [&](int r, int cc) { return S[(size_t)cc * nn + grp[p][r]]; }), B = pack_fragments(nt, h, ng, [&](int r, int cc) { return S[(size_t)r * nn + grp[p][cc]]; });
+    const std::vector<int> &g = *grp[p]; const int ng = (int)g.size();
+    const std::vector<double> F = pack_fragments<double>(nt, 4 * nt, ng, h, [&](int r, int cc) { return S[(size_t)cc * nn + g[r]]; }), B = pack_fragments<double>(nt, 4 * nt, h, ng, [&](int r, int cc) { return S[(size_t)r * nn + g[cc]]; });
     std::vector<double> lp(padn + 16, std::numeric_limits<double>::infinity());
-    for (int m = 0; m < ng; ++m) lp[m] = lam[grp[p][m]];
+    for (int m = 0; m < ng; ++m) lp[m] = lam[g[m]];
     O.h_lam[comp][dir][p] = lp;
     O.fwd[comp][dir][p].upload(F); O.bwd[comp][dir][p].upload(B); O.lam[comp][dir][p].upload(lp);
     if (!O.slab.on) {   // fp32 mode of the octant form: both matrices rounded entry by entry from the same S, so the backward one is the exact transpose of the rounded forward one
       O.fwd32[comp][dir][p].upload(std::vector<float>(F.begin(), F.end())); O.bwd32[comp][dir][p].upload(std::vector<float>(B.begin(), B.end()));
     }
   }
-  return true;
 }
 
 void fdmo_finalize(FdmOct &O) {
@@ -1252,12 +1237,13 @@ void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s) {
   form_geometry(O, nn, nullptr, 0, 1, s);
   O.t.alloc(3 * O.n_oct); O.t.zero(s);      // (scratch for up to three right-hand sides at once)
 }
-void fdmo_scalar_upload_dir(FdmOct &O, int dir, const std::vector<double> &S, const std::vector<double> &lam, int n) {   // S: n x n row-major, columns = M-orthonormal eigenvectors
+void fdmo_scalar_upload_dir(FdmOct &O, int dir, const LineTables &T) {
+  const int n = T.n; const std::vector<double> &S = T.S, &lam = T.lam;
   if (n != (O.slab.on && dir == 2 ? O.slab.ng : O.n[dir])) throw Error("fdmo_scalar_upload_dir: line length mismatch");
   std::vector<double> lp(16 * O.nt + 16, std::numeric_limits<double>::infinity());
   for (int m = 0; m < n; ++m) lp[m] = lam[m];
   O.h_lam[0][dir][0] = lp; O.lam[0][dir][0].upload(lp);
-  O.fwd[0][dir][0].upload(pack_fragments(O.nt, n, n, [&](int r, int cc) { return S[(size_t)cc * n + r]; })); O.bwd[0][dir][0].upload(pack_fragments(O.nt, n, n, [&](int r, int cc) { return S[(size_t)r * n + cc]; }));
+  O.fwd[0][dir][0].upload(pack_fragments<double>(O.nt, 4 * O.nt, n, n, [&](int r, int cc) { return S[(size_t)cc * n + r]; })); O.bwd[0][dir][0].upload(pack_fragments<double>(O.nt, 4 * O.nt, n, n, [&](int r, int cc) { return S[(size_t)r * n + cc]; }));
 }
 static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kappa);
 // z = (a M + kappa K)^-1 g; the x / y share a + kappa (lam_x + lam_y) of the eigenvalue sums is tabulated per plane position, one table per (a, kappa)
@@ -1312,30 +1298,24 @@ void fdmo_init_planar(FdmOct &O, const int nn[3], const double coef[3][3], hipSt
   O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(2 * O.n_oct);
   O.g.zero(s); O.z.zero(s); O.t.zero(s);
 }
-bool fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const std::vector<double> &S, const std::vector<double> &lam, int nn) {
+void fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const LineTables &T) {
+  const int nn = T.n; const std::vector<double> &S = T.S, &lam = T.lam;
   if (nn != O.n[dir]) throw Error("fdmo_upload_dir_planar: line length mismatch");
   if (O.no == 1) {          // no parity split (different conditions at the two ends of a line): the full transform F[mode][node], modes that do not exist carry lam = inf
     std::vector<double> F((size_t)nn * nn, 0.0), lp((size_t)nn + 16, std::numeric_limits<double>::infinity());
     for (int m = 0; m < nn; ++m) { if (!(lam[m] < 1e300)) continue; for (int k = 0; k < nn; ++k) F[(size_t)m * nn + k] = S[(size_t)k * nn + m]; lp[m] = lam[m]; }
     O.h_lam[comp][dir][0] = lp; O.fwd[comp][dir][0].upload(F); O.lam[comp][dir][0].upload(lp);
-    return true;
+    return;
   }
   const int h = (nn + 1) / 2;
-  std::vector<int> grp[2];
-  for (int m = 0; m < nn; ++m) {
-    if (!(lam[m] < 1e300)) continue;
-    double ds = 0, da = 0, nrm = 0;
-    for (int k = 0; k < nn; ++k) { const double a = S[(size_t)k * nn + m], b = S[(size_t)(nn - 1 - k) * nn + m]; ds += (a - b) * (a - b); da += (a + b) * (a + b); nrm += a * a; }
-    if (ds <= 1e-20 * nrm) grp[0].push_back(m); else if (da <= 1e-20 * nrm) grp[1].push_back(m); else return false;
-  }
+  if (!T.parity) throw Error("fdmo_upload_dir_planar: tables whose modes are not all even or odd");
+  const std::vector<int> *const grp[2] = {&T.even, &T.odd};
   for (int p = 0; p < 2; ++p) {
-    if ((int)grp[p].size() > h) return false;
     std::vector<double> F((size_t)h * h, 0.0), lp((size_t)h + 16, std::numeric_limits<double>::infinity());
-    const int ng = (int)grp[p].size();
-    for (int m = 0; m < ng; ++m) { for (int k = 0; k < h; ++k) F[(size_t)m * h + k] = S[(size_t)k * nn + grp[p][m]]; lp[m] = lam[grp[p][m]]; }
+    const std::vector<int> &g = *grp[p]; const int ng = (int)g.size();
+    for (int m = 0; m < ng; ++m) { for (int k = 0; k < h; ++k) F[(size_t)m * h + k] = S[(size_t)k * nn + g[m]]; lp[m] = lam[g[m]]; }
     O.h_lam[comp][dir][p] = lp; O.fwd[comp][dir][p].upload(F); O.lam[comp][dir][p].upload(lp);
   }
-  return true;
 }
 // z = blockdiag(A_cc)^-1 g in quadrant form: T = X Fx^T, U = (Fy T) / (cx lam_x + cy lam_y), V = Fy^T U, Z = V Fx  - four batched GEMMs over the 8 (component, quadrant) planes
 void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g, double *z, const PcgScalars *gate) {

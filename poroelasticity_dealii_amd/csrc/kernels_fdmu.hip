@@ -20,6 +20,7 @@
 // data are component-planar.  Passes: x, y, z (forward + scaling + backward fused), y, x  = 5 sweeps over the vector in 3D.
 // Rows / columns of constrained end nodes are zero in S, so z = 0 on Dirichlet dofs (they are inert inside PCG anyway).
 #include "common.hpp"
+#include "fdm_tables.hpp"
 #include <cmath>
 #include <limits>
 #include <type_traits>
@@ -624,297 +625,63 @@ void launch_pass(hipStream_t s, const FdmuPass &P, const TIn *in, TOut *out) {
 #undef PORO_FDMU_CASE
 }
 
-// ---- host: 1D matrices, generalised eigen-decomposition ------------------------------------------------------------------------
-// symmetric eigenproblem by cyclic Jacobi rotations (n <= 320: a few 1e8 flop, once per mesh); V's columns are the eigenvectors
-void jacobi_eig(int n, std::vector<double> &A, std::vector<double> &V, std::vector<double> &w) {
-  V.assign((size_t)n * n, 0.0); for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0, diag = 0;
-    for (int i = 0; i < n; ++i) { diag += A[(size_t)i * n + i] * A[(size_t)i * n + i]; for (int j = i + 1; j < n; ++j) off += A[(size_t)i * n + j] * A[(size_t)i * n + j]; }
-    if (off <= 1e-30 * diag || off == 0) break;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = A[(size_t)p * n + q];
-        if (std::fabs(apq) < 1e-300) continue;
-        const double app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-        for (int k = 0; k < n; ++k) {   // columns p, q
-          const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-          A[(size_t)k * n + p] = cs * akp - sn * akq; A[(size_t)k * n + q] = sn * akp + cs * akq;
-        }
-        for (int k = 0; k < n; ++k) {   // rows p, q
-          const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-          A[(size_t)p * n + k] = cs * apk - sn * aqk; A[(size_t)q * n + k] = sn * apk + cs * aqk;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
-          V[(size_t)k * n + p] = cs * vkp - sn * vkq; V[(size_t)k * n + q] = sn * vkp + cs * vkq;
-        }
-      }
-  }
-  w.resize(n); for (int i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
-}
-
-// symmetric eigenproblem by Householder tridiagonalisation + implicit QL with accumulated transformations (the classical tred2 / tql2 pair):
-// O(n^3) with a small constant, for the long lines (n = 671 in BASELINE config 2) where the Jacobi sweeps above would take minutes.
-// A is overwritten; V's columns are the eigenvectors.
-void householder_ql_eig(int n, std::vector<double> &A, std::vector<double> &V, std::vector<double> &w) {
-  std::vector<double> d(n, 0.0), e(n, 0.0);
-  auto a = [&](int i, int j) -> double & { return A[(size_t)i * n + j]; };
-  for (int i = n - 1; i > 0; --i) {
-    const int l = i - 1; double h = 0, scale = 0;
-    if (l > 0) {
-      for (int k = 0; k <= l; ++k) scale += std::fabs(a(i, k));
-      if (scale == 0.0) e[i] = a(i, l);
-      else {
-        for (int k = 0; k <= l; ++k) { a(i, k) /= scale; h += a(i, k) * a(i, k); }
-        double f = a(i, l), g = f >= 0.0 ? -std::sqrt(h) : std::sqrt(h);
-        e[i] = scale * g; h -= f * g; a(i, l) = f - g; f = 0.0;
-        for (int j = 0; j <= l; ++j) {
-          a(j, i) = a(i, j) / h;
-          g = 0.0;
-          for (int k = 0; k <= j; ++k) g += a(j, k) * a(i, k);
-          for (int k = j + 1; k <= l; ++k) g += a(k, j) * a(i, k);
-          e[j] = g / h; f += e[j] * a(i, j);
-        }
-        const double hh = f / (h + h);
-        for (int j = 0; j <= l; ++j) {
-          f = a(i, j); e[j] = g = e[j] - hh * f;
-          for (int k = 0; k <= j; ++k) a(j, k) -= f * e[k] + g * a(i, k);
-        }
-      }
-    } else e[i] = a(i, l);
-    d[i] = h;
-  }
-  d[0] = 0.0; e[0] = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const int l = i - 1;
-    if (d[i] != 0.0)
-      for (int j = 0; j <= l; ++j) {
-        double g = 0.0;
-        for (int k = 0; k <= l; ++k) g += a(i, k) * a(k, j);
-        for (int k = 0; k <= l; ++k) a(k, j) -= g * a(k, i);
-      }
-    d[i] = a(i, i); a(i, i) = 1.0;
-    for (int j = 0; j <= l; ++j) a(j, i) = a(i, j) = 0.0;
-  }
-  for (int i = 1; i < n; ++i) e[i - 1] = e[i];
-  e[n - 1] = 0.0;
-  for (int l = 0; l < n; ++l) {
-    int iter = 0, m;
-    do {
-      for (m = l; m < n - 1; ++m) { const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]); if (std::fabs(e[m]) <= 1e-16 * dd) break; }
-      if (m != l) {
-        if (iter++ == 200) throw Error("householder_ql_eig: no convergence");
-        double g = (d[l + 1] - d[l]) / (2.0 * e[l]), r = std::hypot(g, 1.0);
-        g = d[m] - d[l] + e[l] / (g + (g >= 0.0 ? std::fabs(r) : -std::fabs(r)));
-        double sn = 1.0, cs = 1.0, p = 0.0; int i;
-        for (i = m - 1; i >= l; --i) {
-          double f = sn * e[i]; const double b = cs * e[i];
-          e[i + 1] = (r = std::hypot(f, g));
-          if (r == 0.0) { d[i + 1] -= p; e[m] = 0.0; break; }
-          sn = f / r; cs = g / r; g = d[i + 1] - p;
-          r = (d[i] - g) * sn + 2.0 * cs * b;
-          d[i + 1] = g + (p = sn * r); g = cs * r - b;
-          for (int k = 0; k < n; ++k) { f = a(k, i + 1); a(k, i + 1) = sn * a(k, i) + cs * f; a(k, i) = cs * a(k, i) - sn * f; }
-        }
-        if (r == 0.0 && i >= l) continue;
-        d[l] -= p; e[l] = g; e[m] = 0.0;
-      }
-    } while (m != l);
-  }
-  V = A; w = d;
-}
-
-// FE_Q(k) mass / stiffness matrices of n_cells cells of length h (dense, nn = k n_cells + 1); element matrices as in kernels_kron.hip
-void fe1d(int k, const std::vector<double> &hc, std::vector<double> &M, std::vector<double> &K) {
-  const int n_cells = (int)hc.size(), nn = k * n_cells + 1; M.assign((size_t)nn * nn, 0.0); K.assign((size_t)nn * nn, 0.0);
-  static const double M2[3][3] = {{4, 2, -1}, {2, 16, 2}, {-1, 2, 4}}, K2[3][3] = {{7, -8, 1}, {-8, 16, -8}, {1, -8, 7}};
-  static const double M1[2][2] = {{2, 1}, {1, 2}}, K1[2][2] = {{1, -1}, {-1, 1}};
-  for (int c = 0; c < n_cells; ++c)
-    for (int a = 0; a <= k; ++a) for (int b = 0; b <= k; ++b) {
-      const size_t at = (size_t)(k * c + a) * nn + (k * c + b);
-      const double h = hc[c];
-      if (k == 2) { M[at] += h / 30.0 * M2[a][b]; K[at] += K2[a][b] / (3.0 * h); } else { M[at] += h / 6.0 * M1[a][b]; K[at] += K1[a][b] / h; }
+// ---- host: the tables of one line (fdm_tables.hpp) in the fragment orders of the kernels above ------------------------------------------------
+// full-length forms, S^T forward and S backward.  Register form (k_fdmu_reg): chunked order [chunk][k-step u][tile pair p][lane][2] with tile 2p + e of the one
+// matrix in entry e; LDS form (k_fdmu_pass): [MT][KK][64] in the precision of the transforms
+void upload_full(FdmuDir &D, const LineTables &T, bool single) {
+  const int nn = T.n; const std::vector<double> &S = T.S;
+  auto fwd = [&](int r, int c) { return S[(size_t)c * nn + r]; };
+  auto bwd = [&](int r, int c) { return S[(size_t)r * nn + c]; };
+  if (D.reg_form) {
+    const int nch = reg_nch(nn), mtp = (nch + 1) / 2;
+    auto tile = [](int, int p, int e) { return 2 * p + e; };
+    D.fwd.upload(pack_paired_chunks(1, nch, mtp, tile, [&](int r, int c, int) { return r < nn && c < nn ? fwd(r, c) : 0.0; }));
+    D.bwd.upload(pack_paired_chunks(1, nch, mtp, tile, [&](int r, int c, int) { return r < nn && c < nn ? bwd(r, c) : 0.0; }));
+  } else {
+    const int MT = (nn + 15) / 16, KK = (nn + 3) / 4;
+    if (single) {       // (64 floats per fragment: the buffers of doubles hold them exactly)
+      const std::vector<float> f = pack_fragments<float>(MT, KK, nn, nn, fwd), b = pack_fragments<float>(MT, KK, nn, nn, bwd);
+      D.fwd.upload(reinterpret_cast<const double *>(f.data()), f.size() / 2); D.bwd.upload(reinterpret_cast<const double *>(b.data()), b.size() / 2);
     }
-}
-
-}  // namespace
-
-// generalised eigenpairs K s = lam M s of the 1D FE_Q(k) matrices with the end nodes lo / hi removed when fix_lo / fix_hi:
-// S (nn x nn row-major, S^T M S = I on the free block, zero rows for removed nodes, zero columns behind the n_free modes), lam (inf behind n_free)
-void fdmu_eig_1d(int k, int n_cells, double h, bool fix_lo, bool fix_hi, std::vector<double> &S, std::vector<double> &lam) {
-  fdmu_eig_1d(k, std::vector<double>((size_t)n_cells, h), fix_lo, fix_hi, S, lam);
-}
-void fdmu_eig_1d(int k, const std::vector<double> &hc, bool fix_lo, bool fix_hi, std::vector<double> &S, std::vector<double> &lam) {
-  const int n_cells = (int)hc.size();
-  std::vector<double> M, K; fe1d(k, hc, M, K);
-  const int nn = k * n_cells + 1, f0 = fix_lo ? 1 : 0, nf = nn - f0 - (fix_hi ? 1 : 0);
-  S.assign((size_t)nn * nn, 0.0); lam.assign(nn, std::numeric_limits<double>::infinity());
-  if (nf <= 0) return;
-  // Cholesky M_ff = L L^T, C = L^-1 K_ff L^-T, C = Q W Q^T, S_ff = L^-T Q
-  std::vector<double> Lc((size_t)nf * nf, 0.0), C((size_t)nf * nf);
-  for (int i = 0; i < nf; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double s = M[(size_t)(i + f0) * nn + (j + f0)];
-      for (int p = 0; p < j; ++p) s -= Lc[(size_t)i * nf + p] * Lc[(size_t)j * nf + p];
-      if (i == j) { if (!(s > 0)) throw Error("fdmu_eig_1d: mass matrix not positive definite"); Lc[(size_t)i * nf + i] = std::sqrt(s); }
-      else Lc[(size_t)i * nf + j] = s / Lc[(size_t)j * nf + j];
-    }
-  // X = L^-1 K_ff (forward substitution on columns), C = X L^-T = (L^-1 X^T)^T
-  std::vector<double> X((size_t)nf * nf);
-  for (int col = 0; col < nf; ++col)
-    for (int i = 0; i < nf; ++i) {
-      double s = K[(size_t)(i + f0) * nn + (col + f0)];
-      for (int p = 0; p < i; ++p) s -= Lc[(size_t)i * nf + p] * X[(size_t)p * nf + col];
-      X[(size_t)i * nf + col] = s / Lc[(size_t)i * nf + i];
-    }
-  for (int row = 0; row < nf; ++row)         // solve L y = X[row, :]^T  ->  C[:, row] = y
-    for (int i = 0; i < nf; ++i) {
-      double s = X[(size_t)row * nf + i];
-      for (int p = 0; p < i; ++p) s -= Lc[(size_t)i * nf + p] * C[(size_t)p * nf + row];
-      C[(size_t)i * nf + row] = s / Lc[(size_t)i * nf + i];
-    }
-  for (int i = 0; i < nf; ++i) for (int j = i + 1; j < nf; ++j) { const double a = 0.5 * (C[(size_t)i * nf + j] + C[(size_t)j * nf + i]); C[(size_t)i * nf + j] = C[(size_t)j * nf + i] = a; }
-  std::vector<double> Q, wv;
-  if (nf > 96) householder_ql_eig(nf, C, Q, wv); else jacobi_eig(nf, C, Q, wv);
-  for (int j = 0; j < nf; ++j) {             // back substitution L^T s = q_j
-    std::vector<double> sv(nf);
-    for (int i = nf - 1; i >= 0; --i) {
-      double s = Q[(size_t)i * nf + j];
-      for (int p = i + 1; p < nf; ++p) s -= Lc[(size_t)p * nf + i] * sv[p];
-      sv[i] = s / Lc[(size_t)i * nf + i];
-    }
-    for (int i = 0; i < nf; ++i) S[(size_t)(i + f0) * nn + j] = sv[i];
-    lam[j] = std::max(wv[j], 0.0);
+    else { D.fwd.upload(pack_fragments<double>(MT, KK, nn, nn, fwd)); D.bwd.upload(pack_fragments<double>(MT, KK, nn, nn, bwd)); }
   }
-  // the same condition at both ends: M and K are persymmetric, every eigenvector is symmetric or antisymmetric about the centre up to the rounding of
-  // the eigen-solver (1e-9 for the clustered top of a 671-point spectrum).  Make that exact - the even / odd transform kernels rely on it - and restore
-  // the M-normalisation.
-  if (fix_lo == fix_hi)
-    for (int j = 0; j < nf; ++j) {
-      double ds = 0, da = 0;
-      for (int k = 0; k < nn; ++k) { const double a = S[(size_t)k * nn + j], b = S[(size_t)(nn - 1 - k) * nn + j]; ds += (a - b) * (a - b); da += (a + b) * (a + b); }
-      const double sgn = ds <= da ? 1.0 : -1.0;
-      if (std::min(ds, da) > 1e-8 * std::max(ds, da)) continue;         // (not the expected structure: left alone, the full-length kernels take over)
-      for (int k = 0; k < nn / 2; ++k) {
-        const double a = S[(size_t)k * nn + j], b = S[(size_t)(nn - 1 - k) * nn + j], v = 0.5 * (a + sgn * b);
-        S[(size_t)k * nn + j] = v; S[(size_t)(nn - 1 - k) * nn + j] = sgn * v;
-      }
-      if ((nn & 1) && sgn < 0) S[(size_t)(nn / 2) * nn + j] = 0.0;
-      double nrm = 0;
-      for (int i = 0; i < nn; ++i) { double t = 0; for (int p = std::max(0, i - 2 * k); p <= std::min(nn - 1, i + 2 * k); ++p) t += M[(size_t)i * nn + p] * S[(size_t)p * nn + j]; nrm += S[(size_t)i * nn + j] * t; }
-      const double sc = 1.0 / std::sqrt(nrm);
-      for (int i = 0; i < nn; ++i) S[(size_t)i * nn + j] *= sc;
-    }
+  D.lam.upload(T.lam);
 }
-
-double sym_lambda_max(int n, const std::vector<double> &A) {
-  std::vector<double> B = A, V, w; jacobi_eig(n, B, V, w);
-  double m = 0; for (double v : w) m = std::max(m, v);
-  return m;
-}
-// largest eigenvalue of D^-1/2 A D^-1/2 for a small dense symmetric matrix (row-major n x n), D = diag(A): the rigorous element-level bound
-// lambda_max(D^-1 A_global) <= max_e lambda_max(diag(A_e)^-1 A_e) of the Chebyshev preconditioner
-double jacobi_scaled_lambda_max(int n, const std::vector<double> &A) {
-  std::vector<double> B((size_t)n * n), V, w;
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) B[(size_t)i * n + j] = 0.5 * (A[(size_t)i * n + j] + A[(size_t)j * n + i]) / std::sqrt(A[(size_t)i * n + i] * A[(size_t)j * n + j]);
-  jacobi_eig(n, B, V, w);
-  double m = 0; for (double v : w) m = std::max(m, v);
-  return m;
-}
-
-namespace {
-// MFMA A-fragment order of the (nn x nn) matrix Tm (row-major; transposed access when `transpose`): [MT][KK][64], lane -> row 16 mt + (lane & 15), column 4 kk + (lane >> 4)
-template <class TC> void upload_fragments(DevBuf<double> &dst, const std::vector<double> &Tm, int nn, bool transpose) {
-  const int MT = (nn + 15) / 16, KK = (nn + 3) / 4;
-  std::vector<TC> f((size_t)MT * KK * 64, (TC)0);
-  for (int mt = 0; mt < MT; ++mt) for (int kk = 0; kk < KK; ++kk) for (int l = 0; l < 64; ++l) {
-    const int r = 16 * mt + (l & 15), cc = 4 * kk + (l >> 4);
-    if (r < nn && cc < nn) f[((size_t)mt * KK + kk) * 64 + l] = (TC)(transpose ? Tm[(size_t)cc * nn + r] : Tm[(size_t)r * nn + cc]);
-  }
-  const size_t bytes = f.size() * sizeof(TC);
-  dst.alloc((bytes + 7) / 8);
-  PORO_HIP(hipMemcpy(dst.p, f.data(), bytes, hipMemcpyHostToDevice));
-}
-}  // namespace
-
-// chunked order of k_fdmu_reg: [chunk][k-step u][tile pair p][lane][2]; lane -> row 16 (2p + e) + (lane & 15), column 4 (4 chunk + u) + (lane >> 4)
-static void upload_chunked(DevBuf<double> &dst, const std::vector<double> &Tm, int nn, bool transpose) {
-  const int nch = reg_nch(nn), mtp = (nch + 1) / 2;
-  std::vector<double> f((size_t)nch * 4 * mtp * 128, 0.0);
-  for (int ch = 0; ch < nch; ++ch) for (int u = 0; u < 4; ++u) for (int p = 0; p < mtp; ++p) for (int l = 0; l < 64; ++l) for (int e = 0; e < 2; ++e) {
-    const int r = 16 * (2 * p + e) + (l & 15), cc = 4 * (4 * ch + u) + (l >> 4);
-    if (r < nn && cc < nn) f[(((size_t)(ch * 4 + u) * mtp + p) * 64 + l) * 2 + e] = transpose ? Tm[(size_t)cc * nn + r] : Tm[(size_t)r * nn + cc];
-  }
-  dst.upload(f);
-}
-
-// even / odd form: classify the eigenvectors by their symmetry about the centre, pack the half-size matrices in the chunked pair order of k_fdmu_split
-// ([chunk][k-step u][tile p][lane][2]: element 0 = even product, 1 = odd product; lane -> row 16 p + (lane & 15), column 4 (4 chunk + u) + (lane >> 4))
-static bool upload_split(FdmuDir &D, const std::vector<double> &S, const std::vector<double> &lam, int nn) {
-  const int nch = split_nch(nn);
-  const int h = (nn + 1) / 2;
-  std::vector<int> even, odd;
-  for (int m = 0; m < nn; ++m) {
-    if (!(lam[m] < 1e300)) continue;              // removed modes
-    double ds = 0, da = 0, nrm = 0;
-    for (int k = 0; k < nn; ++k) { const double a = S[(size_t)k * nn + m], b = S[(size_t)(nn - 1 - k) * nn + m]; ds += (a - b) * (a - b); da += (a + b) * (a + b); nrm += a * a; }
-    if (ds <= 1e-20 * nrm) even.push_back(m); else if (da <= 1e-20 * nrm) odd.push_back(m); else return false;
-  }
-  const int ne = (int)even.size(), no = (int)odd.size();
-  std::vector<double> lp(nn, std::numeric_limits<double>::infinity());
-  for (int i = 0; i < ne; ++i) lp[i] = lam[even[i]];
-  for (int i = 0; i < no; ++i) lp[ne + i] = lam[odd[i]];
-  if (!nch) {
-    // long lines: blocked packing of k_fdmu_blk, [row block][chunk][k-step u][tile p][lane][2] with 80 rows per parity and block
+// even / odd form: the half-size matrices of the two parity groups side by side (entry 0 = even product, 1 = odd product).  Forward: rows = modes of the group,
+// columns = lower-half nodes; backward: rows = lower-half nodes, columns = modes.  k_fdmu_split: [chunk][k-step u][tile p][lane][2]; lines too long for it:
+// the blocked order of k_fdmu_blk, [row block][chunk][k-step u][tile p][lane][2] with 80 rows per parity and block
+void upload_split(FdmuDir &D, const LineTables &T) {
+  if (!T.parity) throw Error("fdmu_upload_dir: the even / odd form needs tables whose modes are all even or odd");      // (then a parity group fits the half line)
+  const int nn = T.n, h = (nn + 1) / 2, nch = split_nch(nn), ne = (int)T.even.size(), no = (int)T.odd.size();
+  const std::vector<double> &S = T.S; const std::vector<int> *const grp[2] = {&T.even, &T.odd};
+  auto fwd = [&](int r, int c, int e) { const std::vector<int> &g = *grp[e]; return r < (int)g.size() && c < h ? S[(size_t)c * nn + g[r]] : 0.0; };
+  auto bwd = [&](int r, int c, int e) { const std::vector<int> &g = *grp[e]; return r < h && c < (int)g.size() ? S[(size_t)r * nn + g[c]] : 0.0; };
+  if (nch) {
+    auto tile = [](int, int p, int) { return p; };
+    D.fwd.upload(pack_paired_chunks(1, nch, nch, tile, fwd)); D.bwd.upload(pack_paired_chunks(1, nch, nch, tile, bwd));
+  } else {
     constexpr int PP = 5;
-    auto pack_blk = [&](DevBuf<double> &dst, bool forward, int &kk_out, int &nch_out, int &mb_out) {
-      const int rows = forward ? std::max(ne, no) : h, cols = forward ? h : std::max(ne, no);
+    auto tile = [](int b, int p, int) { return PP * b + p; };
+    for (int w = 0; w < 2; ++w) {       // forward, backward
+      const int rows = w == 0 ? std::max(ne, no) : h, cols = w == 0 ? h : std::max(ne, no);
       const int kk = (cols + 3) / 4, nchk = (kk + 3) / 4, mb = (rows + 16 * PP - 1) / (16 * PP);
-      std::vector<double> f((size_t)mb * nchk * 4 * PP * 128, 0.0);
-      for (int b = 0; b < mb; ++b) for (int ch = 0; ch < nchk; ++ch) for (int u = 0; u < 4; ++u) for (int p = 0; p < PP; ++p) for (int l = 0; l < 64; ++l) for (int e = 0; e < 2; ++e) {
-        const int r = 16 * (PP * b + p) + (l & 15), cc = 4 * (4 * ch + u) + (l >> 4);
-        const std::vector<int> &grp = e ? odd : even;
-        double v = 0;
-        if (forward) { if (r < (int)grp.size() && cc < h) v = S[(size_t)cc * nn + grp[r]]; }
-        else { if (r < h && cc < (int)grp.size()) v = S[(size_t)r * nn + grp[cc]]; }
-        f[((((size_t)(b * nchk + ch) * 4 + u) * PP + p) * 64 + l) * 2 + e] = v;
-      }
-      dst.upload(f); kk_out = kk; nch_out = nchk; mb_out = mb;
-    };
-    pack_blk(D.fwd, true, D.blk_kk[0], D.blk_nch[0], D.blk_mb[0]); pack_blk(D.bwd, false, D.blk_kk[1], D.blk_nch[1], D.blk_mb[1]);
-    D.lam.upload(lp); D.n_even = ne; D.split = true; D.blk = true;
-    return true;
-  }
-  if (ne > 16 * nch || no > 16 * nch || h > 16 * nch) return false;
-  auto pack = [&](DevBuf<double> &dst, bool forward) {
-    std::vector<double> f((size_t)nch * 4 * nch * 128, 0.0);
-    for (int ch = 0; ch < nch; ++ch) for (int u = 0; u < 4; ++u) for (int p = 0; p < nch; ++p) for (int l = 0; l < 64; ++l) for (int e = 0; e < 2; ++e) {
-      const int r = 16 * p + (l & 15), cc = 4 * (4 * ch + u) + (l >> 4);
-      const std::vector<int> &grp = e ? odd : even;
-      double v = 0;
-      if (forward) { if (r < (int)grp.size() && cc < h) v = S[(size_t)cc * nn + grp[r]]; }      // rows = modes of the parity group, columns = lower-half nodes
-      else { if (r < h && cc < (int)grp.size()) v = S[(size_t)r * nn + grp[cc]]; }              // rows = lower-half nodes, columns = modes
-      f[(((size_t)(ch * 4 + u) * nch + p) * 64 + l) * 2 + e] = v;
+      if (w == 0) D.fwd.upload(pack_paired_chunks(mb, nchk, PP, tile, fwd)); else D.bwd.upload(pack_paired_chunks(mb, nchk, PP, tile, bwd));
+      D.blk_kk[w] = kk; D.blk_nch[w] = nchk; D.blk_mb[w] = mb;
     }
-    dst.upload(f);
-  };
-  pack(D.fwd, true); pack(D.bwd, false);
-  D.lam.upload(lp); D.n_even = ne; D.split = true; D.blk = false;
-  return true;
+  }
+  std::vector<double> lp(nn, std::numeric_limits<double>::infinity());      // mode order along the line: the even modes first, then the odd ones
+  for (int i = 0; i < ne; ++i) lp[i] = T.lam[T.even[i]];
+  for (int i = 0; i < no; ++i) lp[ne + i] = T.lam[T.odd[i]];
+  D.lam.upload(lp); D.n_even = ne; D.split = true; D.blk = !nch;
 }
+}  // namespace
 
-void fdmu_upload_dir(FdmuDir &D, const std::vector<double> &S, const std::vector<double> &lam, int nn, bool single, bool allow_split) {
+void fdmu_upload_dir(FdmuDir &D, const LineTables &T, bool single, bool allow_split) {
+  const int nn = T.n;
   D.n = nn; D.split = false; D.blk = false; D.n_even = 0; D.reg_form = !single && reg_nch(nn) > 0 && !std::getenv("PORO_FDMU_LDS_FORM");
-  if (!single && allow_split && !std::getenv("PORO_FDMU_LDS_FORM") && !std::getenv("PORO_FDMU_NO_SPLIT") && upload_split(D, S, lam, nn)) return;
+  if (!single && allow_split && !std::getenv("PORO_FDMU_LDS_FORM") && !std::getenv("PORO_FDMU_NO_SPLIT")) { upload_split(D, T); return; }
   if (nn > 320) throw Error("fast diagonalisation of the displacement system: a line of more than 320 points needs the even / odd form (the same Dirichlet condition at both ends of every direction)");
-  if (D.reg_form) { upload_chunked(D.fwd, S, nn, true); upload_chunked(D.bwd, S, nn, false); D.lam.upload(lam); return; }
-  if (single) { upload_fragments<float>(D.fwd, S, nn, true); upload_fragments<float>(D.bwd, S, nn, false); }
-  else { upload_fragments<double>(D.fwd, S, nn, true); upload_fragments<double>(D.bwd, S, nn, false); }
-  D.lam.upload(lam);
+  upload_full(D, T, single);
 }
 
 // z = blockdiag(A_cc)^-1 g.  g, z: node-interleaved vectors of the local grid nn[0] x nn[1] (x nn[2]); t1, t2: planar scratch of the same size.
