@@ -52,10 +52,8 @@ struct Cg1State { double gamma_old, alpha_old, alpha, beta, tol, res0, res; int3
 
 // INVERSE Jacobi diagonal handed to the PCG kernels (they multiply): the full vector of reciprocals, or (uniform boxes) a class byte
 // per node + table[class][component] of reciprocals
-// reciprocal Jacobi diagonal; a ZERO entry marks an inert (Dirichlet) dof that PCG leaves alone; `inert` is the same set as a byte mask
-struct DiagVec { const double *full = nullptr; const uint8_t *cls = nullptr; const double *tab = nullptr; int ncomp = 1; const uint8_t *inert = nullptr;
-                 const double *z = nullptr; /* explicit preconditioner: z = P^-1 g is supplied as a vector (pcg() fills it between the two update kernels) */
-                 double *z1_out = nullptr; double z1_scale = 0; /* optional: the residual update also stores z1_scale * D^-1 g (first Chebyshev iterate) */ };
+// reciprocal Jacobi diagonal; a ZERO entry marks an inert (Dirichlet) dof that PCG leaves alone (the drivers carry the same set as a byte mask beside it)
+struct DiagVec { const double *full = nullptr; const uint8_t *cls = nullptr; const double *tab = nullptr; int ncomp = 1; };
 
 struct FeTablesDev {   // device copies of poro_fe_tables
   int nq_u, nq_p, nq_f, ns_u, ns_p;
@@ -273,7 +271,6 @@ struct poro_ctx {
   std::vector<uint8_t> h_node_mask;
   poro::DevBuf<double> partials; poro::DevBuf<poro::PcgScalars> scal; poro::DevBuf<double> red;   // red: kScalarSlots doubles
   poro::Mailbox *mailbox = nullptr; unsigned long long mb_seq = 0;   // pinned host memory (hipHostMalloc), device-visible at the same address
-  bool cheb_z1_ready = false;   // single-reduction PCG: the update kernel has already stored the first Chebyshev iterate of the coming preconditioner call
   int timing_stride = 1;   // events on every timing_stride-th launch of a family (poro_timers_enable)
   poro::DevBuf<double> cheb_side_lo, cheb_side_hi;   // partial products of the fused Chebyshev kernel on the shared planes (slab partitions)
   poro::DevBuf<poro::Cg1State> cg1_state; poro::DevBuf<double> cg1_z[2], cg1_w[2];   // single-reduction PCG of partitioned runs ([0]: displacement-sized, [1]: pressure-sized)
@@ -341,17 +338,19 @@ void la_rhs_u_finish(hipStream_t s, double *rhs, const double *lift, const doubl
 void pcg_init_residual(hipStream_t s, double *g, const double *Ax, const double *b, const uint8_t *inert /*nullable*/, int64_t n);
 void la_mask_zero(hipStream_t s, double *x, const uint8_t *mask, int64_t n);
 void pcg_dot_dh(hipStream_t s, const PcgScalars *sc, const double *d, const double *h, int64_t n_owned, double *partials);
-void pcg_first_direction(hipStream_t s, double *d, const double *g, const DiagVec &diag, int prec, int64_t n, int64_t n_owned, double *partials /*2 sets: gg, gz*/);
+// z (here and in the two fused updates): the explicit preconditioner's vector z = P^-1 g, null for Jacobi / none (prec)
+void pcg_first_direction(hipStream_t s, double *d, const double *g, const DiagVec &diag, const double *z, int prec, int64_t n, int64_t n_owned, double *partials /*2 sets: gg, gz*/);
 void pcg_scalars_sum(hipStream_t s, const double *partials, int n_sets, double *red);
 void cg1_dots(hipStream_t s, const double *g, const double *z, const double *w, const double *b /*nullable: adds b.b*/, int64_t n_owned, double *partials /*4 sets*/);
 void cg1_scalars(hipStream_t s, Cg1State *st, const double *red, int first, double abs_tol, double rel_tol, int max_iter, int stop_rule);
-void cg1_update(hipStream_t s, const Cg1State *st, double *d, double *sv, double *x, double *g, const double *z, const double *w, const DiagVec &dv /* inert mask; z1_out: also store z1_scale D^-1 g_new */, int64_t n);
+void cg1_update(hipStream_t s, const Cg1State *st, double *d, double *sv, double *x, double *g, const double *z, const double *w, const DiagVec &dv, const uint8_t *inert,
+                double *z1_out /* nullable: also store z1_scale D^-1 g_new there */, double z1_scale, int64_t n);
 void pcg_scalars_start(hipStream_t s, PcgScalars *sc, const double *red /*bb, gg, gz*/, double abs_tol, double rel_tol, int max_iter, int stop_rule);
 // single-rank fast path: the consumers reduce the block partials themselves (no scalar kernels, no host round trip);
 // parity = iteration index & 1 selects the g.z slot read / written
-void pcg_update_g_fused(hipStream_t s, PcgScalars *sc, int parity, double *g, const double *h, const DiagVec &diag, int prec, int64_t n, int64_t n_owned,
+void pcg_update_g_fused(hipStream_t s, PcgScalars *sc, int parity, double *g, const double *h, const DiagVec &diag, const double *z, double *z1_out /* as cg1_update */, double z1_scale, int prec, int64_t n, int64_t n_owned,
                         const double *partials_dh, const double *red /*null: single rank*/, double *partials_out /*2 sets*/);
-void pcg_update_d_fused(hipStream_t s, PcgScalars *sc, int parity, int it, double *x, double *d, const double *g, const DiagVec &diag, int prec, int64_t n,
+void pcg_update_d_fused(hipStream_t s, PcgScalars *sc, int parity, int it, double *x, double *d, const double *g, const DiagVec &diag, const double *z, int prec, int64_t n,
                         const double *partials_in /*2 sets*/, const double *red /*null: single rank*/);
 
 // ---- kernels_kelly.hip: mesh adaptation (Kelly indicator, transfer of the pressure-space vectors) ----

@@ -135,23 +135,30 @@ void finish_u(poro_ctx *c, bool expand) {
   if (expand) la_cons_expand(c->stream, c->cons_u, vec(c, PORO_VEC_U), true);
 }
 
-// the Jacobi diagonal of the displacement system; `dictionary`: in its class / table form where one was built
-DiagVec diag_u(poro_ctx *c, const uint8_t *inert, bool dictionary) {
-  DiagVec dv;
-  dv.full = c->dinv_u.p;
-  dv.ncomp = c->dim;
-  dv.inert = inert;
-  if (dictionary && c->diag_u_cls.p) {
-    dv.cls = c->diag_u_cls.p;
-    dv.tab = c->diag_u_tab.p;
-  }
-  return dv;
+// what every displacement solve shares.  `inert`: the rows kept out of the system (the Dirichlet rows, or those and the hanging ones); `dictionary`: the Jacobi diagonal in its
+// class / table form where one was built
+KrylovSystem krylov_u(poro_ctx *c, const uint8_t *inert, bool dictionary, int *hint) {
+  KrylovSystem sys;
+  sys.n = c->n_u; sys.plane = c->comm.part.plane_u;
+  sys.x = vec(c, PORO_VEC_U); sys.b = vec(c, PORO_VEC_RHS_U);
+  sys.apply = operator_u(c);
+  sys.diag.full = c->dinv_u.p; sys.diag.ncomp = c->dim;
+  if (dictionary && c->diag_u_cls.p) { sys.diag.cls = c->diag_u_cls.p; sys.diag.tab = c->diag_u_tab.p; }
+  sys.inert = inert;
+  sys.g = c->wg_u.p; sys.d = c->wd_u.p; sys.h = c->wh_u.p;
+  sys.hint = hint;
+  return sys;
+}
+// the vector an explicit displacement preconditioner writes
+double *z_u(poro_ctx *c) {
+  if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }
+  return c->wz_u.p;
 }
 
 // lambda_max(D^-1 A): on a uniform box all cells share one element matrix and lambda_max <= lambda_max(diag(K_e)^-1 K_e) holds rigorously
 // (x^T A x = sum_e x_e^T K_e x_e <= mu sum_e x_e^T diag(K_e) x_e = mu x^T D x) but is loose (3.8 against 2.5 for Q2 hexahedra), so the working
 // value is the Lanczos estimate (+5 %) capped by it.  Cached in c->cheb_lmax until the matrix is rebuilt
-double chebyshev_lmax(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj) {
+double chebyshev_lmax(poro_ctx *c, const KrylovSystem &sys) {
   if (c->cheb_lmax > 0) return c->cheb_lmax;
   const bool have_bound = c->box.enabled && c->Ke.p && !c->cons_u.n;
   if (have_bound) {
@@ -159,9 +166,9 @@ double chebyshev_lmax(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj) {
     PORO_HIP(hipMemcpyAsync(ke.data(), c->Ke.p, ke.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PORO_HIP(hipStreamSynchronize(c->stream));
     const double bound = jacobi_scaled_lambda_max(c->dpc_u, ke);              // rigorous but loose
-    c->cheb_lmax = std::min(bound, estimate_lmax_u(c, apply, dj));
+    c->cheb_lmax = std::min(bound, estimate_lmax_u(c, sys));
   } else {
-    c->cheb_lmax = estimate_lmax_u(c, apply, dj);
+    c->cheb_lmax = estimate_lmax_u(c, sys);
   }
   if (std::getenv("PORO_CHEB_VERBOSE")) std::fprintf(stderr, "[poro] lambda_max(D^-1 A_u) ~ %.6f\n", c->cheb_lmax);
   return c->cheb_lmax;
@@ -197,11 +204,11 @@ double chebyshev_default_ratio(poro_ctx *c) {
 // (identical CG iteration counts in the prototype for every ordering at these degrees) with ONE extra stream per step (g) instead of two;
 // the roots are taken alternately from both ends so that no run of small roots inflates the intermediate iterates
 struct ChebPlan { int m; double lmax, ratio; std::vector<double> roots; };
-ChebPlan chebyshev_plan(poro_ctx *c, const poro_solver_opts *opts, const ApplyFn &apply, const DiagVec &dj) {
+ChebPlan chebyshev_plan(poro_ctx *c, const poro_solver_opts *opts, const KrylovSystem &sys) {
   ChebPlan p;
   p.m = opts->poly_degree > 0 ? opts->poly_degree : 6;
   if (p.m & 1) ++p.m;
-  p.lmax = chebyshev_lmax(c, apply, dj);
+  p.lmax = chebyshev_lmax(c, sys);
   // `omega` doubles as the interval ratio; anything below 4 (the SSOR relaxation 1.2 a caller may have left there, 0) means "default"
   p.ratio = opts->omega >= 4.0 ? opts->omega : chebyshev_default_ratio(c);
   const double lmin = p.lmax / p.ratio, theta = 0.5 * (p.lmax + lmin), delta = 0.5 * (p.lmax - lmin);
@@ -217,10 +224,10 @@ ChebPlan chebyshev_plan(poro_ctx *c, const poro_solver_opts *opts, const ApplyFn
 }
 
 // m operator applications without dot products; on 3D boxes (one rank) the recurrence runs inside the structured operator kernel
-int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+int solve_u_chebyshev(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
   hipStream_t s = c->stream;
-  const DiagVec dj = diag_u(c, c->cons_u.inert.p, true);
-  const ChebPlan plan = chebyshev_plan(c, opts, apply, dj);
+  KrylovSystem sys = krylov_u(c, c->cons_u.inert.p, true, c->pcg_hint_cheb_u);
+  const ChebPlan plan = chebyshev_plan(c, opts, sys);
   const int m = plan.m;
   const std::vector<double> &roots = plan.roots;
   if (!c->cheb_z.p) {
@@ -228,10 +235,6 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
     c->cheb_z.zero(s);
     c->cheb_t.alloc(c->n_u);
     c->cheb_t.zero(s);
-  }
-  if (!c->wz_u.p) {
-    c->wz_u.alloc(c->n_u);
-    c->wz_u.zero(s);
   }
   const bool fusable = c->operator_mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && c->box.enabled && kron_supported(c->dim, c->k_u) && c->diag_u_cls.p && !c->cons_u.n &&
                        !std::getenv("PORO_CHEB_UNFUSED");
@@ -245,7 +248,7 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
   }
   const int64_t n_own = owned(c, c->n_u, c->comm.part.plane_u);
 
-  // One step zn = zj + omega D^-1 (g - A zj) in its three forms.  dp != null (the last step inside the iteration) asks for the block partials
+  // One step zn = zj + omega D^-1 (g - A zj) in its three forms.  dp != null (the last step of a call that asks for g . z) takes the block partials
   // of g . zn; each form returns whether it has left them there
   auto cheb_update = [&](const double *g, double *zn, double omega) {
     KronCheb kc;
@@ -273,7 +276,7 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
         Timed te(c, "halo_exchange");
         exchange_planes(c, c->cheb_side_lo.p, c->cheb_side_hi.p, plane);
       }
-      la_cheb_fix_planes(s, zn, zj, g, kc.side_lo, c->comm.recv_lo.p, kc.side_hi, c->comm.recv_hi.p, dj, omega, c->n_u, plane);
+      la_cheb_fix_planes(s, zn, zj, g, kc.side_lo, c->comm.recv_lo.p, kc.side_hi, c->comm.recv_hi.p, sys.diag, omega, c->n_u, plane);
     }
     if (dp) la_dot_partials(s, g, zn, n_own, dp);
     return dp != nullptr;
@@ -285,43 +288,38 @@ int solve_u_chebyshev(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts 
     return dp && slots > 0;
   };
   auto step_unfused = [&](const double *g, double *zj, double *zn, double omega, double *dp) {
-    apply(zj, c->cheb_t.p, nullptr);
-    la_cheb_step(s, zn, zj, g, c->cheb_t.p, dj, omega, c->n_u, n_own, dp);
+    sys.apply(zj, c->cheb_t.p, nullptr);
+    la_cheb_step(s, zn, zj, g, c->cheb_t.p, sys.diag, omega, c->n_u, n_own, dp);
     return dp != nullptr;
   };
-  const ApplyFn P = [&](const double *g, double *z, double *gz_partials) {
+  sys.prec.z = z_u(c);
+  sys.prec.gated = fuse;
+  sys.prec.applications = m;
+  sys.z1.out = (m % 2 == 0) ? sys.prec.z : c->cheb_z.p;     // z_1 = D^-1 g / r_0 rides with the residual update
+  sys.z1.scale = 1.0 / roots[0];
+  sys.prec.fn = [&](const double *g, double *z, const PrecCall &call) {
     Timed tm(c, "precondition_u_chebyshev");
     double *X[2] = {(m % 2 == 0) ? z : c->cheb_z.p, (m % 2 == 0) ? c->cheb_z.p : z};   // z_{j+1} lands in X[j & 1]; the last one (j = m) in z
-    if (!gz_partials && !c->cheb_z1_ready) la_cheb_first(s, X[0], g, dj, 1.0 / roots[0], c->n_u);   // inside the iteration z_1 = D^-1 g / r_0 was stored by the residual update (DiagVec::z1_out)
-    c->cheb_z1_ready = false;
+    if (!call.z1_ready) la_cheb_first(s, X[0], g, sys.diag, 1.0 / roots[0], c->n_u);
     bool dot_done = false;
-    // (the device-side "solve finished" flag may only gate launches inside the iteration: before pcg_scalars_start it still holds the previous solve's state)
-    const PcgScalars *pstate = gz_partials ? c->scal.p : nullptr;
     for (int j = 1; j <= m; ++j) {
       const double omega = 1.0 / roots[j];
       double *zj = X[(j - 1) & 1], *zn = X[j & 1];
-      double *dp = j == m ? gz_partials : nullptr;
+      double *dp = j == m ? call.gz_partials : nullptr;
       if (fuse_multi) dot_done = step_fused_slabs(g, zj, zn, omega, dp);
-      else if (fuse) dot_done = step_fused(g, zj, zn, omega, dp, pstate);
+      else if (fuse) dot_done = step_fused(g, zj, zn, omega, dp, call.gate);
       else dot_done = step_unfused(g, zj, zn, omega, dp);
       ++c->cheb_applies;
     }
-    return dot_done;
+    return dot_done ? GzLeft::in_partials : GzLeft::nowhere;
   };
-  DiagVec dz = dj;
-  dz.z = c->wz_u.p;
-  dz.z1_out = (m % 2 == 0) ? c->wz_u.p : c->cheb_z.p;
-  dz.z1_scale = 1.0 / roots[0];
-  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
-                     c->pcg_hint_cheb_u, fuse);
-  // useful operator applications: one per CG iteration + the initial residual, and m per preconditioner call (one call per iteration + the first direction)
-  if (info) info->operator_applications = (int64_t)info->iterations + 1 + (int64_t)m * (info->iterations + 1);
+  const int rc = pcg(c, sys, opts, info);
   finish_u(c, true);
   return rc;   // (stream-ordered: pcg() returned after the finishing iteration, `distribute` follows in the stream)
 }
 
 // z = blockdiag(A_cc)^-1 g by fast diagonalisation: the same device-controlled SolverCG recurrence with an explicit preconditioner vector
-int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+int solve_u_fdm(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
   build_fdm_u(c);
   const FdmOct *oct = c->fdm_oct.built ? &c->fdm_oct : nullptr;
   const bool separate_gz = std::getenv("PORO_FDMO_SEPARATE_GZ") != nullptr;    // A/B hook, read once per solve: g . z by its own dot kernel, as before pass 2 produced it
@@ -330,55 +328,49 @@ int solve_u_fdm(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts,
   //          direction update; then the operator writes h again.  The prologue has the same order (apply -> init_residual -> preconditioner -> first_direction).
   //   fp64 transforms run on z itself, without the scratch array (k_fdmo_pass: "in place"); the fp32 mode keeps its float scratch array.
   // PORO_FDMO_SEPARATE_BUFFERS (A/B hook, read once per solve): h in wh_u, the scratch array between the passes, plain accesses to x.  The timer family
-  // "fdm_u_shared_buffers" counts the solves that ran on the shared layout (a count, no time; it counts whether or not the context's timing is on).  pcg sees the
-  // layout from h == oct->z and tells the direction update to stream x.
+  // "fdm_u_shared_buffers" counts the solves that ran on the shared layout (a count, no time; it counts whether or not the context's timing is on).
   const bool shared = oct && !oct->slab.on && !oct->planar && std::getenv("PORO_FDMO_SEPARATE_BUFFERS") == nullptr;
   if (shared) c->timers["fdm_u_shared_buffers"].enqueued++;
   double *const scratch = shared && c->fdm_precision != PORO_FDM_FP32 ? nullptr : c->fdm_oct.t.p;
-  const ApplyFn P = [&](const double *g, double *z, double *in_iteration) {
-    // g, z in the layout of the form that is built (octants: three contiguous sweeps); inside the iteration the launches are gated on the device-side "solve finished" flag (before
-    // pcg_scalars_start it still holds the previous solve's state)
-    const PcgScalars *gate = in_iteration ? c->scal.p : nullptr;
+  KrylovSystem sys = krylov_u(c, c->dir_mask.p, false, c->pcg_hint_fdm_u);
+  if (shared) sys.h = c->fdm_oct.z.p;
+  sys.oct.form = oct;
+  sys.oct.stream_x = shared;
+  sys.prec.z = c->wz_u.p;
+  sys.prec.gated = oct != nullptr;     // every launch of an iteration is gated: overshooting is cheap
+  sys.prec.fn = [&](const double *g, double *z, const PrecCall &call) {
+    // g, z in the layout of the form that is built (octants: three contiguous sweeps)
     if (!oct) {
       fdm_precondition_u(c, g, z);
-      return false;
+      return GzLeft::nowhere;
     }
-    // octant form: inside the iteration pass 2 leaves g . z (in oct->gz_part, which k_fdmo_update_d reads); the first application of a solve keeps k_fdmo_first_direction's dot
-    return fdm_precondition_u_form(c, g, z, gate, c->fdm_precision, scratch, in_iteration && !separate_gz ? c->fdm_oct.gz_part.p : nullptr);
+    // octant form: pass 2 leaves g . z in oct->gz_part; the first application of a solve is not asked for it (k_fdmo_first_direction's dot)
+    const bool gz = call.gz_partials && !separate_gz;
+    return fdm_precondition_u_form(c, g, z, call.gate, c->fdm_precision, scratch, gz ? c->fdm_oct.gz_part.p : nullptr) ? GzLeft::in_octant_form : GzLeft::nowhere;
   };
-  DiagVec dz = diag_u(c, c->dir_mask.p, false);
-  dz.z = c->wz_u.p;
-  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, shared ? c->fdm_oct.z.p : c->wh_u.p, opts, info, &P,
-                     c->pcg_hint_fdm_u, oct != nullptr /* every launch of an iteration is gated: overshooting is cheap */, oct);
+  const int rc = pcg(c, sys, opts, info);
   finish_u(c, false);
   return rc;
 }
 
 // z = omega D^-1 g + P B_H^-1 P^T g: Jacobi on this mesh + the block fast diagonalisation of the underlying uniform box; SolverCG's recurrence with an
 // explicit preconditioner vector
-int solve_u_two_level(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
+int solve_u_two_level(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
   if (!two_level_supported(c)) throw Error("PORO_PREC_TWO_LEVEL needs poro_desc.coarse (a refinement of a uniform box whose Dirichlet conditions cover whole faces)");
   const double om = opts->omega > 0 ? opts->omega : 1.0;
-  if (!c->wz_u.p) {
-    c->wz_u.alloc(c->n_u);
-    c->wz_u.zero(c->stream);
-  }
-  const ApplyFn P = [&](const double *g, double *z, double *) {
+  KrylovSystem sys = krylov_u(c, c->cons_u.inert.p, false, c->pcg_hint_u);
+  sys.prec.z = z_u(c);
+  sys.prec.fn = [&](const double *g, double *z, const PrecCall &) {
     two_level_precondition_u(c, g, z, om);
-    return false;
+    return GzLeft::nowhere;
   };
-  DiagVec dz = diag_u(c, c->cons_u.inert.p, false);
-  dz.z = c->wz_u.p;
-  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dz, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, &P,
-                     c->pcg_hint_u);
+  const int rc = pcg(c, sys, opts, info);
   finish_u(c, true);
   return rc;
 }
 
-int solve_u_jacobi(poro_ctx *c, const ApplyFn &apply, const poro_solver_opts *opts, poro_solve_info *info) {
-  const DiagVec dv = diag_u(c, c->cons_u.inert.p, true);
-  const int rc = pcg(c, apply, c->n_u, c->comm.part.plane_u, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), dv, c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info, nullptr,
-                     c->pcg_hint_u);
+int solve_u_jacobi(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
+  const int rc = pcg(c, krylov_u(c, c->cons_u.inert.p, true, c->pcg_hint_u), opts, info);
   finish_u(c, true);
   return rc;
 }
@@ -393,8 +385,7 @@ struct Q1System {
   double *x;
   const double *b;
   int *hint;                          // iteration counts of the last two solves
-  const uint8_t *inert_two_level;     // the inert mask handed to PCG per branch; null selects the kernel form without a mask
-  const uint8_t *inert_jacobi;
+  const uint8_t *inert;               // the inert mask of the two-level and Jacobi paths; null selects the kernel form without a mask
   const uint8_t *inert_fdm = nullptr; // FDM: none, except with prescribed pressures on whole faces (the free-row system: residual norm and g . z see free rows only)
   Q1Set set = Q1Set::free_ends;       // FDM: the table set; fixed_ends = without the prescribed faces' end nodes
   Q1Set coarse_set = Q1Set::free_ends; // two-level: the coarse box's table set; fixed_ends = (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
@@ -457,13 +448,20 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
 // ILU(0) / SSOR / fast-diagonalisation / two-level / Jacobi PCG on one system.  direct_first (FDM only): try the direct solve, whose result is the
 // start of the iteration where its check fails
 int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_solve_info *info, bool direct_first = false) {
-  double *g = c->wg_p.p, *d = c->wd_p.p, *h = c->wh_p.p;
-  if (opts->preconditioner == PORO_PREC_ILU0) return pcg_ilu0(c, c->Ap, q.val, *q.ilu, *q.ilu_valid, q.x, q.b, g, d, h, opts, info);
-  if (opts->preconditioner == PORO_PREC_SSOR) return pcg_ssor(c, c->Ap, q.val, q.x, q.b, g, d, h, opts, info);
-  const bool stencil = q1_stencil(c);
+  const int prec = opts->preconditioner;
   const int64_t n = c->n_p, plane = c->comm.part.plane_p;
+  KrylovSystem sys;
+  sys.n = n; sys.plane = plane;
+  sys.x = q.x; sys.b = q.b;
+  sys.diag.full = q.dinv;
+  sys.inert = q.inert;
+  sys.g = c->wg_p.p; sys.d = c->wd_p.p; sys.h = c->wh_p.p;
+  sys.cg1_set = 1;
+  sys.hint = q.hint;
+  if (prec == PORO_PREC_ILU0 || prec == PORO_PREC_SSOR) return pcg_csr_sweeps(c, c->Ap, q.val, *q.ilu, *q.ilu_valid, sys, opts, info);
+  const bool stencil = q1_stencil(c);
   // the condensed matrix C^T (a M + kappa K) C (:168, StrainProjector.h:104-105)
-  const ApplyFn apply = [&](const double *x, double *y, double *) {
+  sys.apply = [&](const double *x, double *y, double *) {
     la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);
     if (stencil) {
       Timed tm(c, "apply_p_stencil");
@@ -476,42 +474,34 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     exchange_add(c, y, n, plane);
     return false;
   };
-  DiagVec dz;
-  dz.full = q.dinv;
-  if (opts->preconditioner == PORO_PREC_FDM) {
-    build_fdm_q1(c, q.set);
-    const double kk[3] = {q.kappa, q.kappa, q.kappa};
+  if (prec == PORO_PREC_FDM || prec == PORO_PREC_TWO_LEVEL) {
     if (!c->wz_p.p) c->wz_p.alloc(n);
+    sys.prec.z = c->wz_p.p;
+  }
+  if (prec == PORO_PREC_FDM) {
+    build_fdm_q1(c, q.set);
     if (direct_first) {
       poro_solve_info direct;
-      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, h, false, opts, &direct, q.set, q.inert_fdm)) {
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, sys.h, false, opts, &direct, q.set, q.inert_fdm)) {
         if (info) *info = direct;
         return 0;
       }
     }
-    const ApplyFn P = [&](const double *gg, double *z, double *) {
-      fdm_precondition_p(c, q.a, kk, gg, z, q.set);
-      return false;
+    const double kk[3] = {q.kappa, q.kappa, q.kappa};
+    sys.inert = q.inert_fdm;
+    sys.prec.fn = [&](const double *g, double *z, const PrecCall &) {
+      fdm_precondition_p(c, q.a, kk, g, z, q.set);
+      return GzLeft::nowhere;
     };
-    dz.z = c->wz_p.p;
-    dz.inert = q.inert_fdm;
-    return pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, &P, q.hint);
+    return pcg(c, sys, opts, info);
   }
-  int rc;
-  if (opts->preconditioner == PORO_PREC_TWO_LEVEL) {
-    if (!c->wz_p.p) c->wz_p.alloc(n);
-    const double om = opts->omega > 0 ? opts->omega : 1.0;
-    const ApplyFn P = [&](const double *gg, double *z, double *) {
-      two_level_precondition_p(c, q.a, q.kappa, q.dinv, gg, z, om, q.inert_two_level, q.coarse_set);
-      return false;
+  const double om = opts->omega > 0 ? opts->omega : 1.0;
+  if (prec == PORO_PREC_TWO_LEVEL)
+    sys.prec.fn = [&](const double *g, double *z, const PrecCall &) {
+      two_level_precondition_p(c, q.a, q.kappa, q.dinv, g, z, om, q.inert, q.coarse_set);
+      return GzLeft::nowhere;
     };
-    dz.z = c->wz_p.p;
-    dz.inert = q.inert_two_level;
-    rc = pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, &P, q.hint);
-  } else {
-    dz.inert = q.inert_jacobi;
-    rc = pcg(c, apply, n, plane, q.x, q.b, dz, g, d, h, opts, info, nullptr, q.hint);
-  }
+  const int rc = pcg(c, sys, opts, info);
   la_cons_expand(c->stream, c->cons_p, q.x, q.distribute_inhom);                // constraints.distribute (:180, StrainProjector.h:216)
   return rc;
 }
@@ -841,23 +831,17 @@ int poro_disp_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     if (!c->matrix_built) throw Error("disp_solve before disp_assemble_system");
     const int prec = opts->preconditioner;
     if (const char *why = prec_refusal(c, 0, prec, true)) throw Error(why);
-    if (prec == PORO_PREC_ILU0) {
-      const int rc = pcg_ilu0(c, c->Au, c->Au_val.p, c->ilu_u, c->ilu_u_valid, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
+    if (prec == PORO_PREC_ILU0 || prec == PORO_PREC_SSOR) {
+      KrylovSystem sys = krylov_u(c, nullptr, false, nullptr);
+      const int rc = pcg_csr_sweeps(c, c->Au, c->Au_val.p, c->ilu_u, c->ilu_u_valid, sys, opts, info);
       finish_u(c, false);
       PORO_HIP(hipStreamSynchronize(c->stream));
       return rc;
     }
-    if (prec == PORO_PREC_SSOR) {
-      const int rc = pcg_ssor(c, c->Au, c->Au_val.p, vec(c, PORO_VEC_U), vec(c, PORO_VEC_RHS_U), c->wg_u.p, c->wd_u.p, c->wh_u.p, opts, info);
-      finish_u(c, false);
-      PORO_HIP(hipStreamSynchronize(c->stream));
-      return rc;
-    }
-    const ApplyFn apply = operator_u(c);
-    if (prec == PORO_PREC_CHEBYSHEV) return solve_u_chebyshev(c, apply, opts, info);
-    if (prec == PORO_PREC_FDM) return solve_u_fdm(c, apply, opts, info);
-    if (prec == PORO_PREC_TWO_LEVEL) return solve_u_two_level(c, apply, opts, info);
-    return solve_u_jacobi(c, apply, opts, info);
+    if (prec == PORO_PREC_CHEBYSHEV) return solve_u_chebyshev(c, opts, info);
+    if (prec == PORO_PREC_FDM) return solve_u_fdm(c, opts, info);
+    if (prec == PORO_PREC_TWO_LEVEL) return solve_u_two_level(c, opts, info);
+    return solve_u_jacobi(c, opts, info);
   });
 }
 
@@ -933,7 +917,7 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     J.x = vec(c, PORO_VEC_DP);
     J.b = vec(c, PORO_VEC_RESIDUAL_P);
     J.hint = c->pcg_hint_p;
-    J.inert_two_level = J.inert_jacobi = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;     // hanging and prescribed rows alike (the union where both lists are present)
+    J.inert = (c->cons_p.n || c->n_pdir) ? c->cons_p.inert.p : nullptr;     // hanging and prescribed rows alike (the union where both lists are present)
     if (two_level_pdir) J.coarse_set = Q1Set::fixed_ends;
     if (c->n_pdir && (c->cons_p.n || two_level_pdir)) {
       J.distribute_inhom = false;
@@ -1014,7 +998,7 @@ int poro_proj_solve(poro_ctx *c, int32_t entry, const poro_solver_opts *opts, po
     M.x = vec(c, PORO_VEC_STRAIN0 + entry);
     M.b = vec(c, PORO_VEC_PROJ_RHS0 + entry);
     M.hint = c->pcg_hint_proj;
-    M.inert_two_level = M.inert_jacobi = c->cons_p.n ? proj_inert(c) : nullptr;
+    M.inert = c->cons_p.n ? proj_inert(c) : nullptr;
     return solve_q1(c, M, opts, info);
   });
 }

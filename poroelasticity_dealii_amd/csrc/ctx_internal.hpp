@@ -85,13 +85,44 @@ bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_pa
                bool exchange = true /* false: leave the rank's partial product (the caller folds constrained rows first) */);
 
 // ---- Krylov drivers (ctx_pcg.hip) -----------------------------------------------------------------------------------------------------
-typedef std::function<bool(const double *, double *, double *)> ApplyFn;
-int pcg(poro_ctx *c, const ApplyFn &apply, int64_t n, int64_t plane, double *x, const double *b, const DiagVec &diag, double *g, double *d, double *h, const poro_solver_opts *opts,
-        poro_solve_info *info, const ApplyFn *precond = nullptr, int *its_hint = nullptr, bool precond_gated = false, const FdmOct *oct = nullptr);
+// The operator: y = A x, consistent on the shared planes of a partition.  dh_partials != null (inside pcg()'s iteration only): the launch may be gated on c->scal, and a kernel that
+// can leaves the block partials of x . y there; returns whether it did (false: the driver runs its own dot kernel).
+typedef std::function<bool(const double *x, double *y, double *dh_partials)> ApplyFn;
+// An explicit preconditioner: z = P^-1 g as a sequence of launches on the stream.  PrecCall is what the driver asks of ONE call:
+struct PrecCall {
+  const PcgScalars *gate = nullptr;   // the device-side "solve finished" flag the launches may test.  Null wherever it does not describe this solve: before pcg_scalars_start
+                                      // (the first call of a solve; c->scal still holds the previous solve's state), in the single-reduction driver, and for a preconditioner that is not `gated`
+  double *gz_partials = nullptr;      // where to leave the block partials of g . z over the owned rows; null: do not produce g . z (the driver's next kernel does)
+  bool z1_ready = false;              // the residual update has already stored KrylovSystem::z1.scale D^-1 g in z1.out
+};
+enum class GzLeft { nowhere, in_partials /* PrecCall::gz_partials */, in_octant_form /* FdmOct::gz_part, which k_fdmo_update_d reads */ };   // where a call left g . z; nowhere: the driver runs a dot kernel
+typedef std::function<GzLeft(const double *g, double *z, const PrecCall &)> PrecFn;
+
+// One linear system A x = b as the three drivers see it; filled once per solve (ctx.hip: krylov_u and solve_q1 fill what is common to a space)
+struct KrylovSystem {
+  int64_t n = 0, plane = 0;            // local length; dofs of one shared plane (slab partitions)
+  double *x = nullptr; const double *b = nullptr;
+  ApplyFn apply;
+  DiagVec diag;                        // reciprocal Jacobi diagonal (read by PORO_PREC_JACOBI and for z1)
+  const uint8_t *inert = nullptr;      // rows kept out of the system (nullable)
+  double *g = nullptr, *d = nullptr, *h = nullptr;   // work vectors: residual, direction, A d
+  int cg1_set = 0;                     // which of poro_ctx::cg1_w / cg1_z the single-reduction driver uses (0: displacement-sized, 1: pressure-sized)
+  int *hint = nullptr;                 // iteration counts of the last two solves of this system (read for the batch sizes, then updated); nullable
+  struct { PrecFn fn;                  // empty: Jacobi / none by poro_solver_opts::preconditioner
+           double *z = nullptr;        // the vector the driver hands to fn (octant layout: Octant::form->z instead)
+           bool gated = false;         // every launch of fn tests PrecCall::gate: iterations enqueued behind the finishing one cost ~1 us per launch
+           int applications = 0;       // operator applications inside one call (a polynomial's degree): counted in poro_solve_info::operator_applications
+  } prec;
+  struct { const FdmOct *form = nullptr;   // non-null (pcg() only, needs prec.fn): residual and z live in this octant (one rank) / quadrant (slabs) layout, `g` is unused
+           bool stream_x = false;      // h shares form->z's allocation: x streams past the cache in the direction update
+  } oct;
+  struct { double *out = nullptr; double scale = 0; } z1;   // out != null: the residual update also stores scale D^-1 g_new there (a polynomial preconditioner's first iterate)
+};
+int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro_solve_info *info);
 double dot_host(poro_ctx *c, const double *a, const double *b, int64_t n);
-int pcg_ssor(poro_ctx *c, CsrDev &A, const double *val, double *x, const double *b, double *g, double *d, double *h, const poro_solver_opts *opts, poro_solve_info *info);
-int pcg_ilu0(poro_ctx *c, CsrDev &A, const double *val, DevBuf<double> &lu, bool &valid, double *x, const double *b, double *g, double *d, double *h, const poro_solver_opts *opts, poro_solve_info *info);
-double estimate_lmax_u(poro_ctx *c, const ApplyFn &apply, const DiagVec &dj);
+// SSOR / ILU(0) by opts->preconditioner on the CSR matrix (A, val): fills sys.apply and sys.prec, runs the host-driven form.  lu, lu_valid: the ILU(0) factor and whether it belongs to val
+int pcg_csr_sweeps(poro_ctx *c, CsrDev &A, const double *val, DevBuf<double> &lu, bool &lu_valid, KrylovSystem &sys, const poro_solver_opts *opts, poro_solve_info *info);
+double estimate_lmax_u(poro_ctx *c, const KrylovSystem &sys);   // of the displacement system: its operator, Jacobi diagonal and inert rows
 
 // ---- fast-diagonalisation preconditioners (ctx_prec.hip) ------------------------------------------------------------------------------
 bool fdm_p_supported(poro_ctx *c);

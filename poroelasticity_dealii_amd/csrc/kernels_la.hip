@@ -628,42 +628,32 @@ void la_rhs_u_finish(hipStream_t s, double *rhs, const double *lift, const doubl
 }
 // dictionary form only for 2 / 3 components and 32-bit dof indices
 static int diag_nc(const DiagVec &dv, int64_t n) { return (dv.cls && (dv.ncomp == 2 || dv.ncomp == 3) && n < (int64_t)4000000000ll) ? dv.ncomp : 0; }
-void la_cheb_first(hipStream_t s, double *z, const double *g, const DiagVec &dv, double scale, int64_t n) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, nullptr};
+// f(integral_constant<int, NC>()): NC = 2 / 3 selects the dictionary form of a kernel, 0 the full vector (as dispatch_lanes)
+template <class F> void dispatch_nc(const DiagVec &dv, int64_t n, F &&f) {
   switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_cheb_first<2>, grid_for(n), kBlock, 0, s, z, g, D, scale, n); break;
-    case 3: hipLaunchKernelGGL(k_cheb_first<3>, grid_for(n), kBlock, 0, s, z, g, D, scale, n); break;
-    default: hipLaunchKernelGGL(k_cheb_first<0>, grid_for(n), kBlock, 0, s, z, g, D, scale, n);
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 0>());
   }
+}
+// the diagonal as the kernels take it, with the vectors some of them read or write beside it
+static DiagRef diag_ref(const DiagVec &dv, const double *z = nullptr, double *z1_out = nullptr, double z1_scale = 0) { return DiagRef{dv.full, dv.cls, dv.tab, dv.ncomp, z, z1_out, z1_scale}; }
+void la_cheb_first(hipStream_t s, double *z, const double *g, const DiagVec &dv, double scale, int64_t n) {
+  dispatch_nc(dv, n, [&, D = diag_ref(dv)](auto NC) { hipLaunchKernelGGL(k_cheb_first<decltype(NC)::value>, grid_for(n), kBlock, 0, s, z, g, D, scale, n); });
 }
 void la_cheb_fix_planes(hipStream_t s, double *znew, const double *zj, const double *g, const double *own_lo, const double *nbr_lo, const double *own_hi, const double *nbr_hi, const DiagVec &dv, double omega, int64_t n, int64_t plane) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, nullptr};
   const unsigned grid = (unsigned)((2 * plane + kBlock - 1) / kBlock);
-  switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_cheb_fix_planes<2>, grid, kBlock, 0, s, znew, zj, g, own_lo, nbr_lo, own_hi, nbr_hi, D, omega, n, plane); break;
-    case 3: hipLaunchKernelGGL(k_cheb_fix_planes<3>, grid, kBlock, 0, s, znew, zj, g, own_lo, nbr_lo, own_hi, nbr_hi, D, omega, n, plane); break;
-    default: hipLaunchKernelGGL(k_cheb_fix_planes<0>, grid, kBlock, 0, s, znew, zj, g, own_lo, nbr_lo, own_hi, nbr_hi, D, omega, n, plane);
-  }
+  dispatch_nc(dv, n, [&, D = diag_ref(dv)](auto NC) { hipLaunchKernelGGL(k_cheb_fix_planes<decltype(NC)::value>, grid, kBlock, 0, s, znew, zj, g, own_lo, nbr_lo, own_hi, nbr_hi, D, omega, n, plane); });
 }
 void la_cheb_step(hipStream_t s, double *znew, const double *zj, const double *g, const double *Az, const DiagVec &dv, double omega, int64_t n, int64_t n_owned, double *gz_partials) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, nullptr};
-  switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_cheb_step<2>, reduce_grid(n), kBlock, 0, s, znew, zj, g, Az, D, omega, n, n_owned, gz_partials); break;
-    case 3: hipLaunchKernelGGL(k_cheb_step<3>, reduce_grid(n), kBlock, 0, s, znew, zj, g, Az, D, omega, n, n_owned, gz_partials); break;
-    default: hipLaunchKernelGGL(k_cheb_step<0>, reduce_grid(n), kBlock, 0, s, znew, zj, g, Az, D, omega, n, n_owned, gz_partials);
-  }
+  dispatch_nc(dv, n, [&, D = diag_ref(dv)](auto NC) { hipLaunchKernelGGL(k_cheb_step<decltype(NC)::value>, reduce_grid(n), kBlock, 0, s, znew, zj, g, Az, D, omega, n, n_owned, gz_partials); });
 }
 void pcg_init_residual(hipStream_t s, double *g, const double *Ax, const double *b, const uint8_t *inert, int64_t n) {
   hipLaunchKernelGGL(k_pcg_init_residual, grid_for(n), kBlock, 0, s, g, Ax, b, inert, n);
 }
 void la_mask_zero(hipStream_t s, double *x, const uint8_t *mask, int64_t n) { if (n) hipLaunchKernelGGL(k_mask_zero, grid_for(n), kBlock, 0, s, x, mask, n); }
-void pcg_first_direction(hipStream_t s, double *d, const double *g, const DiagVec &dv, int prec, int64_t n, int64_t n_owned, double *partials) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, dv.z};
-  switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_pcg_first_direction<2>, reduce_grid(n), kBlock, 0, s, d, g, D, prec, n, n_owned, partials); break;
-    case 3: hipLaunchKernelGGL(k_pcg_first_direction<3>, reduce_grid(n), kBlock, 0, s, d, g, D, prec, n, n_owned, partials); break;
-    default: hipLaunchKernelGGL(k_pcg_first_direction<0>, reduce_grid(n), kBlock, 0, s, d, g, D, prec, n, n_owned, partials);
-  }
+void pcg_first_direction(hipStream_t s, double *d, const double *g, const DiagVec &dv, const double *z, int prec, int64_t n, int64_t n_owned, double *partials) {
+  dispatch_nc(dv, n, [&, D = diag_ref(dv, z)](auto NC) { hipLaunchKernelGGL(k_pcg_first_direction<decltype(NC)::value>, reduce_grid(n), kBlock, 0, s, d, g, D, prec, n, n_owned, partials); });
 }
 void pcg_dot_dh(hipStream_t s, const PcgScalars *sc, const double *d, const double *h, int64_t n_owned, double *partials) {
   hipLaunchKernelGGL(k_pcg_dot_dh, reduce_grid(n_owned), kBlock, 0, s, sc, d, h, n_owned, partials);
@@ -718,13 +708,8 @@ void cg1_dots(hipStream_t s, const double *g, const double *z, const double *w, 
 void cg1_scalars(hipStream_t s, Cg1State *st, const double *red, int first, double abs_tol, double rel_tol, int max_iter, int stop_rule) {
   hipLaunchKernelGGL(k_cg1_scalars, 1, 1, 0, s, st, red, first, abs_tol, rel_tol, max_iter, stop_rule);
 }
-void cg1_update(hipStream_t s, const Cg1State *st, double *d, double *sv, double *x, double *g, const double *z, const double *w, const DiagVec &dv, int64_t n) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, nullptr};
-  switch (dv.z1_out ? diag_nc(dv, n) : 0) {
-    case 2: hipLaunchKernelGGL(k_cg1_update<2>, grid_for(n), kBlock, 0, s, st, d, sv, x, g, z, w, dv.inert, n, D, dv.z1_out, dv.z1_scale); break;
-    case 3: hipLaunchKernelGGL(k_cg1_update<3>, grid_for(n), kBlock, 0, s, st, d, sv, x, g, z, w, dv.inert, n, D, dv.z1_out, dv.z1_scale); break;
-    default: hipLaunchKernelGGL(k_cg1_update<0>, grid_for(n), kBlock, 0, s, st, d, sv, x, g, z, w, dv.inert, n, D, dv.z1_out, dv.z1_scale);
-  }
+void cg1_update(hipStream_t s, const Cg1State *st, double *d, double *sv, double *x, double *g, const double *z, const double *w, const DiagVec &dv, const uint8_t *inert, double *z1_out, double z1_scale, int64_t n) {
+  dispatch_nc(z1_out ? dv : DiagVec{} /* the diagonal is read for z1_out alone */, n, [&, D = diag_ref(dv)](auto NC) { hipLaunchKernelGGL(k_cg1_update<decltype(NC)::value>, grid_for(n), kBlock, 0, s, st, d, sv, x, g, z, w, inert, n, D, z1_out, z1_scale); });
 }
 void pcg_scalars_sum(hipStream_t s, const double *partials, int n_sets, double *red) {
   hipLaunchKernelGGL(k_scalars_sum, 1, kBlock, 0, s, (const PcgScalars *)nullptr, partials, n_sets, red);
@@ -732,23 +717,13 @@ void pcg_scalars_sum(hipStream_t s, const double *partials, int n_sets, double *
 void pcg_scalars_start(hipStream_t s, PcgScalars *sc, const double *red, double abs_tol, double rel_tol, int max_iter, int stop_rule) {
   hipLaunchKernelGGL(k_scalars_start, 1, 1, 0, s, sc, red, abs_tol, rel_tol, max_iter, stop_rule);
 }
-void pcg_update_g_fused(hipStream_t s, PcgScalars *sc, int parity, double *g, const double *h, const DiagVec &dv, int prec, int64_t n, int64_t n_owned,
+void pcg_update_g_fused(hipStream_t s, PcgScalars *sc, int parity, double *g, const double *h, const DiagVec &dv, const double *z, double *z1_out, double z1_scale, int prec, int64_t n, int64_t n_owned,
                         const double *partials_dh, const double *red, double *partials_out) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, dv.z, dv.z1_out, dv.z1_scale};
-  switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_pcg_update_g_fused<2>, reduce_grid(n), kBlock, 0, s, sc, parity, g, h, D, prec, n, n_owned, partials_dh, red, partials_out); break;
-    case 3: hipLaunchKernelGGL(k_pcg_update_g_fused<3>, reduce_grid(n), kBlock, 0, s, sc, parity, g, h, D, prec, n, n_owned, partials_dh, red, partials_out); break;
-    default: hipLaunchKernelGGL(k_pcg_update_g_fused<0>, reduce_grid(n), kBlock, 0, s, sc, parity, g, h, D, prec, n, n_owned, partials_dh, red, partials_out);
-  }
+  dispatch_nc(dv, n, [&, D = diag_ref(dv, z, z1_out, z1_scale)](auto NC) { hipLaunchKernelGGL(k_pcg_update_g_fused<decltype(NC)::value>, reduce_grid(n), kBlock, 0, s, sc, parity, g, h, D, prec, n, n_owned, partials_dh, red, partials_out); });
 }
-void pcg_update_d_fused(hipStream_t s, PcgScalars *sc, int parity, int it, double *x, double *d, const double *g, const DiagVec &dv, int prec, int64_t n,
+void pcg_update_d_fused(hipStream_t s, PcgScalars *sc, int parity, int it, double *x, double *d, const double *g, const DiagVec &dv, const double *z, int prec, int64_t n,
                         const double *partials_in, const double *red) {
-  const DiagRef D{dv.full, dv.cls, dv.tab, dv.ncomp, dv.z};
-  switch (diag_nc(dv, n)) {
-    case 2: hipLaunchKernelGGL(k_pcg_update_d_fused<2>, reduce_grid(n), kBlock, 0, s, sc, parity, it, x, d, g, D, prec, n, partials_in, red); break;
-    case 3: hipLaunchKernelGGL(k_pcg_update_d_fused<3>, reduce_grid(n), kBlock, 0, s, sc, parity, it, x, d, g, D, prec, n, partials_in, red); break;
-    default: hipLaunchKernelGGL(k_pcg_update_d_fused<0>, reduce_grid(n), kBlock, 0, s, sc, parity, it, x, d, g, D, prec, n, partials_in, red);
-  }
+  dispatch_nc(dv, n, [&, D = diag_ref(dv, z)](auto NC) { hipLaunchKernelGGL(k_pcg_update_d_fused<decltype(NC)::value>, reduce_grid(n), kBlock, 0, s, sc, parity, it, x, d, g, D, prec, n, partials_in, red); });
 }
 
 }  // namespace poro
