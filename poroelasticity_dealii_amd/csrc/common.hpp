@@ -39,8 +39,14 @@ struct PcgScalars {
   double gh2[2];             // g.z of the previous iteration (ping-pong by iteration parity)
   double alpha, beta;
   double tol, res0, res;
-  int32_t it, done, converged, max_iter, finishing, pad_;
+  int32_t it, done, converged, max_iter, finishing;
+  int32_t stop;              // the iteration's stopping decision where it is made in front of the preconditioner call (PcgStopTest): 0 go on, 1 converged, 2 max_iter reached
 };
+// The stopping test of iteration `it`, handed to the FIRST kernel of a gated preconditioner call: sqrt(g . g) <= tol or it >= max_iter, g . g = the sum of the residual update's
+// block partials (sum_partials_wave: the bits of sum_partials).  Every workgroup of that kernel evaluates it for itself and returns at once when it holds; workgroup 0 stores
+// PcgScalars::stop, which the later kernels of the call test with `done` and `finishing` and from which the direction update takes its finishing branch - one decision per
+// iteration, so a z that was not computed is never read.  gg_part == null: no test here (the direction update decides, behind the preconditioner)
+struct PcgStopTest { PcgScalars *sc = nullptr; const double *gg_part = nullptr; int it = 0; };
 
 // Mailbox in pinned, device-visible host memory: a one-block kernel at the end of an enqueued sequence copies a few scalars (and optionally the PCG state) into it and
 // then raises `seq` with a system-scope release; the host spins on `seq` instead of issuing a device-to-host copy + stream synchronisation (which idled the GPU
@@ -247,6 +253,7 @@ struct poro_ctx {
   poro::DevBuf<double> Ke;                   // reference element matrix of the matrix-free operator
   // vectors (ids of include/poroel_hip.h)
   std::map<int, poro::DevBuf<double>> vec, vec_saved;
+  poro::DevBuf<uint8_t> rhs_u_flags;   // box_rhs_u_flags of lift_u and neumann_u, rebuilt with them (box_asm only)
   poro::DevBuf<double> lift_u, neumann_u, diag_u, diag_u_local, diag_J, diag_M, src_local;
   poro::DevBuf<double> dinv_u, dinv_J, dinv_M;   // reciprocals of the Jacobi diagonals
   poro::DevBuf<uint8_t> diag_u_cls; poro::DevBuf<double> diag_u_tab;   // dictionary form of diag_u (uniform boxes): class per node + table[class][dim]
@@ -400,7 +407,10 @@ struct KronCheb { const double *g = nullptr; double *znew = nullptr; double omeg
 bool kron_supported(int dim, int k_u);
 void kron_prepare_device();   // per-device function attributes (dynamic LDS opt-in) of the structured kernels; call after hipSetDevice
 BoxCoupling box_coupling(int dim, int k_u, const BoxDev &box);
-void box_rhs_u(hipStream_t s, int dim, const BoxCoupling &B, double alpha, const double *p, const double *lift, const double *neu, const uint8_t *mask, double *rhs);
+void box_rhs_u(hipStream_t s, int dim, const BoxCoupling &B, double alpha, const double *p, const double *lift, const double *neu, const uint8_t *mask, double *rhs,
+               const uint8_t *flags = nullptr /* box_rhs_u_flags of these lift and neu: the lines without nonzero entries are not read; null: all are */);
+int64_t box_rhs_u_flag_count(int64_t n_u);
+void box_rhs_u_flags(hipStream_t s, const double *lift, const double *neu, int64_t n_u, uint8_t *flags /*[box_rhs_u_flag_count(n_u)]*/);   // to be called again whenever lift or neu change
 void box_asm_u_matrix(hipStream_t s, int dim, int k_u, const BoxDev &box, const double *Ke, const CsrDev &A, const uint8_t *mask, double *val);
 void box_proj_rhs(hipStream_t s, int dim, const BoxCoupling &B, const double *u, int n_comp, const int32_t *tensor_components, double *const *rhs);
 // all peers' windows in one launch: block q of the dense side is dense + q blk (to_block: peer `self` goes to dense_self instead - its own block of the receive buffer)
@@ -424,7 +434,8 @@ void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T);   // T.
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
                 double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr,
-                int precision /* PORO_FDM_FP32: the three passes on the fp32 MFMA with an fp32 intermediate array; g_oct, z_oct and g . z stay fp64 */ = PORO_FDM_FP64);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing
+                int precision /* PORO_FDM_FP32: the three passes on the fp32 MFMA with an fp32 intermediate array; g_oct, z_oct and g . z stay fp64 */ = PORO_FDM_FP64,
+                const PcgStopTest &stop = PcgStopTest{} /* pass 1 runs the iteration's stopping test first; stop.sc == gate */);   // z = blockdiag(A_cc)^-1 g, all in octant form; gate: no-op once gate->done / finishing / stop
 // the same transform kernel for the scalar Q1 systems of a 3D box (nodal layout, one block set, no octants): 3 launches instead of 6
 bool fdmo_scalar_usable(int dim, const int nn[3]);
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s);
@@ -441,7 +452,7 @@ void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double 
 bool fdmo_planar_usable(int dim, const int nn[3]);
 void fdmo_init_planar(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s, bool split = true /* false: different conditions at the two ends of some line - no parity split, full-length transforms */);
 void fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required by the split form
-void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g_q, double *z_q, const PcgScalars *gate = nullptr);
+void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g_q, double *z_q, const PcgScalars *gate = nullptr, const PcgStopTest &stop = PcgStopTest{} /* as fdmo_apply: in the first GEMM */);
 void fdmo_from_nodal(hipStream_t s, const FdmOct &O, const double *v_nodal, double *q_oct);   // q = H v (node-interleaved vector -> octant form)
 void fdmo_to_nodal(hipStream_t s, const FdmOct &O, const double *r_oct, double *v_nodal);     // v = H^-1-form of the backward transform: v_k = a + b, v_k' = a - b
 // the vector kernels of pcg() with g / z in octant form (same device-side scalar protocol as their nodal counterparts in kernels_la.hip)
@@ -451,7 +462,8 @@ void fdmo_first_direction(hipStream_t s, const FdmOct &O, double *d, const doubl
 void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, double *g_oct, const double *h, const uint8_t *inert, const double *partials_dh, double *partials_out /*gg*/, const double *red = nullptr);
 void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z_oct, const double *partials_in /*2 sets*/, const double *red = nullptr,
                    bool gz_from_pass = false /* g . z from O.gz_part (left by fdmo_apply) instead of the second set of partials_in */,
-                   bool stream_x = false /* three components: non-temporal accesses to x (the caller keeps h in z's allocation, see pcg) */);
+                   bool stream_x = false /* three components: non-temporal accesses to x (the caller keeps h in z's allocation, see pcg) */,
+                   bool decided = false /* the preconditioner call in front ran the stopping test (PcgStopTest): take sc->stop instead of testing */);
 void fdmo_dot_owned(hipStream_t s, const FdmOct &O, const double *a_oct, const double *b_oct, double *partials, const PcgScalars *gate);   // block partials of a.b over the planes this rank owns
 // slab form: the pieces of one application around the two all-to-alls (ctx_prec.hip drives them)
 void fdmo_slab_pass(hipStream_t s, const FdmOct &O, int pass /*1, 2, 3*/, const double *in, double *out, const PcgScalars *gate, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

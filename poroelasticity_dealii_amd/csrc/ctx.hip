@@ -338,6 +338,7 @@ int solve_u_fdm(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info
   sys.oct.stream_x = shared;
   sys.prec.z = c->wz_u.p;
   sys.prec.gated = oct != nullptr;     // every launch of an iteration is gated: overshooting is cheap
+  sys.prec.decides_stop = oct && !oct->slab.on;   // octant and planar form: the first kernel of a call can run the stopping test (pcg decides whether it does)
   sys.prec.fn = [&](const double *g, double *z, const PrecCall &call) {
     // g, z in the layout of the form that is built (octants: three contiguous sweeps)
     if (!oct) {
@@ -346,7 +347,7 @@ int solve_u_fdm(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info
     }
     // octant form: pass 2 leaves g . z in oct->gz_part; the first application of a solve is not asked for it (k_fdmo_first_direction's dot)
     const bool gz = call.gz_partials && !separate_gz;
-    return fdm_precondition_u_form(c, g, z, call.gate, c->fdm_precision, scratch, gz ? c->fdm_oct.gz_part.p : nullptr) ? GzLeft::in_octant_form : GzLeft::nowhere;
+    return fdm_precondition_u_form(c, g, z, call.gate, c->fdm_precision, scratch, gz ? c->fdm_oct.gz_part.p : nullptr, call.stop) ? GzLeft::in_octant_form : GzLeft::nowhere;
   };
   const int rc = pcg(c, sys, opts, info);
   finish_u(c, false);
@@ -781,6 +782,10 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         lifting_from_wh(c);
       }
       asm_u_neumann(s, a, c->bface_order.p, c->bface_group_off, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
+      if (c->box_asm) {     // lift_u and neumann_u are final here: which of their lines the right-hand side kernel has to read
+        if (c->rhs_u_flags.n != (size_t)box_rhs_u_flag_count(c->n_u)) c->rhs_u_flags.alloc((size_t)box_rhs_u_flag_count(c->n_u));
+        box_rhs_u_flags(s, c->lift_u.p, c->neumann_u.p, c->n_u, c->rhs_u_flags.p);
+      }
       if (!c->diag_u.p) c->diag_u.alloc(c->n_u);
       la_copy(s, c->diag_u.p, c->diag_u_local.p, c->n_u);
       exchange_add(c, c->diag_u.p, c->n_u, c->comm.part.plane_u);
@@ -794,7 +799,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
     {
       Timed tm(c, "assemble_u_rhs");
       double *rhs = vec(c, PORO_VEC_RHS_U);
-      if (c->box_asm) box_rhs_u(s, c->dim, c->box_cpl, c->mat.biot_alpha, vec(c, PORO_VEC_P), c->lift_u.p, c->neumann_u.p, c->dir_mask.p, rhs);
+      if (c->box_asm) box_rhs_u(s, c->dim, c->box_cpl, c->mat.biot_alpha, vec(c, PORO_VEC_P), c->lift_u.p, c->neumann_u.p, c->dir_mask.p, rhs, c->rhs_u_flags.p);
       else {
         la_fill(s, rhs, 0.0, c->n_u);                                            // rhs_vector = 0 (:204)
         for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_rhs(s, a, cells, n_cells, vec(c, PORO_VEC_P), rhs); });

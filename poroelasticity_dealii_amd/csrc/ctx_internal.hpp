@@ -94,6 +94,7 @@ struct PrecCall {
                                       // (the first call of a solve; c->scal still holds the previous solve's state), in the single-reduction driver, and for a preconditioner that is not `gated`
   double *gz_partials = nullptr;      // where to leave the block partials of g . z over the owned rows; null: do not produce g . z (the driver's next kernel does)
   bool z1_ready = false;              // the residual update has already stored KrylovSystem::z1.scale D^-1 g in z1.out
+  PcgStopTest stop;                   // gg_part != null (only where prec.decides_stop): the call's first kernel runs the iteration's stopping test and the whole call is skipped when it holds
 };
 enum class GzLeft { nowhere, in_partials /* PrecCall::gz_partials */, in_octant_form /* FdmOct::gz_part, which k_fdmo_update_d reads */ };   // where a call left g . z; nowhere: the driver runs a dot kernel
 typedef std::function<GzLeft(const double *g, double *z, const PrecCall &)> PrecFn;
@@ -111,6 +112,7 @@ struct KrylovSystem {
   struct { PrecFn fn;                  // empty: Jacobi / none by poro_solver_opts::preconditioner
            double *z = nullptr;        // the vector the driver hands to fn (octant layout: Octant::form->z instead)
            bool gated = false;         // every launch of fn tests PrecCall::gate: iterations enqueued behind the finishing one cost ~1 us per launch
+           bool decides_stop = false;  // (gated, one rank) fn hands PrecCall::stop to its first kernel: the finishing iteration skips the preconditioner
            int applications = 0;       // operator applications inside one call (a polynomial's degree): counted in poro_solve_info::operator_applications
   } prec;
   struct { const FdmOct *form = nullptr;   // non-null (pcg() only, needs prec.fn): residual and z live in this octant (one rank) / quadrant (slabs) layout, `g` is unused
@@ -140,7 +142,7 @@ bool two_level_supported_p(poro_ctx *c);
 bool two_level_supported_pj(poro_ctx *c);  // ... for the pressure Jacobian with prescribed rows: the coarse box carries them as whole faces (its second table set is the coarse solve)
 void two_level_precondition_p(poro_ctx *c, double a, double kappa, const double *dinv, const double *g, double *z, double omega, const uint8_t *inert, Q1Set coarse_set = Q1Set::free_ends);   // z = omega D^-1 g + P (a M_H + kappa K_H)^-1 P^T g, 0 on the inert rows; Q1Set::fixed_ends: the coarse matrix without its prescribed rows
 void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double omega);   // z = omega D^-1 g + P B_H^-1 P^T g
-bool fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision, double *scratch, double *gz_part = nullptr);   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision, scratch, gz_part: of the octant form's passes
+bool fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision, double *scratch, double *gz_part = nullptr, const PcgStopTest &stop = PcgStopTest{});   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision, scratch, gz_part: of the octant form's passes
 void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision);   // nodal g -> the form that is built (or the nodal kernels of fdm_precondition_u) -> nodal z
 void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which = Q1Set::free_ends);
 void analyse_fdm_u(poro_ctx *c);

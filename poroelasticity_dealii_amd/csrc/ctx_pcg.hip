@@ -126,9 +126,14 @@ int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro
   int batch = expect > 0 ? (cheap_overshoot ? std::min(expect, 256) : std::max(1, expect - 1)) : (precond && !cheap_overshoot && !small ? 1 : 4);   // no history: a poll (~15 us through the mailbox) every 4 iterations
   PrecCall call;
   call.gate = sys.prec.gated ? sc : nullptr; call.gz_partials = part + kMaxPartials; call.z1_ready = sys.z1.out != nullptr;
+  // A gated preconditioner on one rank that can (prec.decides_stop): the stopping test of an iteration runs in the first kernel of its preconditioner call, on the g . g partials the
+  // residual update has just stored, and the finishing iteration skips the whole call - its z would never be read.  The direction update then takes the stored decision.
+  // PORO_PCG_FINAL_PREC (A/B hook, read once per solve): the test behind the preconditioner, in the direction update, as everywhere else
+  const bool stop_in_prec = oct && !multi && sys.prec.gated && sys.prec.decides_stop && std::getenv("PORO_PCG_FINAL_PREC") == nullptr;
   while (true) {
     for (int k = 0; k < batch; ++k) {
       ++it;
+      if (stop_in_prec) call.stop = PcgStopTest{sc, part, it};
       // operator (+ fused or separate d.h partials).  A fused dot runs over ALL local rows of the pre-exchange partial product, which
       // sums to the global d.Ad over the ranks; the separate kernel sees the exchanged h and therefore skips the upper shared plane.
       if (!sys.apply(d, h, part_dh)) pcg_dot_dh(s, sc, d, h, n_own, part_dh);
@@ -142,7 +147,7 @@ int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro
       }
       if (multi) { pcg_scalars_sum(s, part, 2, red + 1); allreduce_sum(c, red + 1, 2); }
       // (octant form: the transform passes leave their g . z partials in oct->gz_part - one per workgroup of pass 2, more than kMaxPartials - not in `part`)
-      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz == GzLeft::in_octant_form, sys.oct.stream_x);
+      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz == GzLeft::in_octant_form, sys.oct.stream_x, stop_in_prec);
       else pcg_update_d_fused(s, sc, (it - 1) & 1, it, x, d, g, sys.diag, zbuf, prec, n, part, multi ? red + 1 : nullptr);
     }
     post_and_wait(c, nullptr, 0, sc); hs = c->mailbox->sc;
@@ -153,6 +158,7 @@ int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro
   }
   // (the last poll returned after the finishing iteration: the solve is complete on the device; wall time of the solve on the host clock.  Operator applications: the initial
   // residual + one per iteration; launches enqueued behind the finishing iteration are no-ops and are not counted)
+  if (hs.stop) c->timers["fdm_u_final_prec_skipped"].enqueued++;      // (a count, no time: the solves whose finishing iteration skipped its preconditioner call)
   return finish_solve(sys, hs, hs.it + 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), info);
 }
 

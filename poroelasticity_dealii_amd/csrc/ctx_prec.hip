@@ -330,21 +330,21 @@ static void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, con
 // fdm_u_pass1, passes 2 and 3 are counted alongside and fdmo_apply takes one event pair per pass
 // gz_part != null (octant form; the others ignore it): pass 2 also leaves the partial sums of g . z there (returns true: no separate dot kernel)
 // scratch == null (octant form): the passes work on z itself (fp64 transforms only)
-bool fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgScalars *gate, int precision, double *scratch, double *gz_part) {
+bool fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgScalars *gate, int precision, double *scratch, double *gz_part, const PcgStopTest &stop) {
   Timed tm(c, "precondition_u_fdm");
   const FdmOct &O = c->fdm_oct;
-  if (O.slab.on) { fdm_precondition_u_slab(c, g, z, gate); return false; }
-  if (O.planar) { fdmo_apply_planar(c->stream, O, g, z, gate); return false; }
+  if (O.slab.on) { if (stop.gg_part) throw Error("fdm_precondition_u_form: the slab form runs no stopping test"); fdm_precondition_u_slab(c, g, z, gate); return false; }
+  if (O.planar) { fdmo_apply_planar(c->stream, O, g, z, gate, stop); return false; }
   const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
   if (!begin_sampled_dispatch(c, names[0])) {
-    fdmo_apply(c->stream, O, g, z, scratch, gate, nullptr, gz_part, precision);
+    fdmo_apply(c->stream, O, g, z, scratch, gate, nullptr, gz_part, precision, stop);
     return gz_part != nullptr;
   }
   c->timers[names[1]].enqueued++;
   c->timers[names[2]].enqueued++;
   hipEvent_t ev[6];
   for (auto &e : ev) e = event_get(c);
-  fdmo_apply(c->stream, O, g, z, scratch, gate, ev, gz_part, precision);
+  fdmo_apply(c->stream, O, g, z, scratch, gate, ev, gz_part, precision, stop);
   for (int k = 0; k < 3; ++k) {
     Timer &t = c->timers[names[k]];
     t.pending.emplace_back(ev[2 * k], ev[2 * k + 1]);

@@ -71,5 +71,49 @@ __device__ inline double sum_partials(const double *p, double *sh /*[5]*/, int n
   __syncthreads();
   return v;
 }
+// the same sum of the kMaxPartials slots with the same bits, computed by ONE wave without LDS or a barrier (any block shape, every wave for itself): lane l plays
+// threads l, 64 + l, 128 + l, 192 + l of sum_partials' 256-thread block in turn, and the butterfly of wave_sum leaves the same bits in every lane
+// In two steps, so that a kernel can issue the loads, then others of its own, and add up when it needs the sum
+constexpr int kPartialsPerLane = kMaxPartials / 64;
+__device__ inline void load_partials_wave(const double *p, double (&v)[kPartialsPerLane]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int k = 0; k < kMaxPartials / kBlock; ++k) v[w * (kMaxPartials / kBlock) + k] = p[64 * w + lane + k * kBlock];
+}
+__device__ inline double sum_partials_wave(const double (&v)[kPartialsPerLane]) {
+  double s[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    s[w] = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxPartials / kBlock; ++k) s[w] += v[w * (kMaxPartials / kBlock) + k];
+  }
+  // wave_sum of the four values, step by step side by side: the four exchanges of a step are independent and go out together (one after the other, the 24 dependent
+  // cross-lane exchanges cost the transform pass 8 us per launch)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    double t[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) t[w] = __shfl_xor(s[w], off, 64);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s[w] += t[w];
+  }
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+// gate of a launch inside a PCG iteration: closed once the solve has finished, or the stopping test in front of this preconditioner call held
+__device__ inline bool pcg_gate_closed(const PcgScalars *gate) { return gate && (gate->done | gate->finishing | gate->stop); }
+// PcgStopTest in the first kernel of a preconditioner call: nonzero (workgroup-uniform) when the iteration finishes the solve
+// (in two steps like the sum: pcg_stop_load requests everything the decision reads)
+struct PcgStopInputs { double gg_parts[kPartialsPerLane]; double tol; int max_iter; };
+__device__ inline void pcg_stop_load(const PcgStopTest &T, PcgStopInputs &in) { load_partials_wave(T.gg_part, in.gg_parts); in.tol = T.sc->tol; in.max_iter = T.sc->max_iter; }
+__device__ inline int pcg_stop_decide(const PcgStopTest &T, const PcgStopInputs &in) {
+  const double gg = sum_partials_wave(in.gg_parts);
+  const int stop = sqrt(gg) <= in.tol ? 1 : T.it >= in.max_iter ? 2 : 0;      // (k_fdmo_update_d's order: success first, then the cap)
+  if (stop && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) T.sc->stop = stop;
+  return stop;
+}
+__device__ inline int pcg_stop_test(const PcgStopTest &T) { PcgStopInputs in; pcg_stop_load(T, in); return pcg_stop_decide(T, in); }
 }  // namespace
 }  // namespace poro

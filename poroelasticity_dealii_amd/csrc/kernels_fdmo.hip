@@ -207,13 +207,17 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
 // stay in the 256 MiB memory-side cache from one kernel of the iteration to the next (as in k_pcg_update_d_fused).  d and z keep plain accesses, and so does the
 // finishing branch below on purpose: it runs once per solve, after the last use of d, g and z.
 template <int NC, bool XNT> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
-                                                                            const double *gz_part, int gz_n) {
+                                                                            const double *gz_part, int gz_n, int decided) {
   __shared__ double sh[5];
   if (sc->done) return;
-  const double gg = red ? red[0] : sum_partials(partials_in, sh), gz = red ? red[1] : gz_part ? sum_partials(gz_part, sh, gz_n) : sum_partials(partials_in + kMaxPartials, sh);
+  // decided: the stopping test of this iteration ran in front of the preconditioner call (PcgStopTest) and sc->stop holds its outcome - taken as it stands, never tested
+  // again: when it finished the solve, no kernel of the call has run, z and the g . z partials are stale and are neither read nor recorded
+  const double gg = red ? red[0] : sum_partials(partials_in, sh);
   const double res = sqrt(gg), gh_old = sc->gh2[parity], alpha = sc->alpha;
-  const bool conv = res <= sc->tol, fail = !conv && it >= sc->max_iter;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { sc->gg = gg; sc->gz = gz; sc->res = res; sc->it = it; }
+  const int stop = decided ? sc->stop : res <= sc->tol ? 1 : it >= sc->max_iter ? 2 : 0;
+  const bool conv = stop == 1, fail = stop == 2, no_z = decided && stop;
+  const double gz = no_z ? 0.0 : red ? red[1] : gz_part ? sum_partials(gz_part, sh, gz_n) : sum_partials(partials_in + kMaxPartials, sh);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { sc->gg = gg; if (!no_z) sc->gz = gz; sc->res = res; sc->it = it; }
   if (conv || fail) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_u; i += (int64_t)gridDim.x * kBlock) x[i] = fma(alpha, d[i], x[i]);
     if (blockIdx.x == 0 && threadIdx.x == 0) { sc->converged = conv ? 1 : 0; sc->finishing = 1; }
@@ -294,6 +298,7 @@ struct OctPass {
   int vec2;                     // rows are 16-byte aligned (even pitch, even chunk offsets): 16-byte block loads; 0: 8-byte loads (the scalar Q1 systems keep their nodal layout)
   double *gz_part;              // octant form, pass 2 (GZ instantiations): one partial sum of g . z per workgroup, see the epilogue of the first GEMM
   const PcgScalars *gate;       // inside a PCG iteration: the launch is a no-op once the solve has finished (the host enqueues iterations ahead of the device-side stopping test)
+  PcgStopTest stop;             // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (common.hpp); gg_part == null elsewhere
   unsigned long long *stamps;   // diagnostic (PORO_FDMO_STAMPS): per block 8 words: 100 MHz time at start / block in LDS / GEMM 1 done / intermediate in LDS / GEMM 2 done / stored, HW_ID, XCC_ID
 };
 
@@ -357,7 +362,15 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   constexpr int PADC = 16 * NL;                              // padded block columns
   extern __shared__ double L[];                              // PADN x LDMAX doubles (dynamic: more than 64 KB from NT = 6 on)
   __shared__ double gz_wave[GZ ? NW : 1];                    // (referenced by the GZ instantiations only: the others allocate nothing for it)
-  if (P.gate && (P.gate->done | P.gate->finishing)) return;
+  // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (PcgStopTest).  It replaces the read of `stop`, which workgroup 0 of this
+  // very launch writes.  Its inputs are requested in front of the gate's own loads, so that the two latencies overlap, and the decision falls before the block is staged:
+  // the test's registers are free again by then (held across the staging loads they cost the five-tile pass its third resident workgroup)
+  if (MODE == 0 && P.stop.gg_part) {
+    PcgStopInputs stop_in;
+    pcg_stop_load(P.stop, stop_in);
+    if (P.gate && (P.gate->done | P.gate->finishing)) return;
+    if (pcg_stop_decide(P.stop, stop_in)) return;
+  } else if (pcg_gate_closed(P.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
   int b, c, o, co = 0; int64_t base;
@@ -573,7 +586,15 @@ k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
   constexpr int PADC = 16 * NL;
   extern __shared__ float Lf[];                              // PADN x LDMAX floats (dynamic: more than 64 KB at NT = 8 only)
   __shared__ double gz_wave[GZ ? NW : 1];
-  if (P.gate && (P.gate->done | P.gate->finishing)) return;
+  // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (PcgStopTest).  It replaces the read of `stop`, which workgroup 0 of this
+  // very launch writes.  Its inputs are requested in front of the gate's own loads, so that the two latencies overlap, and the decision falls before the block is staged:
+  // the test's registers are free again by then (held across the staging loads they cost the five-tile pass its third resident workgroup)
+  if (MODE == 0 && P.stop.gg_part) {
+    PcgStopInputs stop_in;
+    pcg_stop_load(P.stop, stop_in);
+    if (P.gate && (P.gate->done | P.gate->finishing)) return;
+    if (pcg_stop_decide(P.stop, stop_in)) return;
+  } else if (pcg_gate_closed(P.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
   auto arow = [&](int q) { return 4 * kq + q; };             // row of accumulator register q inside its tile
@@ -717,13 +738,17 @@ struct Gemm2D {
   const double *A[8], *B[8]; double *C[8];   // per batch entry
   int scale; const double *lamM[8], *lamN[8]; double cM[8], cN[8];   // epilogue: C[m][n] /= cM lamM[m] + cN lamN[n] (inf -> 0)
   const PcgScalars *gate;
+  PcgStopTest stop;      // the first GEMM of a preconditioner call inside PCG: the iteration's stopping test (common.hpp); gg_part == null elsewhere
 };
 template <bool KCONTIG> struct GemmLds { static constexpr int LD = KCONTIG ? 18 : 80, SIZE = KCONTIG ? 64 * 18 : 16 * 80; };
 template <bool AK, bool BK>
 __global__ void __launch_bounds__(256) k_fdmo_gemm2d(Gemm2D G) {
   typedef GemmLds<AK> LA; typedef GemmLds<BK> LB;
   __shared__ double As[2][LA::SIZE], Bs[2][LB::SIZE];
-  if (G.gate && (G.gate->done | G.gate->finishing)) return;
+  if (G.stop.gg_part) {
+    if (G.gate && (G.gate->done | G.gate->finishing)) return;
+    if (pcg_stop_test(G.stop)) return;
+  } else if (pcg_gate_closed(G.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1, j = lane & 15, kq = lane >> 4;
   const int tiles_n = (G.N + 63) / 64, tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n, b = blockIdx.y;
   const int m0 = 64 * tm, n0 = 64 * tn;
@@ -1191,13 +1216,15 @@ void fdmo_finalize(FdmOct &O) {
   O.plans = plans;
 }
 
-void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part, int precision) {
+void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part, int precision, const PcgStopTest &stop) {
   const bool f32 = precision == PORO_FDM_FP32;     // fp32 transforms: float fragments, `scratch` holds the intermediate array as floats (g_oct, z_oct stay fp64)
   if (f32 && (O.slab.on || O.planar || !O.fwd32[0][0][0].p)) throw Error("fdmo_apply: fp32 transforms exist for the single-rank octant form only");
   OctPass P[3]; const int (&n_items)[3] = O.plans->n_items;
   for (int k = 0; k < 3; ++k) { P[k] = O.plans->pass[f32][k]; P[k].gate = gate; }
   if (gz_part && n_items[1] != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
   P[1].gz_part = gz_part;
+  P[0].stop = stop;                                // (pass 1 is the first kernel of the call in either precision)
+  if (stop.gg_part && stop.sc != gate) throw Error("fdmo_apply: a stopping test without the gate of its solve");
   PassStamps stamps; stamps.attach(s, P, n_items);
   // scratch == null (fp64 only): all three passes on z_oct itself, see "in place" at k_fdmo_pass.  The float intermediate of the fp32 mode needs its own array
   if (f32 && !scratch) throw Error("fdmo_apply: the fp32 transforms need the scratch array");
@@ -1318,11 +1345,12 @@ void fdmo_upload_dir_planar(FdmOct &O, int comp, int dir, const LineTables &T) {
   }
 }
 // z = blockdiag(A_cc)^-1 g in quadrant form: T = X Fx^T, U = (Fy T) / (cx lam_x + cy lam_y), V = Fy^T U, Z = V Fx  - four batched GEMMs over the 8 (component, quadrant) planes
-void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g, double *z, const PcgScalars *gate) {
+void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g, double *z, const PcgScalars *gate, const PcgStopTest &stop) {
   const int hx = O.h[0], hy = O.h[1], hxp = O.hxp; const int64_t co = O.co_stride;
   double *t1 = O.t.p, *t2 = O.t.p + O.n_oct;
   const int no = O.no, nb = 2 * no;                 // blocks: (component, quadrant) - or the two components alone without the parity split
-  Gemm2D G{}; G.nb = nb; G.gate = gate; G.rsC = hxp;
+  if (stop.gg_part && stop.sc != gate) throw Error("fdmo_apply_planar: a stopping test without the gate of its solve");
+  Gemm2D G{}; G.nb = nb; G.gate = gate; G.rsC = hxp; G.stop = stop;
   auto launch = [&](bool ak, bool bk) {
     const dim3 grid((unsigned)(((G.M + 63) / 64) * ((G.N + 63) / 64)), (unsigned)nb);
     if (ak && bk) hipLaunchKernelGGL((k_fdmo_gemm2d<true, true>), grid, 256, 0, s, G);
@@ -1333,6 +1361,7 @@ void fdmo_apply_planar(hipStream_t s, const FdmOct &O, const double *g, double *
   G.M = hy; G.N = hx; G.K = hx; G.rsA = hxp; G.csA = 1; G.rsB = 1; G.csB = hx; G.scale = 0;
   for (int b = 0; b < nb; ++b) { const int c = b / no, q = b % no; G.A[b] = g + (int64_t)b * co; G.B[b] = O.fwd[c][0][q & 1].p; G.C[b] = t1 + (int64_t)b * co; }
   launch(true, true);
+  G.stop = PcgStopTest{};                          // (the later GEMMs read the stored decision)
   // 2: U[my][mx] = sum_ky Fy[my][ky] T[ky][mx], divided by the eigenvalue sums
   G.M = hy; G.N = hx; G.K = hy; G.rsA = hy; G.csA = 1; G.rsB = hxp; G.csB = 1; G.scale = 1;
   for (int b = 0; b < nb; ++b) { const int c = b / no, q = b % no; G.A[b] = O.fwd[c][1][q >> 1].p; G.B[b] = t1 + (int64_t)b * co; G.C[b] = t2 + (int64_t)b * co;
@@ -1357,14 +1386,14 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
   if (single) PORO_OCT_LAUNCH(k_fdmo_update_g, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
   else PORO_OCT_LAUNCH(k_fdmo_update_g2, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
 }
-template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass) {
+template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool decided) {
   hipLaunchKernelGGL((k_fdmo_update_d<NC, XNT>), oct_grid(O.co_stride, NC), kBlock, 0, s, dims_of(O), sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red,
-                     gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0);
+                     gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0, decided ? 1 : 0);
 }
-void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x) {
-  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);       // (planar form)
-  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);
-  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass);
+void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x, bool decided) {
+  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);       // (planar form)
+  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);
+  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);
 }
 
 }  // namespace poro

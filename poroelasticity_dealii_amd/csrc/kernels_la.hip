@@ -27,7 +27,7 @@ __global__ void k_axpy(double *y, double a, const double *x, int64_t n) {
 }
 __global__ void k_dot(const double *a, const double *b, int64_t n, double *partials, const PcgScalars *gate) {
   __shared__ double sh[4];
-  if (gate && (gate->done | gate->finishing)) return;
+  if (pcg_gate_closed(gate)) return;
   double s = 0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) s += a[i] * b[i];
   s = block_sum(s, sh);
@@ -273,7 +273,7 @@ __global__ void k_scalars_start(PcgScalars *sc, const double *red, double abs_to
   sc->res0 = sc->res = sqrt(gg);
   sc->gg = gg; sc->gz = gz; sc->gh2[0] = gz; sc->gh2[1] = gz; sc->dh = 0; sc->alpha = 0; sc->beta = 0;
   sc->it = 0; sc->max_iter = max_iter;
-  sc->converged = sc->res <= sc->tol; sc->done = sc->converged; sc->finishing = 0;
+  sc->converged = sc->res <= sc->tol; sc->done = sc->converged; sc->finishing = 0; sc->stop = 0;
 }
 // g += alpha h and the partials of g.g, g.z (z = g / diag).  red != null (partitioned run): the all-reduced scalars are read instead
 // of the local block partials.  x is NOT touched here: x += alpha d rides in k_pcg_update_d_fused, which reads d anyway.
