@@ -46,7 +46,11 @@ struct PcgScalars {
 // block partials (sum_partials_wave: the bits of sum_partials).  Every workgroup of that kernel evaluates it for itself and returns at once when it holds; workgroup 0 stores
 // PcgScalars::stop, which the later kernels of the call test with `done` and `finishing` and from which the direction update takes its finishing branch - one decision per
 // iteration, so a z that was not computed is never read.  gg_part == null: no test here (the direction update decides, behind the preconditioner)
-struct PcgStopTest { PcgScalars *sc = nullptr; const double *gg_part = nullptr; int it = 0; };
+// Whoever runs the test (workgroup 0) also stores the sum in PcgScalars::gg.  per_wave: every wave adds up all the partials for itself even where the kernel could share the
+// sum out over its four waves (device_reduce.hpp; A/B hook PORO_PCG_STOP_PER_WAVE).  The word sits in the tail padding: the size of the struct, and with it the layout of the
+// kernel arguments that embed it, is what it was.
+struct PcgStopTest { PcgScalars *sc = nullptr; const double *gg_part = nullptr; int it = 0; int per_wave = 0; };
+static_assert(sizeof(PcgStopTest) == 24, "PcgStopTest is embedded in kernel arguments");
 
 // Mailbox in pinned, device-visible host memory: a one-block kernel at the end of an enqueued sequence copies a few scalars (and optionally the PCG state) into it and
 // then raises `seq` with a system-scope release; the host spins on `seq` instead of issuing a device-to-host copy + stream synchronisation (which idled the GPU
@@ -463,7 +467,8 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
 void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z_oct, const double *partials_in /*2 sets*/, const double *red = nullptr,
                    bool gz_from_pass = false /* g . z from O.gz_part (left by fdmo_apply) instead of the second set of partials_in */,
                    bool stream_x = false /* three components: non-temporal accesses to x (the caller keeps h in z's allocation, see pcg) */,
-                   bool decided = false /* the preconditioner call in front ran the stopping test (PcgStopTest): take sc->stop instead of testing */);
+                   bool decided = false /* the preconditioner call in front ran the stopping test (PcgStopTest): take sc->stop instead of testing */,
+                   bool gg_stored = false /* with `decided`: take g . g from PcgScalars::gg, where that test left the sum of the first set of partials_in, instead of adding them up again */);
 void fdmo_dot_owned(hipStream_t s, const FdmOct &O, const double *a_oct, const double *b_oct, double *partials, const PcgScalars *gate);   // block partials of a.b over the planes this rank owns
 // slab form: the pieces of one application around the two all-to-alls (ctx_prec.hip drives them)
 void fdmo_slab_pass(hipStream_t s, const FdmOct &O, int pass /*1, 2, 3*/, const double *in, double *out, const PcgScalars *gate, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

@@ -130,10 +130,14 @@ int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro
   // residual update has just stored, and the finishing iteration skips the whole call - its z would never be read.  The direction update then takes the stored decision.
   // PORO_PCG_FINAL_PREC (A/B hook, read once per solve): the test behind the preconditioner, in the direction update, as everywhere else
   const bool stop_in_prec = oct && !multi && sys.prec.gated && sys.prec.decides_stop && std::getenv("PORO_PCG_FINAL_PREC") == nullptr;
+  // Two more A/B hooks, read once per solve, both restoring what was there before: PORO_PCG_STOP_PER_WAVE - every wave of the transform pass adds up all the g . g partials for
+  // itself (four-wave workgroups share the sum out otherwise); PORO_PCG_GG_RESUM - the direction update adds them up once more instead of reading the sum the test stored
+  const int stop_per_wave = std::getenv("PORO_PCG_STOP_PER_WAVE") != nullptr ? 1 : 0;
+  const bool gg_stored = stop_in_prec && std::getenv("PORO_PCG_GG_RESUM") == nullptr;
   while (true) {
     for (int k = 0; k < batch; ++k) {
       ++it;
-      if (stop_in_prec) call.stop = PcgStopTest{sc, part, it};
+      if (stop_in_prec) call.stop = PcgStopTest{sc, part, it, stop_per_wave};
       // operator (+ fused or separate d.h partials).  A fused dot runs over ALL local rows of the pre-exchange partial product, which
       // sums to the global d.Ad over the ranks; the separate kernel sees the exchanged h and therefore skips the upper shared plane.
       if (!sys.apply(d, h, part_dh)) pcg_dot_dh(s, sc, d, h, n_own, part_dh);
@@ -147,7 +151,7 @@ int pcg(poro_ctx *c, const KrylovSystem &sys, const poro_solver_opts *opts, poro
       }
       if (multi) { pcg_scalars_sum(s, part, 2, red + 1); allreduce_sum(c, red + 1, 2); }
       // (octant form: the transform passes leave their g . z partials in oct->gz_part - one per workgroup of pass 2, more than kMaxPartials - not in `part`)
-      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz == GzLeft::in_octant_form, sys.oct.stream_x, stop_in_prec);
+      if (oct) fdmo_update_d(s, *oct, sc, (it - 1) & 1, it, x, d, zbuf, part, multi ? red + 1 : nullptr, gz == GzLeft::in_octant_form, sys.oct.stream_x, stop_in_prec, gg_stored);
       else pcg_update_d_fused(s, sc, (it - 1) & 1, it, x, d, g, sys.diag, zbuf, prec, n, part, multi ? red + 1 : nullptr);
     }
     post_and_wait(c, nullptr, 0, sc); hs = c->mailbox->sc;

@@ -111,9 +111,35 @@ __device__ inline void pcg_stop_load(const PcgStopTest &T, PcgStopInputs &in) { 
 __device__ inline int pcg_stop_decide(const PcgStopTest &T, const PcgStopInputs &in) {
   const double gg = sum_partials_wave(in.gg_parts);
   const int stop = sqrt(gg) <= in.tol ? 1 : T.it >= in.max_iter ? 2 : 0;      // (k_fdmo_update_d's order: success first, then the cap)
-  if (stop && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) T.sc->stop = stop;
+  // workgroup 0 also leaves the sum itself, stop or not: the direction update of the iteration reads that word instead of adding up the same partials again
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { T.sc->gg = gg; if (stop) T.sc->stop = stop; }
   return stop;
 }
 __device__ inline int pcg_stop_test(const PcgStopTest &T) { PcgStopInputs in; pcg_stop_load(T, in); return pcg_stop_decide(T, in); }
+// The same test shared out over the four waves of a 256-thread workgroup that has a barrier of its own to offer: thread t loads the kMaxPartials / kBlock partials that
+// thread t of sum_partials' block adds (a quarter of the loads and none of the 24 dependent exchanges of the all-in-one-wave form above per wave), every wave leaves its
+// wave_sum in sh[wave], and behind the caller's barrier every thread forms block_sum's (s0 + s1) + (s2 + s3) - the order of additions, hence the bits, of sum_partials.
+//   pcg_stop_load_quarter  - requests the inputs (8 registers until the next step)
+//   pcg_stop_post_quarter  - wave sum -> sh[wave]; the caller's barrier follows
+//   pcg_stop_decide_quarters - behind that barrier: nonzero (workgroup-uniform) when the iteration finishes the solve
+struct PcgStopQuarter { double part[kMaxPartials / kBlock]; double tol; int max_iter; };
+__device__ inline void pcg_stop_load_quarter(const PcgStopTest &T, PcgStopQuarter &in) {
+#pragma unroll
+  for (int k = 0; k < kMaxPartials / kBlock; ++k) in.part[k] = T.gg_part[threadIdx.x + k * kBlock];
+  in.tol = T.sc->tol; in.max_iter = T.sc->max_iter;
+}
+__device__ inline void pcg_stop_post_quarter(const PcgStopQuarter &in, double *sh /*[4]*/) {
+  double v = 0;
+#pragma unroll
+  for (int k = 0; k < kMaxPartials / kBlock; ++k) v += in.part[k];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+}
+__device__ inline int pcg_stop_decide_quarters(const PcgStopTest &T, const PcgStopQuarter &in, const double *sh) {
+  const double gg = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  const int stop = sqrt(gg) <= in.tol ? 1 : T.it >= in.max_iter ? 2 : 0;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { T.sc->gg = gg; if (stop) T.sc->stop = stop; }
+  return stop;
+}
 }  // namespace
 }  // namespace poro

@@ -207,16 +207,18 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
 // stay in the 256 MiB memory-side cache from one kernel of the iteration to the next (as in k_pcg_update_d_fused).  d and z keep plain accesses, and so does the
 // finishing branch below on purpose: it runs once per solve, after the last use of d, g and z.
 template <int NC, bool XNT> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
-                                                                            const double *gz_part, int gz_n, int decided) {
+                                                                            const double *gz_part, int gz_n, int decided /* 2: and sc->gg holds g . g */) {
   __shared__ double sh[5];
   if (sc->done) return;
   // decided: the stopping test of this iteration ran in front of the preconditioner call (PcgStopTest) and sc->stop holds its outcome - taken as it stands, never tested
   // again: when it finished the solve, no kernel of the call has run, z and the g . z partials are stale and are neither read nor recorded
-  const double gg = red ? red[0] : sum_partials(partials_in, sh);
+  // decided == 2: workgroup 0 of the kernel that ran the test stored the sum it tested (the same partials in the same order: the same bits) - one word instead of 8 KB and four barriers
+  const double gg = red ? red[0] : decided == 2 ? sc->gg : sum_partials(partials_in, sh);
   const double res = sqrt(gg), gh_old = sc->gh2[parity], alpha = sc->alpha;
   const int stop = decided ? sc->stop : res <= sc->tol ? 1 : it >= sc->max_iter ? 2 : 0;
   const bool conv = stop == 1, fail = stop == 2, no_z = decided && stop;
   const double gz = no_z ? 0.0 : red ? red[1] : gz_part ? sum_partials(gz_part, sh, gz_n) : sum_partials(partials_in + kMaxPartials, sh);
+  // (decided == 2: the other workgroups may still be reading sc->gg while workgroup 0 stores it here - the very value it has just read, so the race is harmless)
   if (blockIdx.x == 0 && threadIdx.x == 0) { sc->gg = gg; if (!no_z) sc->gz = gz; sc->res = res; sc->it = it; }
   if (conv || fail) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_u; i += (int64_t)gridDim.x * kBlock) x[i] = fma(alpha, d[i], x[i]);
@@ -365,11 +367,22 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (PcgStopTest).  It replaces the read of `stop`, which workgroup 0 of this
   // very launch writes.  Its inputs are requested in front of the gate's own loads, so that the two latencies overlap, and the decision falls before the block is staged:
   // the test's registers are free again by then (held across the staging loads they cost the five-tile pass its third resident workgroup)
+  // Four-wave workgroups (QUARTERS) share the sum out instead: each wave adds a quarter of the partials (8 registers, requested with the staging loads), the four wave sums
+  // meet in LDS at the staging barrier and the decision falls behind it - a workgroup that stops has stored nothing by then.  P.stop.per_wave keeps the form above (A/B hook)
+  // (the Octant variant only: the slab form refuses a stopping test and the scalar passes are handed none, so their pass 1 keeps the form above and pays nothing for this one)
+  constexpr bool QUARTERS = MODE == 0 && VAR == 0 && NW == 4;
+  __shared__ double stop_wave[QUARTERS ? 4 : 1];             // (referenced by the QUARTERS instantiations only)
+  [[maybe_unused]] PcgStopQuarter stop_q; [[maybe_unused]] bool stop_pending = false;
   if (MODE == 0 && P.stop.gg_part) {
-    PcgStopInputs stop_in;
-    pcg_stop_load(P.stop, stop_in);
-    if (P.gate && (P.gate->done | P.gate->finishing)) return;
-    if (pcg_stop_decide(P.stop, stop_in)) return;
+    if (QUARTERS && !P.stop.per_wave) {
+      if (P.gate && (P.gate->done | P.gate->finishing)) return;
+      pcg_stop_load_quarter(P.stop, stop_q); stop_pending = true;
+    } else {
+      PcgStopInputs stop_in;
+      pcg_stop_load(P.stop, stop_in);
+      if (P.gate && (P.gate->done | P.gate->finishing)) return;
+      if (pcg_stop_decide(P.stop, stop_in)) return;
+    }
   } else if (pcg_gate_closed(P.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
@@ -423,11 +436,13 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
       else if (f_vec2) stage[u] = (e < TOT && r < R && c2 < C) ? *reinterpret_cast<const double2 *>(in + base_in + (int64_t)r * P.row_stride + c2) : double2{0.0, 0.0};
       else { const double *src = in + base_in + (int64_t)r * P.row_stride + c2; stage[u].x = (e < TOT && r < R && c2 < C) ? src[0] : 0.0; stage[u].y = (e < TOT && r < R && c2 + 1 < C) ? src[1] : 0.0; }
     }
+    if constexpr (QUARTERS) { if (stop_pending) pcg_stop_post_quarter(stop_q, stop_wave); }   // (the partials were requested first: they are here before the block is)
 #pragma unroll
     for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP); if (e < TOT) *reinterpret_cast<double2 *>(&L[r * LD1 + c2]) = stage[u]; }
   }
   // transform-matrix fragments in two rotating register buffers of 4 k-steps: the 2 NT chunks of the two GEMMs form one sequence, and a buffer is refilled with the
   // chunk after next as soon as the MFMAs that used it have been issued
+  // (deeper buffers for the General variant, whose launches never fill the chip - half a GEMM or a whole one per buffer - were measured and are SLOWER there: DESIGN, "Latency-bound work")
   constexpr int CHK = EXTRA ? 2 : 4, NCH = Gm::KKP / CHK;     // k-steps per chunk (two fragment streams at NT = 5: smaller chunks keep the kernel within the registers of three resident workgroups), chunks per GEMM
   double tf[2][NS][CHK];
   auto load_chunk = [&](int buf, int step) {                 // step < NCH: chunk `step` of T1, else chunk step - NCH of T2
@@ -484,6 +499,7 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   zero_acc();
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();
+  if constexpr (QUARTERS) { if (stop_pending && pcg_stop_decide_quarters(P.stop, stop_q, stop_wave)) return; }   // (workgroup-uniform; the block and fragment loads are out, but nothing is stored outside LDS yet - bar the diagnostic stamp(0))
   stamp(1);
   if (heavy) gemm(CF{}, L1c{}, S0c{}, std::integral_constant<bool, CORNER>{}, P.kk1); else gemm(CF{}, L1c{}, S0c{}, std::false_type{}, P.kk1);
   __syncthreads();                                   // everybody has finished reading the input block
@@ -589,11 +605,20 @@ k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
   // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (PcgStopTest).  It replaces the read of `stop`, which workgroup 0 of this
   // very launch writes.  Its inputs are requested in front of the gate's own loads, so that the two latencies overlap, and the decision falls before the block is staged:
   // the test's registers are free again by then (held across the staging loads they cost the five-tile pass its third resident workgroup)
+  // (four-wave workgroups: a quarter of the sum per wave, as in k_fdmo_pass)
+  constexpr bool QUARTERS = MODE == 0 && NW == 4;
+  __shared__ double stop_wave[QUARTERS ? 4 : 1];
+  [[maybe_unused]] PcgStopQuarter stop_q; [[maybe_unused]] bool stop_pending = false;
   if (MODE == 0 && P.stop.gg_part) {
-    PcgStopInputs stop_in;
-    pcg_stop_load(P.stop, stop_in);
-    if (P.gate && (P.gate->done | P.gate->finishing)) return;
-    if (pcg_stop_decide(P.stop, stop_in)) return;
+    if (QUARTERS && !P.stop.per_wave) {
+      if (P.gate && (P.gate->done | P.gate->finishing)) return;
+      pcg_stop_load_quarter(P.stop, stop_q); stop_pending = true;
+    } else {
+      PcgStopInputs stop_in;
+      pcg_stop_load(P.stop, stop_in);
+      if (P.gate && (P.gate->done | P.gate->finishing)) return;
+      if (pcg_stop_decide(P.stop, stop_in)) return;
+    }
   } else if (pcg_gate_closed(P.gate)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
@@ -615,6 +640,7 @@ k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
       if constexpr (MODE == 0) { const double2 v = ok ? *reinterpret_cast<const double2 *>(in + at) : double2{0.0, 0.0}; stage[u] = float2{(float)v.x, (float)v.y}; }
       else stage[u] = ok ? *reinterpret_cast<const float2 *>(inf + at) : float2{0.f, 0.f};
     }
+    if constexpr (QUARTERS) { if (stop_pending) pcg_stop_post_quarter(stop_q, stop_wave); }
 #pragma unroll
     for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP); if (e < TOT) *reinterpret_cast<float2 *>(&Lf[r * LD1 + c2]) = stage[u]; }
   }
@@ -671,6 +697,7 @@ k_fdmo_pass_f32(OctPass P, const double *in, double *out) {
   zero_acc();
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();
+  if constexpr (QUARTERS) { if (stop_pending && pcg_stop_decide_quarters(P.stop, stop_q, stop_wave)) return; }
   if (heavy) gemm(CF{}, L1c{}, S0c{}, std::integral_constant<bool, CORNER>{}, P.kk1); else gemm(CF{}, L1c{}, S0c{}, std::false_type{}, P.kk1);
   __syncthreads();
   // ---- first result -> LDS in the layout of the second GEMM (MODE 1: divided by the eigenvalue sums on the way) ----
@@ -1386,14 +1413,15 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
   if (single) PORO_OCT_LAUNCH(k_fdmo_update_g, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
   else PORO_OCT_LAUNCH(k_fdmo_update_g2, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
 }
-template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool decided) {
+template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, int decided) {
   hipLaunchKernelGGL((k_fdmo_update_d<NC, XNT>), oct_grid(O.co_stride, NC), kBlock, 0, s, dims_of(O), sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red,
-                     gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0, decided ? 1 : 0);
+                     gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0, decided);
 }
-void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x, bool decided) {
-  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);       // (planar form)
-  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);
-  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, decided);
+void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x, bool decided, bool gg_stored) {
+  const int dec = decided ? (gg_stored && !red ? 2 : 1) : 0;
+  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);       // (planar form)
+  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
+  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
 }
 
 }  // namespace poro

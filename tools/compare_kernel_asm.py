@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the kernels of two AMDGPU assembly files (hipcc --cuda-device-only -S): symbol sets, then per kernel either the whole
 text (function body + .amdhsa_kernel descriptor; default) or, with --resources, the figures that decide occupancy.
-Only the function-index part of local labels (.LBB<n>_, .Lfunc_end<n>) is normalised; instantiation order does not matter."""
+Only the function-index part of local labels (.LBB<n>_, .Lfunc_end<n>, and the "Header=BB<n>_" of loop comments) is normalised; instantiation order does not matter."""
 import re
 import sys
 
@@ -11,6 +11,7 @@ FIGURES = ("next_free_vgpr", "accum_offset", "private_segment_fixed_size", "grou
 def kernels(path):
     text = open(path).read()
     text = re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", text))
+    text = re.sub(r"Header=BB\d+_", "Header=BB_", text)      # (loop comments carry the function index too)
     out = {}
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n(.*?)^\t\.end_amdhsa_kernel", text, re.M | re.S):
         name, desc = m.group(1), m.group(2)
