@@ -273,7 +273,11 @@ typedef struct poro_solve_info {
   double  initial_residual;
   double  final_residual;
   double  seconds;       /* wall time of the solve on device */
-  int64_t operator_applications;
+  int64_t operator_applications;   /* of the Krylov solves: iterations + 1 (the initial residual and one per iteration); iterations + 2 where a partitioned run takes the
+                                      single-reduction recurrence (it applies the operator to P^-1 g before it knows that g has converged; Jacobi, no preconditioner, block
+                                      FDM outside the slab form, two-level); (poly_degree + 1) * (iterations + 1) with PORO_PREC_CHEBYSHEV on either recurrence - the USEFUL
+                                      applications: the single-reduction recurrence launches one polynomial and one operator application more, for the last z.  The SSOR /
+                                      ILU(0) fidelity modes count what they applied; a direct fast-diagonalisation solve reports 1 (the check of its residual) */
 } poro_solve_info;
 
 typedef struct poro_ctx poro_ctx;
