@@ -457,6 +457,28 @@ int  poro_timers_reset(poro_ctx *ctx);            /* clears the accumulators and
 int  poro_timers_enable(poro_ctx *ctx, int on);   /* 0: off; 1: events on every launch; k > 1: on every k-th launch of a family (the events cost ~2.5 us per launch), poro_timers_get scales the sampled time to all launches */
 int  poro_timers_get(poro_ctx *ctx, const char *name, double *seconds, int64_t *launches);
 
+/* Form of the block fast-diagonalisation preconditioner of the displacement system (PORO_PREC_FDM; appended entry points, no struct changes: PORO_ABI_VERSION stays 4).
+ *   PORO_FDM_FORM_DEFAULT:       the octant form where every direction of a single-rank 3D box is mirror-symmetric for every component, else the nodal kernels.
+ *   PORO_FDM_FORM_PER_DIRECTION: the octant form's three contiguous passes (g . z out of pass 2, the stopping test in pass 1, h and z in one array) where only SOME
+ *                                directions are mirror-symmetric - a consolidation column held at the bottom and loaded at the top, a graded tensor-product grid.
+ *                                Direction d is split in parity halves iff every component has the same condition at both of its ends and the eigenvectors of its line came
+ *                                out even or odd; otherwise it keeps whole-length transforms.  A box whose directions are all split runs the octant form as always; one
+ *                                with a transformed line of more than 128 entries keeps the nodal kernels.  fp64 transforms only: with PORO_FDM_FP32 requested as well,
+ *                                poro_ctx_get_fdm_precision reports PORO_FDM_FP64.
+ * Never chosen automatically.  The same mathematics in fp64: iteration counts within +-1 of the nodal kernels'.  Honoured by single-rank 3D contexts; partitioned
+ * contexts, 2D and the coarse box of PORO_PREC_TWO_LEVEL record the request and run what they ran.  The environment variable PORO_FDMO_FORM=per-direction|default sets
+ * the initial request of every context when it is created.
+ * poro_ctx_set_fdm_form: any time between solves; a block FDM built in the other form is released and built again at its next use.  An unknown value is an error.
+ * poro_ctx_get_fdm_form: `effective` = what PORO_PREC_FDM runs on this context, split[d] = 1 where direction d is split in parities.  It BUILDS the block FDM where the
+ * context can use it (host eigenproblems, uploads, a stream synchronise), so that the answer is final: call it outside timed regions.  A context that cannot use
+ * PORO_PREC_FDM on the displacement system, and a partitioned one before its first solve, report PORO_FDM_RUNS_NODAL.  split may be null.
+ * The timer family "fdm_u_per_direction_form" counts the solves that ran the form. */
+#define PORO_FDM_FORM_DEFAULT 0
+#define PORO_FDM_FORM_PER_DIRECTION 1
+enum { PORO_FDM_RUNS_NODAL = 0, PORO_FDM_RUNS_OCTANT = 1, PORO_FDM_RUNS_PER_DIRECTION = 2, PORO_FDM_RUNS_SLAB = 3, PORO_FDM_RUNS_PLANAR = 4 };
+int  poro_ctx_set_fdm_form(poro_ctx *ctx, int32_t form);
+int  poro_ctx_get_fdm_form(poro_ctx *ctx, int32_t *requested, int32_t *effective, int32_t split[3]);
+
 #ifdef __cplusplus
 }
 #endif

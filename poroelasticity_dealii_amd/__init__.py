@@ -20,6 +20,8 @@ OP_CSR, OP_MATRIX_FREE = 0, 1
 SCATTER_COLOURED, SCATTER_ATOMIC = 0, 1
 OPFORM_GENERAL, OPFORM_HYBRID = 0, 1
 FDM_FP64, FDM_FP32 = 0, 1
+FDM_FORM_DEFAULT, FDM_FORM_PER_DIRECTION = 0, 1
+FDM_RUNS_NODAL, FDM_RUNS_OCTANT, FDM_RUNS_PER_DIRECTION, FDM_RUNS_SLAB, FDM_RUNS_PLANAR = 0, 1, 2, 3, 4
 MAT_A_U, MAT_MASS_P, MAT_LAPLACE_P, MAT_JACOBIAN_P = 0, 1, 2, 3
 VEC_U, VEC_RHS_U, VEC_P, VEC_P_OLD, VEC_DP, VEC_RESIDUAL_P, VEC_EPSV, VEC_EPSV0, VEC_SOURCE_P = range(9)
 VEC_STRAIN0, VEC_PROJ_RHS0, VEC_DIAG_U, VEC_STRESS0 = 16, 32, 48, 64
@@ -106,7 +108,8 @@ HIP_SYMBOLS = [
     "poro_state_save", "poro_state_restore", "poro_disp_assemble_system", "poro_disp_solve", "poro_supports_preconditioner", "poro_pres_assemble_residual", "poro_pres_apply_boundary_values", "poro_pres_assemble_jacobian", "poro_pres_solve",
     "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
     "poro_pres_estimate_error", "poro_state_transfer_p",
-    "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get"]
+    "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get",
+    "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form"]
 
 _hip = None
 _host = None
@@ -134,6 +137,8 @@ def load_hip():
         L.poro_ctx_get_operator_form.argtypes = [C.c_void_p, _ip, _lp, _lp]
         L.poro_ctx_set_fdm_precision.argtypes = [C.c_void_p, C.c_int32]
         L.poro_ctx_get_fdm_precision.argtypes = [C.c_void_p, _ip, _ip]
+        L.poro_ctx_set_fdm_form.argtypes = [C.c_void_p, C.c_int32]
+        L.poro_ctx_get_fdm_form.argtypes = [C.c_void_p, _ip, _ip, _ip]
         L.poro_comm_unique_id.argtypes = [C.c_void_p]
         L.poro_ctx_comm_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
         L.poro_ctx_comm_init_callbacks.argtypes = [C.c_void_p, ALLREDUCE_FN, SENDRECV_FN, C.c_void_p]
@@ -491,6 +496,18 @@ class Context:
         self._chk(self.L.poro_ctx_get_fdm_precision(self.ptr, C.byref(r), C.byref(e)))
         return r.value, e.value
 
+    def set_fdm_form(self, form):
+        """FDM_FORM_DEFAULT (the octant form where every direction is mirror-symmetric, else the nodal kernels) or FDM_FORM_PER_DIRECTION: the octant form's three
+        contiguous passes on single-rank 3D boxes where only some directions are (one-sided faces, graded lines).  Any time between solves; a block FDM built in the
+        other form is rebuilt at its next use.  Partitioned and 2D contexts record the request and run what they ran; raises on an unknown value"""
+        self._chk(self.L.poro_ctx_set_fdm_form(self.ptr, int(form)))
+
+    def get_fdm_form(self):
+        """(requested, effective FDM_RUNS_*, (split_x, split_y, split_z)); builds the block FDM where the context can use it, so that the answer is final"""
+        r, e, m = C.c_int32(), C.c_int32(), (C.c_int32 * 3)()
+        self._chk(self.L.poro_ctx_get_fdm_form(self.ptr, C.byref(r), C.byref(e), m))
+        return r.value, e.value, tuple(int(v) for v in m)
+
     def _len(self, which):
         return self.n_u if which in (VEC_U, VEC_RHS_U, VEC_DIAG_U) else self.n_p
 
@@ -661,25 +678,29 @@ def rccl_unique_id():
     return buf.raw
 
 
+_FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit flags word (bits 0-7 and the Chebyshev fields from bit 8 and bit 16 are taken)
+
+
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
+                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
     Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
-    hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it)."""
+    hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it).
+    fdm_per_direction=True: FDM_FORM_PER_DIRECTION for the block FDM of the displacement system (Context.set_fdm_form; carried over to every adapted mesh)."""
     H = load_host()
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
     if refine_every is not None:
         last = C.c_void_p()
-        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                                         int(refine_every), refine_fraction, coarsen_fraction, trace.ctypes.data_as(_dp), max_rows, C.byref(ctx), C.byref(last))
         if rows < 0:
             raise RuntimeError(H.poro_host_last_error().decode())
         return trace[:rows], Context(Problem(last.value) if last.value else problem, ptr=ctx)
-    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
+    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
                            trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
     if rows < 0:
         raise RuntimeError(H.poro_host_last_error().decode())
@@ -694,10 +715,10 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False):
         self.H = load_host()
         self.max_fss = max_fss
-        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
+        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
         if not h:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         self.h = C.c_void_p(h)

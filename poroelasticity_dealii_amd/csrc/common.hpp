@@ -126,6 +126,10 @@ struct FdmOct {
   int nc = 3;                                     // components per node: 3; 2 for the planar (2D) form, which is the quadrant form with a single plane
   bool planar = false;                            // 2D: the transforms are batched tiled GEMMs over whole (component, quadrant) planes (fwd = row-major h x h matrices F[mode][node])
   int own_z = 0;                                  // local node planes that count in dot products (the upper shared plane belongs to the neighbour)
+  // per-direction form (fdmo_init_per_direction; one rank, 3D, opt-in): only the directions of split_mask (bit d) are split in parities, the others keep whole lines (h[d] = n[d]);
+  // no = 2^(split directions) parts per component, Q[c][part][kz][ky][kx] with the parity bits of the split directions packed in the order x, y, z; even row pitch always.
+  // nt_z: tiles of pass 2 (the z line), nt those of passes 1 / 3 (x-y planes); every other form has nt_z = nt
+  bool per_dir = false; int split_mask = 7, nt_z = 0;
   struct Slab {
     bool on = false; int n_ranks = 1, rank = 0;
     int ng = 0, hzg = 0;                          // global nodes of a z line / rows of a transposed block (half length with the parity split, ng without)
@@ -240,6 +244,9 @@ struct poro_ctx {
   int operator_form = 0; poro::HybridPlan hyb;
   // transform precision of the displacement system's block FDM where it runs in the single-rank 3D octant form (poro_ctx_set_fdm_precision); every other form ignores it
   int fdm_precision = 0;
+  // form of the displacement system's block FDM (poro_ctx_set_fdm_form): PORO_FDM_FORM_PER_DIRECTION is honoured by single-rank 3D contexts only; fdm_form_fixed: the nested
+  // coarse box of a two-level preconditioner, which keeps the default whatever is asked
+  int fdm_form = 0; bool fdm_form_fixed = false;
   poro::DevBuf<uint8_t> dir_mask, node_mask; poro::DevBuf<double> dir_val; poro::DevBuf<int32_t> dir_dofs;
   std::vector<int32_t> h_dir_dof; std::vector<double> h_dir_val;
   poro::ConsDev cons_u, cons_p;
@@ -434,7 +441,8 @@ bool fdmo_usable(int dim, const int nn[3]);          // 3D, half lines of at mos
 void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s);   // sizes + buffers
 // slab-partitioned form: nn = LOCAL nodes; layers[q] = node planes rank q holds minus one (its cell layers x degree); the last direction's matrices are uploaded for the GLOBAL line
 void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int rank, const std::vector<int> &node_layers, bool has_upper, hipStream_t s);
-void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required
+void fdmo_init_per_direction(FdmOct &O, const int nn[3], const double coef[3][3], const FdmFormDecision &D, hipStream_t s);   // per-direction form: sizes + buffers from the decision of fdm_form_decide
+void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required (per-direction form: by its split directions only)
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
                 double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr,

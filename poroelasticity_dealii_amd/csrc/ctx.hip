@@ -331,7 +331,9 @@ int solve_u_fdm(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info
   // "fdm_u_shared_buffers" counts the solves that ran on the shared layout (a count, no time; it counts whether or not the context's timing is on).
   const bool shared = oct && !oct->slab.on && !oct->planar && std::getenv("PORO_FDMO_SEPARATE_BUFFERS") == nullptr;
   if (shared) c->timers["fdm_u_shared_buffers"].enqueued++;
-  double *const scratch = shared && c->fdm_precision != PORO_FDM_FP32 ? nullptr : c->fdm_oct.t.p;
+  if (oct && oct->per_dir) c->timers["fdm_u_per_direction_form"].enqueued++;      // (likewise a count: the solves that ran the per-direction form)
+  const int precision = oct && oct->per_dir ? PORO_FDM_FP64 : c->fdm_precision;    // (the per-direction form has fp64 fragments only)
+  double *const scratch = shared && precision != PORO_FDM_FP32 ? nullptr : c->fdm_oct.t.p;
   KrylovSystem sys = krylov_u(c, c->dir_mask.p, false, c->pcg_hint_fdm_u);
   if (shared) sys.h = c->fdm_oct.z.p;
   sys.oct.form = oct;
@@ -347,7 +349,7 @@ int solve_u_fdm(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info
     }
     // octant form: pass 2 leaves g . z in oct->gz_part; the first application of a solve is not asked for it (k_fdmo_first_direction's dot)
     const bool gz = call.gz_partials && !separate_gz;
-    return fdm_precondition_u_form(c, g, z, call.gate, c->fdm_precision, scratch, gz ? c->fdm_oct.gz_part.p : nullptr, call.stop) ? GzLeft::in_octant_form : GzLeft::nowhere;
+    return fdm_precondition_u_form(c, g, z, call.gate, precision, scratch, gz ? c->fdm_oct.gz_part.p : nullptr, call.stop) ? GzLeft::in_octant_form : GzLeft::nowhere;
   };
   const int rc = pcg(c, sys, opts, info);
   finish_u(c, false);
@@ -541,6 +543,7 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       poro_ctx *box = nullptr;
       if (poro_ctx_create(desc->coarse.box_problem, device, PORO_OP_MATRIX_FREE, &box) != 0) throw Error(std::string("poro_desc.coarse.box_problem: ") + poro_last_error());
       PORO_HIP(hipStreamSynchronize(box->stream)); (void)hipStreamDestroy(box->stream); box->stream = c->stream; box->borrowed_stream = true;
+      box->fdm_form = PORO_FDM_FORM_DEFAULT; box->fdm_form_fixed = true;      // (the coarse solve keeps the default form of the block FDM, whatever PORO_FDMO_FORM says)
       box->comm.force_multi = false;      // the box is solved whole on every rank (replicated coarse solve): never the partitioned code path
       c->two_level.box = box;
       setup_two_level(c.get(), desc);
@@ -556,6 +559,12 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       const std::string m(v);
       if (m != "fp32" && m != "fp64") throw Error("PORO_FDMO_PRECISION: fp32 or fp64");
       c->fdm_precision = m == "fp32" ? PORO_FDM_FP32 : PORO_FDM_FP64;
+    }
+    // and the initial form of that block FDM (poro_ctx_set_fdm_form); the nested coarse box above keeps the default whatever this says
+    if (const char *v = std::getenv("PORO_FDMO_FORM")) {
+      const std::string m(v);
+      if (m != "per-direction" && m != "default") throw Error("PORO_FDMO_FORM: per-direction or default");
+      c->fdm_form = m == "per-direction" ? PORO_FDM_FORM_PER_DIRECTION : PORO_FDM_FORM_DEFAULT;
     }
     *out = c.release();
     return 0;
@@ -608,7 +617,7 @@ static bool fdm_u_runs_octant(poro_ctx *c) {
     if (c->fdm_u_state != 1) return false;
     build_fdm_u(c);
   }
-  return c->fdm_oct.built && !c->fdm_oct.planar && !c->fdm_oct.slab.on;
+  return c->fdm_oct.built && !c->fdm_oct.planar && !c->fdm_oct.slab.on && !c->fdm_oct.per_dir;
 }
 int poro_ctx_set_fdm_precision(poro_ctx *c, int32_t precision) {
   return guarded([&] {
@@ -623,6 +632,34 @@ int poro_ctx_get_fdm_precision(poro_ctx *c, int32_t *requested, int32_t *effecti
     if (!c || !requested || !effective) throw Error("null argument");
     *requested = c->fdm_precision; *effective = PORO_FDM_FP64;
     if (c->fdm_precision == PORO_FDM_FP32) { PORO_HIP(hipSetDevice(c->device)); if (fdm_u_runs_octant(c)) *effective = PORO_FDM_FP32; }
+    return 0;
+  });
+}
+
+// The per-direction form is honoured by single-rank 3D contexts (never by the nested coarse box of a two-level preconditioner); elsewhere the request is recorded and ignored
+static bool fdm_form_applies(const poro_ctx *c) { return c->dim == 3 && !c->comm.multi() && !c->fdm_form_fixed; }
+int poro_ctx_set_fdm_form(poro_ctx *c, int32_t form) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    if (form != PORO_FDM_FORM_DEFAULT && form != PORO_FDM_FORM_PER_DIRECTION) throw Error("poro_ctx_set_fdm_form: unknown form " + std::to_string(form) + " (PORO_FDM_FORM_DEFAULT or PORO_FDM_FORM_PER_DIRECTION)");
+    if (form != c->fdm_form && c->fdm_u.built && fdm_form_applies(c)) { PORO_HIP(hipSetDevice(c->device)); release_fdm_u(c); }   // built in the other form: rebuilt at next use
+    c->fdm_form = form;
+    return 0;
+  });
+}
+int poro_ctx_get_fdm_form(poro_ctx *c, int32_t *requested, int32_t *effective, int32_t split[3]) {
+  return guarded([&] {
+    if (!c || !requested || !effective) throw Error("null argument");
+    *requested = c->fdm_form; *effective = PORO_FDM_RUNS_NODAL;
+    int mask = 0;
+    PORO_HIP(hipSetDevice(c->device));
+    if (!c->fdm_u.built && !c->comm.multi()) { analyse_fdm_u(c); if (c->fdm_u_state == 1) build_fdm_u(c); }   // (a partitioned context builds collectively, at its first solve)
+    const FdmOct &O = c->fdm_oct;
+    if (c->fdm_u.built && O.built) {
+      *effective = O.slab.on ? PORO_FDM_RUNS_SLAB : O.planar ? PORO_FDM_RUNS_PLANAR : O.per_dir ? PORO_FDM_RUNS_PER_DIRECTION : PORO_FDM_RUNS_OCTANT;
+      mask = O.per_dir ? O.split_mask : O.planar ? (O.no == 4 ? 3 : 0) : 7;       // (slabs: the z butterfly sits next to the all-to-all)
+    }
+    if (split) for (int d = 0; d < 3; ++d) split[d] = (mask >> d) & 1;
     return 0;
   });
 }
@@ -1102,8 +1139,9 @@ int poro_apply_preconditioner_u(poro_ctx *c, int32_t preconditioner, const doubl
       build_fdm_u(c);
       FdmOct &O = c->fdm_oct;
       // octant form where the solver uses it: butterflies outside (H, H'), the three transform passes in between - the timed part, as inside PCG
-      fdm_precondition_u_nodal(c, g.p, z.p, c->fdm_precision);
-      auto once = [&]() { if (O.built) fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, c->fdm_precision, O.t.p); else fdm_precondition_u(c, g.p, z.p); };
+      const int precision = O.built && O.per_dir ? PORO_FDM_FP64 : c->fdm_precision;      // (the per-direction form has fp64 fragments only)
+      fdm_precondition_u_nodal(c, g.p, z.p, precision);
+      auto once = [&]() { if (O.built) fdm_precondition_u_form(c, O.g.p, O.z.p, nullptr, precision, O.t.p); else fdm_precondition_u(c, g.p, z.p); };
       if (reps > 0 && seconds_per_apply) {
         EventPair ev(c); PORO_HIP(hipEventRecord(ev.e0, s));
         for (int k = 0; k < reps; ++k) once();

@@ -147,6 +147,7 @@ void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int preci
 void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which = Q1Set::free_ends);
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
+void release_fdm_u(poro_ctx *c);   // frees what build_fdm_u made; the next use builds again (a change of the requested form)
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);
 
 // ---- mesh adaptation (ctx_adapt.hip) ------------------------------------------------------------------------------------------------------

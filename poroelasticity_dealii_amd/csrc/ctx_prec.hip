@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <new>
 #include <optional>
 #include <thread>
 #include <unordered_map>
@@ -246,6 +247,14 @@ void analyse_fdm_u(poro_ctx *c) {
   c->fdm_u_why = why;
   c->fdm_u_state = why.empty() ? 1 : -1;
 }
+// everything build_fdm_u made, released: the next use builds it again (poro_ctx_set_fdm_form).  The buffers are not copyable, so the two structures are constructed afresh
+void release_fdm_u(poro_ctx *c) {
+  if (!c->fdm_u.built) return;
+  PORO_HIP(hipStreamSynchronize(c->stream));
+  c->fdm_oct.~FdmOct(); new (&c->fdm_oct) FdmOct();
+  c->fdm_u.~FdmU(); new (&c->fdm_u) FdmU();
+  c->fdm_u_state = 0; c->fdm_u_why.clear();
+}
 void build_fdm_u(poro_ctx *c) {
   FdmU &F = c->fdm_u;
   if (F.built) return;
@@ -269,7 +278,7 @@ void build_fdm_u(poro_ctx *c) {
   }
   // eigenpairs per (direction, end conditions); components with the same end conditions share the host work.  same_ends[d]: every component has the same condition at
   // both ends of direction d; parity[d]: every component's eigenvectors came out even or odd there (they do on a uniform line with the same ends, not on a graded one)
-  LineTables tables[3][4]; bool same_ends[3], parity[3];
+  LineTables tables[3][4]; bool same_ends[3], parity[3], parity_cd[3][3] = {};
   const auto key_of = [&](int comp, int d) { return F.fix[comp][d][0] * 2 + F.fix[comp][d][1]; };
   for (int d = 0; d < dim; ++d) {
     const bool global_dir = multi && d == last;
@@ -278,12 +287,15 @@ void build_fdm_u(poro_ctx *c) {
     for (int comp = 0; comp < dim; ++comp) {
       LineTables &T = tables[d][key_of(comp, d)];
       if (!T.n) T = line_tables(ku, hcell, F.fix[comp][d][0], F.fix[comp][d][1]);
-      same_ends[d] = same_ends[d] && F.fix[comp][d][0] == F.fix[comp][d][1]; parity[d] = parity[d] && T.parity;
+      same_ends[d] = same_ends[d] && F.fix[comp][d][0] == F.fix[comp][d][1]; parity[d] = parity[d] && T.parity; parity_cd[comp][d] = T.parity;
     }
   }
   // octant form (kernels_fdmo.hip): one rank, 3D, every direction mirror-symmetric for every component, half lines of at most 128 entries
   // slab partitions: the quadrant form (x, y split locally; the z butterfly next to the all-to-all) under the same conditions on the GLOBAL line
   bool oct_ok = !F.single && !std::getenv("PORO_FDMU_NO_OCT");
+  // per-direction form (opt-in, poro_ctx_set_fdm_form; one rank, 3D): the same passes where only some directions are mirror-symmetric - one decision function (fdm_tables.hpp).
+  // A box whose directions are all split is the octant form and takes its code path below; one with a line beyond the kernel's reach keeps the nodal kernels
+  bool per_dir = false; FdmFormDecision form;
   bool planar = false;     // 2D, one rank: the quadrant form with a single plane, transforms as batched GEMMs (lines of any length; without the parity split where the end conditions differ)
   { int nn3[3] = {F.nn[0], F.nn[1], F.nn[2]}, sym3[3] = {F.nn[0], F.nn[1], multi ? F.ng : F.nn[2]};
     planar = dim == 2 && !multi && fdmo_planar_usable(dim, nn3);
@@ -292,7 +304,12 @@ void build_fdm_u(poro_ctx *c) {
     for (int d = 0; d < dim; ++d) { symmetric = symmetric && same_ends[d]; all_parity = all_parity && parity[d]; }
     // the planar form also runs without the parity split; its split form and the 3D forms need the same ends everywhere and eigenvectors that are all even or odd
     oct_ok = oct_ok && ((planar && !symmetric) || (symmetric && all_parity));
-    if (oct_ok && planar) fdmo_init_planar(c->fdm_oct, nn3, F.coef, c->stream, symmetric);
+    if (c->fdm_form == PORO_FDM_FORM_PER_DIRECTION && !c->fdm_form_fixed && dim == 3 && !multi && !F.single && !std::getenv("PORO_FDMU_NO_OCT")) {
+      form = fdm_form_decide(F.fix, parity_cd, nn3);
+      per_dir = form.usable && !form.all_split;
+    }
+    if (per_dir) { fdmo_init_per_direction(c->fdm_oct, nn3, F.coef, form, c->stream); oct_ok = true; }
+    else if (oct_ok && planar) fdmo_init_planar(c->fdm_oct, nn3, F.coef, c->stream, symmetric);
     else if (oct_ok && !multi) fdmo_init(c->fdm_oct, nn3, F.coef, c->stream);
     if (oct_ok && multi) { std::vector<int> node_layers(F.n_ranks); for (int q = 0; q < F.n_ranks; ++q) node_layers[q] = ku * F.layers[q];
                            fdmo_init_slab(c->fdm_oct, nn3, F.coef, F.rank, node_layers, c->comm.part.has_upper != 0, c->stream); } }

@@ -264,6 +264,33 @@ template <class T, class El> std::vector<T> pack_fragments(int tiles, int ksteps
   }
   return f;
 }
+// a whole line's transform in fragment order: forward F[mode][node] = S^T, backward B[node][mode] = S - every mode of the line; removed ones are zero columns of S
+inline std::vector<double> whole_line_fragments(const LineTables &T, int tiles, bool backward) {
+  const int n = T.n; const std::vector<double> &S = T.S;
+  return backward ? pack_fragments<double>(tiles, 4 * tiles, n, n, [&](int r, int c) { return S[(size_t)r * n + c]; })
+                  : pack_fragments<double>(tiles, 4 * tiles, n, n, [&](int r, int c) { return S[(size_t)c * n + r]; });
+}
+
+// ---- which form the single-rank 3D block FDM of the displacement system can take (PORO_FDM_FORM_PER_DIRECTION) ----
+constexpr int kFdmoMaxTiles = 8;       // 16-wide tiles per transformed line the pass kernel of kernels_fdmo.hip is instantiated for: lines of <= 128 entries
+// Direction d is SPLIT in parity halves (butterfly in the CG vector kernels, half-size transforms) iff every component has the same end condition at both of its ends and every
+// component's eigenvectors came out even or odd there (LineTables::parity: they do on a uniform line with equal ends, not on a graded one); otherwise it is WHOLE (whole-length
+// transforms).  len[d] = the transformed length: (n + 1) / 2 or n.  Passes 1 / 3 work on x-y planes and are sized by max(len_x, len_y), pass 2 by len_z.  usable: every
+// length fits the kernel; where not, the box keeps the nodal kernels.  all_split: the octant form proper (it keeps its own code path)
+struct FdmFormDecision { bool usable = false, all_split = false; int split[3] = {0, 0, 0}, len[3] = {0, 0, 0}; int nt_xy = 0, nt_z = 0, parts = 1; };
+inline FdmFormDecision fdm_form_decide(const int fix[3][3][2], const bool parity[3][3] /* [component][direction] */, const int nn[3]) {
+  FdmFormDecision D; D.usable = true; D.all_split = true;
+  for (int d = 0; d < 3; ++d) {
+    bool split = true;
+    for (int c = 0; c < 3; ++c) split = split && fix[c][d][0] == fix[c][d][1] && parity[c][d];
+    D.split[d] = split ? 1 : 0; D.len[d] = split ? (nn[d] + 1) / 2 : nn[d];
+    D.all_split = D.all_split && split; if (split) D.parts *= 2;
+    if (nn[d] < 2 || D.len[d] > 16 * kFdmoMaxTiles) D.usable = false;
+  }
+  D.nt_xy = (std::max(D.len[0], D.len[1]) + 15) / 16; D.nt_z = (D.len[2] + 15) / 16;
+  return D;
+}
+
 // two matrices side by side, el(r, c, e) with e = 0 / 1, as [block][chunk][k-step u < 4][pair][64][2]: entry e of lane l of (block b, chunk, u, pair p) holds element
 // (16 tile(b, p, e) + (l & 15), 4 (4 chunk + u) + (l >> 4)) of matrix e; el returns 0 beyond its matrix
 template <class Tile, class El> std::vector<double> pack_paired_chunks(int blocks, int chunks, int pairs, Tile tile, El el) {

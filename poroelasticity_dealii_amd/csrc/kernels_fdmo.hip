@@ -20,6 +20,10 @@
 // the 16 rows of its own output tile).  "contract columns": Y = X T^T, wave w owns output column tile w, data = A operand; "contract rows":
 // Y = T X, wave s owns output row tile s, data = B operand; either way the accumulator of tile (T, W) holds element (16 T + 4 q + kq, 16 W + j) in
 // register q of lane j + 16 kq, so one store routine serves both.
+//
+// Per-direction form (opt-in, poro_ctx_set_fdm_form): the same three passes on boxes where only SOME directions are mirror-symmetric (one-sided Dirichlet faces, graded lines).  A
+// direction that is split keeps the above; a WHOLE direction has no butterfly and a whole-length transform: 2^(split directions) parity parts per component instead of eight, and
+// per-pass tile counts (passes 1 / 3: max(len_x, len_y), pass 2: len_z).  OctDims carries the split mask for the vector kernels, k_fdmo_pass has VAR = 3 for the passes.
 #include "common.hpp"
 #include "fdm_tables.hpp"
 #include "device_reduce.hpp"
@@ -37,8 +41,10 @@ namespace {
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-struct OctDims { int nx, ny, nz, hx, hy, hz, hxp; int64_t co; int no, own_z, nc; };   // nodes and half lengths per direction; hxp = row pitch (hx rounded up to even: 16-byte aligned rows, the pad entry stays zero); co = hxp hy hz entries per (component, octant)
-// no = 8: octant form.  no = 4 (slab partitions): z is not split - every z index is "its own mirror image" (hz = nz, parity blocks 0..3 only); own_z = planes that count in dot products
+struct OctDims { int nx, ny, nz, hx, hy, hz, hxp; int64_t co; int no, own_z, nc; int split; int part[8]; };   // nodes and half lengths per direction; hxp = row pitch (hx rounded up to even: 16-byte aligned rows, the pad entry stays zero); co = hxp hy hz entries per (component, octant)
+// (per-direction form, PD instantiations of the vector kernels) split: bit d set = direction d is split in parities (mirror index n - 1 - k); clear = whole: every index is "its own mirror image" (h = n, no butterfly).  no = parity parts per
+// component = 2^(split directions); part[o] = block of parity combination o = 4 pz + 2 py + px inside a component (the bits of the split directions, packed), -1 where o has a bit of
+// a whole direction.  7: octant form (part[o] = o); 3 (slab partitions, planar form): quadrants; 0: the plain nodal values in planar storage; own_z = planes that count in dot products
 
 // ---- the 8-point butterfly --------------------------------------------------------------------------------------------------------------
 // index bit 0 / 1 / 2 = x / y / z.  Forward: in = values at the lower node (bit clear) and its mirror image (bit set), out = even (bit clear) and odd
@@ -66,13 +72,18 @@ __device__ __forceinline__ void bfly_bwd(double (&v)[8], const bool (&centre)[3]
     }
   }
 }
-struct OctPos {
+// PD (per-direction form): mirrors and the blocks of the parts from D.split / D.part.  PD = false (octants, quadrants, no split) derives them from D.no as always, so that the
+// kernels of the existing forms compile to what they were
+template <bool PD> __device__ __forceinline__ bool part_on(const OctDims &D, int o) { return PD ? D.part[o] >= 0 : o < D.no; }
+template <bool PD> __device__ __forceinline__ int part_at(const OctDims &D, int o) { return PD ? D.part[o] : o; }
+template <bool PD> struct OctPos {
   int64_t node[8]; bool centre[3]; bool live[8]; double weight; bool valid, own;
   // lower-octant position idx = (kz hy + ky) hxp + kx -> the eight mirror nodes; live[m]: node m is distinct from the ones with fewer mirrored directions; valid: not a row pad
   __device__ __forceinline__ OctPos(const OctDims &D, int64_t idx) {
     const int kx = (int)(idx % D.hxp), ky = (int)((idx / D.hxp) % D.hy), kz = (int)(idx / ((int64_t)D.hxp * D.hy));
     valid = kx < D.hx;
-    const int mx = D.no == 1 ? kx : D.nx - 1 - kx, my = D.no == 1 ? ky : D.ny - 1 - ky, mz = D.no == 8 ? D.nz - 1 - kz : kz;   // (no = 1: no direction is split - the plain nodal values in planar storage)
+    const int mx = PD ? ((D.split & 1) ? D.nx - 1 - kx : kx) : (D.no == 1 ? kx : D.nx - 1 - kx), my = PD ? ((D.split & 2) ? D.ny - 1 - ky : ky) : (D.no == 1 ? ky : D.ny - 1 - ky),
+              mz = PD ? ((D.split & 4) ? D.nz - 1 - kz : kz) : (D.no == 8 ? D.nz - 1 - kz : kz);   // (PD = false: no = 8 octants, 4: z not split, 1: no direction is split - the plain nodal values in planar storage)
     centre[0] = mx == kx; centre[1] = my == ky; centre[2] = mz == kz; own = kz < D.own_z;
     weight = (centre[0] ? 1.0 : 0.5) * (centre[1] ? 1.0 : 0.5) * (centre[2] ? 1.0 : 0.5);   // |v|^2 over a mirror orbit = weight * sum of the squared parity parts
 #pragma unroll
@@ -89,10 +100,10 @@ struct OctPos {
 // contiguous streams of every octant array.  (First version: one thread per position, all three components - 8-byte accesses at 24-byte stride: 170 us for the
 // direction update instead of 45.)
 #define PORO_OCT_LOOP(D) for (int64_t t_ = (int64_t)blockIdx.x * kBlock + threadIdx.x; t_ < NC * (D).co; t_ += (int64_t)gridDim.x * kBlock)   /* NC = components per node: 3, or 2 for the planar form */
-#define PORO_OCT_DECODE(D) const int64_t idx = t_ / NC; const int c = (int)(t_ - NC * idx); const OctPos P(D, idx); if (!P.valid) continue;
+#define PORO_OCT_DECODE(D) const int64_t idx = t_ / NC; const int c = (int)(t_ - NC * idx); const OctPos<PD> P(D, idx); if (!P.valid) continue;
 
 // q = H v: node-interleaved vector (dof = 3 node + c) -> octant form; masked dofs count as zero
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_from_nodal(OctDims D, const double *__restrict__ v, const uint8_t *__restrict__ inert, double *__restrict__ q) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_from_nodal(OctDims D, const double *__restrict__ v, const uint8_t *__restrict__ inert, double *__restrict__ q) {
   PORO_OCT_LOOP(D) {
     PORO_OCT_DECODE(D)
     double w[8];
@@ -100,15 +111,15 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_from_nodal(Oc
     for (int m = 0; m < 8; ++m) { const int64_t dof = P.node[m] * NC + c; w[m] = (inert && inert[dof]) ? 0.0 : v[dof]; }
     bfly_fwd(w, P.centre);
 #pragma unroll
-    for (int o = 0; o < 8; ++o) if (o < D.no) q[(int64_t)(c * D.no + o) * D.co + idx] = w[o];
+    for (int o = 0; o < 8; ++o) if (part_on<PD>(D, o)) q[(int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx] = w[o];
   }
 }
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_to_nodal(OctDims D, const double *__restrict__ r, double *__restrict__ v) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_to_nodal(OctDims D, const double *__restrict__ r, double *__restrict__ v) {
   PORO_OCT_LOOP(D) {
     PORO_OCT_DECODE(D)
     double w[8];
 #pragma unroll
-    for (int o = 0; o < 8; ++o) w[o] = o < D.no ? r[(int64_t)(c * D.no + o) * D.co + idx] : 0.0;
+    for (int o = 0; o < 8; ++o) w[o] = part_on<PD>(D, o) ? r[(int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx] : 0.0;
     bfly_bwd(w, P.centre);
 #pragma unroll
     for (int m = 0; m < 8; ++m) if (P.live[m]) v[P.node[m] * NC + c] = w[m];
@@ -117,7 +128,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_to_nodal(OctD
 
 // ---- CG vector kernels with g, z in octant form (protocol of k_pcg_* in kernels_la.hip) ---------------------------------------------------
 // g = H (A x - b), zero on the inert (Dirichlet) dofs
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_init_residual(OctDims D, double *__restrict__ g, const double *__restrict__ Ax, const double *__restrict__ b, const uint8_t *__restrict__ inert) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_init_residual(OctDims D, double *__restrict__ g, const double *__restrict__ Ax, const double *__restrict__ b, const uint8_t *__restrict__ inert) {
   PORO_OCT_LOOP(D) {
     PORO_OCT_DECODE(D)
     double w[8];
@@ -125,18 +136,18 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_init_residual
     for (int m = 0; m < 8; ++m) { const int64_t dof = P.node[m] * NC + c; w[m] = (inert && inert[dof]) ? 0.0 : Ax[dof] - b[dof]; }
     bfly_fwd(w, P.centre);
 #pragma unroll
-    for (int o = 0; o < 8; ++o) if (o < D.no) g[(int64_t)(c * D.no + o) * D.co + idx] = w[o];
+    for (int o = 0; o < 8; ++o) if (part_on<PD>(D, o)) g[(int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx] = w[o];
   }
 }
 // d = -z (nodal); block partials of g.g and g.z
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_first_direction(OctDims D, double *__restrict__ d, const double *__restrict__ g, const double *__restrict__ z, double *partials) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_first_direction(OctDims D, double *__restrict__ d, const double *__restrict__ g, const double *__restrict__ z, double *partials) {
   __shared__ double sh[5];
   double gg = 0, gz = 0;
   PORO_OCT_LOOP(D) {
     PORO_OCT_DECODE(D)
     double w[8]; double s2 = 0, sz = 0;
 #pragma unroll
-    for (int o = 0; o < 8; ++o) { w[o] = 0.0; if (o < D.no) { const int64_t at = (int64_t)(c * D.no + o) * D.co + idx; const double gv = g[at]; w[o] = z[at]; s2 = fma(gv, gv, s2); sz = fma(gv, w[o], sz); } }
+    for (int o = 0; o < 8; ++o) { w[o] = 0.0; if (part_on<PD>(D, o)) { const int64_t at = (int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx; const double gv = g[at]; w[o] = z[at]; s2 = fma(gv, gv, s2); sz = fma(gv, w[o], sz); } }
     if (P.own) { gg = fma(P.weight, s2, gg); gz += sz; }
     bfly_bwd(w, P.centre);
 #pragma unroll
@@ -146,7 +157,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_first_directi
   store_partial(partials, gg); store_partial(partials + kMaxPartials, gz);
 }
 // g += alpha H (A d) and the partials of g.g (g.z follows in a plain dot of the two octant arrays once z = P^-1 g exists)
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g(OctDims D, PcgScalars *sc, int parity, double *__restrict__ g, const double *__restrict__ h, const uint8_t *__restrict__ inert, const double *partials_dh, double *partials_out, const double *red) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g(OctDims D, PcgScalars *sc, int parity, double *__restrict__ g, const double *__restrict__ h, const uint8_t *__restrict__ inert, const double *partials_dh, double *partials_out, const double *red) {
   __shared__ double sh[5];
   if (sc->done) return;
   if (sc->finishing) { if (blockIdx.x == 0 && threadIdx.x == 0) sc->done = 1; return; }   // (see k_pcg_update_g_fused)
@@ -156,14 +167,15 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g(OctD
   PORO_OCT_LOOP(D) {
     PORO_OCT_DECODE(D)
     // inert (Dirichlet) dofs: the residual stays exactly zero whatever the operator left in h.  The octant form exists only where every Dirichlet condition covers a
-    // pair of opposite faces (build_fdm_u), so the eight mirror images of a dof are inert together: one mask byte per thread
+    // pair of opposite faces (build_fdm_u), so the eight mirror images of a dof are inert together: one mask byte per thread.  (Per-direction form: a direction is split only
+    // where every component has the same condition at both of its ends, and a whole direction has no mirror image - the same holds)
     if (inert && inert[P.node[0] * NC + c]) continue;
     double w[8]; double s2 = 0;
 #pragma unroll
     for (int m = 0; m < 8; ++m) w[m] = h[P.node[m] * NC + c];
     bfly_fwd(w, P.centre);
 #pragma unroll
-    for (int o = 0; o < 8; ++o) if (o < D.no) { const int64_t at = (int64_t)(c * D.no + o) * D.co + idx; const double gv = fma(alpha, w[o], g[at]); g[at] = gv; s2 = fma(gv, gv, s2); }
+    for (int o = 0; o < 8; ++o) if (part_on<PD>(D, o)) { const int64_t at = (int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx; const double gv = fma(alpha, w[o], g[at]); g[at] = gv; s2 = fma(gv, gv, s2); }
     if (P.own) gg = fma(P.weight, s2, gg);
   }
   gg = block_sum(gg, sh);
@@ -172,7 +184,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g(OctD
 }
 // the same with TWO neighbouring positions (idx, idx + 1: same row, the pitch is even) per thread: 16-byte accesses on the octant side (twice as long contiguous pieces per
 // component and instruction), the nodal side reads two dofs 8 NC bytes apart
-template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(OctDims D, PcgScalars *sc, int parity, double *__restrict__ g, const double *__restrict__ h, const uint8_t *__restrict__ inert, const double *partials_dh, double *partials_out, const double *red) {
+template <int NC, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(OctDims D, PcgScalars *sc, int parity, double *__restrict__ g, const double *__restrict__ h, const uint8_t *__restrict__ inert, const double *partials_dh, double *partials_out, const double *red) {
   __shared__ double sh[5];
   if (sc->done) return;
   if (sc->finishing) { if (blockIdx.x == 0 && threadIdx.x == 0) sc->done = 1; return; }
@@ -181,7 +193,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
   double gg = 0;
   for (int64_t t_ = (int64_t)blockIdx.x * kBlock + threadIdx.x; t_ < NC * (D.co / 2); t_ += (int64_t)gridDim.x * kBlock) {
     const int64_t pr = t_ / NC; const int c = (int)(t_ - NC * pr); const int64_t idx = 2 * pr;
-    const OctPos P0(D, idx), P1(D, idx + 1);
+    const OctPos<PD> P0(D, idx), P1(D, idx + 1);
     double w0[8], w1[8];
     const bool on0 = P0.valid && !(inert && inert[P0.node[0] * NC + c]), on1 = P1.valid && !(inert && inert[P1.node[0] * NC + c]);
 #pragma unroll
@@ -189,8 +201,8 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
     bfly_fwd(w0, P0.centre); bfly_fwd(w1, P1.centre);
     double s0 = 0, s1 = 0;
 #pragma unroll
-    for (int o = 0; o < 8; ++o) if (o < D.no) {
-      double2 *gp = reinterpret_cast<double2 *>(g + (int64_t)(c * D.no + o) * D.co + idx);
+    for (int o = 0; o < 8; ++o) if (part_on<PD>(D, o)) {
+      double2 *gp = reinterpret_cast<double2 *>(g + (int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx);
       double2 gv = *gp;
       gv.x = fma(alpha, w0[o], gv.x); gv.y = fma(alpha, w1[o], gv.y);       // (inert dofs and row pads: w = 0, g stays what it is - zero)
       *gp = gv; s0 = fma(gv.x, gv.x, s0); s1 = fma(gv.y, gv.y, s1);
@@ -206,7 +218,7 @@ template <int NC> __global__ void __launch_bounds__(kBlock) k_fdmo_update_g2(Oct
 // XNT: x is touched once per iteration and nowhere else: non-temporal accesses keep it from evicting d, g and the shared h | z array (224.6 MB at 72^3 Q2), which then
 // stay in the 256 MiB memory-side cache from one kernel of the iteration to the next (as in k_pcg_update_d_fused).  d and z keep plain accesses, and so does the
 // finishing branch below on purpose: it runs once per solve, after the last use of d, g and z.
-template <int NC, bool XNT> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
+template <int NC, bool XNT, bool PD> __global__ void __launch_bounds__(kBlock) k_fdmo_update_d(OctDims D, PcgScalars *sc, int parity, int it, double *__restrict__ x, double *__restrict__ d, const double *__restrict__ z, int64_t n_u, const double *partials_in, const double *red,
                                                                             const double *gz_part, int gz_n, int decided /* 2: and sc->gg holds g . g */) {
   __shared__ double sh[5];
   if (sc->done) return;
@@ -230,7 +242,7 @@ template <int NC, bool XNT> __global__ void __launch_bounds__(kBlock) k_fdmo_upd
     PORO_OCT_DECODE(D)
     double w[8];
 #pragma unroll
-    for (int o = 0; o < 8; ++o) w[o] = o < D.no ? z[(int64_t)(c * D.no + o) * D.co + idx] : 0.0;
+    for (int o = 0; o < 8; ++o) w[o] = part_on<PD>(D, o) ? z[(int64_t)(c * D.no + part_at<PD>(D, o)) * D.co + idx] : 0.0;
     bfly_bwd(w, P.centre);
 #pragma unroll
     for (int m = 0; m < 8; ++m) if (P.live[m]) {
@@ -298,13 +310,14 @@ struct OctPass {
   // global plane in the gathered buffer - the block is loaded as even / odd combination of a plane and its mirror image
   int slab_io, store_planes, ng, scols, col_unit, rank; float inv_scols; int64_t dest_stride, recv_off; const int64_t *row_in;
   int vec2;                     // rows are 16-byte aligned (even pitch, even chunk offsets): 16-byte block loads; 0: 8-byte loads (the scalar Q1 systems keep their nodal layout)
+  int per_dir, bitz;            // per-direction form (VAR = 3): the descriptor is one of its passes; bit of a part's index that selects the parity of lam_z (a whole z line: both slots hold the one table)
   double *gz_part;              // octant form, pass 2 (GZ instantiations): one partial sum of g . z per workgroup, see the epilogue of the first GEMM
   const PcgScalars *gate;       // inside a PCG iteration: the launch is a no-op once the solve has finished (the host enqueues iterations ahead of the device-side stopping test)
   PcgStopTest stop;             // pass 1 as the first kernel of a preconditioner call inside PCG: the iteration's stopping test (common.hpp); gg_part == null elsewhere
   unsigned long long *stamps;   // diagnostic (PORO_FDMO_STAMPS): per block 8 words: 100 MHz time at start / block in LDS / GEMM 1 done / intermediate in LDS / GEMM 2 done / stored, HW_ID, XCC_ID
 };
 
-constexpr int kFdmoMaxTiles = 8;                                  // 16-wide tiles per half line the transform kernel is instantiated for (half lines of <= 128 entries)
+// (kFdmoMaxTiles, fdm_tables.hpp: 16-wide tiles per line the transform kernel is instantiated for - half lines, or whole lines of the per-direction form, of <= 128 entries)
 template <int NT> constexpr int pass_waves() { return NT == 5 ? 4 : NT; }   // waves of a workgroup: one per tile row / column, except NT = 5 (four waves share 25 tiles)
 template <int NT> struct PassGeom {
   static constexpr int PADN = 16 * NT, KKP = 4 * NT;
@@ -332,7 +345,11 @@ template <int NT> struct PassGeom {
 // VAR = 0: the octant form on one rank (24 blocks, aligned rows, no exchange buffer, no per-block offsets) with those switches folded at compile time;
 // VAR = 1: the quadrant form of the displacement system on slabs (pass 1 stores into / pass 3 loads from the exchange buffer, pass 2 forms the parity parts on load), likewise;
 // VAR = 2: everything else by run-time switches (scalar systems, batched right-hand sides)
-// GZ (MODE = 1, VAR = 0 only): the pass also leaves g . z.  Per block z = B Lambda^-1 F g with B = F^T (fdmo_upload_dir), so sum Q_g Q_z = sum over the modes of
+// VAR = 3: the per-direction form of the displacement system on one rank (PORO_FDM_FORM_PER_DIRECTION): VAR = 0 with 2^(split directions) parts per component instead of
+//          eight.  The same folded switches; what differs is data: the part count (no_shift), the planes of the bxy table per component (bxy_cmul = 2^(split among x, y)), and
+//          which bit of the part's index selects the parity of each matrix set (bit1 / bit2 / bitz).  A whole direction has one matrix set, which the descriptor lists in both
+//          parity slots, so the kernel selects as always.  It keeps GZ, the pass-1 stopping test (QUARTERS included) and the in-place operation of VAR = 0
+// GZ (MODE = 1, VAR = 0 and 3 only): the pass also leaves g . z.  Per block z = B Lambda^-1 F g with B = F^T (fdmo_upload_dir), so sum Q_g Q_z = sum over the modes of
 // ghat^2 / den with ghat = (F x F x F) Q_g - which is what the accumulators hold after the first GEMM, next to the 1 / den that scales them.  Removed modes give
 // 1 / den = 0, pads are exact zeros and every tile of pass 2 belongs to one wave, so the workgroup's sum is its share of g . z: two FMAs per entry and one
 // 8-byte store, no extra load, no extra launch (P.gz_part[blockIdx.x]; k_fdmo_update_d adds the slots up in a fixed order)
@@ -345,11 +362,11 @@ template <int NT> struct PassGeom {
 template <int NT, int MODE, int VAR, bool GZ = false>
 __global__ void __launch_bounds__(64 * pass_waves<NT>())
 k_fdmo_pass(OctPass P, const double *in, double *out) {
-  static_assert(!GZ || (MODE == 1 && VAR == 0), "g . z comes out of pass 2 of the single-rank octant form only");
+  static_assert(!GZ || (MODE == 1 && (VAR == 0 || VAR == 3)), "g . z comes out of pass 2 of the single-rank octant and per-direction forms only");
   // (the kernel argument stays in the kernarg segment - a modified copy would live in scratch because of its dynamically indexed members)
-  constexpr bool GENERAL = VAR == 2, SLAB = VAR == 1;
+  constexpr bool GENERAL = VAR == 2, SLAB = VAR == 1, PERDIR = VAR == 3;
   const int f_vec2 = GENERAL ? P.vec2 : 1, f_slab_z = GENERAL ? P.slab_z : (SLAB && MODE == 1 ? 2 : 0), f_slab_io = GENERAL ? P.slab_io : (SLAB && MODE == 0 ? 1 : SLAB && MODE == 2 ? 2 : 0),
-            f_use_in = GENERAL ? P.use_in_off : 0, f_use_out = GENERAL ? P.use_out_off : 0, f_no_shift = GENERAL ? P.no_shift : (SLAB ? 2 : 3), f_bxy_cmul = GENERAL ? P.bxy_cmul : 4;
+            f_use_in = GENERAL ? P.use_in_off : 0, f_use_out = GENERAL ? P.use_out_off : 0, f_no_shift = (GENERAL || PERDIR) ? P.no_shift : (SLAB ? 2 : 3), f_bxy_cmul = (GENERAL || PERDIR) ? P.bxy_cmul : 4;
   const int64_t *const f_row_in = (GENERAL || (SLAB && MODE == 1)) ? P.row_in : nullptr;
   typedef PassGeom<NT> Gm;
   constexpr int NW = pass_waves<NT>();                       // waves
@@ -369,8 +386,8 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   // the test's registers are free again by then (held across the staging loads they cost the five-tile pass its third resident workgroup)
   // Four-wave workgroups (QUARTERS) share the sum out instead: each wave adds a quarter of the partials (8 registers, requested with the staging loads), the four wave sums
   // meet in LDS at the staging barrier and the decision falls behind it - a workgroup that stops has stored nothing by then.  P.stop.per_wave keeps the form above (A/B hook)
-  // (the Octant variant only: the slab form refuses a stopping test and the scalar passes are handed none, so their pass 1 keeps the form above and pays nothing for this one)
-  constexpr bool QUARTERS = MODE == 0 && VAR == 0 && NW == 4;
+  // (the Octant and PerDirection variants only: the slab form refuses a stopping test and the scalar passes are handed none, so their pass 1 keeps the form above and pays nothing for this one)
+  constexpr bool QUARTERS = MODE == 0 && (VAR == 0 || VAR == 3) && NW == 4;
   __shared__ double stop_wave[QUARTERS ? 4 : 1];             // (referenced by the QUARTERS instantiations only)
   [[maybe_unused]] PcgStopQuarter stop_q; [[maybe_unused]] bool stop_pending = false;
   if (MODE == 0 && P.stop.gg_part) {
@@ -508,7 +525,7 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   if constexpr (MODE == 1) {
     // rows of this wave's tiles: tile row w (and the shared row XT); columns: tile column of the accumulator.  One entry at a time (sched_barrier), otherwise the
     // reciprocal sequences of all of them pile up in registers
-    const double *lamz = P.lam_z[c][(o >> 2) & 1], *bx = P.bxy + (int64_t)(f_bxy_cmul * c + (o & 3)) * P.pl;
+    const double *lamz = P.lam_z[c][(o >> (PERDIR ? P.bitz : 2)) & 1], *bx = P.bxy + (int64_t)(f_bxy_cmul * c + (PERDIR ? (o & (P.bxy_cmul - 1)) : (o & 3))) * P.pl;   // (per-direction form: the x / y bits are the lowest of a part's index)
     const double czc = P.cz[c];
     double lzw[4], lzx[4];
 #pragma unroll
@@ -1002,11 +1019,13 @@ template <auto Kernel, int NT, class Elem> void launch_one(hipStream_t s, int n_
   hipExtLaunchKernelGGL(Kernel, dim3((unsigned)n_items), dim3(64 * pass_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
 }
 // The kernel variant of a pass is stated by whoever builds the descriptor.  Octant / SlabU (VAR = 0 / 1 of k_fdmo_pass) fold the flags below at compile time and never read
-// them, General (VAR = 2) reads them, OctantF32 is k_fdmo_pass_f32 (float fragments in P.T1 / P.T2, float intermediate array; it folds what Octant folds)
-enum class PassVariant { Octant, SlabU, General, OctantF32 };
-constexpr const char *kVariantName[] = {"Octant", "SlabU", "General", "OctantF32"};
+// them, PerDirection (VAR = 3) folds what Octant folds and reads the part geometry (OctPass::per_dir), General (VAR = 2) reads them, OctantF32 is k_fdmo_pass_f32 (float fragments in P.T1 / P.T2, float intermediate array; it folds what Octant folds)
+enum class PassVariant { Octant, SlabU, General, OctantF32, PerDirection };
+constexpr const char *kVariantName[] = {"Octant", "SlabU", "General", "OctantF32", "PerDirection"};
 PassVariant variant_of_flags(const OctPass &P) {       // the variant whose folded switches equal the descriptor's flags
   const bool plain = P.vec2 == 1 && !P.use_in_off && !P.use_out_off && P.bxy_cmul == 4;
+  const bool unit = P.vec2 == 1 && !P.use_in_off && !P.use_out_off && P.slab_z == 0 && P.slab_io == 0 && !P.row_in;
+  if (P.per_dir) return unit && P.bxy_cmul >= 1 && P.bxy_cmul <= 4 && P.no_shift >= 0 && P.no_shift < 3 ? PassVariant::PerDirection : PassVariant::General;
   const bool oct = plain && P.slab_z == 0 && P.slab_io == 0 && !P.row_in && P.no_shift == 3;
   const bool slab_u = plain && P.no_shift == 2 && ((P.mode == 0 && P.slab_io == 1 && !P.slab_z) || (P.mode == 1 && P.slab_z == 2 && P.row_in && !P.slab_io) || (P.mode == 2 && P.slab_io == 2 && !P.slab_z));
   return oct ? PassVariant::Octant : slab_u ? PassVariant::SlabU : PassVariant::General;
@@ -1014,7 +1033,7 @@ PassVariant variant_of_flags(const OctPass &P) {       // the variant whose fold
 template <int NT, int VAR> void launch_modes(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
   if (P.mode == 0) launch_one<k_fdmo_pass<NT, 0, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
   else if (P.mode == 2) launch_one<k_fdmo_pass<NT, 2, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
-  else if (VAR == 0 && P.gz_part) launch_one<k_fdmo_pass<NT, 1, 0, true>, NT, double>(s, n_items, P, in, out, e0, e1);
+  else if ((VAR == 0 || VAR == 3) && P.gz_part) launch_one<k_fdmo_pass<NT, 1, (VAR == 3 ? 3 : 0), true>, NT, double>(s, n_items, P, in, out, e0, e1);
   else launch_one<k_fdmo_pass<NT, 1, VAR>, NT, double>(s, n_items, P, in, out, e0, e1);
 }
 template <int NT> void launch_pass(hipStream_t s, PassVariant v, const OctPass &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
@@ -1022,6 +1041,7 @@ template <int NT> void launch_pass(hipStream_t s, PassVariant v, const OctPass &
     case PassVariant::Octant: launch_modes<NT, 0>(s, P, n_items, in, out, e0, e1); break;
     case PassVariant::SlabU: launch_modes<NT, 1>(s, P, n_items, in, out, e0, e1); break;
     case PassVariant::General: launch_modes<NT, 2>(s, P, n_items, in, out, e0, e1); break;
+    case PassVariant::PerDirection: launch_modes<NT, 3>(s, P, n_items, in, out, e0, e1); break;
     case PassVariant::OctantF32:
       if (P.mode == 0) launch_one<k_fdmo_pass_f32<NT, 0>, NT, float>(s, n_items, P, in, out, e0, e1);
       else if (P.mode == 2) launch_one<k_fdmo_pass_f32<NT, 2>, NT, float>(s, n_items, P, in, out, e0, e1);
@@ -1049,7 +1069,17 @@ void launch_pass_nt(hipStream_t s, int nt, PassVariant v, const OctPass &P, int 
 inline int pass2_chunk(int nt) { return nt == 5 ? 64 : 16 * nt; }
 inline int pass2_chunks(int pl, int nt) { return (pl + pass2_chunk(nt) - 1) / pass2_chunk(nt); }   // chunks of a plane of pl positions = workgroups of pass 2 per block (one rank)
 inline int oct_grid(int64_t co, int nc = 3) { return (int)std::min<int64_t>((nc * co + kBlock - 1) / kBlock, kMaxPartials); }   // threads = positions x components, as many per thread as the partial slots demand
-OctDims dims_of(const FdmOct &O) { return OctDims{O.n[0], O.n[1], O.n[2], O.h[0], O.h[1], O.h[2], O.hxp, O.co_stride, O.no, O.own_z, O.nc}; }
+// split mask of a form: the per-direction form states it; octants split everything, quadrants (slabs, planar form) x and y, no = 1 nothing
+inline int split_mask_of(const FdmOct &O) { return O.per_dir ? O.split_mask : O.no == 8 ? 7 : O.no == 4 ? 3 : 0; }
+OctDims dims_of(const FdmOct &O) {
+  OctDims D{O.n[0], O.n[1], O.n[2], O.h[0], O.h[1], O.h[2], O.hxp, O.co_stride, O.no, O.own_z, O.nc, split_mask_of(O), {}};
+  for (int o = 0; o < 8; ++o) {        // bits of the split directions, packed in the order x, y, z
+    int part = 0, k = 0;
+    for (int d = 0; d < 3; ++d) if (D.split & (1 << d)) part |= ((o >> d) & 1) << k++;
+    D.part[o] = (o & ~D.split) ? -1 : part;
+  }
+  return D;
+}
 SlabGeo geo_of(const FdmOct &O) { const auto &S = O.slab; return SlabGeo{S.cw, S.nchunk, S.cps, S.nb * S.nchunk, S.rank, S.my_chunks, S.hzg, S.ng, S.np, S.scols, (int64_t)O.hxp * O.h[1], O.co_stride}; }
 
 // ---- the pass plan: one description of a form, one builder of the three launch descriptors ---------------------------------------------------------------------------
@@ -1061,13 +1091,20 @@ struct Form {
   int nc, np, vec2, bxy_cmul;          // components and parities that have matrices
   double kappa; const double *bxy;     // scalar: the z coefficient; x / y share of the eigenvalue sums
   int hx() const { return O.h[0]; } int hy() const { return O.h[1]; } int planes() const { return O.h[2]; }
-  int zlen() const { return O.slab.on ? O.slab.hzg : O.h[2]; } int cw() const { return O.slab.on ? O.slab.cw : pass2_chunk(O.nt); }
-  const void *fwd(int c, int d, int p) const { c = scalar ? 0 : c; return f32 ? (const void *)O.fwd32[c][d][p].p : (const void *)O.fwd[c][d][p].p; }
-  const void *bwd(int c, int d, int p) const { c = scalar ? 0 : c; return f32 ? (const void *)O.bwd32[c][d][p].p : (const void *)O.bwd[c][d][p].p; }
-  const double *lam_z(int c, int p) const { return O.lam[scalar ? 0 : c][2][p].p; } double cz(int c) const { return scalar ? kappa : O.coef[c][2]; }
+  int zlen() const { return O.slab.on ? O.slab.hzg : O.h[2]; } int cw() const { return O.slab.on ? O.slab.cw : pass2_chunk(O.nt_z); }
+  // (per-direction form: a whole direction has one matrix set, in parity slot 0 - listed for both parities)
+  int slot(int d, int p) const { return O.per_dir && !(O.split_mask & (1 << d)) ? 0 : p; }
+  int bit(int d) const { int k = 0; for (int e = 0; e < d; ++e) k += (split_mask_of(O) >> e) & 1; return k; }   // bit of a part's index that holds direction d's parity (octants: d)
+  const void *fwd(int c, int d, int p) const { c = scalar ? 0 : c; p = slot(d, p); return f32 ? (const void *)O.fwd32[c][d][p].p : (const void *)O.fwd[c][d][p].p; }
+  const void *bwd(int c, int d, int p) const { c = scalar ? 0 : c; p = slot(d, p); return f32 ? (const void *)O.bwd32[c][d][p].p : (const void *)O.bwd[c][d][p].p; }
+  const double *lam_z(int c, int p) const { return O.lam[scalar ? 0 : c][2][slot(2, p)].p; } double cz(int c) const { return scalar ? kappa : O.coef[c][2]; }
 };
 // displacement system (octants on one rank, quadrants on slabs; rows padded to even length) / nb right-hand sides of the scalar Q1 system a M + kappa K (nodal layout)
-Form disp_form(const FdmOct &O, bool f32) { return Form{O, false, f32, O.hxp, 3 * O.no, O.slab.on ? 2 : 3, 3, 2, 1, 4, 0.0, O.bxy.p}; }
+// per-direction form: 2^(split directions) parts per component, 2^(split among x, y) planes of the bxy table per component
+Form disp_form(const FdmOct &O, bool f32) {
+  if (O.per_dir) { int ns = 0; for (int d = 0; d < 3; ++d) ns += (O.split_mask >> d) & 1; return Form{O, false, false, O.hxp, 3 * O.no, ns, 3, 2, 1, 1 << ((O.split_mask & 1) + ((O.split_mask >> 1) & 1)), 0.0, O.bxy.p}; }
+  return Form{O, false, f32, O.hxp, 3 * O.no, O.slab.on ? 2 : 3, 3, 2, 1, 4, 0.0, O.bxy.p};
+}
 Form scalar_form(const FdmOct &O, int nb, double kappa, const double *table) { return Form{O, true, false, O.h[0], nb, 0, nb, 1, 0, 0, kappa, table}; }
 // pass 1: per z-plane X[ky][kx] -> Fy (X Fx^T); pass 2: per chunk of cw columns X[kz][col] -> Bz scale (Fz X); pass 3: per z-plane X[my][mx] -> (By X) Bx^T.
 // Everything but the per-call fields (gate, gz_part, in_blk / out_blk, stamps) and the slab extras (plan_slab_pass)
@@ -1075,12 +1112,16 @@ OctPass plan_pass(const Form &F, int pass) {
   auto ksteps = [](int n) { return (n + 3) / 4; };
   const int hx = F.hx(), hy = F.hy(), zlen = F.zlen(), cw = F.cw(), pl = F.pitch * hy; const bool first = pass == 1, transposed = F.O.slab.on;
   OctPass P{};
+  if (F.O.per_dir) {        // the parity bits of a part's index are packed: only the split directions have one (a whole direction's two slots hold the same matrices - any bit will do)
+    P.per_dir = 1; P.bitz = F.bit(2);
+  }
+  const int bx = F.O.per_dir ? F.bit(0) : 0, by = F.O.per_dir ? F.bit(1) : 1, bz = F.O.per_dir ? F.bit(2) : 2;
   P.co_stride = F.O.co_stride; P.pl = pl; P.bxy = F.bxy; P.vec2 = F.vec2; P.no_shift = F.no_shift; P.bxy_cmul = F.bxy_cmul;
   if (pass == 2) {       // (transposed: one block [zlen][cw] per workgroup instead of cw columns of a block of the array)
-    P.mode = 1; P.R = zlen; P.C = cw; P.kk1 = P.kk2 = ksteps(zlen); P.bit1 = P.bit2 = 2;
-    P.nblk = transposed ? 1 : pass2_chunks(pl, F.O.nt); P.blk_stride = transposed ? (int64_t)zlen * cw : cw; P.row_stride = transposed ? cw : pl;
+    P.mode = 1; P.R = zlen; P.C = cw; P.kk1 = P.kk2 = ksteps(zlen); P.bit1 = P.bit2 = bz;
+    P.nblk = transposed ? 1 : pass2_chunks(pl, F.O.nt_z); P.blk_stride = transposed ? (int64_t)zlen * cw : cw; P.row_stride = transposed ? cw : pl;
   } else {
-    P.mode = first ? 0 : 2; P.R = hy; P.C = F.pitch; P.kk1 = ksteps(first ? hx : hy); P.kk2 = ksteps(first ? hy : hx); P.bit1 = first ? 0 : 1; P.bit2 = first ? 1 : 0;
+    P.mode = first ? 0 : 2; P.R = hy; P.C = F.pitch; P.kk1 = ksteps(first ? hx : hy); P.kk2 = ksteps(first ? hy : hx); P.bit1 = first ? bx : by; P.bit2 = first ? by : bx;
     P.nblk = F.planes(); P.blk_stride = pl; P.row_stride = F.pitch;
   }
   for (int c = 0; c < F.nc; ++c) {
@@ -1137,7 +1178,7 @@ void form_geometry(FdmOct &O, const int nn[3], const double (*coef)[3], int nspl
     if (d < 2) hmax = std::max(hmax, O.h[d]);
     for (int c = 0; coef && c < 3; ++c) O.coef[c][d] = coef[c][d];
   }
-  O.nt = (hmax + 15) / 16; O.hxp = nsplit ? (O.h[0] + 1) & ~1 : O.h[0]; O.no = no;
+  O.nt = O.nt_z = (hmax + 15) / 16; O.hxp = nsplit ? (O.h[0] + 1) & ~1 : O.h[0]; O.no = no;
   O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = (coef ? 3 : 1) * no * O.co_stride;
   if (coef) { O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct); O.g.zero(s); O.z.zero(s); O.t.zero(s); }
 }
@@ -1167,6 +1208,29 @@ void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t 
   if (n_u > O.n_oct) throw Error("fdmo_init: the octant array is smaller than the nodal vector");
   O.own_z = O.n[2];
   O.gz_n = 24 * pass2_chunks(O.hxp * O.h[1], O.nt);   // workgroups of pass 2: one g . z partial each (grows with the box - not bounded by kMaxPartials)
+  O.gz_part.alloc(O.gz_n); O.gz_part.zero(s);
+}
+// Per-direction form (PORO_FDM_FORM_PER_DIRECTION; one rank, 3D): direction d is split in parities where D.split[d], else it keeps its whole line - no butterfly in the CG vector
+// kernels, whole-length transforms.  Layout Q[c][part][kz][ky][kx] with 2^(split directions) parts per component; the row pitch is even whether or not x is split (16-byte
+// block loads, paired accesses of the residual update; the pad entry is zero and stays zero).  Passes 1 / 3 and pass 2 have their own tile counts (D.nt_xy, D.nt_z), and
+// every direction's fragments are packed for the pass that uses them
+void fdmo_init_per_direction(FdmOct &O, const int nn[3], const double coef[3][3], const FdmFormDecision &D, hipStream_t s) {
+  if (!D.usable) throw Error("fdmo_init_per_direction: a line of more than 128 entries");
+  O.per_dir = true; O.split_mask = 0; O.no = 1;
+  for (int d = 0; d < 3; ++d) {
+    O.n[d] = nn[d]; O.h[d] = D.len[d];
+    if (D.split[d]) { O.split_mask |= 1 << d; O.no *= 2; }
+    for (int c = 0; c < 3; ++c) O.coef[c][d] = coef[c][d];
+  }
+  O.nt = D.nt_xy; O.nt_z = D.nt_z; O.hxp = (O.h[0] + 1) & ~1;
+  O.co_stride = (int64_t)O.hxp * O.h[1] * O.h[2]; O.n_oct = (int64_t)3 * O.no * O.co_stride;
+  // z doubles as the operator's nodal output h (fdmo_init): 2 h >= n in a split direction, h = n in a whole one, so the form's array holds the nodal vector - with equality,
+  // up to the row pitch, where no direction is split
+  if ((int64_t)3 * nn[0] * nn[1] * nn[2] > O.n_oct) throw Error("fdmo_init_per_direction: the form's array is smaller than the nodal vector");
+  if (O.hxp > 16 * O.nt || O.h[1] > 16 * O.nt || O.h[2] > 16 * O.nt_z) throw Error("fdmo_init_per_direction: tile counts do not cover the lines");
+  O.g.alloc(O.n_oct); O.z.alloc(O.n_oct); O.t.alloc(O.n_oct); O.g.zero(s); O.z.zero(s); O.t.zero(s);
+  O.own_z = O.n[2];
+  O.gz_n = 3 * O.no * pass2_chunks(O.hxp * O.h[1], O.nt_z);
   O.gz_part.alloc(O.gz_n); O.gz_part.zero(s);
 }
 // chunks, shares, plane tables and buffers of the slab form, after n / h / hxp / nt / co_stride are set: nb blocks per plane position set, np parity parts of a z line
@@ -1208,8 +1272,18 @@ void fdmo_scalar_init_slab(FdmOct &O, const int nn[3], int rank, const std::vect
   slab_layout(O, 1, 1, rank, node_layers, s);
 }
 
+// a whole direction of the per-direction form: every mode of the line (removed ones: zero columns of S, lam = inf), one matrix set in parity slot 0
+static void fdmo_upload_dir_whole(FdmOct &O, int comp, int dir, const LineTables &T) {
+  const int nt = dir == 2 ? O.nt_z : O.nt;
+  std::vector<double> lp(16 * nt + 16, std::numeric_limits<double>::infinity());
+  for (int m = 0; m < T.n; ++m) lp[m] = T.lam[m];
+  O.h_lam[comp][dir][0] = lp; O.lam[comp][dir][0].upload(lp);
+  O.fwd[comp][dir][0].upload(whole_line_fragments(T, nt, false)); O.bwd[comp][dir][0].upload(whole_line_fragments(T, nt, true));
+}
 void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T) {
-  const int nn = T.n, h = (nn + 1) / 2, nt = O.nt, padn = 16 * nt;
+  if (O.per_dir && T.n != O.n[dir]) throw Error("fdmo_upload_dir: line length mismatch");
+  if (O.per_dir && !(O.split_mask & (1 << dir))) { fdmo_upload_dir_whole(O, comp, dir, T); return; }
+  const int nn = T.n, h = (nn + 1) / 2, nt = dir == 2 ? O.nt_z : O.nt, padn = 16 * nt;      // (the tile count of the pass that uses the direction; one for all but the per-direction form)
   const std::vector<double> &S = T.S, &lam = T.lam;
   if (nn != (O.slab.on && dir == 2 ? O.slab.ng : O.n[dir])) throw Error("fdmo_upload_dir: line length mismatch");
   if (!T.parity) throw Error("fdmo_upload_dir: tables whose modes are not all even or odd");      // (the caller decides the form from T.parity before any upload)
@@ -1222,7 +1296,7 @@ void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T) {
     for (int m = 0; m < ng; ++m) lp[m] = lam[g[m]];
     O.h_lam[comp][dir][p] = lp;
     O.fwd[comp][dir][p].upload(F); O.bwd[comp][dir][p].upload(B); O.lam[comp][dir][p].upload(lp);
-    if (!O.slab.on) {   // fp32 mode of the octant form: both matrices rounded entry by entry from the same S, so the backward one is the exact transpose of the rounded forward one
+    if (!O.slab.on && !O.per_dir) {   // fp32 mode of the octant form: both matrices rounded entry by entry from the same S, so the backward one is the exact transpose of the rounded forward one
       O.fwd32[comp][dir][p].upload(std::vector<float>(F.begin(), F.end())); O.bwd32[comp][dir][p].upload(std::vector<float>(B.begin(), B.end()));
     }
   }
@@ -1230,12 +1304,16 @@ void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T) {
 
 void fdmo_finalize(FdmOct &O) {
   const int hx = O.h[0], hy = O.h[1], hxp = O.hxp; const size_t pl = (size_t)hxp * hy;
-  std::vector<double> B(12 * pl, 1.0);             // (row pads: any finite non-zero value, their data are zeros)
-  for (int c = 0; c < 3; ++c) for (int py = 0; py < 2; ++py) for (int px = 0; px < 2; ++px) for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx)
-    B[(size_t)(4 * c + 2 * py + px) * pl + (size_t)my * hxp + mx] = O.coef[c][0] * O.h_lam[c][0][px][mx] + O.coef[c][1] * O.h_lam[c][1][py][my];
+  // planes per component: one per parity combination of x and y (per-direction form: of those of the two that are split, x in the lowest bit)
+  const int sx = O.per_dir ? (O.split_mask & 1) : 1, sy = O.per_dir ? ((O.split_mask >> 1) & 1) : 1, cmul = 1 << (sx + sy);
+  std::vector<double> B((size_t)3 * cmul * pl, 1.0);             // (row pads: any finite non-zero value, their data are zeros)
+  for (int c = 0; c < 3; ++c) for (int q = 0; q < cmul; ++q) for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx) {
+    const int px = sx ? q & 1 : 0, py = sy ? (q >> sx) & 1 : 0;
+    B[(size_t)(cmul * c + q) * pl + (size_t)my * hxp + mx] = O.coef[c][0] * O.h_lam[c][0][px][mx] + O.coef[c][1] * O.h_lam[c][1][py][my];
+  }
   O.bxy.upload(B);
   auto plans = std::make_shared<FdmoPlans>();
-  for (int f32 = 0; f32 < (O.slab.on ? 1 : 2); ++f32) for (int k = 0; k < 3; ++k) {
+  for (int f32 = 0; f32 < (O.slab.on || O.per_dir ? 1 : 2); ++f32) for (int k = 0; k < 3; ++k) {
     const Form F = disp_form(O, f32 != 0);
     plans->pass[f32][k] = O.slab.on ? plan_slab_pass(F, k + 1) : plan_pass(F, k + 1);
     plans->n_items[k] = F.blocks * plans->pass[f32][k].nblk;
@@ -1245,7 +1323,7 @@ void fdmo_finalize(FdmOct &O) {
 
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch, const PcgScalars *gate, hipEvent_t *ev, double *gz_part, int precision, const PcgStopTest &stop) {
   const bool f32 = precision == PORO_FDM_FP32;     // fp32 transforms: float fragments, `scratch` holds the intermediate array as floats (g_oct, z_oct stay fp64)
-  if (f32 && (O.slab.on || O.planar || !O.fwd32[0][0][0].p)) throw Error("fdmo_apply: fp32 transforms exist for the single-rank octant form only");
+  if (f32 && (O.slab.on || O.planar || O.per_dir || !O.fwd32[0][0][0].p)) throw Error("fdmo_apply: fp32 transforms exist for the single-rank octant form only");
   OctPass P[3]; const int (&n_items)[3] = O.plans->n_items;
   for (int k = 0; k < 3; ++k) { P[k] = O.plans->pass[f32][k]; P[k].gate = gate; }
   if (gz_part && n_items[1] != O.gz_n) throw Error("fdmo_apply: the g.z partial buffer does not match the grid of pass 2");
@@ -1257,7 +1335,7 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
   if (f32 && !scratch) throw Error("fdmo_apply: the fp32 transforms need the scratch array");
   double *const mid = scratch ? scratch : z_oct;
   const double *const in[3] = {g_oct, mid, mid}; double *const out[3] = {mid, mid, z_oct};      // (pass 2 works in place)
-  for (int k = 0; k < 3; ++k) launch_pass_nt(s, O.nt, f32 ? PassVariant::OctantF32 : PassVariant::Octant, P[k], n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
+  for (int k = 0; k < 3; ++k) launch_pass_nt(s, k == 1 ? O.nt_z : O.nt, f32 ? PassVariant::OctantF32 : O.per_dir ? PassVariant::PerDirection : PassVariant::Octant, P[k], n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
   stamps.dump(s);
 }
 
@@ -1340,8 +1418,9 @@ void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double 
   if (n_items > 0) launch_pass_nt(s, O.nt, PassVariant::General, P, n_items, in, out);
 }
 
-#define PORO_OCT_LAUNCH(kernel, O, ...) do { if ((O).nc == 2) hipLaunchKernelGGL(kernel<2>, oct_grid((O).co_stride, 2), kBlock, 0, s, dims_of(O), __VA_ARGS__); \
-                                              else hipLaunchKernelGGL(kernel<3>, oct_grid((O).co_stride, 3), kBlock, 0, s, dims_of(O), __VA_ARGS__); } while (0)
+#define PORO_OCT_LAUNCH(kernel, O, ...) do { if ((O).nc == 2) hipLaunchKernelGGL((kernel<2, false>), oct_grid((O).co_stride, 2), kBlock, 0, s, dims_of(O), __VA_ARGS__); \
+                                              else if ((O).per_dir) hipLaunchKernelGGL((kernel<3, true>), oct_grid((O).co_stride, 3), kBlock, 0, s, dims_of(O), __VA_ARGS__); \
+                                              else hipLaunchKernelGGL((kernel<3, false>), oct_grid((O).co_stride, 3), kBlock, 0, s, dims_of(O), __VA_ARGS__); } while (0)
 // ---- planar form, host side: quadrant layout Q[c][2 py + px][ky][kx] (one plane), transforms as row-major h x h matrices F[mode][node] per (component, direction, parity) ----
 bool fdmo_planar_usable(int dim, const int nn[3]) { return dim == 2 && nn[0] >= 2 && nn[1] >= 2 && nn[0] <= 4096 && nn[1] <= 4096; }
 void fdmo_init_planar(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s, bool split) {
@@ -1413,15 +1492,17 @@ void fdmo_update_g(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, d
   if (single) PORO_OCT_LAUNCH(k_fdmo_update_g, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
   else PORO_OCT_LAUNCH(k_fdmo_update_g2, O, sc, parity, g, h, inert, partials_dh, partials_out, red);
 }
-template <int NC, bool XNT> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, int decided) {
-  hipLaunchKernelGGL((k_fdmo_update_d<NC, XNT>), oct_grid(O.co_stride, NC), kBlock, 0, s, dims_of(O), sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red,
+template <int NC, bool XNT, bool PD> static void launch_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, int decided) {
+  hipLaunchKernelGGL((k_fdmo_update_d<NC, XNT, PD>), oct_grid(O.co_stride, NC), kBlock, 0, s, dims_of(O), sc, parity, it, x, d, z, (int64_t)O.nc * O.n[0] * O.n[1] * O.n[2], partials_in, red,
                      gz_from_pass ? (const double *)O.gz_part.p : (const double *)nullptr, gz_from_pass ? O.gz_n : 0, decided);
 }
 void fdmo_update_d(hipStream_t s, const FdmOct &O, PcgScalars *sc, int parity, int it, double *x, double *d, const double *z, const double *partials_in, const double *red, bool gz_from_pass, bool stream_x, bool decided, bool gg_stored) {
   const int dec = decided ? (gg_stored && !red ? 2 : 1) : 0;
-  if (O.nc == 2) launch_update_d<2, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);       // (planar form)
-  else if (stream_x) launch_update_d<3, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
-  else launch_update_d<3, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
+  if (O.nc == 2) launch_update_d<2, false, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);       // (planar form)
+  else if (O.per_dir && stream_x) launch_update_d<3, true, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
+  else if (O.per_dir) launch_update_d<3, false, true>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
+  else if (stream_x) launch_update_d<3, true, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
+  else launch_update_d<3, false, false>(s, O, sc, parity, it, x, d, z, partials_in, red, gz_from_pass, dec);
 }
 
 }  // namespace poro

@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -19,9 +19,13 @@
 
 using namespace poro_host;
 
+static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
+                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
+                                  "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
+
 int main(int argc, char **argv) {
-  if (argc < 2) { std::cerr << "specify the file name" << std::endl; return 1; }   // parse_command_line.h:9-13
-  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false;
+  if (argc < 2) { std::cerr << "specify the file name" << std::endl << kUsage << std::endl; return 1; }   // parse_command_line.h:9-13 (the usage line is this driver's)
+  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false, fdm_per_direction = false;
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   for (int i = 2; i < argc; ++i) {
@@ -41,6 +45,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--atomic-scatter")) atomic_scatter = true;   // general meshes, --matrix-free: one launch per operator application with fp64 atomic adds (last bits differ from run to run)
     else if (!std::strcmp(argv[i], "--hybrid-operator")) hybrid_operator = true; // refined boxes (--refine-every), --matrix-free: the box's structured kernel + the general kernels on the fine cells only; no effect on box-tagged meshes, an error where the mesh cannot take it
     else if (!std::strcmp(argv[i], "--fdm-fp32")) fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--fdm-per-direction")) fdm_per_direction = true;   // with --block-fdm / --fastest: the per-direction form of the block FDM (single-rank 3D boxes whose directions are not all mirror-symmetric; elsewhere no effect)
     else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) refine_every = std::atoi(argv[++i]);            // 0 = never (default)
     else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) coarsen_fraction = std::atof(argv[++i]);
@@ -54,6 +59,7 @@ int main(int argc, char **argv) {
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
   if (fdm_fp32 && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
+  if (fdm_per_direction && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-per-direction needs --block-fdm or --fastest" << std::endl; return 1; }
   if (refine_every < 0) { std::cerr << "--refine-every needs a non-negative step count" << std::endl; return 1; }
   if (refine_every > 0 && !mesh_file.empty()) { std::cerr << "--refine-every adapts boxes only (not --mesh)" << std::endl; return 1; }
   try {
@@ -75,7 +81,7 @@ int main(int argc, char **argv) {
       if (refine_every > 0) build_refined_box_problem_mask(P, data.dim, n, size, degree, std::vector<uint8_t>((size_t)n[0] * n[1] * n[2], 0));
       else build_box_problem(P, data.dim, n, size, degree);
     }
-    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator;
+    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
     rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
@@ -93,6 +99,12 @@ int main(int argc, char **argv) {
                     << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
         };
       rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
+      if (fdm_per_direction) {           // (only with the option, so the reference's log stays as it is)
+        static const char *const runs[] = {"nodal kernels", "octant form", "per-direction form", "slab form", "planar form"};
+        int32_t req = 0, eff = 0, split[3] = {0, 0, 0};
+        if (poro_ctx_get_fdm_form(prob.context(), &req, &eff, split) != 0) throw std::runtime_error(poro_last_error());
+        std::cout << "block FDM form: " << runs[eff] << ", split directions (x y z): " << split[0] << " " << split[1] << " " << split[2] << std::endl;
+      }
       if (!pressure_labels.empty())
         std::cout << "prescribed pressures: " << prob.problem()->d.n_dirichlet_p << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner]
                   << ", projection preconditioner: " << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
