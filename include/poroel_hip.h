@@ -479,6 +479,27 @@ enum { PORO_FDM_RUNS_NODAL = 0, PORO_FDM_RUNS_OCTANT = 1, PORO_FDM_RUNS_PER_DIRE
 int  poro_ctx_set_fdm_form(poro_ctx *ctx, int32_t form);
 int  poro_ctx_get_fdm_form(poro_ctx *ctx, int32_t *requested, int32_t *effective, int32_t split[3]);
 
+/* Heterogeneous permeability: a per-cell k / mu for the pressure system (appended entry points, no struct changes: PORO_ABI_VERSION stays 4).
+ * poro_ctx_set_cell_permeability: k_over_mu[n_cells], one value per cell in the descriptor's cell order, replaces poro_material.k_over_mu in the pressure residual, the
+ * pressure Jacobian and poro_pres_solve: K_kappa = sum_c kappa_c K_c takes the place of kappa K.  NULL returns to the scalar; the residual and the Jacobian are then
+ * bitwise what they were before a field was set.  The projection (mass matrix) and the displacement system are not affected.  ONE RANK ONLY: refused (< 0, poro_last_error
+ * names the reason) on a partitioned context (n_ranks > 1), for a wrong n_cells and for a value that is not finite and > 0.  The call re-assembles the Laplace matrix and
+ * invalidates the cached Jacobian (call poro_pres_assemble_jacobian again), the ILU factor and the cached factors of the line solve below.
+ * poro_ctx_get_cell_permeability: kind = 0 no field; 1 a field that is constant (exact equality) within every cell layer of the SLOWEST direction of a uniform box or
+ * tensor-product grid (kappa(z) in 3D, kappa(y) in 2D); 2 any other field.  out (may be NULL) receives the values, n_cells as in the setter.
+ * Preconditioners of poro_pres_solve while a field is set (poro_supports_preconditioner(ctx, 1, ...) tells): PORO_PREC_JACOBI / NONE / ILU0 / SSOR as without one.
+ * PORO_PREC_FDM on uniform boxes and tensor-product grids, with or without whole prescribed faces: x (and y) transforms with the constant-coefficient eigenpairs, then one
+ * SPD tridiagonal solve per mode along the slowest direction, (a Mz + Kz^kappa + (lam_x + lam_y) Mz^kappa) t = r, then back.  kind 1: the exact inverse - a direct solve
+ * on matrix-free boxes (info.iterations = 0), the preconditioner of CG on tensor grids and CSR contexts.  kind 2: the same form built from the arithmetic layer means
+ * preconditions CG; never a direct solve (a field layered along another direction is of this kind: its layer means are one constant).  PORO_PREC_TWO_LEVEL is refused
+ * for the pressure system while a field is set: the coarse box is a constant-coefficient context.
+ * Exports with a field set: poro_export_csr(PORO_MAT_LAPLACE_P) returns K_kappa (the scalar is not applied), PORO_MAT_JACOBIAN_P returns M / (M_b dt) + K_kappa. */
+int  poro_ctx_set_cell_permeability(poro_ctx *ctx, const double *k_over_mu /* NULL: back to the scalar */, int64_t n_cells);
+int  poro_ctx_get_cell_permeability(poro_ctx *ctx, double *out /* may be NULL */, int64_t n_cells, int32_t *kind);
+/* parity hook: y = J x with the operator the Krylov solver of poro_pres_solve applies - the (variable-coefficient) stencil on matrix-free boxes, the CSR Jacobian elsewhere;
+ * without condensation and with the prescribed rows in place.  After poro_pres_assemble_jacobian; host in/out */
+int  poro_pres_apply_jacobian(poro_ctx *ctx, const double *x_host, double *y_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,7 +109,8 @@ HIP_SYMBOLS = [
     "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
     "poro_pres_estimate_error", "poro_state_transfer_p",
     "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get",
-    "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form"]
+    "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form",
+    "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian"]
 
 _hip = None
 _host = None
@@ -174,6 +175,9 @@ def load_hip():
         L.poro_timers_reset.argtypes = [C.c_void_p]
         L.poro_timers_enable.argtypes = [C.c_void_p, C.c_int]
         L.poro_timers_get.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
+        L.poro_ctx_set_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_ctx_get_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
+        L.poro_pres_apply_jacobian.argtypes = [C.c_void_p, _dp, _dp]
         _hip = L
     return _hip
 
@@ -214,6 +218,11 @@ def load_host():
         L.poro_host_build_gmsh_refined.argtypes = [C.c_char_p, C.c_int, C.c_int] + bc
         L.poro_host_set_pressure_bc.argtypes = [C.c_void_p, C.c_int, _ip, _dp]
         L.poro_host_tie_boundary.argtypes = [C.c_void_p, C.c_int, _ip, _ip]
+        L.poro_host_set_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_host_set_permeability_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.poro_host_inherit_cell_permeability.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_host_get_cell_permeability.restype = C.c_int64
+        L.poro_host_get_cell_permeability.argtypes = [C.c_void_p, _dp]
         L.poro_host_partition.restype = C.c_void_p
         L.poro_host_partition.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.poro_host_partition_ex.restype = C.c_void_p
@@ -423,6 +432,43 @@ class Problem:
         self.desc = self.desc_ptr.contents
         return self
 
+    def set_cell_permeability(self, values):
+        """extension: per-cell k / mu of the pressure system, one value per cell of this mesh (None: back to the scalar of the material).  Kept with the problem: Context,
+        run_problem and Runner hand it to the contexts they create, and an adaptive run carries it to every new mesh (a child takes its parent's value)"""
+        H = load_host()
+        if values is None:
+            rc = H.poro_host_set_cell_permeability(self.handle, None, 0)
+        else:
+            a, p = _arr_d(np.asarray(values).reshape(-1))
+            rc = H.poro_host_set_cell_permeability(self.handle, p, a.size)
+        if rc != 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        return self
+
+    def set_permeability_layers(self, layers):
+        """the same by layers [(top, value), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the value of the first layer whose top is >=
+        the coordinate of its centre"""
+        top, pt = _arr_d([l[0] for l in layers]); val, pv = _arr_d([l[1] for l in layers])
+        if load_host().poro_host_set_permeability_layers(self.handle, len(layers), pt, pv) != 0:
+            raise RuntimeError(load_host().poro_host_last_error().decode())
+        return self
+
+    def inherit_cell_permeability(self, old):
+        """what an adaptive run does with the field: this refined box takes the field of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
+        if load_host().poro_host_inherit_cell_permeability(self.handle, old.handle) != 0:
+            raise RuntimeError(load_host().poro_host_last_error().decode())
+        return self
+
+    def cell_permeability(self):
+        """the per-cell k / mu this problem carries, or None"""
+        H = load_host()
+        n = H.poro_host_get_cell_permeability(self.handle, None)
+        if not n:
+            return None
+        out = np.empty(n)
+        H.poro_host_get_cell_permeability(self.handle, out.ctypes.data_as(_dp))
+        return out
+
     def close(self):
         if self.handle:
             if self.owned:
@@ -445,6 +491,15 @@ class Context:
             p = C.c_void_p()
             self._chk(self.L.poro_ctx_create(problem.desc_ptr, device, operator_mode, C.byref(p)))
             ptr = p
+            carried = getattr(problem, "cell_permeability", None)      # (a Problem; descriptor holders of other kinds carry no field)
+            field = carried() if carried else None
+            if field is not None:                   # a per-cell k / mu the problem carries (Problem.set_cell_permeability / set_permeability_layers)
+                self.ptr = ptr
+                try:
+                    self.set_cell_permeability(field)
+                except RuntimeError:
+                    self.close()
+                    raise
         self.ptr = ptr
         self._cb = None
 
@@ -507,6 +562,34 @@ class Context:
         r, e, m = C.c_int32(), C.c_int32(), (C.c_int32 * 3)()
         self._chk(self.L.poro_ctx_get_fdm_form(self.ptr, C.byref(r), C.byref(e), m))
         return r.value, e.value, tuple(int(v) for v in m)
+
+    def set_cell_permeability(self, values):
+        """per-cell k / mu of the pressure system, one value per cell in the descriptor's cell order (None: back to the scalar of the material).  One rank; re-assembles
+        the Laplace matrix and invalidates the cached Jacobian: call pres_assemble_jacobian again.  Raises on a wrong length and on values that are not finite and > 0"""
+        if values is None:
+            self._chk(self.L.poro_ctx_set_cell_permeability(self.ptr, None, 0))
+            return
+        a, p = _arr_d(np.asarray(values).reshape(-1))
+        self._chk(self.L.poro_ctx_set_cell_permeability(self.ptr, p, a.size))
+
+    def get_cell_permeability(self):
+        """(values or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid (PREC_FDM is exact), 2 general"""
+        kind = C.c_int32()
+        self._chk(self.L.poro_ctx_get_cell_permeability(self.ptr, None, 0, C.byref(kind)))
+        if not kind.value:
+            return None, 0
+        out = np.empty(self.problem.desc.n_cells)
+        self._chk(self.L.poro_ctx_get_cell_permeability(self.ptr, out.ctypes.data_as(_dp), out.size, C.byref(kind)))
+        return out, kind.value
+
+    def pres_apply_jacobian(self, x):
+        """y = J x with the operator the Krylov solver of pres_solve applies (the stencil on matrix-free boxes, CSR elsewhere); after pres_assemble_jacobian"""
+        a, p = _arr_d(x)
+        if a.size != self.n_p:
+            raise ValueError("pres_apply_jacobian: one value per pressure dof")
+        y = np.empty_like(a)
+        self._chk(self.L.poro_pres_apply_jacobian(self.ptr, p, y.ctypes.data_as(_dp)))
+        return y
 
     def _len(self, which):
         return self.n_u if which in (VEC_U, VEC_RHS_U, VEC_DIAG_U) else self.n_p
@@ -683,13 +766,16 @@ _FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit f
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4):
+                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
     Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
     hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it).
-    fdm_per_direction=True: FDM_FORM_PER_DIRECTION for the block FDM of the displacement system (Context.set_fdm_form; carried over to every adapted mesh)."""
+    fdm_per_direction=True: FDM_FORM_PER_DIRECTION for the block FDM of the displacement system (Context.set_fdm_form; carried over to every adapted mesh).
+    permeability: per-cell k / mu (Problem.set_cell_permeability on `problem`, which keeps it), carried over to every adapted mesh."""
     H = load_host()
+    if permeability is not None:
+        problem.set_cell_permeability(permeability)
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
@@ -715,8 +801,10 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None):
         self.H = load_host()
+        if permeability is not None:             # per-cell k / mu: Problem.set_cell_permeability on `problem`, which keeps it; adapt() carries it to every new mesh
+            problem.set_cell_permeability(permeability)
         self.max_fss = max_fss
         h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
         if not h:

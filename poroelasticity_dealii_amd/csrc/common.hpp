@@ -302,6 +302,14 @@ struct poro_ctx {
   bool timing = false; std::map<std::string, poro::Timer> timers; std::vector<hipEvent_t> event_pool;
   double jac_dt = -1;
   poro::KellyDev kelly;
+  // per-cell k / mu of the pressure system (poro_ctx_set_cell_permeability; one rank).  kind: 0 none, 1 layered along the slowest direction of `lines`, 2 general.
+  // cell: the caller's cell order (the weights of the assembly, Kp = K_kappa).  lattice: lattice cell order, for the stencil kernels of matrix-free boxes.  layer: per cell
+  // layer of the slowest direction the value (kind 1) or the arithmetic mean (kind 2) - the coefficient of the line-solve form of PORO_PREC_FDM, one set of 1D arrays and
+  // cached reciprocal pivots per table set (free ends / fixed ends); `a` = the 1 / (M_b dt) the pivots belong to
+  struct Perm {
+    int kind = 0; std::vector<double> host, layer; poro::DevBuf<double> cell, lattice;
+    struct Line { bool built = false; int lo = 0, hi = 0; double a = -1; poro::DevBuf<double> coef, inv; } line[2];
+  } perm;
 };
 
 namespace poro {
@@ -394,7 +402,8 @@ void asm_u_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_
 // order / group_off: the boundary faces grouped by (colour of the cell, local face number), one launch per group (no atomics, fixed summation order)
 void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const std::vector<int64_t> &group_off, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id,
                    int n_neu, const int32_t *label, const int32_t *comp, const double *value, double *rhs);
-void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *M, double *K, double *src);
+// M, src == null: the Laplace matrix alone (K += K_c; with cell_w: K += cell_w[c] K_c, the per-cell coefficient of poro_ctx_set_cell_permeability)
+void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *M, double *K, double *src, const double *cell_w = nullptr);
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *u, int n_comp, const int32_t *comps /*host*/,
                   double *const *rhs /*host array of device ptrs*/);
 
@@ -409,6 +418,9 @@ void mf_diag(hipStream_t s, const MfArgs &a, double *diag);
 // y = (a M + kappa K) x for the Q1 pressure space of a uniform box (constant-coefficient 3^dim-point stencil)
 void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y);
 void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R);
+// the same with a per-cell coefficient kap (lattice cell order): y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q)
+void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, const double *x, double *y);
+void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, const double *t, const double *p, const double *src, double *R);
 
 // polynomial-preconditioner step fused into the structured operator's stores: z_new = z_j + omega D^-1 (g - A z_j), D^-1 in dictionary form; z_new != z_j
 struct KronCheb { const double *g = nullptr; double *znew = nullptr; double omega = 0; const uint8_t *cls = nullptr; const double *tab = nullptr;
@@ -428,6 +440,9 @@ void box_proj_rhs(hipStream_t s, int dim, const BoxCoupling &B, const double *u,
 void fdm_window_batch(hipStream_t s, double *grid, double *dense, double *dense_self, int self, bool to_block, const FdmWindow *win, int n_peers, int n_planes_pad, int64_t C, int64_t grid_stride, int64_t blk);
 void fdm_window(hipStream_t s, double *dst, const double *src, bool to_block, int n_planes, int n_planes_pad, int64_t C, int64_t ncols_valid, int64_t grid_stride, int64_t grid_col0, int64_t grid_plane0);
 void fdm_transform(hipStream_t s, const double *T, int n_l, int64_t SI, int64_t n_outer, const double *in, double *out, const FdmScale *scale);
+// layered per-cell coefficient: reciprocal pivots of the line systems (once per a), and the line solves themselves, between the x / y transforms (coef: perm_line.hpp)
+void q1_line_factor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv);
+void q1_line_solve(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out);   // in != out, [plane of the slowest direction][column]
 void fdm_apply(hipStream_t s, const FdmScalar &F, double a, const double k[3], const double *g, double *z, double *t1, double *t2);
 // ---- kernels_fdmu.hip ---------------------------------------------------------------------------
 void fdmu_upload_dir(FdmuDir &D, const LineTables &T, bool single, bool split);   // split: the even / odd form (T.parity required) unless a switch or `single` rules it out; D.split tells

@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include "common.hpp"
 #include "ctx_internal.hpp"
+#include "perm_line.hpp"
 
 using namespace poro;
 using namespace poro::ctx_detail;
@@ -392,6 +393,8 @@ struct Q1System {
   const uint8_t *inert_fdm = nullptr; // FDM: none, except with prescribed pressures on whole faces (the free-row system: residual norm and g . z see free rows only)
   Q1Set set = Q1Set::free_ends;       // FDM: the table set; fixed_ends = without the prescribed faces' end nodes
   Q1Set coarse_set = Q1Set::free_ends; // two-level: the coarse box's table set; fixed_ends = (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
+  const double *kap = nullptr;        // a per-cell k / mu is set and the operator is the box stencil: the field in lattice cell order (kappa is then 1: val holds a M + K_kappa)
+  int perm_kind = 0;                  // c->perm.kind for the pressure Jacobian (FDM: the line-solve form; direct only for kind 1), 0 for the projection
   bool distribute_inhom = true;       // constraints.distribute with the inhomogeneities; an UPDATE of a vector that already carries them (dp beside prescribed pressures) is distributed without
 };
 
@@ -408,7 +411,8 @@ bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE &&
 // Q1Set::fixed_ends + mask (prescribed pressures on whole faces): x_e = J_ff^-1 b_e on the free rows and exactly 0 on the masked ones; the check leaves the masked rows out,
 // where (J x)_i is the coupling to the free neighbours and not part of the system
 bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *const *b, double *const *x, double *y_scratch, bool batched,
-                     const poro_solver_opts *opts, poro_solve_info *info, Q1Set set = Q1Set::free_ends, const uint8_t *mask = nullptr) {
+                     const poro_solver_opts *opts, poro_solve_info *info, Q1Set set = Q1Set::free_ends, const uint8_t *mask = nullptr, const double *kap = nullptr) {
+  // kap != null (a layered per-cell k / mu, one rank): the line-solve form is the exact inverse, the check runs through the variable-coefficient stencil
   hipStream_t s = c->stream;
   const double *y[3];
   for (int e = 0; e < n; ++e) y[e] = y_scratch + (size_t)e * c->n_p;
@@ -418,12 +422,13 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
     fdmo_scalar_apply_many(s, c->q1_free.fused, a, kappa, n, b, x);
   } else {
     const double kk[3] = {kappa, kappa, kappa};
-    for (int e = 0; e < n; ++e) fdm_precondition_p(c, a, kk, b[e], x[e], set);
+    for (int e = 0; e < n; ++e) { if (kap) fdm_precondition_p_layered(c, a, b[e], x[e], set); else fdm_precondition_p(c, a, kk, b[e], x[e], set); }
   }
   for (int e = 0; e < n; ++e) {
     {
       Timed tm(c, "apply_p_stencil");
-      p_stencil_apply(s, c->dim, c->box, a, kappa, x[e], const_cast<double *>(y[e]));
+      if (kap) p_stencil_apply_var(s, c->dim, c->box, a, kap, x[e], const_cast<double *>(y[e]));
+      else p_stencil_apply(s, c->dim, c->box, a, kappa, x[e], const_cast<double *>(y[e]));
     }
     exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p);
   }
@@ -468,7 +473,8 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);
     if (stencil) {
       Timed tm(c, "apply_p_stencil");
-      p_stencil_apply(c->stream, c->dim, c->box, q.a, q.kappa, x, y);
+      if (q.kap) p_stencil_apply_var(c->stream, c->dim, c->box, q.a, q.kap, x, y);
+      else p_stencil_apply(c->stream, c->dim, c->box, q.a, q.kappa, x, y);
     } else {
       Timed tm(c, "apply_p_csr");
       la_csr_spmv(c->stream, c->Ap, q.val, x, y);
@@ -485,7 +491,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     build_fdm_q1(c, q.set);
     if (direct_first) {
       poro_solve_info direct;
-      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, sys.h, false, opts, &direct, q.set, q.inert_fdm)) {
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, sys.h, false, opts, &direct, q.set, q.inert_fdm, q.kap)) {
         if (info) *info = direct;
         return 0;
       }
@@ -493,7 +499,8 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     const double kk[3] = {q.kappa, q.kappa, q.kappa};
     sys.inert = q.inert_fdm;
     sys.prec.fn = [&](const double *g, double *z, const PrecCall &) {
-      fdm_precondition_p(c, q.a, kk, g, z, q.set);
+      if (q.perm_kind) fdm_precondition_p_layered(c, q.a, g, z, q.set);       // layer values (exact) or layer means
+      else fdm_precondition_p(c, q.a, kk, g, z, q.set);
       return GzLeft::nowhere;
     };
     return pcg(c, sys, opts, info);
@@ -661,6 +668,84 @@ int poro_ctx_get_fdm_form(poro_ctx *c, int32_t *requested, int32_t *effective, i
     }
     if (split) for (int d = 0; d < 3; ++d) split[d] = (mask >> d) & 1;
     return 0;
+  });
+}
+
+// Kp = sum_c w_c K_c over the coloured cell loop (w == null: the plain Laplace matrix, bit for bit what setup() assembled: same kernel, same order)
+static void assemble_laplace_p(poro_ctx *c, const double *w) {
+  hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
+  c->Kp.zero(s);
+  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_matrices(s, a, cells, n_cells, c->Ap.rp.p, c->Ap.col.p, nullptr, c->Kp.p, nullptr, w); });
+}
+int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Perm &P = c->perm;
+    auto invalidate = [&] { c->jac_dt = -1; c->ilu_J_valid = false; for (auto &L : P.line) { L.built = false; L.a = -1; } };
+    if (!k_over_mu) {
+      if (!P.kind) return 0;
+      assemble_laplace_p(c, nullptr);
+      P.kind = 0; P.host.clear(); P.layer.clear(); P.cell.release(); P.lattice.release();
+      invalidate();
+      return 0;
+    }
+    if (c->comm.part.n_ranks > 1 || c->comm.multi()) throw Error("poro_ctx_set_cell_permeability: partitioned contexts are not supported (one rank only)");
+    if (n_cells != c->n_cells) throw Error("poro_ctx_set_cell_permeability: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
+    for (int64_t i = 0; i < n_cells; ++i)
+      if (!(std::isfinite(k_over_mu[i]) && k_over_mu[i] > 0)) throw Error("poro_ctx_set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
+    std::vector<double> host(k_over_mu, k_over_mu + n_cells), lattice, layer;
+    int kind = 2;
+    if (c->lines.on) {
+      // boxes and tensor-product grids: the caller's cell order -> lattice order through every cell's first vertex (= its first pressure dof, lexicographic numbering)
+      const int dim = c->dim; const int nc[3] = {c->lines.n[0], c->lines.n[1], dim == 3 ? c->lines.n[2] : 1};
+      std::vector<int32_t> dofs((size_t)c->n_cells * c->nv);
+      PORO_HIP(hipMemcpyAsync(dofs.data(), c->cell_dofs_p.p, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      PORO_HIP(hipStreamSynchronize(c->stream));
+      lattice.assign((size_t)c->n_cells, 0.0);
+      std::vector<uint8_t> seen((size_t)c->n_cells, 0);
+      for (int64_t e = 0; e < c->n_cells; ++e) {
+        const int64_t v = dofs[(size_t)e * c->nv], np0 = nc[0] + 1, np1 = nc[1] + 1;
+        const int64_t i = v % np0, j = (v / np0) % np1, k = dim == 3 ? v / (np0 * np1) : 0;
+        if (i >= nc[0] || j >= nc[1] || k >= nc[2]) throw Error("poro_ctx_set_cell_permeability: cell " + std::to_string(e) + " does not start at a lattice cell's first vertex");
+        const int64_t at = (k * nc[1] + j) * nc[0] + i;
+        if (seen[at]) throw Error("poro_ctx_set_cell_permeability: two cells on one lattice cell");
+        seen[at] = 1; lattice[at] = host[e];
+      }
+      kind = perm_layers(dim, nc, lattice, layer) ? 1 : 2;
+    }
+    P.cell.upload(host);
+    if (c->box.enabled && c->lines.on) P.lattice.upload(lattice); else P.lattice.release();
+    assemble_laplace_p(c, P.cell.p);
+    P.host = std::move(host); P.layer = std::move(layer); P.kind = kind;
+    invalidate();
+    return 0;
+  });
+}
+int poro_ctx_get_cell_permeability(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) {
+  return guarded([&] {
+    if (!c || !kind) throw Error("null argument");
+    *kind = c->perm.kind;
+    if (out && c->perm.kind) {
+      if (n_cells != c->n_cells) throw Error("poro_ctx_get_cell_permeability: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
+      std::memcpy(out, c->perm.host.data(), (size_t)n_cells * sizeof(double));
+    }
+    return 0;
+  });
+}
+int poro_pres_apply_jacobian(poro_ctx *c, const double *x_host, double *y_host) {
+  return guarded([&] {
+    if (!c || !x_host || !y_host) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device)); hipStream_t s = c->stream;
+    if (c->jac_dt < 0) throw Error("pres_apply_jacobian before pres_assemble_jacobian");
+    const double a = 1. / c->mat.biot_M / c->jac_dt;
+    DevBuf<double> x, y; x.upload(x_host, c->n_p); y.alloc(c->n_p);
+    if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
+      if (c->perm.kind) p_stencil_apply_var(s, c->dim, c->box, a, c->perm.lattice.p, x.p, y.p);
+      else p_stencil_apply(s, c->dim, c->box, a, c->mat.k_over_mu, x.p, y.p);
+    } else la_csr_spmv(s, c->Ap, c->Jp.p, x.p, y.p);
+    exchange_add(c, y.p, c->n_p, c->comm.part.plane_p);
+    PORO_HIP(hipMemcpyAsync(y_host, y.p, c->n_p * sizeof(double), hipMemcpyDeviceToHost, s)); PORO_HIP(hipStreamSynchronize(s)); return 0;
   });
 }
 
@@ -894,8 +979,11 @@ int poro_pres_assemble_residual(poro_ctx *c, double dt, double *l2) {
     {
       Timed tm(c, "pressure_residual");
       la_pressure_tmp(s, c->tmp_p.p, vec(c, PORO_VEC_EPSV), vec(c, PORO_VEC_EPSV0), vec(c, PORO_VEC_P), vec(c, PORO_VEC_P_OLD), c->mat.biot_alpha / dt, 1. / c->mat.biot_M / dt, c->n_p);
-      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
-      else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
+      // a per-cell k / mu: Kp holds K_kappa (coefficient 1), the box stencil reads the field
+      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
+        if (c->perm.kind) p_residual_stencil_var(s, c->dim, c->box, c->perm.lattice.p, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
+        else p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
+      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
     }
     la_cons_reduce(s, c->cons_p, R);                                              // constraints.condense(residual) (:153); partial rows first, interface sums after
     exchange_add(c, R, c->n_p, c->comm.part.plane_p);
@@ -929,7 +1017,7 @@ int poro_pres_assemble_jacobian(poro_ctx *c, double dt) {
     // J = M/(M_b dt) + (k/mu) K depends on dt only (the reference recomputes it every pressure iteration): same dt, same matrix
     if (c->jac_dt == dt) return 0;
     Timed tm(c, "pressure_jacobian");
-    la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, c->mat.k_over_mu, c->Ap.nnz);
+    la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->Ap.nnz);   // (per-cell k / mu: Kp holds K_kappa)
     la_csr_diag(c->stream, c->Ap, c->Jp.p, c->diag_J.p);
     exchange_add(c, c->diag_J.p, c->n_p, c->comm.part.plane_p);
     if (!c->dinv_J.p) c->dinv_J.alloc(c->n_p);
@@ -951,7 +1039,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     const bool two_level_pdir = prec == PORO_PREC_TWO_LEVEL && c->n_pdir;           // the coarse box carries the prescribed set as whole faces (two_level_supported_pj)
     Q1System J;
     J.a = 1. / c->mat.biot_M / c->jac_dt;
-    J.kappa = c->mat.k_over_mu;
+    J.kappa = c->perm.kind ? 1.0 : c->mat.k_over_mu;
+    J.perm_kind = c->perm.kind;
+    if (c->perm.kind && q1_stencil(c)) J.kap = c->perm.lattice.p;
     J.val = c->Jp.p;
     J.dinv = c->dinv_J.p;
     J.ilu = &c->ilu_J;
@@ -977,7 +1067,7 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     bool direct_first = false;
     if (prec == PORO_PREC_FDM) {
       static const bool iterative = std::getenv("PORO_PRES_ITERATIVE") != nullptr;
-      direct_first = !iterative && opts->stop_rule == PORO_STOP_RHS && q1_stencil(c);
+      direct_first = !iterative && opts->stop_rule == PORO_STOP_RHS && q1_stencil(c) && c->perm.kind != 2;   // (a general field: the layer means precondition CG, never a direct solve)
     }
     return solve_q1(c, J, opts, info, direct_first);
   });

@@ -145,6 +145,7 @@ void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double om
 bool fdm_precondition_u_form(poro_ctx *c, const double *g_form, double *z_form, const PcgScalars *gate, int precision, double *scratch, double *gz_part = nullptr, const PcgStopTest &stop = PcgStopTest{});   // c->fdm_oct is built: g, z in its layout (slab / planar / octant form); precision, scratch, gz_part: of the octant form's passes
 void fdm_precondition_u_nodal(poro_ctx *c, const double *g, double *z, int precision);   // nodal g -> the form that is built (or the nodal kernels of fdm_precondition_u) -> nodal z
 void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which = Q1Set::free_ends);
+void fdm_precondition_p_layered(poro_ctx *c, double a, const double *g, double *z, Q1Set which = Q1Set::free_ends);   // a per-cell coefficient is set: the line-solve form with c->perm.layer (exact for kind 1)
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
 void release_fdm_u(poro_ctx *c);   // frees what build_fdm_u made; the next use builds again (a change of the requested form)

@@ -14,6 +14,7 @@
 #include <unordered_map>
 #include "common.hpp"
 #include "ctx_internal.hpp"
+#include "perm_line.hpp"
 
 using namespace poro;
 using namespace poro::ctx_detail;
@@ -196,6 +197,38 @@ void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *
   fdm_window_batch(s, back, F.recvbuf.p, nullptr, r, false, F.windows.p + 3 * N, N, F.max_nl, F.C, SIp, blk2);
   if (dim == 3) { fdm_transform(s, L.dir[1].S.p, L.dir[1].n, n0, nl, t2, t1, nullptr); fdm_transform(s, L.dir[0].S.p, n0, 1, (int64_t)L.dir[1].n * nl, t1, z, nullptr); }
   else fdm_transform(s, L.dir[0].S.p, n0, 1, nl, t1, z, nullptr);
+}
+
+// A per-cell k / mu is set (c->perm): z = (a M + K_layer)^-1 g with K_layer built from c->perm.layer, the layer values (kind 1: the exact inverse of the Jacobian) or the
+// layer means (kind 2: a preconditioner).  x / y transforms with the table set `which` (coefficient 1: kappa sits in the 1D matrices of the slowest direction), the line
+// solve, and back.  The 1D arrays are uploaded at the first use after the field changed, the reciprocal pivots computed on the device whenever a changed
+void fdm_precondition_p_layered(poro_ctx *c, double a, const double *g, double *z, Q1Set which) {
+  Timed tm(c, "precondition_p_fdm_layered");
+  const bool fixed = which == Q1Set::fixed_ends; const int last = c->dim - 1, nl = c->lines.n[last] + 1;
+  if (!c->perm.kind || c->comm.multi()) throw Error("fdm_precondition_p_layered: needs a per-cell permeability on a single-rank context");
+  FdmQ1 &T = q1_set(c, which);
+  poro_ctx::Perm::Line &L = c->perm.line[fixed ? 1 : 0];
+  if (!L.built) {
+    L.lo = fixed && c->pdir_face[last][0]; L.hi = fixed && c->pdir_face[last][1];
+    L.coef.upload(perm_line_coefficients(c->lines.hcell[last], c->perm.layer, L.lo, L.hi));
+    if (L.inv.n != (size_t)c->n_p) L.inv.alloc(c->n_p);
+    L.a = -1; L.built = true;
+  }
+  if (L.a != a) { q1_line_factor(c->stream, c->dim, T.nodal, nl, a, L.coef.p, L.inv.p); L.a = a; }
+  // 5 launches in 3D, 3 in 2D
+  hipStream_t s = c->stream; const FdmScalar &F = T.nodal; const int n0 = F.dir[0].n, n1 = F.dir[1].n; double *t1 = c->fdm_t1.p, *t2 = c->fdm_t2.p;
+  auto lines = [&](const double *in, double *out) { Timed tl(c, "q1_line_solve"); q1_line_solve(s, c->dim, F, nl, a, L.lo, L.hi, L.coef.p, L.inv.p, in, out); };
+  if (c->dim == 2) {
+    fdm_transform(s, F.dir[0].St.p, n0, 1, nl, g, t1, nullptr);
+    lines(t1, t2);
+    fdm_transform(s, F.dir[0].S.p, n0, 1, nl, t2, z, nullptr);
+  } else {
+    fdm_transform(s, F.dir[0].St.p, n0, 1, (int64_t)n1 * nl, g, t1, nullptr);
+    fdm_transform(s, F.dir[1].St.p, n1, n0, nl, t1, t2, nullptr);
+    lines(t2, t1);
+    fdm_transform(s, F.dir[1].S.p, n1, n0, nl, t1, t2, nullptr);
+    fdm_transform(s, F.dir[0].S.p, n0, 1, (int64_t)n1 * nl, t2, z, nullptr);
+  }
 }
 
 // ---- block fast diagonalisation of the displacement system (kernels_fdmu.hip) ---------------------------------------------------------
@@ -515,6 +548,9 @@ const char *prec_refusal(poro_ctx *c, int which_system, int prec, bool solving) 
     return solving ? nullptr : "unknown preconditioner";      // asymmetry kept: disp_solve runs an unknown value as PORO_PREC_NONE
   }
   if (which_system != 1 && which_system != 2) return "unknown system (0 displacement, 1 pressure, 2 projection)";
+  // a per-cell k / mu (poro_ctx_set_cell_permeability): the coarse box of the two-level form is a constant-coefficient context
+  if (which_system == 1 && c->perm.kind && prec == PORO_PREC_TWO_LEVEL)
+    return "PORO_PREC_TWO_LEVEL (pressure): not available while a per-cell permeability is set - the coarse box is a constant-coefficient context (PORO_PREC_JACOBI / NONE / ILU0 / SSOR everywhere, PORO_PREC_FDM on boxes and tensor-product grids)";
   if (which_system == 1 && (c->cons_p.n || c->n_pdir)) {
     // hanging rows: the two-level form.  Prescribed rows: two-level where the coarse box carries the condition as whole faces (two_level_supported_pj), the
     // fixed-ends table set where they cover whole faces of a box / tensor grid on one rank (fdm_pj_supported: never with hanging rows)

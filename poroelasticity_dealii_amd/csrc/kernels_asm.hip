@@ -258,7 +258,8 @@ template <int DIM> __global__ void k_asm_u_neumann(AsmArgs a, int64_t n_group, c
 // ---- K-asm-p + K-src-p: Q1 mass / Laplace matrices and the well source integral (one wave per cell) -----------
 template <int DIM> __global__ void __launch_bounds__(64)
 k_asm_p(AsmArgs a, const int32_t *__restrict__ cells, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, double *__restrict__ M,
-        double *__restrict__ K, double *__restrict__ src) {
+        double *__restrict__ K, double *__restrict__ src, const double *__restrict__ cell_w) {
+  // cell_w != null (poro_ctx_set_cell_permeability): K alone is assembled, every cell's Laplace entries times its weight - K_kappa = sum_c kappa_c K_c; M and src stay as they are
   constexpr int NV = 1 << DIM;
   __shared__ double sG[NV * NV * DIM];   // [q][v][d]
   __shared__ double sJi[NV * DIM * DIM];
@@ -298,9 +299,11 @@ k_asm_p(AsmArgs a, const int32_t *__restrict__ cells, const int64_t *__restrict_
     }
     const int32_t r = sDof[i];
     const int64_t pos = csr_find(col, rp[r], rp[r + 1], sDof[j]);
-    M[pos] += m; K[pos] += k;
+    if (cell_w) K[pos] += cell_w[cell] * k;
+    else if (M) { M[pos] += m; K[pos] += k; }
+    else K[pos] += k;
   }
-  for (int i = tid; i < NV; i += nt) {
+  if (src) for (int i = tid; i < NV; i += nt) {
     double s = 0;
     for (int q = 0; q < nq; ++q) s += a.fe.q1_qp[q * NV + i] * sS[q] * sJxW[q];
     src[sDof[i]] += s;
@@ -405,9 +408,9 @@ void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const 
                       hipLaunchKernelGGL(k_asm_u_neumann<3>, grid, 64, 0, s, a, n, o, bc, bl, bi, n_neu, label, comp, value, rhs));
   }
 }
-void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const int64_t *rp, const int32_t *col, double *M, double *K, double *src) {
+void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const int64_t *rp, const int32_t *col, double *M, double *K, double *src, const double *cell_w) {
   if (!n) return;
-  PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL(k_asm_p<2>, (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src), hipLaunchKernelGGL(k_asm_p<3>, (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src));
+  PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL(k_asm_p<2>, (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w), hipLaunchKernelGGL(k_asm_p<3>, (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w));
 }
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const double *u, int n_comp, const int32_t *comps, double *const *rhs) {
   if (!n || !n_comp) return;

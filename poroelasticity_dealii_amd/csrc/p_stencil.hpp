@@ -76,6 +76,104 @@ template <int DIM> __device__ __forceinline__ double p_stencil_sum(int n0, int n
   return acc;
 }
 
+// ---- per-cell coefficient: y = (a M + K_kappa) x, K_kappa = sum_c kappa_c K_c --------------------------------------------------------------------------------
+// The row of a node is the constant mass stencil above plus, over the <= 2^DIM cells around it, kappa_c times the row of the Q1 element Laplace matrix of a box
+// cell, K_e = k (x) m (x) m + m (x) k (x) m + m (x) m (x) k with the 1D element matrices m = h/6 [[2, 1], [1, 2]], k = 1/h [[1, -1], [-1, 1]].  kappa is stored
+// in lattice cell order (x fastest).  Same discipline as above: the cell index is clamped into the box and loaded unconditionally, a cell outside the box gets
+// weight 0 by a select, and cells and taps are summed in one fixed order - the result is the same bit for bit from call to call.
+template <int DIM> struct PStencilCells { static constexpr int N = 1 << DIM; double w[N]; };
+
+// the weights of the 2^DIM cells around `node`, index = c0 + 2 c1 (+ 4 c2) with c_d = 0 for the cell on the low side of the node in direction d
+template <int DIM> __device__ __forceinline__ void p_stencil_load_cells(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, PStencilCells<DIM> &C) {
+  const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
+  const int nc[3] = {n0 - 1, n1 - 1, n2 - 1};      // cells per direction (>= 1 in every direction of the box)
+  int at[3][2]; bool in[3][2];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) { const int ci = idx[d] - 1 + c; in[d][c] = ci >= 0 && ci < nc[d]; at[d][c] = min(max(ci, 0), nc[d] - 1); }
+  if constexpr (DIM == 2) {
+#pragma unroll
+    for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+      for (int c0 = 0; c0 < 2; ++c0) { const double v = kap[(int64_t)at[1][c1] * nc[0] + at[0][c0]]; C.w[2 * c1 + c0] = (in[0][c0] && in[1][c1]) ? v : 0.0; }
+  } else {
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+      for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+        for (int c0 = 0; c0 < 2; ++c0) {
+          const double v = kap[((int64_t)at[2][c2] * nc[1] + at[1][c1]) * nc[0] + at[0][c0]];
+          C.w[4 * c2 + 2 * c1 + c0] = (in[0][c0] && in[1][c1] && in[2][c2]) ? v : 0.0;
+        }
+  }
+}
+
+template <int DIM> __device__ __forceinline__ double p_stencil_sum_var(int n0, int n1, int n2, double h0, double h1, double h2, double a, int64_t node,
+                                                                       const PStencilTaps<DIM> &T, const PStencilCells<DIM> &C) {
+  const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
+  const int nd[3] = {n0, n1, n2};
+  const double h[3] = {h0, h1, h2};
+  double M1[3][3];             // the assembled 1D mass rows, as in p_stencil_sum
+  double em[3][2][3], ek[3][2][3];   // [direction][cell side][offset -1,0,+1]: the node's row of the 1D ELEMENT matrices of that cell; zero where the cell does not hold the neighbour
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    const double L = idx[d] > 0 ? 1.0 : 0.0, R = idx[d] < nd[d] - 1 ? 1.0 : 0.0;
+    M1[d][0] = L * h[d] / 6; M1[d][2] = R * h[d] / 6; M1[d][1] = (L + R) * h[d] / 3;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int o = 0; o < 3; ++o) {
+        const int own = 1 - c, other = own + o - 1;           // local vertex numbers of the node and of its neighbour in that cell
+        const bool held = other == 0 || other == 1;
+        em[d][c][o] = held ? (other == own ? h[d] / 3 : h[d] / 6) : 0.0;
+        ek[d][c][o] = held ? (other == own ? 1.0 / h[d] : -1.0 / h[d]) : 0.0;
+      }
+  }
+  double acc = 0;
+  if constexpr (DIM == 2) {
+#pragma unroll
+    for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+      for (int di = 0; di < 3; ++di) {
+        double wK = 0;
+#pragma unroll
+        for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+          for (int c0 = 0; c0 < 2; ++c0) {
+            const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1);        // (known at compile time after unrolling)
+            if (held) wK = fma(C.w[2 * c1 + c0], ek[0][c0][di] * em[1][c1][dj] + em[0][c0][di] * ek[1][c1][dj], wK);
+          }
+        const double w = a * (M1[0][di] * M1[1][dj]) + wK;
+        acc = w != 0.0 ? fma(w, T.v[3 * dj + di], acc) : acc;
+      }
+  } else {
+#pragma unroll
+    for (int dk = 0; dk < 3; ++dk)
+#pragma unroll
+      for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+        for (int di = 0; di < 3; ++di) {
+          double wK = 0;
+#pragma unroll
+          for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+              for (int c0 = 0; c0 < 2; ++c0) {
+                const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1) && (dk == 1 || dk == 2 * c2);
+                if (held)
+                  wK = fma(C.w[4 * c2 + 2 * c1 + c0],
+                           ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]) + em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk] + em[1][c1][dj] * ek[2][c2][dk]), wK);
+              }
+          const double w = a * (M1[0][di] * (M1[1][dj] * M1[2][dk])) + wK;
+          acc = w != 0.0 ? fma(w, T.v[9 * dk + 3 * dj + di], acc) : acc;
+        }
+  }
+  return acc;
+}
+
 template <int DIM> __device__ __forceinline__ double p_stencil_row(int n0, int n1, int n2, double h0, double h1, double h2, double a, double kappa, int64_t node,
                                                                    const double *__restrict__ x) {
   PStencilTaps<DIM> T;

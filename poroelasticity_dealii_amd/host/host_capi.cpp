@@ -208,6 +208,28 @@ int poro_host_tie_boundary(void *h, int n, const int32_t *labels, const int32_t 
     return 0;
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+// extension: per-cell k / mu of the pressure system, one value per cell of the problem's mesh (values == NULL: back to the scalar).  Kept with the problem; the drivers
+// hand it to every context they create from it (poro_ctx_set_cell_permeability), also on the meshes an adaptive run builds (a child takes its parent's value)
+int poro_host_set_cell_permeability(void *h, const double *values, int64_t n) {
+  try { static_cast<ProblemData *>(h)->set_cell_permeability(values, n); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// the same by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre
+int poro_host_set_permeability_layers(void *h, int n, const double *top, const double *value) {
+  try { static_cast<ProblemData *>(h)->set_permeability_layers(n, top, value); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// what refine_mesh does with the field: `h` (a refined box) takes the field of `old` (a refined box over the same coarse box), cell by coarse cell
+int poro_host_inherit_cell_permeability(void *h, void *old) {
+  try { static_cast<ProblemData *>(h)->inherit_cell_permeability(*static_cast<ProblemData *>(old)); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// the field the problem carries: returns its length (0: none), copies when out != NULL
+int64_t poro_host_get_cell_permeability(void *h, double *out) {
+  const auto &f = static_cast<ProblemData *>(h)->cell_k_over_mu;
+  if (out && !f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(double));
+  return (int64_t)f.size();
+}
 const poro_desc *poro_host_desc(void *h) { return &static_cast<ProblemData *>(h)->d; }
 void poro_host_free(void *h) { delete static_cast<ProblemData *>(h); }
 

@@ -437,6 +437,47 @@ struct ProblemData {
   bool refined_box = false; int box_n[3] = {1, 1, 1}; double box_size[3] = {1, 1, 1}; int box_k_u = 0;
   std::vector<uint8_t> refine_mask; std::vector<int32_t> cell_coarse, cell_child; std::vector<std::array<int, 3>> lattice_p;
   poro_desc d{};
+  // optional per-cell k / mu of the pressure system, one value per cell of `mesh` (empty: the scalar of `mat`).  Not part of poro_desc: whoever creates a context from this
+  // problem hands it over with poro_ctx_set_cell_permeability (PoroElasticProblem does, also for every mesh refine_mesh builds)
+  std::vector<double> cell_k_over_mu;
+  void set_cell_permeability(const double *values, int64_t n) {
+    if (!values) { cell_k_over_mu.clear(); return; }
+    if (n != mesh.n_cells()) throw std::runtime_error("set_cell_permeability: " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells");
+    for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
+    cell_k_over_mu.assign(values, values + n);
+  }
+  // layers along the slowest direction (z in 3D, y in 2D): a cell takes the value of the first layer whose `top` is >= the coordinate of its centre there
+  void set_permeability_layers(int n_layers, const double *top, const double *value) {
+    if (n_layers < 1 || !top || !value) throw std::runtime_error("set_permeability_layers: needs at least one TOP=VALUE layer");
+    const int dim = mesh.dim, nv = 1 << dim; const int64_t nc = mesh.n_cells();
+    std::vector<double> f((size_t)nc);
+    for (int64_t c = 0; c < nc; ++c) {
+      double z = 0;
+      for (int v = 0; v < nv; ++v) z += mesh.vertices[(size_t)mesh.cells[c * nv + v] * dim + (dim - 1)];
+      z /= nv;
+      int l = 0;
+      while (l < n_layers && !(top[l] >= z)) ++l;
+      if (l == n_layers) throw std::runtime_error("set_permeability_layers: the centre of cell " + std::to_string(c) + " (" + std::to_string(z) + ") lies above every layer top");
+      f[(size_t)c] = value[l];
+    }
+    set_cell_permeability(f.data(), nc);
+  }
+  // the field of a refined box `O` over the same coarse box on this refined box: every cell takes the value of its coarse cell - a child its parent's, a parent the mean of
+  // its children (which all hold the parent's value unless the caller set them apart)
+  void inherit_cell_permeability(const ProblemData &O) {
+    if (O.cell_k_over_mu.empty()) { cell_k_over_mu.clear(); return; }
+    if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error("inherit_cell_permeability: two refined boxes over the same coarse box are needed");
+    const size_t ncoarse = refine_mask.size();
+    std::vector<double> sum(ncoarse, 0.0), first(ncoarse, 0.0); std::vector<int> cnt(ncoarse, 0); std::vector<uint8_t> same(ncoarse, 1);
+    for (size_t c = 0; c < O.cell_coarse.size(); ++c) {
+      const int32_t cc = O.cell_coarse[c]; const double v = O.cell_k_over_mu[c];
+      if (!cnt[cc]) first[cc] = v; else if (v != first[cc]) same[cc] = 0;
+      sum[cc] += v; cnt[cc]++;
+    }
+    cell_k_over_mu.resize(cell_coarse.size());
+    // (one cell, or 2^dim equal values: the value itself, exactly; the mean is formed only where the children differ)
+    for (size_t c = 0; c < cell_coarse.size(); ++c) { const int32_t cc = cell_coarse[c]; cell_k_over_mu[c] = same[cc] ? first[cc] : sum[cc] / cnt[cc]; }
+  }
 
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are
   // not constrained yet, then close(): a hanging node whose master carries a boundary value gets it as an inhomogeneity

@@ -185,7 +185,8 @@ template <int dim> class PoroElasticProblem {
   // refine_mesh (:447-498) on one-level refined boxes, followed by the two calls of :338-339.  Sequence: estimate (KellyErrorEstimator on the device) -> mark
   // (fixed fraction + level limits, mesh.hpp) -> the new ProblemData from the mask -> a new context in the same operator mode, scatter mode, FDM precision and operator form ->
   // setup_dofs -> transfer of p, eps_v, eps_v0 on the device -> swap, the old context is destroyed.  The preconditioner choice of initialize() is made again on the
-  // new context (rc.preconditioner < 0 lands on the two-level form once hanging nodes exist).  Work counters carry over; the displacement warm start is lost (every
+  // new context (rc.preconditioner < 0 lands on the two-level form once hanging nodes exist; with a per-cell k / mu the pressure system takes Jacobi there: the library
+  // refuses the two-level form of the pressure system while a field is set).  Work counters carry over; the displacement warm start is lost (every
   // reinit of the reference leaves zero vectors).  Returns the cell counts before and after.
   std::pair<int64_t, int64_t> refine_mesh(const RunControls &rc) {
     const ProblemData &O = *pd;
@@ -198,6 +199,7 @@ template <int dim> class PoroElasticProblem {
     std::unique_ptr<ProblemData> N(new ProblemData());
     N->bc = O.bc; N->mat = O.mat;
     build_refined_box_problem_mask(*N, O.mesh.dim, O.box_n, O.box_size, O.box_k_u, mask);    // :481-483
+    N->inherit_cell_permeability(O);                                                         // a child takes its parent's k / mu; make_ctx below hands the field to the new context
     std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
     transfer_rows_p(O, *N, ptr, node, weight);
     int32_t scatter = PORO_SCATTER_COLOURED, fdm_req = PORO_FDM_FP64;
@@ -432,6 +434,11 @@ template <int dim> class PoroElasticProblem {
   static poro_ctx *make_ctx(ProblemData &P, int device, int operator_mode) {
     poro_ctx *c = nullptr;
     check(poro_ctx_create(&P.d, device, operator_mode, &c), "poro_ctx_create");
+    // a per-cell k / mu of the problem goes to the context before anything is assembled from it
+    if (!P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0) {
+      const std::string why = poro_last_error(); poro_ctx_destroy(c);
+      throw std::runtime_error("ctx_set_cell_permeability: " + why);
+    }
     return c;
   }
 };

@@ -1,10 +1,13 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
 // (read_mesh, :438-445).  --output DIR writes DIR/solution-NNNN.vtk after every step like output_results (:227-291).
 // --pressure-bc LABEL=VALUE (repeatable; an extension, the reference has no pressure boundary conditions) prescribes the pressure on a boundary label, e.g. a drained face
 // `--pressure-bc 3=0`; the run then also prints which preconditioners the pressure and projection systems got.
+// --permeability-layers TOP=VALUE[,TOP=VALUE...] (an extension: the reference's permeability is one constant) sets k / mu layer by layer along the slowest direction, in the
+// units of k / mu: a cell takes the VALUE of the first layer whose TOP is >= the coordinate of its centre (e.g. a caprock over a reservoir: `0=1e-11,5=1e-14` on the box
+// [-5, 5]^3).  --fastest then takes the fast diagonalisation for the pressure system on boxes and Jacobi elsewhere; the run prints the choice.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <cmath>
@@ -20,7 +23,7 @@
 using namespace poro_host;
 
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
-                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
+                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
 int main(int argc, char **argv) {
@@ -28,6 +31,7 @@ int main(int argc, char **argv) {
   std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false, fdm_per_direction = false;
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
+  std::vector<double> layer_top, layer_value;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -55,6 +59,19 @@ int main(int argc, char **argv) {
       if (!eq || end != eq || eq == arg || !end2 || end2 == eq + 1 || *end2 || label < 0) { std::cerr << "--pressure-bc needs LABEL=VALUE, got " << arg << std::endl; return 1; }
       pressure_labels.push_back((int32_t)label); pressure_values.push_back(value);
     }
+    else if (!std::strcmp(argv[i], "--permeability-layers") && i + 1 < argc) {   // k / mu by layers of the slowest direction, bottom to top
+      const std::string arg = argv[++i]; size_t at = 0;
+      while (at <= arg.size()) {
+        const size_t comma = std::min(arg.find(',', at), arg.size()); const std::string item = arg.substr(at, comma - at); const size_t eq = item.find('=');
+        char *e1 = nullptr, *e2 = nullptr;
+        const double top = std::strtod(item.c_str(), &e1), value = eq == std::string::npos ? 0.0 : std::strtod(item.c_str() + eq + 1, &e2);
+        if (eq == std::string::npos || eq == 0 || e1 != item.c_str() + eq || !e2 || e2 == item.c_str() + eq + 1 || *e2 || !(value > 0) || !std::isfinite(value) || (!layer_top.empty() && !(top > layer_top.back()))) {
+          std::cerr << "--permeability-layers needs TOP=VALUE[,TOP=VALUE...] with ascending tops and positive values, got " << arg << std::endl; return 1;
+        }
+        layer_top.push_back(top); layer_value.push_back(value);
+        at = comma + 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
@@ -81,6 +98,7 @@ int main(int argc, char **argv) {
       if (refine_every > 0) build_refined_box_problem_mask(P, data.dim, n, size, degree, std::vector<uint8_t>((size_t)n[0] * n[1] * n[2], 0));
       else build_box_problem(P, data.dim, n, size, degree);
     }
+    if (!layer_top.empty()) P.set_permeability_layers((int)layer_top.size(), layer_top.data(), layer_value.data());
     RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
@@ -92,7 +110,7 @@ int main(int argc, char **argv) {
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
     static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
     auto go = [&](auto &prob) {
-      if (!pressure_labels.empty())        // (only with the extension, so the reference's log stays as it is)
+      if (!pressure_labels.empty() || !layer_top.empty())        // (only with the extensions, so the reference's log stays as it is)
         prob.on_adapt = [&](int step, int64_t before, int64_t after) {     // the choice is made again on every adapted mesh
           std::cout << "adapted before step " << step << ": " << before << " -> " << after << " cells; prescribed pressures: " << prob.problem()->d.n_dirichlet_p
                     << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << ", projection preconditioner: "
@@ -104,6 +122,11 @@ int main(int argc, char **argv) {
         int32_t req = 0, eff = 0, split[3] = {0, 0, 0};
         if (poro_ctx_get_fdm_form(prob.context(), &req, &eff, split) != 0) throw std::runtime_error(poro_last_error());
         std::cout << "block FDM form: " << runs[eff] << ", split directions (x y z): " << split[0] << " " << split[1] << " " << split[2] << std::endl;
+      }
+      if (!layer_top.empty()) {
+        int32_t kind = 0;
+        if (poro_ctx_get_cell_permeability(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
+        std::cout << "permeability layers: " << layer_top.size() << ", field kind " << kind << "; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << std::endl;
       }
       if (!pressure_labels.empty())
         std::cout << "prescribed pressures: " << prob.problem()->d.n_dirichlet_p << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner]
