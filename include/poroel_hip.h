@@ -500,6 +500,31 @@ int  poro_ctx_get_cell_permeability(poro_ctx *ctx, double *out /* may be NULL */
  * without condensation and with the prescribed rows in place.  After poro_pres_assemble_jacobian; host in/out */
 int  poro_pres_apply_jacobian(poro_ctx *ctx, const double *x_host, double *y_host);
 
+/* Heterogeneous elastic moduli: a per-cell Lame lambda and shear modulus G for the displacement system (appended entry points, no struct changes: PORO_ABI_VERSION stays 4).
+ * poro_ctx_set_cell_moduli: lame_lambda[n_cells], shear_G[n_cells], one pair per cell in the descriptor's cell order, replace poro_material.lame_lambda / shear_G wherever the
+ * displacement system reads them: the general matrix-free cell kernels (both scatter modes, operator and diagonal), the coloured CSR assembly (so PORO_MAT_A_U, the SpMV, SSOR
+ * and ILU0 follow), the lifting of the Dirichlet values, poro_apply_operator and PORO_VEC_DIAG_U.  Both NULL returns to the scalars: results are then bitwise what they were
+ * before a field was set.  One NULL is refused.  ONE RANK ONLY: refused (< 0, poro_last_error names the reason) on a partitioned context (n_ranks > 1), on a context in
+ * PORO_OPFORM_HYBRID, for a wrong n_cells and for a cell whose values are not finite with G > 0 and 3 lambda + 2 G > 0 (the message names the cell).
+ * The call drops the assembled matrix, the Jacobi diagonal and its dictionary, the lifting vector, the element matrix, the Chebyshev eigenvalue estimate, the ILU factor and
+ * the FDM tables of the displacement system: call poro_disp_assemble_system next - it rebuilds whatever its rebuild flag says.
+ * Box-tagged contexts with a field: the structured kernels and the single element matrix are constant-coefficient, so operator, diagonal, lifting and the CSR assembly take the
+ * general cell loop (several times slower per application); PORO_PREC_CHEBYSHEV runs its unfused recurrence.  The coupling right-hand side, the pressure stencils
+ * and the projection do not depend on the moduli and keep their kernels.  poro_ctx_set_scatter_mode is honoured on such a box.
+ * Preconditioners of poro_disp_solve while a field is set (poro_supports_preconditioner(ctx, 0, ...) tells): PORO_PREC_JACOBI / CHEBYSHEV / NONE everywhere, ILU0 / SSOR on the
+ * assembled operator.  PORO_PREC_FDM on uniform boxes and tensor-product grids whose Dirichlet sets it accepts without a field: the x (and y) transforms with the eigenpairs of
+ * every (component, direction), then one SPD banded solve per component and mode along the slowest direction (tridiagonal for Q1, pentadiagonal for Q2; the factorisation is
+ * cached per field, (k_u + 1) n_u doubles), then back.  kind 1: the exact inverse of the block diagonal; kind 2: the same form built from the arithmetic layer means of lambda
+ * and G, a preconditioner.  With a field only the nodal tables are built: poro_ctx_set_fdm_precision, poro_ctx_set_fdm_form and the PORO_FDMO_* / PORO_FDMU_SINGLE switches
+ * are ignored (the getters report PORO_FDM_FP64 / PORO_FDM_RUNS_NODAL).  PORO_PREC_TWO_LEVEL is refused (the coarse box is a constant-coefficient context) and so is
+ * PORO_OPFORM_HYBRID, also the other way round: a context in the hybrid form refuses the field.
+ * poro_get_effective_stresses and poro_pres_update_volumetric_strain (K = lambda + 2 G / 3) then use NODAL moduli: at a pressure dof the arithmetic mean over the cells that
+ * touch it - the layer's value inside a layer, the mean on an interface.
+ * poro_ctx_get_cell_moduli: kind = 0 no field; 1 both arrays constant (exact equality) within every cell layer of the SLOWEST direction of a uniform box or tensor-product
+ * grid; 2 any other field.  lambda_out / G_out (each may be NULL) receive the values, n as n_cells in the setter. */
+int  poro_ctx_set_cell_moduli(poro_ctx *ctx, const double *lame_lambda, const double *shear_G /* both NULL: back to the scalars */, int64_t n_cells);
+int  poro_ctx_get_cell_moduli(poro_ctx *ctx, double *lambda_out, double *G_out /* may be NULL */, int64_t n, int32_t *kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,7 +110,8 @@ HIP_SYMBOLS = [
     "poro_pres_estimate_error", "poro_state_transfer_p",
     "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get",
     "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form",
-    "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian"]
+    "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian",
+    "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli"]
 
 _hip = None
 _host = None
@@ -178,6 +179,8 @@ def load_hip():
         L.poro_ctx_set_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64]
         L.poro_ctx_get_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
         L.poro_pres_apply_jacobian.argtypes = [C.c_void_p, _dp, _dp]
+        L.poro_ctx_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
+        L.poro_ctx_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _ip]
         _hip = L
     return _hip
 
@@ -223,6 +226,11 @@ def load_host():
         L.poro_host_inherit_cell_permeability.argtypes = [C.c_void_p, C.c_void_p]
         L.poro_host_get_cell_permeability.restype = C.c_int64
         L.poro_host_get_cell_permeability.argtypes = [C.c_void_p, _dp]
+        L.poro_host_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
+        L.poro_host_set_moduli_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+        L.poro_host_inherit_cell_moduli.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_host_get_cell_moduli.restype = C.c_int64
+        L.poro_host_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp]
         L.poro_host_partition.restype = C.c_void_p
         L.poro_host_partition.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.poro_host_partition_ex.restype = C.c_void_p
@@ -469,6 +477,45 @@ class Problem:
         H.poro_host_get_cell_permeability(self.handle, out.ctypes.data_as(_dp))
         return out
 
+    def set_cell_moduli(self, lame_lambda, shear_G):
+        """extension: per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell of this mesh (both None: back to the scalars of the material).
+        Kept with the problem like the permeability: Context, run_problem and Runner hand it to the contexts they create, an adaptive run carries it to every new mesh"""
+        H = load_host()
+        if lame_lambda is None and shear_G is None:
+            rc = H.poro_host_set_cell_moduli(self.handle, None, None, 0)
+        else:
+            a, pa = _arr_d(np.asarray(lame_lambda).reshape(-1)); b, pb = _arr_d(np.asarray(shear_G).reshape(-1))
+            if a.size != b.size:
+                raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
+            rc = H.poro_host_set_cell_moduli(self.handle, pa, pb, a.size)
+        if rc != 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        return self
+
+    def set_moduli_layers(self, layers):
+        """the same by layers [(top, young, poisson), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the first layer whose top is >= the
+        coordinate of its centre; lambda = E nu / ((1 + nu) (1 - 2 nu)), G = E / (2 (1 + nu)) as for the parameter file's values"""
+        top, pt = _arr_d([l[0] for l in layers]); E, pe = _arr_d([l[1] for l in layers]); nu, pn = _arr_d([l[2] for l in layers])
+        if load_host().poro_host_set_moduli_layers(self.handle, len(layers), pt, pe, pn) != 0:
+            raise RuntimeError(load_host().poro_host_last_error().decode())
+        return self
+
+    def inherit_cell_moduli(self, old):
+        """what an adaptive run does with the field: this refined box takes the moduli of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
+        if load_host().poro_host_inherit_cell_moduli(self.handle, old.handle) != 0:
+            raise RuntimeError(load_host().poro_host_last_error().decode())
+        return self
+
+    def cell_moduli(self):
+        """(lame_lambda, shear_G) this problem carries, or None"""
+        H = load_host()
+        n = H.poro_host_get_cell_moduli(self.handle, None, None)
+        if not n:
+            return None
+        lam = np.empty(n); G = np.empty(n)
+        H.poro_host_get_cell_moduli(self.handle, lam.ctypes.data_as(_dp), G.ctypes.data_as(_dp))
+        return lam, G
+
     def close(self):
         if self.handle:
             if self.owned:
@@ -497,6 +544,15 @@ class Context:
                 self.ptr = ptr
                 try:
                     self.set_cell_permeability(field)
+                except RuntimeError:
+                    self.close()
+                    raise
+            carried = getattr(problem, "cell_moduli", None)
+            moduli = carried() if carried else None
+            if moduli is not None:                  # per-cell lambda, G the problem carries (Problem.set_cell_moduli / set_moduli_layers)
+                self.ptr = ptr
+                try:
+                    self.set_cell_moduli(*moduli)
                 except RuntimeError:
                     self.close()
                     raise
@@ -581,6 +637,32 @@ class Context:
         out = np.empty(self.problem.desc.n_cells)
         self._chk(self.L.poro_ctx_get_cell_permeability(self.ptr, out.ctypes.data_as(_dp), out.size, C.byref(kind)))
         return out, kind.value
+
+    def set_cell_moduli(self, lame_lambda, shear_G):
+        """per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell in the descriptor's cell order (both None: back to the scalars of the
+        material; one None is refused).  One rank.  Drops the assembled displacement system: call disp_assemble next.  Raises on a wrong length and on values that are
+        not finite with G > 0 and 3 lambda + 2 G > 0"""
+        if lame_lambda is None and shear_G is None:
+            self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, None, None, 0))
+            return
+        if lame_lambda is None or shear_G is None:
+            a, pa = _arr_d(np.asarray(shear_G if lame_lambda is None else lame_lambda).reshape(-1))      # (the library words the refusal)
+            self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, None if lame_lambda is None else pa, None if shear_G is None else pa, a.size))
+            return
+        a, pa = _arr_d(np.asarray(lame_lambda).reshape(-1)); b, pb = _arr_d(np.asarray(shear_G).reshape(-1))
+        if a.size != b.size:
+            raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
+        self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, pa, pb, a.size))
+
+    def get_cell_moduli(self):
+        """(lame_lambda or None, shear_G or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid, 2 general"""
+        kind = C.c_int32()
+        self._chk(self.L.poro_ctx_get_cell_moduli(self.ptr, None, None, 0, C.byref(kind)))
+        if not kind.value:
+            return None, None, 0
+        lam = np.empty(self.problem.desc.n_cells); G = np.empty_like(lam)
+        self._chk(self.L.poro_ctx_get_cell_moduli(self.ptr, lam.ctypes.data_as(_dp), G.ctypes.data_as(_dp), lam.size, C.byref(kind)))
+        return lam, G, kind.value
 
     def pres_apply_jacobian(self, x):
         """y = J x with the operator the Krylov solver of pres_solve applies (the stencil on matrix-free boxes, CSR elsewhere); after pres_assemble_jacobian"""

@@ -101,7 +101,10 @@ struct FdmU : SlabLayout {
               int dim = 0; int nn[3] = {1, 1, 1}; double coef[3][3] = {}; FdmuDir dir[3][3]; FdmuDir last_global[3]; bool built = false, single = false;
               int fix[3][3][2] = {};
               // slab-partitioned form: node planes of the last direction are gathered per column group by an all-to-all (as FdmDist for the Q1 systems)
-              bool dist = false; DevBuf<double> sendbuf, recvbuf, tz1, tz2; };
+              bool dist = false; DevBuf<double> sendbuf, recvbuf, tz1, tz2;
+              // per-cell moduli (poro_ctx::mod): the last direction is a banded line solve between stage 0 and stage 1 of fdmu_apply (kernels_fdmu_line.hip).  line_coef:
+              // [component][3 matrices][k_u + 1 bands][nodes of the line], line_fac: the cached factorisation, (k_u + 1) n_u doubles; both go with the tables (release_fdm_u)
+              bool line = false; DevBuf<double> line_coef, line_fac; };
 // octant form of the block fast diagonalisation (kernels_fdmo.hip; 3D boxes, one rank, every direction mirror-symmetric for every component).
 // The even / odd butterflies of the three directions commute with everything inside the preconditioner, so they are hoisted out of it: the CG residual g and
 // the preconditioned residual z live as 8 octants per component, Q[c][o][kz][ky][kx] with o = 4 pz + 2 py + px (p = 0: even part e_k = v_k + v_k', 1: odd
@@ -310,9 +313,17 @@ struct poro_ctx {
     int kind = 0; std::vector<double> host, layer; poro::DevBuf<double> cell, lattice;
     struct Line { bool built = false; int lo = 0, hi = 0; double a = -1; poro::DevBuf<double> coef, inv; } line[2];
   } perm;
+  // per-cell Lame lambda and shear modulus G of the displacement system (poro_ctx_set_cell_moduli; one rank).  kind as for `perm`.  cell: [n_cells][2] = (lambda, G) in the
+  // caller's cell order, what the general cell kernels and the coloured assembly read.  node: [n_p][2], the arithmetic mean over the cells that touch a pressure dof - the
+  // constants of the effective stresses and of the fixed-stress strain update.  layer_lam / layer_G: per cell layer of the slowest direction the value (kind 1) or the
+  // arithmetic mean (kind 2).  While kind != 0 a box-tagged context runs the general cell loop for everything that depends on the moduli (box_fast_u below)
+  struct Moduli { int kind = 0; std::vector<double> host_lam, host_G, layer_lam, layer_G; poro::DevBuf<double> cell, node; } mod;
 };
 
 namespace poro {
+
+// the constant-coefficient structured kernels (k_kron*, the single Ke, box_asm_u_matrix, the diagonal dictionary) serve the displacement system: a box without per-cell moduli
+inline bool box_fast_u(const poro_ctx *c) { return c->box.enabled && !c->mod.kind; }
 
 // ---- kernels_la.hip -----------------------------------------------------------------------------
 void la_fill(hipStream_t s, double *x, double v, int64_t n);
@@ -358,6 +369,9 @@ void la_ilu_apply(hipStream_t s, const CsrDev &A, const double *lu, const SsorLe
 void la_ssor_apply(hipStream_t s, const CsrDev &A, const double *val, const SsorLevels &lv, double omega, const double *src, double *dst);
 void la_sum_strains(hipStream_t s, double *ev, const double *const *strains, int n, int64_t len);
 void la_effective_stress(hipStream_t s, const double *const *strains, double *const *stresses, int dim, double lam, double G, int64_t len);
+// the same two with nodal constants node_mod[len][2] = (lambda, G): sigma from them; ev[i] += alpha / (lambda_i + 2 G_i / 3) dp[i]
+void la_effective_stress_nodal(hipStream_t s, const double *const *strains, double *const *stresses, int dim, const double *node_mod, int64_t len);
+void la_strain_update_nodal(hipStream_t s, double *ev, const double *dp, double alpha, const double *node_mod, int64_t len);
 void la_set_constrained(hipStream_t s, double *x, const uint8_t *mask, const double *val, int64_t n);
 void la_rhs_u_finish(hipStream_t s, double *rhs, const double *lift, const double *neumann, const uint8_t *mask, int64_t n);
 // PCG pieces (device-side control, see solver in ctx.hip)
@@ -395,6 +409,7 @@ struct AsmArgs {
   poro_material mat;
   int interleaved_u;   // dof = node * dim + component everywhere (lets K-asm-u look CSR positions up per node pair)
   int mfg_sf;          // poro_ctx::mfg_sf: the sum-factorised general kernels may stand in for the table-driven one
+  const double *cell_mod;   // [n_cells][2] = (lambda, G) per cell, or null: mat.lame_lambda / mat.shear_G (see poro_ctx::mod)
 };
 void asm_u_matrix(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *val, double *lift);
 void asm_u_element_matrix(hipStream_t s, const AsmArgs &a, int32_t cell, double *Ke);
@@ -451,6 +466,12 @@ void fdmu_apply(hipStream_t s, const FdmU &F, const double *g, double *z, void *
 void fdmu_window(hipStream_t s, double *dst, const double *src, bool to_block, int ncomp, int n_planes, int n_planes_pad, int64_t C, int64_t ncols_valid,
                  int64_t grid_stride, int64_t grid_planes, int64_t grid_col0, int64_t grid_plane0);
 void fdmu_lines(hipStream_t s, const FdmU &F, const FdmuDir *last_dir, int64_t C, int64_t col0, int64_t ncol_valid, void *in, void *out);
+// ---- kernels_fdmu_line.hip: the line solve that stands in for the last direction's transform pair when per-cell moduli are set (moduli_line.hpp) ----
+// nl nodes per line, ncol columns per plane (x fastest, n0 of them per row); coef: [component][3][ku + 1][nl]; lam0 / lam1: the eigenvalues of the leading directions per
+// component by position along x / y (lam1 null in 2D; not finite = removed mode); fixed[c][side]: component c is prescribed on that end face of the line direction
+struct FdmuLineArgs { int nl, n0; int64_t ncol; const double *coef; const double *lam0[3], *lam1[3]; int fixed[3][2]; };
+void fdmu_line_factor(hipStream_t s, int ku, int ncomp, const FdmuLineArgs &a, double *fac /*[ncomp][ku + 1][nl][ncol]: reciprocal pivots, multipliers*/);
+void fdmu_line_solve(hipStream_t s, int ku, int ncomp, const FdmuLineArgs &a, const double *fac, double *v /*[ncomp][nl][ncol], in place*/);
 // ---- kernels_fdmo.hip: octant form (see FdmOct) --------------------------------------------------
 bool fdmo_usable(int dim, const int nn[3]);          // 3D, half lines of at most 128 entries (8 MFMA tiles)
 void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t s);   // sizes + buffers

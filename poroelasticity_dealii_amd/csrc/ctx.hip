@@ -161,7 +161,7 @@ double *z_u(poro_ctx *c) {
 // value is the Lanczos estimate (+5 %) capped by it.  Cached in c->cheb_lmax until the matrix is rebuilt
 double chebyshev_lmax(poro_ctx *c, const KrylovSystem &sys) {
   if (c->cheb_lmax > 0) return c->cheb_lmax;
-  const bool have_bound = c->box.enabled && c->Ke.p && !c->cons_u.n;
+  const bool have_bound = box_fast_u(c) && c->Ke.p && !c->cons_u.n;      // (per-cell moduli: no single element matrix, the Lanczos estimate alone)
   if (have_bound) {
     std::vector<double> ke((size_t)c->dpc_u * c->dpc_u);
     PORO_HIP(hipMemcpyAsync(ke.data(), c->Ke.p, ke.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -237,7 +237,7 @@ int solve_u_chebyshev(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info
     c->cheb_t.alloc(c->n_u);
     c->cheb_t.zero(s);
   }
-  const bool fusable = c->operator_mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && c->box.enabled && kron_supported(c->dim, c->k_u) && c->diag_u_cls.p && !c->cons_u.n &&
+  const bool fusable = c->operator_mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && box_fast_u(c) && kron_supported(c->dim, c->k_u) && c->diag_u_cls.p && !c->cons_u.n &&
                        !std::getenv("PORO_CHEB_UNFUSED");
   const bool fuse = fusable && !c->comm.multi();
   // slab partitions (3D): the fused kernel runs on every rank with its LOCAL partial product; on the two shared node planes it also leaves the raw partial, the neighbours
@@ -582,7 +582,7 @@ int poro_ctx_set_scatter_mode(poro_ctx *c, int32_t mode) {
   return guarded([&] {
     if (!c) throw Error("null argument");
     if (mode != PORO_SCATTER_COLOURED && mode != PORO_SCATTER_ATOMIC) throw Error("poro_ctx_set_scatter_mode: unknown mode " + std::to_string(mode) + " (PORO_SCATTER_COLOURED or PORO_SCATTER_ATOMIC)");
-    if (c->box.enabled) return 0;   // the structured kernels have no scatter: nothing to select
+    if (box_fast_u(c)) return 0;   // the structured kernels have no scatter: nothing to select (a box with per-cell moduli runs the general cell loop and takes the mode)
     PORO_HIP(hipSetDevice(c->device));
     if (mode == PORO_SCATTER_ATOMIC && c->operator_mode == PORO_OP_MATRIX_FREE) build_spatial_cells(c);   // (a CSR context that applies the matrix-free operator builds it then)
     c->scatter_mode = mode;
@@ -597,6 +597,7 @@ int poro_ctx_set_operator_form(poro_ctx *c, int32_t form) {
   return guarded([&] {
     if (!c) throw Error("null argument");
     if (form != PORO_OPFORM_GENERAL && form != PORO_OPFORM_HYBRID) throw Error("poro_ctx_set_operator_form: unknown form " + std::to_string(form) + " (PORO_OPFORM_GENERAL or PORO_OPFORM_HYBRID)");
+    if (form == PORO_OPFORM_HYBRID && c->mod.kind) throw Error("poro_ctx_set_operator_form: PORO_OPFORM_HYBRID is not available while per-cell moduli are set - the box part of the hybrid operator is a constant-coefficient kernel");
     if (c->box.enabled) return 0;   // the structured kernels already run on every cell: nothing to select
     PORO_HIP(hipSetDevice(c->device));
     if (form == PORO_OPFORM_HYBRID) hybrid_enable(c);   // throws where the mesh cannot take it: the form stays as it was (GENERAL, or a HYBRID that was accepted before)
@@ -749,6 +750,87 @@ int poro_pres_apply_jacobian(poro_ctx *c, const double *x_host, double *y_host) 
   });
 }
 
+// Per-cell Lame lambda and shear modulus G.  Everything the displacement system derives from the moduli is dropped here and rebuilt by the next
+// poro_disp_assemble_system: the assembled matrix, the Jacobi diagonal and its dictionary, the lifting, Ke, lambda_max of the Chebyshev form, the ILU factor, the FDM tables
+int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const double *shear_G, int64_t n_cells) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Moduli &M = c->mod;
+    auto invalidate = [&] {
+      c->matrix_built = false; c->ilu_u_valid = false; c->cheb_lmax = 0;
+      c->diag_u_cls.release(); c->diag_u_tab.release();
+      release_fdm_u(c);
+      for (int *h : {c->pcg_hint_u, c->pcg_hint_fdm_u, c->pcg_hint_cheb_u}) h[0] = h[1] = 0;
+    };
+    if (!lame_lambda && !shear_G) {
+      if (!M.kind) return 0;
+      PORO_HIP(hipStreamSynchronize(c->stream));
+      M.kind = 0; M.host_lam.clear(); M.host_G.clear(); M.layer_lam.clear(); M.layer_G.clear(); M.cell.release(); M.node.release();
+      invalidate();
+      return 0;
+    }
+    if (!lame_lambda || !shear_G) throw Error("poro_ctx_set_cell_moduli: lame_lambda and shear_G come together (one of the two arrays is NULL)");
+    if (c->comm.part.n_ranks > 1 || c->comm.multi()) throw Error("poro_ctx_set_cell_moduli: partitioned contexts are not supported (one rank only)");
+    if (c->operator_form == PORO_OPFORM_HYBRID) throw Error("poro_ctx_set_cell_moduli: the context runs PORO_OPFORM_HYBRID, whose box part is a constant-coefficient kernel (select PORO_OPFORM_GENERAL first)");
+    if (n_cells != c->n_cells) throw Error("poro_ctx_set_cell_moduli: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
+    for (int64_t i = 0; i < n_cells; ++i) {
+      const double l = lame_lambda[i], g = shear_G[i];
+      if (!(std::isfinite(l) && std::isfinite(g))) throw Error("poro_ctx_set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite");
+      if (!(g > 0)) throw Error("poro_ctx_set_cell_moduli: shear_G of cell " + std::to_string(i) + " is not > 0");
+      if (!(3 * l + 2 * g > 0)) throw Error("poro_ctx_set_cell_moduli: 3 lambda + 2 G of cell " + std::to_string(i) + " is not > 0");
+    }
+    std::vector<double> lam(lame_lambda, lame_lambda + n_cells), G(shear_G, shear_G + n_cells), layer_lam, layer_G;
+    std::vector<int32_t> dofs((size_t)c->n_cells * c->nv);
+    PORO_HIP(hipMemcpyAsync(dofs.data(), c->cell_dofs_p.p, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    int kind = 2;
+    if (c->lines.on) {
+      // boxes and tensor-product grids: the caller's cell order -> lattice order through every cell's first vertex (= its first pressure dof, lexicographic numbering)
+      const int dim = c->dim; const int nc[3] = {c->lines.n[0], c->lines.n[1], dim == 3 ? c->lines.n[2] : 1};
+      std::vector<double> lat_lam((size_t)c->n_cells, 0.0), lat_G((size_t)c->n_cells, 0.0);
+      std::vector<uint8_t> seen((size_t)c->n_cells, 0);
+      for (int64_t e = 0; e < c->n_cells; ++e) {
+        const int64_t v = dofs[(size_t)e * c->nv], np0 = nc[0] + 1, np1 = nc[1] + 1;
+        const int64_t i = v % np0, j = (v / np0) % np1, k = dim == 3 ? v / (np0 * np1) : 0;
+        if (i >= nc[0] || j >= nc[1] || k >= nc[2]) throw Error("poro_ctx_set_cell_moduli: cell " + std::to_string(e) + " does not start at a lattice cell's first vertex");
+        const int64_t at = (k * nc[1] + j) * nc[0] + i;
+        if (seen[at]) throw Error("poro_ctx_set_cell_moduli: two cells on one lattice cell");
+        seen[at] = 1; lat_lam[at] = lam[e]; lat_G[at] = G[e];
+      }
+      const bool l1 = perm_layers(dim, nc, lat_lam, layer_lam), l2 = perm_layers(dim, nc, lat_G, layer_G);      // (a layered array's values are its layer means)
+      kind = l1 && l2 ? 1 : 2;
+    }
+    // nodal constants of the pressure space: the arithmetic mean over the cells that touch the dof
+    std::vector<double> node((size_t)2 * c->n_p, 0.0), pair((size_t)2 * n_cells); std::vector<int32_t> touch((size_t)c->n_p, 0);
+    for (int64_t e = 0; e < n_cells; ++e) {
+      pair[2 * e] = lam[e]; pair[2 * e + 1] = G[e];
+      for (int v = 0; v < c->nv; ++v) { const int32_t d = dofs[(size_t)e * c->nv + v]; node[2 * (size_t)d] += lam[e]; node[2 * (size_t)d + 1] += G[e]; touch[d]++; }
+    }
+    for (int64_t i = 0; i < c->n_p; ++i) {
+      if (!touch[i]) { node[2 * i] = c->mat.lame_lambda; node[2 * i + 1] = c->mat.shear_G; continue; }      // (a dof no cell of this context touches)
+      node[2 * i] /= touch[i]; node[2 * i + 1] /= touch[i];
+    }
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    M.cell.upload(pair); M.node.upload(node);
+    M.host_lam = std::move(lam); M.host_G = std::move(G); M.layer_lam = std::move(layer_lam); M.layer_G = std::move(layer_G); M.kind = kind;
+    invalidate();
+    return 0;
+  });
+}
+int poro_ctx_get_cell_moduli(poro_ctx *c, double *lambda_out, double *G_out, int64_t n, int32_t *kind) {
+  return guarded([&] {
+    if (!c || !kind) throw Error("null argument");
+    *kind = c->mod.kind;
+    if ((lambda_out || G_out) && c->mod.kind) {
+      if (n != c->n_cells) throw Error("poro_ctx_get_cell_moduli: n is " + std::to_string(n) + ", the context has " + std::to_string(c->n_cells) + " cells");
+      if (lambda_out) std::memcpy(lambda_out, c->mod.host_lam.data(), (size_t)n * sizeof(double));
+      if (G_out) std::memcpy(G_out, c->mod.host_G.data(), (size_t)n * sizeof(double));
+    }
+    return 0;
+  });
+}
+
 void poro_ctx_destroy(poro_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -871,10 +953,10 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
-    if (rebuild_matrix || !c->matrix_built) {
+    if (rebuild_matrix || !c->matrix_built) {      // (poro_ctx_set_cell_moduli clears matrix_built: the next call rebuilds whatever the flag says)
       Timed tm(c, "assemble_u_matrix");
       c->lift_u.zero(s); c->neumann_u.zero(s);
-      if (c->operator_mode == PORO_OP_CSR && c->box_asm) {
+      if (c->operator_mode == PORO_OP_CSR && c->box_asm && !c->mod.kind) {
         // uniform box: one element matrix, every CSR entry written once by its owner (kernels_box.hip); the lifting -(A_full g) comes
         // from the unconstrained structured operator
         if (!c->Ke.p) c->Ke.alloc((size_t)c->dpc_u * c->dpc_u);
@@ -889,8 +971,8 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         c->Au_val.zero(s);
         for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_matrix(s, a, cells, n_cells, c->Au.rp.p, c->Au.col.p, c->Au_val.p, c->lift_u.p); });
         la_csr_diag(s, c->Au, c->Au_val.p, c->diag_u_local.p);
-      } else if (!c->box.enabled) {
-        // general mesh, matrix-free: the diagonal and the lifting -(A_full g) come from the same quadrature-level cell loop
+      } else if (!box_fast_u(c)) {
+        // general mesh (or a box with per-cell moduli), matrix-free: the diagonal and the lifting -(A_full g) come from the same quadrature-level cell loop
         // (coloured in either scatter mode: assembled data stay bitwise stable)
         count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, nullptr, c->diag_u_local.p, false, 1));
         count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->dir_val.p, c->wh_u.p, false, 0));
@@ -915,7 +997,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
       if (!c->dinv_u.p) c->dinv_u.alloc(c->n_u);
       la_reciprocal(s, c->dinv_u.p, c->diag_u.p, c->n_u);
       la_mask_zero(s, c->dinv_u.p, c->cons_u.inert.p, c->n_u);                   // zero reciprocal = inert (Dirichlet or hanging) dof (DiagVec)
-      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) build_diag_dictionary(c);
+      if (c->operator_mode == PORO_OP_MATRIX_FREE && box_fast_u(c)) build_diag_dictionary(c);
       c->matrix_built = true; c->ilu_u_valid = false; c->cheb_lmax = 0;
     }
     {
@@ -935,7 +1017,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
       if (c->cons_u.any_inhom) {
         la_fill(s, c->wd_u.p, 0.0, c->n_u); la_cons_expand(s, c->cons_u, c->wd_u.p, true);
         if (c->operator_mode == PORO_OP_CSR) la_csr_spmv(s, c->Au, c->Au_val.p, c->wd_u.p, c->wh_u.p);
-        else if (!c->box.enabled) {
+        else if (!box_fast_u(c)) {
           // general mesh: a set-up quantity like the lifting above, so coloured in either scatter mode (VEC_RHS_U stays bitwise stable); otherwise as mf_operator
           count_mfg_launches(c, mfg_apply(s, a, c->color_cells.p, c->color_off, c->n_u, c->wd_u.p, c->wh_u.p, true, 0));
           kron_fix_constrained(s, mf_args(c), c->wd_u.p, c->wh_u.p, nullptr, 0);
@@ -1074,7 +1156,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
 }
 
 int poro_pres_update_volumetric_strain(poro_ctx *c) {
-  return guarded([&] { PORO_HIP(hipSetDevice(c->device)); la_axpy(c->stream, vec(c, PORO_VEC_EPSV), c->mat.biot_alpha / c->mat.bulk_K, vec(c, PORO_VEC_DP), c->n_p); return 0; });
+  return guarded([&] { PORO_HIP(hipSetDevice(c->device)); if (c->mod.kind) la_strain_update_nodal(c->stream, vec(c, PORO_VEC_EPSV), vec(c, PORO_VEC_DP), c->mat.biot_alpha, c->mod.node.p, c->n_p);   // per-cell moduli: K = lambda + 2 G / 3 from the nodal means
+                         else la_axpy(c->stream, vec(c, PORO_VEC_EPSV), c->mat.biot_alpha / c->mat.bulk_K, vec(c, PORO_VEC_DP), c->n_p);
+                         return 0; });
 }
 
 int poro_proj_assemble_matrix(poro_ctx *c) {
@@ -1183,7 +1267,8 @@ int poro_get_effective_stresses(poro_ctx *c) {
     PORO_HIP(hipSetDevice(c->device));
     const int ne = c->dim * (c->dim + 1) / 2; const double *e[6]; double *g[6];
     for (int k = 0; k < ne; ++k) { e[k] = vec(c, PORO_VEC_STRAIN0 + k); g[k] = vec(c, PORO_VEC_STRESS0 + k); }
-    la_effective_stress(c->stream, e, g, c->dim, c->mat.lame_lambda, c->mat.shear_G, c->n_p);
+    if (c->mod.kind) la_effective_stress_nodal(c->stream, e, g, c->dim, c->mod.node.p, c->n_p);      // per-cell moduli: the nodal means
+    else la_effective_stress(c->stream, e, g, c->dim, c->mat.lame_lambda, c->mat.shear_G, c->n_p);
     PORO_HIP(hipStreamSynchronize(c->stream)); return 0;
   });
 }
@@ -1226,6 +1311,7 @@ int poro_apply_preconditioner_u(poro_ctx *c, int32_t preconditioner, const doubl
     if (!c->matrix_built) throw Error("apply_preconditioner_u before disp_assemble_system");
     DevBuf<double> g, z; g.upload(g_host, c->n_u); z.alloc(c->n_u); z.zero(s);
     if (preconditioner == PORO_PREC_FDM) {
+      if (const char *why = prec_refusal(c, 0, preconditioner, true)) throw Error(why);
       build_fdm_u(c);
       FdmOct &O = c->fdm_oct;
       // octant form where the solver uses it: butterflies outside (H, H'), the three transform passes in between - the timed part, as inside PCG

@@ -221,7 +221,7 @@ AsmArgs asm_args(poro_ctx *c) {
   AsmArgs a{};
   a.dim = c->dim; a.k_u = c->k_u; a.ns_u = c->ns_u; a.ns_p = c->ns_p; a.nv = c->nv; a.dpc_u = c->dpc_u; a.fe = c->fe;
   a.cell_dofs_u = c->cell_dofs_u.p; a.cell_dofs_p = c->cell_dofs_p.p; a.cell_X = c->cell_X.p; a.cell_geo = c->cell_geo.p; a.dir_mask = c->dir_mask.p; a.dir_val = c->dir_val.p; a.mat = c->mat;
-  a.interleaved_u = c->interleaved_u; a.mfg_sf = c->mfg_sf;
+  a.interleaved_u = c->interleaved_u; a.mfg_sf = c->mfg_sf; a.cell_mod = c->mod.kind ? c->mod.cell.p : nullptr;
   return a;
 }
 MfArgs mf_args(poro_ctx *c) {
@@ -274,7 +274,7 @@ void count_mfg_launches(poro_ctx *c, int n) { if (c->timing) c->timers["mfg_cell
 
 // y = A_u x without forming A_u: sum-factorised sweeps where available, element-matrix gather otherwise
 void mf_operator(poro_ctx *c, const double *x, double *y, bool constrained) {
-  if (!c->box.enabled) {   // general mesh: quadrature-level cell loop; the Dirichlet rows from the constraint list as for the structured kernels
+  if (!box_fast_u(c)) {   // general mesh, or a box with per-cell moduli: quadrature-level cell loop; the Dirichlet rows from the constraint list as for the structured kernels
     mfg_operator(c, x, y, constrained);
     if (constrained) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, 0);
     return;
@@ -295,14 +295,14 @@ bool is_u_vec(int which) { return which == PORO_VEC_U || which == PORO_VEC_RHS_U
 // by the operator kernel itself (fused), false when the caller still has to launch the dot kernel.
 bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_partials, bool fix_rows, const PcgScalars *pcg_state, bool exchange) {
   bool fused = false;
-  if (mode == PORO_OP_MATRIX_FREE && c->box.enabled && c->mf_variant == 1 && kron_supported(c->dim, c->k_u)) {
+  if (mode == PORO_OP_MATRIX_FREE && box_fast_u(c) && c->mf_variant == 1 && kron_supported(c->dim, c->k_u)) {
     const int slots = sampled_dispatch(c, "apply_u_matrix_free", [&](hipEvent_t e0, hipEvent_t e1) {
       return kron_apply(c->stream, mf_args(c), x, y, true, c->n_cus, dot_partials, e0, e1, pcg_state);
     });
     // inside PCG the Dirichlet rows are inert (zero residual and direction), so what the structured kernel leaves there is never read
     fused = dot_partials != nullptr && slots > 0;   // slots < 0: too many workgroups for the partial slots, the kernel ran without the fused x.y
     if (fix_rows) { Timed tm(c, "apply_u_dirichlet_rows"); kron_fix_constrained(c->stream, mf_args(c), x, y, fused ? dot_partials : nullptr, slots > 0 ? slots : -slots); }
-  } else if (mode == PORO_OP_MATRIX_FREE && !c->box.enabled) {
+  } else if (mode == PORO_OP_MATRIX_FREE && !box_fast_u(c)) {
     Timed tm(c, "apply_u_matrix_free");
     mfg_operator(c, x, y, true);
     if (fix_rows) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, 0);

@@ -148,6 +148,7 @@ void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *
 void fdm_precondition_p_layered(poro_ctx *c, double a, const double *g, double *z, Q1Set which = Q1Set::free_ends);   // a per-cell coefficient is set: the line-solve form with c->perm.layer (exact for kind 1)
 void analyse_fdm_u(poro_ctx *c);
 void build_fdm_u(poro_ctx *c);
+FdmuLineArgs fdmu_line_args(poro_ctx *c);   // per-cell moduli, after build_fdm_u: the arguments of the line-solve kernels (kernels_fdmu_line.hip)
 void release_fdm_u(poro_ctx *c);   // frees what build_fdm_u made; the next use builds again (a change of the requested form)
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);
 

@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "ctx_internal.hpp"
 #include "perm_line.hpp"
+#include "moduli_line.hpp"
 
 using namespace poro;
 using namespace poro::ctx_detail;
@@ -295,7 +296,11 @@ void build_fdm_u(poro_ctx *c) {
   if (c->fdm_u_state != 1) throw Error("PORO_PREC_FDM (displacement): " + c->fdm_u_why);
   const int dim = c->dim, last = dim - 1, ku = c->k_u;
   const bool multi = c->comm.multi();
-  F.dim = dim; F.single = !multi && std::getenv("PORO_FDMU_SINGLE") != nullptr;   // fp32 transforms (experimental switch, one rank)
+  // per-cell moduli (one rank): the nodal tables of the leading directions alone - no octant, planar, per-direction or fp32 form, whatever the settings ask for - and the
+  // banded line solve of the last direction (kernels_fdmu_line.hip) with the layer values (kind 1: the exact block inverse) or the layer means (kind 2)
+  const bool line = c->mod.kind != 0;
+  if (line && multi) throw Error("PORO_PREC_FDM (displacement): per-cell moduli on a partitioned context");
+  F.dim = dim; F.single = !multi && !line && std::getenv("PORO_FDMU_SINGLE") != nullptr;   // fp32 transforms (experimental switch, one rank)
   for (int d = 0; d < 3; ++d) F.nn[d] = d < dim ? c->lines.nn[d] : 1;
   const double l2g = c->mat.lame_lambda + 2 * c->mat.shear_G, G = c->mat.shear_G;
   for (int comp = 0; comp < dim; ++comp) for (int d = 0; d < dim; ++d) F.coef[comp][d] = d == comp ? l2g : G;
@@ -314,6 +319,7 @@ void build_fdm_u(poro_ctx *c) {
   LineTables tables[3][4]; bool same_ends[3], parity[3], parity_cd[3][3] = {};
   const auto key_of = [&](int comp, int d) { return F.fix[comp][d][0] * 2 + F.fix[comp][d][1]; };
   for (int d = 0; d < dim; ++d) {
+    if (line && d == last) { same_ends[d] = parity[d] = false; continue; }      // (no eigenpairs along the line direction)
     const bool global_dir = multi && d == last;
     const std::vector<double> hcell = global_dir ? std::vector<double>((size_t)n_cells_last, c->box.h[d]) : c->lines.hcell[d];
     same_ends[d] = parity[d] = true;
@@ -325,7 +331,7 @@ void build_fdm_u(poro_ctx *c) {
   }
   // octant form (kernels_fdmo.hip): one rank, 3D, every direction mirror-symmetric for every component, half lines of at most 128 entries
   // slab partitions: the quadrant form (x, y split locally; the z butterfly next to the all-to-all) under the same conditions on the GLOBAL line
-  bool oct_ok = !F.single && !std::getenv("PORO_FDMU_NO_OCT");
+  bool oct_ok = !F.single && !line && !std::getenv("PORO_FDMU_NO_OCT");
   // per-direction form (opt-in, poro_ctx_set_fdm_form; one rank, 3D): the same passes where only some directions are mirror-symmetric - one decision function (fdm_tables.hpp).
   // A box whose directions are all split is the octant form and takes its code path below; one with a line beyond the kernel's reach keeps the nodal kernels
   bool per_dir = false; FdmFormDecision form;
@@ -337,7 +343,7 @@ void build_fdm_u(poro_ctx *c) {
     for (int d = 0; d < dim; ++d) { symmetric = symmetric && same_ends[d]; all_parity = all_parity && parity[d]; }
     // the planar form also runs without the parity split; its split form and the 3D forms need the same ends everywhere and eigenvectors that are all even or odd
     oct_ok = oct_ok && ((planar && !symmetric) || (symmetric && all_parity));
-    if (c->fdm_form == PORO_FDM_FORM_PER_DIRECTION && !c->fdm_form_fixed && dim == 3 && !multi && !F.single && !std::getenv("PORO_FDMU_NO_OCT")) {
+    if (c->fdm_form == PORO_FDM_FORM_PER_DIRECTION && !c->fdm_form_fixed && dim == 3 && !multi && !F.single && !line && !std::getenv("PORO_FDMU_NO_OCT")) {
       form = fdm_form_decide(F.fix, parity_cd, nn3);
       per_dir = form.usable && !form.all_split;
     }
@@ -349,6 +355,7 @@ void build_fdm_u(poro_ctx *c) {
   // A direction takes the even / odd form of the nodal kernels (half the MFMA work) when it has the same ends and the parity for every component - all components
   // of a pass share one kernel
   for (int d = 0; d < dim; ++d) for (int comp = 0; comp < dim; ++comp) {
+    if (line && d == last) continue;
     const bool global_dir = multi && d == last;
     const LineTables &T = tables[d][key_of(comp, d)];
     FdmuDir &D = global_dir ? F.last_global[comp] : F.dir[comp][d];
@@ -359,7 +366,28 @@ void build_fdm_u(poro_ctx *c) {
   if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }
   if (oct_ok && !planar) fdmo_finalize(c->fdm_oct);
   c->fdm_oct.built = oct_ok;
+  if (line) {
+    std::vector<double> coef;
+    for (int comp = 0; comp < dim; ++comp) {
+      const std::vector<double> cc = moduli_line_coefficients(dim, ku, comp, c->lines.hcell[last], c->mod.layer_lam, c->mod.layer_G, F.fix[comp][last][0] != 0, F.fix[comp][last][1] != 0);
+      coef.insert(coef.end(), cc.begin(), cc.end());
+    }
+    F.line_coef.upload(coef);
+    F.line_fac.alloc((size_t)(ku + 1) * c->n_u);                                    // reciprocal pivots and multipliers: (k_u + 1) n_u doubles, at most 3 n_u
+    F.line = true;
+    fdmu_line_factor(c->stream, ku, dim, fdmu_line_args(c), F.line_fac.p);            // T does not depend on dt: once per field
+  }
   F.built = true;
+}
+FdmuLineArgs fdmu_line_args(poro_ctx *c) {
+  const FdmU &F = c->fdm_u; const int dim = F.dim, last = dim - 1;
+  FdmuLineArgs a{};
+  a.nl = F.nn[last]; a.n0 = F.nn[0]; a.ncol = c->n_u / dim / a.nl; a.coef = F.line_coef.p;
+  for (int comp = 0; comp < dim; ++comp) {
+    a.lam0[comp] = F.dir[comp][0].lam.p; a.lam1[comp] = dim == 3 ? F.dir[comp][1].lam.p : nullptr;
+    a.fixed[comp][0] = F.fix[comp][last][0]; a.fixed[comp][1] = F.fix[comp][last][1];
+  }
+  return a;
 }
 // slab form of the octant kernels: g, z in quadrant layout.  x / y sweeps on the local planes, whole z lines per column share between two all-to-alls
 static void fdm_precondition_u_slab(poro_ctx *c, const double *g, double *z, const PcgScalars *gate) {
@@ -499,6 +527,12 @@ void two_level_precondition_u(poro_ctx *c, const double *g, double *z, double om
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z) {
   Timed tm(c, "precondition_u_fdm");
   hipStream_t s = c->stream; FdmU &F = c->fdm_u;
+  if (F.line) {      // per-cell moduli: x (y) forward, one banded solve per mode column and component along the last direction, (y) x backward
+    fdmu_apply(s, F, g, z, c->fdmu_t1.p, c->fdmu_t2.p, 0);
+    { Timed tl(c, "fdm_u_line_solve"); fdmu_line_solve(s, c->k_u, F.dim, fdmu_line_args(c), F.line_fac.p, F.dim == 3 ? c->fdmu_t2.p : c->fdmu_t1.p); }
+    fdmu_apply(s, F, g, z, c->fdmu_t1.p, c->fdmu_t2.p, 1);
+    return;
+  }
   if (!F.dist) { fdmu_apply(s, F, g, z, c->fdmu_t1.p, c->fdmu_t2.p, 2); return; }
   // leading directions locally (the shared planes are transformed by both owners), then whole lines of the partitioned direction for this
   // rank's column group: gather by an all-to-all, fused forward / scale / backward pass with the GLOBAL 1D eigenvectors, scatter back
@@ -533,6 +567,9 @@ const char *prec_refusal(poro_ctx *c, int which_system, int prec, bool solving) 
   const char *one_rank = prec == PORO_PREC_SSOR ? "PORO_PREC_SSOR is a single-rank fidelity mode (the sweeps are order dependent)"
                                                 : "PORO_PREC_ILU0 is implemented for one rank (the factorisation is sequential in the row order)";
   if (which_system == 0) {
+    // per-cell moduli (poro_ctx_set_cell_moduli): the coarse box of the two-level form and the tables of the block fast diagonalisation are constant-coefficient
+    if (c->mod.kind && prec == PORO_PREC_TWO_LEVEL)
+      return "PORO_PREC_TWO_LEVEL (displacement): not available while per-cell moduli are set - the coarse box is a constant-coefficient context (PORO_PREC_JACOBI / CHEBYSHEV / NONE everywhere, ILU0 / SSOR on the assembled operator, PORO_PREC_FDM on boxes and tensor-product grids)";
     if (prec == PORO_PREC_TWO_LEVEL)
       return two_level_supported(c) ? nullptr : "PORO_PREC_TWO_LEVEL needs poro_desc.coarse (a refinement of a uniform box whose Dirichlet conditions cover whole faces)";
     // condensed operators exist at operator level only: Jacobi, the polynomial built on it, the two-level form above

@@ -135,7 +135,7 @@ k_asm_u_matrix(AsmArgs a, const int32_t *__restrict__ cells, int32_t single_cell
     }
   }
   __syncthreads();
-  const double lam = a.mat.lame_lambda, G = a.mat.shear_G;
+  const double lam = a.cell_mod ? a.cell_mod[2 * cell] : a.mat.lame_lambda, G = a.cell_mod ? a.cell_mod[2 * cell + 1] : a.mat.shear_G;   // per-cell moduli (poro_ctx_set_cell_moduli) where set
   auto entry = [&](int i, int j) {
     const int si = i / DIM, ci = i % DIM, sj = j / DIM, cj = j % DIM, o = si * ns + sj, nn = ns * ns;
     double t = lam * S.H[(ci * DIM + cj) * nn + o] + G * S.H[(cj * DIM + ci) * nn + o];

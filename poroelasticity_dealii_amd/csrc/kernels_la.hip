@@ -616,6 +616,30 @@ void la_effective_stress(hipStream_t s, const double *const *strains, double *co
   for (int k = 0; k < ne; ++k) { P.eps[k] = strains[k]; P.sig[k] = stresses[k]; }
   hipLaunchKernelGGL(k_effective_stress, grid_for(len), kBlock, 0, s, P, dim, lam, G, len);
 }
+// per-cell moduli (poro_ctx_set_cell_moduli): the constants at a pressure dof are node_mod[i] = (lambda_i, G_i)
+__global__ void k_effective_stress_nodal(SymPtrs P, int dim, const double *__restrict__ node_mod, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const int ne = dim == 2 ? 3 : 6;
+    const double lam = node_mod[2 * i], G = node_mod[2 * i + 1];
+    const double tr = dim == 2 ? P.eps[0][i] + P.eps[2][i] : P.eps[0][i] + P.eps[3][i] + P.eps[5][i];
+    for (int e = 0; e < ne; ++e) {
+      const bool diag = dim == 2 ? (e == 0 || e == 2) : (e == 0 || e == 3 || e == 5);
+      P.sig[e][i] = 2.0 * G * P.eps[e][i] + (diag ? lam * tr : 0.0);
+    }
+  }
+}
+__global__ void k_strain_update_nodal(double *__restrict__ ev, const double *__restrict__ dp, double alpha, const double *__restrict__ node_mod, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    ev[i] += alpha / (node_mod[2 * i] + 2.0 * node_mod[2 * i + 1] / 3.0) * dp[i];
+}
+void la_effective_stress_nodal(hipStream_t s, const double *const *strains, double *const *stresses, int dim, const double *node_mod, int64_t len) {
+  SymPtrs P{}; const int ne = dim == 2 ? 3 : 6;
+  for (int k = 0; k < ne; ++k) { P.eps[k] = strains[k]; P.sig[k] = stresses[k]; }
+  hipLaunchKernelGGL(k_effective_stress_nodal, grid_for(len), kBlock, 0, s, P, dim, node_mod, len);
+}
+void la_strain_update_nodal(hipStream_t s, double *ev, const double *dp, double alpha, const double *node_mod, int64_t len) {
+  hipLaunchKernelGGL(k_strain_update_nodal, grid_for(len), kBlock, 0, s, ev, dp, alpha, node_mod, len);
+}
 void la_sum_strains(hipStream_t s, double *ev, const double *const *strains, int n, int64_t len) {
   StrainPtrs sp{}; for (int k = 0; k < n; ++k) sp.p[k] = strains[k];
   hipLaunchKernelGGL(k_sum_strains, grid_for(len), kBlock, 0, s, ev, sp, n, len);

@@ -10,13 +10,25 @@
 // caller (inert inside PCG; poro_apply_operator finishes them from the constraint list).
 // Second scatter mode (opt-in, poro_ctx_set_scatter_mode): ONE launch over all cells, the final y[dof] += v a relaxed agent-scope fp64 atomic add
 // (global_atomic_add_f64).  Everything before the scatter is the same code; the sums then differ in the last bits from run to run.
+// Per-cell moduli (poro_ctx_set_cell_moduli): this file is compiled a second time, by kernels_mfg_cm.hip with PORO_MFG_CELL_MODULI defined - a static switch: the kernels
+// of that translation unit read the cell's (lambda, G) from AsmArgs::cell_mod, the kernels of this one are the constant-moduli kernels, instruction for instruction what
+// they were before the switch existed.  mfg_apply hands a call with a.cell_mod != null over to the other unit's mfg_apply_cell_moduli.
 #include "common.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 namespace poro {
+#ifdef PORO_MFG_CELL_MODULI
+int mfg_apply_cell_moduli(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
+                          const int32_t *all_cells);
+#endif
 namespace {
+#ifdef PORO_MFG_CELL_MODULI
+constexpr bool kCellModuli = true;
+#else
+constexpr bool kCellModuli = false;
+#endif
 
 template <int DIM> __device__ inline double jac_inv(const double *X, const double *dN, double *Ji) {
   constexpr int NV = 1 << DIM;
@@ -60,7 +72,7 @@ k_mfg(AsmArgs a, const int32_t *__restrict__ cells, const double *__restrict__ x
   const int tid = threadIdx.x;
   const int64_t cell = cells[blockIdx.x];
   const int nq = a.fe.nq_u, ns = a.ns_u, dpc = a.dpc_u;
-  const double lam = a.mat.lame_lambda, G = a.mat.shear_G;
+  const double lam = kCellModuli ? a.cell_mod[2 * cell] : a.mat.lame_lambda, G = kCellModuli ? a.cell_mod[2 * cell + 1] : a.mat.shear_G;   // kCellModuli: the cell's own pair, read once per cell
   for (int i = tid; i < NV * DIM; i += 64) sX[i] = a.cell_X[cell * NV * DIM + i];
   for (int i = tid; i < dpc; i += 64) {
     const int32_t dof = a.cell_dofs_u[cell * dpc + i];
@@ -150,7 +162,7 @@ k_mfg3_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
   const int64_t cell = slot < n_cells ? cells[slot] : cells[0];
   const int i = p % N1, j = (p / N1) % N1, k = p / (N1 * N1);
   const int ti = live ? i : 0, tj = live ? j : 0, tk = live ? k : 0;   // point of the 1D tables: dead lanes (N1 = 3: p = 27..31 has k = 3) stay inside them
-  const double lam = a.mat.lame_lambda, G = a.mat.shear_G;
+  const double lam = kCellModuli ? a.cell_mod[2 * cell] : a.mat.lame_lambda, G = kCellModuli ? a.cell_mod[2 * cell + 1] : a.mat.shear_G;   // kCellModuli: the cell's own pair, read once per cell
   int32_t dof[3] = {0, 0, 0}; bool dir[3] = {true, true, true};
   if (live) {
 #pragma unroll
@@ -308,7 +320,7 @@ k_mfg2_sf(AsmArgs a, Sf1D T, const int32_t *__restrict__ cells, int n_cells, con
   const bool live = p < NP && slot < n_cells;
   const int64_t cell = slot < n_cells ? cells[slot] : cells[0];
   const int i = p % N1, j = (p / N1) % N1;
-  const double lam = a.mat.lame_lambda, G = a.mat.shear_G;
+  const double lam = kCellModuli ? a.cell_mod[2 * cell] : a.mat.lame_lambda, G = kCellModuli ? a.cell_mod[2 * cell + 1] : a.mat.shear_G;   // kCellModuli: the cell's own pair, read once per cell
   int32_t dof[2] = {0, 0}; bool dir[2] = {true, true};
   if (live) {
 #pragma unroll
@@ -413,6 +425,7 @@ Sf1D sf_tables(int k) {
 
 }  // namespace
 
+#ifndef PORO_MFG_CELL_MODULI
 // does the descriptor carry the tables sf_tables(k) implies (tensor-product Gauss(k+1) points, x fastest; lexicographic equidistant Lagrange nodes)?
 // Only then may the sum-factorised kernels stand in for k_mfg, which reads poro_desc.fe like the assembly kernels do.
 bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k) {
@@ -447,6 +460,7 @@ bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k) {
   }
   return true;
 }
+#endif
 
 namespace {
 // one launch of the cell kernel that fits the mesh over `nc` cells of the list `cells`
@@ -470,8 +484,17 @@ void launch_cells(hipStream_t s, const AsmArgs &a, bool sf, const Sf1D &T, const
 
 // y = A_u x (mode 0) or y = diag(A_u) (mode 1); y is zeroed here.  all_cells == null: over the colour classes, one launch each (bitwise reproducible).
 // all_cells != null (mode 0 only): one launch over that list of all cells in any order, atomic scatter.  Returns the cell-kernel launches
+#ifdef PORO_MFG_CELL_MODULI
+int mfg_apply_cell_moduli(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
+                          const int32_t *all_cells) {
+  if (!a.cell_mod) throw Error("mfg_apply_cell_moduli: no per-cell moduli");
+#else
+int mfg_apply_cell_moduli(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
+                          const int32_t *all_cells);      // kernels_mfg_cm.hip: this file compiled with the switch
 int mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const std::vector<int64_t> &color_off, int64_t n_u, const double *x, double *y, bool constrained, int mode,
               const int32_t *all_cells) {
+  if (a.cell_mod) return mfg_apply_cell_moduli(s, a, color_cells, color_off, n_u, x, y, constrained, mode, all_cells);
+#endif
   if (a.fe.nq_u > kMaxNq || a.dpc_u > kMaxDpc) throw Error("mfg_apply: element too large");
   if (all_cells && mode != 0) throw Error("mfg_apply: the atomic scatter is for mode 0");
   PORO_HIP(hipMemsetAsync(y, 0, n_u * sizeof(double), s));
@@ -481,9 +504,12 @@ int mfg_apply(hipStream_t s, const AsmArgs &a, const int32_t *color_cells, const
   if (all_cells) {
     const int64_t nc = color_off.empty() ? 0 : color_off.back() - color_off.front();
     if (!nc) return 0;
+#ifndef PORO_MFG_CELL_MODULI
     static const bool transposed = std::getenv("PORO_MFG_ATOMIC_SHAPE") && std::string(std::getenv("PORO_MFG_ATOMIC_SHAPE")) == "transposed";
-    if (transposed && sf && a.dim == 3) launch_cells<kScatterAtomicTransposed>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);
-    else launch_cells<kScatterAtomic>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);
+    if (transposed && sf && a.dim == 3) launch_cells<kScatterAtomicTransposed>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);   // (diagnostic shape: constant moduli only)
+    else
+#endif
+    launch_cells<kScatterAtomic>(s, a, sf, T, all_cells, nc, x, y, constrained ? 1 : 0, mode);
     return 1;
   }
   int launches = 0;

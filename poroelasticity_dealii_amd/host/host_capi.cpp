@@ -230,6 +230,27 @@ int64_t poro_host_get_cell_permeability(void *h, double *out) {
   if (out && !f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(double));
   return (int64_t)f.size();
 }
+// extension: per-cell Lame lambda and shear modulus G of the displacement system (both NULL: back to the scalars); kept with the problem and handed over like the permeability
+int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) {
+  try { static_cast<ProblemData *>(h)->set_cell_moduli(lam, G, n); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre; (E, nu) -> (lambda, G) as the parameter file's are
+int poro_host_set_moduli_layers(void *h, int n, const double *top, const double *young, const double *poisson) {
+  try { static_cast<ProblemData *>(h)->set_moduli_layers(n, top, young, poisson); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+int poro_host_inherit_cell_moduli(void *h, void *old) {
+  try { static_cast<ProblemData *>(h)->inherit_cell_moduli(*static_cast<ProblemData *>(old)); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// the field the problem carries: returns its length (0: none), copies where the pointers are not NULL
+int64_t poro_host_get_cell_moduli(void *h, double *lam_out, double *G_out) {
+  const ProblemData &P = *static_cast<ProblemData *>(h);
+  if (lam_out && !P.cell_lambda.empty()) std::memcpy(lam_out, P.cell_lambda.data(), P.cell_lambda.size() * sizeof(double));
+  if (G_out && !P.cell_G.empty()) std::memcpy(G_out, P.cell_G.data(), P.cell_G.size() * sizeof(double));
+  return (int64_t)P.cell_lambda.size();
+}
 const poro_desc *poro_host_desc(void *h) { return &static_cast<ProblemData *>(h)->d; }
 void poro_host_free(void *h) { delete static_cast<ProblemData *>(h); }
 

@@ -479,6 +479,57 @@ struct ProblemData {
     for (size_t c = 0; c < cell_coarse.size(); ++c) { const int32_t cc = cell_coarse[c]; cell_k_over_mu[c] = same[cc] ? first[cc] : sum[cc] / cnt[cc]; }
   }
 
+  // optional per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell of `mesh` (empty: the scalars of `mat`).  Handed over like the
+  // permeability above, with poro_ctx_set_cell_moduli
+  std::vector<double> cell_lambda, cell_G;
+  void set_cell_moduli(const double *lam, const double *G, int64_t n) {
+    if (!lam && !G) { cell_lambda.clear(); cell_G.clear(); return; }
+    if (!lam || !G) throw std::runtime_error("set_cell_moduli: lambda and G come together");
+    if (n != mesh.n_cells()) throw std::runtime_error("set_cell_moduli: " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells");
+    for (int64_t i = 0; i < n; ++i)
+      if (!(std::isfinite(lam[i]) && std::isfinite(G[i]) && G[i] > 0 && 3 * lam[i] + 2 * G[i] > 0))
+        throw std::runtime_error("set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite with G > 0 and 3 lambda + 2 G > 0");
+    cell_lambda.assign(lam, lam + n); cell_G.assign(G, G + n);
+  }
+  // layers along the slowest direction by Young's modulus and Poisson's ratio: a cell takes the first layer whose `top` is >= the coordinate of its centre there; lambda and G
+  // by the formulas of InputDataPoroel::compute_derived_parameters
+  void set_moduli_layers(int n_layers, const double *top, const double *young, const double *poisson) {
+    if (n_layers < 1 || !top || !young || !poisson) throw std::runtime_error("set_moduli_layers: needs at least one TOP=YOUNG:POISSON layer");
+    for (int l = 0; l < n_layers; ++l)
+      if (!(std::isfinite(young[l]) && young[l] > 0 && poisson[l] > -1.0 && poisson[l] < 0.5))
+        throw std::runtime_error("set_moduli_layers: layer " + std::to_string(l) + " needs a Young's modulus > 0 and a Poisson ratio in (-1, 0.5)");
+    const int dim = mesh.dim, nv = 1 << dim; const int64_t nc = mesh.n_cells();
+    std::vector<double> lam((size_t)nc), G((size_t)nc);
+    for (int64_t c = 0; c < nc; ++c) {
+      double z = 0;
+      for (int v = 0; v < nv; ++v) z += mesh.vertices[(size_t)mesh.cells[c * nv + v] * dim + (dim - 1)];
+      z /= nv;
+      int l = 0;
+      while (l < n_layers && !(top[l] >= z)) ++l;
+      if (l == n_layers) throw std::runtime_error("set_moduli_layers: the centre of cell " + std::to_string(c) + " (" + std::to_string(z) + ") lies above every layer top");
+      const double E = young[l], nu = poisson[l];
+      lam[(size_t)c] = E * nu / ((1. + nu) * (1. - 2. * nu)); G[(size_t)c] = 0.5 * E / (1 + nu);
+    }
+    set_cell_moduli(lam.data(), G.data(), nc);
+  }
+  // as inherit_cell_permeability: a child takes its parent's pair, a coarsened parent the mean of its children
+  void inherit_cell_moduli(const ProblemData &O) {
+    if (O.cell_lambda.empty()) { cell_lambda.clear(); cell_G.clear(); return; }
+    if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error("inherit_cell_moduli: two refined boxes over the same coarse box are needed");
+    const size_t ncoarse = refine_mask.size();
+    const std::vector<double> *src[2] = {&O.cell_lambda, &O.cell_G}; std::vector<double> *dst[2] = {&cell_lambda, &cell_G};
+    for (int a = 0; a < 2; ++a) {
+      std::vector<double> sum(ncoarse, 0.0), first(ncoarse, 0.0); std::vector<int> cnt(ncoarse, 0); std::vector<uint8_t> same(ncoarse, 1);
+      for (size_t c = 0; c < O.cell_coarse.size(); ++c) {
+        const int32_t cc = O.cell_coarse[c]; const double v = (*src[a])[c];
+        if (!cnt[cc]) first[cc] = v; else if (v != first[cc]) same[cc] = 0;
+        sum[cc] += v; cnt[cc]++;
+      }
+      dst[a]->resize(cell_coarse.size());
+      for (size_t c = 0; c < cell_coarse.size(); ++c) { const int32_t cc = cell_coarse[c]; (*dst[a])[c] = same[cc] ? first[cc] : sum[cc] / cnt[cc]; }
+    }
+  }
+
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are
   // not constrained yet, then close(): a hanging node whose master carries a boundary value gets it as an inhomogeneity
   void close_constraints() {

@@ -199,6 +199,7 @@ template <int dim> class PoroElasticProblem {
     std::unique_ptr<ProblemData> N(new ProblemData());
     N->bc = O.bc; N->mat = O.mat;
     build_refined_box_problem_mask(*N, O.mesh.dim, O.box_n, O.box_size, O.box_k_u, mask);    // :481-483
+    N->inherit_cell_moduli(O);                                                               // likewise lambda, G (poro_ctx_set_cell_moduli)
     N->inherit_cell_permeability(O);                                                         // a child takes its parent's k / mu; make_ctx below hands the field to the new context
     std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
     transfer_rows_p(O, *N, ptr, node, weight);
@@ -438,6 +439,11 @@ template <int dim> class PoroElasticProblem {
     if (!P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0) {
       const std::string why = poro_last_error(); poro_ctx_destroy(c);
       throw std::runtime_error("ctx_set_cell_permeability: " + why);
+    }
+    // likewise per-cell moduli
+    if (!P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0) {
+      const std::string why = poro_last_error(); poro_ctx_destroy(c);
+      throw std::runtime_error("ctx_set_cell_moduli: " + why);
     }
     return c;
   }

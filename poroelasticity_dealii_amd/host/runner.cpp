@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -8,6 +8,9 @@
 // --permeability-layers TOP=VALUE[,TOP=VALUE...] (an extension: the reference's permeability is one constant) sets k / mu layer by layer along the slowest direction, in the
 // units of k / mu: a cell takes the VALUE of the first layer whose TOP is >= the coordinate of its centre (e.g. a caprock over a reservoir: `0=1e-11,5=1e-14` on the box
 // [-5, 5]^3).  --fastest then takes the fast diagonalisation for the pressure system on boxes and Jacobi elsewhere; the run prints the choice.
+// --moduli-layers TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] (an extension likewise) sets Young's modulus and Poisson's ratio layer by layer along the slowest direction, the
+// layers chosen by cell centres in the same way; lambda and G follow by the parameter file's formulas.  On a box the displacement operator then runs the general cell loop;
+// --fastest takes the fast diagonalisation (line-solve form) on boxes and Chebyshev elsewhere; the run prints the field's kind and the choice, also after every adapt.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <cmath>
@@ -23,7 +26,7 @@
 using namespace poro_host;
 
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
-                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
+                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
 int main(int argc, char **argv) {
@@ -32,6 +35,7 @@ int main(int argc, char **argv) {
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   std::vector<double> layer_top, layer_value;
+  std::vector<double> moduli_top, moduli_young, moduli_poisson;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -72,6 +76,20 @@ int main(int argc, char **argv) {
         at = comma + 1;
       }
     }
+    else if (!std::strcmp(argv[i], "--moduli-layers") && i + 1 < argc) {   // Young's modulus and Poisson's ratio by layers of the slowest direction, bottom to top
+      const std::string arg = argv[++i]; size_t at = 0;
+      while (at <= arg.size()) {
+        const size_t comma = std::min(arg.find(',', at), arg.size()); const std::string item = arg.substr(at, comma - at); const size_t eq = item.find('='), colon = item.find(':');
+        char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+        const bool shaped = eq != std::string::npos && eq != 0 && colon != std::string::npos && colon > eq + 1 && colon + 1 < item.size();
+        const double top = std::strtod(item.c_str(), &e1), young = shaped ? std::strtod(item.c_str() + eq + 1, &e2) : 0.0, poisson = shaped ? std::strtod(item.c_str() + colon + 1, &e3) : 0.0;
+        if (!shaped || e1 != item.c_str() + eq || e2 != item.c_str() + colon || !e3 || *e3 || !(young > 0) || !std::isfinite(young) || !(poisson > -1.0 && poisson < 0.5) || (!moduli_top.empty() && !(top > moduli_top.back()))) {
+          std::cerr << "--moduli-layers needs TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] with ascending tops, YOUNG > 0 and POISSON in (-1, 0.5), got " << arg << std::endl; return 1;
+        }
+        moduli_top.push_back(top); moduli_young.push_back(young); moduli_poisson.push_back(poisson);
+        at = comma + 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
@@ -99,6 +117,7 @@ int main(int argc, char **argv) {
       else build_box_problem(P, data.dim, n, size, degree);
     }
     if (!layer_top.empty()) P.set_permeability_layers((int)layer_top.size(), layer_top.data(), layer_value.data());
+    if (!moduli_top.empty()) P.set_moduli_layers((int)moduli_top.size(), moduli_top.data(), moduli_young.data(), moduli_poisson.data());
     RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
@@ -110,8 +129,14 @@ int main(int argc, char **argv) {
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
     static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
     auto go = [&](auto &prob) {
-      if (!pressure_labels.empty() || !layer_top.empty())        // (only with the extensions, so the reference's log stays as it is)
+      auto moduli_line = [&](std::ostream &os) {            // the field's kind on the present context and the displacement preconditioner chosen for it
+        int32_t kind = 0;
+        if (poro_ctx_get_cell_moduli(prob.context(), nullptr, nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
+        os << "moduli layers: " << moduli_top.size() << ", field kind " << kind << "; displacement preconditioner: " << prec_name[prob.displacement_solver.control.preconditioner];
+      };
+      if (!pressure_labels.empty() || !layer_top.empty() || !moduli_top.empty())        // (only with the extensions, so the reference's log stays as it is)
         prob.on_adapt = [&](int step, int64_t before, int64_t after) {     // the choice is made again on every adapted mesh
+          if (!moduli_top.empty()) { std::cout << "adapted before step " << step << ": "; moduli_line(std::cout); std::cout << std::endl; }
           std::cout << "adapted before step " << step << ": " << before << " -> " << after << " cells; prescribed pressures: " << prob.problem()->d.n_dirichlet_p
                     << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << ", projection preconditioner: "
                     << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
@@ -123,6 +148,7 @@ int main(int argc, char **argv) {
         if (poro_ctx_get_fdm_form(prob.context(), &req, &eff, split) != 0) throw std::runtime_error(poro_last_error());
         std::cout << "block FDM form: " << runs[eff] << ", split directions (x y z): " << split[0] << " " << split[1] << " " << split[2] << std::endl;
       }
+      if (!moduli_top.empty()) { moduli_line(std::cout); std::cout << std::endl; }
       if (!layer_top.empty()) {
         int32_t kind = 0;
         if (poro_ctx_get_cell_permeability(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
