@@ -273,6 +273,17 @@ def _arr_d(a):
     return a, a.ctypes.data_as(_dp)
 
 
+def _field_args(*arrays):
+    """the arguments of a per-cell field setter behind its handle: (the flattened arrays, which the caller keeps alive over the call; [pointer, ..., length]).  All None
+    (back to the scalars): null pointers and length 0"""
+    if all(a is None for a in arrays):
+        return (), [None] * len(arrays) + [0]
+    flat = [_arr_d(np.asarray(a).reshape(-1)) for a in arrays]
+    if len({a.size for a, _ in flat}) != 1:
+        raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
+    return flat, [p for _, p in flat] + [flat[0][0].size]
+
+
 def read_input(path=None):
     """InputDataPoroel::read_input_file (InputDataPoroel.h:77-86); path=None gives the declared defaults."""
     out = InputFlat()
@@ -424,8 +435,7 @@ class Problem:
         """extension: rigid frictionless plates [(boundary label, component)] - that displacement component takes one (unknown) value on the whole boundary;
         ordinary entries x[dof] = x[master] of the displacement constraint list (poro_desc.cons_u)"""
         lab, pl = _arr_i([c[0] for c in conditions]); comp, pc = _arr_i([c[1] for c in conditions])
-        if load_host().poro_host_tie_boundary(self.handle, len(conditions), pl, pc) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
+        self._host("tie_boundary", len(conditions), pl, pc)
         self.desc = self.desc_ptr.contents
         return self
 
@@ -435,86 +445,68 @@ class Problem:
         masters give.  The coarse problem of PREC_TWO_LEVEL (refined boxes: same labels; Gmsh grids with an auxiliary box: the labels translated to the box's sides)
         gets the same condition, also when it was built before this call"""
         lab, pl = _arr_i([c[0] for c in conditions]); val, pv = _arr_d([c[1] for c in conditions])
-        if load_host().poro_host_set_pressure_bc(self.handle, len(conditions), pl, pv) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
+        self._host("set_pressure_bc", len(conditions), pl, pv)
         self.desc = self.desc_ptr.contents
         return self
+
+    def _host(self, name, *args):
+        """poro_host_<name>(handle, *args); raises what the host layer reports"""
+        H = load_host()
+        if getattr(H, "poro_host_" + name)(self.handle, *args) != 0:
+            raise RuntimeError(H.poro_host_last_error().decode())
+        return self
+
+    def _carried(self, name, n_arrays):
+        """the n_arrays arrays of the per-cell field poro_host_get_<name> reads, or None where the problem carries none"""
+        get = getattr(load_host(), "poro_host_get_" + name)
+        n = get(self.handle, *[None] * n_arrays)
+        if not n:
+            return None
+        out = [np.empty(n) for _ in range(n_arrays)]
+        get(self.handle, *[o.ctypes.data_as(_dp) for o in out])
+        return out
 
     def set_cell_permeability(self, values):
         """extension: per-cell k / mu of the pressure system, one value per cell of this mesh (None: back to the scalar of the material).  Kept with the problem: Context,
         run_problem and Runner hand it to the contexts they create, and an adaptive run carries it to every new mesh (a child takes its parent's value)"""
-        H = load_host()
-        if values is None:
-            rc = H.poro_host_set_cell_permeability(self.handle, None, 0)
-        else:
-            a, p = _arr_d(np.asarray(values).reshape(-1))
-            rc = H.poro_host_set_cell_permeability(self.handle, p, a.size)
-        if rc != 0:
-            raise RuntimeError(H.poro_host_last_error().decode())
-        return self
+        keep, args = _field_args(values)
+        return self._host("set_cell_permeability", *args)
 
     def set_permeability_layers(self, layers):
         """the same by layers [(top, value), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the value of the first layer whose top is >=
         the coordinate of its centre"""
         top, pt = _arr_d([l[0] for l in layers]); val, pv = _arr_d([l[1] for l in layers])
-        if load_host().poro_host_set_permeability_layers(self.handle, len(layers), pt, pv) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
-        return self
+        return self._host("set_permeability_layers", len(layers), pt, pv)
 
     def inherit_cell_permeability(self, old):
         """what an adaptive run does with the field: this refined box takes the field of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
-        if load_host().poro_host_inherit_cell_permeability(self.handle, old.handle) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
-        return self
+        return self._host("inherit_cell_permeability", old.handle)
 
     def cell_permeability(self):
         """the per-cell k / mu this problem carries, or None"""
-        H = load_host()
-        n = H.poro_host_get_cell_permeability(self.handle, None)
-        if not n:
-            return None
-        out = np.empty(n)
-        H.poro_host_get_cell_permeability(self.handle, out.ctypes.data_as(_dp))
-        return out
+        f = self._carried("cell_permeability", 1)
+        return f and f[0]
 
     def set_cell_moduli(self, lame_lambda, shear_G):
         """extension: per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell of this mesh (both None: back to the scalars of the material).
         Kept with the problem like the permeability: Context, run_problem and Runner hand it to the contexts they create, an adaptive run carries it to every new mesh"""
-        H = load_host()
-        if lame_lambda is None and shear_G is None:
-            rc = H.poro_host_set_cell_moduli(self.handle, None, None, 0)
-        else:
-            a, pa = _arr_d(np.asarray(lame_lambda).reshape(-1)); b, pb = _arr_d(np.asarray(shear_G).reshape(-1))
-            if a.size != b.size:
-                raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
-            rc = H.poro_host_set_cell_moduli(self.handle, pa, pb, a.size)
-        if rc != 0:
-            raise RuntimeError(H.poro_host_last_error().decode())
-        return self
+        keep, args = _field_args(lame_lambda, shear_G)
+        return self._host("set_cell_moduli", *args)
 
     def set_moduli_layers(self, layers):
         """the same by layers [(top, young, poisson), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the first layer whose top is >= the
         coordinate of its centre; lambda = E nu / ((1 + nu) (1 - 2 nu)), G = E / (2 (1 + nu)) as for the parameter file's values"""
         top, pt = _arr_d([l[0] for l in layers]); E, pe = _arr_d([l[1] for l in layers]); nu, pn = _arr_d([l[2] for l in layers])
-        if load_host().poro_host_set_moduli_layers(self.handle, len(layers), pt, pe, pn) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
-        return self
+        return self._host("set_moduli_layers", len(layers), pt, pe, pn)
 
     def inherit_cell_moduli(self, old):
         """what an adaptive run does with the field: this refined box takes the moduli of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
-        if load_host().poro_host_inherit_cell_moduli(self.handle, old.handle) != 0:
-            raise RuntimeError(load_host().poro_host_last_error().decode())
-        return self
+        return self._host("inherit_cell_moduli", old.handle)
 
     def cell_moduli(self):
         """(lame_lambda, shear_G) this problem carries, or None"""
-        H = load_host()
-        n = H.poro_host_get_cell_moduli(self.handle, None, None)
-        if not n:
-            return None
-        lam = np.empty(n); G = np.empty(n)
-        H.poro_host_get_cell_moduli(self.handle, lam.ctypes.data_as(_dp), G.ctypes.data_as(_dp))
-        return lam, G
+        f = self._carried("cell_moduli", 2)
+        return f and tuple(f)
 
     def close(self):
         if self.handle:
@@ -538,24 +530,17 @@ class Context:
             p = C.c_void_p()
             self._chk(self.L.poro_ctx_create(problem.desc_ptr, device, operator_mode, C.byref(p)))
             ptr = p
-            carried = getattr(problem, "cell_permeability", None)      # (a Problem; descriptor holders of other kinds carry no field)
-            field = carried() if carried else None
-            if field is not None:                   # a per-cell k / mu the problem carries (Problem.set_cell_permeability / set_permeability_layers)
-                self.ptr = ptr
-                try:
-                    self.set_cell_permeability(field)
-                except RuntimeError:
-                    self.close()
-                    raise
-            carried = getattr(problem, "cell_moduli", None)
-            moduli = carried() if carried else None
-            if moduli is not None:                  # per-cell lambda, G the problem carries (Problem.set_cell_moduli / set_moduli_layers)
-                self.ptr = ptr
-                try:
-                    self.set_cell_moduli(*moduli)
-                except RuntimeError:
-                    self.close()
-                    raise
+            # the per-cell fields the problem carries (Problem.set_cell_permeability / set_permeability_layers, set_cell_moduli / set_moduli_layers)
+            for name, hand_over in (("cell_permeability", self.set_cell_permeability), ("cell_moduli", self.set_cell_moduli)):
+                carried = getattr(problem, name, None)                 # (a Problem; descriptor holders of other kinds carry no field)
+                field = carried() if carried else None
+                if field is not None:
+                    self.ptr = ptr
+                    try:
+                        hand_over(*(field if isinstance(field, tuple) else (field,)))
+                    except RuntimeError:
+                        self.close()
+                        raise
         self.ptr = ptr
         self._cb = None
 
@@ -619,50 +604,40 @@ class Context:
         self._chk(self.L.poro_ctx_get_fdm_form(self.ptr, C.byref(r), C.byref(e), m))
         return r.value, e.value, tuple(int(v) for v in m)
 
+    def _get_field(self, get, n_arrays):
+        """(array or None, ..., kind) of the per-cell field the getter `get` of the library reads"""
+        kind = C.c_int32()
+        self._chk(get(self.ptr, *[None] * n_arrays, 0, C.byref(kind)))
+        if not kind.value:
+            return (None,) * n_arrays + (0,)
+        out = [np.empty(self.problem.desc.n_cells) for _ in range(n_arrays)]
+        self._chk(get(self.ptr, *[o.ctypes.data_as(_dp) for o in out], out[0].size, C.byref(kind)))
+        return (*out, kind.value)
+
     def set_cell_permeability(self, values):
         """per-cell k / mu of the pressure system, one value per cell in the descriptor's cell order (None: back to the scalar of the material).  One rank; re-assembles
         the Laplace matrix and invalidates the cached Jacobian: call pres_assemble_jacobian again.  Raises on a wrong length and on values that are not finite and > 0"""
-        if values is None:
-            self._chk(self.L.poro_ctx_set_cell_permeability(self.ptr, None, 0))
-            return
-        a, p = _arr_d(np.asarray(values).reshape(-1))
-        self._chk(self.L.poro_ctx_set_cell_permeability(self.ptr, p, a.size))
+        keep, args = _field_args(values)
+        self._chk(self.L.poro_ctx_set_cell_permeability(self.ptr, *args))
 
     def get_cell_permeability(self):
         """(values or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid (PREC_FDM is exact), 2 general"""
-        kind = C.c_int32()
-        self._chk(self.L.poro_ctx_get_cell_permeability(self.ptr, None, 0, C.byref(kind)))
-        if not kind.value:
-            return None, 0
-        out = np.empty(self.problem.desc.n_cells)
-        self._chk(self.L.poro_ctx_get_cell_permeability(self.ptr, out.ctypes.data_as(_dp), out.size, C.byref(kind)))
-        return out, kind.value
+        return self._get_field(self.L.poro_ctx_get_cell_permeability, 1)
 
     def set_cell_moduli(self, lame_lambda, shear_G):
         """per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell in the descriptor's cell order (both None: back to the scalars of the
         material; one None is refused).  One rank.  Drops the assembled displacement system: call disp_assemble next.  Raises on a wrong length and on values that are
         not finite with G > 0 and 3 lambda + 2 G > 0"""
-        if lame_lambda is None and shear_G is None:
-            self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, None, None, 0))
-            return
-        if lame_lambda is None or shear_G is None:
+        if (lame_lambda is None) != (shear_G is None):
             a, pa = _arr_d(np.asarray(shear_G if lame_lambda is None else lame_lambda).reshape(-1))      # (the library words the refusal)
             self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, None if lame_lambda is None else pa, None if shear_G is None else pa, a.size))
             return
-        a, pa = _arr_d(np.asarray(lame_lambda).reshape(-1)); b, pb = _arr_d(np.asarray(shear_G).reshape(-1))
-        if a.size != b.size:
-            raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
-        self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, pa, pb, a.size))
+        keep, args = _field_args(lame_lambda, shear_G)
+        self._chk(self.L.poro_ctx_set_cell_moduli(self.ptr, *args))
 
     def get_cell_moduli(self):
         """(lame_lambda or None, shear_G or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid, 2 general"""
-        kind = C.c_int32()
-        self._chk(self.L.poro_ctx_get_cell_moduli(self.ptr, None, None, 0, C.byref(kind)))
-        if not kind.value:
-            return None, None, 0
-        lam = np.empty(self.problem.desc.n_cells); G = np.empty_like(lam)
-        self._chk(self.L.poro_ctx_get_cell_moduli(self.ptr, lam.ctypes.data_as(_dp), G.ctypes.data_as(_dp), lam.size, C.byref(kind)))
-        return lam, G, kind.value
+        return self._get_field(self.L.poro_ctx_get_cell_moduli, 2)
 
     def pres_apply_jacobian(self, x):
         """y = J x with the operator the Krylov solver of pres_solve applies (the stencil on matrix-free boxes, CSR elsewhere); after pres_assemble_jacobian"""

@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/poroel_hip.h"
 #include "fdm_tables.hpp"      // poro::Error (declared there: that header compiles without this one) and LineTables, the 1D tables of a grid line
+#include "cell_field.hpp"      // poro::CellField, the host state of a per-cell coefficient field
 
 namespace poro {
 
@@ -305,19 +306,19 @@ struct poro_ctx {
   bool timing = false; std::map<std::string, poro::Timer> timers; std::vector<hipEvent_t> event_pool;
   double jac_dt = -1;
   poro::KellyDev kelly;
-  // per-cell k / mu of the pressure system (poro_ctx_set_cell_permeability; one rank).  kind: 0 none, 1 layered along the slowest direction of `lines`, 2 general.
-  // cell: the caller's cell order (the weights of the assembly, Kp = K_kappa).  lattice: lattice cell order, for the stencil kernels of matrix-free boxes.  layer: per cell
-  // layer of the slowest direction the value (kind 1) or the arithmetic mean (kind 2) - the coefficient of the line-solve form of PORO_PREC_FDM, one set of 1D arrays and
-  // cached reciprocal pivots per table set (free ends / fixed ends); `a` = the 1 / (M_b dt) the pivots belong to
-  struct Perm {
-    int kind = 0; std::vector<double> host, layer; poro::DevBuf<double> cell, lattice;
+  // The per-cell coefficient fields (ctx_fields.hip; one rank).  Both are a poro::CellField (cell_field.hpp): kind 0 none, 1 layered along the slowest direction of
+  // `lines`, 2 general; host[a]: the caller's arrays; layer[a]: per cell layer of that direction the value (kind 1) or the arithmetic mean (kind 2) - the coefficients of
+  // the line-solve forms of PORO_PREC_FDM.  What each adds is its device state.  perm: k / mu of the pressure system.  cell: the caller's cell order (the weights of the
+  // assembly, Kp = K_kappa).  lattice: lattice cell order, for the stencil kernels of matrix-free boxes.  line: one set of 1D arrays and cached reciprocal pivots per
+  // table set (free ends / fixed ends); `a` = the 1 / (M_b dt) the pivots belong to
+  struct Perm : poro::CellField<1> {
+    poro::DevBuf<double> cell, lattice;
     struct Line { bool built = false; int lo = 0, hi = 0; double a = -1; poro::DevBuf<double> coef, inv; } line[2];
   } perm;
-  // per-cell Lame lambda and shear modulus G of the displacement system (poro_ctx_set_cell_moduli; one rank).  kind as for `perm`.  cell: [n_cells][2] = (lambda, G) in the
-  // caller's cell order, what the general cell kernels and the coloured assembly read.  node: [n_p][2], the arithmetic mean over the cells that touch a pressure dof - the
-  // constants of the effective stresses and of the fixed-stress strain update.  layer_lam / layer_G: per cell layer of the slowest direction the value (kind 1) or the
-  // arithmetic mean (kind 2).  While kind != 0 a box-tagged context runs the general cell loop for everything that depends on the moduli (box_fast_u below)
-  struct Moduli { int kind = 0; std::vector<double> host_lam, host_G, layer_lam, layer_G; poro::DevBuf<double> cell, node; } mod;
+  // mod: (Lame lambda, shear modulus G) of the displacement system, components 0 and 1.  cell: [n_cells][2] = (lambda, G) in the caller's cell order, what the general
+  // cell kernels and the coloured assembly read.  node: [n_p][2], the arithmetic mean over the cells that touch a pressure dof - the constants of the effective stresses and
+  // of the fixed-stress strain update.  While kind != 0 a box-tagged context runs the general cell loop for everything that depends on the moduli (box_fast_u below)
+  struct Moduli : poro::CellField<2> { poro::DevBuf<double> cell, node; } mod;
 };
 
 namespace poro {

@@ -1,4 +1,5 @@
-// extern "C" entry points of include/poroel_hip.h (the drop-in boundary); the host logic behind them lives in ctx_setup / ctx_comm / ctx_pcg / ctx_prec.hip.
+// extern "C" entry points of include/poroel_hip.h (the drop-in boundary); the host logic behind them lives in ctx_setup / ctx_comm / ctx_pcg / ctx_prec.hip, the entry points
+// of the per-cell coefficient fields in ctx_fields.hip.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <algorithm>
@@ -12,24 +13,12 @@
 #include <unordered_map>
 #include "common.hpp"
 #include "ctx_internal.hpp"
-#include "perm_line.hpp"
 
 using namespace poro;
 using namespace poro::ctx_detail;
 
 namespace {
-template <class F> int guarded(F &&f) {
-  try { return f(); }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
-
 // ---- pieces of poro_disp_assemble_system ------------------------------------------------------------------------------------------------
-// fn(cells, n_cells) once per colour of the cell colouring (one launch each: the cells of a colour share no dof)
-template <class F> void for_each_colour(poro_ctx *c, F &&fn) {
-  for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
-    fn(c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k]);
-}
-
 // lifting -(A_full g) on the free rows, from wh_u = A_full g (the unconstrained operator applied to the Dirichlet values)
 void lifting_from_wh(poro_ctx *c) {
   la_fill(c->stream, c->lift_u.p, 0.0, c->n_u);
@@ -672,68 +661,6 @@ int poro_ctx_get_fdm_form(poro_ctx *c, int32_t *requested, int32_t *effective, i
   });
 }
 
-// Kp = sum_c w_c K_c over the coloured cell loop (w == null: the plain Laplace matrix, bit for bit what setup() assembled: same kernel, same order)
-static void assemble_laplace_p(poro_ctx *c, const double *w) {
-  hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
-  c->Kp.zero(s);
-  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_matrices(s, a, cells, n_cells, c->Ap.rp.p, c->Ap.col.p, nullptr, c->Kp.p, nullptr, w); });
-}
-int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) {
-  return guarded([&] {
-    if (!c) throw Error("null argument");
-    PORO_HIP(hipSetDevice(c->device));
-    poro_ctx::Perm &P = c->perm;
-    auto invalidate = [&] { c->jac_dt = -1; c->ilu_J_valid = false; for (auto &L : P.line) { L.built = false; L.a = -1; } };
-    if (!k_over_mu) {
-      if (!P.kind) return 0;
-      assemble_laplace_p(c, nullptr);
-      P.kind = 0; P.host.clear(); P.layer.clear(); P.cell.release(); P.lattice.release();
-      invalidate();
-      return 0;
-    }
-    if (c->comm.part.n_ranks > 1 || c->comm.multi()) throw Error("poro_ctx_set_cell_permeability: partitioned contexts are not supported (one rank only)");
-    if (n_cells != c->n_cells) throw Error("poro_ctx_set_cell_permeability: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
-    for (int64_t i = 0; i < n_cells; ++i)
-      if (!(std::isfinite(k_over_mu[i]) && k_over_mu[i] > 0)) throw Error("poro_ctx_set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
-    std::vector<double> host(k_over_mu, k_over_mu + n_cells), lattice, layer;
-    int kind = 2;
-    if (c->lines.on) {
-      // boxes and tensor-product grids: the caller's cell order -> lattice order through every cell's first vertex (= its first pressure dof, lexicographic numbering)
-      const int dim = c->dim; const int nc[3] = {c->lines.n[0], c->lines.n[1], dim == 3 ? c->lines.n[2] : 1};
-      std::vector<int32_t> dofs((size_t)c->n_cells * c->nv);
-      PORO_HIP(hipMemcpyAsync(dofs.data(), c->cell_dofs_p.p, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      PORO_HIP(hipStreamSynchronize(c->stream));
-      lattice.assign((size_t)c->n_cells, 0.0);
-      std::vector<uint8_t> seen((size_t)c->n_cells, 0);
-      for (int64_t e = 0; e < c->n_cells; ++e) {
-        const int64_t v = dofs[(size_t)e * c->nv], np0 = nc[0] + 1, np1 = nc[1] + 1;
-        const int64_t i = v % np0, j = (v / np0) % np1, k = dim == 3 ? v / (np0 * np1) : 0;
-        if (i >= nc[0] || j >= nc[1] || k >= nc[2]) throw Error("poro_ctx_set_cell_permeability: cell " + std::to_string(e) + " does not start at a lattice cell's first vertex");
-        const int64_t at = (k * nc[1] + j) * nc[0] + i;
-        if (seen[at]) throw Error("poro_ctx_set_cell_permeability: two cells on one lattice cell");
-        seen[at] = 1; lattice[at] = host[e];
-      }
-      kind = perm_layers(dim, nc, lattice, layer) ? 1 : 2;
-    }
-    P.cell.upload(host);
-    if (c->box.enabled && c->lines.on) P.lattice.upload(lattice); else P.lattice.release();
-    assemble_laplace_p(c, P.cell.p);
-    P.host = std::move(host); P.layer = std::move(layer); P.kind = kind;
-    invalidate();
-    return 0;
-  });
-}
-int poro_ctx_get_cell_permeability(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) {
-  return guarded([&] {
-    if (!c || !kind) throw Error("null argument");
-    *kind = c->perm.kind;
-    if (out && c->perm.kind) {
-      if (n_cells != c->n_cells) throw Error("poro_ctx_get_cell_permeability: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
-      std::memcpy(out, c->perm.host.data(), (size_t)n_cells * sizeof(double));
-    }
-    return 0;
-  });
-}
 int poro_pres_apply_jacobian(poro_ctx *c, const double *x_host, double *y_host) {
   return guarded([&] {
     if (!c || !x_host || !y_host) throw Error("null argument");
@@ -747,87 +674,6 @@ int poro_pres_apply_jacobian(poro_ctx *c, const double *x_host, double *y_host) 
     } else la_csr_spmv(s, c->Ap, c->Jp.p, x.p, y.p);
     exchange_add(c, y.p, c->n_p, c->comm.part.plane_p);
     PORO_HIP(hipMemcpyAsync(y_host, y.p, c->n_p * sizeof(double), hipMemcpyDeviceToHost, s)); PORO_HIP(hipStreamSynchronize(s)); return 0;
-  });
-}
-
-// Per-cell Lame lambda and shear modulus G.  Everything the displacement system derives from the moduli is dropped here and rebuilt by the next
-// poro_disp_assemble_system: the assembled matrix, the Jacobi diagonal and its dictionary, the lifting, Ke, lambda_max of the Chebyshev form, the ILU factor, the FDM tables
-int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const double *shear_G, int64_t n_cells) {
-  return guarded([&] {
-    if (!c) throw Error("null argument");
-    PORO_HIP(hipSetDevice(c->device));
-    poro_ctx::Moduli &M = c->mod;
-    auto invalidate = [&] {
-      c->matrix_built = false; c->ilu_u_valid = false; c->cheb_lmax = 0;
-      c->diag_u_cls.release(); c->diag_u_tab.release();
-      release_fdm_u(c);
-      for (int *h : {c->pcg_hint_u, c->pcg_hint_fdm_u, c->pcg_hint_cheb_u}) h[0] = h[1] = 0;
-    };
-    if (!lame_lambda && !shear_G) {
-      if (!M.kind) return 0;
-      PORO_HIP(hipStreamSynchronize(c->stream));
-      M.kind = 0; M.host_lam.clear(); M.host_G.clear(); M.layer_lam.clear(); M.layer_G.clear(); M.cell.release(); M.node.release();
-      invalidate();
-      return 0;
-    }
-    if (!lame_lambda || !shear_G) throw Error("poro_ctx_set_cell_moduli: lame_lambda and shear_G come together (one of the two arrays is NULL)");
-    if (c->comm.part.n_ranks > 1 || c->comm.multi()) throw Error("poro_ctx_set_cell_moduli: partitioned contexts are not supported (one rank only)");
-    if (c->operator_form == PORO_OPFORM_HYBRID) throw Error("poro_ctx_set_cell_moduli: the context runs PORO_OPFORM_HYBRID, whose box part is a constant-coefficient kernel (select PORO_OPFORM_GENERAL first)");
-    if (n_cells != c->n_cells) throw Error("poro_ctx_set_cell_moduli: n_cells is " + std::to_string(n_cells) + ", the context has " + std::to_string(c->n_cells) + " cells");
-    for (int64_t i = 0; i < n_cells; ++i) {
-      const double l = lame_lambda[i], g = shear_G[i];
-      if (!(std::isfinite(l) && std::isfinite(g))) throw Error("poro_ctx_set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite");
-      if (!(g > 0)) throw Error("poro_ctx_set_cell_moduli: shear_G of cell " + std::to_string(i) + " is not > 0");
-      if (!(3 * l + 2 * g > 0)) throw Error("poro_ctx_set_cell_moduli: 3 lambda + 2 G of cell " + std::to_string(i) + " is not > 0");
-    }
-    std::vector<double> lam(lame_lambda, lame_lambda + n_cells), G(shear_G, shear_G + n_cells), layer_lam, layer_G;
-    std::vector<int32_t> dofs((size_t)c->n_cells * c->nv);
-    PORO_HIP(hipMemcpyAsync(dofs.data(), c->cell_dofs_p.p, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    PORO_HIP(hipStreamSynchronize(c->stream));
-    int kind = 2;
-    if (c->lines.on) {
-      // boxes and tensor-product grids: the caller's cell order -> lattice order through every cell's first vertex (= its first pressure dof, lexicographic numbering)
-      const int dim = c->dim; const int nc[3] = {c->lines.n[0], c->lines.n[1], dim == 3 ? c->lines.n[2] : 1};
-      std::vector<double> lat_lam((size_t)c->n_cells, 0.0), lat_G((size_t)c->n_cells, 0.0);
-      std::vector<uint8_t> seen((size_t)c->n_cells, 0);
-      for (int64_t e = 0; e < c->n_cells; ++e) {
-        const int64_t v = dofs[(size_t)e * c->nv], np0 = nc[0] + 1, np1 = nc[1] + 1;
-        const int64_t i = v % np0, j = (v / np0) % np1, k = dim == 3 ? v / (np0 * np1) : 0;
-        if (i >= nc[0] || j >= nc[1] || k >= nc[2]) throw Error("poro_ctx_set_cell_moduli: cell " + std::to_string(e) + " does not start at a lattice cell's first vertex");
-        const int64_t at = (k * nc[1] + j) * nc[0] + i;
-        if (seen[at]) throw Error("poro_ctx_set_cell_moduli: two cells on one lattice cell");
-        seen[at] = 1; lat_lam[at] = lam[e]; lat_G[at] = G[e];
-      }
-      const bool l1 = perm_layers(dim, nc, lat_lam, layer_lam), l2 = perm_layers(dim, nc, lat_G, layer_G);      // (a layered array's values are its layer means)
-      kind = l1 && l2 ? 1 : 2;
-    }
-    // nodal constants of the pressure space: the arithmetic mean over the cells that touch the dof
-    std::vector<double> node((size_t)2 * c->n_p, 0.0), pair((size_t)2 * n_cells); std::vector<int32_t> touch((size_t)c->n_p, 0);
-    for (int64_t e = 0; e < n_cells; ++e) {
-      pair[2 * e] = lam[e]; pair[2 * e + 1] = G[e];
-      for (int v = 0; v < c->nv; ++v) { const int32_t d = dofs[(size_t)e * c->nv + v]; node[2 * (size_t)d] += lam[e]; node[2 * (size_t)d + 1] += G[e]; touch[d]++; }
-    }
-    for (int64_t i = 0; i < c->n_p; ++i) {
-      if (!touch[i]) { node[2 * i] = c->mat.lame_lambda; node[2 * i + 1] = c->mat.shear_G; continue; }      // (a dof no cell of this context touches)
-      node[2 * i] /= touch[i]; node[2 * i + 1] /= touch[i];
-    }
-    PORO_HIP(hipStreamSynchronize(c->stream));
-    M.cell.upload(pair); M.node.upload(node);
-    M.host_lam = std::move(lam); M.host_G = std::move(G); M.layer_lam = std::move(layer_lam); M.layer_G = std::move(layer_G); M.kind = kind;
-    invalidate();
-    return 0;
-  });
-}
-int poro_ctx_get_cell_moduli(poro_ctx *c, double *lambda_out, double *G_out, int64_t n, int32_t *kind) {
-  return guarded([&] {
-    if (!c || !kind) throw Error("null argument");
-    *kind = c->mod.kind;
-    if ((lambda_out || G_out) && c->mod.kind) {
-      if (n != c->n_cells) throw Error("poro_ctx_get_cell_moduli: n is " + std::to_string(n) + ", the context has " + std::to_string(c->n_cells) + " cells");
-      if (lambda_out) std::memcpy(lambda_out, c->mod.host_lam.data(), (size_t)n * sizeof(double));
-      if (G_out) std::memcpy(G_out, c->mod.host_G.data(), (size_t)n * sizeof(double));
-    }
-    return 0;
   });
 }
 

@@ -58,10 +58,6 @@ void build_kelly_tables(poro_ctx *c) {
 }  // namespace poro
 
 namespace {
-template <class F> int guarded(F &&f) {
-  try { return f(); }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
 bool pressure_space_vector(poro_ctx *c, int which) {
   auto it = c->vec.find(which);
   if (it == c->vec.end()) throw Error("unknown vector id " + std::to_string(which));

@@ -1,0 +1,132 @@
+// The per-cell coefficient fields of a context: k / mu of the pressure system (poro_ctx_set / get_cell_permeability) and Lame lambda, shear G of the displacement system
+// (poro_ctx_set / get_cell_moduli).  What the two share - the refusals, the caller's cell order -> lattice order, the classification by layers, the host state - is
+// cell_field.hpp; each setter adds its value checks, its device state and what it invalidates.  A setter that throws leaves the context as it was: the device state
+// changes first, then the host state, then the caches go
+#include <cmath>
+#include <cstring>
+#include "common.hpp"
+#include "ctx_internal.hpp"
+
+using namespace poro;
+using namespace poro::ctx_detail;
+
+namespace {
+// the refusals every entry point words alike; `who` is its name, `name` its name for the count
+void refuse_partitioned(const poro_ctx *c, const std::string &who) { if (c->comm.part.n_ranks > 1 || c->comm.multi()) throw Error(who + ": partitioned contexts are not supported (one rank only)"); }
+void check_count(const poro_ctx *c, const std::string &who, const char *name, int64_t n) { if (n != c->n_cells) throw Error(who + ": " + name + " is " + std::to_string(n) + ", the context has " + std::to_string(c->n_cells) + " cells"); }
+std::vector<int32_t> download_cell_dofs_p(poro_ctx *c) {
+  std::vector<int32_t> dofs((size_t)c->n_cells * c->nv);
+  PORO_HIP(hipMemcpyAsync(dofs.data(), c->cell_dofs_p.p, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  PORO_HIP(hipStreamSynchronize(c->stream));
+  return dofs;
+}
+// F takes the arrays; on boxes and tensor-product grids (c->lines) it classifies them on the lattice - dofs: cell_dofs_p - and the lattice-ordered copies come back
+template <int N> std::array<std::vector<double>, N> take(const poro_ctx *c, CellField<N> &F, const double *const (&comp)[N], const std::vector<int32_t> &dofs, const char *who) {
+  if (!c->lines.on) return F.set(comp, c->n_cells);
+  const std::vector<int64_t> order = cell_lattice_order(c->dim, c->lines.n, dofs.data(), c->nv, c->n_cells, who);      // (lines.n is 1 beyond dim)
+  return F.set(comp, c->n_cells, &order, c->dim, c->lines.n);
+}
+// the getters: *kind always; the arrays that are asked for (out[a] != null) while a field is set
+template <class Field, int N> int give(poro_ctx *c, Field poro_ctx::*field, double *const (&out)[N], int64_t n, int32_t *kind, const std::string &who, const char *name) {
+  return guarded([&] {
+    if (!c || !kind) throw Error("null argument");
+    const CellField<N> &F = c->*field;
+    *kind = F.kind;
+    for (int a = 0; a < N && F.kind; ++a) if (out[a]) { check_count(c, who, name, n); std::memcpy(out[a], F.host[a].data(), (size_t)n * sizeof(double)); }
+    return 0;
+  });
+}
+
+// Kp = sum_c w_c K_c over the coloured cell loop (w == null: the plain Laplace matrix, bit for bit what setup() assembled: same kernel, same order)
+void assemble_laplace_p(poro_ctx *c, const double *w) {
+  hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
+  c->Kp.zero(s);
+  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_matrices(s, a, cells, n_cells, c->Ap.rp.p, c->Ap.col.p, nullptr, c->Kp.p, nullptr, w); });
+}
+}  // namespace
+
+extern "C" {
+
+int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Perm &P = c->perm;
+    auto invalidate = [&] { c->jac_dt = -1; c->ilu_J_valid = false; for (auto &L : P.line) { L.built = false; L.a = -1; } };
+    if (!k_over_mu) {
+      if (!P.kind) return 0;
+      assemble_laplace_p(c, nullptr);
+      P.clear(); P.cell.release(); P.lattice.release();
+      invalidate();
+      return 0;
+    }
+    refuse_partitioned(c, "poro_ctx_set_cell_permeability");
+    check_count(c, "poro_ctx_set_cell_permeability", "n_cells", n_cells);
+    for (int64_t i = 0; i < n_cells; ++i)
+      if (!(std::isfinite(k_over_mu[i]) && k_over_mu[i] > 0)) throw Error("poro_ctx_set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
+    CellField<1> F;
+    const auto lattice = take(c, F, {k_over_mu}, c->lines.on ? download_cell_dofs_p(c) : std::vector<int32_t>(), "poro_ctx_set_cell_permeability");
+    P.cell.upload(F.host[0]);
+    if (c->box.enabled && c->lines.on) P.lattice.upload(lattice[0]); else P.lattice.release();
+    assemble_laplace_p(c, P.cell.p);
+    static_cast<CellField<1> &>(P) = std::move(F);
+    invalidate();
+    return 0;
+  });
+}
+int poro_ctx_get_cell_permeability(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) { return give(c, &poro_ctx::perm, {out}, n_cells, kind, "poro_ctx_get_cell_permeability", "n_cells"); }
+
+// Per-cell Lame lambda and shear modulus G.  Everything the displacement system derives from the moduli is dropped here and rebuilt by the next
+// poro_disp_assemble_system: the assembled matrix, the Jacobi diagonal and its dictionary, the lifting, Ke, lambda_max of the Chebyshev form, the ILU factor, the FDM tables
+int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const double *shear_G, int64_t n_cells) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Moduli &M = c->mod;
+    auto invalidate = [&] {
+      c->matrix_built = false; c->ilu_u_valid = false; c->cheb_lmax = 0;
+      c->diag_u_cls.release(); c->diag_u_tab.release();
+      release_fdm_u(c);
+      for (int *h : {c->pcg_hint_u, c->pcg_hint_fdm_u, c->pcg_hint_cheb_u}) h[0] = h[1] = 0;
+    };
+    if (!lame_lambda && !shear_G) {
+      if (!M.kind) return 0;
+      PORO_HIP(hipStreamSynchronize(c->stream));
+      M.clear(); M.cell.release(); M.node.release();
+      invalidate();
+      return 0;
+    }
+    if (!lame_lambda || !shear_G) throw Error("poro_ctx_set_cell_moduli: lame_lambda and shear_G come together (one of the two arrays is NULL)");
+    refuse_partitioned(c, "poro_ctx_set_cell_moduli");
+    if (c->operator_form == PORO_OPFORM_HYBRID) throw Error("poro_ctx_set_cell_moduli: the context runs PORO_OPFORM_HYBRID, whose box part is a constant-coefficient kernel (select PORO_OPFORM_GENERAL first)");
+    check_count(c, "poro_ctx_set_cell_moduli", "n_cells", n_cells);
+    for (int64_t i = 0; i < n_cells; ++i) {
+      const double l = lame_lambda[i], g = shear_G[i];
+      if (!(std::isfinite(l) && std::isfinite(g))) throw Error("poro_ctx_set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite");
+      if (!(g > 0)) throw Error("poro_ctx_set_cell_moduli: shear_G of cell " + std::to_string(i) + " is not > 0");
+      if (!(3 * l + 2 * g > 0)) throw Error("poro_ctx_set_cell_moduli: 3 lambda + 2 G of cell " + std::to_string(i) + " is not > 0");
+    }
+    const std::vector<int32_t> dofs = download_cell_dofs_p(c);
+    CellField<2> F;
+    take(c, F, {lame_lambda, shear_G}, dofs, "poro_ctx_set_cell_moduli");      // (a layered array's values are its layer means)
+    // nodal constants of the pressure space: the arithmetic mean over the cells that touch the dof
+    const std::vector<double> &lam = F.host[0], &G = F.host[1];
+    std::vector<double> node((size_t)2 * c->n_p, 0.0), pair((size_t)2 * n_cells); std::vector<int32_t> touch((size_t)c->n_p, 0);
+    for (int64_t e = 0; e < n_cells; ++e) {
+      pair[2 * e] = lam[e]; pair[2 * e + 1] = G[e];
+      for (int v = 0; v < c->nv; ++v) { const int32_t d = dofs[(size_t)e * c->nv + v]; node[2 * (size_t)d] += lam[e]; node[2 * (size_t)d + 1] += G[e]; touch[d]++; }
+    }
+    for (int64_t i = 0; i < c->n_p; ++i) {
+      if (!touch[i]) { node[2 * i] = c->mat.lame_lambda; node[2 * i + 1] = c->mat.shear_G; continue; }      // (a dof no cell of this context touches)
+      node[2 * i] /= touch[i]; node[2 * i + 1] /= touch[i];
+    }
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    M.cell.upload(pair); M.node.upload(node);
+    static_cast<CellField<2> &>(M) = std::move(F);
+    invalidate();
+    return 0;
+  });
+}
+int poro_ctx_get_cell_moduli(poro_ctx *c, double *lambda_out, double *G_out, int64_t n, int32_t *kind) { return give(c, &poro_ctx::mod, {lambda_out, G_out}, n, kind, "poro_ctx_get_cell_moduli", "n"); }
+
+}  // extern "C"

@@ -13,6 +13,16 @@ namespace ctx_detail {
 
 extern thread_local std::string g_err;
 inline int ipow(int b, int e) { int r = 1; while (e--) r *= b; return r; }
+// the body of an extern "C" entry point: what it throws becomes poro_last_error() and the return value -1
+template <class F> int guarded(F &&f) {
+  try { return f(); }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// fn(cells, n_cells) once per colour of the cell colouring (one launch each: the cells of a colour share no dof)
+template <class F> void for_each_colour(poro_ctx *c, F &&fn) {
+  for (size_t k = 0; k + 1 < c->color_off.size(); ++k)
+    fn(c->color_cells.p + c->color_off[k], c->color_off[k + 1] - c->color_off[k]);
+}
 
 // ---- RCCL, resolved at run time so single-GPU use has no dependency on it (ctx_comm.hip) ----------------------------------------
 struct Rccl {

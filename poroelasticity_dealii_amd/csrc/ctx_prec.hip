@@ -211,7 +211,7 @@ void fdm_precondition_p_layered(poro_ctx *c, double a, const double *g, double *
   poro_ctx::Perm::Line &L = c->perm.line[fixed ? 1 : 0];
   if (!L.built) {
     L.lo = fixed && c->pdir_face[last][0]; L.hi = fixed && c->pdir_face[last][1];
-    L.coef.upload(perm_line_coefficients(c->lines.hcell[last], c->perm.layer, L.lo, L.hi));
+    L.coef.upload(perm_line_coefficients(c->lines.hcell[last], c->perm.layer[0], L.lo, L.hi));
     if (L.inv.n != (size_t)c->n_p) L.inv.alloc(c->n_p);
     L.a = -1; L.built = true;
   }
@@ -369,7 +369,7 @@ void build_fdm_u(poro_ctx *c) {
   if (line) {
     std::vector<double> coef;
     for (int comp = 0; comp < dim; ++comp) {
-      const std::vector<double> cc = moduli_line_coefficients(dim, ku, comp, c->lines.hcell[last], c->mod.layer_lam, c->mod.layer_G, F.fix[comp][last][0] != 0, F.fix[comp][last][1] != 0);
+      const std::vector<double> cc = moduli_line_coefficients(dim, ku, comp, c->lines.hcell[last], c->mod.layer[0], c->mod.layer[1], F.fix[comp][last][0] != 0, F.fix[comp][last][1] != 0);
       coef.insert(coef.end(), cc.begin(), cc.end());
     }
     F.line_coef.upload(coef);

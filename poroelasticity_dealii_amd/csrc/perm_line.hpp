@@ -1,9 +1,8 @@
 // Host-only: the 1D coefficient arrays of the line solve that PORO_PREC_FDM runs along the slowest direction when a per-cell k / mu is set (kernels_fdm.hip:
-// k_q1_line_solve), and the classification of a cell field on a tensor-product lattice.  No HIP, no project header: compiles into the device library and into
-// stand-alone checks alike.
+// k_q1_line_solve).  No HIP, no project header: compiles into the device library and into stand-alone checks alike.  (What is common to every per-cell field,
+// the classification by layers among it: cell_field.hpp.)
 #pragma once
 #include <cstddef>
-#include <cstdint>
 #include <vector>
 
 namespace poro {
@@ -24,23 +23,6 @@ inline std::vector<double> perm_line_coefficients(const std::vector<double> &hce
   if (fixed_lo) { md[0] = wd[0] = 0; kd[0] = 1; mo[0] = wo[0] = ko[0] = 0; }
   if (fixed_hi) { md[n] = wd[n] = 0; kd[n] = 1; if (n) mo[n - 1] = wo[n - 1] = ko[n - 1] = 0; }
   return c;
-}
-
-// A field in lattice cell order (x fastest) on nc[0] x nc[1] (x nc[2]) cells: is it constant within every layer of the slowest direction (exact equality)?  layer_mean
-// gets the arithmetic mean of every layer (the layer's value where the answer is yes)
-inline bool perm_layers(int dim, const int nc[3], const std::vector<double> &lattice, std::vector<double> &layer_mean) {
-  const int64_t per_layer = dim == 3 ? (int64_t)nc[0] * nc[1] : nc[0];
-  const int n_layers = nc[dim - 1];
-  layer_mean.assign((size_t)n_layers, 0.0);
-  bool layered = true;
-  for (int k = 0; k < n_layers; ++k) {
-    const double *v = lattice.data() + (size_t)k * per_layer;
-    double sum = 0;
-    for (int64_t i = 0; i < per_layer; ++i) { sum += v[i]; if (v[i] != v[0]) layered = false; }
-    layer_mean[k] = sum / (double)per_layer;
-  }
-  if (layered) for (int k = 0; k < n_layers; ++k) layer_mean[k] = lattice[(size_t)k * per_layer];
-  return layered;
 }
 
 }  // namespace poro

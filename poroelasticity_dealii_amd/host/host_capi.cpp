@@ -17,6 +17,16 @@ void fill_bc(BoundaryConditions &bc, int n_dir, const int32_t *dl, const int32_t
   bc.dirichlet_labels.assign(dl, dl + n_dir); bc.dirichlet_components.assign(dc, dc + n_dir); bc.dirichlet_values.assign(dv, dv + n_dir);
   bc.neumann_labels.assign(nl, nl + n_neu); bc.neumann_components.assign(nc, nc + n_neu); bc.neumann_values.assign(nv, nv + n_neu);
 }
+// f(problem behind the handle): 0, or -1 with what it threw in poro_host_last_error()
+template <class F> int on_problem(void *h, F &&f) {
+  try { f(*static_cast<ProblemData *>(h)); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// a per-cell field the problem carries: its length (0: none); copied where out != NULL
+int64_t copy_field(const std::vector<double> &f, double *out) {
+  if (out && !f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(double));
+  return (int64_t)f.size();
+}
 }  // namespace
 
 extern "C" {
@@ -210,46 +220,22 @@ int poro_host_tie_boundary(void *h, int n, const int32_t *labels, const int32_t 
 }
 // extension: per-cell k / mu of the pressure system, one value per cell of the problem's mesh (values == NULL: back to the scalar).  Kept with the problem; the drivers
 // hand it to every context they create from it (poro_ctx_set_cell_permeability), also on the meshes an adaptive run builds (a child takes its parent's value)
-int poro_host_set_cell_permeability(void *h, const double *values, int64_t n) {
-  try { static_cast<ProblemData *>(h)->set_cell_permeability(values, n); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
+int poro_host_set_cell_permeability(void *h, const double *values, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_permeability(values, n); }); }
 // the same by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre
-int poro_host_set_permeability_layers(void *h, int n, const double *top, const double *value) {
-  try { static_cast<ProblemData *>(h)->set_permeability_layers(n, top, value); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
+int poro_host_set_permeability_layers(void *h, int n, const double *top, const double *value) { return on_problem(h, [&](ProblemData &P) { P.set_permeability_layers(n, top, value); }); }
 // what refine_mesh does with the field: `h` (a refined box) takes the field of `old` (a refined box over the same coarse box), cell by coarse cell
-int poro_host_inherit_cell_permeability(void *h, void *old) {
-  try { static_cast<ProblemData *>(h)->inherit_cell_permeability(*static_cast<ProblemData *>(old)); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
+int poro_host_inherit_cell_permeability(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_permeability(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies when out != NULL
-int64_t poro_host_get_cell_permeability(void *h, double *out) {
-  const auto &f = static_cast<ProblemData *>(h)->cell_k_over_mu;
-  if (out && !f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(double));
-  return (int64_t)f.size();
-}
+int64_t poro_host_get_cell_permeability(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_k_over_mu, out); }
 // extension: per-cell Lame lambda and shear modulus G of the displacement system (both NULL: back to the scalars); kept with the problem and handed over like the permeability
-int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) {
-  try { static_cast<ProblemData *>(h)->set_cell_moduli(lam, G, n); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
+int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_moduli(lam, G, n); }); }
 // by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre; (E, nu) -> (lambda, G) as the parameter file's are
-int poro_host_set_moduli_layers(void *h, int n, const double *top, const double *young, const double *poisson) {
-  try { static_cast<ProblemData *>(h)->set_moduli_layers(n, top, young, poisson); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
-int poro_host_inherit_cell_moduli(void *h, void *old) {
-  try { static_cast<ProblemData *>(h)->inherit_cell_moduli(*static_cast<ProblemData *>(old)); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
+int poro_host_set_moduli_layers(void *h, int n, const double *top, const double *young, const double *poisson) { return on_problem(h, [&](ProblemData &P) { P.set_moduli_layers(n, top, young, poisson); }); }
+int poro_host_inherit_cell_moduli(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_moduli(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies where the pointers are not NULL
 int64_t poro_host_get_cell_moduli(void *h, double *lam_out, double *G_out) {
-  const ProblemData &P = *static_cast<ProblemData *>(h);
-  if (lam_out && !P.cell_lambda.empty()) std::memcpy(lam_out, P.cell_lambda.data(), P.cell_lambda.size() * sizeof(double));
-  if (G_out && !P.cell_G.empty()) std::memcpy(G_out, P.cell_G.data(), P.cell_G.size() * sizeof(double));
-  return (int64_t)P.cell_lambda.size();
+  const ProblemData &P = *static_cast<ProblemData *>(h); copy_field(P.cell_G, G_out);
+  return copy_field(P.cell_lambda, lam_out);
 }
 const poro_desc *poro_host_desc(void *h) { return &static_cast<ProblemData *>(h)->d; }
 void poro_host_free(void *h) { delete static_cast<ProblemData *>(h); }

@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 #include "fe_tables.hpp"
+#include "../csrc/cell_field.hpp"      // what the per-cell coefficient fields share: layers by cell centres, inheritance through coarse cells
 
 namespace poro_host {
 
@@ -437,97 +438,64 @@ struct ProblemData {
   bool refined_box = false; int box_n[3] = {1, 1, 1}; double box_size[3] = {1, 1, 1}; int box_k_u = 0;
   std::vector<uint8_t> refine_mask; std::vector<int32_t> cell_coarse, cell_child; std::vector<std::array<int, 3>> lattice_p;
   poro_desc d{};
-  // optional per-cell k / mu of the pressure system, one value per cell of `mesh` (empty: the scalar of `mat`).  Not part of poro_desc: whoever creates a context from this
-  // problem hands it over with poro_ctx_set_cell_permeability (PoroElasticProblem does, also for every mesh refine_mesh builds)
+  // The optional per-cell coefficient fields, one value per cell of `mesh` (empty: the scalars of `mat`).  Not part of poro_desc: whoever creates a context from this
+  // problem hands them over with poro_ctx_set_cell_permeability / poro_ctx_set_cell_moduli (PoroElasticProblem does, also for every mesh refine_mesh builds).  What the
+  // fields share is csrc/cell_field.hpp.  set_*_layers: layers along the slowest direction (z in 3D, y in 2D), a cell takes the first layer whose `top` is >= the
+  // coordinate of its centre there.  inherit_*: the field of a refined box `O` over the same coarse box on this refined box, every cell takes the value of its coarse
+  // cell - a child its parent's, a parent the mean of its children (which all hold the parent's value unless the caller set them apart)
+  void check_field_length(const char *who, int64_t n) const { if (n != mesh.n_cells()) throw std::runtime_error(std::string(who) + ": " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells"); }
+  std::vector<int> cell_layers(int n_layers, const double *top, const char *who) const { return poro::cell_layers_by_centre(mesh.vertices, mesh.cells, mesh.dim, n_layers, top, who); }
+  std::vector<double> inherited(const ProblemData &O, const std::vector<double> &old, const char *who) const {
+    if (old.empty()) return {};
+    if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error(std::string(who) + ": two refined boxes over the same coarse box are needed");
+    return poro::cell_field_inherit(O.cell_coarse, old, cell_coarse, refine_mask.size());
+  }
+
+  // k / mu of the pressure system
   std::vector<double> cell_k_over_mu;
   void set_cell_permeability(const double *values, int64_t n) {
     if (!values) { cell_k_over_mu.clear(); return; }
-    if (n != mesh.n_cells()) throw std::runtime_error("set_cell_permeability: " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells");
+    check_field_length("set_cell_permeability", n);
     for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
     cell_k_over_mu.assign(values, values + n);
   }
-  // layers along the slowest direction (z in 3D, y in 2D): a cell takes the value of the first layer whose `top` is >= the coordinate of its centre there
   void set_permeability_layers(int n_layers, const double *top, const double *value) {
     if (n_layers < 1 || !top || !value) throw std::runtime_error("set_permeability_layers: needs at least one TOP=VALUE layer");
-    const int dim = mesh.dim, nv = 1 << dim; const int64_t nc = mesh.n_cells();
-    std::vector<double> f((size_t)nc);
-    for (int64_t c = 0; c < nc; ++c) {
-      double z = 0;
-      for (int v = 0; v < nv; ++v) z += mesh.vertices[(size_t)mesh.cells[c * nv + v] * dim + (dim - 1)];
-      z /= nv;
-      int l = 0;
-      while (l < n_layers && !(top[l] >= z)) ++l;
-      if (l == n_layers) throw std::runtime_error("set_permeability_layers: the centre of cell " + std::to_string(c) + " (" + std::to_string(z) + ") lies above every layer top");
-      f[(size_t)c] = value[l];
-    }
-    set_cell_permeability(f.data(), nc);
+    const std::vector<int> layer = cell_layers(n_layers, top, "set_permeability_layers");
+    std::vector<double> f(layer.size());
+    for (size_t c = 0; c < layer.size(); ++c) f[c] = value[layer[c]];
+    set_cell_permeability(f.data(), (int64_t)f.size());
   }
-  // the field of a refined box `O` over the same coarse box on this refined box: every cell takes the value of its coarse cell - a child its parent's, a parent the mean of
-  // its children (which all hold the parent's value unless the caller set them apart)
-  void inherit_cell_permeability(const ProblemData &O) {
-    if (O.cell_k_over_mu.empty()) { cell_k_over_mu.clear(); return; }
-    if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error("inherit_cell_permeability: two refined boxes over the same coarse box are needed");
-    const size_t ncoarse = refine_mask.size();
-    std::vector<double> sum(ncoarse, 0.0), first(ncoarse, 0.0); std::vector<int> cnt(ncoarse, 0); std::vector<uint8_t> same(ncoarse, 1);
-    for (size_t c = 0; c < O.cell_coarse.size(); ++c) {
-      const int32_t cc = O.cell_coarse[c]; const double v = O.cell_k_over_mu[c];
-      if (!cnt[cc]) first[cc] = v; else if (v != first[cc]) same[cc] = 0;
-      sum[cc] += v; cnt[cc]++;
-    }
-    cell_k_over_mu.resize(cell_coarse.size());
-    // (one cell, or 2^dim equal values: the value itself, exactly; the mean is formed only where the children differ)
-    for (size_t c = 0; c < cell_coarse.size(); ++c) { const int32_t cc = cell_coarse[c]; cell_k_over_mu[c] = same[cc] ? first[cc] : sum[cc] / cnt[cc]; }
-  }
+  void inherit_cell_permeability(const ProblemData &O) { cell_k_over_mu = inherited(O, O.cell_k_over_mu, "inherit_cell_permeability"); }
 
-  // optional per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell of `mesh` (empty: the scalars of `mat`).  Handed over like the
-  // permeability above, with poro_ctx_set_cell_moduli
+  // Lame lambda and shear modulus G of the displacement system (the two come together)
   std::vector<double> cell_lambda, cell_G;
   void set_cell_moduli(const double *lam, const double *G, int64_t n) {
     if (!lam && !G) { cell_lambda.clear(); cell_G.clear(); return; }
     if (!lam || !G) throw std::runtime_error("set_cell_moduli: lambda and G come together");
-    if (n != mesh.n_cells()) throw std::runtime_error("set_cell_moduli: " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells");
+    check_field_length("set_cell_moduli", n);
     for (int64_t i = 0; i < n; ++i)
       if (!(std::isfinite(lam[i]) && std::isfinite(G[i]) && G[i] > 0 && 3 * lam[i] + 2 * G[i] > 0))
         throw std::runtime_error("set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite with G > 0 and 3 lambda + 2 G > 0");
     cell_lambda.assign(lam, lam + n); cell_G.assign(G, G + n);
   }
-  // layers along the slowest direction by Young's modulus and Poisson's ratio: a cell takes the first layer whose `top` is >= the coordinate of its centre there; lambda and G
-  // by the formulas of InputDataPoroel::compute_derived_parameters
+  // by Young's modulus and Poisson's ratio; lambda and G by the formulas of InputDataPoroel::compute_derived_parameters
   void set_moduli_layers(int n_layers, const double *top, const double *young, const double *poisson) {
     if (n_layers < 1 || !top || !young || !poisson) throw std::runtime_error("set_moduli_layers: needs at least one TOP=YOUNG:POISSON layer");
     for (int l = 0; l < n_layers; ++l)
       if (!(std::isfinite(young[l]) && young[l] > 0 && poisson[l] > -1.0 && poisson[l] < 0.5))
         throw std::runtime_error("set_moduli_layers: layer " + std::to_string(l) + " needs a Young's modulus > 0 and a Poisson ratio in (-1, 0.5)");
-    const int dim = mesh.dim, nv = 1 << dim; const int64_t nc = mesh.n_cells();
-    std::vector<double> lam((size_t)nc), G((size_t)nc);
-    for (int64_t c = 0; c < nc; ++c) {
-      double z = 0;
-      for (int v = 0; v < nv; ++v) z += mesh.vertices[(size_t)mesh.cells[c * nv + v] * dim + (dim - 1)];
-      z /= nv;
-      int l = 0;
-      while (l < n_layers && !(top[l] >= z)) ++l;
-      if (l == n_layers) throw std::runtime_error("set_moduli_layers: the centre of cell " + std::to_string(c) + " (" + std::to_string(z) + ") lies above every layer top");
-      const double E = young[l], nu = poisson[l];
-      lam[(size_t)c] = E * nu / ((1. + nu) * (1. - 2. * nu)); G[(size_t)c] = 0.5 * E / (1 + nu);
+    const std::vector<int> layer = cell_layers(n_layers, top, "set_moduli_layers");
+    std::vector<double> lam(layer.size()), G(layer.size());
+    for (size_t c = 0; c < layer.size(); ++c) {
+      const double E = young[layer[c]], nu = poisson[layer[c]];
+      lam[c] = E * nu / ((1. + nu) * (1. - 2. * nu)); G[c] = 0.5 * E / (1 + nu);
     }
-    set_cell_moduli(lam.data(), G.data(), nc);
+    set_cell_moduli(lam.data(), G.data(), (int64_t)lam.size());
   }
-  // as inherit_cell_permeability: a child takes its parent's pair, a coarsened parent the mean of its children
   void inherit_cell_moduli(const ProblemData &O) {
-    if (O.cell_lambda.empty()) { cell_lambda.clear(); cell_G.clear(); return; }
-    if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error("inherit_cell_moduli: two refined boxes over the same coarse box are needed");
-    const size_t ncoarse = refine_mask.size();
-    const std::vector<double> *src[2] = {&O.cell_lambda, &O.cell_G}; std::vector<double> *dst[2] = {&cell_lambda, &cell_G};
-    for (int a = 0; a < 2; ++a) {
-      std::vector<double> sum(ncoarse, 0.0), first(ncoarse, 0.0); std::vector<int> cnt(ncoarse, 0); std::vector<uint8_t> same(ncoarse, 1);
-      for (size_t c = 0; c < O.cell_coarse.size(); ++c) {
-        const int32_t cc = O.cell_coarse[c]; const double v = (*src[a])[c];
-        if (!cnt[cc]) first[cc] = v; else if (v != first[cc]) same[cc] = 0;
-        sum[cc] += v; cnt[cc]++;
-      }
-      dst[a]->resize(cell_coarse.size());
-      for (size_t c = 0; c < cell_coarse.size(); ++c) { const int32_t cc = cell_coarse[c]; (*dst[a])[c] = same[cc] ? first[cc] : sum[cc] / cnt[cc]; }
-    }
+    std::vector<double> lam = inherited(O, O.cell_lambda, "inherit_cell_moduli");
+    cell_G = inherited(O, O.cell_G, "inherit_cell_moduli"); cell_lambda = std::move(lam);
   }
 
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are

@@ -435,16 +435,10 @@ template <int dim> class PoroElasticProblem {
   static poro_ctx *make_ctx(ProblemData &P, int device, int operator_mode) {
     poro_ctx *c = nullptr;
     check(poro_ctx_create(&P.d, device, operator_mode, &c), "poro_ctx_create");
-    // a per-cell k / mu of the problem goes to the context before anything is assembled from it
-    if (!P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0) {
-      const std::string why = poro_last_error(); poro_ctx_destroy(c);
-      throw std::runtime_error("ctx_set_cell_permeability: " + why);
-    }
-    // likewise per-cell moduli
-    if (!P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0) {
-      const std::string why = poro_last_error(); poro_ctx_destroy(c);
-      throw std::runtime_error("ctx_set_cell_moduli: " + why);
-    }
+    // the per-cell fields of the problem go to the context before anything is assembled from it
+    const char *failed = !P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0 ? "ctx_set_cell_permeability: "
+                         : !P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0 ? "ctx_set_cell_moduli: " : nullptr;
+    if (failed) { const std::string why = poro_last_error(); poro_ctx_destroy(c); throw std::runtime_error(failed + why); }
     return c;
   }
 };

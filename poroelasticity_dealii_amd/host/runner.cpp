@@ -13,10 +13,12 @@
 // --fastest takes the fast diagonalisation (line-solve form) on boxes and Chebyshev elsewhere; the run prints the field's kind and the choice, also after every adapt.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <iostream>
 #include <string>
 #include "input_data.hpp"
@@ -28,6 +30,23 @@ using namespace poro_host;
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
                                   "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
+
+// TOP=V[:V...][,TOP=V[:V...]...], one array of `fields` per number of an item (the tops first): appends every item.  False unless every item has that shape, every number
+// is read whole and the tops ascend (from the last one the array holds already)
+static bool parse_layers(const std::string &arg, std::initializer_list<std::vector<double> *> fields) {
+  for (size_t at = 0, comma; at <= arg.size(); at = comma + 1) {
+    comma = std::min(arg.find(',', at), arg.size());
+    std::string rest = arg.substr(at, comma - at); size_t k = 0;
+    for (std::vector<double> *out : fields) {
+      const size_t end = ++k == fields.size() ? rest.size() : rest.find(k == 1 ? '=' : ':');      // (the last number takes what is left)
+      const std::string text = rest.substr(0, end); char *stop = nullptr; const double v = std::strtod(text.c_str(), &stop);
+      if (end == std::string::npos || text.empty() || *stop || (k == 1 && !out->empty() && !(v > out->back()))) return false;
+      out->push_back(v); rest.erase(0, end + 1);
+    }
+  }
+  return true;
+}
+static bool positive(double v) { return v > 0 && std::isfinite(v); }
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl << kUsage << std::endl; return 1; }   // parse_command_line.h:9-13 (the usage line is this driver's)
@@ -64,30 +83,16 @@ int main(int argc, char **argv) {
       pressure_labels.push_back((int32_t)label); pressure_values.push_back(value);
     }
     else if (!std::strcmp(argv[i], "--permeability-layers") && i + 1 < argc) {   // k / mu by layers of the slowest direction, bottom to top
-      const std::string arg = argv[++i]; size_t at = 0;
-      while (at <= arg.size()) {
-        const size_t comma = std::min(arg.find(',', at), arg.size()); const std::string item = arg.substr(at, comma - at); const size_t eq = item.find('=');
-        char *e1 = nullptr, *e2 = nullptr;
-        const double top = std::strtod(item.c_str(), &e1), value = eq == std::string::npos ? 0.0 : std::strtod(item.c_str() + eq + 1, &e2);
-        if (eq == std::string::npos || eq == 0 || e1 != item.c_str() + eq || !e2 || e2 == item.c_str() + eq + 1 || *e2 || !(value > 0) || !std::isfinite(value) || (!layer_top.empty() && !(top > layer_top.back()))) {
-          std::cerr << "--permeability-layers needs TOP=VALUE[,TOP=VALUE...] with ascending tops and positive values, got " << arg << std::endl; return 1;
-        }
-        layer_top.push_back(top); layer_value.push_back(value);
-        at = comma + 1;
+      const char *arg = argv[++i];
+      if (!parse_layers(arg, {&layer_top, &layer_value}) || !std::all_of(layer_value.begin(), layer_value.end(), positive)) {
+        std::cerr << "--permeability-layers needs TOP=VALUE[,TOP=VALUE...] with ascending tops and positive values, got " << arg << std::endl; return 1;
       }
     }
     else if (!std::strcmp(argv[i], "--moduli-layers") && i + 1 < argc) {   // Young's modulus and Poisson's ratio by layers of the slowest direction, bottom to top
-      const std::string arg = argv[++i]; size_t at = 0;
-      while (at <= arg.size()) {
-        const size_t comma = std::min(arg.find(',', at), arg.size()); const std::string item = arg.substr(at, comma - at); const size_t eq = item.find('='), colon = item.find(':');
-        char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
-        const bool shaped = eq != std::string::npos && eq != 0 && colon != std::string::npos && colon > eq + 1 && colon + 1 < item.size();
-        const double top = std::strtod(item.c_str(), &e1), young = shaped ? std::strtod(item.c_str() + eq + 1, &e2) : 0.0, poisson = shaped ? std::strtod(item.c_str() + colon + 1, &e3) : 0.0;
-        if (!shaped || e1 != item.c_str() + eq || e2 != item.c_str() + colon || !e3 || *e3 || !(young > 0) || !std::isfinite(young) || !(poisson > -1.0 && poisson < 0.5) || (!moduli_top.empty() && !(top > moduli_top.back()))) {
-          std::cerr << "--moduli-layers needs TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] with ascending tops, YOUNG > 0 and POISSON in (-1, 0.5), got " << arg << std::endl; return 1;
-        }
-        moduli_top.push_back(top); moduli_young.push_back(young); moduli_poisson.push_back(poisson);
-        at = comma + 1;
+      const char *arg = argv[++i];
+      if (!parse_layers(arg, {&moduli_top, &moduli_young, &moduli_poisson}) || !std::all_of(moduli_young.begin(), moduli_young.end(), positive) ||
+          !std::all_of(moduli_poisson.begin(), moduli_poisson.end(), [](double v) { return v > -1.0 && v < 0.5; })) {
+        std::cerr << "--moduli-layers needs TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] with ascending tops, YOUNG > 0 and POISSON in (-1, 0.5), got " << arg << std::endl; return 1;
       }
     }
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev

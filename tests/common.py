@@ -1,6 +1,7 @@
 """Shared problem definitions of the test-suite: the bundled input.data values (reference input.data:1-41),
 committed here as numbers because /root/reference does not exist on the GPU box."""
 import os
+import subprocess
 
 import numpy as np
 
@@ -58,3 +59,40 @@ def global_problem(mesh, deg):
     if mesh.startswith("refined:"):
         return pk.Problem.refined_box(len(n), n, [10.0] * len(n), deg, material(), BC_2D if len(n) == 2 else BC_3D, [m // 4 for m in n], [max(3 * m // 4, m // 4 + 1) for m in n])
     return box_problem(len(n), n, deg)
+
+
+# ---- per-cell coefficient fields (test_permeability_cpu.py, test_moduli_cpu.py) ----------------------------------------------------------------------------------
+ROLLERS3 = [(0, 0, 0.0), (2, 1, 0.0), (4, 2, 0.0)]
+
+
+def centres(P):
+    d = P.desc; nv = 1 << d.dim
+    X = P.array("vertex_coords", (d.n_vertices, d.dim)); cv = P.array("cell_vertices", (d.n_cells, nv), np.int32)
+    return X[cv].mean(axis=1)
+
+
+def layered_field_problems():
+    """a graded box of 3 x 2 x 5 cells and a refined box of 3 x 2 x 4 cells with three refined ones: the meshes the layers by cell centres are checked on"""
+    mask = np.zeros(3 * 2 * 4, dtype=np.int32); mask[[1, 8, 23]] = 1
+    return (pk.Problem.graded_box(3, [3, 2, 5], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, [0.6, 0.0, 0.9]),
+            pk.Problem.refined_box_mask(3, [3, 2, 4], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask))
+
+
+def refine_and_coarsen_pair():
+    """(A, B, nc): two refined boxes over the same 3 x 2 x 4 = nc coarse cells; from A to B cell 1 is coarsened, 8 stays refined, 23 is refined"""
+    n = [3, 2, 4]; nc = int(np.prod(n))
+
+    def build(mask):
+        return pk.Problem.refined_box_mask(3, n, [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask)
+    m1 = np.zeros(nc, dtype=np.int32); m1[[1, 8]] = 1
+    m2 = np.zeros(nc, dtype=np.int32); m2[[8, 23]] = 1
+    return build(m1), build(m2), nc
+
+
+def build_sanitized_check(tmp_path, name):
+    """tests/<name>.cpp, a stand-alone program over a host-only header of csrc/, built with the address and undefined-behaviour sanitizers; returns the executable"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / name)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(root, "poroelasticity_dealii_amd", "csrc"),
+                           os.path.join(root, "tests", name + ".cpp"), "-o", exe])
+    return exe

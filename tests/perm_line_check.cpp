@@ -12,9 +12,5 @@ int main(int argc, char **argv) {
   for (int i = 0; i < n; ++i) { h[i] = std::strtod(argv[3 + i], nullptr); k[i] = std::strtod(argv[3 + n + i], nullptr); }
   const std::vector<double> c = poro::perm_line_coefficients(h, k, std::atoi(argv[1]) != 0, std::atoi(argv[2]) != 0);
   for (int r = 0; r < 6; ++r) { for (int i = 0; i <= n; ++i) std::printf("%.17g ", c[(size_t)r * (n + 1) + i]); std::printf("\n"); }
-  // the classification: a layered and a non-layered field on 2 x 1 x 2 cells
-  const int nc[3] = {2, 1, 2}; std::vector<double> mean;
-  if (!poro::perm_layers(3, nc, {1.0, 1.0, 3.0, 3.0}, mean) || mean[0] != 1.0 || mean[1] != 3.0) return 3;
-  if (poro::perm_layers(3, nc, {1.0, 2.0, 3.0, 3.0}, mean) || mean[0] != 1.5 || mean[1] != 3.0) return 4;
   return 0;
 }

@@ -10,7 +10,7 @@ import pytest
 import scipy.sparse.linalg as spl
 
 import poroelasticity_dealii_amd as pk
-from common import material
+from common import build_sanitized_check, centres, layered_field_problems, material, refine_and_coarsen_pair
 from moduli_reference import FDM_CASES, ModuliReference, fdm_problem, fe1d_weighted, layer_decades, layered_block_inverse, per_cell
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,9 +26,7 @@ def test_symbols_and_abi():
 
 def test_line_mathematics_under_the_sanitizers(tmp_path):
     """moduli_line.hpp through tests/moduli_line_check.cpp: band arrays against dense numpy matrices, the banded L D L^T solve against numpy.linalg.solve, removed modes"""
-    exe = str(tmp_path / "moduli_line_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "poroelasticity_dealii_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "moduli_line_check.cpp"), "-o", exe])
+    exe = build_sanitized_check(tmp_path, "moduli_line_check")
     rng = np.random.default_rng(23)
     for dim, k, comp, n, lo, hi, l0, l1 in ((3, 1, 2, 1, 0, 0, 0.7, 2.0), (3, 2, 0, 1, 1, 0, 3.0, 0.0), (3, 2, 2, 6, 1, 1, 1.5, 40.0), (3, 1, 1, 7, 0, 1, 0.0, 9.0), (2, 2, 1, 4, 1, 0, 5.0, 0.0),
                                             (2, 1, 0, 5, 0, 0, 0.3, 0.0), (3, 2, 1, 3, 1, 0, np.inf, 1.0), (3, 1, 0, 4, 0, 1, 2.0, np.inf)):
@@ -85,20 +83,9 @@ def test_numpy_model_of_the_layered_block_inverse(name):
 
 
 # ---- host layer ---------------------------------------------------------------------------------------------------------------------------------------------------
-ROLLERS3 = [(0, 0, 0.0), (2, 1, 0.0), (4, 2, 0.0)]
-
-
-def centres(P):
-    d = P.desc; nv = 1 << d.dim
-    X = P.array("vertex_coords", (d.n_vertices, d.dim)); cv = P.array("cell_vertices", (d.n_cells, nv), np.int32)
-    return X[cv].mean(axis=1)
-
-
 def test_moduli_layers_by_cell_centres_and_validation():
     layers = [(-1.0, 1.4e10, 0.3), (0.5, 2e7, 0.45), (2.0, 3e12, 0.0)]
-    mask = np.zeros(3 * 2 * 4, dtype=np.int32); mask[[1, 8, 23]] = 1
-    for P in (pk.Problem.graded_box(3, [3, 2, 5], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, [0.6, 0.0, 0.9]),
-              pk.Problem.refined_box_mask(3, [3, 2, 4], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask)):
+    for P in layered_field_problems():
         try:
             assert P.cell_moduli() is None
             P.set_moduli_layers(layers)
@@ -130,13 +117,7 @@ def test_moduli_layers_by_cell_centres_and_validation():
 
 
 def test_moduli_inheritance_through_a_refine_and_a_coarsen():
-    n = [3, 2, 4]; nc = int(np.prod(n))
-
-    def build(mask):
-        return pk.Problem.refined_box_mask(3, n, [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask)
-    m1 = np.zeros(nc, dtype=np.int32); m1[[1, 8]] = 1
-    m2 = np.zeros(nc, dtype=np.int32); m2[[8, 23]] = 1                       # cell 1 is coarsened, 8 stays refined, 23 is refined
-    A, B = build(m1), build(m2)
+    A, B, nc = refine_and_coarsen_pair()
     try:
         ca, _ = A.cell_parents(); cb, _ = B.cell_parents()
         rng = np.random.default_rng(5)

@@ -9,16 +9,9 @@ import numpy as np
 import pytest
 
 import poroelasticity_dealii_amd as pk
-from common import material
+from common import build_sanitized_check, centres, layered_field_problems, material, refine_and_coarsen_pair
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ROLLERS3 = [(0, 0, 0.0), (2, 1, 0.0), (4, 2, 0.0)]
-
-
-def centres(P):
-    d = P.desc; nv = 1 << d.dim
-    X = P.array("vertex_coords", (d.n_vertices, d.dim)); cv = P.array("cell_vertices", (d.n_cells, nv), np.int32)
-    return X[cv].mean(axis=1)
 
 
 def expected_layers(P, layers):
@@ -29,9 +22,7 @@ def expected_layers(P, layers):
 
 def test_layers_by_cell_centres_on_graded_and_refined_boxes():
     layers = [(-1.0, 3.0), (0.5, 1e-3), (2.0, 7.0)]
-    mask = np.zeros(3 * 2 * 4, dtype=np.int32); mask[[1, 8, 23]] = 1
-    for P in (pk.Problem.graded_box(3, [3, 2, 5], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, [0.6, 0.0, 0.9]),
-              pk.Problem.refined_box_mask(3, [3, 2, 4], [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask)):
+    for P in layered_field_problems():
         try:
             assert P.cell_permeability() is None
             P.set_permeability_layers(layers)
@@ -51,12 +42,7 @@ def test_layers_by_cell_centres_on_graded_and_refined_boxes():
 
 
 def test_inheritance_through_cell_parents():
-    n = [3, 2, 4]; nc = int(np.prod(n))
-    def build(mask):
-        return pk.Problem.refined_box_mask(3, n, [3.0, 2.0, 4.0], 1, material(), ROLLERS3, mask)
-    m1 = np.zeros(nc, dtype=np.int32); m1[[1, 8]] = 1
-    m2 = np.zeros(nc, dtype=np.int32); m2[[8, 23]] = 1                       # cell 1 is coarsened, 8 stays refined, 23 is refined
-    A, B = build(m1), build(m2)
+    A, B, nc = refine_and_coarsen_pair()
     try:
         ca, _ = A.cell_parents(); cb, _ = B.cell_parents()
         per_coarse = 1.0 + np.random.default_rng(3).random(nc)
@@ -88,9 +74,7 @@ def test_symbols_and_abi():
 
 def test_line_coefficients_against_numpy(tmp_path):
     """perm_line.hpp through tests/perm_line_check.cpp (host-only, built here with the address and undefined-behaviour sanitizers and run directly)"""
-    exe = str(tmp_path / "perm_line_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "poroelasticity_dealii_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "perm_line_check.cpp"), "-o", exe])
+    exe = build_sanitized_check(tmp_path, "perm_line_check")
     rng = np.random.default_rng(17)
     for n, lo, hi in ((1, 0, 0), (1, 1, 0), (3, 0, 1), (6, 1, 1), (7, 0, 0)):
         h = 0.5 + rng.random(n); k = 10.0 ** rng.uniform(-3, 1, n)
