@@ -525,6 +525,21 @@ int  poro_pres_apply_jacobian(poro_ctx *ctx, const double *x_host, double *y_hos
 int  poro_ctx_set_cell_moduli(poro_ctx *ctx, const double *lame_lambda, const double *shear_G /* both NULL: back to the scalars */, int64_t n_cells);
 int  poro_ctx_get_cell_moduli(poro_ctx *ctx, double *lambda_out, double *G_out /* may be NULL */, int64_t n, int32_t *kind);
 
+/* Anisotropic permeability: a per-cell DIAGONAL tensor kappa_c = diag(kx, ky[, kz]) / mu whose principal axes are the global coordinate axes (appended entry points, no
+ * struct changes: PORO_ABI_VERSION stays 4).  K_kappa = sum_c int_c grad(phi_i) . kappa_c grad(phi_j) takes the place of kappa K wherever poro_ctx_set_cell_permeability
+ * puts its scalar field: the residual, the Jacobian, poro_pres_apply_jacobian, poro_pres_solve, the exports (PORO_MAT_LAPLACE_P = K_kappa, PORO_MAT_JACOBIAN_P =
+ * M / (M_b dt) + K_kappa).  k_over_mu[n_cells][dim], x first, cells in the descriptor's order.
+ * A context holds the scalar field OR the tensor: setting one drops the other, NULL to either setter returns to poro_material.k_over_mu (bitwise, as above).  While a tensor
+ * is set poro_ctx_get_cell_permeability reports the tensor's kind and refuses a non-NULL out.  Refusals and invalidations as for the scalar field: ONE RANK ONLY, a wrong
+ * n_cells, a component that is not finite and > 0 (the message names the cell and the component); a refused call leaves the context as it was.
+ * kind = 0 no tensor; 1 EVERY component constant (exact equality) within every cell layer of the slowest direction of a uniform box or tensor-product grid; 2 anything else.
+ * PORO_PREC_FDM stays exact for kind 1: in the eigenbasis of the leading directions one SPD tridiagonal system per mode is left,
+ * (a Mz + lam_x Mz^kx + lam_y Mz^ky + Kz^kz) t = r  (2D: (a My + lam_x My^kx + Ky^ky) t = r) - a direct solve on matrix-free boxes (info.iterations = 0), the
+ * preconditioner of CG on tensor grids and CSR contexts; kind 2: the same form with per-component arithmetic layer means, never claimed exact.  PORO_PREC_TWO_LEVEL is
+ * refused for the pressure system; the other preconditioners as without a field. */
+int  poro_ctx_set_cell_permeability_tensor(poro_ctx *ctx, const double *k_over_mu /* [n_cells][dim], x first; NULL: back to the scalar */, int64_t n_cells);
+int  poro_ctx_get_cell_permeability_tensor(poro_ctx *ctx, double *out /* [n_cells][dim], may be NULL */, int64_t n_cells, int32_t *kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,7 @@ HIP_SYMBOLS = [
     "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get",
     "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form",
     "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian",
+    "poro_ctx_set_cell_permeability_tensor", "poro_ctx_get_cell_permeability_tensor",
     "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli"]
 
 _hip = None
@@ -178,6 +179,8 @@ def load_hip():
         L.poro_timers_get.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
         L.poro_ctx_set_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64]
         L.poro_ctx_get_cell_permeability.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
+        L.poro_ctx_set_cell_permeability_tensor.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_ctx_get_cell_permeability_tensor.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
         L.poro_pres_apply_jacobian.argtypes = [C.c_void_p, _dp, _dp]
         L.poro_ctx_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
         L.poro_ctx_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _ip]
@@ -226,6 +229,11 @@ def load_host():
         L.poro_host_inherit_cell_permeability.argtypes = [C.c_void_p, C.c_void_p]
         L.poro_host_get_cell_permeability.restype = C.c_int64
         L.poro_host_get_cell_permeability.argtypes = [C.c_void_p, _dp]
+        L.poro_host_set_cell_permeability_tensor.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_host_set_permeability_tensor_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+        L.poro_host_inherit_cell_permeability_tensor.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_host_get_cell_permeability_tensor.restype = C.c_int64
+        L.poro_host_get_cell_permeability_tensor.argtypes = [C.c_void_p, _dp]
         L.poro_host_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
         L.poro_host_set_moduli_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
         L.poro_host_inherit_cell_moduli.argtypes = [C.c_void_p, C.c_void_p]
@@ -282,6 +290,16 @@ def _field_args(*arrays):
     if len({a.size for a, _ in flat}) != 1:
         raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
     return flat, [p for _, p in flat] + [flat[0][0].size]
+
+
+def _tensor_args(values, dim):
+    """the arguments of a tensor setter behind its handle: values of shape (n_cells, dim), x first -> (the array to keep alive, [pointer, n_cells]); None: back to the scalar"""
+    if values is None:
+        return None, [None, 0]
+    a, p = _arr_d(np.asarray(values, dtype=np.float64).reshape(-1))
+    if a.size % dim:
+        raise ValueError(f"set_cell_permeability_tensor: values of shape (n_cells, {dim}) are needed")
+    return a, [p, a.size // dim]
 
 
 def read_input(path=None):
@@ -487,6 +505,29 @@ class Problem:
         f = self._carried("cell_permeability", 1)
         return f and f[0]
 
+    def set_cell_permeability_tensor(self, values):
+        """extension: the per-cell diagonal tensor diag(kx, ky[, kz]) / mu of the pressure system, shape (n_cells, dim), x first (None: none).  Kept with the problem and
+        handed over like the scalar field, which it replaces (a problem carries one of the two); an adaptive run carries it to every new mesh, component by component"""
+        keep, args = _tensor_args(values, self.desc.dim)
+        return self._host("set_cell_permeability_tensor", *args)
+
+    def set_permeability_tensor_layers(self, layers):
+        """the same by layers [(top, kx, ky[, kz]), ...] along the slowest direction, tops ascending, chosen by cell centres as set_permeability_layers does"""
+        dim = self.desc.dim
+        if any(len(l) != dim + 1 for l in layers):
+            raise ValueError(f"set_permeability_tensor_layers: every layer is (top, {', '.join(['kx', 'ky', 'kz'][:dim])})")
+        cols = [_arr_d([l[i] for l in layers]) for i in range(dim + 1)]
+        return self._host("set_permeability_tensor_layers", len(layers), *[p for _, p in cols], *[None] * (3 - dim))
+
+    def inherit_cell_permeability_tensor(self, old):
+        """what an adaptive run does with the tensor: a child takes its parent's components exactly, a coarsened parent the per-component mean"""
+        return self._host("inherit_cell_permeability_tensor", old.handle)
+
+    def cell_permeability_tensor(self):
+        """the per-cell tensor this problem carries, shape (n_cells, dim), or None"""
+        f = self._carried("cell_permeability_tensor", 1)
+        return f and f[0].reshape(-1, self.desc.dim)
+
     def set_cell_moduli(self, lame_lambda, shear_G):
         """extension: per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell of this mesh (both None: back to the scalars of the material).
         Kept with the problem like the permeability: Context, run_problem and Runner hand it to the contexts they create, an adaptive run carries it to every new mesh"""
@@ -531,7 +572,7 @@ class Context:
             self._chk(self.L.poro_ctx_create(problem.desc_ptr, device, operator_mode, C.byref(p)))
             ptr = p
             # the per-cell fields the problem carries (Problem.set_cell_permeability / set_permeability_layers, set_cell_moduli / set_moduli_layers)
-            for name, hand_over in (("cell_permeability", self.set_cell_permeability), ("cell_moduli", self.set_cell_moduli)):
+            for name, hand_over in (("cell_permeability", self.set_cell_permeability), ("cell_permeability_tensor", self.set_cell_permeability_tensor), ("cell_moduli", self.set_cell_moduli)):
                 carried = getattr(problem, name, None)                 # (a Problem; descriptor holders of other kinds carry no field)
                 field = carried() if carried else None
                 if field is not None:
@@ -623,6 +664,24 @@ class Context:
     def get_cell_permeability(self):
         """(values or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid (PREC_FDM is exact), 2 general"""
         return self._get_field(self.L.poro_ctx_get_cell_permeability, 1)
+
+    def set_cell_permeability_tensor(self, values):
+        """per-cell diagonal tensor diag(kx, ky[, kz]) / mu of the pressure system, shape (n_cells, dim), x first, cells in the descriptor's order (None: back to the scalar
+        of the material).  Replaces a scalar field (a context holds one of the two).  One rank; invalidates like set_cell_permeability: call pres_assemble_jacobian
+        again.  Raises on a wrong length and on a component that is not finite and > 0"""
+        keep, args = _tensor_args(values, self.dim)
+        self._chk(self.L.poro_ctx_set_cell_permeability_tensor(self.ptr, *args))
+
+    def get_cell_permeability_tensor(self):
+        """(values of shape (n_cells, dim) or None, kind): kind 0 no tensor, 1 every component layered along the slowest direction of a box / tensor-product grid
+        (PREC_FDM is exact), 2 general"""
+        kind = C.c_int32()
+        self._chk(self.L.poro_ctx_get_cell_permeability_tensor(self.ptr, None, 0, C.byref(kind)))
+        if not kind.value:
+            return None, 0
+        out = np.empty((self.problem.desc.n_cells, self.dim))
+        self._chk(self.L.poro_ctx_get_cell_permeability_tensor(self.ptr, out.ctypes.data_as(_dp), out.shape[0], C.byref(kind)))
+        return out, kind.value
 
     def set_cell_moduli(self, lame_lambda, shear_G):
         """per-cell Lame lambda and shear modulus G of the displacement system, one pair per cell in the descriptor's cell order (both None: back to the scalars of the
@@ -823,16 +882,19 @@ _FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit f
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None):
+                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None, permeability_tensor=None):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
     Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
     hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it).
     fdm_per_direction=True: FDM_FORM_PER_DIRECTION for the block FDM of the displacement system (Context.set_fdm_form; carried over to every adapted mesh).
-    permeability: per-cell k / mu (Problem.set_cell_permeability on `problem`, which keeps it), carried over to every adapted mesh."""
+    permeability: per-cell k / mu (Problem.set_cell_permeability on `problem`, which keeps it), carried over to every adapted mesh.
+    permeability_tensor: per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim) (Problem.set_cell_permeability_tensor), likewise."""
     H = load_host()
     if permeability is not None:
         problem.set_cell_permeability(permeability)
+    if permeability_tensor is not None:
+        problem.set_cell_permeability_tensor(permeability_tensor)
     max_rows = 1 + n_steps * max_fss
     trace = np.zeros((max_rows, 8))
     ctx = C.c_void_p()
@@ -858,8 +920,10 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None):
         self.H = load_host()
+        if permeability_tensor is not None:      # per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim): Problem.set_cell_permeability_tensor, kept and carried like the scalar field
+            problem.set_cell_permeability_tensor(permeability_tensor)
         if permeability is not None:             # per-cell k / mu: Problem.set_cell_permeability on `problem`, which keeps it; adapt() carries it to every new mesh
             problem.set_cell_permeability(permeability)
         self.max_fss = max_fss

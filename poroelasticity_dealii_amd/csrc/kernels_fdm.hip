@@ -214,8 +214,84 @@ k_q1_line_solve(LineCols L, int nl, double a, int fixed_lo, int fixed_hi, const 
   }
 }
 
+// ---- layered diagonal tensor (poro_ctx_set_cell_permeability_tensor): J = a Mx(x)My(x)Mz + Kx(x)My(x)Mz^kx + Mx(x)Ky(x)Mz^ky + Mx(x)My(x)Kz^kz -----------------------------
+// The one sigma = lam_x + lam_y above becomes one multiplier per leading direction, each on its own weighted mass line:  (a Mz + lam_x[p] Mz^kx + lam_y[q] Mz^ky + Kz^kz) t = r
+// (2D: (a My + lam_x[p] My^kx + Ky^ky) t = r).  coef = [md | mo | w0d | w0o | (w1d | w1o) | kd | ko] (perm_tensor_line_coefficients).  Everything else is k_q1_line_factor /
+// k_q1_line_solve: one lane per column, cached reciprocal pivots, no division in the sweeps, identity rows on prescribed ends, exact zeros for removed modes
+template <int DIM> __device__ __forceinline__ bool line_sigma2(const LineCols &L, int64_t col, double &s0, double &s1) {
+  const int i = (int)(col % L.n0); const int64_t j = col / L.n0;
+  double l1 = 0.0;
+  if constexpr (DIM == 3) l1 = L.lam1[j];
+  const double l0 = L.lam0[i];
+  const bool removed = !(l0 < 1e300) || !(l1 < 1e300);
+  s0 = removed ? 0.0 : l0; s1 = removed ? 0.0 : l1;
+  return removed;
+}
+// entry k of the line matrix's diagonal (arr = 0) or off-diagonal (arr = 1)
+template <int DIM> __device__ __forceinline__ double line_entry_tensor(const double *__restrict__ coef, int nl, int arr, int k, double a, double s0, double s1) {
+  const double *m = coef + (size_t)arr * nl, *w0 = m + 2 * (size_t)nl, *kk = m + 2 * (size_t)DIM * nl;
+  double v = fma(s0, w0[k], fma(a, m[k], kk[k]));
+  if constexpr (DIM == 3) v = fma(s1, (w0 + 2 * (size_t)nl)[k], v);
+  return v;
+}
+template <int DIM> __global__ void __launch_bounds__(64)
+k_q1_line_factor_tensor(LineCols L, int nl, double a, const double *__restrict__ coef, double *__restrict__ inv) {
+  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= L.ncol) return;
+  double s0, s1; (void)line_sigma2<DIM>(L, col, s0, s1);
+  double ip = 0, off = 0;
+  for (int k = 0; k < nl; ++k) {
+    const double d = line_entry_tensor<DIM>(coef, nl, 0, k, a, s0, s1) - off * off * ip;
+    ip = 1.0 / d;
+    inv[(int64_t)k * L.ncol + col] = ip;
+    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
+  }
+}
+template <int DIM> __global__ void __launch_bounds__(64)
+k_q1_line_solve_tensor(LineCols L, int nl, double a, int fixed_lo, int fixed_hi, const double *__restrict__ coef, const double *__restrict__ inv, const double *__restrict__ in, double *__restrict__ out) {
+  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= L.ncol) return;
+  double s0, s1;
+  if (line_sigma2<DIM>(L, col, s0, s1)) {
+    for (int k = 0; k < nl; ++k) out[(int64_t)k * L.ncol + col] = 0.0;
+    return;
+  }
+  double t = 0, off = 0;           // t = y_{k-1} / pivot_{k-1}
+#pragma unroll 4
+  for (int k = 0; k < nl; ++k) {
+    const int64_t at = (int64_t)k * L.ncol + col;
+    const bool fixed = (k == 0 && fixed_lo) || (k == nl - 1 && fixed_hi);
+    const double r = fixed ? 0.0 : in[at];
+    const double y = fma(-off, t, r);
+    out[at] = y;
+    t = y * inv[at];
+    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
+  }
+  double x = t;                    // x_{nl-1}
+  out[(int64_t)(nl - 1) * L.ncol + col] = x;
+#pragma unroll 4
+  for (int k = nl - 2; k >= 0; --k) {
+    const int64_t at = (int64_t)k * L.ncol + col;
+    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
+    x = fma(-off, x, out[at]) * inv[at];
+    out[at] = x;
+  }
+}
+
 }  // namespace
 
+void q1_line_factor_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv) {
+  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
+  const unsigned grid = (unsigned)((L.ncol + 63) / 64);
+  if (dim == 2) hipLaunchKernelGGL(k_q1_line_factor_tensor<2>, grid, 64, 0, s, L, nl, a, coef, inv);
+  else hipLaunchKernelGGL(k_q1_line_factor_tensor<3>, grid, 64, 0, s, L, nl, a, coef, inv);
+}
+void q1_line_solve_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out) {
+  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
+  const unsigned grid = (unsigned)((L.ncol + 63) / 64);
+  if (dim == 2) hipLaunchKernelGGL(k_q1_line_solve_tensor<2>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
+  else hipLaunchKernelGGL(k_q1_line_solve_tensor<3>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
+}
 void q1_line_factor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv) {
   const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
   const unsigned grid = (unsigned)((L.ncol + 63) / 64);

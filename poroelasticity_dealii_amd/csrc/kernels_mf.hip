@@ -243,15 +243,44 @@ k_p_residual_stencil_var(int n0, int n1, int n2, double h0, double h1, double h2
   const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum_var<DIM>(n0, n1, n2, h0, h1, h2, 0.0, node, Tp, C);
   R[node] = -((s1 + s2) + src[node]);
 }
-void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, const double *t, const double *p, const double *src, double *R) {
+// ---- and with a per-cell diagonal tensor (poro_ctx_set_cell_permeability_tensor): kap = DIM planes of lattice-ordered weights ---------------------------------------
+template <int DIM> __global__ void __launch_bounds__(256)
+k_p_stencil_tensor(int n0, int n1, int n2, double h0, double h1, double h2, double a, const double *__restrict__ kap, const double *__restrict__ x, double *__restrict__ y) {
+  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= (int64_t)n0 * n1 * n2) return;
+  PStencilTaps<DIM> T; PStencilCellsT<DIM> C;
+  p_stencil_load<DIM>(n0, n1, n2, node, x, T); p_stencil_load_cells_tensor<DIM>(n0, n1, n2, node, kap, C);
+  y[node] = p_stencil_sum_tensor<DIM, true>(n0, n1, n2, h0, h1, h2, a, node, T, C);
+}
+template <int DIM> __global__ void __launch_bounds__(256)
+k_p_residual_stencil_tensor(int n0, int n1, int n2, double h0, double h1, double h2, const double *__restrict__ kap, const double *__restrict__ t, const double *__restrict__ p,
+                            const double *__restrict__ src, double *__restrict__ R) {
+  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= (int64_t)n0 * n1 * n2) return;
+  PStencilTaps<DIM> Tt, Tp; PStencilCellsT<DIM> C;
+  p_stencil_load<DIM>(n0, n1, n2, node, t, Tt); p_stencil_load<DIM>(n0, n1, n2, node, p, Tp); p_stencil_load_cells_tensor<DIM>(n0, n1, n2, node, kap, C);
+  const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum_tensor<DIM, false>(n0, n1, n2, h0, h1, h2, 0.0, node, Tp, C);
+  R[node] = -((s1 + s2) + src[node]);
+}
+void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, const double *t, const double *p, const double *src, double *R, bool tensor) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const unsigned grid = (unsigned)(((int64_t)n0 * n1 * n2 + 255) / 256);
+  if (tensor) {
+    if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil_tensor<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kap, t, p, src, R);
+    else hipLaunchKernelGGL(k_p_residual_stencil_tensor<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kap, t, p, src, R);
+    return;
+  }
   if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil_var<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kap, t, p, src, R);
   else hipLaunchKernelGGL(k_p_residual_stencil_var<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kap, t, p, src, R);
 }
-void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, const double *x, double *y) {
+void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, const double *x, double *y, bool tensor) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const unsigned grid = (unsigned)(((int64_t)n0 * n1 * n2 + 255) / 256);
+  if (tensor) {
+    if (dim == 2) hipLaunchKernelGGL(k_p_stencil_tensor<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kap, x, y);
+    else hipLaunchKernelGGL(k_p_stencil_tensor<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kap, x, y);
+    return;
+  }
   if (dim == 2) hipLaunchKernelGGL(k_p_stencil_var<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kap, x, y);
   else hipLaunchKernelGGL(k_p_stencil_var<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kap, x, y);
 }

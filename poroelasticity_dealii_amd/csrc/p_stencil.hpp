@@ -174,6 +174,89 @@ template <int DIM> __device__ __forceinline__ double p_stencil_sum_var(int n0, i
   return acc;
 }
 
+// ---- per-cell diagonal tensor: K_kappa = sum_c ∫_c grad(phi_i) . diag(kappa_c) grad(phi_j), K_e = kx k (x) m (x) m + ky m (x) k (x) m + kz m (x) m (x) k -------------
+// The row of a node sums DIM weights per surrounding cell, one per direction of the derivative.  kap holds one plane of `plane` cells per component, each in lattice cell
+// order, so that consecutive lanes read consecutive addresses of every plane.  Same discipline: clamped cell index, unconditional loads, a select for the cells outside
+// the box, one fixed order of cells, components and taps.
+template <int DIM> struct PStencilCellsT { PStencilCells<DIM> d[DIM]; };
+
+template <int DIM> __device__ __forceinline__ void p_stencil_load_cells_tensor(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, PStencilCellsT<DIM> &C) {
+  const int64_t plane = (int64_t)(n0 - 1) * (n1 - 1) * (DIM == 3 ? n2 - 1 : 1);
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) p_stencil_load_cells<DIM>(n0, n1, n2, node, kap + d * plane, C.d[d]);
+}
+
+// MASS: the a M part is summed with the taps (the Jacobian); without it the function gives K_kappa x alone
+template <int DIM, bool MASS> __device__ __forceinline__ double p_stencil_sum_tensor(int n0, int n1, int n2, double h0, double h1, double h2, double a, int64_t node,
+                                                                                      const PStencilTaps<DIM> &T, const PStencilCellsT<DIM> &C) {
+  const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
+  const int nd[3] = {n0, n1, n2};
+  const double h[3] = {h0, h1, h2};
+  double M1[3][3];             // the assembled 1D mass rows, as in p_stencil_sum
+  double em[3][2][3], ek[3][2][3];   // as in p_stencil_sum_var
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    const double L = idx[d] > 0 ? 1.0 : 0.0, R = idx[d] < nd[d] - 1 ? 1.0 : 0.0;
+    M1[d][0] = L * h[d] / 6; M1[d][2] = R * h[d] / 6; M1[d][1] = (L + R) * h[d] / 3;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int o = 0; o < 3; ++o) {
+        const int own = 1 - c, other = own + o - 1;
+        const bool held = other == 0 || other == 1;
+        em[d][c][o] = held ? (other == own ? h[d] / 3 : h[d] / 6) : 0.0;
+        ek[d][c][o] = held ? (other == own ? 1.0 / h[d] : -1.0 / h[d]) : 0.0;
+      }
+  }
+  double acc = 0;
+  if constexpr (DIM == 2) {
+#pragma unroll
+    for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+      for (int di = 0; di < 3; ++di) {
+        double wK = 0;
+#pragma unroll
+        for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+          for (int c0 = 0; c0 < 2; ++c0) {
+            const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1);        // (known at compile time after unrolling)
+            if (held) {
+              wK = fma(C.d[0].w[2 * c1 + c0], ek[0][c0][di] * em[1][c1][dj], wK);
+              wK = fma(C.d[1].w[2 * c1 + c0], em[0][c0][di] * ek[1][c1][dj], wK);
+            }
+          }
+        const double w = MASS ? a * (M1[0][di] * M1[1][dj]) + wK : wK;
+        acc = w != 0.0 ? fma(w, T.v[3 * dj + di], acc) : acc;
+      }
+  } else {
+#pragma unroll
+    for (int dk = 0; dk < 3; ++dk)
+#pragma unroll
+      for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+        for (int di = 0; di < 3; ++di) {
+          double wK = 0;
+#pragma unroll
+          for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int c1 = 0; c1 < 2; ++c1)
+#pragma unroll
+              for (int c0 = 0; c0 < 2; ++c0) {
+                const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1) && (dk == 1 || dk == 2 * c2);
+                if (held) {
+                  const int cell = 4 * c2 + 2 * c1 + c0;
+                  wK = fma(C.d[0].w[cell], ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]), wK);
+                  wK = fma(C.d[1].w[cell], em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk]), wK);
+                  wK = fma(C.d[2].w[cell], em[0][c0][di] * (em[1][c1][dj] * ek[2][c2][dk]), wK);
+                }
+              }
+          const double w = MASS ? a * (M1[0][di] * (M1[1][dj] * M1[2][dk])) + wK : wK;
+          acc = w != 0.0 ? fma(w, T.v[9 * dk + 3 * dj + di], acc) : acc;
+        }
+  }
+  return acc;
+}
+
 template <int DIM> __device__ __forceinline__ double p_stencil_row(int n0, int n1, int n2, double h0, double h1, double h2, double a, double kappa, int64_t node,
                                                                    const double *__restrict__ x) {
   PStencilTaps<DIM> T;

@@ -25,4 +25,33 @@ inline std::vector<double> perm_line_coefficients(const std::vector<double> &hce
   return c;
 }
 
+// The same for a layered diagonal tensor diag(kx, ky[, kz]) (poro_ctx_set_cell_permeability_tensor; k_q1_line_solve_tensor).  In the eigenbasis of the leading
+// directions the line system of mode (p, q) is  a Mz + lam_x[p] Mz^kx + lam_y[q] Mz^ky + Kz^kz  (2D: a My + lam_x[p] My^kx + Ky^ky): every leading direction brings
+// its own weighted mass line, the line direction's component weights the Laplace line.
+// [md | mo | w0d | w0o | (w1d | w1o) | kd | ko]: 2 (dim + 1) arrays of nl = hcell.size() + 1 entries; layer[d]: the layer values of component d, d < dim.
+inline std::vector<double> perm_tensor_line_coefficients(int dim, const std::vector<double> &hcell, const std::vector<double> *layer, bool fixed_lo, bool fixed_hi) {
+  const size_t n = hcell.size(), nl = n + 1; const int na = 2 * (dim + 1);
+  std::vector<double> c((size_t)na * nl, 0.0);
+  double *md = c.data(), *mo = md + nl, *kd = md + (size_t)(na - 2) * nl, *ko = kd + nl;
+  for (size_t e = 0; e < n; ++e) {
+    const double h = hcell[e], k = layer[dim - 1][e];
+    md[e] += h / 3; md[e + 1] += h / 3; mo[e] += h / 6;
+    for (int d = 0; d + 1 < dim; ++d) {
+      double *wd = md + (size_t)(2 + 2 * d) * nl, *wo = wd + nl; const double w = layer[d][e];
+      wd[e] += w * h / 3; wd[e + 1] += w * h / 3; wo[e] += w * h / 6;
+    }
+    kd[e] += k / h; kd[e + 1] += k / h; ko[e] -= k / h;
+  }
+  for (int side = 0; side < 2; ++side) {
+    if (!(side ? fixed_hi : fixed_lo)) continue;
+    const size_t at = side ? n : 0;
+    for (int arr = 0; arr < na; arr += 2) {
+      double *dg = md + (size_t)arr * nl, *of = dg + nl;
+      dg[at] = arr == na - 2 ? 1.0 : 0.0;
+      if (!side) of[0] = 0; else if (n) of[n - 1] = 0;
+    }
+  }
+  return c;
+}
+
 }  // namespace poro

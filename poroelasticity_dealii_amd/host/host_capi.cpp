@@ -227,6 +227,12 @@ int poro_host_set_permeability_layers(void *h, int n, const double *top, const d
 int poro_host_inherit_cell_permeability(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_permeability(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies when out != NULL
 int64_t poro_host_get_cell_permeability(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_k_over_mu, out); }
+// extension: the per-cell diagonal tensor diag(kx, ky[, kz]) / mu, values[n][dim] with x first (NULL: none); a problem carries the scalar field or the tensor
+int poro_host_set_cell_permeability_tensor(void *h, const double *values, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_permeability_tensor(values, n); }); }
+int poro_host_set_permeability_tensor_layers(void *h, int n, const double *top, const double *kx, const double *ky, const double *kz /* not read in 2D */) { return on_problem(h, [&](ProblemData &P) { P.set_permeability_tensor_layers(n, top, kx, ky, kz); }); }
+int poro_host_inherit_cell_permeability_tensor(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_permeability_tensor(*static_cast<ProblemData *>(old)); }); }
+// returns the number of doubles the problem carries (n_cells * dim; 0: none)
+int64_t poro_host_get_cell_permeability_tensor(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_k_tensor, out); }
 // extension: per-cell Lame lambda and shear modulus G of the displacement system (both NULL: back to the scalars); kept with the problem and handed over like the permeability
 int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_moduli(lam, G, n); }); }
 // by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre; (E, nu) -> (lambda, G) as the parameter file's are

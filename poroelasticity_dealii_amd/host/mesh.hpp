@@ -457,7 +457,7 @@ struct ProblemData {
     if (!values) { cell_k_over_mu.clear(); return; }
     check_field_length("set_cell_permeability", n);
     for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
-    cell_k_over_mu.assign(values, values + n);
+    cell_k_over_mu.assign(values, values + n); cell_k_tensor.clear();
   }
   void set_permeability_layers(int n_layers, const double *top, const double *value) {
     if (n_layers < 1 || !top || !value) throw std::runtime_error("set_permeability_layers: needs at least one TOP=VALUE layer");
@@ -467,6 +467,40 @@ struct ProblemData {
     set_cell_permeability(f.data(), (int64_t)f.size());
   }
   void inherit_cell_permeability(const ProblemData &O) { cell_k_over_mu = inherited(O, O.cell_k_over_mu, "inherit_cell_permeability"); }
+
+  // the diagonal tensor diag(kx, ky[, kz]) / mu of the pressure system, [n_cells][dim], x first (poro_ctx_set_cell_permeability_tensor).  The problem carries the scalar
+  // field or the tensor: setting one drops the other
+  std::vector<double> cell_k_tensor;
+  void set_cell_permeability_tensor(const double *values, int64_t n) {
+    if (!values) { cell_k_tensor.clear(); return; }
+    check_field_length("set_cell_permeability_tensor", n);
+    const int dim = mesh.dim;
+    for (int64_t i = 0; i < n * dim; ++i)
+      if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability_tensor: component " + std::to_string(i % dim) + " of cell " + std::to_string(i / dim) + " is not finite and > 0");
+    cell_k_tensor.assign(values, values + n * dim); cell_k_over_mu.clear();
+  }
+  // kz is not read in 2D (may be null)
+  void set_permeability_tensor_layers(int n_layers, const double *top, const double *kx, const double *ky, const double *kz) {
+    const int dim = mesh.dim;
+    if (n_layers < 1 || !top || !kx || !ky || (dim == 3 && !kz)) throw std::runtime_error("set_permeability_tensor_layers: needs at least one TOP=KX:KY[:KZ] layer with one value per direction");
+    const std::vector<int> layer = cell_layers(n_layers, top, "set_permeability_tensor_layers");
+    const double *comp[3] = {kx, ky, kz};
+    std::vector<double> f(layer.size() * dim);
+    for (size_t c = 0; c < layer.size(); ++c) for (int d = 0; d < dim; ++d) f[c * dim + d] = comp[d][layer[c]];
+    set_cell_permeability_tensor(f.data(), (int64_t)layer.size());
+  }
+  // component by component through the coarse cells: a child takes its parent's components exactly, a coarsened parent the per-component mean
+  void inherit_cell_permeability_tensor(const ProblemData &O) {
+    const int dim = mesh.dim; const size_t n_old = O.cell_k_tensor.size() / dim;
+    std::vector<double> out, one(n_old);
+    for (int d = 0; d < dim && n_old; ++d) {
+      for (size_t c = 0; c < n_old; ++c) one[c] = O.cell_k_tensor[c * dim + d];
+      const std::vector<double> got = inherited(O, one, "inherit_cell_permeability_tensor");
+      if (!d) out.resize(got.size() * dim);
+      for (size_t c = 0; c < got.size(); ++c) out[c * dim + d] = got[c];
+    }
+    cell_k_tensor = std::move(out);
+  }
 
   // Lame lambda and shear modulus G of the displacement system (the two come together)
   std::vector<double> cell_lambda, cell_G;

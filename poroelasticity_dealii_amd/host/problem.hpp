@@ -201,6 +201,7 @@ template <int dim> class PoroElasticProblem {
     build_refined_box_problem_mask(*N, O.mesh.dim, O.box_n, O.box_size, O.box_k_u, mask);    // :481-483
     N->inherit_cell_moduli(O);                                                               // likewise lambda, G (poro_ctx_set_cell_moduli)
     N->inherit_cell_permeability(O);                                                         // a child takes its parent's k / mu; make_ctx below hands the field to the new context
+    N->inherit_cell_permeability_tensor(O);                                                  // or its parent's diag(kx, ky, kz) / mu, component by component
     std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
     transfer_rows_p(O, *N, ptr, node, weight);
     int32_t scatter = PORO_SCATTER_COLOURED, fdm_req = PORO_FDM_FP64;
@@ -437,6 +438,7 @@ template <int dim> class PoroElasticProblem {
     check(poro_ctx_create(&P.d, device, operator_mode, &c), "poro_ctx_create");
     // the per-cell fields of the problem go to the context before anything is assembled from it
     const char *failed = !P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0 ? "ctx_set_cell_permeability: "
+                         : !P.cell_k_tensor.empty() && poro_ctx_set_cell_permeability_tensor(c, P.cell_k_tensor.data(), (int64_t)P.cell_k_tensor.size() / P.mesh.dim) != 0 ? "ctx_set_cell_permeability_tensor: "
                          : !P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0 ? "ctx_set_cell_moduli: " : nullptr;
     if (failed) { const std::string why = poro_last_error(); poro_ctx_destroy(c); throw std::runtime_error(failed + why); }
     return c;

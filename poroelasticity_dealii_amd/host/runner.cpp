@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -8,6 +8,8 @@
 // --permeability-layers TOP=VALUE[,TOP=VALUE...] (an extension: the reference's permeability is one constant) sets k / mu layer by layer along the slowest direction, in the
 // units of k / mu: a cell takes the VALUE of the first layer whose TOP is >= the coordinate of its centre (e.g. a caprock over a reservoir: `0=1e-11,5=1e-14` on the box
 // [-5, 5]^3).  --fastest then takes the fast diagonalisation for the pressure system on boxes and Jacobi elsewhere; the run prints the choice.
+// --permeability-tensor-layers TOP=KX:KY[:KZ][,TOP=KX:KY[:KZ]...] (an extension likewise) sets the diagonal tensor diag(kx, ky[, kz]) / mu layer by layer in the same way: one
+// value per direction of the problem (KZ in 3D only), e.g. a sediment with kv = kh / 100: `5=1e-11:1e-11:1e-13`.  Not together with --permeability-layers.
 // --moduli-layers TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] (an extension likewise) sets Young's modulus and Poisson's ratio layer by layer along the slowest direction, the
 // layers chosen by cell centres in the same way; lambda and G follow by the parameter file's formulas.  On a box the displacement operator then runs the general cell loop;
 // --fastest takes the fast diagonalisation (line-solve form) on boxes and Chebyshev elsewhere; the run prints the field's kind and the choice, also after every adapt.
@@ -28,7 +30,7 @@
 using namespace poro_host;
 
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
-                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
+                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
 // TOP=V[:V...][,TOP=V[:V...]...], one array of `fields` per number of an item (the tops first): appends every item.  False unless every item has that shape, every number
@@ -54,6 +56,7 @@ int main(int argc, char **argv) {
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   std::vector<double> layer_top, layer_value;
+  std::vector<double> tensor_top, tensor_k[3];
   std::vector<double> moduli_top, moduli_young, moduli_poisson;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
@@ -88,6 +91,16 @@ int main(int argc, char **argv) {
         std::cerr << "--permeability-layers needs TOP=VALUE[,TOP=VALUE...] with ascending tops and positive values, got " << arg << std::endl; return 1;
       }
     }
+    else if (!std::strcmp(argv[i], "--permeability-tensor-layers") && i + 1 < argc) {   // diag(kx, ky[, kz]) / mu by layers of the slowest direction, bottom to top
+      const char *arg = argv[++i];
+      std::vector<double> top3, k3[3], top2, k2[2];             // every item with three values, or every item with two
+      const bool three = parse_layers(arg, {&top3, &k3[0], &k3[1], &k3[2]}), two = !three && parse_layers(arg, {&top2, &k2[0], &k2[1]});
+      bool ok = (three || two) && tensor_top.empty();
+      if (three) { tensor_top = top3; for (int d = 0; d < 3; ++d) tensor_k[d] = k3[d]; }
+      if (two) { tensor_top = top2; for (int d = 0; d < 2; ++d) tensor_k[d] = k2[d]; }
+      for (int d = 0; d < 3; ++d) ok = ok && std::all_of(tensor_k[d].begin(), tensor_k[d].end(), positive);
+      if (!ok) { std::cerr << "--permeability-tensor-layers needs (once) TOP=KX:KY[:KZ][,TOP=KX:KY[:KZ]...] with ascending tops and positive values, got " << arg << std::endl; return 1; }
+    }
     else if (!std::strcmp(argv[i], "--moduli-layers") && i + 1 < argc) {   // Young's modulus and Poisson's ratio by layers of the slowest direction, bottom to top
       const char *arg = argv[++i];
       if (!parse_layers(arg, {&moduli_top, &moduli_young, &moduli_poisson}) || !std::all_of(moduli_young.begin(), moduli_young.end(), positive) ||
@@ -100,6 +113,7 @@ int main(int argc, char **argv) {
   }
   if (fdm_fp32 && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
   if (fdm_per_direction && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-per-direction needs --block-fdm or --fastest" << std::endl; return 1; }
+  if (!layer_top.empty() && !tensor_top.empty()) { std::cerr << "--permeability-tensor-layers and --permeability-layers exclude each other (a context holds the scalar field or the tensor)" << std::endl; return 1; }
   if (refine_every < 0) { std::cerr << "--refine-every needs a non-negative step count" << std::endl; return 1; }
   if (refine_every > 0 && !mesh_file.empty()) { std::cerr << "--refine-every adapts boxes only (not --mesh)" << std::endl; return 1; }
   try {
@@ -122,6 +136,10 @@ int main(int argc, char **argv) {
       else build_box_problem(P, data.dim, n, size, degree);
     }
     if (!layer_top.empty()) P.set_permeability_layers((int)layer_top.size(), layer_top.data(), layer_value.data());
+    if (!tensor_top.empty()) {
+      if ((data.dim == 3) != !tensor_k[2].empty()) throw std::runtime_error("--permeability-tensor-layers: a " + std::to_string(data.dim) + "D problem needs " + (data.dim == 3 ? "TOP=KX:KY:KZ" : "TOP=KX:KY") + " layers");
+      P.set_permeability_tensor_layers((int)tensor_top.size(), tensor_top.data(), tensor_k[0].data(), tensor_k[1].data(), data.dim == 3 ? tensor_k[2].data() : nullptr);
+    }
     if (!moduli_top.empty()) P.set_moduli_layers((int)moduli_top.size(), moduli_top.data(), moduli_young.data(), moduli_poisson.data());
     RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
@@ -139,8 +157,14 @@ int main(int argc, char **argv) {
         if (poro_ctx_get_cell_moduli(prob.context(), nullptr, nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
         os << "moduli layers: " << moduli_top.size() << ", field kind " << kind << "; displacement preconditioner: " << prec_name[prob.displacement_solver.control.preconditioner];
       };
-      if (!pressure_labels.empty() || !layer_top.empty() || !moduli_top.empty())        // (only with the extensions, so the reference's log stays as it is)
+      auto tensor_line = [&](std::ostream &os) {            // likewise the tensor's kind and the pressure preconditioner chosen for it
+        int32_t kind = 0;
+        if (poro_ctx_get_cell_permeability_tensor(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
+        os << "permeability tensor layers: " << tensor_top.size() << ", field kind " << kind << "; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner];
+      };
+      if (!pressure_labels.empty() || !layer_top.empty() || !moduli_top.empty() || !tensor_top.empty())        // (only with the extensions, so the reference's log stays as it is)
         prob.on_adapt = [&](int step, int64_t before, int64_t after) {     // the choice is made again on every adapted mesh
+          if (!tensor_top.empty()) { std::cout << "adapted before step " << step << ": "; tensor_line(std::cout); std::cout << std::endl; }
           if (!moduli_top.empty()) { std::cout << "adapted before step " << step << ": "; moduli_line(std::cout); std::cout << std::endl; }
           std::cout << "adapted before step " << step << ": " << before << " -> " << after << " cells; prescribed pressures: " << prob.problem()->d.n_dirichlet_p
                     << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << ", projection preconditioner: "
@@ -154,6 +178,7 @@ int main(int argc, char **argv) {
         std::cout << "block FDM form: " << runs[eff] << ", split directions (x y z): " << split[0] << " " << split[1] << " " << split[2] << std::endl;
       }
       if (!moduli_top.empty()) { moduli_line(std::cout); std::cout << std::endl; }
+      if (!tensor_top.empty()) { tensor_line(std::cout); std::cout << std::endl; }
       if (!layer_top.empty()) {
         int32_t kind = 0;
         if (poro_ctx_get_cell_permeability(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
