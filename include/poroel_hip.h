@@ -448,7 +448,10 @@ int  poro_export_csr(poro_ctx *ctx, int which, int64_t *row_ptr, int32_t *col, d
 int  poro_apply_operator(poro_ctx *ctx, int which, const double *x_host, double *y_host);
 /* z = P^-1 g with the displacement preconditioner (PORO_PREC_JACOBI | PORO_PREC_FDM), host in/out: parity hook for the preconditioner
  * PoroElasticDisplacementSolver<dim>::solve hands to cg.solve (:302-305; the reference's is PreconditionSSOR).  reps > 0 additionally times
- * `reps` applications on the device (HIP events) into *seconds_per_apply. */
+ * `reps` applications on the device (HIP events) into *seconds_per_apply.
+ * Partitioned contexts: PORO_PREC_FDM is COLLECTIVE - every rank calls it, each with its own window of g (its slab, shared planes included, the same values in both
+ * copies of a shared plane), and gets its window of z; the set-up agrees on the form through all-reduces and every application runs two all-to-alls.  PORO_PREC_JACOBI
+ * is local (the assembled diagonal already holds the neighbours' share on the shared planes). */
 int  poro_apply_preconditioner_u(poro_ctx *ctx, int32_t preconditioner, const double *g_host, double *z_host, int32_t reps, double *seconds_per_apply);
 /* repeat y = A_u x `reps` times on device-resident synthetic x; returns mean seconds per application (HIP events) */
 int  poro_bench_operator(poro_ctx *ctx, int which, int operator_mode, int reps, double *seconds_per_apply);
