@@ -53,12 +53,13 @@ template <int N> struct CellField {
   int kind = 0;
   std::vector<double> host[N], layer[N];
   void clear() { kind = 0; for (int a = 0; a < N; ++a) { host[a].clear(); layer[a].clear(); } }
-  // Takes the N arrays of n_cells values.  order (cell_lattice_order on dim, nc; null: no lattice, kind 2): classifies every component and returns the lattice-ordered
-  // copies (empty without a lattice)
-  std::array<std::vector<double>, N> set(const double *const (&comp)[N], int64_t n_cells, const std::vector<int64_t> *order = nullptr, int dim = 0, const int *nc = nullptr) {
+  // Takes the first `used` of the N arrays of n_cells values; the components past them stay empty and do not enter `kind`.  order (cell_lattice_order on dim, nc; null:
+  // no lattice, kind 2): classifies every component and returns the lattice-ordered copies (empty without a lattice)
+  std::array<std::vector<double>, N> set(const double *const (&comp)[N], int64_t n_cells, const std::vector<int64_t> *order = nullptr, int dim = 0, const int *nc = nullptr, int used = N) {
     std::array<std::vector<double>, N> lattice;
     kind = order ? 1 : 2;
-    for (int a = 0; a < N; ++a) {
+    for (int a = used; a < N; ++a) { host[a].clear(); layer[a].clear(); }
+    for (int a = 0; a < used; ++a) {
       host[a].assign(comp[a], comp[a] + n_cells); layer[a].clear();
       if (!order) continue;
       lattice[a].assign((size_t)nc[0] * nc[1] * (dim == 3 ? nc[2] : 1), 0.0);

@@ -308,17 +308,16 @@ struct poro_ctx {
   poro::KellyDev kelly;
   // The per-cell coefficient fields (ctx_fields.hip; one rank).  Both are a poro::CellField (cell_field.hpp): kind 0 none, 1 layered along the slowest direction of
   // `lines`, 2 general; host[a]: the caller's arrays; layer[a]: per cell layer of that direction the value (kind 1) or the arithmetic mean (kind 2) - the coefficients of
-  // the line-solve forms of PORO_PREC_FDM.  What each adds is its device state.  perm: k / mu of the pressure system.  cell: the caller's cell order (the weights of the
-  // assembly, Kp = K_kappa).  lattice: lattice cell order, for the stencil kernels of matrix-free boxes.  line: one set of 1D arrays and cached reciprocal pivots per
-  // table set (free ends / fixed ends); `a` = the 1 / (M_b dt) the pivots belong to
-  struct Perm : poro::CellField<1> {
+  // the line-solve forms of PORO_PREC_FDM.  What each adds is its device state.  perm: k / mu of the pressure system, components 0 .. ncomp - 1.  ncomp: 0 while
+  // kind == 0, 1 for one k / mu per cell (poro_ctx_set_cell_permeability), dim for the diagonal tensor diag(kx, ky[, kz]) / mu (poro_ctx_set_cell_permeability_tensor).
+  // cell: [n_cells][ncomp] in the caller's cell order (the weights of the assembly, Kp = K_kappa).  lattice: one plane of n_cells per component, each in lattice cell
+  // order (consecutive lanes of the stencil kernels of matrix-free boxes read consecutive addresses).  line: one set of 1D arrays (perm_line_coefficients) and cached
+  // reciprocal pivots per table set (free ends / fixed ends); `a` = the 1 / (M_b dt) the pivots belong to
+  struct Perm : poro::CellField<3> {
+    int ncomp = 0;
     poro::DevBuf<double> cell, lattice;
     struct Line { bool built = false; int lo = 0, hi = 0; double a = -1; poro::DevBuf<double> coef, inv; } line[2];
   } perm;
-  // permt: the diagonal tensor diag(kx, ky[, kz]) / mu of the pressure system (poro_ctx_set_cell_permeability_tensor), components 0 .. dim - 1; a context holds perm or
-  // permt, never both.  cell: [n_cells][dim] in the caller's cell order (the weights of the assembly).  lattice: one plane of n_cells per component, each in lattice cell
-  // order (consecutive lanes of the stencil kernels read consecutive addresses).  line: as perm.line, with the 2 (dim + 1) arrays of perm_tensor_line_coefficients
-  struct PermTensor : poro::CellField<3> { poro::DevBuf<double> cell, lattice; Perm::Line line[2]; } permt;
   // mod: (Lame lambda, shear modulus G) of the displacement system, components 0 and 1.  cell: [n_cells][2] = (lambda, G) in the caller's cell order, what the general
   // cell kernels and the coloured assembly read.  node: [n_p][2], the arithmetic mean over the cells that touch a pressure dof - the constants of the effective stresses and
   // of the fixed-stress strain update.  While kind != 0 a box-tagged context runs the general cell loop for everything that depends on the moduli (box_fast_u below)
@@ -329,9 +328,6 @@ namespace poro {
 
 // the constant-coefficient structured kernels (k_kron*, the single Ke, box_asm_u_matrix, the diagonal dictionary) serve the displacement system: a box without per-cell moduli
 inline bool box_fast_u(const poro_ctx *c) { return c->box.enabled && !c->mod.kind; }
-// the per-cell coefficient of the pressure system, scalar or tensor: its kind, and the lattice-ordered field of the stencil kernels (tensor: dim planes)
-inline int perm_kind(const poro_ctx *c) { return c->perm.kind ? c->perm.kind : c->permt.kind; }
-inline const double *perm_lattice(const poro_ctx *c) { return c->permt.kind ? c->permt.lattice.p : c->perm.lattice.p; }
 
 // ---- kernels_la.hip -----------------------------------------------------------------------------
 void la_fill(hipStream_t s, double *x, double v, int64_t n);
@@ -425,10 +421,10 @@ void asm_u_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_
 // order / group_off: the boundary faces grouped by (colour of the cell, local face number), one launch per group (no atomics, fixed summation order)
 void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const std::vector<int64_t> &group_off, const int32_t *bf_cell, const int32_t *bf_local, const int32_t *bf_id,
                    int n_neu, const int32_t *label, const int32_t *comp, const double *value, double *rhs);
-// M, src == null: the Laplace matrix alone (K += K_c; with cell_w: K += cell_w[c] K_c, the per-cell coefficient of poro_ctx_set_cell_permeability)
-// cell_wt ([n_cells][dim], instead of cell_w): K += sum_q (sum_c cell_wt[cell][c] G_i[c] G_j[c]) JxW, the diagonal tensor of poro_ctx_set_cell_permeability_tensor
+// M, src == null: the Laplace matrix alone (K += K_c).  With cell_w ([n_cells][ncomp], K alone), ncomp == 1: K += cell_w[c] K_c, the per-cell coefficient of
+// poro_ctx_set_cell_permeability; ncomp == dim: K += sum_q (sum_d cell_w[c][d] G_i[d] G_j[d]) JxW, the diagonal tensor of poro_ctx_set_cell_permeability_tensor
 void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const int64_t *rp, const int32_t *col, double *M, double *K, double *src, const double *cell_w = nullptr,
-                    const double *cell_wt = nullptr);
+                    int ncomp = 1);
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *u, int n_comp, const int32_t *comps /*host*/,
                   double *const *rhs /*host array of device ptrs*/);
 
@@ -443,10 +439,10 @@ void mf_diag(hipStream_t s, const MfArgs &a, double *diag);
 // y = (a M + kappa K) x for the Q1 pressure space of a uniform box (constant-coefficient 3^dim-point stencil)
 void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y);
 void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R);
-// the same with a per-cell coefficient kap (lattice cell order): y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q)
-// tensor: kap holds dim planes of n_cells weights, component d weights the derivatives along direction d (K_e = kx k(x)m(x)m + ky m(x)k(x)m + kz m(x)m(x)k)
-void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, const double *x, double *y, bool tensor = false);
-void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, const double *t, const double *p, const double *src, double *R, bool tensor = false);
+// the same with a per-cell coefficient: y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q).  kap holds ncomp planes of n_cells weights in lattice cell order, ncomp = 1
+// (one k / mu per cell) or dim (component d weights the derivatives along direction d, K_e = kx k(x)m(x)m + ky m(x)k(x)m + kz m(x)m(x)k)
+void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, int ncomp, const double *x, double *y);
+void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, int ncomp, const double *t, const double *p, const double *src, double *R);
 
 // polynomial-preconditioner step fused into the structured operator's stores: z_new = z_j + omega D^-1 (g - A z_j), D^-1 in dictionary form; z_new != z_j
 struct KronCheb { const double *g = nullptr; double *znew = nullptr; double omega = 0; const uint8_t *cls = nullptr; const double *tab = nullptr;
@@ -467,11 +463,9 @@ void fdm_window_batch(hipStream_t s, double *grid, double *dense, double *dense_
 void fdm_window(hipStream_t s, double *dst, const double *src, bool to_block, int n_planes, int n_planes_pad, int64_t C, int64_t ncols_valid, int64_t grid_stride, int64_t grid_col0, int64_t grid_plane0);
 void fdm_transform(hipStream_t s, const double *T, int n_l, int64_t SI, int64_t n_outer, const double *in, double *out, const FdmScale *scale);
 // layered per-cell coefficient: reciprocal pivots of the line systems (once per a), and the line solves themselves, between the x / y transforms (coef: perm_line.hpp)
-void q1_line_factor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv);
-void q1_line_solve(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out);   // in != out, [plane of the slowest direction][column]
-// the same two for a layered diagonal tensor: one multiplier per leading direction on its own weighted mass line (coef: perm_tensor_line_coefficients, 2 (dim + 1) arrays)
-void q1_line_factor_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv);
-void q1_line_solve_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out);
+// nw: the weighted mass lines of coef, one multiplier each (1: lam_x + lam_y on the one line; 2: the diagonal tensor in 3D, lam_x and lam_y on a line each)
+void q1_line_factor(hipStream_t s, int dim, int nw, const FdmScalar &F, int nl, double a, const double *coef, double *inv);
+void q1_line_solve(hipStream_t s, int dim, int nw, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out);   // in != out, [plane of the slowest direction][column]
 void fdm_apply(hipStream_t s, const FdmScalar &F, double a, const double k[3], const double *g, double *z, double *t1, double *t2);
 // ---- kernels_fdmu.hip ---------------------------------------------------------------------------
 void fdmu_upload_dir(FdmuDir &D, const LineTables &T, bool single, bool split);   // split: the even / odd form (T.parity required) unless a switch or `single` rules it out; D.split tells

@@ -383,8 +383,8 @@ struct Q1System {
   Q1Set set = Q1Set::free_ends;       // FDM: the table set; fixed_ends = without the prescribed faces' end nodes
   Q1Set coarse_set = Q1Set::free_ends; // two-level: the coarse box's table set; fixed_ends = (J_H)_ff^-1 (the pressure Jacobian with prescribed rows)
   const double *kap = nullptr;        // a per-cell k / mu is set and the operator is the box stencil: the field in lattice cell order (kappa is then 1: val holds a M + K_kappa)
-  bool kap_tensor = false;            // kap is a diagonal tensor: dim planes (poro_ctx_set_cell_permeability_tensor)
-  int perm_kind = 0;                  // perm_kind(c), the scalar field's or the tensor's, for the pressure Jacobian (FDM: the line-solve form; direct only for kind 1), 0 for the projection
+  int kap_ncomp = 0;                  // the planes of kap: c->perm.ncomp, 1 or dim (the diagonal tensor of poro_ctx_set_cell_permeability_tensor)
+  int perm_kind = 0;                  // c->perm.kind for the pressure Jacobian (FDM: the line-solve form; direct only for kind 1), 0 for the projection
   bool distribute_inhom = true;       // constraints.distribute with the inhomogeneities; an UPDATE of a vector that already carries them (dp beside prescribed pressures) is distributed without
 };
 
@@ -401,7 +401,7 @@ bool q1_stencil(poro_ctx *c) { return c->operator_mode == PORO_OP_MATRIX_FREE &&
 // Q1Set::fixed_ends + mask (prescribed pressures on whole faces): x_e = J_ff^-1 b_e on the free rows and exactly 0 on the masked ones; the check leaves the masked rows out,
 // where (J x)_i is the coupling to the free neighbours and not part of the system
 bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *const *b, double *const *x, double *y_scratch, bool batched,
-                     const poro_solver_opts *opts, poro_solve_info *info, Q1Set set = Q1Set::free_ends, const uint8_t *mask = nullptr, const double *kap = nullptr, bool kap_tensor = false) {
+                     const poro_solver_opts *opts, poro_solve_info *info, Q1Set set = Q1Set::free_ends, const uint8_t *mask = nullptr, const double *kap = nullptr, int kap_ncomp = 0) {
   // kap != null (a layered per-cell k / mu, one rank): the line-solve form is the exact inverse, the check runs through the variable-coefficient stencil
   hipStream_t s = c->stream;
   const double *y[3];
@@ -417,7 +417,7 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
   for (int e = 0; e < n; ++e) {
     {
       Timed tm(c, "apply_p_stencil");
-      if (kap) p_stencil_apply_var(s, c->dim, c->box, a, kap, x[e], const_cast<double *>(y[e]), kap_tensor);
+      if (kap) p_stencil_apply_var(s, c->dim, c->box, a, kap, kap_ncomp, x[e], const_cast<double *>(y[e]));
       else p_stencil_apply(s, c->dim, c->box, a, kappa, x[e], const_cast<double *>(y[e]));
     }
     exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p);
@@ -463,7 +463,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     la_cons_expand(c->stream, c->cons_p, const_cast<double *>(x), false);
     if (stencil) {
       Timed tm(c, "apply_p_stencil");
-      if (q.kap) p_stencil_apply_var(c->stream, c->dim, c->box, q.a, q.kap, x, y, q.kap_tensor);
+      if (q.kap) p_stencil_apply_var(c->stream, c->dim, c->box, q.a, q.kap, q.kap_ncomp, x, y);
       else p_stencil_apply(c->stream, c->dim, c->box, q.a, q.kappa, x, y);
     } else {
       Timed tm(c, "apply_p_csr");
@@ -481,7 +481,7 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
     build_fdm_q1(c, q.set);
     if (direct_first) {
       poro_solve_info direct;
-      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, sys.h, false, opts, &direct, q.set, q.inert_fdm, q.kap, q.kap_tensor)) {
+      if (solve_q1_direct(c, q.a, q.kappa, 1, &q.b, &q.x, sys.h, false, opts, &direct, q.set, q.inert_fdm, q.kap, q.kap_ncomp)) {
         if (info) *info = direct;
         return 0;
       }
@@ -670,7 +670,7 @@ int poro_pres_apply_jacobian(poro_ctx *c, const double *x_host, double *y_host) 
     const double a = 1. / c->mat.biot_M / c->jac_dt;
     DevBuf<double> x, y; x.upload(x_host, c->n_p); y.alloc(c->n_p);
     if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
-      if (perm_kind(c)) p_stencil_apply_var(s, c->dim, c->box, a, perm_lattice(c), x.p, y.p, c->permt.kind != 0);
+      if (c->perm.kind) p_stencil_apply_var(s, c->dim, c->box, a, c->perm.lattice.p, c->perm.ncomp, x.p, y.p);
       else p_stencil_apply(s, c->dim, c->box, a, c->mat.k_over_mu, x.p, y.p);
     } else la_csr_spmv(s, c->Ap, c->Jp.p, x.p, y.p);
     exchange_add(c, y.p, c->n_p, c->comm.part.plane_p);
@@ -910,9 +910,9 @@ int poro_pres_assemble_residual(poro_ctx *c, double dt, double *l2) {
       la_pressure_tmp(s, c->tmp_p.p, vec(c, PORO_VEC_EPSV), vec(c, PORO_VEC_EPSV0), vec(c, PORO_VEC_P), vec(c, PORO_VEC_P_OLD), c->mat.biot_alpha / dt, 1. / c->mat.biot_M / dt, c->n_p);
       // a per-cell k / mu: Kp holds K_kappa (coefficient 1), the box stencil reads the field
       if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
-        if (perm_kind(c)) p_residual_stencil_var(s, c->dim, c->box, perm_lattice(c), c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R, c->permt.kind != 0);
+        if (c->perm.kind) p_residual_stencil_var(s, c->dim, c->box, c->perm.lattice.p, c->perm.ncomp, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
         else p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
-      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, perm_kind(c) ? 1.0 : c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
+      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
     }
     la_cons_reduce(s, c->cons_p, R);                                              // constraints.condense(residual) (:153); partial rows first, interface sums after
     exchange_add(c, R, c->n_p, c->comm.part.plane_p);
@@ -946,7 +946,7 @@ int poro_pres_assemble_jacobian(poro_ctx *c, double dt) {
     // J = M/(M_b dt) + (k/mu) K depends on dt only (the reference recomputes it every pressure iteration): same dt, same matrix
     if (c->jac_dt == dt) return 0;
     Timed tm(c, "pressure_jacobian");
-    la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, perm_kind(c) ? 1.0 : c->mat.k_over_mu, c->Ap.nnz);   // (per-cell k / mu: Kp holds K_kappa)
+    la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->Ap.nnz);   // (per-cell k / mu: Kp holds K_kappa)
     la_csr_diag(c->stream, c->Ap, c->Jp.p, c->diag_J.p);
     exchange_add(c, c->diag_J.p, c->n_p, c->comm.part.plane_p);
     if (!c->dinv_J.p) c->dinv_J.alloc(c->n_p);
@@ -968,9 +968,9 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     const bool two_level_pdir = prec == PORO_PREC_TWO_LEVEL && c->n_pdir;           // the coarse box carries the prescribed set as whole faces (two_level_supported_pj)
     Q1System J;
     J.a = 1. / c->mat.biot_M / c->jac_dt;
-    J.kappa = perm_kind(c) ? 1.0 : c->mat.k_over_mu;
-    J.perm_kind = perm_kind(c);
-    if (perm_kind(c) && q1_stencil(c)) { J.kap = perm_lattice(c); J.kap_tensor = c->permt.kind != 0; }
+    J.kappa = c->perm.kind ? 1.0 : c->mat.k_over_mu;
+    J.perm_kind = c->perm.kind;
+    if (c->perm.kind && q1_stencil(c)) { J.kap = c->perm.lattice.p; J.kap_ncomp = c->perm.ncomp; }
     J.val = c->Jp.p;
     J.dinv = c->dinv_J.p;
     J.ilu = &c->ilu_J;
@@ -996,7 +996,7 @@ int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *
     bool direct_first = false;
     if (prec == PORO_PREC_FDM) {
       static const bool iterative = std::getenv("PORO_PRES_ITERATIVE") != nullptr;
-      direct_first = !iterative && opts->stop_rule == PORO_STOP_RHS && q1_stencil(c) && perm_kind(c) != 2;   // (a general field: the layer means precondition CG, never a direct solve)
+      direct_first = !iterative && opts->stop_rule == PORO_STOP_RHS && q1_stencil(c) && c->perm.kind != 2;   // (a general field: the layer means precondition CG, never a direct solve)
     }
     return solve_q1(c, J, opts, info, direct_first);
   });

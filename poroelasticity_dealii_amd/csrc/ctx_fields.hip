@@ -1,5 +1,5 @@
-// The per-cell coefficient fields of a context: k / mu of the pressure system (poro_ctx_set / get_cell_permeability), its diagonal tensor diag(kx, ky[, kz]) / mu
-// (poro_ctx_set / get_cell_permeability_tensor; a context holds one of the two) and Lame lambda, shear G of the displacement system
+// The per-cell coefficient fields of a context: k / mu of the pressure system (poro_ctx_set / get_cell_permeability) or its diagonal tensor diag(kx, ky[, kz]) / mu
+// (poro_ctx_set / get_cell_permeability_tensor) - one field, c->perm, of 1 or dim components - and Lame lambda, shear G of the displacement system
 // (poro_ctx_set / get_cell_moduli).  What they share - the refusals, the caller's cell order -> lattice order, the classification by layers, the host state - is
 // cell_field.hpp; each setter adds its value checks, its device state and what it invalidates.  A setter that throws leaves the context as it was: the device state
 // changes first, then the host state, then the caches go
@@ -22,10 +22,11 @@ std::vector<int32_t> download_cell_dofs_p(poro_ctx *c) {
   return dofs;
 }
 // F takes the arrays; on boxes and tensor-product grids (c->lines) it classifies them on the lattice - dofs: cell_dofs_p - and the lattice-ordered copies come back
-template <int N> std::array<std::vector<double>, N> take(const poro_ctx *c, CellField<N> &F, const double *const (&comp)[N], const std::vector<int32_t> &dofs, const char *who) {
-  if (!c->lines.on) return F.set(comp, c->n_cells);
+// used: the components that are taken (CellField::set)
+template <int N> std::array<std::vector<double>, N> take(const poro_ctx *c, CellField<N> &F, const double *const (&comp)[N], const std::vector<int32_t> &dofs, const char *who, int used = N) {
+  if (!c->lines.on) return F.set(comp, c->n_cells, nullptr, 0, nullptr, used);
   const std::vector<int64_t> order = cell_lattice_order(c->dim, c->lines.n, dofs.data(), c->nv, c->n_cells, who);      // (lines.n is 1 beyond dim)
-  return F.set(comp, c->n_cells, &order, c->dim, c->lines.n);
+  return F.set(comp, c->n_cells, &order, c->dim, c->lines.n, used);
 }
 // the getters: *kind always; the arrays that are asked for (out[a] != null) while a field is set
 template <class Field, int N> int give(poro_ctx *c, Field poro_ctx::*field, double *const (&out)[N], int64_t n, int32_t *kind, const std::string &who, const char *name) {
@@ -38,101 +39,79 @@ template <class Field, int N> int give(poro_ctx *c, Field poro_ctx::*field, doub
   });
 }
 
-// Kp = sum_c w_c K_c over the coloured cell loop (w == null: the plain Laplace matrix, bit for bit what setup() assembled: same kernel, same order)
-// wt ([n_cells][dim], instead of w): the diagonal tensor's weights
-void assemble_laplace_p(poro_ctx *c, const double *w, const double *wt = nullptr) {
+// Kp = K_kappa over the coloured cell loop, w = [n_cells][ncomp] weights (w == null: the plain Laplace matrix, bit for bit what setup() assembled: same kernel, same order)
+void assemble_laplace_p(poro_ctx *c, const double *w, int ncomp = 1) {
   hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
   c->Kp.zero(s);
-  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_matrices(s, a, cells, n_cells, c->Ap.rp.p, c->Ap.col.p, nullptr, c->Kp.p, nullptr, w, wt); });
+  for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_matrices(s, a, cells, n_cells, c->Ap.rp.p, c->Ap.col.p, nullptr, c->Kp.p, nullptr, w, ncomp); });
 }
-// The pressure system holds the scalar field (perm) or the diagonal tensor (permt): what the two setters share.  Both caches of line pivots go with every change
+// what goes with every change of the pressure system's field, the caches of line pivots among it
 void invalidate_pressure(poro_ctx *c) {
   c->jac_dt = -1; c->ilu_J_valid = false;
   for (auto &L : c->perm.line) { L.built = false; L.a = -1; }
-  for (auto &L : c->permt.line) { L.built = false; L.a = -1; }
 }
-void drop_scalar(poro_ctx *c) { c->perm.clear(); c->perm.cell.release(); c->perm.lattice.release(); }
-void drop_tensor(poro_ctx *c) { c->permt.clear(); c->permt.cell.release(); c->permt.lattice.release(); }
 // NULL to either setter: back to poro_material.k_over_mu, the plain Laplace matrix bit for bit
 int back_to_constant(poro_ctx *c) {
-  if (!perm_kind(c)) return 0;
+  poro_ctx::Perm &P = c->perm;
+  if (!P.kind) return 0;
   assemble_laplace_p(c, nullptr);
-  drop_scalar(c); drop_tensor(c);
+  P.clear(); P.ncomp = 0; P.cell.release(); P.lattice.release();
   invalidate_pressure(c);
   return 0;
+}
+// The two setters: k_over_mu is [n_cells][ncomp], ncomp = 1 (one k / mu per cell) or dim (diag(kx, ky[, kz]) / mu, x first); `who` names the entry point in the refusals
+int set_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells, int ncomp, const std::string &who) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    if (!k_over_mu) return back_to_constant(c);
+    refuse_partitioned(c, who);
+    check_count(c, who, "n_cells", n_cells);
+    std::vector<double> comp[3];
+    for (int d = 0; d < ncomp; ++d) comp[d].resize((size_t)n_cells);
+    for (int64_t i = 0; i < n_cells; ++i)
+      for (int d = 0; d < ncomp; ++d) {
+        const double v = comp[d][(size_t)i] = k_over_mu[i * ncomp + d];
+        if (!(std::isfinite(v) && v > 0)) throw Error(who + ": " + (ncomp > 1 ? "component " + std::to_string(d) + " of cell " : "value of cell ") + std::to_string(i) + " is not finite and > 0");
+      }
+    CellField<3> F;
+    const auto lattice = take(c, F, {comp[0].data(), comp[1].data(), comp[2].data()}, c->lines.on ? download_cell_dofs_p(c) : std::vector<int32_t>(), who.c_str(), ncomp);
+    poro_ctx::Perm &P = c->perm;
+    P.cell.upload(k_over_mu, (size_t)n_cells * ncomp);
+    if (c->box.enabled && c->lines.on) {
+      std::vector<double> planes; planes.reserve((size_t)n_cells * ncomp);
+      for (int d = 0; d < ncomp; ++d) planes.insert(planes.end(), lattice[d].begin(), lattice[d].end());
+      P.lattice.upload(planes);
+    } else P.lattice.release();
+    assemble_laplace_p(c, P.cell.p, ncomp);
+    static_cast<CellField<3> &>(P) = std::move(F); P.ncomp = ncomp;
+    invalidate_pressure(c);
+    return 0;
+  });
 }
 }  // namespace
 
 extern "C" {
 
-int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) {
-  return guarded([&] {
-    if (!c) throw Error("null argument");
-    PORO_HIP(hipSetDevice(c->device));
-    poro_ctx::Perm &P = c->perm;
-    if (!k_over_mu) return back_to_constant(c);
-    refuse_partitioned(c, "poro_ctx_set_cell_permeability");
-    check_count(c, "poro_ctx_set_cell_permeability", "n_cells", n_cells);
-    for (int64_t i = 0; i < n_cells; ++i)
-      if (!(std::isfinite(k_over_mu[i]) && k_over_mu[i] > 0)) throw Error("poro_ctx_set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
-    CellField<1> F;
-    const auto lattice = take(c, F, {k_over_mu}, c->lines.on ? download_cell_dofs_p(c) : std::vector<int32_t>(), "poro_ctx_set_cell_permeability");
-    P.cell.upload(F.host[0]);
-    if (c->box.enabled && c->lines.on) P.lattice.upload(lattice[0]); else P.lattice.release();
-    assemble_laplace_p(c, P.cell.p);
-    static_cast<CellField<1> &>(P) = std::move(F);
-    drop_tensor(c);
-    invalidate_pressure(c);
-    return 0;
-  });
-}
+int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) { return set_permeability(c, k_over_mu, n_cells, 1, "poro_ctx_set_cell_permeability"); }
 int poro_ctx_get_cell_permeability(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) {
-  if (c && kind && c->permt.kind)      // a tensor is set: its kind; the values belong to the other getter
+  if (c && kind && c->perm.ncomp > 1)      // a tensor is set: its kind; the values belong to the other getter
     return guarded([&] {
-      *kind = c->permt.kind;
+      *kind = c->perm.kind;
       if (out) throw Error("poro_ctx_get_cell_permeability: a permeability tensor is set, its values come from poro_ctx_get_cell_permeability_tensor");
       return 0;
     });
-  return give(c, &poro_ctx::perm, {out}, n_cells, kind, "poro_ctx_get_cell_permeability", "n_cells");
+  return give(c, &poro_ctx::perm, {out, (double *)nullptr, (double *)nullptr}, n_cells, kind, "poro_ctx_get_cell_permeability", "n_cells");
 }
 
-// Per-cell diagonal tensor diag(kx, ky[, kz]) / mu, k_over_mu[cell][component], x first.  The field is CellField<3> on every context; a 2D context classifies its second
-// component in the third slot once more, which changes nothing, and never reads it
-int poro_ctx_set_cell_permeability_tensor(poro_ctx *c, const double *k_over_mu, int64_t n_cells) {
-  return guarded([&] {
-    if (!c) throw Error("null argument");
-    PORO_HIP(hipSetDevice(c->device));
-    if (!k_over_mu) return back_to_constant(c);
-    const char *who = "poro_ctx_set_cell_permeability_tensor"; const int dim = c->dim;
-    refuse_partitioned(c, who);
-    check_count(c, who, "n_cells", n_cells);
-    for (int64_t i = 0; i < n_cells; ++i)
-      for (int d = 0; d < dim; ++d)
-        if (!(std::isfinite(k_over_mu[i * dim + d]) && k_over_mu[i * dim + d] > 0))
-          throw Error(std::string(who) + ": component " + std::to_string(d) + " of cell " + std::to_string(i) + " is not finite and > 0");
-    std::vector<double> comp[3];
-    for (int d = 0; d < 3; ++d) { comp[d].resize((size_t)n_cells); for (int64_t i = 0; i < n_cells; ++i) comp[d][(size_t)i] = k_over_mu[i * dim + std::min(d, dim - 1)]; }
-    CellField<3> F;
-    const auto lattice = take(c, F, {comp[0].data(), comp[1].data(), comp[2].data()}, c->lines.on ? download_cell_dofs_p(c) : std::vector<int32_t>(), who);
-    poro_ctx::PermTensor &P = c->permt;
-    P.cell.upload(k_over_mu, (size_t)n_cells * dim);
-    if (c->box.enabled && c->lines.on) {
-      std::vector<double> planes; planes.reserve((size_t)n_cells * dim);
-      for (int d = 0; d < dim; ++d) planes.insert(planes.end(), lattice[d].begin(), lattice[d].end());
-      P.lattice.upload(planes);
-    } else P.lattice.release();
-    assemble_laplace_p(c, nullptr, P.cell.p);
-    static_cast<CellField<3> &>(P) = std::move(F);
-    drop_scalar(c);
-    invalidate_pressure(c);
-    return 0;
-  });
-}
+// Per-cell diagonal tensor diag(kx, ky[, kz]) / mu, k_over_mu[cell][component], x first
+int poro_ctx_set_cell_permeability_tensor(poro_ctx *c, const double *k_over_mu, int64_t n_cells) { return set_permeability(c, k_over_mu, n_cells, c ? c->dim : 0, "poro_ctx_set_cell_permeability_tensor"); }
 int poro_ctx_get_cell_permeability_tensor(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) {
-  if (!c || !out || !c->permt.kind) return give(c, &poro_ctx::permt, {(double *)nullptr, (double *)nullptr, (double *)nullptr}, n_cells, kind, "poro_ctx_get_cell_permeability_tensor", "n_cells");
+  if (c && kind && c->perm.ncomp == 1) { *kind = 0; return 0; }      // one k / mu per cell is set: no tensor
+  if (!c || !out || !c->perm.kind) return give(c, &poro_ctx::perm, {(double *)nullptr, (double *)nullptr, (double *)nullptr}, n_cells, kind, "poro_ctx_get_cell_permeability_tensor", "n_cells");
   std::vector<double> comp[3]; const int dim = c->dim;
   for (int d = 0; d < dim; ++d) comp[d].resize((size_t)std::max<int64_t>(n_cells, c->n_cells));
-  const int rc = give(c, &poro_ctx::permt, {comp[0].data(), comp[1].data(), dim == 3 ? comp[2].data() : (double *)nullptr}, n_cells, kind, "poro_ctx_get_cell_permeability_tensor", "n_cells");
+  const int rc = give(c, &poro_ctx::perm, {comp[0].data(), comp[1].data(), dim == 3 ? comp[2].data() : (double *)nullptr}, n_cells, kind, "poro_ctx_get_cell_permeability_tensor", "n_cells");
   if (rc == 0) for (int64_t i = 0; i < n_cells; ++i) for (int d = 0; d < dim; ++d) out[i * dim + d] = comp[d][(size_t)i];
   return rc;
 }

@@ -206,20 +206,21 @@ void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *
 void fdm_precondition_p_layered(poro_ctx *c, double a, const double *g, double *z, Q1Set which) {
   Timed tm(c, "precondition_p_fdm_layered");
   const bool fixed = which == Q1Set::fixed_ends; const int last = c->dim - 1, nl = c->lines.n[last] + 1;
-  if (!perm_kind(c) || c->comm.multi()) throw Error("fdm_precondition_p_layered: needs a per-cell permeability on a single-rank context");
+  poro_ctx::Perm &P = c->perm;
+  if (!P.kind || c->comm.multi()) throw Error("fdm_precondition_p_layered: needs a per-cell permeability on a single-rank context");
   FdmQ1 &T = q1_set(c, which);
-  const bool tensor = c->permt.kind != 0;      // a diagonal tensor: one weighted mass line per leading direction (k_q1_line_*_tensor)
-  poro_ctx::Perm::Line &L = tensor ? c->permt.line[fixed ? 1 : 0] : c->perm.line[fixed ? 1 : 0];
+  const int nw = P.ncomp == 1 ? 1 : last;      // weighted mass lines: one k / mu weights the one line of lam_x + lam_y, a diagonal tensor one line per leading direction
+  poro_ctx::Perm::Line &L = P.line[fixed ? 1 : 0];
   if (!L.built) {
     L.lo = fixed && c->pdir_face[last][0]; L.hi = fixed && c->pdir_face[last][1];
-    L.coef.upload(tensor ? perm_tensor_line_coefficients(c->dim, c->lines.hcell[last], c->permt.layer, L.lo, L.hi) : perm_line_coefficients(c->lines.hcell[last], c->perm.layer[0], L.lo, L.hi));
+    L.coef.upload(perm_line_coefficients(c->lines.hcell[last], P.layer, nw, P.layer[P.ncomp - 1], L.lo, L.hi));
     if (L.inv.n != (size_t)c->n_p) L.inv.alloc(c->n_p);
     L.a = -1; L.built = true;
   }
-  if (L.a != a) { (tensor ? q1_line_factor_tensor : q1_line_factor)(c->stream, c->dim, T.nodal, nl, a, L.coef.p, L.inv.p); L.a = a; }
+  if (L.a != a) { q1_line_factor(c->stream, c->dim, nw, T.nodal, nl, a, L.coef.p, L.inv.p); L.a = a; }
   // 5 launches in 3D, 3 in 2D
   hipStream_t s = c->stream; const FdmScalar &F = T.nodal; const int n0 = F.dir[0].n, n1 = F.dir[1].n; double *t1 = c->fdm_t1.p, *t2 = c->fdm_t2.p;
-  auto lines = [&](const double *in, double *out) { Timed tl(c, "q1_line_solve"); (tensor ? q1_line_solve_tensor : q1_line_solve)(s, c->dim, F, nl, a, L.lo, L.hi, L.coef.p, L.inv.p, in, out); };
+  auto lines = [&](const double *in, double *out) { Timed tl(c, "q1_line_solve"); q1_line_solve(s, c->dim, nw, F, nl, a, L.lo, L.hi, L.coef.p, L.inv.p, in, out); };
   if (c->dim == 2) {
     fdm_transform(s, F.dir[0].St.p, n0, 1, nl, g, t1, nullptr);
     lines(t1, t2);
@@ -587,7 +588,7 @@ const char *prec_refusal(poro_ctx *c, int which_system, int prec, bool solving) 
   }
   if (which_system != 1 && which_system != 2) return "unknown system (0 displacement, 1 pressure, 2 projection)";
   // a per-cell k / mu (poro_ctx_set_cell_permeability): the coarse box of the two-level form is a constant-coefficient context
-  if (which_system == 1 && perm_kind(c) && prec == PORO_PREC_TWO_LEVEL)
+  if (which_system == 1 && c->perm.kind && prec == PORO_PREC_TWO_LEVEL)
     return "PORO_PREC_TWO_LEVEL (pressure): not available while a per-cell permeability is set - the coarse box is a constant-coefficient context (PORO_PREC_JACOBI / NONE / ILU0 / SSOR everywhere, PORO_PREC_FDM on boxes and tensor-product grids)";
   if (which_system == 1 && (c->cons_p.n || c->n_pdir)) {
     // hanging rows: the two-level form.  Prescribed rows: two-level where the coarse box carries the condition as whole faces (two_level_supported_pj), the

@@ -258,10 +258,10 @@ template <int DIM> __global__ void k_asm_u_neumann(AsmArgs a, int64_t n_group, c
 // ---- K-asm-p + K-src-p: Q1 mass / Laplace matrices and the well source integral (one wave per cell) -----------
 template <int DIM, bool TENSOR> __global__ void __launch_bounds__(64)
 k_asm_p(AsmArgs a, const int32_t *__restrict__ cells, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, double *__restrict__ M,
-        double *__restrict__ K, double *__restrict__ src, const double *__restrict__ cell_w, const double *__restrict__ cell_wt) {
-  // TENSOR (cell_wt, poro_ctx_set_cell_permeability_tensor): as cell_w, with one weight per global axis inside the gradient product.  A template switch, so that the
-  // instance without it is compiled from the code it always had: the scalar-weight and no-weight branches stay bit for bit
+        double *__restrict__ K, double *__restrict__ src, const double *__restrict__ cell_w) {
   // cell_w != null (poro_ctx_set_cell_permeability): K alone is assembled, every cell's Laplace entries times its weight - K_kappa = sum_c kappa_c K_c; M and src stay as they are
+  // TENSOR (cell_w is [n_cells][DIM], poro_ctx_set_cell_permeability_tensor): the same with one weight per global axis inside the gradient product.  A template switch, so
+  // that the instance without it is compiled from the code it always had: the scalar-weight and no-weight branches stay bit for bit
   constexpr int NV = 1 << DIM;
   __shared__ double sG[NV * NV * DIM];   // [q][v][d]
   __shared__ double sJi[NV * DIM * DIM];
@@ -296,7 +296,7 @@ k_asm_p(AsmArgs a, const int32_t *__restrict__ cells, const int64_t *__restrict_
       double kt = 0;
       for (int q = 0; q < nq; ++q) {
         double wdot = 0;
-        for (int c = 0; c < DIM; ++c) wdot += cell_wt[cell * DIM + c] * (sG[(q * NV + i) * DIM + c] * sG[(q * NV + j) * DIM + c]);
+        for (int c = 0; c < DIM; ++c) wdot += cell_w[cell * DIM + c] * (sG[(q * NV + i) * DIM + c] * sG[(q * NV + j) * DIM + c]);
         kt += wdot * sJxW[q];
       }
       const int32_t rt = sDof[i];
@@ -421,14 +421,10 @@ void asm_u_neumann(hipStream_t s, const AsmArgs &a, const int32_t *order, const 
                       hipLaunchKernelGGL(k_asm_u_neumann<3>, grid, 64, 0, s, a, n, o, bc, bl, bi, n_neu, label, comp, value, rhs));
   }
 }
-void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const int64_t *rp, const int32_t *col, double *M, double *K, double *src, const double *cell_w, const double *cell_wt) {
+void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const int64_t *rp, const int32_t *col, double *M, double *K, double *src, const double *cell_w, int ncomp) {
   if (!n) return;
-  if (cell_wt) {
-    if (M || src || cell_w) throw Error("asm_p_matrices: the tensor weights assemble K alone");
-    PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL((k_asm_p<2, true>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w, cell_wt), hipLaunchKernelGGL((k_asm_p<3, true>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w, cell_wt));
-    return;
-  }
-  PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL((k_asm_p<2, false>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w, cell_wt), hipLaunchKernelGGL((k_asm_p<3, false>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w, cell_wt));
+  if (cell_w && ncomp != 1) PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL((k_asm_p<2, true>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w), hipLaunchKernelGGL((k_asm_p<3, true>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w));
+  else PORO_DIM_DISPATCH(a.dim, hipLaunchKernelGGL((k_asm_p<2, false>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w), hipLaunchKernelGGL((k_asm_p<3, false>), (unsigned)n, 64, 0, s, a, cells, rp, col, M, K, src, cell_w));
 }
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n, const double *u, int n_comp, const int32_t *comps, double *const *rhs) {
   if (!n || !n_comp) return;

@@ -148,111 +148,55 @@ __global__ void __launch_bounds__(256) k_fdm_window_batch(double *grid, double *
   }
 }
 
-// ---- layered coefficient (poro_ctx_set_cell_permeability, kappa = kappa(slowest direction)): the line solve between the x / y transforms --------------------------
-// J = a Mx(x)My(x)Mz + Kx(x)My(x)Mz^k + Mx(x)Ky(x)Mz^k + Mx(x)My(x)Kz^k.  Mz, Mz^k, Kz^k have no common eigenvectors, but x and y keep theirs, and what is left per mode
-// (p, q) is one SPD tridiagonal system along the slowest direction:  (a Mz + Kz^k + (lam_x[p] + lam_y[q]) Mz^k) t = r.
-// One lane per column (p, q): consecutive lanes touch consecutive addresses of a plane.  coef = the six 1D arrays [md | mo | wd | wo | kd | ko], nl entries each: diagonal and
-// off-diagonal (entry k couples k and k + 1) of Mz, Mz^k, Kz^k; they depend on the loop index alone, so the compiler fetches them with uniform loads.  A prescribed end
-// face is an identity row in coef (the host builder) and a zero right-hand side here.
+// ---- layered per-cell coefficient (poro_ctx_set_cell_permeability[_tensor], constant within every cell layer of the slowest direction): the line solve between the x / y transforms
+// J = a Mx(x)My(x)Mz + Kx(x)My(x)Mz^kx + Mx(x)Ky(x)Mz^ky + Mx(x)My(x)Kz^kz.  Mz, Mz^k, Kz^k have no common eigenvectors, but x and y keep theirs, and what is left per mode
+// (p, q) is one SPD tridiagonal system along the slowest direction:  (a Mz + lam_x[p] Mz^kx + lam_y[q] Mz^ky + Kz^kz) t = r  (2D: (a My + lam_x[p] My^kx + Ky^ky) t = r).
+// NW = the number of weighted mass lines: 2 for a diagonal tensor in 3D; 1 in 2D and for one k / mu per cell, where kx = ky and the single multiplier is
+// sigma = lam_x[p] + lam_y[q].
+// One lane per column (p, q): consecutive lanes touch consecutive addresses of a plane.  coef = the 1D arrays [md | mo | w0d | w0o | (w1d | w1o) | kd | ko]
+// (perm_line_coefficients), nl entries each: diagonal and off-diagonal (entry k couples k and k + 1) of Mz, the Mz^k, Kz^k; they depend on the loop index alone, so the
+// compiler fetches them with uniform loads.  A prescribed end face is an identity row in coef (the host builder) and a zero right-hand side here.
 // A column of a mode that the fixed-ends tables removed (eigenvalue stored as 1e300, see upload_dir) is not solved: it returns exactly 0, and its pivots are those of sigma = 0,
 // so that nothing of the size kappa h 1e300 is ever formed.
 struct LineCols { const double *lam0, *lam1; int n0; int64_t ncol; };          // lam1 == null: 2D (columns = the x modes)
-template <int DIM> __device__ __forceinline__ bool line_sigma(const LineCols &L, int64_t col, double &sigma) {
+template <int DIM, int NW> __device__ __forceinline__ bool line_sigma(const LineCols &L, int64_t col, double (&sigma)[NW]) {
   const int i = (int)(col % L.n0); const int64_t j = col / L.n0;
   double l1 = 0.0;
   if constexpr (DIM == 3) l1 = L.lam1[j];
   const double l0 = L.lam0[i];
   const bool removed = !(l0 < 1e300) || !(l1 < 1e300);
-  sigma = removed ? 0.0 : l0 + l1;
+  if constexpr (NW == 1) sigma[0] = removed ? 0.0 : l0 + l1;
+  else { sigma[0] = removed ? 0.0 : l0; sigma[1] = removed ? 0.0 : l1; }
   return removed;
 }
+// entry k of the line matrix's diagonal (arr = 0) or off-diagonal (arr = 1; couples k and k + 1, entry nl - 1 is 0 and unused)
+template <int NW> __device__ __forceinline__ double line_entry(const double *__restrict__ coef, int nl, int arr, int k, double a, const double (&sigma)[NW]) {
+  const double *m = coef + (size_t)arr * nl, *w = m + 2 * (size_t)nl, *kk = m + 2 * (size_t)(NW + 1) * nl;
+  double v = fma(sigma[0], w[k], fma(a, m[k], kk[k]));
+  if constexpr (NW == 2) v = fma(sigma[1], (w + 2 * (size_t)nl)[k], v);
+  return v;
+}
 // reciprocal pivots of the Thomas elimination, inv[k * ncol + col]: they depend on a = 1 / (M_b dt) and the mesh alone, so they are computed once per dt
-template <int DIM> __global__ void __launch_bounds__(64)
+template <int DIM, int NW> __global__ void __launch_bounds__(64)
 k_q1_line_factor(LineCols L, int nl, double a, const double *__restrict__ coef, double *__restrict__ inv) {
   const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= L.ncol) return;
-  double sigma; (void)line_sigma<DIM>(L, col, sigma);
-  const double *md = coef, *mo = coef + nl, *wd = coef + 2 * nl, *wo = coef + 3 * nl, *kd = coef + 4 * nl, *ko = coef + 5 * nl;
+  double sigma[NW]; (void)line_sigma<DIM, NW>(L, col, sigma);
   double ip = 0, off = 0;
   for (int k = 0; k < nl; ++k) {
-    const double d = fma(sigma, wd[k], fma(a, md[k], kd[k])) - off * off * ip;
+    const double d = line_entry<NW>(coef, nl, 0, k, a, sigma) - off * off * ip;
     ip = 1.0 / d;
     inv[(int64_t)k * L.ncol + col] = ip;
-    off = fma(sigma, wo[k], fma(a, mo[k], ko[k]));          // couples k and k + 1 (entry nl - 1 is 0 and unused)
+    off = line_entry<NW>(coef, nl, 1, k, a, sigma);
   }
 }
 // out = T^-1 in, both [k * ncol + col] (in != out, so that the loads of the forward sweep run ahead of its stores); no division, no scratch: one forward and one backward sweep with the cached reciprocal pivots
-template <int DIM> __global__ void __launch_bounds__(64)
+template <int DIM, int NW> __global__ void __launch_bounds__(64)
 k_q1_line_solve(LineCols L, int nl, double a, int fixed_lo, int fixed_hi, const double *__restrict__ coef, const double *__restrict__ inv, const double *__restrict__ in, double *__restrict__ out) {
   const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= L.ncol) return;
-  double sigma;
-  if (line_sigma<DIM>(L, col, sigma)) {
-    for (int k = 0; k < nl; ++k) out[(int64_t)k * L.ncol + col] = 0.0;
-    return;
-  }
-  const double *mo = coef + nl, *wo = coef + 3 * nl, *ko = coef + 5 * nl;
-  double t = 0, off = 0;           // t = y_{k-1} / pivot_{k-1}
-#pragma unroll 4
-  for (int k = 0; k < nl; ++k) {
-    const int64_t at = (int64_t)k * L.ncol + col;
-    const bool fixed = (k == 0 && fixed_lo) || (k == nl - 1 && fixed_hi);
-    const double r = fixed ? 0.0 : in[at];
-    const double y = fma(-off, t, r);
-    out[at] = y;
-    t = y * inv[at];
-    off = fma(sigma, wo[k], fma(a, mo[k], ko[k]));
-  }
-  double x = t;                    // x_{nl-1}
-  out[(int64_t)(nl - 1) * L.ncol + col] = x;
-#pragma unroll 4
-  for (int k = nl - 2; k >= 0; --k) {
-    const int64_t at = (int64_t)k * L.ncol + col;
-    off = fma(sigma, wo[k], fma(a, mo[k], ko[k]));
-    x = fma(-off, x, out[at]) * inv[at];
-    out[at] = x;
-  }
-}
-
-// ---- layered diagonal tensor (poro_ctx_set_cell_permeability_tensor): J = a Mx(x)My(x)Mz + Kx(x)My(x)Mz^kx + Mx(x)Ky(x)Mz^ky + Mx(x)My(x)Kz^kz -----------------------------
-// The one sigma = lam_x + lam_y above becomes one multiplier per leading direction, each on its own weighted mass line:  (a Mz + lam_x[p] Mz^kx + lam_y[q] Mz^ky + Kz^kz) t = r
-// (2D: (a My + lam_x[p] My^kx + Ky^ky) t = r).  coef = [md | mo | w0d | w0o | (w1d | w1o) | kd | ko] (perm_tensor_line_coefficients).  Everything else is k_q1_line_factor /
-// k_q1_line_solve: one lane per column, cached reciprocal pivots, no division in the sweeps, identity rows on prescribed ends, exact zeros for removed modes
-template <int DIM> __device__ __forceinline__ bool line_sigma2(const LineCols &L, int64_t col, double &s0, double &s1) {
-  const int i = (int)(col % L.n0); const int64_t j = col / L.n0;
-  double l1 = 0.0;
-  if constexpr (DIM == 3) l1 = L.lam1[j];
-  const double l0 = L.lam0[i];
-  const bool removed = !(l0 < 1e300) || !(l1 < 1e300);
-  s0 = removed ? 0.0 : l0; s1 = removed ? 0.0 : l1;
-  return removed;
-}
-// entry k of the line matrix's diagonal (arr = 0) or off-diagonal (arr = 1)
-template <int DIM> __device__ __forceinline__ double line_entry_tensor(const double *__restrict__ coef, int nl, int arr, int k, double a, double s0, double s1) {
-  const double *m = coef + (size_t)arr * nl, *w0 = m + 2 * (size_t)nl, *kk = m + 2 * (size_t)DIM * nl;
-  double v = fma(s0, w0[k], fma(a, m[k], kk[k]));
-  if constexpr (DIM == 3) v = fma(s1, (w0 + 2 * (size_t)nl)[k], v);
-  return v;
-}
-template <int DIM> __global__ void __launch_bounds__(64)
-k_q1_line_factor_tensor(LineCols L, int nl, double a, const double *__restrict__ coef, double *__restrict__ inv) {
-  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= L.ncol) return;
-  double s0, s1; (void)line_sigma2<DIM>(L, col, s0, s1);
-  double ip = 0, off = 0;
-  for (int k = 0; k < nl; ++k) {
-    const double d = line_entry_tensor<DIM>(coef, nl, 0, k, a, s0, s1) - off * off * ip;
-    ip = 1.0 / d;
-    inv[(int64_t)k * L.ncol + col] = ip;
-    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
-  }
-}
-template <int DIM> __global__ void __launch_bounds__(64)
-k_q1_line_solve_tensor(LineCols L, int nl, double a, int fixed_lo, int fixed_hi, const double *__restrict__ coef, const double *__restrict__ inv, const double *__restrict__ in, double *__restrict__ out) {
-  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= L.ncol) return;
-  double s0, s1;
-  if (line_sigma2<DIM>(L, col, s0, s1)) {
+  double sigma[NW];
+  if (line_sigma<DIM, NW>(L, col, sigma)) {
     for (int k = 0; k < nl; ++k) out[(int64_t)k * L.ncol + col] = 0.0;
     return;
   }
@@ -265,44 +209,35 @@ k_q1_line_solve_tensor(LineCols L, int nl, double a, int fixed_lo, int fixed_hi,
     const double y = fma(-off, t, r);
     out[at] = y;
     t = y * inv[at];
-    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
+    off = line_entry<NW>(coef, nl, 1, k, a, sigma);
   }
   double x = t;                    // x_{nl-1}
   out[(int64_t)(nl - 1) * L.ncol + col] = x;
 #pragma unroll 4
   for (int k = nl - 2; k >= 0; --k) {
     const int64_t at = (int64_t)k * L.ncol + col;
-    off = line_entry_tensor<DIM>(coef, nl, 1, k, a, s0, s1);
+    off = line_entry<NW>(coef, nl, 1, k, a, sigma);
     x = fma(-off, x, out[at]) * inv[at];
     out[at] = x;
   }
 }
+LineCols line_cols(int dim, const FdmScalar &F) { return {F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n}; }
 
 }  // namespace
 
-void q1_line_factor_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv) {
-  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
+void q1_line_factor(hipStream_t s, int dim, int nw, const FdmScalar &F, int nl, double a, const double *coef, double *inv) {
+  const LineCols L = line_cols(dim, F);
   const unsigned grid = (unsigned)((L.ncol + 63) / 64);
-  if (dim == 2) hipLaunchKernelGGL(k_q1_line_factor_tensor<2>, grid, 64, 0, s, L, nl, a, coef, inv);
-  else hipLaunchKernelGGL(k_q1_line_factor_tensor<3>, grid, 64, 0, s, L, nl, a, coef, inv);
+  if (dim == 2) hipLaunchKernelGGL((k_q1_line_factor<2, 1>), grid, 64, 0, s, L, nl, a, coef, inv);
+  else if (nw == 1) hipLaunchKernelGGL((k_q1_line_factor<3, 1>), grid, 64, 0, s, L, nl, a, coef, inv);
+  else hipLaunchKernelGGL((k_q1_line_factor<3, 2>), grid, 64, 0, s, L, nl, a, coef, inv);
 }
-void q1_line_solve_tensor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out) {
-  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
+void q1_line_solve(hipStream_t s, int dim, int nw, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out) {
+  const LineCols L = line_cols(dim, F);
   const unsigned grid = (unsigned)((L.ncol + 63) / 64);
-  if (dim == 2) hipLaunchKernelGGL(k_q1_line_solve_tensor<2>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
-  else hipLaunchKernelGGL(k_q1_line_solve_tensor<3>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
-}
-void q1_line_factor(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, const double *coef, double *inv) {
-  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
-  const unsigned grid = (unsigned)((L.ncol + 63) / 64);
-  if (dim == 2) hipLaunchKernelGGL(k_q1_line_factor<2>, grid, 64, 0, s, L, nl, a, coef, inv);
-  else hipLaunchKernelGGL(k_q1_line_factor<3>, grid, 64, 0, s, L, nl, a, coef, inv);
-}
-void q1_line_solve(hipStream_t s, int dim, const FdmScalar &F, int nl, double a, bool fixed_lo, bool fixed_hi, const double *coef, const double *inv, const double *in, double *out) {
-  const LineCols L{F.dir[0].lam.p, dim == 3 ? F.dir[1].lam.p : nullptr, F.dir[0].n, dim == 3 ? (int64_t)F.dir[0].n * F.dir[1].n : (int64_t)F.dir[0].n};
-  const unsigned grid = (unsigned)((L.ncol + 63) / 64);
-  if (dim == 2) hipLaunchKernelGGL(k_q1_line_solve<2>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
-  else hipLaunchKernelGGL(k_q1_line_solve<3>, grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
+  if (dim == 2) hipLaunchKernelGGL((k_q1_line_solve<2, 1>), grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
+  else if (nw == 1) hipLaunchKernelGGL((k_q1_line_solve<3, 1>), grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
+  else hipLaunchKernelGGL((k_q1_line_solve<3, 2>), grid, 64, 0, s, L, nl, a, fixed_lo ? 1 : 0, fixed_hi ? 1 : 0, coef, inv, in, out);
 }
 void fdm_window_batch(hipStream_t s, double *grid, double *dense, double *dense_self, int self, bool to_block, const FdmWindow *win, int n_peers, int n_planes_pad, int64_t C, int64_t grid_stride, int64_t blk) {
   const int64_t n = (int64_t)n_planes_pad * C;

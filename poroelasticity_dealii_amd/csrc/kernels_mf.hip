@@ -224,65 +224,48 @@ void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double
   else hipLaunchKernelGGL(k_p_stencil<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kappa, x, y);
 }
 
-// ---- the same two kernels with a per-cell coefficient (poro_ctx_set_cell_permeability): y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q); kap in lattice cell order
-template <int DIM> __global__ void __launch_bounds__(256)
-k_p_stencil_var(int n0, int n1, int n2, double h0, double h1, double h2, double a, const double *__restrict__ kap, const double *__restrict__ x, double *__restrict__ y) {
+// ---- the same two kernels with a per-cell coefficient: y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q); kap = NK planes of lattice-ordered weights, NK = 1
+// (poro_ctx_set_cell_permeability) or DIM (poro_ctx_set_cell_permeability_tensor)
+template <int DIM, int NK> __global__ void __launch_bounds__(256)
+k_p_stencil_cells(int n0, int n1, int n2, double h0, double h1, double h2, double a, const double *__restrict__ kap, const double *__restrict__ x, double *__restrict__ y) {
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= (int64_t)n0 * n1 * n2) return;
-  PStencilTaps<DIM> T; PStencilCells<DIM> C;
-  p_stencil_load<DIM>(n0, n1, n2, node, x, T); p_stencil_load_cells<DIM>(n0, n1, n2, node, kap, C);
-  y[node] = p_stencil_sum_var<DIM>(n0, n1, n2, h0, h1, h2, a, node, T, C);
+  PStencilTaps<DIM> T; PStencilCells<DIM, NK> C;
+  p_stencil_load<DIM>(n0, n1, n2, node, x, T); p_stencil_load_cells<DIM, NK>(n0, n1, n2, node, kap, C);
+  y[node] = p_stencil_sum_cells<DIM, NK, true>(n0, n1, n2, h0, h1, h2, a, node, T, C);
 }
-template <int DIM> __global__ void __launch_bounds__(256)
-k_p_residual_stencil_var(int n0, int n1, int n2, double h0, double h1, double h2, const double *__restrict__ kap, const double *__restrict__ t, const double *__restrict__ p,
-                         const double *__restrict__ src, double *__restrict__ R) {
+template <int DIM, int NK> __global__ void __launch_bounds__(256)
+k_p_residual_stencil_cells(int n0, int n1, int n2, double h0, double h1, double h2, const double *__restrict__ kap, const double *__restrict__ t, const double *__restrict__ p,
+                           const double *__restrict__ src, double *__restrict__ R) {
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= (int64_t)n0 * n1 * n2) return;
-  PStencilTaps<DIM> Tt, Tp; PStencilCells<DIM> C;
-  p_stencil_load<DIM>(n0, n1, n2, node, t, Tt); p_stencil_load<DIM>(n0, n1, n2, node, p, Tp); p_stencil_load_cells<DIM>(n0, n1, n2, node, kap, C);
-  const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum_var<DIM>(n0, n1, n2, h0, h1, h2, 0.0, node, Tp, C);
+  PStencilTaps<DIM> Tt, Tp; PStencilCells<DIM, NK> C;
+  p_stencil_load<DIM>(n0, n1, n2, node, t, Tt); p_stencil_load<DIM>(n0, n1, n2, node, p, Tp); p_stencil_load_cells<DIM, NK>(n0, n1, n2, node, kap, C);
+  // K_kappa p alone.  The one-weight instance keeps the form it always had, the mass part with a = 0 (the same sum in exact arithmetic; its instructions stay as they were)
+  const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum_cells<DIM, NK, NK == 1>(n0, n1, n2, h0, h1, h2, 0.0, node, Tp, C);
   R[node] = -((s1 + s2) + src[node]);
 }
-// ---- and with a per-cell diagonal tensor (poro_ctx_set_cell_permeability_tensor): kap = DIM planes of lattice-ordered weights ---------------------------------------
-template <int DIM> __global__ void __launch_bounds__(256)
-k_p_stencil_tensor(int n0, int n1, int n2, double h0, double h1, double h2, double a, const double *__restrict__ kap, const double *__restrict__ x, double *__restrict__ y) {
-  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= (int64_t)n0 * n1 * n2) return;
-  PStencilTaps<DIM> T; PStencilCellsT<DIM> C;
-  p_stencil_load<DIM>(n0, n1, n2, node, x, T); p_stencil_load_cells_tensor<DIM>(n0, n1, n2, node, kap, C);
-  y[node] = p_stencil_sum_tensor<DIM, true>(n0, n1, n2, h0, h1, h2, a, node, T, C);
+// f(DIM, NK) for the instance of (dim, ncomp); ncomp is 1 or dim
+template <class F> void for_dim_ncomp(int dim, int ncomp, F f) {
+  using std::integral_constant;
+  if (ncomp != 1 && ncomp != dim) throw Error("per-cell pressure stencil: " + std::to_string(ncomp) + " components per cell in " + std::to_string(dim) + "D");
+  if (dim == 2) { if (ncomp == 1) f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); else f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); }
+  else if (ncomp == 1) f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
+  else f(integral_constant<int, 3>{}, integral_constant<int, 3>{});
 }
-template <int DIM> __global__ void __launch_bounds__(256)
-k_p_residual_stencil_tensor(int n0, int n1, int n2, double h0, double h1, double h2, const double *__restrict__ kap, const double *__restrict__ t, const double *__restrict__ p,
-                            const double *__restrict__ src, double *__restrict__ R) {
-  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= (int64_t)n0 * n1 * n2) return;
-  PStencilTaps<DIM> Tt, Tp; PStencilCellsT<DIM> C;
-  p_stencil_load<DIM>(n0, n1, n2, node, t, Tt); p_stencil_load<DIM>(n0, n1, n2, node, p, Tp); p_stencil_load_cells_tensor<DIM>(n0, n1, n2, node, kap, C);
-  const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum_tensor<DIM, false>(n0, n1, n2, h0, h1, h2, 0.0, node, Tp, C);
-  R[node] = -((s1 + s2) + src[node]);
-}
-void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, const double *t, const double *p, const double *src, double *R, bool tensor) {
+void p_residual_stencil_var(hipStream_t s, int dim, const BoxDev &box, const double *kap, int ncomp, const double *t, const double *p, const double *src, double *R) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const unsigned grid = (unsigned)(((int64_t)n0 * n1 * n2 + 255) / 256);
-  if (tensor) {
-    if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil_tensor<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kap, t, p, src, R);
-    else hipLaunchKernelGGL(k_p_residual_stencil_tensor<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kap, t, p, src, R);
-    return;
-  }
-  if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil_var<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kap, t, p, src, R);
-  else hipLaunchKernelGGL(k_p_residual_stencil_var<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kap, t, p, src, R);
+  for_dim_ncomp(dim, ncomp, [&](auto D, auto NK) {
+    hipLaunchKernelGGL((k_p_residual_stencil_cells<decltype(D)::value, decltype(NK)::value>), grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], dim == 3 ? box.h[2] : 1.0, kap, t, p, src, R);
+  });
 }
-void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, const double *x, double *y, bool tensor) {
+void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, int ncomp, const double *x, double *y) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const unsigned grid = (unsigned)(((int64_t)n0 * n1 * n2 + 255) / 256);
-  if (tensor) {
-    if (dim == 2) hipLaunchKernelGGL(k_p_stencil_tensor<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kap, x, y);
-    else hipLaunchKernelGGL(k_p_stencil_tensor<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kap, x, y);
-    return;
-  }
-  if (dim == 2) hipLaunchKernelGGL(k_p_stencil_var<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kap, x, y);
-  else hipLaunchKernelGGL(k_p_stencil_var<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kap, x, y);
+  for_dim_ncomp(dim, ncomp, [&](auto D, auto NK) {
+    hipLaunchKernelGGL((k_p_stencil_cells<decltype(D)::value, decltype(NK)::value>), grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], dim == 3 ? box.h[2] : 1.0, a, kap, x, y);
+  });
 }
 
 // dot_partials (optional, kMaxPartials slots zeroed once by the caller): per-workgroup partial sums of x.y over all local rows

@@ -76,15 +76,17 @@ template <int DIM> __device__ __forceinline__ double p_stencil_sum(int n0, int n
   return acc;
 }
 
-// ---- per-cell coefficient: y = (a M + K_kappa) x, K_kappa = sum_c kappa_c K_c --------------------------------------------------------------------------------
-// The row of a node is the constant mass stencil above plus, over the <= 2^DIM cells around it, kappa_c times the row of the Q1 element Laplace matrix of a box
-// cell, K_e = k (x) m (x) m + m (x) k (x) m + m (x) m (x) k with the 1D element matrices m = h/6 [[2, 1], [1, 2]], k = 1/h [[1, -1], [-1, 1]].  kappa is stored
-// in lattice cell order (x fastest).  Same discipline as above: the cell index is clamped into the box and loaded unconditionally, a cell outside the box gets
-// weight 0 by a select, and cells and taps are summed in one fixed order - the result is the same bit for bit from call to call.
-template <int DIM> struct PStencilCells { static constexpr int N = 1 << DIM; double w[N]; };
+// ---- per-cell coefficient: y = (a M + K_kappa) x, K_kappa = sum_c K_c(kappa_c) ---------------------------------------------------------------------------------
+// The row of a node is the constant mass stencil above plus, over the <= 2^DIM cells around it, the row of the weighted Q1 element Laplace matrix of a box cell,
+// K_e = kx k (x) m (x) m + ky m (x) k (x) m + kz m (x) m (x) k with the 1D element matrices m = h/6 [[2, 1], [1, 2]], k = 1/h [[1, -1], [-1, 1]].  NK weights per cell:
+// 1 (one k / mu: kx = ky = kz, summed before the weight multiplies) or DIM (its diagonal tensor, component d weights the derivatives along direction d).  kap holds one
+// plane of cells per component, each in lattice cell order (x fastest), so that consecutive lanes read consecutive addresses of every plane.  Same discipline as
+// above: the cell index is clamped into the box and loaded unconditionally, a cell outside the box gets weight 0 by a select, and cells, components and taps are
+// summed in one fixed order - the result is the same bit for bit from call to call.
+template <int DIM, int NK> struct PStencilCells { static constexpr int N = 1 << DIM; double w[NK][N]; };
 
-// the weights of the 2^DIM cells around `node`, index = c0 + 2 c1 (+ 4 c2) with c_d = 0 for the cell on the low side of the node in direction d
-template <int DIM> __device__ __forceinline__ void p_stencil_load_cells(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, PStencilCells<DIM> &C) {
+// one component's weights of the 2^DIM cells around `node`, index = c0 + 2 c1 (+ 4 c2) with c_d = 0 for the cell on the low side of the node in direction d
+template <int DIM> __device__ __forceinline__ void p_stencil_load_plane(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, double (&w)[1 << DIM]) {
   const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
   const int nc[3] = {n0 - 1, n1 - 1, n2 - 1};      // cells per direction (>= 1 in every direction of the box)
   int at[3][2]; bool in[3][2];
@@ -96,7 +98,7 @@ template <int DIM> __device__ __forceinline__ void p_stencil_load_cells(int n0, 
 #pragma unroll
     for (int c1 = 0; c1 < 2; ++c1)
 #pragma unroll
-      for (int c0 = 0; c0 < 2; ++c0) { const double v = kap[(int64_t)at[1][c1] * nc[0] + at[0][c0]]; C.w[2 * c1 + c0] = (in[0][c0] && in[1][c1]) ? v : 0.0; }
+      for (int c0 = 0; c0 < 2; ++c0) { const double v = kap[(int64_t)at[1][c1] * nc[0] + at[0][c0]]; w[2 * c1 + c0] = (in[0][c0] && in[1][c1]) ? v : 0.0; }
   } else {
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2)
@@ -105,13 +107,24 @@ template <int DIM> __device__ __forceinline__ void p_stencil_load_cells(int n0, 
 #pragma unroll
         for (int c0 = 0; c0 < 2; ++c0) {
           const double v = kap[((int64_t)at[2][c2] * nc[1] + at[1][c1]) * nc[0] + at[0][c0]];
-          C.w[4 * c2 + 2 * c1 + c0] = (in[0][c0] && in[1][c1] && in[2][c2]) ? v : 0.0;
+          w[4 * c2 + 2 * c1 + c0] = (in[0][c0] && in[1][c1] && in[2][c2]) ? v : 0.0;
         }
   }
 }
+// all NK components.  (One component: without the plane arithmetic in the source - the compiler does not fold it away without a trace: the 2D kernels take one more SGPR with it)
+template <int DIM, int NK> __device__ __forceinline__ void p_stencil_load_cells(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, PStencilCells<DIM, NK> &C) {
+  if constexpr (NK == 1) p_stencil_load_plane<DIM>(n0, n1, n2, node, kap, C.w[0]);
+  else {
+    const int64_t plane = (int64_t)(n0 - 1) * (n1 - 1) * (DIM == 3 ? n2 - 1 : 1);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) p_stencil_load_plane<DIM>(n0, n1, n2, node, kap + k * plane, C.w[k]);
+  }
+}
 
-template <int DIM> __device__ __forceinline__ double p_stencil_sum_var(int n0, int n1, int n2, double h0, double h1, double h2, double a, int64_t node,
-                                                                       const PStencilTaps<DIM> &T, const PStencilCells<DIM> &C) {
+// MASS: the a M part is summed with the taps (the Jacobian); without it the function gives K_kappa x alone
+template <int DIM, int NK, bool MASS> __device__ __forceinline__ double p_stencil_sum_cells(int n0, int n1, int n2, double h0, double h1, double h2, double a, int64_t node,
+                                                                                            const PStencilTaps<DIM> &T, const PStencilCells<DIM, NK> &C) {
+  static_assert(NK == 1 || NK == DIM, "one weight per cell, or one per direction");
   const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
   const int nd[3] = {n0, n1, n2};
   const double h[3] = {h0, h1, h2};
@@ -131,83 +144,7 @@ template <int DIM> __device__ __forceinline__ double p_stencil_sum_var(int n0, i
         ek[d][c][o] = held ? (other == own ? 1.0 / h[d] : -1.0 / h[d]) : 0.0;
       }
   }
-  double acc = 0;
-  if constexpr (DIM == 2) {
-#pragma unroll
-    for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-      for (int di = 0; di < 3; ++di) {
-        double wK = 0;
-#pragma unroll
-        for (int c1 = 0; c1 < 2; ++c1)
-#pragma unroll
-          for (int c0 = 0; c0 < 2; ++c0) {
-            const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1);        // (known at compile time after unrolling)
-            if (held) wK = fma(C.w[2 * c1 + c0], ek[0][c0][di] * em[1][c1][dj] + em[0][c0][di] * ek[1][c1][dj], wK);
-          }
-        const double w = a * (M1[0][di] * M1[1][dj]) + wK;
-        acc = w != 0.0 ? fma(w, T.v[3 * dj + di], acc) : acc;
-      }
-  } else {
-#pragma unroll
-    for (int dk = 0; dk < 3; ++dk)
-#pragma unroll
-      for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-        for (int di = 0; di < 3; ++di) {
-          double wK = 0;
-#pragma unroll
-          for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-            for (int c1 = 0; c1 < 2; ++c1)
-#pragma unroll
-              for (int c0 = 0; c0 < 2; ++c0) {
-                const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1) && (dk == 1 || dk == 2 * c2);
-                if (held)
-                  wK = fma(C.w[4 * c2 + 2 * c1 + c0],
-                           ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]) + em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk] + em[1][c1][dj] * ek[2][c2][dk]), wK);
-              }
-          const double w = a * (M1[0][di] * (M1[1][dj] * M1[2][dk])) + wK;
-          acc = w != 0.0 ? fma(w, T.v[9 * dk + 3 * dj + di], acc) : acc;
-        }
-  }
-  return acc;
-}
-
-// ---- per-cell diagonal tensor: K_kappa = sum_c ∫_c grad(phi_i) . diag(kappa_c) grad(phi_j), K_e = kx k (x) m (x) m + ky m (x) k (x) m + kz m (x) m (x) k -------------
-// The row of a node sums DIM weights per surrounding cell, one per direction of the derivative.  kap holds one plane of `plane` cells per component, each in lattice cell
-// order, so that consecutive lanes read consecutive addresses of every plane.  Same discipline: clamped cell index, unconditional loads, a select for the cells outside
-// the box, one fixed order of cells, components and taps.
-template <int DIM> struct PStencilCellsT { PStencilCells<DIM> d[DIM]; };
-
-template <int DIM> __device__ __forceinline__ void p_stencil_load_cells_tensor(int n0, int n1, int n2, int64_t node, const double *__restrict__ kap, PStencilCellsT<DIM> &C) {
-  const int64_t plane = (int64_t)(n0 - 1) * (n1 - 1) * (DIM == 3 ? n2 - 1 : 1);
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) p_stencil_load_cells<DIM>(n0, n1, n2, node, kap + d * plane, C.d[d]);
-}
-
-// MASS: the a M part is summed with the taps (the Jacobian); without it the function gives K_kappa x alone
-template <int DIM, bool MASS> __device__ __forceinline__ double p_stencil_sum_tensor(int n0, int n1, int n2, double h0, double h1, double h2, double a, int64_t node,
-                                                                                      const PStencilTaps<DIM> &T, const PStencilCellsT<DIM> &C) {
-  const int idx[3] = {(int)(node % n0), (int)((node / n0) % n1), (int)(node / ((int64_t)n0 * n1))};
-  const int nd[3] = {n0, n1, n2};
-  const double h[3] = {h0, h1, h2};
-  double M1[3][3];             // the assembled 1D mass rows, as in p_stencil_sum
-  double em[3][2][3], ek[3][2][3];   // as in p_stencil_sum_var
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) {
-    const double L = idx[d] > 0 ? 1.0 : 0.0, R = idx[d] < nd[d] - 1 ? 1.0 : 0.0;
-    M1[d][0] = L * h[d] / 6; M1[d][2] = R * h[d] / 6; M1[d][1] = (L + R) * h[d] / 3;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int o = 0; o < 3; ++o) {
-        const int own = 1 - c, other = own + o - 1;
-        const bool held = other == 0 || other == 1;
-        em[d][c][o] = held ? (other == own ? h[d] / 3 : h[d] / 6) : 0.0;
-        ek[d][c][o] = held ? (other == own ? 1.0 / h[d] : -1.0 / h[d]) : 0.0;
-      }
-  }
+  // The weight expressions of NK = 1 and NK = DIM stay apart as they are: the compiler contracts into fma across an expression, so that a regrouped one rounds differently
   double acc = 0;
   if constexpr (DIM == 2) {
 #pragma unroll
@@ -221,8 +158,12 @@ template <int DIM, bool MASS> __device__ __forceinline__ double p_stencil_sum_te
           for (int c0 = 0; c0 < 2; ++c0) {
             const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1);        // (known at compile time after unrolling)
             if (held) {
-              wK = fma(C.d[0].w[2 * c1 + c0], ek[0][c0][di] * em[1][c1][dj], wK);
-              wK = fma(C.d[1].w[2 * c1 + c0], em[0][c0][di] * ek[1][c1][dj], wK);
+              const int cell = 2 * c1 + c0;
+              if constexpr (NK == 1) wK = fma(C.w[0][cell], ek[0][c0][di] * em[1][c1][dj] + em[0][c0][di] * ek[1][c1][dj], wK);
+              else {
+                wK = fma(C.w[0][cell], ek[0][c0][di] * em[1][c1][dj], wK);
+                wK = fma(C.w[1][cell], em[0][c0][di] * ek[1][c1][dj], wK);
+              }
             }
           }
         const double w = MASS ? a * (M1[0][di] * M1[1][dj]) + wK : wK;
@@ -245,9 +186,14 @@ template <int DIM, bool MASS> __device__ __forceinline__ double p_stencil_sum_te
                 const bool held = (di == 1 || di == 2 * c0) && (dj == 1 || dj == 2 * c1) && (dk == 1 || dk == 2 * c2);
                 if (held) {
                   const int cell = 4 * c2 + 2 * c1 + c0;
-                  wK = fma(C.d[0].w[cell], ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]), wK);
-                  wK = fma(C.d[1].w[cell], em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk]), wK);
-                  wK = fma(C.d[2].w[cell], em[0][c0][di] * (em[1][c1][dj] * ek[2][c2][dk]), wK);
+                  if constexpr (NK == 1)
+                    wK = fma(C.w[0][cell],
+                             ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]) + em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk] + em[1][c1][dj] * ek[2][c2][dk]), wK);
+                  else {
+                    wK = fma(C.w[0][cell], ek[0][c0][di] * (em[1][c1][dj] * em[2][c2][dk]), wK);
+                    wK = fma(C.w[1][cell], em[0][c0][di] * (ek[1][c1][dj] * em[2][c2][dk]), wK);
+                    wK = fma(C.w[2][cell], em[0][c0][di] * (em[1][c1][dj] * ek[2][c2][dk]), wK);
+                  }
                 }
               }
           const double w = MASS ? a * (M1[0][di] * (M1[1][dj] * M1[2][dk])) + wK : wK;

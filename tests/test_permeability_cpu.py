@@ -78,7 +78,7 @@ def test_line_coefficients_against_numpy(tmp_path):
     rng = np.random.default_rng(17)
     for n, lo, hi in ((1, 0, 0), (1, 1, 0), (3, 0, 1), (6, 1, 1), (7, 0, 0)):
         h = 0.5 + rng.random(n); k = 10.0 ** rng.uniform(-3, 1, n)
-        out = subprocess.run([exe, str(lo), str(hi)] + [repr(float(v)) for v in np.r_[h, k]], check=True, capture_output=True, text=True).stdout.split()
+        out = subprocess.run([exe, "1", str(lo), str(hi)] + [repr(float(v)) for v in np.r_[h, k, k]], check=True, capture_output=True, text=True).stdout.split()     # one weight line = the Laplace weights
         got = np.array([float(v) for v in out]).reshape(6, n + 1)
         nl = n + 1
         M = np.zeros((nl, nl)); W = np.zeros((nl, nl)); K = np.zeros((nl, nl))

@@ -1,6 +1,6 @@
 """Host layer of the per-cell permeability tensor diag(kx, ky[, kz]) / mu (no GPU): layers by cell centres, inheritance through the coarse cells of refined boxes, the
 exported symbols, the ABI number, the command-line flag of poro_run, and the 1D coefficient builder of the tensor line solve (csrc/perm_line.hpp:
-perm_tensor_line_coefficients, through a small stand-alone program) against a numpy 1D assembly."""
+perm_line_coefficients, through a small stand-alone program) against a numpy 1D assembly."""
 import os
 import re
 import subprocess
@@ -93,15 +93,15 @@ def test_command_line_flag():
 
 
 def test_line_coefficients_against_numpy(tmp_path):
-    """perm_tensor_line_coefficients through tests/perm_tensor_line_check.cpp (host-only, built here with the address and undefined-behaviour sanitizers and run directly):
-    [md mo | w0d w0o | (w1d w1o) | kd ko] against the 1D Q1 assembly, free, fixed-lo, fixed-hi and single-cell lines"""
-    exe = build_sanitized_check(tmp_path, "perm_tensor_line_check")
+    """perm_line_coefficients with dim - 1 weight lines through tests/perm_line_check.cpp (host-only, built here with the address and undefined-behaviour sanitizers and run
+    directly): [md mo | w0d w0o | (w1d w1o) | kd ko] against the 1D Q1 assembly, free, fixed-lo, fixed-hi and single-cell lines"""
+    exe = build_sanitized_check(tmp_path, "perm_line_check")
     rng = np.random.default_rng(17)
     m1 = np.array([[2.0, 1.0], [1.0, 2.0]]); k1 = np.array([[1.0, -1.0], [-1.0, 1.0]])
     for dim in (2, 3):
         for n, lo, hi in ((1, 0, 0), (1, 1, 0), (1, 0, 1), (3, 0, 1), (4, 1, 0), (6, 1, 1), (7, 0, 0)):
             h = 0.5 + rng.random(n); k = 10.0 ** rng.uniform(-3, 1, (dim, n))
-            out = subprocess.run([exe, str(dim), str(lo), str(hi)] + [repr(float(v)) for v in np.r_[h, k.ravel()]], check=True, capture_output=True, text=True).stdout.split()
+            out = subprocess.run([exe, str(dim - 1), str(lo), str(hi)] + [repr(float(v)) for v in np.r_[h, k.ravel()]], check=True, capture_output=True, text=True).stdout.split()
             got = np.array([float(v) for v in out]).reshape(2 * (dim + 1), n + 1)
             nl = n + 1
             mats = [np.zeros((nl, nl)) for _ in range(dim + 1)]       # M, M^k0 (, M^k1), K^k_last

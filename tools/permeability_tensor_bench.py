@@ -1,5 +1,5 @@
-"""Per-cell permeability tensor on the MI355X: what the tensor stencils and the tensor line solve of PREC_FDM cost next to the scalar per-cell kernels
-(k_p_stencil_var, k_p_residual_stencil_var, k_q1_line_solve - unchanged code), timed in the same session.  Writes profiles/permeability_tensor.json.
+"""Per-cell permeability tensor on the MI355X: what the tensor instances of the per-cell stencils and of the line solve of PREC_FDM (k_p_stencil_cells<3, 3>,
+k_p_residual_stencil_cells<3, 3>, k_q1_line_solve<3, 2>) cost next to the one-weight instances (<3, 1>), timed in the same session.  Writes profiles/permeability_tensor.json.
 
     python tools/permeability_tensor_bench.py [--cells 72] [--runs 5] [--out profiles/permeability_tensor.json]
 
