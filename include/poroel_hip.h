@@ -543,6 +543,22 @@ int  poro_ctx_get_cell_moduli(poro_ctx *ctx, double *lambda_out, double *G_out /
 int  poro_ctx_set_cell_permeability_tensor(poro_ctx *ctx, const double *k_over_mu /* [n_cells][dim], x first; NULL: back to the scalar */, int64_t n_cells);
 int  poro_ctx_get_cell_permeability_tensor(poro_ctx *ctx, double *out /* [n_cells][dim], may be NULL */, int64_t n_cells, int32_t *kind);
 
+/* Form of the displacement operator on a box with per-cell moduli (appended entry points, no struct changes: PORO_ABI_VERSION stays 4).
+ *   PORO_MODULI_OP_CELLS:      the general cell loop, as poro_ctx_set_cell_moduli describes (the default).
+ *   PORO_MODULI_OP_STRUCTURED: one structured launch per application where lambda and G are constant within every cell layer of z (kind 1): the operator is still a sum of
+ *                              Kronecker products of 1D matrices whose z factor carries the weight.  The same mathematics in another summation order: results
+ *                              agree with the cell loop to rounding (1e-12 of max|y|), not bitwise; bitwise reproducible from run to run.
+ * Never chosen automatically.  The request may be made at any time and stays through field changes.  It is EFFECTIVE on a single-rank box-tagged (uniform) 3D context of
+ * degree 1 or 2 in PORO_OP_MATRIX_FREE mode with the sum-factorised variant while a kind-1 field is set; everywhere else - no field, a kind-2 field, 2D, tensor-product
+ * grids without the box tag, refined meshes, PORO_OP_CSR - the request is recorded and the context runs exactly what it ran.  While effective, the operator of
+ * poro_disp_solve (with the fused x . y), the Chebyshev recurrence, poro_apply_operator and poro_bench_operator take the structured kernel; the scatter mode is stored and
+ * reported but not used.  The Jacobi diagonal, the lifting and the CSR assembly keep the cell loop (once per field or assembly).
+ * The environment variable PORO_MODULI_OPERATOR=structured|cells sets the initial request of every context when it is created.
+ * poro_ctx_get_moduli_operator: `effective` = what an application runs now.  An unknown form is an error. */
+enum { PORO_MODULI_OP_CELLS = 0, PORO_MODULI_OP_STRUCTURED = 1 };
+int  poro_ctx_set_moduli_operator(poro_ctx *ctx, int32_t form);
+int  poro_ctx_get_moduli_operator(poro_ctx *ctx, int32_t *requested, int32_t *effective);
+
 #ifdef __cplusplus
 }
 #endif

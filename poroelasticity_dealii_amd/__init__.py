@@ -21,6 +21,7 @@ SCATTER_COLOURED, SCATTER_ATOMIC = 0, 1
 OPFORM_GENERAL, OPFORM_HYBRID = 0, 1
 FDM_FP64, FDM_FP32 = 0, 1
 FDM_FORM_DEFAULT, FDM_FORM_PER_DIRECTION = 0, 1
+MODULI_OP_CELLS, MODULI_OP_STRUCTURED = 0, 1
 FDM_RUNS_NODAL, FDM_RUNS_OCTANT, FDM_RUNS_PER_DIRECTION, FDM_RUNS_SLAB, FDM_RUNS_PLANAR = 0, 1, 2, 3, 4
 MAT_A_U, MAT_MASS_P, MAT_LAPLACE_P, MAT_JACOBIAN_P = 0, 1, 2, 3
 VEC_U, VEC_RHS_U, VEC_P, VEC_P_OLD, VEC_DP, VEC_RESIDUAL_P, VEC_EPSV, VEC_EPSV0, VEC_SOURCE_P = range(9)
@@ -112,7 +113,8 @@ HIP_SYMBOLS = [
     "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form",
     "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian",
     "poro_ctx_set_cell_permeability_tensor", "poro_ctx_get_cell_permeability_tensor",
-    "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli"]
+    "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli",
+    "poro_ctx_set_moduli_operator", "poro_ctx_get_moduli_operator"]
 
 _hip = None
 _host = None
@@ -142,6 +144,8 @@ def load_hip():
         L.poro_ctx_get_fdm_precision.argtypes = [C.c_void_p, _ip, _ip]
         L.poro_ctx_set_fdm_form.argtypes = [C.c_void_p, C.c_int32]
         L.poro_ctx_get_fdm_form.argtypes = [C.c_void_p, _ip, _ip, _ip]
+        L.poro_ctx_set_moduli_operator.argtypes = [C.c_void_p, C.c_int32]
+        L.poro_ctx_get_moduli_operator.argtypes = [C.c_void_p, _ip, _ip]
         L.poro_comm_unique_id.argtypes = [C.c_void_p]
         L.poro_ctx_comm_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
         L.poro_ctx_comm_init_callbacks.argtypes = [C.c_void_p, ALLREDUCE_FN, SENDRECV_FN, C.c_void_p]
@@ -237,6 +241,7 @@ def load_host():
         L.poro_host_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
         L.poro_host_set_moduli_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
         L.poro_host_inherit_cell_moduli.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_host_set_moduli_structured.argtypes = [C.c_void_p, C.c_int]
         L.poro_host_get_cell_moduli.restype = C.c_int64
         L.poro_host_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp]
         L.poro_host_partition.restype = C.c_void_p
@@ -540,6 +545,10 @@ class Problem:
         top, pt = _arr_d([l[0] for l in layers]); E, pe = _arr_d([l[1] for l in layers]); nu, pn = _arr_d([l[2] for l in layers])
         return self._host("set_moduli_layers", len(layers), pt, pe, pn)
 
+    def set_moduli_structured(self, on):
+        """MODULI_OP_STRUCTURED for the contexts run_problem and Runner create from this problem (their moduli_structured argument sets it)"""
+        return self._host("set_moduli_structured", int(bool(on)))
+
     def inherit_cell_moduli(self, old):
         """what an adaptive run does with the field: this refined box takes the moduli of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
         return self._host("inherit_cell_moduli", old.handle)
@@ -644,6 +653,18 @@ class Context:
         r, e, m = C.c_int32(), C.c_int32(), (C.c_int32 * 3)()
         self._chk(self.L.poro_ctx_get_fdm_form(self.ptr, C.byref(r), C.byref(e), m))
         return r.value, e.value, tuple(int(v) for v in m)
+
+    def set_moduli_operator(self, form):
+        """MODULI_OP_CELLS (the general cell loop on a box with per-cell moduli, the default) or MODULI_OP_STRUCTURED: one structured launch per operator application
+        where the field is constant within every cell layer of z.  Any time; stays through field changes.  Effective on single-rank uniform 3D boxes of degree 1 or 2 in
+        matrix-free mode with a kind-1 field; everywhere else the request is recorded and the context runs what it ran.  Raises on an unknown value"""
+        self._chk(self.L.poro_ctx_set_moduli_operator(self.ptr, int(form)))
+
+    def get_moduli_operator(self):
+        """(requested, effective): MODULI_OP_*; effective = what an operator application runs now"""
+        r, e = C.c_int32(), C.c_int32()
+        self._chk(self.L.poro_ctx_get_moduli_operator(self.ptr, C.byref(r), C.byref(e)))
+        return r.value, e.value
 
     def _get_field(self, get, n_arrays):
         """(array or None, ..., kind) of the per-cell field the getter `get` of the library reads"""
@@ -882,15 +903,19 @@ _FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit f
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None, permeability_tensor=None):
+                atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None, permeability_tensor=None,
+                moduli_structured=False):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
     Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
     hybrid_operator=True: OPFORM_HYBRID on refined boxes (carried over to every adapted mesh; a no-op on box-tagged meshes, an error where the mesh cannot take it).
     fdm_per_direction=True: FDM_FORM_PER_DIRECTION for the block FDM of the displacement system (Context.set_fdm_form; carried over to every adapted mesh).
+    moduli_structured=True: MODULI_OP_STRUCTURED for the displacement operator (Context.set_moduli_operator; requested on every adapted mesh, where it has no effect:
+    a refined mesh has no box tag).
     permeability: per-cell k / mu (Problem.set_cell_permeability on `problem`, which keeps it), carried over to every adapted mesh.
     permeability_tensor: per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim) (Problem.set_cell_permeability_tensor), likewise."""
     H = load_host()
+    problem.set_moduli_structured(moduli_structured)
     if permeability is not None:
         problem.set_cell_permeability(permeability)
     if permeability_tensor is not None:
@@ -920,8 +945,9 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None, moduli_structured=False):
         self.H = load_host()
+        problem.set_moduli_structured(moduli_structured)      # MODULI_OP_STRUCTURED (Context.set_moduli_operator), requested again on every mesh adapt() builds
         if permeability_tensor is not None:      # per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim): Problem.set_cell_permeability_tensor, kept and carried like the scalar field
             problem.set_cell_permeability_tensor(permeability_tensor)
         if permeability is not None:             # per-cell k / mu: Problem.set_cell_permeability on `problem`, which keeps it; adapt() carries it to every new mesh

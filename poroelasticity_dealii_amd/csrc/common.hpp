@@ -321,13 +321,25 @@ struct poro_ctx {
   // mod: (Lame lambda, shear modulus G) of the displacement system, components 0 and 1.  cell: [n_cells][2] = (lambda, G) in the caller's cell order, what the general
   // cell kernels and the coloured assembly read.  node: [n_p][2], the arithmetic mean over the cells that touch a pressure dof - the constants of the effective stresses and
   // of the fixed-stress strain update.  While kind != 0 a box-tagged context runs the general cell loop for everything that depends on the moduli (box_fast_u below)
-  struct Moduli : poro::CellField<2> { poro::DevBuf<double> cell, node; } mod;
+  // planes: the per-plane weight table of the structured operator for layered moduli (moduli_planes.hpp), uploaded while that form is effective (moduli_structured below)
+  struct Moduli : poro::CellField<2> { poro::DevBuf<double> cell, node, planes; } mod;
+  // requested form of the displacement operator on a box with per-cell moduli (poro_ctx_set_moduli_operator): PORO_MODULI_OP_CELLS, the general cell loop, or
+  // PORO_MODULI_OP_STRUCTURED, kernels_kron_lm.hip where it applies.  Never chosen automatically; stays through field changes
+  int moduli_op = 0;
 };
 
 namespace poro {
 
 // the constant-coefficient structured kernels (k_kron*, the single Ke, box_asm_u_matrix, the diagonal dictionary) serve the displacement system: a box without per-cell moduli
 inline bool box_fast_u(const poro_ctx *c) { return c->box.enabled && !c->mod.kind; }
+// where the structured operator for layered moduli can stand in for the cell loop: a single-rank uniform 3D box of degree 1 or 2 in matrix-free mode with the
+// sum-factorised variant, and a field that is constant within every cell layer of z
+inline bool moduli_structured_applies(const poro_ctx *c) {
+  return c->box.enabled && c->dim == 3 && (c->k_u == 1 || c->k_u == 2) && c->mod.kind == 1 && c->operator_mode == PORO_OP_MATRIX_FREE && c->mf_variant == 1 && !c->comm.multi() &&
+         c->comm.part.n_ranks <= 1;
+}
+// ... and does: requested, and the table is on the device (ctx_fields.hip: sync_moduli_planes keeps the two in step)
+inline bool moduli_structured(const poro_ctx *c) { return c->moduli_op == PORO_MODULI_OP_STRUCTURED && c->mod.planes.p && moduli_structured_applies(c); }
 
 // ---- kernels_la.hip -----------------------------------------------------------------------------
 void la_fill(hipStream_t s, double *x, double v, int64_t n);
@@ -531,6 +543,11 @@ int kron_apply(hipStream_t s, const MfArgs &a, const double *x, double *y, bool 
                const PcgScalars *pcg = nullptr /* launch becomes a no-op once pcg->done / finishing is set */,
                const KronCheb *cheb = nullptr /* 3D only: store the Chebyshev update instead of the product (y is not written) */);   // returns the workgroup count (= partial slots used)
 void kron_fix_constrained(hipStream_t s, const MfArgs &a, const double *x, double *y, double *dot_partials, int slot_base);
+// ---- kernels_kron_lm.hip: the same operator on a 3D box with lambda, G layered along z (poro_ctx_set_moduli_operator) ----
+void kron_lm_prepare_device();   // as kron_prepare_device
+// planes: device copy of moduli_plane_table (moduli_planes.hpp); arguments and return value as kron_apply
+int kron_lm_apply(hipStream_t s, const MfArgs &a, const double *planes, const double *x, double *y, bool constrained, int n_cus, double *dot_partials = nullptr, hipEvent_t ev0 = nullptr,
+                  hipEvent_t ev1 = nullptr, const PcgScalars *pcg = nullptr);
 // ---- kernels_hyb.hip: the pieces of the hybrid operator form between the fine-cell launches and the box product ------------------
 void hyb_gather(hipStream_t s, int dim, int64_t n_box_nodes, const int64_t *inj, const double *x, double *x_box);   // x_box[b] = x[inj[b]], node-wise
 // y[inj[b]] += y_box[b] - sum over the refined box cells around b of (Ke x_box)'s row of b; `box` = mf_args of the box context (geometry, nodemask: Dirichlet columns zeroed

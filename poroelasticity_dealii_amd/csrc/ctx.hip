@@ -525,6 +525,7 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
     c->device = device; c->operator_mode = operator_mode;
     PORO_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     kron_prepare_device();   // function attributes are per device: opt in to the large dynamic LDS on THIS one
+    kron_lm_prepare_device();
     { void *mbp = nullptr; PORO_HIP(hipHostMalloc(&mbp, sizeof(Mailbox), hipHostMallocDefault)); std::memset(mbp, 0, sizeof(Mailbox)); c->mailbox = static_cast<Mailbox *>(mbp); }
     setup(c.get(), desc);
     if (desc->coarse.enabled) {
@@ -563,7 +564,33 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
       if (m != "per-direction" && m != "default") throw Error("PORO_FDMO_FORM: per-direction or default");
       c->fdm_form = m == "per-direction" ? PORO_FDM_FORM_PER_DIRECTION : PORO_FDM_FORM_DEFAULT;
     }
+    // and the requested form of the displacement operator on boxes with layered moduli (poro_ctx_set_moduli_operator)
+    if (const char *v = std::getenv("PORO_MODULI_OPERATOR")) {
+      const std::string m(v);
+      if (m != "structured" && m != "cells") throw Error("PORO_MODULI_OPERATOR: structured or cells");
+      c->moduli_op = m == "structured" ? PORO_MODULI_OP_STRUCTURED : PORO_MODULI_OP_CELLS;
+    }
     *out = c.release();
+    return 0;
+  });
+}
+
+// The structured form is honoured where moduli_structured_applies (common.hpp); elsewhere the request is recorded and the cell loop runs as before
+int poro_ctx_set_moduli_operator(poro_ctx *c, int32_t form) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    if (form != PORO_MODULI_OP_CELLS && form != PORO_MODULI_OP_STRUCTURED) throw Error("poro_ctx_set_moduli_operator: unknown form " + std::to_string(form) + " (PORO_MODULI_OP_CELLS or PORO_MODULI_OP_STRUCTURED)");
+    PORO_HIP(hipSetDevice(c->device));
+    const int before = c->moduli_op;
+    c->moduli_op = form;
+    try { sync_moduli_planes(c); } catch (...) { c->moduli_op = before; throw; }
+    return 0;
+  });
+}
+int poro_ctx_get_moduli_operator(poro_ctx *c, int32_t *requested, int32_t *effective) {
+  return guarded([&] {
+    if (!c || !requested || !effective) throw Error("null argument");
+    *requested = c->moduli_op; *effective = moduli_structured(c) ? PORO_MODULI_OP_STRUCTURED : PORO_MODULI_OP_CELLS;
     return 0;
   });
 }

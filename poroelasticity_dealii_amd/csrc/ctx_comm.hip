@@ -274,6 +274,11 @@ void count_mfg_launches(poro_ctx *c, int n) { if (c->timing) c->timers["mfg_cell
 
 // y = A_u x without forming A_u: sum-factorised sweeps where available, element-matrix gather otherwise
 void mf_operator(poro_ctx *c, const double *x, double *y, bool constrained) {
+  if (moduli_structured(c)) {   // a box with moduli layered along z, structured form requested: one launch instead of the coloured cell loop
+    const int slots = kron_lm_apply(c->stream, mf_args(c), c->mod.planes.p, x, y, constrained, c->n_cus);
+    if (constrained) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, std::abs(slots));
+    return;
+  }
   if (!box_fast_u(c)) {   // general mesh, or a box with per-cell moduli: quadrature-level cell loop; the Dirichlet rows from the constraint list as for the structured kernels
     mfg_operator(c, x, y, constrained);
     if (constrained) kron_fix_constrained(c->stream, mf_args(c), x, y, nullptr, 0);
@@ -301,6 +306,12 @@ bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_pa
     });
     // inside PCG the Dirichlet rows are inert (zero residual and direction), so what the structured kernel leaves there is never read
     fused = dot_partials != nullptr && slots > 0;   // slots < 0: too many workgroups for the partial slots, the kernel ran without the fused x.y
+    if (fix_rows) { Timed tm(c, "apply_u_dirichlet_rows"); kron_fix_constrained(c->stream, mf_args(c), x, y, fused ? dot_partials : nullptr, slots > 0 ? slots : -slots); }
+  } else if (mode == PORO_OP_MATRIX_FREE && moduli_structured(c)) {      // as the constant-coefficient branch above, with the layered kernel (the scatter mode is not used)
+    const int slots = sampled_dispatch(c, "apply_u_matrix_free", [&](hipEvent_t e0, hipEvent_t e1) {
+      return kron_lm_apply(c->stream, mf_args(c), c->mod.planes.p, x, y, true, c->n_cus, dot_partials, e0, e1, pcg_state);
+    });
+    fused = dot_partials != nullptr && slots > 0;
     if (fix_rows) { Timed tm(c, "apply_u_dirichlet_rows"); kron_fix_constrained(c->stream, mf_args(c), x, y, fused ? dot_partials : nullptr, slots > 0 ? slots : -slots); }
   } else if (mode == PORO_OP_MATRIX_FREE && !box_fast_u(c)) {
     Timed tm(c, "apply_u_matrix_free");

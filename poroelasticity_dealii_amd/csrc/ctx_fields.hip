@@ -7,6 +7,7 @@
 #include <cstring>
 #include "common.hpp"
 #include "ctx_internal.hpp"
+#include "moduli_planes.hpp"
 
 using namespace poro;
 using namespace poro::ctx_detail;
@@ -91,6 +92,16 @@ int set_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells, int 
 }
 }  // namespace
 
+// the plane table of the structured operator for layered moduli goes with the field, the request and what the context is: called wherever one of them changes
+void poro::ctx_detail::sync_moduli_planes(poro_ctx *c) {
+  poro_ctx::Moduli &M = c->mod;
+  if (c->moduli_op != PORO_MODULI_OP_STRUCTURED || !moduli_structured_applies(c)) { if (M.planes.p) { PORO_HIP(hipStreamSynchronize(c->stream)); M.planes.release(); } return; }
+  if ((int)M.layer[0].size() != c->box.n[2] || M.layer[1].size() != M.layer[0].size()) throw Error("structured moduli operator: the field's layers do not match the box");
+  const std::vector<double> t = moduli_plane_table(c->k_u, M.layer[0], M.layer[1]);
+  PORO_HIP(hipStreamSynchronize(c->stream));      // (an operator application that reads the old table may still be in flight)
+  M.planes.upload(t);
+}
+
 extern "C" {
 
 int poro_ctx_set_cell_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells) { return set_permeability(c, k_over_mu, n_cells, 1, "poro_ctx_set_cell_permeability"); }
@@ -132,7 +143,7 @@ int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const doubl
     if (!lame_lambda && !shear_G) {
       if (!M.kind) return 0;
       PORO_HIP(hipStreamSynchronize(c->stream));
-      M.clear(); M.cell.release(); M.node.release();
+      M.clear(); M.cell.release(); M.node.release(); M.planes.release();
       invalidate();
       return 0;
     }
@@ -164,6 +175,7 @@ int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const doubl
     M.cell.upload(pair); M.node.upload(node);
     static_cast<CellField<2> &>(M) = std::move(F);
     invalidate();
+    sync_moduli_planes(c);
     return 0;
   });
 }

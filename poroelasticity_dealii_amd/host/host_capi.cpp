@@ -237,6 +237,9 @@ int64_t poro_host_get_cell_permeability_tensor(void *h, double *out) { return co
 int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_moduli(lam, G, n); }); }
 // by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre; (E, nu) -> (lambda, G) as the parameter file's are
 int poro_host_set_moduli_layers(void *h, int n, const double *top, const double *young, const double *poisson) { return on_problem(h, [&](ProblemData &P) { P.set_moduli_layers(n, top, young, poisson); }); }
+// the structured operator for layered moduli (PORO_MODULI_OP_STRUCTURED) for the contexts poro_host_run, poro_host_run_adaptive and poro_host_runner_create make from this problem
+// (their flags word is full); kept with the problem like the moduli it applies to
+int poro_host_set_moduli_structured(void *h, int on) { return on_problem(h, [&](ProblemData &P) { P.moduli_structured = on != 0; }); }
 int poro_host_inherit_cell_moduli(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_moduli(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies where the pointers are not NULL
 int64_t poro_host_get_cell_moduli(void *h, double *lam_out, double *G_out) {
@@ -292,6 +295,7 @@ int poro_host_run(void *problem_data, int device, int operator_mode, double p_in
     auto *P = static_cast<ProblemData *>(problem_data);
     RunControls rc; rc.p_init = p_init; rc.time_step = dt; rc.n_steps = n_steps; rc.fss_tol = fss_tol; rc.pressure_tol = pressure_tol;
     rc.max_fss_iterations = max_fss; rc.max_pressure_iterations = max_pres; rc.abs_tol_u = abs_u; rc.rel_tol_u = rel_u; rc.max_iter = max_it; rc.preconditioner = preconditioner; rc.coupled_fss = (flags & 1) != 0; rc.incremental_strain = (flags & 2) != 0; rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) rc.preconditioner_p = PORO_PREC_TWO_LEVEL; rc.atomic_scatter = (flags & 32) != 0; rc.fdm_fp32 = (flags & 64) != 0; rc.hybrid_operator = (flags & 128) != 0; rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; rc.chebyshev_degree = (flags >> 8) & 0xff; rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
+    rc.moduli_structured = P->moduli_structured;
     int rows = 0;
     if (P->mesh.dim == 2) { PoroElasticProblem<2> prob(*P, device, operator_mode); rows = prob.run(rc, trace, max_rows); if (ctx_out) *ctx_out = prob.release(); }
     else { PoroElasticProblem<3> prob(*P, device, operator_mode); rows = prob.run(rc, trace, max_rows); if (ctx_out) *ctx_out = prob.release(); }
@@ -310,6 +314,7 @@ int poro_host_run_adaptive(void *problem_data, int device, int operator_mode, do
     auto *P = static_cast<ProblemData *>(problem_data);
     RunControls rc; rc.p_init = p_init; rc.time_step = dt; rc.n_steps = n_steps; rc.fss_tol = fss_tol; rc.pressure_tol = pressure_tol;
     rc.max_fss_iterations = max_fss; rc.max_pressure_iterations = max_pres; rc.abs_tol_u = abs_u; rc.rel_tol_u = rel_u; rc.max_iter = max_it; rc.preconditioner = preconditioner; rc.coupled_fss = (flags & 1) != 0; rc.incremental_strain = (flags & 2) != 0; rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) rc.preconditioner_p = PORO_PREC_TWO_LEVEL; rc.atomic_scatter = (flags & 32) != 0; rc.fdm_fp32 = (flags & 64) != 0; rc.hybrid_operator = (flags & 128) != 0; rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; rc.chebyshev_degree = (flags >> 8) & 0xff; rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
+    rc.moduli_structured = P->moduli_structured;
     if (refine_every < 0) throw std::runtime_error("run_adaptive: refine_every must be >= 0");
     rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
     int rows = 0;
@@ -333,6 +338,7 @@ void *poro_host_runner_create(void *problem_data, int device, int operator_mode,
     auto *R = new HostRunner(); R->dim = P->mesh.dim;
     R->rc.p_init = p_init; R->rc.time_step = dt; R->rc.fss_tol = fss_tol; R->rc.pressure_tol = pressure_tol; R->rc.max_fss_iterations = max_fss;
     R->rc.max_pressure_iterations = max_pres; R->rc.abs_tol_u = abs_u; R->rc.rel_tol_u = rel_u; R->rc.max_iter = max_it; R->rc.preconditioner = preconditioner; R->rc.coupled_fss = (flags & 1) != 0; R->rc.incremental_strain = (flags & 2) != 0; R->rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) R->rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) R->rc.preconditioner_p = PORO_PREC_TWO_LEVEL; R->rc.atomic_scatter = (flags & 32) != 0; R->rc.fdm_fp32 = (flags & 64) != 0; R->rc.hybrid_operator = (flags & 128) != 0; R->rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; R->rc.chebyshev_degree = (flags >> 8) & 0xff; R->rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
+    R->rc.moduli_structured = P->moduli_structured;
     if (R->dim == 2) R->p2 = new PoroElasticProblem<2>(*P, device, operator_mode); else R->p3 = new PoroElasticProblem<3>(*P, device, operator_mode);
     return R;
   } catch (const std::exception &e) { g_err = e.what(); return nullptr; }

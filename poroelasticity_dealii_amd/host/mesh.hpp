@@ -504,6 +504,7 @@ struct ProblemData {
 
   // Lame lambda and shear modulus G of the displacement system (the two come together)
   std::vector<double> cell_lambda, cell_G;
+  bool moduli_structured = false;   // PORO_MODULI_OP_STRUCTURED for the contexts a run creates from this problem (host_capi.cpp: the run entry points copy it into RunControls)
   void set_cell_moduli(const double *lam, const double *G, int64_t n) {
     if (!lam && !G) { cell_lambda.clear(); cell_G.clear(); return; }
     if (!lam || !G) throw std::runtime_error("set_cell_moduli: lambda and G come together");

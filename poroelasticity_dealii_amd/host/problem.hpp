@@ -54,6 +54,7 @@ struct RunControls {
   int preconditioner_p = -1;                                        // pressure / projection solves; -1 = fast diagonalisation where the context supports it, else the two-level form, else Jacobi
   bool fdm_fp32 = false;                                            // PORO_FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (elsewhere no effect).  Never chosen automatically
   bool fdm_per_direction = false;                                   // PORO_FDM_FORM_PER_DIRECTION: the block FDM's contiguous passes on single-rank 3D boxes whose directions are not all mirror-symmetric (elsewhere no effect).  Never chosen automatically
+  bool moduli_structured = false;                                   // PORO_MODULI_OP_STRUCTURED: the structured operator on single-rank uniform 3D boxes with moduli layered along z, matrix-free (elsewhere no effect).  Never chosen automatically
   bool atomic_scatter = false;                                      // general meshes, matrix-free: PORO_SCATTER_ATOMIC (one launch per operator application; not bitwise reproducible).  Never chosen automatically
   bool hybrid_operator = false;                                     // refined boxes, matrix-free: PORO_OPFORM_HYBRID (structured kernel on the coarse box + general kernels on the fine cells); a no-op on box-tagged meshes, an error on meshes that cannot take it.  Never chosen automatically
   int refine_every = 0;                                             // refine_mesh when time_step_number % refine_every == 0 (the reference hard-wires 5, PoroelasticityFSS.h:333); 0 = never
@@ -211,6 +212,7 @@ template <int dim> class PoroElasticProblem {
     if (scatter != PORO_SCATTER_COLOURED || rc.atomic_scatter) check(poro_ctx_set_scatter_mode(fresh.c, rc.atomic_scatter ? PORO_SCATTER_ATOMIC : scatter), "ctx_set_scatter_mode");
     if (fdm_req != PORO_FDM_FP64) check(poro_ctx_set_fdm_precision(fresh.c, fdm_req), "ctx_set_fdm_precision");
     if (rc.fdm_per_direction) check(poro_ctx_set_fdm_form(fresh.c, PORO_FDM_FORM_PER_DIRECTION), "ctx_set_fdm_form");      // (next to the FDM precision: the new context takes the requested form of the block FDM)
+    if (rc.moduli_structured) check(poro_ctx_set_moduli_operator(fresh.c, PORO_MODULI_OP_STRUCTURED), "ctx_set_moduli_operator");      // (recorded; a refined mesh has no box tag and keeps the cell loop)
     int32_t form = PORO_OPFORM_GENERAL;
     check(poro_ctx_get_operator_form(ctx, &form, nullptr, nullptr), "ctx_get_operator_form");
     if (form != PORO_OPFORM_GENERAL || rc.hybrid_operator) check(poro_ctx_set_operator_form(fresh.c, rc.hybrid_operator ? PORO_OPFORM_HYBRID : form), "ctx_set_operator_form");
@@ -344,6 +346,7 @@ template <int dim> class PoroElasticProblem {
     if (rc.atomic_scatter) check(poro_ctx_set_scatter_mode(context(), PORO_SCATTER_ATOMIC), "ctx_set_scatter_mode");
     if (rc.fdm_fp32) check(poro_ctx_set_fdm_precision(context(), PORO_FDM_FP32), "ctx_set_fdm_precision");
     if (rc.fdm_per_direction) check(poro_ctx_set_fdm_form(context(), PORO_FDM_FORM_PER_DIRECTION), "ctx_set_fdm_form");
+    if (rc.moduli_structured) check(poro_ctx_set_moduli_operator(context(), PORO_MODULI_OP_STRUCTURED), "ctx_set_moduli_operator");
     if (rc.hybrid_operator) check(poro_ctx_set_operator_form(context(), PORO_OPFORM_HYBRID), "ctx_set_operator_form");
     choose_preconditioners(rc);
     setup_dofs();                                          // :308

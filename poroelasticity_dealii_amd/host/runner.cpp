@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -30,7 +30,7 @@
 using namespace poro_host;
 
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
-                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] "
+                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
 // TOP=V[:V...][,TOP=V[:V...]...], one array of `fields` per number of an item (the tops first): appends every item.  False unless every item has that shape, every number
@@ -52,7 +52,7 @@ static bool positive(double v) { return v > 0 && std::isfinite(v); }
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl << kUsage << std::endl; return 1; }   // parse_command_line.h:9-13 (the usage line is this driver's)
-  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false, fdm_per_direction = false;
+  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false, fdm_per_direction = false, moduli_structured = false;
   int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   std::vector<double> layer_top, layer_value;
@@ -76,6 +76,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--hybrid-operator")) hybrid_operator = true; // refined boxes (--refine-every), --matrix-free: the box's structured kernel + the general kernels on the fine cells only; no effect on box-tagged meshes, an error where the mesh cannot take it
     else if (!std::strcmp(argv[i], "--fdm-fp32")) fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
     else if (!std::strcmp(argv[i], "--fdm-per-direction")) fdm_per_direction = true;   // with --block-fdm / --fastest: the per-direction form of the block FDM (single-rank 3D boxes whose directions are not all mirror-symmetric; elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--moduli-structured")) moduli_structured = true;   // with --moduli-layers and --matrix-free: the structured operator on uniform 3D boxes whose layers follow the cell layers of z (elsewhere no effect)
     else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) refine_every = std::atoi(argv[++i]);            // 0 = never (default)
     else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) coarsen_fraction = std::atof(argv[++i]);
@@ -141,7 +142,7 @@ int main(int argc, char **argv) {
       P.set_permeability_tensor_layers((int)tensor_top.size(), tensor_top.data(), tensor_k[0].data(), tensor_k[1].data(), data.dim == 3 ? tensor_k[2].data() : nullptr);
     }
     if (!moduli_top.empty()) P.set_moduli_layers((int)moduli_top.size(), moduli_top.data(), moduli_young.data(), moduli_poisson.data());
-    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction;
+    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction; rc.moduli_structured = moduli_structured;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
     rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
@@ -156,6 +157,11 @@ int main(int argc, char **argv) {
         int32_t kind = 0;
         if (poro_ctx_get_cell_moduli(prob.context(), nullptr, nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
         os << "moduli layers: " << moduli_top.size() << ", field kind " << kind << "; displacement preconditioner: " << prec_name[prob.displacement_solver.control.preconditioner];
+        if (moduli_structured) {           // (only with the option) what an operator application runs on the present context
+          int32_t req = 0, eff = 0;
+          if (poro_ctx_get_moduli_operator(prob.context(), &req, &eff) != 0) throw std::runtime_error(poro_last_error());
+          os << "; moduli operator: " << (eff == PORO_MODULI_OP_STRUCTURED ? "structured" : "cell loop");
+        }
       };
       auto tensor_line = [&](std::ostream &os) {            // likewise the tensor's kind and the pressure preconditioner chosen for it
         int32_t kind = 0;
