@@ -559,6 +559,28 @@ enum { PORO_MODULI_OP_CELLS = 0, PORO_MODULI_OP_STRUCTURED = 1 };
 int  poro_ctx_set_moduli_operator(poro_ctx *ctx, int32_t form);
 int  poro_ctx_get_moduli_operator(poro_ctx *ctx, int32_t *requested, int32_t *effective);
 
+/* Gravity: body force and Darcy gravity flux (appended entry points, no struct changes: PORO_ABI_VERSION stays 4).  Off by default - the reference's body force is
+ * identically zero and that stays the parity definition.  With a gravity vector g, bulk density rho_b (one scalar, or one value per cell) and fluid density
+ * rho_f:
+ *   displacement right-hand side   b_i += sum_c rho_b,c int_c g . phi_i                                   (beside the tractions)
+ *   Darcy's law                    q = -kappa (grad p - rho_f g), so the pressure residual becomes R = -((M t + kappa K p) + (src + f_g)),
+ *                                  f_g[i] = -sum_c rho_f int_c (kappa_c g) . grad(phi_i),  kappa_c = poro_material.k_over_mu, the per-cell k / mu or its diagonal tensor
+ *                                  (kappa_c g componentwise), whichever the context holds.  For p = rho_f g . x + const the flux part of R vanishes on every row.
+ * Both vectors are constant in time: they are built when a setting changes and summed into constant vectors the time step reads anyway (the traction vector; the source
+ * vector of the residual), so a step costs what it cost, and without gravity every result is bitwise what it was.  PORO_VEC_SOURCE_P keeps meaning the well alone.
+ * poro_ctx_set_gravity: g is [dim]; NULL or all zeros switches gravity off (the earlier bits come back).  bulk_density: the scalar rho_b (>= 0); fluid_density: rho_f
+ *   (>= 0; 0: no flux term).  Any time; the next poro_disp_assemble_system rebuilds the load vector alone (not the matrix, the diagonal, the lifting or the tables of
+ *   PORO_PREC_FDM) whatever its rebuild_matrix says, the next poro_pres_assemble_residual reads the new flux.  Works on slab and general partitions: both vectors are the
+ *   rank's partial sums over its cells, completed by the interface sums of the right-hand side and of the residual.
+ * poro_ctx_set_cell_density: rho[n_cells] > 0 in the descriptor's cell order replaces the scalar rho_b (NULL: back to it).  One rank only.  A refused call (wrong count, a
+ *   value that is not finite and > 0 - the message names the cell) leaves the context as it was.  `kind` of the getter as for the other per-cell fields.
+ * poro_get_gravity_vectors: the two vectors alone, without tractions and well (zeros while off); either pointer may be NULL. */
+int  poro_ctx_set_gravity(poro_ctx *ctx, const double *g /* [dim] or NULL */, double bulk_density, double fluid_density);
+int  poro_ctx_get_gravity(poro_ctx *ctx, double *g /* [dim], may be NULL */, double *bulk_density, double *fluid_density, int32_t *on);
+int  poro_ctx_set_cell_density(poro_ctx *ctx, const double *rho /* [n_cells], NULL: back to the scalar */, int64_t n_cells);
+int  poro_ctx_get_cell_density(poro_ctx *ctx, double *out /* [n_cells], may be NULL */, int64_t n_cells, int32_t *kind);
+int  poro_get_gravity_vectors(poro_ctx *ctx, double *body_u /* [n_dofs_u] or NULL */, double *flux_p /* [n_dofs_p] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,7 +114,8 @@ HIP_SYMBOLS = [
     "poro_ctx_set_cell_permeability", "poro_ctx_get_cell_permeability", "poro_pres_apply_jacobian",
     "poro_ctx_set_cell_permeability_tensor", "poro_ctx_get_cell_permeability_tensor",
     "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli",
-    "poro_ctx_set_moduli_operator", "poro_ctx_get_moduli_operator"]
+    "poro_ctx_set_moduli_operator", "poro_ctx_get_moduli_operator",
+    "poro_ctx_set_gravity", "poro_ctx_get_gravity", "poro_ctx_set_cell_density", "poro_ctx_get_cell_density", "poro_get_gravity_vectors"]
 
 _hip = None
 _host = None
@@ -188,6 +189,11 @@ def load_hip():
         L.poro_pres_apply_jacobian.argtypes = [C.c_void_p, _dp, _dp]
         L.poro_ctx_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
         L.poro_ctx_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _ip]
+        L.poro_ctx_set_gravity.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double]
+        L.poro_ctx_get_gravity.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+        L.poro_ctx_set_cell_density.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_ctx_get_cell_density.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
+        L.poro_get_gravity_vectors.argtypes = [C.c_void_p, _dp, _dp]
         _hip = L
     return _hip
 
@@ -244,6 +250,13 @@ def load_host():
         L.poro_host_set_moduli_structured.argtypes = [C.c_void_p, C.c_int]
         L.poro_host_get_cell_moduli.restype = C.c_int64
         L.poro_host_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp]
+        L.poro_host_set_gravity.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int]
+        L.poro_host_get_gravity.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+        L.poro_host_set_cell_density.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.poro_host_set_density_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.poro_host_inherit_cell_density.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_host_get_cell_density.restype = C.c_int64
+        L.poro_host_get_cell_density.argtypes = [C.c_void_p, _dp]
         L.poro_host_partition.restype = C.c_void_p
         L.poro_host_partition.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.poro_host_partition_ex.restype = C.c_void_p
@@ -558,6 +571,43 @@ class Problem:
         f = self._carried("cell_moduli", 2)
         return f and tuple(f)
 
+    def set_gravity(self, g, fluid_density=0.0, bulk_density=None, hydrostatic_init=False):
+        """extension: gravity.  g: the vector, one component per dimension (None or zeros: off); fluid_density: rho_f of the Darcy gravity flux q = -kappa (grad p - rho_f g)
+        (0: no flux term); bulk_density: the scalar rho_b of the body force rho_b g (None: keep the problem's, 2700 at first - the default of "Properties/Bulk density");
+        hydrostatic_init: a run starts from p_init + rho_f g . (x - x_top), x_top the vertex furthest against g.  Kept with the problem like the per-cell fields: Context,
+        run_problem and Runner hand it to the contexts they create, an adaptive run to every new mesh"""
+        gp = None
+        if g is not None:
+            ga, gp = _arr_d(g)
+            if ga.size != self.desc.dim:
+                raise ValueError(f"set_gravity: g needs {self.desc.dim} components")
+        return self._host("set_gravity", gp, float(fluid_density), -1.0 if bulk_density is None else float(bulk_density), int(bool(hydrostatic_init)))
+
+    def gravity(self):
+        """(g[dim], fluid_density, bulk_density, hydrostatic_init) this problem carries; g is None while gravity is off"""
+        g, rf, rb, hy = (C.c_double * 3)(), C.c_double(), C.c_double(), C.c_int32()
+        on = load_host().poro_host_get_gravity(self.handle, g, C.byref(rf), C.byref(rb), C.byref(hy))
+        return (np.array(g[:self.desc.dim]) if on else None), rf.value, rb.value, bool(hy.value)
+
+    def set_cell_density(self, values):
+        """extension: per-cell bulk density of the body force, one value per cell of this mesh (None: back to the scalar).  Kept and carried like the other per-cell fields"""
+        keep, args = _field_args(values)
+        return self._host("set_cell_density", *args)
+
+    def set_density_layers(self, layers):
+        """the same by layers [(top, rho), ...] along the slowest direction, tops ascending, chosen by cell centres as set_permeability_layers does"""
+        top, pt = _arr_d([l[0] for l in layers]); val, pv = _arr_d([l[1] for l in layers])
+        return self._host("set_density_layers", len(layers), pt, pv)
+
+    def inherit_cell_density(self, old):
+        """what an adaptive run does with the density: a child takes its parent's value, a coarsened parent the mean of its children; g and the scalar densities go along"""
+        return self._host("inherit_cell_density", old.handle)
+
+    def cell_density(self):
+        """the per-cell bulk density this problem carries, or None"""
+        f = self._carried("cell_density", 1)
+        return f and f[0]
+
     def close(self):
         if self.handle:
             if self.owned:
@@ -581,7 +631,8 @@ class Context:
             self._chk(self.L.poro_ctx_create(problem.desc_ptr, device, operator_mode, C.byref(p)))
             ptr = p
             # the per-cell fields the problem carries (Problem.set_cell_permeability / set_permeability_layers, set_cell_moduli / set_moduli_layers)
-            for name, hand_over in (("cell_permeability", self.set_cell_permeability), ("cell_permeability_tensor", self.set_cell_permeability_tensor), ("cell_moduli", self.set_cell_moduli)):
+            for name, hand_over in (("cell_permeability", self.set_cell_permeability), ("cell_permeability_tensor", self.set_cell_permeability_tensor), ("cell_moduli", self.set_cell_moduli),
+                                    ("cell_density", self.set_cell_density), ("gravity", lambda g, rho_f, rho_b, _hyd: g is not None and self.set_gravity(g, rho_b, rho_f))):
                 carried = getattr(problem, name, None)                 # (a Problem; descriptor holders of other kinds carry no field)
                 field = carried() if carried else None
                 if field is not None:
@@ -718,6 +769,39 @@ class Context:
     def get_cell_moduli(self):
         """(lame_lambda or None, shear_G or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid, 2 general"""
         return self._get_field(self.L.poro_ctx_get_cell_moduli, 2)
+
+    def set_gravity(self, g, bulk_density, fluid_density=0.0):
+        """gravity vector g (one component per dimension; None or zeros: off), the scalar bulk density rho_b of the body force and the fluid density rho_f of the Darcy
+        gravity flux (0: none).  Right-hand sides only: b_i += sum_c rho_b int_c g . phi_i, and R = -((M t + kappa K p) + (src + f_g)) with
+        f_g[i] = -sum_c rho_f int_c (kappa_c g) . grad(phi_i).  Any time; the next disp_assemble_system rebuilds the load vector alone, whatever its `rebuild` says"""
+        gp = None
+        if g is not None:
+            ga, gp = _arr_d(g)
+            if ga.size != self.dim:
+                raise ValueError(f"set_gravity: g needs {self.dim} components")
+        self._chk(self.L.poro_ctx_set_gravity(self.ptr, gp, float(bulk_density), float(fluid_density)))
+
+    def get_gravity(self):
+        """(g[dim], bulk_density, fluid_density, on)"""
+        g, rb, rf, on = np.zeros(self.dim), C.c_double(), C.c_double(), C.c_int32()
+        self._chk(self.L.poro_ctx_get_gravity(self.ptr, g.ctypes.data_as(_dp), C.byref(rb), C.byref(rf), C.byref(on)))
+        return g, rb.value, rf.value, bool(on.value)
+
+    def set_cell_density(self, values):
+        """per-cell bulk density in place of the scalar of set_gravity, one value per cell in the descriptor's cell order (None: back to the scalar).  One rank.  Raises on a
+        wrong length and on a value that is not finite and > 0 (the message names the cell); the context then stays as it was"""
+        keep, args = _field_args(values)
+        self._chk(self.L.poro_ctx_set_cell_density(self.ptr, *args))
+
+    def get_cell_density(self):
+        """(values or None, kind): kind 0 no field, 1 layered along the slowest direction of a box / tensor-product grid, 2 general"""
+        return self._get_field(self.L.poro_ctx_get_cell_density, 1)
+
+    def gravity_vectors(self):
+        """(body_u[n_u], flux_p[n_p]): the two gravity vectors alone, without tractions and well source (zeros while gravity is off / the fluid density is 0)"""
+        b, f = np.empty(self.n_u), np.empty(self.n_p)
+        self._chk(self.L.poro_get_gravity_vectors(self.ptr, b.ctypes.data_as(_dp), f.ctypes.data_as(_dp)))
+        return b, f
 
     def pres_apply_jacobian(self, x):
         """y = J x with the operator the Krylov solver of pres_solve applies (the stencil on matrix-free boxes, CSR elsewhere); after pres_assemble_jacobian"""
@@ -898,13 +982,24 @@ def rccl_unique_id():
     return buf.raw
 
 
+def _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init):
+    """the gravity arguments of run_problem / Runner -> Problem.set_gravity / set_cell_density on `problem`, which keeps them; nothing given: nothing touched"""
+    if gravity is None and fluid_density is None and density is None and not hydrostatic_init:
+        return
+    g0, rho_f0, _, _ = problem.gravity()
+    scalar = density is not None and np.ndim(density) == 0
+    problem.set_gravity(g0 if gravity is None else gravity, rho_f0 if fluid_density is None else fluid_density, float(density) if scalar else None, hydrostatic_init)
+    if density is not None and not scalar:
+        problem.set_cell_density(density)
+
+
 _FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit flags word (bits 0-7 and the Chebyshev fields from bit 8 and bit 16 are taken)
 
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                 abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, refine_every=None, refine_fraction=0.6, coarsen_fraction=0.4, permeability=None, permeability_tensor=None,
-                moduli_structured=False):
+                moduli_structured=False, gravity=None, fluid_density=None, density=None, hydrostatic_init=False):
     """PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:294-415) through the C++ host driver; returns (trace, Context).
     refine_every = N (not None) goes through the adaptive entry: refine_mesh every N-th step (:333-340; 0 = never) on a mask- or block-refined box; the returned
     Context then belongs to the mesh the run ended on (Context.problem, a new Problem the caller closes when the mesh was refined at least once).
@@ -913,9 +1008,12 @@ def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fs
     moduli_structured=True: MODULI_OP_STRUCTURED for the displacement operator (Context.set_moduli_operator; requested on every adapted mesh, where it has no effect:
     a refined mesh has no box tag).
     permeability: per-cell k / mu (Problem.set_cell_permeability on `problem`, which keeps it), carried over to every adapted mesh.
-    permeability_tensor: per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim) (Problem.set_cell_permeability_tensor), likewise."""
+    permeability_tensor: per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim) (Problem.set_cell_permeability_tensor), likewise.
+    gravity: the vector g (Problem.set_gravity on `problem`, which keeps it); fluid_density: rho_f of the Darcy gravity flux; density: the bulk density, one scalar or one
+    value per cell (Problem.set_cell_density); hydrostatic_init: start from p_init + rho_f g . (x - x_top) instead of the uniform p_init.  Carried to every adapted mesh."""
     H = load_host()
     problem.set_moduli_structured(moduli_structured)
+    _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init)
     if permeability is not None:
         problem.set_cell_permeability(permeability)
     if permeability_tensor is not None:
@@ -945,8 +1043,10 @@ class Runner:
 
     def __init__(self, problem, device=0, operator_mode=OP_MATRIX_FREE, p_init=10e6, dt=60.0, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
                  abs_u=1e-12, rel_u=0.0, max_it=1000, prec=PREC_JACOBI, coupled_fss=False, incremental_strain=False, reduction=False, cheb_degree=0, cheb_ratio=0, jacobi_p=False, two_level_p=False,
-                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None, moduli_structured=False):
+                 atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None, moduli_structured=False,
+                 gravity=None, fluid_density=None, density=None, hydrostatic_init=False):
         self.H = load_host()
+        _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init)      # Problem.set_gravity / set_cell_density on `problem`, which keeps them; adapt() carries them to every new mesh
         problem.set_moduli_structured(moduli_structured)      # MODULI_OP_STRUCTURED (Context.set_moduli_operator), requested again on every mesh adapt() builds
         if permeability_tensor is not None:      # per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim): Problem.set_cell_permeability_tensor, kept and carried like the scalar field
             problem.set_cell_permeability_tensor(permeability_tensor)

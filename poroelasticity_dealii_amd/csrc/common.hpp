@@ -326,6 +326,17 @@ struct poro_ctx {
   // requested form of the displacement operator on a box with per-cell moduli (poro_ctx_set_moduli_operator): PORO_MODULI_OP_CELLS, the general cell loop, or
   // PORO_MODULI_OP_STRUCTURED, kernels_kron_lm.hip where it applies.  Never chosen automatically; stays through field changes
   int moduli_op = 0;
+  // Gravity (poro_ctx_set_gravity, poro_ctx_set_cell_density; ctx_fields.hip, kernels_gravity.hip).  on: g has a non-zero component.  dens: the per-cell bulk density
+  // (one rank), cell: [n_cells] in the caller's cell order, lattice: the same in lattice cell order (uniform boxes); kind 0: the scalar rho_b.  body_u / flux_p: the two
+  // gravity vectors alone (rank-partial sums on a partition), built while gravity is on.  They are folded into constant vectors the step kernels read anyway: body_u is
+  // summed into neumann_u behind the tractions (assemble_loads_u), src_p = src_local + flux_p takes the place of src_local in the pressure residual (source_p below) -
+  // src_local and PORO_VEC_SOURCE_P keep meaning the well alone.  loads_stale: neumann_u and rhs_u_flags have to be rebuilt before the next right-hand side
+  struct Gravity {
+    bool on = false, loads_stale = false; double g[3] = {0, 0, 0}, rho_b = 0, rho_f = 0;
+    struct Density : poro::CellField<1> { poro::DevBuf<double> cell, lattice; } dens;
+    poro::DevBuf<double> body_u, flux_p, src_p;
+    bool flux_on() const { return on && rho_f != 0; }
+  } grav;
 };
 
 namespace poro {
@@ -439,6 +450,15 @@ void asm_p_matrices(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64
                     int ncomp = 1);
 void asm_proj_rhs(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *u, int n_comp, const int32_t *comps /*host*/,
                   double *const *rhs /*host array of device ptrs*/);
+
+// ---- kernels_gravity.hip: the gravity vectors (set-up only) ------------------------------------------
+// out = the body-force vector of a uniform box, out[node * dim + d] = g_d sum_c rho_c int_c phi_node; rho_lattice: per cell in lattice order, or null: rho0
+void box_body_u(hipStream_t s, int dim, int k_u, const BoxDev &box, const double *rho_lattice, double rho0, const double *g, double *out);
+// out = -rho_f sum_c int_c (kappa_c g) . grad(phi_i) on a uniform box; kap_lattice: ncomp planes of per-cell weights in lattice order (ncomp = 1 | dim), or null: kap0
+void box_gravity_p(hipStream_t s, int dim, const BoxDev &box, const double *kap_lattice, int ncomp, double kap0, double rho_f, const double *g, double *out);
+// the same two on any mesh, added into `out` over the cells of one colour; cell_rho: [n_cells] or null: rho0; cell_w: [n_cells][ncomp] or null: kap0
+void asm_u_body(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *cell_rho, double rho0, const double *g, double *out);
+void asm_p_gravity(hipStream_t s, const AsmArgs &a, const int32_t *cells, int64_t n_cells, const double *cell_w, int ncomp, double kap0, double rho_f, const double *g, double *out);
 
 // ---- kernels_mfg.hip: matrix-free operator on general meshes (one wave per cell; coloured scatter, or one launch with an atomic scatter) ----------------
 bool mfg_sf_tables_match(const poro_fe_tables &f, int dim, int k);

@@ -508,6 +508,21 @@ int solve_q1(poro_ctx *c, const Q1System &q, const poro_solver_opts *opts, poro_
 
 }  // namespace
 
+// The constant load vector of the displacement right-hand side and what is derived from it: neumann_u = the tractions, then (gravity on) + the body-force vector, always in
+// this order from zero, so that the bits depend on the settings alone and not on the order of the calls; then the line flags of the box kernel.  Called where the
+// matrix block is rebuilt and where gravity or the density changed (Gravity::loads_stale): the matrix, the diagonal, the lifting and the FDM tables stay
+void poro::ctx_detail::assemble_loads_u(poro_ctx *c) {
+  hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
+  c->neumann_u.zero(s);
+  asm_u_neumann(s, a, c->bface_order.p, c->bface_group_off, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
+  if (c->grav.on) la_axpy(s, c->neumann_u.p, 1.0, c->grav.body_u.p, c->n_u);      // (never without gravity: no +0.0 enters the default)
+  if (c->box_asm) {     // lift_u and neumann_u are final here: which of their lines the right-hand side kernel has to read
+    if (c->rhs_u_flags.n != (size_t)box_rhs_u_flag_count(c->n_u)) c->rhs_u_flags.alloc((size_t)box_rhs_u_flag_count(c->n_u));
+    box_rhs_u_flags(s, c->lift_u.p, c->neumann_u.p, c->n_u, c->rhs_u_flags.p);
+  }
+  c->grav.loads_stale = false;
+}
+
 // ======================================= extern "C" ================================================================
 extern "C" {
 
@@ -829,7 +844,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
     hipStream_t s = c->stream; const AsmArgs a = asm_args(c);
     if (rebuild_matrix || !c->matrix_built) {      // (poro_ctx_set_cell_moduli clears matrix_built: the next call rebuilds whatever the flag says)
       Timed tm(c, "assemble_u_matrix");
-      c->lift_u.zero(s); c->neumann_u.zero(s);
+      c->lift_u.zero(s);                                                         // (neumann_u: assemble_loads_u below)
       if (c->operator_mode == PORO_OP_CSR && c->box_asm && !c->mod.kind) {
         // uniform box: one element matrix, every CSR entry written once by its owner (kernels_box.hip); the lifting -(A_full g) comes
         // from the unconstrained structured operator
@@ -859,11 +874,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
         if (c->mf_variant == 1 && kron_supported(c->dim, c->k_u) && !std::getenv("PORO_DIAG_SKIP_SELFCHECK")) check_sum_factorised_operator(c);
         lifting_from_wh(c);
       }
-      asm_u_neumann(s, a, c->bface_order.p, c->bface_group_off, c->bface_cell.p, c->bface_local.p, c->bface_id.p, c->n_neumann, c->neu_label.p, c->neu_comp.p, c->neu_val.p, c->neumann_u.p);
-      if (c->box_asm) {     // lift_u and neumann_u are final here: which of their lines the right-hand side kernel has to read
-        if (c->rhs_u_flags.n != (size_t)box_rhs_u_flag_count(c->n_u)) c->rhs_u_flags.alloc((size_t)box_rhs_u_flag_count(c->n_u));
-        box_rhs_u_flags(s, c->lift_u.p, c->neumann_u.p, c->n_u, c->rhs_u_flags.p);
-      }
+      assemble_loads_u(c);
       if (!c->diag_u.p) c->diag_u.alloc(c->n_u);
       la_copy(s, c->diag_u.p, c->diag_u_local.p, c->n_u);
       exchange_add(c, c->diag_u.p, c->n_u, c->comm.part.plane_u);
@@ -874,6 +885,7 @@ int poro_disp_assemble_system(poro_ctx *c, int rebuild_matrix) {
       if (c->operator_mode == PORO_OP_MATRIX_FREE && box_fast_u(c)) build_diag_dictionary(c);
       c->matrix_built = true; c->ilu_u_valid = false; c->cheb_lmax = 0;
     }
+    if (c->grav.loads_stale) assemble_loads_u(c);      // gravity or the density changed since: the load vector alone, the matrix block stays
     {
       Timed tm(c, "assemble_u_rhs");
       double *rhs = vec(c, PORO_VEC_RHS_U);
@@ -932,14 +944,15 @@ int poro_pres_assemble_residual(poro_ctx *c, double dt, double *l2) {
   return guarded([&] {
     PORO_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream; double *R = vec(c, PORO_VEC_RESIDUAL_P);
+    const double *src = c->grav.flux_on() ? c->grav.src_p.p : c->src_local.p;      // the well source alone, or (gravity with a fluid density) well + Darcy gravity flux, summed at set-up
     {
       Timed tm(c, "pressure_residual");
       la_pressure_tmp(s, c->tmp_p.p, vec(c, PORO_VEC_EPSV), vec(c, PORO_VEC_EPSV0), vec(c, PORO_VEC_P), vec(c, PORO_VEC_P_OLD), c->mat.biot_alpha / dt, 1. / c->mat.biot_M / dt, c->n_p);
       // a per-cell k / mu: Kp holds K_kappa (coefficient 1), the box stencil reads the field
       if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
-        if (c->perm.kind) p_residual_stencil_var(s, c->dim, c->box, c->perm.lattice.p, c->perm.ncomp, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
-        else p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
-      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), c->src_local.p, R);
+        if (c->perm.kind) p_residual_stencil_var(s, c->dim, c->box, c->perm.lattice.p, c->perm.ncomp, c->tmp_p.p, vec(c, PORO_VEC_P), src, R);
+        else p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), src, R);
+      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->tmp_p.p, vec(c, PORO_VEC_P), src, R);
     }
     la_cons_reduce(s, c->cons_p, R);                                              // constraints.condense(residual) (:153); partial rows first, interface sums after
     exchange_add(c, R, c->n_p, c->comm.part.plane_p);

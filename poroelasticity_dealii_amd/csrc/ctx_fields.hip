@@ -1,6 +1,7 @@
 // The per-cell coefficient fields of a context: k / mu of the pressure system (poro_ctx_set / get_cell_permeability) or its diagonal tensor diag(kx, ky[, kz]) / mu
 // (poro_ctx_set / get_cell_permeability_tensor) - one field, c->perm, of 1 or dim components - and Lame lambda, shear G of the displacement system
-// (poro_ctx_set / get_cell_moduli).  What they share - the refusals, the caller's cell order -> lattice order, the classification by layers, the host state - is
+// (poro_ctx_set / get_cell_moduli) - and gravity with its per-cell bulk density (poro_ctx_set / get_gravity, poro_ctx_set / get_cell_density), which changes right-hand
+// sides only.  What they share - the refusals, the caller's cell order -> lattice order, the classification by layers, the host state - is
 // cell_field.hpp; each setter adds its value checks, its device state and what it invalidates.  A setter that throws leaves the context as it was: the device state
 // changes first, then the host state, then the caches go
 #include <cmath>
@@ -51,6 +52,42 @@ void invalidate_pressure(poro_ctx *c) {
   c->jac_dt = -1; c->ilu_J_valid = false;
   for (auto &L : c->perm.line) { L.built = false; L.a = -1; }
 }
+// ---- gravity: the two vectors from the present settings (kernels_gravity.hip).  Uniform boxes take the closed-form node kernels, every other mesh the coloured cell loop
+int64_t box_nodes(const poro_ctx *c, int k) { return (int64_t)(k * c->box.n[0] + 1) * (k * c->box.n[1] + 1) * (c->dim == 3 ? k * c->box.n[2] + 1 : 1); }
+// body_u = sum_c rho_c int_c g . phi_i; the load vector that carries it is rebuilt by the next poro_disp_assemble_system (assemble_loads_u), and only that
+void build_gravity_body(poro_ctx *c) {
+  poro_ctx::Gravity &G = c->grav; hipStream_t s = c->stream;
+  G.loads_stale = true;
+  if (!G.on) { if (G.body_u.p) { PORO_HIP(hipStreamSynchronize(s)); G.body_u.release(); } return; }
+  if (G.body_u.n != (size_t)c->n_u) G.body_u.alloc(c->n_u);
+  const double *lattice = G.dens.kind ? G.dens.lattice.p : nullptr;
+  Timed tm(c, "gravity_body_u");
+  if (c->box.enabled && (c->k_u == 1 || c->k_u == 2) && box_nodes(c, c->k_u) * c->dim == c->n_u && (!G.dens.kind || lattice)) box_body_u(s, c->dim, c->k_u, c->box, lattice, G.rho_b, G.g, G.body_u.p);
+  else {
+    const AsmArgs a = asm_args(c);
+    G.body_u.zero(s);
+    for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_u_body(s, a, cells, n_cells, G.dens.kind ? G.dens.cell.p : nullptr, G.rho_b, G.g, G.body_u.p); });
+  }
+}
+// flux_p = -sum_c rho_f int_c (kappa_c g) . grad(phi_i) with the permeability the context holds, and src_p = src_local + flux_p, what the pressure residual reads
+void build_gravity_flux(poro_ctx *c) {
+  poro_ctx::Gravity &G = c->grav; const poro_ctx::Perm &P = c->perm; hipStream_t s = c->stream;
+  if (!G.flux_on()) { if (G.flux_p.p) { PORO_HIP(hipStreamSynchronize(s)); G.flux_p.release(); G.src_p.release(); } return; }
+  if (G.flux_p.n != (size_t)c->n_p) { G.flux_p.alloc(c->n_p); G.src_p.alloc(c->n_p); }
+  const int ncomp = P.kind ? P.ncomp : 1;
+  {
+    Timed tm(c, "gravity_flux_p");
+    if (c->box.enabled && box_nodes(c, 1) == c->n_p && (!P.kind || P.lattice.p)) box_gravity_p(s, c->dim, c->box, P.kind ? P.lattice.p : nullptr, ncomp, c->mat.k_over_mu, G.rho_f, G.g, G.flux_p.p);
+    else {
+      const AsmArgs a = asm_args(c);
+      G.flux_p.zero(s);
+      for_each_colour(c, [&](const int32_t *cells, int64_t n_cells) { asm_p_gravity(s, a, cells, n_cells, P.kind ? P.cell.p : nullptr, ncomp, c->mat.k_over_mu, G.rho_f, G.g, G.flux_p.p); });
+    }
+  }
+  la_copy(s, G.src_p.p, c->src_local.p, c->n_p);
+  la_axpy(s, G.src_p.p, 1.0, G.flux_p.p, c->n_p);
+}
+
 // NULL to either setter: back to poro_material.k_over_mu, the plain Laplace matrix bit for bit
 int back_to_constant(poro_ctx *c) {
   poro_ctx::Perm &P = c->perm;
@@ -58,6 +95,7 @@ int back_to_constant(poro_ctx *c) {
   assemble_laplace_p(c, nullptr);
   P.clear(); P.ncomp = 0; P.cell.release(); P.lattice.release();
   invalidate_pressure(c);
+  build_gravity_flux(c);
   return 0;
 }
 // The two setters: k_over_mu is [n_cells][ncomp], ncomp = 1 (one k / mu per cell) or dim (diag(kx, ky[, kz]) / mu, x first); `who` names the entry point in the refusals
@@ -87,6 +125,7 @@ int set_permeability(poro_ctx *c, const double *k_over_mu, int64_t n_cells, int 
     assemble_laplace_p(c, P.cell.p, ncomp);
     static_cast<CellField<3> &>(P) = std::move(F); P.ncomp = ncomp;
     invalidate_pressure(c);
+    build_gravity_flux(c);      // (while gravity is on: the Darcy gravity flux follows the field)
     return 0;
   });
 }
@@ -180,5 +219,84 @@ int poro_ctx_set_cell_moduli(poro_ctx *c, const double *lame_lambda, const doubl
   });
 }
 int poro_ctx_get_cell_moduli(poro_ctx *c, double *lambda_out, double *G_out, int64_t n, int32_t *kind) { return give(c, &poro_ctx::mod, {lambda_out, G_out}, n, kind, "poro_ctx_get_cell_moduli", "n"); }
+
+// Gravity.  Right-hand sides only: the body-force vector rides in the load vector behind the tractions, the Darcy gravity flux beside the well source; nothing the operators,
+// the preconditioners or the Krylov drivers read changes, and nothing is invalidated but the load vector (rebuilt by the next poro_disp_assemble_system)
+int poro_ctx_set_gravity(poro_ctx *c, const double *g, double bulk_density, double fluid_density) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Gravity &G = c->grav;
+    double gv[3] = {0, 0, 0}; bool on = false;
+    for (int d = 0; g && d < c->dim; ++d) {
+      if (!std::isfinite(g[d])) throw Error("poro_ctx_set_gravity: component " + std::to_string(d) + " of g is not finite");
+      gv[d] = g[d]; on = on || g[d] != 0.0;
+    }
+    if (!(std::isfinite(bulk_density) && bulk_density >= 0)) throw Error("poro_ctx_set_gravity: bulk_density is not finite and >= 0");
+    if (!(std::isfinite(fluid_density) && fluid_density >= 0)) throw Error("poro_ctx_set_gravity: fluid_density is not finite and >= 0");
+    for (int d = 0; d < 3; ++d) G.g[d] = on ? gv[d] : 0.0;
+    G.on = on; G.rho_b = bulk_density; G.rho_f = fluid_density;
+    build_gravity_body(c); build_gravity_flux(c);
+    return 0;
+  });
+}
+int poro_ctx_get_gravity(poro_ctx *c, double *g, double *bulk_density, double *fluid_density, int32_t *on) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    for (int d = 0; g && d < c->dim; ++d) g[d] = c->grav.g[d];
+    if (bulk_density) *bulk_density = c->grav.rho_b;
+    if (fluid_density) *fluid_density = c->grav.rho_f;
+    if (on) *on = c->grav.on ? 1 : 0;
+    return 0;
+  });
+}
+// Per-cell bulk density in place of the scalar of poro_ctx_set_gravity (kept while gravity is off, used when it comes on)
+int poro_ctx_set_cell_density(poro_ctx *c, const double *rho, int64_t n_cells) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    poro_ctx::Gravity::Density &D = c->grav.dens;
+    if (!rho) {
+      if (!D.kind) return 0;
+      PORO_HIP(hipStreamSynchronize(c->stream));
+      D.clear(); D.cell.release(); D.lattice.release();
+      if (c->grav.on) build_gravity_body(c);
+      return 0;
+    }
+    refuse_partitioned(c, "poro_ctx_set_cell_density");
+    check_count(c, "poro_ctx_set_cell_density", "n_cells", n_cells);
+    for (int64_t i = 0; i < n_cells; ++i)
+      if (!(std::isfinite(rho[i]) && rho[i] > 0)) throw Error("poro_ctx_set_cell_density: value of cell " + std::to_string(i) + " is not finite and > 0");
+    CellField<1> F;
+    const auto lattice = take(c, F, {rho}, c->lines.on ? download_cell_dofs_p(c) : std::vector<int32_t>(), "poro_ctx_set_cell_density");
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    D.cell.upload(rho, (size_t)n_cells);
+    if (c->box.enabled && c->lines.on) D.lattice.upload(lattice[0]); else D.lattice.release();
+    static_cast<CellField<1> &>(D) = std::move(F);
+    if (c->grav.on) build_gravity_body(c);
+    return 0;
+  });
+}
+int poro_ctx_get_cell_density(poro_ctx *c, double *out, int64_t n_cells, int32_t *kind) {
+  if (!c || !kind) return guarded([&]() -> int { throw Error("null argument"); });
+  return guarded([&] {
+    const CellField<1> &F = c->grav.dens;
+    *kind = F.kind;
+    if (out && F.kind) { check_count(c, "poro_ctx_get_cell_density", "n_cells", n_cells); std::memcpy(out, F.host[0].data(), (size_t)n_cells * sizeof(double)); }
+    return 0;
+  });
+}
+// The two gravity vectors alone (no tractions, no well source; rank-partial sums on a partition); zeros while gravity is off or fluid_density is 0
+int poro_get_gravity_vectors(poro_ctx *c, double *body_u, double *flux_p) {
+  return guarded([&] {
+    if (!c) throw Error("null argument");
+    PORO_HIP(hipSetDevice(c->device));
+    const poro_ctx::Gravity &G = c->grav;
+    if (body_u) { if (G.on) PORO_HIP(hipMemcpyAsync(body_u, G.body_u.p, (size_t)c->n_u * sizeof(double), hipMemcpyDeviceToHost, c->stream)); else std::memset(body_u, 0, (size_t)c->n_u * sizeof(double)); }
+    if (flux_p) { if (G.flux_on()) PORO_HIP(hipMemcpyAsync(flux_p, G.flux_p.p, (size_t)c->n_p * sizeof(double), hipMemcpyDeviceToHost, c->stream)); else std::memset(flux_p, 0, (size_t)c->n_p * sizeof(double)); }
+    PORO_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+  });
+}
 
 }  // extern "C"

@@ -84,6 +84,7 @@ MfArgs mf_args(poro_ctx *c);
 void mf_operator(poro_ctx *c, const double *x, double *y, bool constrained);
 void mfg_operator(poro_ctx *c, const double *x, double *y, bool constrained);   // general cell loop, mode 0, in the context's scatter mode
 void build_spatial_cells(poro_ctx *c);
+void assemble_loads_u(poro_ctx *c);     // (ctx.hip) neumann_u = tractions (+ the body-force vector while gravity is on) and the box kernel's line flags of it
 void sync_moduli_planes(poro_ctx *c);   // (ctx_fields.hip) uploads the plane table of the structured operator for layered moduli where that form is requested and applies, drops it elsewhere
 // ---- hybrid operator form (ctx_hybrid.hip) ---------------------------------------------------------------------------------------------------
 void hybrid_enable(poro_ctx *c);                                               // derives the plan at the first call (host work, uploads, a stream synchronise) and checks it; throws where the mesh cannot take the form

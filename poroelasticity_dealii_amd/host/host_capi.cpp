@@ -246,6 +246,25 @@ int64_t poro_host_get_cell_moduli(void *h, double *lam_out, double *G_out) {
   const ProblemData &P = *static_cast<ProblemData *>(h); copy_field(P.cell_G, G_out);
   return copy_field(P.cell_lambda, lam_out);
 }
+// extension: gravity.  g[dim] (NULL or zeros: off), the fluid density of the Darcy gravity flux (0: none), the scalar bulk density (< 0: keep the present one, 2700 at
+// first) and whether a run starts from the hydrostatic pressure; kept with the problem, handed to every context the drivers create (poro_ctx_set_gravity)
+int poro_host_set_gravity(void *h, const double *g, double fluid_density, double bulk_density, int hydrostatic_init) {
+  return on_problem(h, [&](ProblemData &P) { P.set_gravity(g, fluid_density, bulk_density); P.hydrostatic_init = hydrostatic_init != 0; });
+}
+// what the problem carries: g[3], the two scalar densities, the hydrostatic start; returns 1 while some component of g is not zero
+int poro_host_get_gravity(void *h, double *g, double *fluid_density, double *bulk_density, int32_t *hydrostatic_init) {
+  const ProblemData &P = *static_cast<ProblemData *>(h);
+  for (int d = 0; g && d < 3; ++d) g[d] = P.gravity[d];
+  if (fluid_density) *fluid_density = P.fluid_density;
+  if (bulk_density) *bulk_density = P.bulk_density;
+  if (hydrostatic_init) *hydrostatic_init = P.hydrostatic_init ? 1 : 0;
+  return P.has_gravity() ? 1 : 0;
+}
+// per-cell bulk density (values == NULL: back to the scalar), by layers of the slowest direction, through a refine / coarsen pair, and what the problem carries
+int poro_host_set_cell_density(void *h, const double *values, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_density(values, n); }); }
+int poro_host_set_density_layers(void *h, int n, const double *top, const double *rho) { return on_problem(h, [&](ProblemData &P) { P.set_density_layers(n, top, rho); }); }
+int poro_host_inherit_cell_density(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_density(*static_cast<ProblemData *>(old)); }); }
+int64_t poro_host_get_cell_density(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_density, out); }
 const poro_desc *poro_host_desc(void *h) { return &static_cast<ProblemData *>(h)->d; }
 void poro_host_free(void *h) { delete static_cast<ProblemData *>(h); }
 

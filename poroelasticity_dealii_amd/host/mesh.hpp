@@ -533,6 +533,53 @@ struct ProblemData {
     cell_G = inherited(O, O.cell_G, "inherit_cell_moduli"); cell_lambda = std::move(lam);
   }
 
+  // Gravity (poro_ctx_set_gravity / poro_ctx_set_cell_density): the vector g, the fluid density rho_f of the Darcy gravity flux (0: no flux term), the scalar bulk density
+  // (the declared default of "Properties/Bulk density"; poro_run copies the parsed value) and the optional per-cell bulk density.  All zeros: no gravity, the reference's
+  // body force.  hydrostatic_init: a run starts from p_init + rho_f g . (x - x_top), x_top = the vertex furthest against g, instead of the uniform p_init
+  double gravity[3] = {0, 0, 0}, fluid_density = 0, bulk_density = 2700; bool hydrostatic_init = false;
+  std::vector<double> cell_density;
+  bool has_gravity() const { return gravity[0] != 0 || gravity[1] != 0 || gravity[2] != 0; }
+  void set_gravity(const double *g /* [dim]; null: off */, double rho_f, double rho_b /* < 0: keep the present scalar */) {
+    for (int d = 0; g && d < mesh.dim; ++d) if (!std::isfinite(g[d])) throw std::runtime_error("set_gravity: component " + std::to_string(d) + " of g is not finite");
+    if (!(std::isfinite(rho_f) && rho_f >= 0)) throw std::runtime_error("set_gravity: the fluid density is not finite and >= 0");
+    if (!std::isfinite(rho_b)) throw std::runtime_error("set_gravity: the bulk density is not finite");
+    for (int d = 0; d < 3; ++d) gravity[d] = g && d < mesh.dim ? g[d] : 0.0;
+    fluid_density = rho_f; if (rho_b >= 0) bulk_density = rho_b;
+  }
+  void set_cell_density(const double *values, int64_t n) {
+    if (!values) { cell_density.clear(); return; }
+    check_field_length("set_cell_density", n);
+    for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_density: value of cell " + std::to_string(i) + " is not finite and > 0");
+    cell_density.assign(values, values + n);
+  }
+  void set_density_layers(int n_layers, const double *top, const double *rho) {
+    if (n_layers < 1 || !top || !rho) throw std::runtime_error("set_density_layers: needs at least one TOP=RHO layer");
+    const std::vector<int> layer = cell_layers(n_layers, top, "set_density_layers");
+    std::vector<double> f(layer.size());
+    for (size_t c = 0; c < layer.size(); ++c) f[c] = rho[layer[c]];
+    set_cell_density(f.data(), (int64_t)f.size());
+  }
+  // a child takes its parent's density, a coarsened parent the mean of its children; the scalars go along
+  void inherit_cell_density(const ProblemData &O) {
+    cell_density = inherited(O, O.cell_density, "inherit_cell_density");
+    for (int d = 0; d < 3; ++d) gravity[d] = O.gravity[d];
+    fluid_density = O.fluid_density; bulk_density = O.bulk_density; hydrostatic_init = O.hydrostatic_init;
+  }
+  // p_init + rho_f g . (x - x_top) at every pressure dof (the vertices; a linear function, so conforming at hanging nodes)
+  std::vector<double> hydrostatic_pressure(double p_init) const {
+    const int dim = mesh.dim, nv = 1 << dim; const int64_t n_vert = (int64_t)mesh.vertices.size() / dim;
+    double lowest = 0; bool first = true;      // x_top minimises g . x
+    for (int64_t v = 0; v < n_vert; ++v) { double gx = 0; for (int d = 0; d < dim; ++d) gx += gravity[d] * mesh.vertices[(size_t)v * dim + d]; if (first || gx < lowest) { lowest = gx; first = false; } }
+    std::vector<double> p((size_t)d.n_dofs_p, p_init);
+    for (int64_t c = 0; c < mesh.n_cells(); ++c)
+      for (int v = 0; v < nv; ++v) {
+        const int64_t vert = mesh.cells[(size_t)c * nv + v]; double gx = 0;
+        for (int k = 0; k < dim; ++k) gx += gravity[k] * mesh.vertices[(size_t)vert * dim + k];
+        p[(size_t)d.cell_dofs_p[(size_t)c * nv + v]] = p_init + fluid_density * (gx - lowest);
+      }
+    return p;
+  }
+
   // ConstraintMatrix semantics of PoroElasticDisplacementSolver.h:112-136: hanging-node constraints first, boundary values only for dofs that are
   // not constrained yet, then close(): a hanging node whose master carries a boundary value gets it as an inhomogeneity
   void close_constraints() {

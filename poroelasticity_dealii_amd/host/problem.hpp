@@ -203,6 +203,7 @@ template <int dim> class PoroElasticProblem {
     N->inherit_cell_moduli(O);                                                               // likewise lambda, G (poro_ctx_set_cell_moduli)
     N->inherit_cell_permeability(O);                                                         // a child takes its parent's k / mu; make_ctx below hands the field to the new context
     N->inherit_cell_permeability_tensor(O);                                                  // or its parent's diag(kx, ky, kz) / mu, component by component
+    N->inherit_cell_density(O);                                                              // the bulk density likewise, with g and the two scalar densities (poro_ctx_set_gravity)
     std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
     transfer_rows_p(O, *N, ptr, node, weight);
     int32_t scatter = PORO_SCATTER_COLOURED, fdm_req = PORO_FDM_FP64;
@@ -351,6 +352,11 @@ template <int dim> class PoroElasticProblem {
     choose_preconditioners(rc);
     setup_dofs();                                          // :308
     pressure_solver.solution = rc.p_init;                  // :311
+    if (pd->hydrostatic_init && pd->has_gravity()) {       // (extension: gravity) p_init at the top, hydrostatic below
+      if (pd->part.n_ranks > 1) throw std::runtime_error("initialize: hydrostatic_init is implemented for one rank");
+      const std::vector<double> ph = pd->hydrostatic_pressure(rc.p_init);
+      check(poro_vec_set(ctx, PORO_VEC_P, ph.data(), (int64_t)ph.size()), "vec_set");
+    }
     check(poro_pres_apply_boundary_values(ctx), "pres_apply_boundary_values");   // (extension: prescribed pressures; no-op for the reference's problems)
     assemble_displacement();                               // :312
     solve_displacement();                                  // :313
@@ -442,7 +448,9 @@ template <int dim> class PoroElasticProblem {
     // the per-cell fields of the problem go to the context before anything is assembled from it
     const char *failed = !P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0 ? "ctx_set_cell_permeability: "
                          : !P.cell_k_tensor.empty() && poro_ctx_set_cell_permeability_tensor(c, P.cell_k_tensor.data(), (int64_t)P.cell_k_tensor.size() / P.mesh.dim) != 0 ? "ctx_set_cell_permeability_tensor: "
-                         : !P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0 ? "ctx_set_cell_moduli: " : nullptr;
+                         : !P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0 ? "ctx_set_cell_moduli: "
+                         : !P.cell_density.empty() && poro_ctx_set_cell_density(c, P.cell_density.data(), (int64_t)P.cell_density.size()) != 0 ? "ctx_set_cell_density: "
+                         : P.has_gravity() && poro_ctx_set_gravity(c, P.gravity, P.bulk_density, P.fluid_density) != 0 ? "ctx_set_gravity: " : nullptr;      // (after the permeability: the gravity flux is built once)
     if (failed) { const std::string why = poro_last_error(); poro_ctx_destroy(c); throw std::runtime_error(failed + why); }
     return c;
   }

@@ -31,6 +31,7 @@ using namespace poro_host;
 
 static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
                                   "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
+                                  "[--gravity GX,GY[,GZ]] [--fluid-density RHO] [--density-layers TOP=RHO[,TOP=RHO...]] [--hydrostatic-init] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
 // TOP=V[:V...][,TOP=V[:V...]...], one array of `fields` per number of an item (the tops first): appends every item.  False unless every item has that shape, every number
@@ -58,6 +59,7 @@ int main(int argc, char **argv) {
   std::vector<double> layer_top, layer_value;
   std::vector<double> tensor_top, tensor_k[3];
   std::vector<double> moduli_top, moduli_young, moduli_poisson;
+  std::vector<double> gravity, density_top, density_value; double fluid_density = 0; bool hydrostatic_init = false;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -109,6 +111,22 @@ int main(int argc, char **argv) {
         std::cerr << "--moduli-layers needs TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] with ascending tops, YOUNG > 0 and POISSON in (-1, 0.5), got " << arg << std::endl; return 1;
       }
     }
+    else if (!std::strcmp(argv[i], "--gravity") && i + 1 < argc) {         // the gravity vector, one component per dimension: body force rho_b g (Properties/Bulk density, or --density-layers)
+      const char *arg = argv[++i]; gravity.clear();
+      for (const char *at = arg;;) { char *end = nullptr; const double v = std::strtod(at, &end); if (end == at || !std::isfinite(v)) { gravity.clear(); break; } gravity.push_back(v); if (!*end) break; if (*end != ',') { gravity.clear(); break; } at = end + 1; }
+      if (gravity.size() != 2 && gravity.size() != 3) { std::cerr << "--gravity needs GX,GY[,GZ], got " << arg << std::endl; return 1; }
+    }
+    else if (!std::strcmp(argv[i], "--fluid-density") && i + 1 < argc) {   // with --gravity: the Darcy gravity flux, q = -k / mu (grad p - RHO g)
+      const char *arg = argv[++i]; char *end = nullptr; fluid_density = std::strtod(arg, &end);
+      if (end == arg || *end || !(std::isfinite(fluid_density) && fluid_density >= 0)) { std::cerr << "--fluid-density needs a density >= 0, got " << arg << std::endl; return 1; }
+    }
+    else if (!std::strcmp(argv[i], "--density-layers") && i + 1 < argc) {  // bulk density by layers of the slowest direction, bottom to top
+      const char *arg = argv[++i];
+      if (!parse_layers(arg, {&density_top, &density_value}) || !std::all_of(density_value.begin(), density_value.end(), positive)) {
+        std::cerr << "--density-layers needs TOP=RHO[,TOP=RHO...] with ascending tops and positive values, got " << arg << std::endl; return 1;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--hydrostatic-init")) hydrostatic_init = true;   // with --gravity and --fluid-density: start from the initial pressure at the top and the hydrostatic pressure below
     else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
@@ -142,6 +160,11 @@ int main(int argc, char **argv) {
       P.set_permeability_tensor_layers((int)tensor_top.size(), tensor_top.data(), tensor_k[0].data(), tensor_k[1].data(), data.dim == 3 ? tensor_k[2].data() : nullptr);
     }
     if (!moduli_top.empty()) P.set_moduli_layers((int)moduli_top.size(), moduli_top.data(), moduli_young.data(), moduli_poisson.data());
+    if (!gravity.empty()) {
+      if ((int)gravity.size() != data.dim) throw std::runtime_error("--gravity: a " + std::to_string(data.dim) + "D problem needs " + std::to_string(data.dim) + " components");
+      P.set_gravity(gravity.data(), fluid_density, data.bulk_density); P.hydrostatic_init = hydrostatic_init;
+    }
+    if (!density_top.empty()) P.set_density_layers((int)density_top.size(), density_top.data(), density_value.data());
     RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction; rc.moduli_structured = moduli_structured;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
@@ -168,8 +191,15 @@ int main(int argc, char **argv) {
         if (poro_ctx_get_cell_permeability_tensor(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
         os << "permeability tensor layers: " << tensor_top.size() << ", field kind " << kind << "; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner];
       };
-      if (!pressure_labels.empty() || !layer_top.empty() || !moduli_top.empty() || !tensor_top.empty())        // (only with the extensions, so the reference's log stays as it is)
+      auto gravity_line = [&](std::ostream &os) {           // what the present context holds
+        double g[3] = {0, 0, 0}, rho_b = 0, rho_f = 0; int32_t on = 0, kind = 0;
+        if (poro_ctx_get_gravity(prob.context(), g, &rho_b, &rho_f, &on) != 0 || poro_ctx_get_cell_density(prob.context(), nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
+        os << "gravity: " << (on ? "on" : "off") << ", g = (" << g[0] << ", " << g[1]; if (data.dim == 3) os << ", " << g[2];
+        os << "), bulk density " << rho_b << ", density layers: " << density_top.size() << " (field kind " << kind << "), fluid density " << rho_f << ", hydrostatic start: " << (hydrostatic_init ? "yes" : "no");
+      };
+      if (!pressure_labels.empty() || !layer_top.empty() || !moduli_top.empty() || !tensor_top.empty() || !gravity.empty())        // (only with the extensions, so the reference's log stays as it is)
         prob.on_adapt = [&](int step, int64_t before, int64_t after) {     // the choice is made again on every adapted mesh
+          if (!gravity.empty()) { std::cout << "adapted before step " << step << ": "; gravity_line(std::cout); std::cout << std::endl; }
           if (!tensor_top.empty()) { std::cout << "adapted before step " << step << ": "; tensor_line(std::cout); std::cout << std::endl; }
           if (!moduli_top.empty()) { std::cout << "adapted before step " << step << ": "; moduli_line(std::cout); std::cout << std::endl; }
           std::cout << "adapted before step " << step << ": " << before << " -> " << after << " cells; prescribed pressures: " << prob.problem()->d.n_dirichlet_p
@@ -184,6 +214,7 @@ int main(int argc, char **argv) {
         std::cout << "block FDM form: " << runs[eff] << ", split directions (x y z): " << split[0] << " " << split[1] << " " << split[2] << std::endl;
       }
       if (!moduli_top.empty()) { moduli_line(std::cout); std::cout << std::endl; }
+      if (!gravity.empty()) { gravity_line(std::cout); std::cout << std::endl; }
       if (!tensor_top.empty()) { tensor_line(std::cout); std::cout << std::endl; }
       if (!layer_top.empty()) {
         int32_t kind = 0;
