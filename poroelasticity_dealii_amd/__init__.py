@@ -89,6 +89,15 @@ class SolveInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RunOptions(C.Structure):
+    """poro_host_run_options (host/run_controls.hpp), member by member; tests/test_run_options_cpu.py holds the two layouts against each other"""
+    _fields_ = [("p_init", C.c_double), ("time_step", C.c_double), ("n_steps", C.c_int32), ("fss_tol", C.c_double), ("pressure_tol", C.c_double),
+                ("max_fss_iterations", C.c_int32), ("max_pressure_iterations", C.c_int32), ("abs_tol_u", C.c_double), ("rel_tol_u", C.c_double), ("max_iter", C.c_int32),
+                ("preconditioner", C.c_int32), ("stop_rule_u", C.c_int32), ("preconditioner_p", C.c_int32)] + [
+        (n, C.c_int32) for n in ("coupled_fss", "incremental_strain", "atomic_scatter", "fdm_fp32", "hybrid_operator", "fdm_per_direction", "moduli_structured")] + [
+        ("chebyshev_degree", C.c_int32), ("chebyshev_ratio", C.c_double), ("refine_every", C.c_int32), ("refine_fraction", C.c_double), ("coarsen_fraction", C.c_double)]
+
+
 class InputFlat(C.Structure):
     _fields_ = [("dim", C.c_int32), ("domain_size", C.c_double * 3), ("initial_refinement_level", C.c_int32), ("max_refinement_level", C.c_int32)] + [
         (n, C.c_double) for n in ("youngs_modulus", "poisson_ratio", "biot_coef", "perm", "poro", "visc", "bulk_density", "f_comp", "r_well", "flow_rate",
@@ -221,8 +230,7 @@ def load_host():
         L.poro_host_mark_fixed_fraction.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, _ip]
         L.poro_host_transfer_rows_p.restype = C.c_int64
         L.poro_host_transfer_rows_p.argtypes = [C.c_void_p, C.c_void_p, _lp, _ip, _dp]
-        L.poro_host_run_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                             C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.poro_host_run_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RunOptions), _dp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.poro_host_runner_adapt.argtypes = [C.c_void_p, C.c_double, C.c_double, _lp]
         L.poro_host_runner_problem.restype = C.c_void_p
         L.poro_host_runner_problem.argtypes = [C.c_void_p]
@@ -247,7 +255,6 @@ def load_host():
         L.poro_host_set_cell_moduli.argtypes = [C.c_void_p, _dp, _dp, C.c_int64]
         L.poro_host_set_moduli_layers.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
         L.poro_host_inherit_cell_moduli.argtypes = [C.c_void_p, C.c_void_p]
-        L.poro_host_set_moduli_structured.argtypes = [C.c_void_p, C.c_int]
         L.poro_host_get_cell_moduli.restype = C.c_int64
         L.poro_host_get_cell_moduli.argtypes = [C.c_void_p, _dp, _dp]
         L.poro_host_set_gravity.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int]
@@ -268,10 +275,9 @@ def load_host():
         L.poro_host_free.argtypes = [C.c_void_p]
         L.poro_host_free.restype = None
         L.poro_host_read_input.argtypes = [C.c_char_p, C.POINTER(InputFlat)]
-        L.poro_host_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                    C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_void_p)]
+        L.poro_host_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RunOptions), _dp, C.c_int, C.POINTER(C.c_void_p)]
         L.poro_host_runner_create.restype = C.c_void_p
-        L.poro_host_runner_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
+        L.poro_host_runner_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RunOptions)]
         L.poro_host_runner_ctx.restype = C.c_void_p
         L.poro_host_runner_ctx.argtypes = [C.c_void_p]
         L.poro_host_runner_initialize.argtypes = [C.c_void_p]
@@ -308,6 +314,12 @@ def _field_args(*arrays):
     if len({a.size for a, _ in flat}) != 1:
         raise ValueError("set_cell_moduli: lame_lambda and shear_G differ in length")
     return flat, [p for _, p in flat] + [flat[0][0].size]
+
+
+def _layer_args(layers):
+    """the arguments of a layer setter behind its handle: layers [(top, value, ...), ...] -> (the columns to keep alive, [n_layers, pointer to the tops, pointer per value])"""
+    cols = [_arr_d(c) for c in zip(*layers)]
+    return cols, [len(layers)] + [p for _, p in cols]
 
 
 def _tensor_args(values, dim):
@@ -511,8 +523,8 @@ class Problem:
     def set_permeability_layers(self, layers):
         """the same by layers [(top, value), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the value of the first layer whose top is >=
         the coordinate of its centre"""
-        top, pt = _arr_d([l[0] for l in layers]); val, pv = _arr_d([l[1] for l in layers])
-        return self._host("set_permeability_layers", len(layers), pt, pv)
+        keep, args = _layer_args(layers)
+        return self._host("set_permeability_layers", *args)
 
     def inherit_cell_permeability(self, old):
         """what an adaptive run does with the field: this refined box takes the field of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
@@ -534,8 +546,8 @@ class Problem:
         dim = self.desc.dim
         if any(len(l) != dim + 1 for l in layers):
             raise ValueError(f"set_permeability_tensor_layers: every layer is (top, {', '.join(['kx', 'ky', 'kz'][:dim])})")
-        cols = [_arr_d([l[i] for l in layers]) for i in range(dim + 1)]
-        return self._host("set_permeability_tensor_layers", len(layers), *[p for _, p in cols], *[None] * (3 - dim))
+        keep, args = _layer_args(layers)
+        return self._host("set_permeability_tensor_layers", *args, *[None] * (3 - dim))
 
     def inherit_cell_permeability_tensor(self, old):
         """what an adaptive run does with the tensor: a child takes its parent's components exactly, a coarsened parent the per-component mean"""
@@ -555,12 +567,8 @@ class Problem:
     def set_moduli_layers(self, layers):
         """the same by layers [(top, young, poisson), ...] along the slowest direction (z in 3D, y in 2D), tops ascending: a cell takes the first layer whose top is >= the
         coordinate of its centre; lambda = E nu / ((1 + nu) (1 - 2 nu)), G = E / (2 (1 + nu)) as for the parameter file's values"""
-        top, pt = _arr_d([l[0] for l in layers]); E, pe = _arr_d([l[1] for l in layers]); nu, pn = _arr_d([l[2] for l in layers])
-        return self._host("set_moduli_layers", len(layers), pt, pe, pn)
-
-    def set_moduli_structured(self, on):
-        """MODULI_OP_STRUCTURED for the contexts run_problem and Runner create from this problem (their moduli_structured argument sets it)"""
-        return self._host("set_moduli_structured", int(bool(on)))
+        keep, args = _layer_args(layers)
+        return self._host("set_moduli_layers", *args)
 
     def inherit_cell_moduli(self, old):
         """what an adaptive run does with the field: this refined box takes the moduli of `old`, a refined box over the same coarse box, coarse cell by coarse cell"""
@@ -596,8 +604,8 @@ class Problem:
 
     def set_density_layers(self, layers):
         """the same by layers [(top, rho), ...] along the slowest direction, tops ascending, chosen by cell centres as set_permeability_layers does"""
-        top, pt = _arr_d([l[0] for l in layers]); val, pv = _arr_d([l[1] for l in layers])
-        return self._host("set_density_layers", len(layers), pt, pv)
+        keep, args = _layer_args(layers)
+        return self._host("set_density_layers", *args)
 
     def inherit_cell_density(self, old):
         """what an adaptive run does with the density: a child takes its parent's value, a coarsened parent the mean of its children; g and the scalar densities go along"""
@@ -993,7 +1001,16 @@ def _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init):
         problem.set_cell_density(density)
 
 
-_FLAG_FDM_PER_DIRECTION = -(1 << 31)      # bit 31 of the host runner's 32-bit flags word (bits 0-7 and the Chebyshev fields from bit 8 and bit 16 are taken)
+def _run_options(kw):
+    """the RunOptions of a run from the keyword arguments of run_problem / Runner (their locals()); every value goes through as given"""
+    return RunOptions(
+        p_init=kw["p_init"], time_step=kw["dt"], n_steps=kw.get("n_steps", 1), fss_tol=kw["fss_tol"], pressure_tol=kw["pressure_tol"], max_fss_iterations=kw["max_fss"],
+        max_pressure_iterations=kw["max_pres"], abs_tol_u=kw["abs_u"], rel_tol_u=kw["rel_u"], max_iter=kw["max_it"], preconditioner=kw["prec"],
+        stop_rule_u=STOP_REDUCTION if kw["reduction"] else STOP_RHS,
+        preconditioner_p=PREC_TWO_LEVEL if kw["two_level_p"] else PREC_JACOBI if kw["jacobi_p"] else -1,      # -1: the strongest form the mesh supports
+        chebyshev_degree=int(kw["cheb_degree"]), chebyshev_ratio=kw["cheb_ratio"],
+        refine_every=int(kw.get("refine_every") or 0), refine_fraction=kw.get("refine_fraction", 0.6), coarsen_fraction=kw.get("coarsen_fraction", 0.4),
+        **{n: bool(kw[n]) for n in ("coupled_fss", "incremental_strain", "atomic_scatter", "fdm_fp32", "hybrid_operator", "fdm_per_direction", "moduli_structured")})
 
 
 def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fss_tol=1e-8, pressure_tol=1e-8, max_fss=50, max_pres=50,
@@ -1012,7 +1029,7 @@ def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fs
     gravity: the vector g (Problem.set_gravity on `problem`, which keeps it); fluid_density: rho_f of the Darcy gravity flux; density: the bulk density, one scalar or one
     value per cell (Problem.set_cell_density); hydrostatic_init: start from p_init + rho_f g . (x - x_top) instead of the uniform p_init.  Carried to every adapted mesh."""
     H = load_host()
-    problem.set_moduli_structured(moduli_structured)
+    opts = _run_options(locals())
     _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init)
     if permeability is not None:
         problem.set_cell_permeability(permeability)
@@ -1023,13 +1040,11 @@ def run_problem(problem, n_steps, p_init, dt, device=0, operator_mode=OP_CSR, fs
     ctx = C.c_void_p()
     if refine_every is not None:
         last = C.c_void_p()
-        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
-                                        int(refine_every), refine_fraction, coarsen_fraction, trace.ctypes.data_as(_dp), max_rows, C.byref(ctx), C.byref(last))
+        rows = H.poro_host_run_adaptive(problem.handle, device, operator_mode, C.byref(opts), trace.ctypes.data_as(_dp), max_rows, C.byref(ctx), C.byref(last))
         if rows < 0:
             raise RuntimeError(H.poro_host_last_error().decode())
         return trace[:rows], Context(Problem(last.value) if last.value else problem, ptr=ctx)
-    rows = H.poro_host_run(problem.handle, device, operator_mode, p_init, dt, n_steps, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16),
-                           trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
+    rows = H.poro_host_run(problem.handle, device, operator_mode, C.byref(opts), trace.ctypes.data_as(_dp), max_rows, C.byref(ctx))
     if rows < 0:
         raise RuntimeError(H.poro_host_last_error().decode())
     return trace[:rows], Context(problem, ptr=ctx)
@@ -1046,14 +1061,14 @@ class Runner:
                  atomic_scatter=False, fdm_fp32=False, hybrid_operator=False, fdm_per_direction=False, permeability=None, permeability_tensor=None, moduli_structured=False,
                  gravity=None, fluid_density=None, density=None, hydrostatic_init=False):
         self.H = load_host()
+        opts = _run_options(locals())
         _hand_gravity(problem, gravity, fluid_density, density, hydrostatic_init)      # Problem.set_gravity / set_cell_density on `problem`, which keeps them; adapt() carries them to every new mesh
-        problem.set_moduli_structured(moduli_structured)      # MODULI_OP_STRUCTURED (Context.set_moduli_operator), requested again on every mesh adapt() builds
         if permeability_tensor is not None:      # per-cell diag(kx, ky[, kz]) / mu, shape (n_cells, dim): Problem.set_cell_permeability_tensor, kept and carried like the scalar field
             problem.set_cell_permeability_tensor(permeability_tensor)
         if permeability is not None:             # per-cell k / mu: Problem.set_cell_permeability on `problem`, which keeps it; adapt() carries it to every new mesh
             problem.set_cell_permeability(permeability)
         self.max_fss = max_fss
-        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, p_init, dt, fss_tol, pressure_tol, max_fss, max_pres, abs_u, rel_u, max_it, prec, int(bool(coupled_fss)) | (2 if incremental_strain else 0) | (4 if reduction else 0) | (8 if jacobi_p else 0) | (16 if two_level_p else 0) | (32 if atomic_scatter else 0) | (64 if fdm_fp32 else 0) | (128 if hybrid_operator else 0) | (_FLAG_FDM_PER_DIRECTION if fdm_per_direction else 0) | (int(cheb_degree) << 8) | (int(cheb_ratio) << 16))
+        h = self.H.poro_host_runner_create(problem.handle, device, operator_mode, C.byref(opts))
         if not h:
             raise RuntimeError(self.H.poro_host_last_error().decode())
         self.h = C.c_void_p(h)

@@ -1,5 +1,6 @@
 // C entry points of the host layer (mesh / DoF / FE-table provider, parameter file front end and the
 // run() driver), so tests and bench.py can reach the C++ host code through ctypes.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -22,10 +23,33 @@ template <class F> int on_problem(void *h, F &&f) {
   try { f(*static_cast<ProblemData *>(h)); return 0; }
   catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
-// a per-cell field the problem carries: its length (0: none); copied where out != NULL
+// an array of a per-cell field the problem carries: its length (0: none); copied where out != NULL
 int64_t copy_field(const std::vector<double> &f, double *out) {
   if (out && !f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(double));
   return (int64_t)f.size();
+}
+// component a of a field (none where the field has fewer)
+int64_t copy_field(const ProblemData::PerCellField &f, int a, double *out) { return a < f.ncomp() ? copy_field(f.comp[a], out) : 0; }
+// what poro_host_runner_create hands out: the problem of either dimension and the options it runs with
+struct HostRunner {
+  int dim; RunControls rc; PoroElasticProblem<2> *p2 = nullptr; PoroElasticProblem<3> *p3 = nullptr;
+  ~HostRunner() { delete p2; delete p3; }
+};
+// f(the PoroElasticProblem<dim> the runner holds, its RunControls)
+template <class F> auto on_runner(void *r, F &&f) {
+  auto *R = static_cast<HostRunner *>(r);
+  if (R->dim == 2) return f(*R->p2, R->rc);
+  return f(*R->p3, R->rc);
+}
+// the same for the calls that report 0 / -1
+template <class F> int try_on_runner(void *r, F &&f) {
+  try { on_runner(r, f); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// work[11] = apply_u, apply_p, asm_rhs_u, asm_matrix_u, residual_p, jacobian_p, proj_rhs, cg_u, cg_p, cg_proj, seconds_solve_u*1e6
+template <class W> void fill_work(const W &w, int64_t *work) {
+  const int64_t all[11] = {w.apply_u, w.apply_p, w.asm_rhs_u, w.asm_matrix_u, w.residual_p, w.jacobian_p, w.proj_rhs, w.cg_u, w.cg_p, w.cg_proj, (int64_t)(w.seconds_solve_u * 1e6)};
+  std::copy(all, all + 11, work);
 }
 }  // namespace
 
@@ -184,7 +208,7 @@ void *poro_host_partition(void *global, int rank, int n_ranks) {
   try { auto *L = new ProblemData(); try { partition_problem(*static_cast<ProblemData *>(global), rank, n_ranks, *L); } catch (...) { delete L; throw; } return L; }
   catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
-// the same with options.  flags bit 0: the piece carries the coarse space of the two-level preconditioner (its own copy of the global box problem + the global
+// the same with options.  flags = 1: the piece carries the coarse space of the two-level preconditioner (its own copy of the global box problem + the global
 // interpolation rows of its nodes; displacement ghosts and owners per node).  Refused when the global problem has no coarse space
 void *poro_host_partition_ex(void *global, int rank, int n_ranks, int flags) {
   try { auto *L = new ProblemData(); try { partition_problem(*static_cast<ProblemData *>(global), rank, n_ranks, *L, (flags & 1) != 0); } catch (...) { delete L; throw; } return L; }
@@ -226,25 +250,22 @@ int poro_host_set_permeability_layers(void *h, int n, const double *top, const d
 // what refine_mesh does with the field: `h` (a refined box) takes the field of `old` (a refined box over the same coarse box), cell by coarse cell
 int poro_host_inherit_cell_permeability(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_permeability(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies when out != NULL
-int64_t poro_host_get_cell_permeability(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_k_over_mu, out); }
+int64_t poro_host_get_cell_permeability(void *h, double *out) { const ProblemData &P = *static_cast<ProblemData *>(h); return P.carries_permeability(false) ? copy_field(P.permeability, 0, out) : 0; }
 // extension: the per-cell diagonal tensor diag(kx, ky[, kz]) / mu, values[n][dim] with x first (NULL: none); a problem carries the scalar field or the tensor
 int poro_host_set_cell_permeability_tensor(void *h, const double *values, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_permeability_tensor(values, n); }); }
 int poro_host_set_permeability_tensor_layers(void *h, int n, const double *top, const double *kx, const double *ky, const double *kz /* not read in 2D */) { return on_problem(h, [&](ProblemData &P) { P.set_permeability_tensor_layers(n, top, kx, ky, kz); }); }
 int poro_host_inherit_cell_permeability_tensor(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_permeability_tensor(*static_cast<ProblemData *>(old)); }); }
-// returns the number of doubles the problem carries (n_cells * dim; 0: none)
-int64_t poro_host_get_cell_permeability_tensor(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_k_tensor, out); }
+// returns the number of doubles the problem carries (n_cells * dim; 0: none), out[cell][dim]
+int64_t poro_host_get_cell_permeability_tensor(void *h, double *out) { const ProblemData &P = *static_cast<ProblemData *>(h); return P.carries_permeability(true) ? copy_field(P.permeability.interleaved(), out) : 0; }
 // extension: per-cell Lame lambda and shear modulus G of the displacement system (both NULL: back to the scalars); kept with the problem and handed over like the permeability
 int poro_host_set_cell_moduli(void *h, const double *lam, const double *G, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_moduli(lam, G, n); }); }
 // by layers of the slowest direction: a cell takes the first layer whose top[l] is >= the coordinate of its centre; (E, nu) -> (lambda, G) as the parameter file's are
 int poro_host_set_moduli_layers(void *h, int n, const double *top, const double *young, const double *poisson) { return on_problem(h, [&](ProblemData &P) { P.set_moduli_layers(n, top, young, poisson); }); }
-// the structured operator for layered moduli (PORO_MODULI_OP_STRUCTURED) for the contexts poro_host_run, poro_host_run_adaptive and poro_host_runner_create make from this problem
-// (their flags word is full); kept with the problem like the moduli it applies to
-int poro_host_set_moduli_structured(void *h, int on) { return on_problem(h, [&](ProblemData &P) { P.moduli_structured = on != 0; }); }
 int poro_host_inherit_cell_moduli(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_moduli(*static_cast<ProblemData *>(old)); }); }
 // the field the problem carries: returns its length (0: none), copies where the pointers are not NULL
 int64_t poro_host_get_cell_moduli(void *h, double *lam_out, double *G_out) {
-  const ProblemData &P = *static_cast<ProblemData *>(h); copy_field(P.cell_G, G_out);
-  return copy_field(P.cell_lambda, lam_out);
+  const ProblemData &P = *static_cast<ProblemData *>(h); copy_field(P.moduli, 1, G_out);
+  return copy_field(P.moduli, 0, lam_out);
 }
 // extension: gravity.  g[dim] (NULL or zeros: off), the fluid density of the Darcy gravity flux (0: none), the scalar bulk density (< 0: keep the present one, 2700 at
 // first) and whether a run starts from the hydrostatic pressure; kept with the problem, handed to every context the drivers create (poro_ctx_set_gravity)
@@ -264,7 +285,7 @@ int poro_host_get_gravity(void *h, double *g, double *fluid_density, double *bul
 int poro_host_set_cell_density(void *h, const double *values, int64_t n) { return on_problem(h, [&](ProblemData &P) { P.set_cell_density(values, n); }); }
 int poro_host_set_density_layers(void *h, int n, const double *top, const double *rho) { return on_problem(h, [&](ProblemData &P) { P.set_density_layers(n, top, rho); }); }
 int poro_host_inherit_cell_density(void *h, void *old) { return on_problem(h, [&](ProblemData &P) { P.inherit_cell_density(*static_cast<ProblemData *>(old)); }); }
-int64_t poro_host_get_cell_density(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->cell_density, out); }
+int64_t poro_host_get_cell_density(void *h, double *out) { return copy_field(static_cast<ProblemData *>(h)->density, 0, out); }
 const poro_desc *poro_host_desc(void *h) { return &static_cast<ProblemData *>(h)->d; }
 void poro_host_free(void *h) { delete static_cast<ProblemData *>(h); }
 
@@ -306,127 +327,71 @@ int poro_host_read_input(const char *path /* NULL = declared defaults */, poro_i
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
-// PoroElasticProblem<dim>::run() on the HIP back end (problem.hpp).  trace rows: see PoroElasticProblem::time_step.
-int poro_host_run(void *problem_data, int device, int operator_mode, double p_init, double dt, int n_steps,
-                  double fss_tol, double pressure_tol, int max_fss, int max_pres,
-                  double abs_u, double rel_u, int max_it, int preconditioner, int flags /* bit 0: coupled_fss, bit 1: incremental_strain, bit 2: PORO_STOP_REDUCTION for the displacement solve, bit 3: Jacobi for the pressure / projection solves (default: the strongest form the mesh supports), bit 4: PORO_PREC_TWO_LEVEL for them, bit 5: PORO_SCATTER_ATOMIC for the general matrix-free operator, bit 6: PORO_FDM_FP32 for the displacement system's octant-form block FDM, bit 7: PORO_OPFORM_HYBRID for the matrix-free operator on refined boxes, bits 8-15: Chebyshev degree, bits 16-30: Chebyshev interval ratio (0 = defaults), bit 31: PORO_FDM_FORM_PER_DIRECTION for the displacement system's block FDM */, double *trace, int max_rows, poro_ctx **ctx_out) {
+// PoroElasticProblem<dim>::run() on the HIP back end (problem.hpp); the options: host/run_controls.hpp.  trace rows: see PoroElasticProblem::time_step.
+// With mesh adaptation (opts->refine_every > 0: refine_mesh every refine_every-th step, PoroelasticityFSS.h:333-340) the problem must be a mask- or block-refined box, and
+// *problem_out receives the mesh the run ended on when it was refined at least once (the caller frees it with poro_host_free; the context in *ctx_out belongs to it),
+// else NULL (the context belongs to `problem_data`).
+int poro_host_run_adaptive(void *problem_data, int device, int operator_mode, const poro_host_run_options *opts, double *trace, int max_rows, poro_ctx **ctx_out, void **problem_out) {
   try {
     auto *P = static_cast<ProblemData *>(problem_data);
-    RunControls rc; rc.p_init = p_init; rc.time_step = dt; rc.n_steps = n_steps; rc.fss_tol = fss_tol; rc.pressure_tol = pressure_tol;
-    rc.max_fss_iterations = max_fss; rc.max_pressure_iterations = max_pres; rc.abs_tol_u = abs_u; rc.rel_tol_u = rel_u; rc.max_iter = max_it; rc.preconditioner = preconditioner; rc.coupled_fss = (flags & 1) != 0; rc.incremental_strain = (flags & 2) != 0; rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) rc.preconditioner_p = PORO_PREC_TWO_LEVEL; rc.atomic_scatter = (flags & 32) != 0; rc.fdm_fp32 = (flags & 64) != 0; rc.hybrid_operator = (flags & 128) != 0; rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; rc.chebyshev_degree = (flags >> 8) & 0xff; rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
-    rc.moduli_structured = P->moduli_structured;
-    int rows = 0;
-    if (P->mesh.dim == 2) { PoroElasticProblem<2> prob(*P, device, operator_mode); rows = prob.run(rc, trace, max_rows); if (ctx_out) *ctx_out = prob.release(); }
-    else { PoroElasticProblem<3> prob(*P, device, operator_mode); rows = prob.run(rc, trace, max_rows); if (ctx_out) *ctx_out = prob.release(); }
-    return rows;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
-
-// The same with mesh adaptation (refine_mesh every refine_every-th step, PoroelasticityFSS.h:333-340; 0 = never: the run of poro_host_run).  `flags` as for poro_host_run.
-// The problem must be a mask- or block-refined box.  *problem_out receives the mesh the run ended on when it was refined at least once (the caller frees it with
-// poro_host_free; the context in *ctx_out belongs to it), else NULL (the context belongs to `problem_data`).
-int poro_host_run_adaptive(void *problem_data, int device, int operator_mode, double p_init, double dt, int n_steps,
-                           double fss_tol, double pressure_tol, int max_fss, int max_pres,
-                           double abs_u, double rel_u, int max_it, int preconditioner, int flags, int refine_every, double refine_fraction, double coarsen_fraction,
-                           double *trace, int max_rows, poro_ctx **ctx_out, void **problem_out) {
-  try {
-    auto *P = static_cast<ProblemData *>(problem_data);
-    RunControls rc; rc.p_init = p_init; rc.time_step = dt; rc.n_steps = n_steps; rc.fss_tol = fss_tol; rc.pressure_tol = pressure_tol;
-    rc.max_fss_iterations = max_fss; rc.max_pressure_iterations = max_pres; rc.abs_tol_u = abs_u; rc.rel_tol_u = rel_u; rc.max_iter = max_it; rc.preconditioner = preconditioner; rc.coupled_fss = (flags & 1) != 0; rc.incremental_strain = (flags & 2) != 0; rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) rc.preconditioner_p = PORO_PREC_TWO_LEVEL; rc.atomic_scatter = (flags & 32) != 0; rc.fdm_fp32 = (flags & 64) != 0; rc.hybrid_operator = (flags & 128) != 0; rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; rc.chebyshev_degree = (flags >> 8) & 0xff; rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
-    rc.moduli_structured = P->moduli_structured;
-    if (refine_every < 0) throw std::runtime_error("run_adaptive: refine_every must be >= 0");
-    rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
+    const RunControls rc = to_run_controls(*opts);
+    if (rc.refine_every > 0 && !problem_out) throw std::runtime_error("run: refine_every needs poro_host_run_adaptive, which hands out the mesh the run ends on");
     int rows = 0;
     if (problem_out) *problem_out = nullptr;
-    auto go = [&](auto &prob) { rows = prob.run(rc, trace, max_rows); if (problem_out) *problem_out = prob.release_problem(); if (ctx_out) *ctx_out = prob.release(); };
-    if (P->mesh.dim == 2) { PoroElasticProblem<2> prob(*P, device, operator_mode); go(prob); }
-    else { PoroElasticProblem<3> prob(*P, device, operator_mode); go(prob); }
+    auto go = [&](auto &&prob) { rows = prob.run(rc, trace, max_rows); if (problem_out) *problem_out = prob.release_problem(); if (ctx_out) *ctx_out = prob.release(); };
+    if (P->mesh.dim == 2) go(PoroElasticProblem<2>(*P, device, operator_mode)); else go(PoroElasticProblem<3>(*P, device, operator_mode));
     return rows;
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+// the same on one mesh (refine_every must be 0)
+int poro_host_run(void *problem_data, int device, int operator_mode, const poro_host_run_options *opts, double *trace, int max_rows, poro_ctx **ctx_out) {
+  return poro_host_run_adaptive(problem_data, device, operator_mode, opts, trace, max_rows, ctx_out, nullptr);
+}
 
-// Steppable driver for bench.py: the same PoroElasticProblem object, one time step per call.
-struct HostRunner {
-  int dim; RunControls rc; PoroElasticProblem<2> *p2 = nullptr; PoroElasticProblem<3> *p3 = nullptr;
-  ~HostRunner() { delete p2; delete p3; }
-};
-void *poro_host_runner_create(void *problem_data, int device, int operator_mode, double p_init, double dt, double fss_tol, double pressure_tol,
-                              int max_fss, int max_pres, double abs_u, double rel_u, int max_it, int preconditioner, int flags /* bit 0: coupled_fss, bit 1: incremental_strain, bit 2: PORO_STOP_REDUCTION for the displacement solve, bit 3: Jacobi for the pressure / projection solves (default: the strongest form the mesh supports), bit 4: PORO_PREC_TWO_LEVEL for them, bit 5: PORO_SCATTER_ATOMIC for the general matrix-free operator, bit 6: PORO_FDM_FP32 for the displacement system's octant-form block FDM, bit 7: PORO_OPFORM_HYBRID for the matrix-free operator on refined boxes, bits 8-15: Chebyshev degree, bits 16-30: Chebyshev interval ratio (0 = defaults), bit 31: PORO_FDM_FORM_PER_DIRECTION for the displacement system's block FDM */) {
+// Steppable driver for bench.py (HostRunner): the same PoroElasticProblem object, one time step per call.
+void *poro_host_runner_create(void *problem_data, int device, int operator_mode, const poro_host_run_options *opts) {
   try {
     auto *P = static_cast<ProblemData *>(problem_data);
-    auto *R = new HostRunner(); R->dim = P->mesh.dim;
-    R->rc.p_init = p_init; R->rc.time_step = dt; R->rc.fss_tol = fss_tol; R->rc.pressure_tol = pressure_tol; R->rc.max_fss_iterations = max_fss;
-    R->rc.max_pressure_iterations = max_pres; R->rc.abs_tol_u = abs_u; R->rc.rel_tol_u = rel_u; R->rc.max_iter = max_it; R->rc.preconditioner = preconditioner; R->rc.coupled_fss = (flags & 1) != 0; R->rc.incremental_strain = (flags & 2) != 0; R->rc.stop_rule_u = (flags & 4) ? PORO_STOP_REDUCTION : PORO_STOP_RHS; if (flags & 8) R->rc.preconditioner_p = PORO_PREC_JACOBI; if (flags & 16) R->rc.preconditioner_p = PORO_PREC_TWO_LEVEL; R->rc.atomic_scatter = (flags & 32) != 0; R->rc.fdm_fp32 = (flags & 64) != 0; R->rc.hybrid_operator = (flags & 128) != 0; R->rc.fdm_per_direction = (((unsigned)flags >> 31) & 1u) != 0; R->rc.chebyshev_degree = (flags >> 8) & 0xff; R->rc.chebyshev_ratio = (double)((flags >> 16) & 0x7fff);
-    R->rc.moduli_structured = P->moduli_structured;
+    std::unique_ptr<HostRunner> R(new HostRunner()); R->dim = P->mesh.dim; R->rc = to_run_controls(*opts);
     if (R->dim == 2) R->p2 = new PoroElasticProblem<2>(*P, device, operator_mode); else R->p3 = new PoroElasticProblem<3>(*P, device, operator_mode);
-    return R;
+    return R.release();
   } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 // refine_mesh + the two calls of PoroelasticityFSS.h:338-339 between two steps; cells[2] = cell counts before and after.  Afterwards poro_host_runner_ctx and
 // poro_host_runner_problem give the new context and mesh, both owned (and freed) by the runner
 int poro_host_runner_adapt(void *r, double refine_fraction, double coarsen_fraction, int64_t *cells) {
-  try {
-    auto *R = static_cast<HostRunner *>(r);
-    RunControls rc = R->rc; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
-    const std::pair<int64_t, int64_t> n = R->dim == 2 ? R->p2->refine_mesh(rc) : R->p3->refine_mesh(rc);
+  return try_on_runner(r, [&](auto &prob, RunControls rc) {
+    rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
+    const std::pair<int64_t, int64_t> n = prob.refine_mesh(rc);
     if (cells) { cells[0] = n.first; cells[1] = n.second; }
-    return 0;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+  });
 }
-void *poro_host_runner_problem(void *r) { auto *R = static_cast<HostRunner *>(r); return const_cast<ProblemData *>(R->dim == 2 ? R->p2->problem() : R->p3->problem()); }
-poro_ctx *poro_host_runner_ctx(void *r) { auto *R = static_cast<HostRunner *>(r); return R->dim == 2 ? R->p2->context() : R->p3->context(); }
-int poro_host_runner_initialize(void *r) {
-  try { auto *R = static_cast<HostRunner *>(r); if (R->dim == 2) R->p2->initialize(R->rc); else R->p3->initialize(R->rc); return 0; }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
-// one time step; trace rows as poro_host_run; work[11] = apply_u, apply_p, asm_rhs_u, asm_matrix_u, residual_p, jacobian_p, proj_rhs, cg_u, cg_p, cg_proj, seconds_solve_u*1e6
+void *poro_host_runner_problem(void *r) { return on_runner(r, [](auto &prob, const RunControls &) { return const_cast<ProblemData *>(prob.problem()); }); }
+poro_ctx *poro_host_runner_ctx(void *r) { return on_runner(r, [](auto &prob, const RunControls &) { return prob.context(); }); }
+int poro_host_runner_initialize(void *r) { return try_on_runner(r, [](auto &prob, const RunControls &rc) { prob.initialize(rc); }); }
+// one time step; trace rows as poro_host_run; work: see fill_work
 int poro_host_runner_step(void *r, double *trace, int max_rows, int64_t *work) {
   try {
-    auto *R = static_cast<HostRunner *>(r);
-    auto fill = [&](auto &w) { work[0] = w.apply_u; work[1] = w.apply_p; work[2] = w.asm_rhs_u; work[3] = w.asm_matrix_u; work[4] = w.residual_p; work[5] = w.jacobian_p;
-                               work[6] = w.proj_rhs; work[7] = w.cg_u; work[8] = w.cg_p; work[9] = w.cg_proj; work[10] = (int64_t)(w.seconds_solve_u * 1e6); };
-    int rows;
-    if (R->dim == 2) { rows = R->p2->time_step(R->rc, trace, max_rows); if (work) fill(R->p2->work); }
-    else { rows = R->p3->time_step(R->rc, trace, max_rows); if (work) fill(R->p3->work); }
-    return rows;
+    return on_runner(r, [&](auto &prob, const RunControls &rc) { const int rows = prob.time_step(rc, trace, max_rows); if (work) fill_work(prob.work, work); return rows; });
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
-}
-// roll back to the snapshot, then one time step, in ONE call (a benchmark that repeats a step pays one host-language round trip instead of two)
-int poro_host_runner_restore_and_step(void *r, double *trace, int max_rows, int64_t *work) {
-  try { auto *R = static_cast<HostRunner *>(r); if (R->dim == 2) R->p2->restore_state(); else R->p3->restore_state(); }
-  catch (const std::exception &e) { g_err = e.what(); return -1; }
-  return poro_host_runner_step(r, trace, max_rows, work);
 }
 // action 0: snapshot the device state, 1: roll back to it
 int poro_host_runner_state(void *r, int action) {
-  try {
-    auto *R = static_cast<HostRunner *>(r);
-    if (R->dim == 2) { if (action) R->p2->restore_state(); else R->p2->save_state(); }
-    else { if (action) R->p3->restore_state(); else R->p3->save_state(); }
-    return 0;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+  return try_on_runner(r, [&](auto &prob, const RunControls &) { if (action) prob.restore_state(); else prob.save_state(); });
+}
+// roll back to the snapshot, then one time step, in ONE call (a benchmark that repeats a step pays one host-language round trip instead of two)
+int poro_host_runner_restore_and_step(void *r, double *trace, int max_rows, int64_t *work) {
+  return poro_host_runner_state(r, 1) != 0 ? -1 : poro_host_runner_step(r, trace, max_rows, work);
 }
 // tail of the time loop body (PoroelasticityFSS.h:409-411): shear strains, effective stresses and, with a directory, solution-NNNN.vtk
 int poro_host_runner_postprocess(void *r, const char *output_dir, int corrected) {
-  try {
-    auto *R = static_cast<HostRunner *>(r);
-    RunControls rc = R->rc; rc.output_dir = output_dir ? output_dir : ""; rc.corrected_postprocessing = corrected != 0;
-    if (R->dim == 2) R->p2->postprocess(rc); else R->p3->postprocess(rc);
-    return 0;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+  return try_on_runner(r, [&](auto &prob, RunControls rc) { rc.output_dir = output_dir ? output_dir : ""; rc.corrected_postprocessing = corrected != 0; prob.postprocess(rc); });
 }
 // cumulative work counters since creation (same layout as poro_host_runner_step's `work`)
-void poro_host_runner_work(void *r, int64_t *work) {
-  auto *R = static_cast<HostRunner *>(r);
-  auto fill = [&](auto &w) { work[0] = w.apply_u; work[1] = w.apply_p; work[2] = w.asm_rhs_u; work[3] = w.asm_matrix_u; work[4] = w.residual_p; work[5] = w.jacobian_p;
-                             work[6] = w.proj_rhs; work[7] = w.cg_u; work[8] = w.cg_p; work[9] = w.cg_proj; work[10] = (int64_t)(w.seconds_solve_u * 1e6); };
-  if (R->dim == 2) fill(R->p2->work); else fill(R->p3->work);
-}
+void poro_host_runner_work(void *r, int64_t *work) { on_runner(r, [&](auto &prob, const RunControls &) { fill_work(prob.work, work); }); }
 // the preconditioners the driver chose for the current context (initialize, and again after every adapt): out[3] = displacement, pressure, projection (PORO_PREC_*)
 void poro_host_runner_preconditioners(void *r, int32_t *out) {
-  auto *R = static_cast<HostRunner *>(r);
-  auto fill = [&](auto &p) { out[0] = p.displacement_solver.control.preconditioner; out[1] = p.pressure_solver.control.preconditioner; out[2] = p.strain_projector.control.preconditioner; };
-  if (R->dim == 2) fill(*R->p2); else fill(*R->p3);
+  on_runner(r, [&](auto &p, const RunControls &) { out[0] = p.displacement_solver.control.preconditioner; out[1] = p.pressure_solver.control.preconditioner; out[2] = p.strain_projector.control.preconditioner; });
 }
 void poro_host_runner_free(void *r) { delete static_cast<HostRunner *>(r); }
 

@@ -438,11 +438,10 @@ struct ProblemData {
   bool refined_box = false; int box_n[3] = {1, 1, 1}; double box_size[3] = {1, 1, 1}; int box_k_u = 0;
   std::vector<uint8_t> refine_mask; std::vector<int32_t> cell_coarse, cell_child; std::vector<std::array<int, 3>> lattice_p;
   poro_desc d{};
-  // The optional per-cell coefficient fields, one value per cell of `mesh` (empty: the scalars of `mat`).  Not part of poro_desc: whoever creates a context from this
-  // problem hands them over with poro_ctx_set_cell_permeability / poro_ctx_set_cell_moduli (PoroElasticProblem does, also for every mesh refine_mesh builds).  What the
-  // fields share is csrc/cell_field.hpp.  set_*_layers: layers along the slowest direction (z in 3D, y in 2D), a cell takes the first layer whose `top` is >= the
-  // coordinate of its centre there.  inherit_*: the field of a refined box `O` over the same coarse box on this refined box, every cell takes the value of its coarse
-  // cell - a child its parent's, a parent the mean of its children (which all hold the parent's value unless the caller set them apart)
+  // The optional per-cell coefficient fields, one value per component and cell of `mesh` (none: the scalars of `mat`).  Not part of poro_desc: whoever creates a context
+  // from this problem hands them over with poro_ctx_set_cell_permeability[_tensor] / poro_ctx_set_cell_moduli / poro_ctx_set_cell_density (PoroElasticProblem does, also for
+  // every mesh refine_mesh builds).  What the fields share on the device side is csrc/cell_field.hpp; what they share here is PerCellField.  Each family below keeps what
+  // is its own: its validator, its conversions and its refusal texts
   void check_field_length(const char *who, int64_t n) const { if (n != mesh.n_cells()) throw std::runtime_error(std::string(who) + ": " + std::to_string(n) + " values for " + std::to_string(mesh.n_cells()) + " cells"); }
   std::vector<int> cell_layers(int n_layers, const double *top, const char *who) const { return poro::cell_layers_by_centre(mesh.vertices, mesh.cells, mesh.dim, n_layers, top, who); }
   std::vector<double> inherited(const ProblemData &O, const std::vector<double> &old, const char *who) const {
@@ -450,94 +449,107 @@ struct ProblemData {
     if (!O.refined_box || !refined_box || O.refine_mask.size() != refine_mask.size()) throw std::runtime_error(std::string(who) + ": two refined boxes over the same coarse box are needed");
     return poro::cell_field_inherit(O.cell_coarse, old, cell_coarse, refine_mask.size());
   }
+  static auto valid_positive(const char *who) {      // the validator of the one-component fields
+    return [who](int64_t i, const double *v) { if (!(std::isfinite(v[0]) && v[0] > 0)) throw std::runtime_error(std::string(who) + ": value of cell " + std::to_string(i) + " is not finite and > 0"); };
+  }
+  struct PerCellField {
+    std::vector<std::vector<double>> comp;      // comp[a][cell]; no component: the problem carries no such field
+    int ncomp() const { return (int)comp.size(); } bool empty() const { return comp.empty(); } void clear() { comp.clear(); }
+    std::vector<double> interleaved() const {   // [cell][ncomp]
+      std::vector<double> out(comp.empty() ? 0 : comp.size() * comp[0].size());
+      for (size_t a = 0; a < comp.size(); ++a) for (size_t c = 0; c < comp[a].size(); ++c) out[c * comp.size() + a] = comp[a][c];
+      return out;
+    }
+    // component a of cell i is values[a][i * stride]; valid(i, the cell's components) throws the family's refusal.  Nothing changes unless every cell passes
+    template <class Valid> void set(const ProblemData &P, const char *who, const std::vector<const double *> &values, int64_t stride, int64_t n, Valid &&valid) {
+      P.check_field_length(who, n);
+      std::vector<std::vector<double>> got(values.size(), std::vector<double>((size_t)n)); std::vector<double> v(values.size());
+      for (int64_t i = 0; i < n; ++i) {
+        for (size_t a = 0; a < values.size(); ++a) got[a][(size_t)i] = v[a] = values[a][i * stride];
+        valid(i, v.data());
+      }
+      comp = std::move(got);
+    }
+    // layers along the slowest direction (z in 3D, y in 2D): a cell takes layer_value[a][l] of the first layer l whose top[l] is >= the coordinate of its centre there
+    template <class Valid> void set_by_layers(const ProblemData &P, const char *who, int n_layers, const double *top, const std::vector<const double *> &layer_value, Valid &&valid) {
+      const std::vector<int> layer = P.cell_layers(n_layers, top, who);
+      std::vector<std::vector<double>> f(layer_value.size(), std::vector<double>(layer.size())); std::vector<const double *> at;
+      for (size_t a = 0; a < f.size(); ++a) { for (size_t c = 0; c < layer.size(); ++c) f[a][c] = layer_value[a][layer[c]]; at.push_back(f[a].data()); }
+      set(P, who, at, 1, (int64_t)layer.size(), valid);
+    }
+    // the field `old` of the refined box O, a refined box over the same coarse box as P, on P, component by component: every cell takes the value of its coarse cell -
+    // a child its parent's, a parent the mean of its children (which all hold the parent's value unless the caller set them apart)
+    void inherit(const ProblemData &P, const ProblemData &O, const PerCellField &old, const char *who) {
+      std::vector<std::vector<double>> got;
+      for (const std::vector<double> &one : old.comp) got.push_back(P.inherited(O, one, who));
+      comp = std::move(got);
+    }
+  };
 
-  // k / mu of the pressure system
-  std::vector<double> cell_k_over_mu;
+  // k / mu of the pressure system: one component, or the diagonal tensor diag(kx, ky[, kz]) / mu with `dim` components, x first (poro_ctx_set_cell_permeability[_tensor]);
+  // one field, as in the context.  The scalar and the tensor entry points each set, drop (null values) and inherit the field of their own shape only
+  PerCellField permeability;
+  bool carries_permeability(bool tensor) const { return !permeability.empty() && (permeability.ncomp() > 1) == tensor; }
   void set_cell_permeability(const double *values, int64_t n) {
-    if (!values) { cell_k_over_mu.clear(); return; }
-    check_field_length("set_cell_permeability", n);
-    for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability: value of cell " + std::to_string(i) + " is not finite and > 0");
-    cell_k_over_mu.assign(values, values + n); cell_k_tensor.clear();
+    if (!values) { if (carries_permeability(false)) permeability.clear(); return; }
+    permeability.set(*this, "set_cell_permeability", {values}, 1, n, valid_positive("set_cell_permeability"));
   }
   void set_permeability_layers(int n_layers, const double *top, const double *value) {
     if (n_layers < 1 || !top || !value) throw std::runtime_error("set_permeability_layers: needs at least one TOP=VALUE layer");
-    const std::vector<int> layer = cell_layers(n_layers, top, "set_permeability_layers");
-    std::vector<double> f(layer.size());
-    for (size_t c = 0; c < layer.size(); ++c) f[c] = value[layer[c]];
-    set_cell_permeability(f.data(), (int64_t)f.size());
+    permeability.set_by_layers(*this, "set_permeability_layers", n_layers, top, {value}, valid_positive("set_cell_permeability"));
   }
-  void inherit_cell_permeability(const ProblemData &O) { cell_k_over_mu = inherited(O, O.cell_k_over_mu, "inherit_cell_permeability"); }
-
-  // the diagonal tensor diag(kx, ky[, kz]) / mu of the pressure system, [n_cells][dim], x first (poro_ctx_set_cell_permeability_tensor).  The problem carries the scalar
-  // field or the tensor: setting one drops the other
-  std::vector<double> cell_k_tensor;
+  auto valid_tensor() const {
+    return [dim = mesh.dim](int64_t i, const double *v) {
+      for (int d = 0; d < dim; ++d) if (!(std::isfinite(v[d]) && v[d] > 0)) throw std::runtime_error("set_cell_permeability_tensor: component " + std::to_string(d) + " of cell " + std::to_string(i) + " is not finite and > 0");
+    };
+  }
+  // values[n][dim]
   void set_cell_permeability_tensor(const double *values, int64_t n) {
-    if (!values) { cell_k_tensor.clear(); return; }
-    check_field_length("set_cell_permeability_tensor", n);
-    const int dim = mesh.dim;
-    for (int64_t i = 0; i < n * dim; ++i)
-      if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_permeability_tensor: component " + std::to_string(i % dim) + " of cell " + std::to_string(i / dim) + " is not finite and > 0");
-    cell_k_tensor.assign(values, values + n * dim); cell_k_over_mu.clear();
+    if (!values) { if (carries_permeability(true)) permeability.clear(); return; }
+    std::vector<const double *> at; for (int d = 0; d < mesh.dim; ++d) at.push_back(values + d);
+    permeability.set(*this, "set_cell_permeability_tensor", at, mesh.dim, n, valid_tensor());
   }
   // kz is not read in 2D (may be null)
   void set_permeability_tensor_layers(int n_layers, const double *top, const double *kx, const double *ky, const double *kz) {
     const int dim = mesh.dim;
     if (n_layers < 1 || !top || !kx || !ky || (dim == 3 && !kz)) throw std::runtime_error("set_permeability_tensor_layers: needs at least one TOP=KX:KY[:KZ] layer with one value per direction");
-    const std::vector<int> layer = cell_layers(n_layers, top, "set_permeability_tensor_layers");
-    const double *comp[3] = {kx, ky, kz};
-    std::vector<double> f(layer.size() * dim);
-    for (size_t c = 0; c < layer.size(); ++c) for (int d = 0; d < dim; ++d) f[c * dim + d] = comp[d][layer[c]];
-    set_cell_permeability_tensor(f.data(), (int64_t)layer.size());
+    permeability.set_by_layers(*this, "set_permeability_tensor_layers", n_layers, top, dim == 3 ? std::vector<const double *>{kx, ky, kz} : std::vector<const double *>{kx, ky}, valid_tensor());
   }
-  // component by component through the coarse cells: a child takes its parent's components exactly, a coarsened parent the per-component mean
-  void inherit_cell_permeability_tensor(const ProblemData &O) {
-    const int dim = mesh.dim; const size_t n_old = O.cell_k_tensor.size() / dim;
-    std::vector<double> out, one(n_old);
-    for (int d = 0; d < dim && n_old; ++d) {
-      for (size_t c = 0; c < n_old; ++c) one[c] = O.cell_k_tensor[c * dim + d];
-      const std::vector<double> got = inherited(O, one, "inherit_cell_permeability_tensor");
-      if (!d) out.resize(got.size() * dim);
-      for (size_t c = 0; c < got.size(); ++c) out[c * dim + d] = got[c];
-    }
-    cell_k_tensor = std::move(out);
+  void inherit_cell_permeability(const ProblemData &O, bool tensor = false) {
+    if (O.carries_permeability(tensor)) permeability.inherit(*this, O, O.permeability, tensor ? "inherit_cell_permeability_tensor" : "inherit_cell_permeability");
+    else if (carries_permeability(tensor)) permeability.clear();
   }
+  void inherit_cell_permeability_tensor(const ProblemData &O) { inherit_cell_permeability(O, true); }
 
-  // Lame lambda and shear modulus G of the displacement system (the two come together)
-  std::vector<double> cell_lambda, cell_G;
-  bool moduli_structured = false;   // PORO_MODULI_OP_STRUCTURED for the contexts a run creates from this problem (host_capi.cpp: the run entry points copy it into RunControls)
+  // Lame lambda and shear modulus G of the displacement system: two components, lambda first
+  PerCellField moduli;
   void set_cell_moduli(const double *lam, const double *G, int64_t n) {
-    if (!lam && !G) { cell_lambda.clear(); cell_G.clear(); return; }
+    if (!lam && !G) { moduli.clear(); return; }
     if (!lam || !G) throw std::runtime_error("set_cell_moduli: lambda and G come together");
-    check_field_length("set_cell_moduli", n);
-    for (int64_t i = 0; i < n; ++i)
-      if (!(std::isfinite(lam[i]) && std::isfinite(G[i]) && G[i] > 0 && 3 * lam[i] + 2 * G[i] > 0))
-        throw std::runtime_error("set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite with G > 0 and 3 lambda + 2 G > 0");
-    cell_lambda.assign(lam, lam + n); cell_G.assign(G, G + n);
+    moduli.set(*this, "set_cell_moduli", {lam, G}, 1, n, valid_moduli);
   }
   // by Young's modulus and Poisson's ratio; lambda and G by the formulas of InputDataPoroel::compute_derived_parameters
   void set_moduli_layers(int n_layers, const double *top, const double *young, const double *poisson) {
     if (n_layers < 1 || !top || !young || !poisson) throw std::runtime_error("set_moduli_layers: needs at least one TOP=YOUNG:POISSON layer");
-    for (int l = 0; l < n_layers; ++l)
-      if (!(std::isfinite(young[l]) && young[l] > 0 && poisson[l] > -1.0 && poisson[l] < 0.5))
-        throw std::runtime_error("set_moduli_layers: layer " + std::to_string(l) + " needs a Young's modulus > 0 and a Poisson ratio in (-1, 0.5)");
-    const std::vector<int> layer = cell_layers(n_layers, top, "set_moduli_layers");
-    std::vector<double> lam(layer.size()), G(layer.size());
-    for (size_t c = 0; c < layer.size(); ++c) {
-      const double E = young[layer[c]], nu = poisson[layer[c]];
-      lam[c] = E * nu / ((1. + nu) * (1. - 2. * nu)); G[c] = 0.5 * E / (1 + nu);
+    std::vector<double> lam((size_t)n_layers), G((size_t)n_layers);
+    for (int l = 0; l < n_layers; ++l) {
+      const double E = young[l], nu = poisson[l];
+      if (!(std::isfinite(E) && E > 0 && nu > -1.0 && nu < 0.5)) throw std::runtime_error("set_moduli_layers: layer " + std::to_string(l) + " needs a Young's modulus > 0 and a Poisson ratio in (-1, 0.5)");
+      lam[l] = E * nu / ((1. + nu) * (1. - 2. * nu)); G[l] = 0.5 * E / (1 + nu);
     }
-    set_cell_moduli(lam.data(), G.data(), (int64_t)lam.size());
+    moduli.set_by_layers(*this, "set_moduli_layers", n_layers, top, {lam.data(), G.data()}, valid_moduli);
   }
-  void inherit_cell_moduli(const ProblemData &O) {
-    std::vector<double> lam = inherited(O, O.cell_lambda, "inherit_cell_moduli");
-    cell_G = inherited(O, O.cell_G, "inherit_cell_moduli"); cell_lambda = std::move(lam);
+  void inherit_cell_moduli(const ProblemData &O) { moduli.inherit(*this, O, O.moduli, "inherit_cell_moduli"); }
+  static void valid_moduli(int64_t i, const double *v) {
+    if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && v[1] > 0 && 3 * v[0] + 2 * v[1] > 0))
+      throw std::runtime_error("set_cell_moduli: moduli of cell " + std::to_string(i) + " are not finite with G > 0 and 3 lambda + 2 G > 0");
   }
 
   // Gravity (poro_ctx_set_gravity / poro_ctx_set_cell_density): the vector g, the fluid density rho_f of the Darcy gravity flux (0: no flux term), the scalar bulk density
   // (the declared default of "Properties/Bulk density"; poro_run copies the parsed value) and the optional per-cell bulk density.  All zeros: no gravity, the reference's
   // body force.  hydrostatic_init: a run starts from p_init + rho_f g . (x - x_top), x_top = the vertex furthest against g, instead of the uniform p_init
   double gravity[3] = {0, 0, 0}, fluid_density = 0, bulk_density = 2700; bool hydrostatic_init = false;
-  std::vector<double> cell_density;
+  PerCellField density;
   bool has_gravity() const { return gravity[0] != 0 || gravity[1] != 0 || gravity[2] != 0; }
   void set_gravity(const double *g /* [dim]; null: off */, double rho_f, double rho_b /* < 0: keep the present scalar */) {
     for (int d = 0; g && d < mesh.dim; ++d) if (!std::isfinite(g[d])) throw std::runtime_error("set_gravity: component " + std::to_string(d) + " of g is not finite");
@@ -547,21 +559,16 @@ struct ProblemData {
     fluid_density = rho_f; if (rho_b >= 0) bulk_density = rho_b;
   }
   void set_cell_density(const double *values, int64_t n) {
-    if (!values) { cell_density.clear(); return; }
-    check_field_length("set_cell_density", n);
-    for (int64_t i = 0; i < n; ++i) if (!(std::isfinite(values[i]) && values[i] > 0)) throw std::runtime_error("set_cell_density: value of cell " + std::to_string(i) + " is not finite and > 0");
-    cell_density.assign(values, values + n);
+    if (!values) { density.clear(); return; }
+    density.set(*this, "set_cell_density", {values}, 1, n, valid_positive("set_cell_density"));
   }
   void set_density_layers(int n_layers, const double *top, const double *rho) {
     if (n_layers < 1 || !top || !rho) throw std::runtime_error("set_density_layers: needs at least one TOP=RHO layer");
-    const std::vector<int> layer = cell_layers(n_layers, top, "set_density_layers");
-    std::vector<double> f(layer.size());
-    for (size_t c = 0; c < layer.size(); ++c) f[c] = rho[layer[c]];
-    set_cell_density(f.data(), (int64_t)f.size());
+    density.set_by_layers(*this, "set_density_layers", n_layers, top, {rho}, valid_positive("set_cell_density"));
   }
   // a child takes its parent's density, a coarsened parent the mean of its children; the scalars go along
   void inherit_cell_density(const ProblemData &O) {
-    cell_density = inherited(O, O.cell_density, "inherit_cell_density");
+    density.inherit(*this, O, O.density, "inherit_cell_density");
     for (int d = 0; d < 3; ++d) gravity[d] = O.gravity[d];
     fluid_density = O.fluid_density; bulk_density = O.bulk_density; hydrostatic_init = O.hydrostatic_init;
   }

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include "../../include/poroel_hip.h"
 #include "mesh.hpp"
+#include "run_controls.hpp"
 
 namespace poro_host {
 
@@ -37,28 +38,6 @@ struct DeviceVector {
   double l2_norm() const { double a, b; check(poro_vec_norm(ctx, id, &a, &b), "vec_norm"); return a; }
   double linfty_norm() const { double a, b; check(poro_vec_norm(ctx, id, &a, &b), "vec_norm"); return b; }
   void get(std::vector<double> &h, int64_t n) const { h.resize(n); check(poro_vec_get(ctx, id, h.data(), n), "vec_get"); }
-};
-
-struct RunControls {
-  double p_init = 10e6, time_step = 60; int n_steps = 1;
-  double fss_tol = 1e-8, pressure_tol = 1e-8; int max_fss_iterations = 50, max_pressure_iterations = 50;
-  double abs_tol_u = 1e-12, rel_tol_u = 0.0; int max_iter = 1000;   // PoroElasticDisplacementSolver.h:298-299
-  int stop_rule_u = PORO_STOP_RHS;                                  // PORO_STOP_REDUCTION: rel_tol_u is taken against the residual of the warm start (every step of a transient solves)
-  int preconditioner = PORO_PREC_JACOBI;                            // displacement solve; PORO_PREC_SSOR = the reference's PreconditionSSOR (CSR operator, one rank) for all three systems
-  bool coupled_fss = false;                                         // true = restore the get_volumetric_strain() call the reference commented out (:399): eps_v follows the new
-                                                                    // displacement inside the fixed-stress loop, which then really iterates (SURVEY 8f-4 "corrected physics", first half)
-  bool incremental_strain = false;                                  // true = storage term against the previous step, alpha (eps_v - eps_v^n) / dt, instead of the initial state eps_v0 (:317, :361-363)
-  bool corrected_postprocessing = false;                            // false = the reference's output (shear RHS never assembled, 2D "sigma_yy" shows sigma_xx); true = both fixed
-  std::string output_dir;                                           // "" = no files; the reference always writes ./solution/solution-NNNN.vtk (:285-290)
-  int chebyshev_degree = 0; double chebyshev_ratio = 0.0;           // PORO_PREC_CHEBYSHEV: 0 = the library's defaults
-  int preconditioner_p = -1;                                        // pressure / projection solves; -1 = fast diagonalisation where the context supports it, else the two-level form, else Jacobi
-  bool fdm_fp32 = false;                                            // PORO_FDM_FP32: fp32 transforms in the displacement system's block FDM where it runs in the single-rank 3D octant form (elsewhere no effect).  Never chosen automatically
-  bool fdm_per_direction = false;                                   // PORO_FDM_FORM_PER_DIRECTION: the block FDM's contiguous passes on single-rank 3D boxes whose directions are not all mirror-symmetric (elsewhere no effect).  Never chosen automatically
-  bool moduli_structured = false;                                   // PORO_MODULI_OP_STRUCTURED: the structured operator on single-rank uniform 3D boxes with moduli layered along z, matrix-free (elsewhere no effect).  Never chosen automatically
-  bool atomic_scatter = false;                                      // general meshes, matrix-free: PORO_SCATTER_ATOMIC (one launch per operator application; not bitwise reproducible).  Never chosen automatically
-  bool hybrid_operator = false;                                     // refined boxes, matrix-free: PORO_OPFORM_HYBRID (structured kernel on the coarse box + general kernels on the fine cells); a no-op on box-tagged meshes, an error on meshes that cannot take it.  Never chosen automatically
-  int refine_every = 0;                                             // refine_mesh when time_step_number % refine_every == 0 (the reference hard-wires 5, PoroelasticityFSS.h:333); 0 = never
-  double refine_fraction = 0.6, coarsen_fraction = 0.4;             // refine_and_coarsen_fixed_fraction (:460-462)
 };
 
 }  // namespace poro_host
@@ -200,9 +179,8 @@ template <int dim> class PoroElasticProblem {
     std::unique_ptr<ProblemData> N(new ProblemData());
     N->bc = O.bc; N->mat = O.mat;
     build_refined_box_problem_mask(*N, O.mesh.dim, O.box_n, O.box_size, O.box_k_u, mask);    // :481-483
-    N->inherit_cell_moduli(O);                                                               // likewise lambda, G (poro_ctx_set_cell_moduli)
-    N->inherit_cell_permeability(O);                                                         // a child takes its parent's k / mu; make_ctx below hands the field to the new context
-    N->inherit_cell_permeability_tensor(O);                                                  // or its parent's diag(kx, ky, kz) / mu, component by component
+    N->inherit_cell_moduli(O);                                                               // lambda, G (poro_ctx_set_cell_moduli); make_ctx below hands the fields to the new context
+    N->permeability.inherit(*N, O, O.permeability, "inherit_cell_permeability");             // a child takes its parent's k / mu, or its parent's diag(kx, ky, kz) / mu component by component
     N->inherit_cell_density(O);                                                              // the bulk density likewise, with g and the two scalar densities (poro_ctx_set_gravity)
     std::vector<int64_t> ptr; std::vector<int32_t> node; std::vector<double> weight;
     transfer_rows_p(O, *N, ptr, node, weight);
@@ -446,10 +424,12 @@ template <int dim> class PoroElasticProblem {
     poro_ctx *c = nullptr;
     check(poro_ctx_create(&P.d, device, operator_mode, &c), "poro_ctx_create");
     // the per-cell fields of the problem go to the context before anything is assembled from it
-    const char *failed = !P.cell_k_over_mu.empty() && poro_ctx_set_cell_permeability(c, P.cell_k_over_mu.data(), (int64_t)P.cell_k_over_mu.size()) != 0 ? "ctx_set_cell_permeability: "
-                         : !P.cell_k_tensor.empty() && poro_ctx_set_cell_permeability_tensor(c, P.cell_k_tensor.data(), (int64_t)P.cell_k_tensor.size() / P.mesh.dim) != 0 ? "ctx_set_cell_permeability_tensor: "
-                         : !P.cell_lambda.empty() && poro_ctx_set_cell_moduli(c, P.cell_lambda.data(), P.cell_G.data(), (int64_t)P.cell_lambda.size()) != 0 ? "ctx_set_cell_moduli: "
-                         : !P.cell_density.empty() && poro_ctx_set_cell_density(c, P.cell_density.data(), (int64_t)P.cell_density.size()) != 0 ? "ctx_set_cell_density: "
+    const ProblemData::PerCellField &k = P.permeability, &m = P.moduli, &rho = P.density; const int64_t n = P.mesh.n_cells();
+    const std::vector<double> tensor = k.ncomp() > 1 ? k.interleaved() : std::vector<double>();      // [cell][dim], x first
+    const char *failed = k.ncomp() == 1 && poro_ctx_set_cell_permeability(c, k.comp[0].data(), n) != 0 ? "ctx_set_cell_permeability: "
+                         : k.ncomp() > 1 && poro_ctx_set_cell_permeability_tensor(c, tensor.data(), n) != 0 ? "ctx_set_cell_permeability_tensor: "
+                         : !m.empty() && poro_ctx_set_cell_moduli(c, m.comp[0].data(), m.comp[1].data(), n) != 0 ? "ctx_set_cell_moduli: "
+                         : !rho.empty() && poro_ctx_set_cell_density(c, rho.comp[0].data(), n) != 0 ? "ctx_set_cell_density: "
                          : P.has_gravity() && poro_ctx_set_gravity(c, P.gravity, P.bulk_density, P.fluid_density) != 0 ? "ctx_set_gravity: " : nullptr;      // (after the permeability: the gravity flux is built once)
     if (failed) { const std::string why = poro_last_error(); poro_ctx_destroy(c); throw std::runtime_error(failed + why); }
     return c;

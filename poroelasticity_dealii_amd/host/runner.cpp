@@ -53,8 +53,8 @@ static bool positive(double v) { return v > 0 && std::isfinite(v); }
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::cerr << "specify the file name" << std::endl << kUsage << std::endl; return 1; }   // parse_command_line.h:9-13 (the usage line is this driver's)
-  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0, prec = PORO_PREC_JACOBI; std::string output_dir; bool corrected = false, coupled = false, incremental = false, atomic_scatter = false, fdm_fp32 = false, hybrid_operator = false, fdm_per_direction = false, moduli_structured = false;
-  int refine_every = 0; double refine_fraction = 0.6, coarsen_fraction = 0.4;
+  std::string mesh_file; int degree = 2, op = PORO_OP_CSR, steps = -1, device = 0;
+  RunControls rc;      // the options go straight into it; the parameter file adds its own below
   std::vector<int32_t> pressure_labels; std::vector<double> pressure_values;
   std::vector<double> layer_top, layer_value;
   std::vector<double> tensor_top, tensor_k[3];
@@ -66,22 +66,22 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--steps") && i + 1 < argc) steps = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--matrix-free")) op = PORO_OP_MATRIX_FREE;
-    else if (!std::strcmp(argv[i], "--output") && i + 1 < argc) output_dir = argv[++i];
-    else if (!std::strcmp(argv[i], "--corrected-output")) corrected = true;
-    else if (!std::strcmp(argv[i], "--incremental-strain")) incremental = true;   // storage term against the previous step instead of the initial state
-    else if (!std::strcmp(argv[i], "--coupled-fss")) coupled = true;    // restore get_volumetric_strain() inside the fixed-stress loop (:399)
-    else if (!std::strcmp(argv[i], "--ssor")) prec = PORO_PREC_SSOR;   // the reference's PreconditionSSOR instead of Jacobi
-    else if (!std::strcmp(argv[i], "--chebyshev")) prec = PORO_PREC_CHEBYSHEV;   // polynomial preconditioner (any mesh / operator)
-    else if (!std::strcmp(argv[i], "--block-fdm")) prec = PORO_PREC_FDM;         // block fast diagonalisation (uniform boxes with face-wise Dirichlet data)
-    else if (!std::strcmp(argv[i], "--two-level")) prec = PORO_PREC_TWO_LEVEL;   // Jacobi + block fast diagonalisation of the underlying / auxiliary box (refined boxes, rectangle-filling Gmsh meshes)
-    else if (!std::strcmp(argv[i], "--atomic-scatter")) atomic_scatter = true;   // general meshes, --matrix-free: one launch per operator application with fp64 atomic adds (last bits differ from run to run)
-    else if (!std::strcmp(argv[i], "--hybrid-operator")) hybrid_operator = true; // refined boxes (--refine-every), --matrix-free: the box's structured kernel + the general kernels on the fine cells only; no effect on box-tagged meshes, an error where the mesh cannot take it
-    else if (!std::strcmp(argv[i], "--fdm-fp32")) fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
-    else if (!std::strcmp(argv[i], "--fdm-per-direction")) fdm_per_direction = true;   // with --block-fdm / --fastest: the per-direction form of the block FDM (single-rank 3D boxes whose directions are not all mirror-symmetric; elsewhere no effect)
-    else if (!std::strcmp(argv[i], "--moduli-structured")) moduli_structured = true;   // with --moduli-layers and --matrix-free: the structured operator on uniform 3D boxes whose layers follow the cell layers of z (elsewhere no effect)
-    else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) refine_every = std::atoi(argv[++i]);            // 0 = never (default)
-    else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
-    else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) coarsen_fraction = std::atof(argv[++i]);
+    else if (!std::strcmp(argv[i], "--output") && i + 1 < argc) rc.output_dir = argv[++i];
+    else if (!std::strcmp(argv[i], "--corrected-output")) rc.corrected_postprocessing = true;
+    else if (!std::strcmp(argv[i], "--incremental-strain")) rc.incremental_strain = true;   // storage term against the previous step instead of the initial state
+    else if (!std::strcmp(argv[i], "--coupled-fss")) rc.coupled_fss = true;    // restore get_volumetric_strain() inside the fixed-stress loop (:399)
+    else if (!std::strcmp(argv[i], "--ssor")) rc.preconditioner = PORO_PREC_SSOR;   // the reference's PreconditionSSOR instead of Jacobi
+    else if (!std::strcmp(argv[i], "--chebyshev")) rc.preconditioner = PORO_PREC_CHEBYSHEV;   // polynomial preconditioner (any mesh / operator)
+    else if (!std::strcmp(argv[i], "--block-fdm")) rc.preconditioner = PORO_PREC_FDM;         // block fast diagonalisation (uniform boxes with face-wise Dirichlet data)
+    else if (!std::strcmp(argv[i], "--two-level")) rc.preconditioner = PORO_PREC_TWO_LEVEL;   // Jacobi + block fast diagonalisation of the underlying / auxiliary box (refined boxes, rectangle-filling Gmsh meshes)
+    else if (!std::strcmp(argv[i], "--atomic-scatter")) rc.atomic_scatter = true;   // general meshes, --matrix-free: one launch per operator application with fp64 atomic adds (last bits differ from run to run)
+    else if (!std::strcmp(argv[i], "--hybrid-operator")) rc.hybrid_operator = true; // refined boxes (--refine-every), --matrix-free: the box's structured kernel + the general kernels on the fine cells only; no effect on box-tagged meshes, an error where the mesh cannot take it
+    else if (!std::strcmp(argv[i], "--fdm-fp32")) rc.fdm_fp32 = true;               // with --block-fdm / --fastest: fp32 transforms in the displacement system's block FDM (single-rank 3D octant form; elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--fdm-per-direction")) rc.fdm_per_direction = true;   // with --block-fdm / --fastest: the per-direction form of the block FDM (single-rank 3D boxes whose directions are not all mirror-symmetric; elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--moduli-structured")) rc.moduli_structured = true;   // with --moduli-layers and --matrix-free: the structured operator on uniform 3D boxes whose layers follow the cell layers of z (elsewhere no effect)
+    else if (!std::strcmp(argv[i], "--refine-every") && i + 1 < argc) rc.refine_every = std::atoi(argv[++i]);            // 0 = never (default)
+    else if (!std::strcmp(argv[i], "--refine-fraction") && i + 1 < argc) rc.refine_fraction = std::atof(argv[++i]);
+    else if (!std::strcmp(argv[i], "--coarsen-fraction") && i + 1 < argc) rc.coarsen_fraction = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--pressure-bc") && i + 1 < argc) {           // prescribed pressure VALUE on the boundary LABEL (one rank; boxes: whole faces, which keeps the fast diagonalisation)
       const char *arg = argv[++i], *eq = std::strchr(arg, '='); char *end = nullptr, *end2 = nullptr;
       const long label = std::strtol(arg, &end, 10); const double value = eq ? std::strtod(eq + 1, &end2) : 0.0;
@@ -127,14 +127,14 @@ int main(int argc, char **argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--hydrostatic-init")) hydrostatic_init = true;   // with --gravity and --fluid-density: start from the initial pressure at the top and the hydrostatic pressure below
-    else if (!std::strcmp(argv[i], "--fastest")) prec = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
+    else if (!std::strcmp(argv[i], "--fastest")) rc.preconditioner = -1;                      // the strongest preconditioner the mesh supports: block FDM, else two-level, else Chebyshev
     else { std::cerr << "unknown option " << argv[i] << std::endl; return 1; }
   }
-  if (fdm_fp32 && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
-  if (fdm_per_direction && prec != PORO_PREC_FDM && prec != -1) { std::cerr << "--fdm-per-direction needs --block-fdm or --fastest" << std::endl; return 1; }
+  if (rc.fdm_fp32 && rc.preconditioner != PORO_PREC_FDM && rc.preconditioner != -1) { std::cerr << "--fdm-fp32 needs --block-fdm or --fastest" << std::endl; return 1; }
+  if (rc.fdm_per_direction && rc.preconditioner != PORO_PREC_FDM && rc.preconditioner != -1) { std::cerr << "--fdm-per-direction needs --block-fdm or --fastest" << std::endl; return 1; }
   if (!layer_top.empty() && !tensor_top.empty()) { std::cerr << "--permeability-tensor-layers and --permeability-layers exclude each other (a context holds the scalar field or the tensor)" << std::endl; return 1; }
-  if (refine_every < 0) { std::cerr << "--refine-every needs a non-negative step count" << std::endl; return 1; }
-  if (refine_every > 0 && !mesh_file.empty()) { std::cerr << "--refine-every adapts boxes only (not --mesh)" << std::endl; return 1; }
+  if (rc.refine_every < 0) { std::cerr << "--refine-every needs a non-negative step count" << std::endl; return 1; }
+  if (rc.refine_every > 0 && !mesh_file.empty()) { std::cerr << "--refine-every adapts boxes only (not --mesh)" << std::endl; return 1; }
   try {
     input_data::InputDataPoroel data;
     data.read_input_file(argv[1]);
@@ -151,7 +151,7 @@ int main(int argc, char **argv) {
     else {
       int n[3] = {1, 1, 1}; double size[3] = {1, 1, 1};
       for (int d = 0; d < data.dim; ++d) { n[d] = 1 << data.initial_refinement_level; size[d] = data.domain_size.at(d); }
-      if (refine_every > 0) build_refined_box_problem_mask(P, data.dim, n, size, degree, std::vector<uint8_t>((size_t)n[0] * n[1] * n[2], 0));
+      if (rc.refine_every > 0) build_refined_box_problem_mask(P, data.dim, n, size, degree, std::vector<uint8_t>((size_t)n[0] * n[1] * n[2], 0));
       else build_box_problem(P, data.dim, n, size, degree);
     }
     if (!layer_top.empty()) P.set_permeability_layers((int)layer_top.size(), layer_top.data(), layer_value.data());
@@ -165,10 +165,8 @@ int main(int argc, char **argv) {
       P.set_gravity(gravity.data(), fluid_density, data.bulk_density); P.hydrostatic_init = hydrostatic_init;
     }
     if (!density_top.empty()) P.set_density_layers((int)density_top.size(), density_top.data(), density_value.data());
-    RunControls rc; rc.preconditioner = prec; rc.output_dir = output_dir; rc.corrected_postprocessing = corrected; rc.coupled_fss = coupled; rc.incremental_strain = incremental; rc.atomic_scatter = atomic_scatter; rc.fdm_fp32 = fdm_fp32; rc.hybrid_operator = hybrid_operator; rc.fdm_per_direction = fdm_per_direction; rc.moduli_structured = moduli_structured;
     rc.p_init = data.p_init; rc.time_step = data.time_step; rc.fss_tol = data.fss_tol; rc.pressure_tol = data.pressure_tol;
     rc.max_fss_iterations = data.max_fss_iterations; rc.max_pressure_iterations = data.max_pressure_iterations;
-    rc.refine_every = refine_every; rc.refine_fraction = refine_fraction; rc.coarsen_fraction = coarsen_fraction;
     int n_steps = 0; for (double t = 0; t < data.t_max; t += data.time_step) ++n_steps;   // while (time < t_max) (:327)
     rc.n_steps = steps >= 0 ? steps : n_steps;
     std::vector<double> trace(8 * (size_t)(1 + rc.n_steps * rc.max_fss_iterations));
@@ -180,7 +178,7 @@ int main(int argc, char **argv) {
         int32_t kind = 0;
         if (poro_ctx_get_cell_moduli(prob.context(), nullptr, nullptr, 0, &kind) != 0) throw std::runtime_error(poro_last_error());
         os << "moduli layers: " << moduli_top.size() << ", field kind " << kind << "; displacement preconditioner: " << prec_name[prob.displacement_solver.control.preconditioner];
-        if (moduli_structured) {           // (only with the option) what an operator application runs on the present context
+        if (rc.moduli_structured) {           // (only with the option) what an operator application runs on the present context
           int32_t req = 0, eff = 0;
           if (poro_ctx_get_moduli_operator(prob.context(), &req, &eff) != 0) throw std::runtime_error(poro_last_error());
           os << "; moduli operator: " << (eff == PORO_MODULI_OP_STRUCTURED ? "structured" : "cell loop");
@@ -207,7 +205,7 @@ int main(int argc, char **argv) {
                     << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
         };
       rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
-      if (fdm_per_direction) {           // (only with the option, so the reference's log stays as it is)
+      if (rc.fdm_per_direction) {           // (only with the option, so the reference's log stays as it is)
         static const char *const runs[] = {"nodal kernels", "octant form", "per-direction form", "slab form", "planar form"};
         int32_t req = 0, eff = 0, split[3] = {0, 0, 0};
         if (poro_ctx_get_fdm_form(prob.context(), &req, &eff, split) != 0) throw std::runtime_error(poro_last_error());

@@ -90,7 +90,7 @@ def refine_and_coarsen_pair():
 
 
 def build_sanitized_check(tmp_path, name):
-    """tests/<name>.cpp, a stand-alone program over a host-only header of csrc/, built with the address and undefined-behaviour sanitizers; returns the executable"""
+    """tests/<name>.cpp, a stand-alone program over a host-only header of csrc/ or host/, built with the address and undefined-behaviour sanitizers; returns the executable"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / name)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(root, "poroelasticity_dealii_amd", "csrc"),

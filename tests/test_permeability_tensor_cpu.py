@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import poroelasticity_dealii_amd as pk
-from common import INPUT_DATA, build_sanitized_check, centres, layered_field_problems, refine_and_coarsen_pair
+from common import INPUT_DATA, ROLLERS3, build_sanitized_check, centres, layered_field_problems, material, refine_and_coarsen_pair
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PORO_RUN = os.path.join(ROOT, "poroelasticity_dealii_amd", "lib", "poro_run")
@@ -64,6 +64,48 @@ def test_inheritance_through_cell_parents():
         assert B.cell_permeability_tensor() is None
     finally:
         A.close(); B.close()
+
+
+def test_the_problem_carries_one_permeability_field():
+    """the scalar after the tensor, and the tensor after the scalar, leave exactly one readable through the getters; None to one entry point leaves the other's field"""
+    A, B, nc = refine_and_coarsen_pair()
+    try:
+        n = A.desc.n_cells
+        scalar = 1.0 + np.arange(n); tensor = 1.0 + np.arange(3.0 * n).reshape(n, 3)
+        A.set_cell_permeability_tensor(tensor); A.set_cell_permeability(scalar)
+        assert A.cell_permeability_tensor() is None and np.array_equal(A.cell_permeability(), scalar)
+        A.set_cell_permeability_tensor(None)                                         # (no tensor to drop: the scalar stays)
+        assert A.cell_permeability_tensor() is None and np.array_equal(A.cell_permeability(), scalar)
+        A.set_cell_permeability_tensor(tensor)
+        assert A.cell_permeability() is None and np.array_equal(A.cell_permeability_tensor(), tensor)
+        A.set_cell_permeability(None)                                                # (no scalar to drop: the tensor stays)
+        assert A.cell_permeability() is None and np.array_equal(A.cell_permeability_tensor(), tensor)
+        # inheritance likewise: each entry point carries the field of its own shape
+        B.inherit_cell_permeability(A)
+        assert B.cell_permeability() is None and B.cell_permeability_tensor() is None
+        B.inherit_cell_permeability_tensor(A)
+        assert B.cell_permeability() is None and B.cell_permeability_tensor().shape == (B.desc.n_cells, 3)
+    finally:
+        A.close(); B.close()
+
+
+def test_layered_tensor_through_a_refine_and_coarsen_round_trip():
+    """a tensor set by layers on the unrefined 2 x 2 x 2 box, carried to the box with three cells refined and back: the layer values, exactly, per component"""
+    layers = [(0.0, 3.0, 5.0, 0.03), (2.0, 1e-3, 2e-3, 1e-6)]
+    masks = [np.zeros(8, dtype=np.int32), np.array([1, 0, 0, 1, 0, 0, 1, 0], dtype=np.int32), np.zeros(8, dtype=np.int32)]
+    A, B, C = [pk.Problem.refined_box_mask(3, [2, 2, 2], [4.0, 4.0, 4.0], 1, material(), ROLLERS3, m) for m in masks]
+    try:
+        def by_layers(P):
+            return np.array([l[1:] for l in layers])[np.searchsorted([l[0] for l in layers], centres(P)[:, -1], side="left")]
+        A.set_permeability_tensor_layers(layers)
+        B.inherit_cell_permeability_tensor(A); C.inherit_cell_permeability_tensor(B)
+        assert (A.desc.n_cells, B.desc.n_cells, C.desc.n_cells) == (8, 8 + 3 * 7, 8)
+        for P in (A, B, C):
+            f = P.cell_permeability_tensor()
+            assert f.shape == (P.desc.n_cells, 3) and np.array_equal(f, by_layers(P))
+        assert len(set(B.cell_permeability_tensor()[:, 2])) == 2 and np.array_equal(C.cell_permeability_tensor(), A.cell_permeability_tensor())
+    finally:
+        A.close(); B.close(); C.close()
 
 
 def test_symbols_and_abi():
