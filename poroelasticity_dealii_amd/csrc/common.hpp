@@ -113,6 +113,12 @@ struct FdmU : SlabLayout {
 // direction.  Each of the 24 (component, octant) blocks is then an independent half-size 3D transform, done in three passes (x y fused per plane, z
 // forward + eigenvalue scaling + z backward, y x fused per plane); the butterflies ride in the CG update kernels, which touch every entry anyway.
 struct FdmoPlans;
+// strip form of the scalar Q1 passes: the share of the CUs a block-per-workgroup launch must reach to keep the block form.  Measured on one MI355X (256 CUs) with
+// tools/q1_strips_bench.py, block -> strip form in us per three passes, at (workgroups of the block form) / CUs: 0.09 (24^3 vertices, 1 right-hand side) 24.0 -> 22.6,
+// 0.19 (48^3, 1) 32.7 -> 21.7, 0.28 (72^3, 1) 58.1 -> 41.3 and (24^3, 3) 19.0 -> 14.8, 0.56 (48^3, 3) 31.2 -> 23.8 - but 0.47 (120^3, 1; eight tiles) 134.4 -> 140.3,
+// 0.84 (72^3, 3) 57.7 -> 71.8, 1.41 (120^3, 3) 265 -> 360: every strip workgroup stages the whole block, so the form pays only while the chip is mostly empty.  The
+// crossover lies between 0.28 and 0.47 ("Strip form of the Q1 passes")
+constexpr double kFdmoStripFill = 0.4;
 struct FdmOct {
   bool built = false; int nt = 0;                 // 16-wide MFMA tiles per half line (max over the directions), 1..8
   int n[3] = {1, 1, 1}, h[3] = {1, 1, 1}; int hxp = 2;   // hxp: row pitch = h[0] rounded up to even (16-byte aligned rows; the pad entry is zero and stays zero)
@@ -150,6 +156,9 @@ struct FdmOct {
   std::shared_ptr<FdmoPlans> plans;              // displacement forms: the launch descriptors of the three passes, planned once by fdmo_finalize (kernels_fdmo.hip)
   struct ScalarTable { double a, kappa; DevBuf<double> t; };
   std::list<ScalarTable> scalar_tables;           // scalar form: a + kappa (lam_x + lam_y) per plane position, one table per (a, kappa) seen (pressure Jacobian, mass matrix)
+  // scalar form on one rank: a pass whose block-per-workgroup launch would start fewer workgroups than this runs in the strip form (k_fdmo_strip, fdmo_scalar_apply_many);
+  // kFdmoStripFill x the CUs of the device, set where the table set is built (PORO_FDMO_SCALAR_STRIPS = another factor; 0 keeps every pass in the block form)
+  double strip_limit = 0;
 };
 // one table set of the scalar Q1 systems: the six-launch form (kernels_fdm.hip) and, where usable, the same tables for the three-launch transform kernel
 // (kernels_fdmo.hip: 3D boxes, lines of at most 80 vertices)
@@ -361,6 +370,7 @@ void la_nodal_interp(hipStream_t s, const int64_t *ptr, const int32_t *col, cons
 void la_two_level_combine(hipStream_t s, const int64_t *ptr, const int32_t *col, const double *w, int64_t n_rows, int ncomp, const double *zc, const double *g, const double *dinv, const uint8_t *inert, double omega, double *z, int lanes = 1);
 void la_copy_many(hipStream_t s, int count, double *const *dst, const double *const *src, const int64_t *n);   // several device-to-device copies in one launch
 void la_post(hipStream_t s, Mailbox *mb, unsigned long long seq, const double *src, int n, const PcgScalars *sc);
+void la_reduce_post(hipStream_t s, const double *partials, int n_sets, double *red, int max_not_sum_mask, Mailbox *mb, unsigned long long seq);   // la_reduce_finish + la_post(red, n_sets) in one launch
 void la_copy(hipStream_t s, double *y, const double *x, int64_t n);
 void la_axpy(hipStream_t s, double *y, double a, const double *x, int64_t n);
 void la_add_range(hipStream_t s, double *y, const double *x, int64_t n);
@@ -528,8 +538,8 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
 bool fdmo_scalar_usable(int dim, const int nn[3]);
 void fdmo_scalar_init(FdmOct &O, const int nn[3], hipStream_t s);
 void fdmo_scalar_upload_dir(FdmOct &O, int dir, const LineTables &T);
-void fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate = nullptr);
-void fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate = nullptr);   // up to 3 right-hand sides in one set of launches
+int fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate = nullptr);   // both return the number of launches in the strip form (FdmOct::strip_limit)
+int fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate = nullptr);   // up to 3 right-hand sides in one set of launches
 // block partials of |y_e - b_e|^2 and |b_e|^2 for up to three (y, b) pairs: sets 2e and 2e + 1 of `partials`
 // mask != null: rows with mask[i] != 0 count in neither norm (prescribed rows of a system solved on its free rows)
 void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask = nullptr);

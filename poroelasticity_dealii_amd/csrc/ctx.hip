@@ -409,7 +409,7 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
   const auto t0 = std::chrono::steady_clock::now();
   if (batched) {
     Timed tm(c, "precondition_p_fdm");
-    fdmo_scalar_apply_many(s, c->q1_free.fused, a, kappa, n, b, x);
+    count_strip_launches(c, fdmo_scalar_apply_many(s, c->q1_free.fused, a, kappa, n, b, x));
   } else {
     const double kk[3] = {kappa, kappa, kappa};
     for (int e = 0; e < n; ++e) { if (kap) fdm_precondition_p_layered(c, a, b[e], x[e], set); else fdm_precondition_p(c, a, kk, b[e], x[e], set); }
@@ -423,9 +423,7 @@ bool solve_q1_direct(poro_ctx *c, double a, double kappa, int n, const double *c
     exchange_add(c, const_cast<double *>(y[e]), c->n_p, c->comm.part.plane_p);
   }
   la_residual_norms_many(s, n, y, b, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p, mask);
-  pcg_scalars_sum(s, c->partials.p, 2 * n, c->red.p);
-  allreduce_sum(c, c->red.p, 2 * n);
-  post_and_wait(c, c->red.p, 2 * n);
+  post_sums_and_wait(c, c->partials.p, 2 * n, 0, 2 * n);      // (sums: la_reduce_finish adds in the order of pcg_scalars_sum)
   bool all = true;
   for (int e = 0; e < n; ++e) {
     const double res = std::sqrt(c->mailbox->vals[2 * e]), bn = std::sqrt(c->mailbox->vals[2 * e + 1]);
@@ -809,9 +807,7 @@ int poro_vec_norm(poro_ctx *c, int which, double *l2, double *linf) {
     PORO_HIP(hipSetDevice(c->device));
     const int64_t n = vec_len(c, which), plane = is_u_vec(which) ? c->comm.part.plane_u : c->comm.part.plane_p;
     la_norm_partials(c->stream, vec(c, which), owned(c, n, plane), c->partials.p, c->partials.p + kMaxPartials);
-    la_reduce_finish(c->stream, c->partials.p, 2, c->red.p, 2);
-    allreduce_sum(c, c->red.p, 1);   // linf stays rank-local under a partition (reporting only, PoroelasticityFSS.h:387-389)
-    post_and_wait(c, c->red.p, 2);
+    post_sums_and_wait(c, c->partials.p, 2, 2, 1);   // linf stays rank-local under a partition (reporting only, PoroelasticityFSS.h:387-389)
     if (l2) *l2 = std::sqrt(c->mailbox->vals[0]); if (linf) *linf = c->mailbox->vals[1]; return 0;
   });
 }
@@ -958,9 +954,7 @@ int poro_pres_assemble_residual(poro_ctx *c, double dt, double *l2) {
     exchange_add(c, R, c->n_p, c->comm.part.plane_p);
     if (c->n_pdir) la_mask_zero(s, R, c->pdir_mask.p, c->n_p);                    // prescribed-pressure rows are not part of the Newton system
     la_dot_partials(s, R, R, owned(c, c->n_p, c->comm.part.plane_p), c->partials.p);
-    la_reduce_finish(s, c->partials.p, 1, c->red.p, 0);
-    allreduce_sum(c, c->red.p, 1);
-    post_and_wait(c, c->red.p, 1);
+    post_sums_and_wait(c, c->partials.p, 1, 0, 1);
     if (l2) *l2 = std::sqrt(c->mailbox->vals[0]);
     return 0;
   });

@@ -74,10 +74,28 @@ Timer *begin_sampled_dispatch(poro_ctx *c, const char *family) {
 
 // ---- device -> host scalars without a copy engine or a stream synchronisation (Mailbox, common.hpp) ------------------------------------------
 // enqueue the publishing kernel behind everything that is in the stream, then spin on the sequence number in pinned host memory
+static void mailbox_wait(poro_ctx *c, unsigned long long want);
 void post_and_wait(poro_ctx *c, const double *dev_src, int n, const PcgScalars *sc) {
   if (n > 16) throw Error("post_and_wait: at most 16 scalars");
   const unsigned long long want = ++c->mb_seq;
   la_post(c->stream, c->mailbox, want, dev_src, n, sc);
+  mailbox_wait(c, want);
+}
+// the same for n_sets sums (maxima: max_mask, la_reduce_finish) of block partials.  One rank: ONE launch adds them up in la_reduce_finish's order, leaves them in c->red and
+// publishes them; partitioned: the all-reduce of the first n_allreduce of them sits between la_reduce_finish and the publishing kernel, as before
+void post_sums_and_wait(poro_ctx *c, const double *partials, int n_sets, int max_mask, int n_allreduce) {
+  if (n_sets > 16) throw Error("post_sums_and_wait: at most 16 scalars");
+  if (c->comm.multi()) {
+    la_reduce_finish(c->stream, partials, n_sets, c->red.p, max_mask);
+    allreduce_sum(c, c->red.p, n_allreduce);
+    post_and_wait(c, c->red.p, n_sets);
+    return;
+  }
+  const unsigned long long want = ++c->mb_seq;
+  la_reduce_post(c->stream, partials, n_sets, c->red.p, max_mask, c->mailbox, want);
+  mailbox_wait(c, want);
+}
+static void mailbox_wait(poro_ctx *c, unsigned long long want) {
   PORO_HIP(hipGetLastError());
   const auto t0 = std::chrono::steady_clock::now(); unsigned spins = 0;
   while (__atomic_load_n(const_cast<unsigned long long *>(&c->mailbox->seq), __ATOMIC_ACQUIRE) != want) {

@@ -113,7 +113,11 @@ void build_fdm_q1(poro_ctx *c, Q1Set which) {
   // one rank, 3D, lines of at most 80 nodes: the three-launch form through the block-FDM transform kernel (kernels_fdmo.hip) instead of six single-direction launches
   int np3[3] = {c->lines.n[0] + 1, c->lines.n[1] + 1, c->dim == 3 ? c->lines.n[2] + 1 : 1};
   const bool fused = !multi && fdmo_scalar_usable(c->dim, np3) && !std::getenv("PORO_FDM_P_UNFUSED");
-  if (fused) fdmo_scalar_init(T.fused, np3, c->stream);
+  if (fused) {
+    fdmo_scalar_init(T.fused, np3, c->stream);
+    const char *strips = std::getenv("PORO_FDMO_SCALAR_STRIPS");     // (=0: every pass in the block-per-workgroup form; another number: that factor in place of kFdmoStripFill)
+    T.fused.strip_limit = (strips ? std::max(0.0, std::atof(strips)) : kFdmoStripFill) * c->n_cus;
+  }
   for (int d = 0; d < c->dim; ++d) {                                 // (partitioned: the local slab; the last direction is replaced by fdm_dist.last)
     const std::vector<double> &hcell = c->lines.hcell[d]; const bool lo = fixed && c->pdir_face[d][0], hi = fixed && c->pdir_face[d][1];
     upload_dir(T.nodal.dir[d], c->lines.uniform && !lo && !hi ? q1_eig((int)hcell.size(), hcell[0]) : line_tables(1, hcell, lo, hi), fused ? &T.fused : nullptr, d);   // (closed form on a uniform line with free ends)
@@ -150,6 +154,7 @@ void alltoall_blocks(poro_ctx *c, double *send, double *recv, int64_t blk, bool 
 }
 // z = (a M + sum_d k_d K_d)^-1 g for the Q1 space of the (global) box, from the table set `which`
 // Q1Set::fixed_ends (whole prescribed faces removed, one rank): z = J_ff^-1 g_f on the free rows, exactly 0 on the prescribed ones whatever g holds there
+void count_strip_launches(poro_ctx *c, int n) { if (n) c->timers["fdm_q1_strip_launches"].enqueued += n; }      // (a count, no time: launches of the scalar passes in the strip form)
 void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *g, double *z, Q1Set which) {
   Timed tm(c, "precondition_p_fdm");
   hipStream_t s = c->stream;
@@ -157,7 +162,7 @@ void fdm_precondition_p(poro_ctx *c, double a, const double k[3], const double *
   FdmQ1 &T = q1_set(c, which);
   if (fixed || !c->comm.multi()) {
     std::optional<Timed> tf; if (fixed) tf.emplace(c, "precondition_p_fdm_fixed_ends");
-    if (T.fused.built && isotropic) fdmo_scalar_apply(s, T.fused, a, k[0], g, z);
+    if (T.fused.built && isotropic) count_strip_launches(c, fdmo_scalar_apply(s, T.fused, a, k[0], g, z));
     else fdm_apply(s, T.nodal, a, k, g, z, c->fdm_t1.p, c->fdm_t2.p);
     return;
   }

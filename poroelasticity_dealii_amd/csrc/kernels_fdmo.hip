@@ -586,6 +586,105 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   }
 }
 
+// ---- the strip form of the scalar passes (one rank, the flags of the General variant without the slab extras) ------------------------------------------------------------
+// A scalar Q1 system has one block per z plane (passes 1 / 3) and a few dozen chunks (pass 2): k_fdmo_pass starts far fewer workgroups than the chip has CUs, and a launch
+// lasts as long as ONE workgroup needs for its two chained GEMMs.  Here a block is shared out over NT workgroups of NT waves, one tile per wave and GEMM:
+//   MODE 0 (Y = T2 (X T1^T)): workgroup (block, s) computes tile column s of the intermediate - which needs all of X - and from it tile column s of Y;
+//   MODE 2 (Y = (T1 X) T2^T): likewise tile row s of the intermediate and of Y;
+//   MODE 1 (independent lines): chunks of 16 columns (P.C = 16) instead of one tile column per wave, wave w owns tile row w.
+// Every workgroup of a block stages the whole block (L2 hits after the first); no tile is computed twice.  Bits: a tile's accumulator sees the k-steps of its two sums in
+// ascending order and skips the same trailing ones (kk1, kk2) as in k_fdmo_pass, and pass 2 scales with the same operations (`scale`), so the stored values are the same.
+// Passes 1 / 3 read blocks that other workgroups of the same launch read too: NOT in place (the scalar form runs g -> t, t -> t (pass 2, own columns only), t -> z).
+// No stopping test, no g . z, no stamps: the scalar passes are handed none.  A strip without valid outputs leaves at once (lines much shorter than the longest direction's)
+template <int NT, int MODE>
+__global__ void __launch_bounds__(64 * NT)
+k_fdmo_strip(OctPass P, const double *in, double *out) {
+  typedef PassGeom<NT> Gm;
+  constexpr bool kColsFirst = MODE == 0, kColsSecond = MODE == 2;
+  constexpr int LD1 = MODE == 1 ? 16 : (kColsFirst ? Gm::LDA : Gm::LDB), LD2 = MODE == 1 ? 16 : (kColsSecond ? Gm::LDA : Gm::LDB);   // (LD = 16: the B role's 16 (mod 32), PassGeom)
+  constexpr int PADC = MODE == 1 ? 16 : Gm::PADN, KKP = Gm::KKP;
+  extern __shared__ double L[];                              // PADN x LDMAX doubles (MODE 1: PADN x 16)
+  if (pcg_gate_closed(P.gate)) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, kq = lane >> 4;
+  const int item = MODE == 1 ? (int)blockIdx.x : (int)blockIdx.x / NT, s = MODE == 1 ? 0 : (int)blockIdx.x - item * NT;
+  const int co = item / P.nblk, b = item - co * P.nblk;      // co = right-hand side (no parity parts: no_shift = 0)
+  const int R = P.R, C = MODE == 1 ? min(P.C, P.pl - b * P.C) : P.C;
+  if ((MODE == 0 && 16 * s >= C) || (MODE == 2 && 16 * s >= R)) return;       // (workgroup-uniform, before any barrier)
+  const int64_t base = (int64_t)co * P.co_stride + (int64_t)b * P.blk_stride;
+  const int64_t base_in = P.use_in_off ? (int64_t)b * P.blk_stride : base, base_out = P.use_out_off ? (int64_t)b * P.blk_stride : base;
+  if (P.use_in_off) in = P.in_blk[co];
+  if (P.use_out_off) out = P.out_blk[co];
+  const int f1 = MODE == 1 ? w : s;                          // tile row of T1 this wave multiplies with (T2: always w)
+  const double *__restrict__ T1 = static_cast<const double *>(P.T1[co][0]) + (int64_t)f1 * KKP * 64 + lane, *__restrict__ T2 = static_cast<const double *>(P.T2[co][0]) + (int64_t)w * KKP * 64 + lane;
+  // all fragments of GEMM 1 and the block are requested at once, those of GEMM 2 behind the LDS stores: one memory latency in front of each GEMM at most
+  double t1[KKP], t2[KKP];
+#pragma unroll
+  for (int kk = 0; kk < KKP; ++kk) t1[kk] = T1[kk * 64];
+  {
+    constexpr int TOT = Gm::PADN * PADC, PER = TOT / (64 * NT);      // (16 NT x 16 NT or 16 NT x 16 entries: a multiple of the 64 NT threads)
+    static_assert(TOT % (64 * NT) == 0, "staging loop");
+    double stage[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NT, r = e / PADC, cc = e - r * PADC; stage[u] = (r < R && cc < C) ? in[base_in + (int64_t)r * P.row_stride + cc] : 0.0; }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NT, r = e / PADC, cc = e - r * PADC; L[r * LD1 + cc] = stage[u]; }
+  }
+#pragma unroll
+  for (int kk = 0; kk < KKP; ++kk) t2[kk] = T2[kk * 64];
+  __syncthreads();
+  v4d acc = v4d{0, 0, 0, 0};
+  {
+    const double *La = kColsFirst ? L + (16 * w + j) * LD1 + kq : L + kq * LD1 + (MODE == 1 ? 0 : 16 * w) + j;
+#pragma unroll
+    for (int kk = 0; kk < KKP; ++kk) {
+      if (kk < KKP - 3 || kk < P.kk1) {                      // (as in k_fdmo_pass: only whole trailing k-steps are skipped)
+        const double d = kColsFirst ? La[4 * kk] : La[4 * kk * LD1];
+        acc = kColsFirst ? __builtin_amdgcn_mfma_f64_16x16x4f64(d, t1[kk], acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(t1[kk], d, acc, 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();                                           // everybody has finished reading the input block
+  {
+    const int tr = MODE == 2 ? s : w, tc = MODE == 0 ? s : (MODE == 2 ? w : 0);
+    if constexpr (MODE == 1) {
+      const double *lamz = P.lam_z[co][0]; const double czc = P.cz[co];
+      const double bxy = P.bxy[min(b * P.C + j, P.pl - 1)];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        // (one fused multiply-add: what the compiler makes of `czc * lam + bxy` in every instantiation of k_fdmo_pass - the assembly of both is on record, profiles/q1_strips_isa.txt)
+        const double den = fma(czc, lamz[16 * w + 4 * q + kq], bxy);
+        double r = __builtin_amdgcn_rcp(den);
+        r = den < 1e300 ? fma(r, fma(-den, r, 1.0), r) : 0.0;
+        L[(16 * tr + 4 * q + kq) * LD2 + 16 * tc + j] = acc[q] * r;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) L[(16 * tr + 4 * q + kq) * LD2 + 16 * tc + j] = acc[q];
+    }
+  }
+  acc = v4d{0, 0, 0, 0};
+  __syncthreads();
+  {
+    const double *La = kColsSecond ? L + (16 * s + j) * LD2 + kq : L + kq * LD2 + 16 * s + j;      // (MODE 1: s = 0)
+#pragma unroll
+    for (int kk = 0; kk < KKP; ++kk) {
+      if (kk < KKP - 3 || kk < P.kk2) {
+        const double d = kColsSecond ? La[4 * kk] : La[4 * kk * LD2];
+        acc = kColsSecond ? __builtin_amdgcn_mfma_f64_16x16x4f64(d, t2[kk], acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(t2[kk], d, acc, 0, 0, 0);
+      }
+    }
+  }
+  {
+    const int tr = MODE == 2 ? s : w, tc = MODE == 0 ? s : (MODE == 2 ? w : 0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = 16 * tr + 4 * q + kq, cc = 16 * tc + j;
+      if (r < R && cc < C) out[base_out + (int64_t)r * P.row_stride + cc] = acc[q];
+    }
+  }
+}
+
 
 // ---- the transform pass with fp32 transforms (opt-in: poro_ctx_set_fdm_precision, PORO_FDM_FP32) ---------------------------------------------------------------------
 // The single-rank octant form only (VAR = 0 of k_fdmo_pass: 24 blocks, aligned rows, no exchange buffer), with the same workgroup shapes, tile ownership, fragment streams
@@ -1379,22 +1478,58 @@ void fdmo_scalar_upload_dir(FdmOct &O, int dir, const LineTables &T) {
 }
 static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kappa);
 // z = (a M + kappa K)^-1 g; the x / y share a + kappa (lam_x + lam_y) of the eigenvalue sums is tabulated per plane position, one table per (a, kappa)
-void fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate) {
+int fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const double *g, double *z, const PcgScalars *gate) {
   const double *gs[1] = {g}; double *zs[1] = {z};
-  fdmo_scalar_apply_many(s, O, a, kappa, 1, gs, zs, gate);
+  return fdmo_scalar_apply_many(s, O, a, kappa, 1, gs, zs, gate);
+}
+// the strip form of a scalar pass (k_fdmo_strip): NT workgroups of NT waves per block (passes 1 / 3), 16-column chunks (pass 2)
+template <int NT, int MODE> void launch_strip_one(hipStream_t s, int n_wg, const OctPass &P, const double *in, double *out) {
+  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * (MODE == 1 ? 16 : PassGeom<NT>::LDMAX) * sizeof(double));
+  if (lds > 64 * 1024) {
+    static std::mutex mu; static std::set<int> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done.count(dev)) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdmo_strip<NT, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert(dev); }
+  }
+  hipLaunchKernelGGL((k_fdmo_strip<NT, MODE>), dim3((unsigned)n_wg), dim3(64 * NT), lds, s, P, in, out);
+}
+template <int NT> void launch_strip(hipStream_t s, const OctPass &P, int n_items, const double *in, double *out) {
+  if (P.mode == 0) launch_strip_one<NT, 0>(s, n_items * NT, P, in, out);
+  else if (P.mode == 2) launch_strip_one<NT, 2>(s, n_items * NT, P, in, out);
+  else launch_strip_one<NT, 1>(s, n_items, P, in, out);
+}
+void launch_strip_nt(hipStream_t s, int nt, const OctPass &P, int n_items, const double *in, double *out) {
+  if (variant_of_flags(P) != PassVariant::General || P.slab_z || P.slab_io || P.row_in || P.no_shift || P.bxy_cmul || P.stop.gg_part || P.gz_part || P.stamps) throw Error("fdmo: the strip form serves the scalar passes of one rank only");
+  switch (nt) {
+    case 2: launch_strip<2>(s, P, n_items, in, out); break;
+    case 3: launch_strip<3>(s, P, n_items, in, out); break;
+    case 4: launch_strip<4>(s, P, n_items, in, out); break;
+    case 5: launch_strip<5>(s, P, n_items, in, out); break;
+    case 6: launch_strip<6>(s, P, n_items, in, out); break;
+    case 7: launch_strip<7>(s, P, n_items, in, out); break;
+    case 8: launch_strip<8>(s, P, n_items, in, out); break;
+    default: throw Error("fdmo: lines of more than 128 entries");
+  }
 }
 // the same for up to three right-hand sides in separate vectors: one set of three launches with 3 x the workgroups (the Q1 systems of config 4 fill less than a third of the chip)
-void fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate) {
+// Strip form (k_fdmo_strip): a pass takes it when its block-per-workgroup launch would start fewer workgroups than O.strip_limit (kFdmoStripFill x the CUs of the device;
+// 0 = the form is off).  Lines of one tile (nt = 1) have nothing to share out.  Returns the number of strip launches (the count-only timer family "fdm_q1_strip_launches")
+int fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate) {
   if (nb < 1 || nb > 3) throw Error("fdmo_scalar_apply_many: 1..3 right-hand sides");
   const Form F = scalar_form(O, nb, kappa, scalar_table(s, O, a, kappa));
   const double *const in[3] = {g[0], O.t.p, O.t.p}; double *const out[3] = {O.t.p, O.t.p, z[0]};
+  int strips = 0;
   for (int k = 0; k < 3; ++k) {
     OctPass P = plan_pass(F, k + 1);
     P.gate = gate;
     for (int c = 0; c < nb; ++c) { P.in_blk[c] = g[c]; P.out_blk[c] = z[c]; }
     P.use_in_off = k == 0; P.use_out_off = k == 2;           // pass 1 reads, pass 3 writes every right-hand side's own vector; in between they sit side by side in O.t
-    launch_pass_nt(s, O.nt, PassVariant::General, P, nb * P.nblk, in[k], out[k]);
+    const bool strip = O.nt >= 2 && !O.slab.on && (double)nb * P.nblk < O.strip_limit && g[0] != O.t.p && z[0] != O.t.p;
+    if (!strip) { launch_pass_nt(s, O.nt, PassVariant::General, P, nb * P.nblk, in[k], out[k]); continue; }
+    if (k == 1) { P.C = 16; P.blk_stride = 16; P.nblk = (P.pl + 15) / 16; }       // pass 2: 16-column chunks, the last one partial
+    launch_strip_nt(s, O.nt, P, nb * P.nblk, in[k], out[k]);
+    ++strips;
   }
+  return strips;
 }
 
 static const double *scalar_table(hipStream_t s, FdmOct &O, double a, double kappa) {

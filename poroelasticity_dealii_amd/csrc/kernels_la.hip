@@ -51,6 +51,21 @@ __global__ void k_reduce_finish(const double *partials, int n_sets, double *red,
     if (threadIdx.x == 0) red[k] = v;
   }
 }
+// k_reduce_finish (= k_scalars_sum where max_mask = 0: the same additions in the same order) and k_post behind it in one launch: one block sums the sets, writes them to
+// red AND to the mailbox, then publishes the sequence number.  One rank only - a partitioned run has an all-reduce between the two
+__global__ void k_reduce_post(const double *partials, int n_sets, double *red, int max_mask, Mailbox *mb, unsigned long long seq) {
+  __shared__ double sh[4];
+  for (int k = 0; k < n_sets; ++k) {
+    const bool is_max = (max_mask >> k) & 1;
+    double v = 0;
+    for (int i = threadIdx.x; i < kMaxPartials; i += kBlock) { const double t = partials[k * kMaxPartials + i]; v = is_max ? fmax(v, t) : v + t; }
+    v = is_max ? block_max(v, sh) : block_sum(v, sh);
+    if (threadIdx.x == 0) { red[k] = v; mb->vals[k] = v; }
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(const_cast<unsigned long long *>(&mb->seq), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 template <int L> __global__ void k_spmv(int64_t n, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
                                         const double *__restrict__ x, double *__restrict__ y) {
@@ -466,6 +481,9 @@ void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const
   else hipLaunchKernelGGL(k_residual_norms_many<false>, reduce_grid(n), kBlock, 0, s, V, nb, n, partials, mask);
 }
 void la_post(hipStream_t s, Mailbox *mb, unsigned long long seq, const double *src, int n, const PcgScalars *sc) { hipLaunchKernelGGL(k_post, 1, 64, 0, s, mb, seq, src, n, sc); }
+void la_reduce_post(hipStream_t s, const double *partials, int n_sets, double *red, int max_mask, Mailbox *mb, unsigned long long seq) {
+  hipLaunchKernelGGL(k_reduce_post, 1, kBlock, 0, s, partials, n_sets, red, max_mask, mb, seq);
+}
 void la_fill(hipStream_t s, double *x, double v, int64_t n) { if (n) hipLaunchKernelGGL(k_fill, grid_for(n), kBlock, 0, s, x, v, n); }
 // device-to-device copy as a kernel: hipMemcpyAsync costs the host ~50 us per call (measured between the back-to-back copies of poro_state_restore), a launch ~5 us
 __global__ void k_copy(double *__restrict__ y, const double *__restrict__ x, int64_t n) {
