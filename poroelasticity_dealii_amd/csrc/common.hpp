@@ -153,6 +153,10 @@ struct FdmOct {
     DevBuf<int64_t> row_out; DevBuf<int32_t> row_kz;   // [rows_back]: offset (in buf) of a row of the scattering all-to-all, global plane of that row
     DevBuf<double> buf, tz;                       // all-to-all buffers; transposed array [chunk][pz][hzg][cw]
   } slab;
+  // class-split passes (single-rank octant form, fp64; fdmo_upload_dir_classes): every (component, direction) line passed class_split_tables.  Per [component][direction][parity]:
+  // the two class transforms [class: vertex, midpoint] in fragment order, the mixes [64 slots][4], the eigenvalues by slot [class][64]; bxy_vm = bxy in the class-major mode order
+  bool class_split = false;
+  DevBuf<double> cfwd[3][3][2][2], cbwd[3][3][2][2], cmix[3][3][2], clam[3][3][2], bxy_vm; std::vector<double> h_clam[3][3][2];
   std::shared_ptr<FdmoPlans> plans;              // displacement forms: the launch descriptors of the three passes, planned once by fdmo_finalize (kernels_fdmo.hip)
   struct ScalarTable { double a, kappa; DevBuf<double> t; };
   std::list<ScalarTable> scalar_tables;           // scalar form: a + kappa (lam_x + lam_y) per plane position, one table per (a, kappa) seen (pressure Jacobian, mass matrix)
@@ -529,6 +533,8 @@ void fdmo_init(FdmOct &O, const int nn[3], const double coef[3][3], hipStream_t 
 void fdmo_init_slab(FdmOct &O, const int nn[3], const double coef[3][3], int rank, const std::vector<int> &node_layers, bool has_upper, hipStream_t s);
 void fdmo_init_per_direction(FdmOct &O, const int nn[3], const double coef[3][3], const FdmFormDecision &D, hipStream_t s);   // per-direction form: sizes + buffers from the decision of fdm_form_decide
 void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T);   // T.parity required (per-direction form: by its split directions only)
+void fdmo_upload_dir_classes(FdmOct &O, int comp, int dir, const ClassSplitTables &T);   // octant form on one rank with O.class_split set (before the first upload): the class-split tables of the line, next to fdmo_upload_dir's
+bool fdmo_class_split_runs(const FdmOct &O, int precision);   // whether fdmo_apply takes the class-split passes (k_fdmo_pass_vm) at this precision
 void fdmo_finalize(FdmOct &O);   // after every (component, direction) has been uploaded: derived tables
 void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_oct, double *scratch_oct, const PcgScalars *gate = nullptr, hipEvent_t *ev /* optional: 3 start / stop pairs attached to the three pass dispatches */ = nullptr,
                 double *gz_part /* optional: O.gz_part - pass 2 also leaves the O.gz_n partial sums of g . z there */ = nullptr,

@@ -323,7 +323,7 @@ void build_fdm_u(poro_ctx *c) {
   }
   // eigenpairs per (direction, end conditions); components with the same end conditions share the host work.  same_ends[d]: every component has the same condition at
   // both ends of direction d; parity[d]: every component's eigenvectors came out even or odd there (they do on a uniform line with the same ends, not on a graded one)
-  LineTables tables[3][4]; bool same_ends[3], parity[3], parity_cd[3][3] = {};
+  LineTables tables[3][4]; ClassSplitTables classes[3][4]; bool same_ends[3], parity[3], parity_cd[3][3] = {};
   const auto key_of = [&](int comp, int d) { return F.fix[comp][d][0] * 2 + F.fix[comp][d][1]; };
   for (int d = 0; d < dim; ++d) {
     if (line && d == last) { same_ends[d] = parity[d] = false; continue; }      // (no eigenpairs along the line direction)
@@ -356,7 +356,19 @@ void build_fdm_u(poro_ctx *c) {
     }
     if (per_dir) { fdmo_init_per_direction(c->fdm_oct, nn3, F.coef, form, c->stream); oct_ok = true; }
     else if (oct_ok && planar) fdmo_init_planar(c->fdm_oct, nn3, F.coef, c->stream, symmetric);
-    else if (oct_ok && !multi) fdmo_init(c->fdm_oct, nn3, F.coef, c->stream);
+    else if (oct_ok && !multi) {
+      fdmo_init(c->fdm_oct, nn3, F.coef, c->stream);
+      // class-split passes: Q2 lines on which the vertex / midpoint classes decouple frequency by frequency - all nine (component, direction) lines must pass the numerical
+      // check of class_split_tables; PORO_FDMO_CLASS_SPLIT=0 (read here, once per build) keeps the dense passes
+      const char *hook = std::getenv("PORO_FDMO_CLASS_SPLIT");
+      bool all = !(hook && std::atoi(hook) == 0);
+      for (int d = 0; d < dim && all; ++d) for (int comp = 0; comp < dim && all; ++comp) {
+        ClassSplitTables &CS = classes[d][key_of(comp, d)];
+        if (!CS.n) CS = class_split_tables(ku, c->lines.hcell[d], F.fix[comp][d][0] != 0, F.fix[comp][d][1] != 0, tables[d][key_of(comp, d)]);
+        all = all && CS.ok;
+      }
+      c->fdm_oct.class_split = all;
+    }
     if (oct_ok && multi) { std::vector<int> node_layers(F.n_ranks); for (int q = 0; q < F.n_ranks; ++q) node_layers[q] = ku * F.layers[q];
                            fdmo_init_slab(c->fdm_oct, nn3, F.coef, F.rank, node_layers, c->comm.part.has_upper != 0, c->stream); } }
   // A direction takes the even / odd form of the nodal kernels (half the MFMA work) when it has the same ends and the parity for every component - all components
@@ -368,6 +380,7 @@ void build_fdm_u(poro_ctx *c) {
     FdmuDir &D = global_dir ? F.last_global[comp] : F.dir[comp][d];
     if (!(planar && oct_ok && T.n > 320 && !same_ends[d])) fdmu_upload_dir(D, T, global_dir ? false : F.single, same_ends[d] && parity[d]);   // (the nodal kernels have no full-length form beyond 320 points; the planar form does not need them)
     if (oct_ok) { if (planar) fdmo_upload_dir_planar(c->fdm_oct, comp, d, T); else fdmo_upload_dir(c->fdm_oct, comp, d, T); }
+    if (oct_ok && c->fdm_oct.class_split) fdmo_upload_dir_classes(c->fdm_oct, comp, d, classes[d][key_of(comp, d)]);
   }
   c->fdmu_t1.alloc(c->n_u); c->fdmu_t2.alloc(c->n_u); c->fdmu_t1.zero(c->stream); c->fdmu_t2.zero(c->stream);   // (only finite values ever live in the scratch arrays)
   if (!c->wz_u.p) { c->wz_u.alloc(c->n_u); c->wz_u.zero(c->stream); }
@@ -421,6 +434,7 @@ bool fdm_precondition_u_form(poro_ctx *c, const double *g, double *z, const PcgS
   if (O.slab.on) { if (stop.gg_part) throw Error("fdm_precondition_u_form: the slab form runs no stopping test"); fdm_precondition_u_slab(c, g, z, gate); return false; }
   if (O.planar) { fdmo_apply_planar(c->stream, O, g, z, gate, stop); return false; }
   const char *names[3] = {"fdm_u_pass1", "fdm_u_pass2", "fdm_u_pass3"};
+  if (fdmo_class_split_runs(O, precision)) c->timers["fdm_u_class_split"].enqueued++;      // (a count, no time: applications that took the class-split passes)
   if (!begin_sampled_dispatch(c, names[0])) {
     fdmo_apply(c->stream, O, g, z, scratch, gate, nullptr, gz_part, precision, stop);
     return gz_part != nullptr;

@@ -271,6 +271,131 @@ inline std::vector<double> whole_line_fragments(const LineTables &T, int tiles, 
                   : pack_fragments<double>(tiles, 4 * tiles, n, n, [&](int r, int c) { return S[(size_t)c * n + r]; });
 }
 
+// ---- class-split form of a uniform Q2 line with equal ends ----
+// On such a line the vertex nodes and the midpoint nodes each carry pure trigonometric vectors (free ends: cos(m pi i / (nn - 1)), removed ends: the sines): with
+// a_m = that function on the vertices (zero on the midpoints) and b_m = the same on the midpoints, K and M couple a_m and b_m only with each other.  The M-orthonormal
+// eigenvectors are therefore F = S W, S = blockdiag(S_v, S_m) after sorting the nodes by class and W one 2 x 2 generalised eigenvector matrix per frequency (1 x 1 where a
+// class vanishes): a half-line transform becomes two class transforms of half the length plus two FMAs per entry.
+// Per parity group (0: even modes, 1: odd): lower-half node 2 p is position p of the vertex class, node 2 p + 1 position p of the midpoint class (the centre node goes by
+// its index); the frequencies of the group, ascending, are the slots 0, 1, ... of BOTH classes, and the two modes of a frequency take its slot in each class.
+struct ClassSplitGroup {
+  int nv = 0, nm = 0;                 // positions per class: (h + 1) / 2 and h / 2 of the h = (nn + 1) / 2 lower-half nodes
+  int slots = 0;                      // frequencies of the group
+  std::vector<double> Fv, Fm;         // class transforms [slot][position] (zero rows where the class has no vector at that frequency)
+  std::vector<double> mix;            // [slot][4] = w_vv, w_mv, w_vm, w_mm: mode (v, s) = w_vv (Fv g_v)[s] + w_mv (Fm g_m)[s], mode (m, s) = w_vm (Fv g_v)[s] + w_mm (Fm g_m)[s]
+  std::vector<double> lam_v, lam_m;   // [slot]: eigenvalues of the two modes (inf: no such mode)
+};
+struct ClassSplitTables {
+  bool ok = false; const char *why = ""; int n = 0; ClassSplitGroup grp[2];
+  double off_block = 0, orth = 0, resid = 0, eig_dev = 0;      // what the verification measured (relative figures)
+};
+// The verdict comes from the numbers: the trigonometric vectors are built from the node INDEX, the pencils from the line's own fe1d matrices, and the result is accepted only
+// if (1) the off-block entries of S^T K S and S^T M S are <= 1e-12 of the largest entry, (2) F^T M F = I and F^T K F = Lambda to 1e-12 (the latter relative to the largest
+// eigenvalue) and (3) the sorted eigenvalues equal those of T = line_tables(...) to 1e-12 of the largest.  A graded line fails (1); lines without classes (Q1), without
+// parity (different ends) or of another length than T are turned down before.
+inline ClassSplitTables class_split_tables(int k, const std::vector<double> &hc, bool fix_lo, bool fix_hi, const LineTables &T) {
+  ClassSplitTables R; const int N = (int)hc.size(), nn = 2 * N + 1, h = (nn + 1) / 2; R.n = nn;
+  if (k != 2) { R.why = "no midpoint class (not Q2)"; return R; }
+  if (T.n != nn || !T.parity || fix_lo != fix_hi) { R.why = "modes without parity"; return R; }
+  const bool fix = fix_lo; const double pi = 3.14159265358979323846, kTol = 1e-12;
+  std::vector<double> M, K; fe1d(2, hc, M, K);
+  auto band = [&](const std::vector<double> &A, const std::vector<double> &x, std::vector<double> &y) {
+    y.assign(nn, 0.0);
+    for (int i = 0; i < nn; ++i) for (int p = std::max(0, i - 2); p <= std::min(nn - 1, i + 2); ++p) y[i] += A[(size_t)i * nn + p] * x[p];
+  };
+  auto dot = [&](const std::vector<double> &x, const std::vector<double> &y) { double s = 0; for (int i = 0; i < nn; ++i) s += x[i] * y[i]; return s; };
+  // class vectors of every frequency; a vector that vanishes (cosines on the midpoints at m = N, sines on the vertices at m = N) is absent
+  struct Vec { int m, cls; std::vector<double> v, Mv, Kv; };
+  std::vector<Vec> vecs; std::vector<int> at_v(N + 1, -1), at_m(N + 1, -1);
+  for (int m = fix ? 1 : 0; m <= N; ++m) for (int cls = 0; cls < 2; ++cls) {
+    Vec V; V.m = m; V.cls = cls; V.v.assign(nn, 0.0); double big = 0;
+    for (int i = cls; i < nn; i += 2) { V.v[i] = (fix && (i == 0 || i == nn - 1)) ? 0.0 : fix ? std::sin(m * pi * i / (2.0 * N)) : std::cos(m * pi * i / (2.0 * N)); big = std::max(big, std::fabs(V.v[i])); }
+    if (big < 1e-9) continue;
+    band(M, V.v, V.Mv); band(K, V.v, V.Kv);
+    (cls ? at_m : at_v)[m] = (int)vecs.size(); vecs.push_back(std::move(V));
+  }
+  const int nvec = (int)vecs.size();
+  // (1) S^T K S and S^T M S: nothing outside the 2 x 2 blocks
+  { double big = 0, off = 0;
+    for (int w = 0; w < 2; ++w) {
+      double bw = 0, ow = 0;
+      for (int a = 0; a < nvec; ++a) for (int b = 0; b < nvec; ++b) {
+        const double e = std::fabs(dot(vecs[a].v, w ? vecs[b].Mv : vecs[b].Kv));
+        bw = std::max(bw, e); if (vecs[a].m != vecs[b].m) ow = std::max(ow, e);
+      }
+      big = std::max(big, bw); if (bw > 0) off = std::max(off, ow / bw);
+    }
+    R.off_block = off;
+    if (!(big > 0) || !(off <= kTol)) { R.why = "vertex / midpoint classes couple across frequencies"; return R; } }
+  // the pencils, frequency by frequency; full-line eigenvectors for the checks below
+  for (int p = 0; p < 2; ++p) { R.grp[p].nv = (h + 1) / 2; R.grp[p].nm = h / 2; }
+  std::vector<std::vector<double>> Fcol; std::vector<double> Flam; const double inf = std::numeric_limits<double>::infinity();
+  for (int m = fix ? 1 : 0; m <= N; ++m) {
+    const int ia = at_v[m], ib = at_m[m];
+    if (ia < 0 && ib < 0) continue;
+    const std::vector<double> &ref = vecs[ia >= 0 ? ia : ib].v;
+    double ds = 0, da = 0;
+    for (int i = 0; i < nn; ++i) { const double a = ref[i], b = ref[nn - 1 - i]; ds += (a - b) * (a - b); da += (a + b) * (a + b); }
+    if (std::min(ds, da) > 1e-20 * std::max(ds, da)) { R.why = "a class vector is neither even nor odd"; return R; }
+    ClassSplitGroup &G = R.grp[ds <= da ? 0 : 1]; const int s = G.slots++;
+    G.Fv.resize((size_t)G.slots * G.nv, 0.0); G.Fm.resize((size_t)G.slots * G.nm, 0.0); G.mix.resize((size_t)G.slots * 4, 0.0); G.lam_v.resize(G.slots, inf); G.lam_m.resize(G.slots, inf);
+    if (ia >= 0) for (int q = 0; q < G.nv; ++q) G.Fv[(size_t)s * G.nv + q] = vecs[ia].v[2 * q];
+    if (ib >= 0) for (int q = 0; q < G.nm; ++q) G.Fm[(size_t)s * G.nm + q] = vecs[ib].v[2 * q + 1];
+    double *w = &G.mix[(size_t)s * 4];
+    if (ia >= 0 && ib >= 0) {
+      const double maa = dot(vecs[ia].v, vecs[ia].Mv), mab = dot(vecs[ia].v, vecs[ib].Mv), mbb = dot(vecs[ib].v, vecs[ib].Mv);
+      const double kr[2][2] = {{dot(vecs[ia].v, vecs[ia].Kv), dot(vecs[ia].v, vecs[ib].Kv)}, {dot(vecs[ib].v, vecs[ia].Kv), dot(vecs[ib].v, vecs[ib].Kv)}};
+      if (!(maa > 0)) { R.why = "class mass block not positive definite"; return R; }
+      const double l11 = std::sqrt(maa), l21 = mab / l11, d2 = mbb - l21 * l21;
+      if (!(d2 > 0)) { R.why = "class mass block not positive definite"; return R; }
+      const double l22 = std::sqrt(d2);
+      // C = L^-1 Kr L^-T, C = Q diag(lam) Q^T, W = L^-T Q
+      double X[2][2], Z[2][2];
+      for (int j = 0; j < 2; ++j) { X[0][j] = kr[0][j] / l11; X[1][j] = (kr[1][j] - l21 * X[0][j]) / l22; }
+      for (int j = 0; j < 2; ++j) { Z[0][j] = X[j][0] / l11; Z[1][j] = (X[j][1] - l21 * Z[0][j]) / l22; }      // Z = L^-1 X^T = C^T
+      std::vector<double> C = {Z[0][0], 0.5 * (Z[0][1] + Z[1][0]), 0.5 * (Z[0][1] + Z[1][0]), Z[1][1]}, Q, lam;
+      jacobi_eig(2, C, Q, lam);
+      const int jv = lam[0] <= lam[1] ? 0 : 1, jm = 1 - jv;           // the lower mode of the pair takes the vertex slot
+      const int js[2] = {jv, jm};
+      for (int e = 0; e < 2; ++e) { const double q0 = Q[js[e]], q1 = Q[2 + js[e]], w1 = q1 / l22, w0 = (q0 - l21 * w1) / l11; w[2 * e] = w0; w[2 * e + 1] = w1; }
+      G.lam_v[s] = std::max(lam[jv], 0.0); G.lam_m[s] = std::max(lam[jm], 0.0);
+    } else if (ia >= 0) { const double maa = dot(vecs[ia].v, vecs[ia].Mv); w[0] = 1.0 / std::sqrt(maa); G.lam_v[s] = std::max(dot(vecs[ia].v, vecs[ia].Kv) / maa, 0.0); }
+    else { const double mbb = dot(vecs[ib].v, vecs[ib].Mv); w[3] = 1.0 / std::sqrt(mbb); G.lam_m[s] = std::max(dot(vecs[ib].v, vecs[ib].Kv) / mbb, 0.0); }
+    for (int e = 0; e < 2; ++e) {
+      const double lam_e = e ? G.lam_m[s] : G.lam_v[s];
+      if (!(lam_e < 1e300)) continue;
+      std::vector<double> f(nn, 0.0);
+      for (int i = 0; i < nn; ++i) f[i] = (ia >= 0 ? w[2 * e] * vecs[ia].v[i] : 0.0) + (ib >= 0 ? w[2 * e + 1] * vecs[ib].v[i] : 0.0);
+      Fcol.push_back(std::move(f)); Flam.push_back(lam_e);
+    }
+  }
+  // (2) F^T M F = I, F^T K F = Lambda; (3) the spectrum of line_tables
+  const int nmode = (int)Fcol.size(); double lam_max = 0; for (double v : Flam) lam_max = std::max(lam_max, v);
+  int nfree = 0; std::vector<double> ref; for (int j = 0; j < nn; ++j) if (T.lam[j] < 1e300) { ++nfree; ref.push_back(T.lam[j]); lam_max = std::max(lam_max, T.lam[j]); }
+  if (nmode != nfree || !(lam_max > 0)) { R.why = "mode count differs from the line's"; return R; }
+  { std::vector<double> Mf, Kf;
+    for (int b = 0; b < nmode; ++b) {
+      band(M, Fcol[b], Mf); band(K, Fcol[b], Kf);
+      for (int a = 0; a < nmode; ++a) {
+        R.orth = std::max(R.orth, std::fabs(dot(Fcol[a], Mf) - (a == b ? 1.0 : 0.0)));
+        R.resid = std::max(R.resid, std::fabs(dot(Fcol[a], Kf) - (a == b ? Flam[a] : 0.0)) / lam_max);
+      }
+    }
+    if (!(R.orth <= kTol) || !(R.resid <= kTol)) { R.why = "class-split eigenvectors do not diagonalise the pencil"; return R; } }
+  { std::vector<double> mine = Flam; std::sort(mine.begin(), mine.end()); std::sort(ref.begin(), ref.end());
+    for (int j = 0; j < nmode; ++j) R.eig_dev = std::max(R.eig_dev, std::fabs(mine[j] - ref[j]) / lam_max);
+    if (!(R.eig_dev <= kTol)) { R.why = "eigenvalues differ from the line's"; return R; } }
+  for (int p = 0; p < 2; ++p) if (R.grp[p].slots > std::max(R.grp[p].nv, R.grp[p].nm)) { R.why = "more frequencies than class positions"; return R; }
+  R.ok = true; return R;
+}
+// a class transform in fragment order for the class-split pass kernels: `tiles` 16-wide tiles of output rows, `ksteps` k-steps of 4.  Forward [slot][position], backward
+// [position][slot] from the SAME entries: the backward matrix is the exact transpose of the forward one
+inline std::vector<double> class_fragments(const ClassSplitGroup &G, int cls, int tiles, int ksteps, bool backward) {
+  const std::vector<double> &F = cls ? G.Fm : G.Fv; const int np = cls ? G.nm : G.nv, ns = G.slots;
+  return backward ? pack_fragments<double>(tiles, ksteps, np, ns, [&](int r, int c) { return F[(size_t)c * np + r]; })
+                  : pack_fragments<double>(tiles, ksteps, ns, np, [&](int r, int c) { return F[(size_t)r * np + c]; });
+}
+
 // ---- which form the single-rank 3D block FDM of the displacement system can take (PORO_FDM_FORM_PER_DIRECTION) ----
 constexpr int kFdmoMaxTiles = 8;       // 16-wide tiles per transformed line the pass kernel of kernels_fdmo.hip is instantiated for: lines of <= 128 entries
 // Direction d is SPLIT in parity halves (butterfly in the CG vector kernels, half-size transforms) iff every component has the same end condition at both of its ends and every

@@ -586,6 +586,287 @@ k_fdmo_pass(OctPass P, const double *in, double *out) {
   }
 }
 
+// ---- the class-split passes of the octant form (one rank, fp64; uniform Q2 lines with equal ends: class_split_tables, fdm_tables.hpp) --------------------------------
+// Every half-line transform F = S W: two class transforms (vertex / midpoint positions, half the length each) and a 2 x 2 mix per frequency.  The three passes become
+//   pass 1: read g (nodal half-line order), x forward, mix, y forward, mix      -> class-major modes in x and y
+//   pass 2: z forward, mix, scale, transposed mix, z backward                   (in place; z stays nodal at the interfaces)
+//   pass 3: transposed mixes, y backward, x backward                            -> z in nodal half-line order
+// so g and z keep their layout for the CG vector kernels; the order between the passes is private: slot s of the vertex class at index s, of the midpoint class at
+// nv + s - compact, the same hy x hxp planes.  In LDS a line of 16 NT entries is two class regions of H = 8 NT: position / slot p of the vertex class at p, of the
+// midpoint class at H + p (node 2 p / 2 p + 1 of the nodal order).  A class GEMM contracts over its own region only: (nv + 3) / 4 and (nm + 3) / 4 k-steps instead of 4 NT.
+// A wave always holds tile t of BOTH classes (for some batch tiles): the two partners of a frequency sit in the same lane and accumulator slot of accv / accm, so every
+// forward mix is two FMAs per entry in registers.  The transposed mixes of pass 3 act on its input: they ride in its staging loop.
+// Kept from k_fdmo_pass<.., 0>: in-place operation (the block is staged in full before the first store, blocks are disjoint), the gate, the stopping test of pass 1
+// (pcg_stop_load / pcg_stop_decide: the bits of every other form of the test), g . z out of pass 2 as the sum of ghat^2 / den in a fixed order with one slot per workgroup
+// of the same grid, exact zeros from removed modes (1 / den = 0, zero mix) and pads (zero rows of the class transforms), no scratch.
+struct OctPassVM {
+  int mode, R, C, nblk, pl;           // as in OctPass
+  int64_t co_stride, blk_stride, row_stride;
+  int bit1, bit2;                     // octant bit that selects the parity of the tables of GEMM 1 / 2
+  int kkv[2], kkm[2];                 // k-steps of the vertex / midpoint class in GEMM 1 / 2
+  int nvx, nvy, nmy;                  // passes 1 / 3: vertex positions of an x line (= index of the first midpoint slot in the compact order), vertex / midpoint positions of a y line
+  const double *Tv[2][3][2], *Tm[2][3][2];     // [GEMM][component][parity]: class transforms in fragment order [(NT + 1) / 2 tiles][2 NT k-steps][64]
+  const double *mix[2][3][2];         // [GEMM][component][parity]: [slot][4] of the direction of that GEMM
+  const double *lam_z[3][2];          // pass 2: [class][64] eigenvalues by slot
+  double cz[3]; const double *bxy;    // bxy in the compact class-major order of the plane
+  double *gz_part; const PcgScalars *gate; PcgStopTest stop;
+};
+template <int NT> constexpr int vm_waves() { return NT == 5 ? 4 : (NT + 1) / 2; }      // one per class-tile pair; NT = 5: four, one per SIMD (see the roles in the kernel)
+// registers: three workgroups per CU fit the LDS up to NT = 5 (PassGeom), so their waves must fit three to a SIMD - 168 registers; beyond, the accumulators alone need more
+template <int NT> constexpr int vm_waves_per_simd() { return NT <= 5 ? 3 : NT == 6 ? 2 : 1; }
+template <int NT, int MODE, bool GZ = false>
+__global__ void __launch_bounds__(64 * vm_waves<NT>()) __attribute__((amdgpu_waves_per_eu(vm_waves_per_simd<NT>())))
+k_fdmo_pass_vm(OctPassVM P, const double *in, double *out) {
+  static_assert(!GZ || MODE == 1, "g . z comes out of pass 2");
+  typedef PassGeom<NT> Gm;
+  constexpr bool QUAD = NT == 5;
+  constexpr int NW = vm_waves<NT>(), NCT = (NT + 1) / 2, H = 8 * NT, KK = 2 * NT, PADN = Gm::PADN;
+  constexpr int NB = MODE == 1 ? (NT == 5 ? 4 : NT) : NT;      // batch tiles (pass 2: the columns of a chunk, pass2_chunk)
+  constexpr bool kColsFirst = MODE == 0, kColsSecond = MODE == 2;
+  constexpr int LD1 = kColsFirst ? Gm::LDA : Gm::LDB, LD2 = kColsSecond ? Gm::LDA : Gm::LDB;
+  extern __shared__ double L[];                              // PADN x LDMAX doubles
+  __shared__ double gz_wave[GZ ? NW : 1];
+  if (MODE == 0 && P.stop.gg_part) {
+    PcgStopInputs stop_in;
+    pcg_stop_load(P.stop, stop_in);
+    if (P.gate && (P.gate->done | P.gate->finishing)) return;
+    if (pcg_stop_decide(P.stop, stop_in)) return;
+  } else if (pcg_gate_closed(P.gate)) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, kq = lane >> 4;
+  const int co = blockIdx.x / P.nblk, b = blockIdx.x % P.nblk, c = co >> 3, o = co & 7;
+  const int64_t base = (int64_t)co * P.co_stride + (int64_t)b * P.blk_stride;
+  const int R = P.R, C = MODE == 1 ? min(P.C, P.pl - b * P.C) : P.C;
+  const int p1 = (o >> P.bit1) & 1, p2 = (o >> P.bit2) & 1;
+  auto node_of = [](int r) { return r < H ? 2 * r : 2 * (r - H) + 1; };      // LDS line index -> nodal index
+  // ---- block -> LDS, every entry of the padded block written once (the pads meet zero columns of the class transforms, but must be finite) ----
+  if constexpr (MODE == 0) {            // nodal rows and columns -> class regions: a 16-byte load is one (vertex, midpoint) pair of a row
+    constexpr int TOT = PADN * H, PER = (TOT + 64 * NW - 1) / (64 * NW);
+    double2 stage[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + u * 64 * NW, r = e / H, cp = e - r * H, rn = node_of(r);
+      stage[u] = (e < TOT && rn < R && 2 * cp < C) ? *reinterpret_cast<const double2 *>(in + base + (int64_t)rn * P.row_stride + 2 * cp) : double2{0.0, 0.0};
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NW, r = e / H, cp = e - r * H; if (e < TOT) { L[r * LD1 + cp] = stage[u].x; L[r * LD1 + H + cp] = stage[u].y; } }
+  } else if constexpr (MODE == 1) {     // nodal rows -> class regions, the columns of the chunk as they are
+    constexpr int HP = 8 * NB, TOT = PADN * HP, PER = (TOT + 64 * NW - 1) / (64 * NW);
+    double2 stage[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP), rn = node_of(r);
+      stage[u] = (e < TOT && rn < R && c2 < C) ? *reinterpret_cast<const double2 *>(in + base + (int64_t)rn * P.row_stride + c2) : double2{0.0, 0.0};
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int e = tid + u * 64 * NW, r = e / HP, c2 = 2 * (e - r * HP); if (e < TOT) *reinterpret_cast<double2 *>(&L[r * LD1 + c2]) = stage[u]; }
+  } else {                              // compact class-major modes -> class regions, with the transposed mixes of y and x: a thread takes the four partners of (y slot, x slot)
+    constexpr int TOT = H * H, PER = (TOT + 64 * NW - 1) / (64 * NW);
+    const int nvx = P.nvx, nmx = C - P.nvx, nvy = P.nvy, nmy = P.nmy;     // (C = the row pitch: the pad entry counts as a midpoint slot - it holds a zero)
+    const double *__restrict__ my = P.mix[0][c][p1], *__restrict__ mx = P.mix[1][c][p2];
+    double stage[PER][4];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + u * 64 * NW, sy = e / H, sx = e - sy * H;
+      const bool ok = e < TOT, rv = ok && sy < nvy, rm = ok && sy < nmy, cv = sx < nvx, cm = sx < nmx;
+      const double *src = in + base + sx;
+      stage[u][0] = (rv && cv) ? src[(int64_t)sy * P.row_stride] : 0.0;
+      stage[u][1] = (rv && cm) ? src[(int64_t)sy * P.row_stride + nvx] : 0.0;
+      stage[u][2] = (rm && cv) ? src[(int64_t)(nvy + sy) * P.row_stride] : 0.0;
+      stage[u][3] = (rm && cm) ? src[(int64_t)(nvy + sy) * P.row_stride + nvx] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = tid + u * 64 * NW, sy = e / H, sx = e - sy * H;
+      if (e < TOT) {
+        const double2 y0 = *reinterpret_cast<const double2 *>(my + 4 * sy), y1 = *reinterpret_cast<const double2 *>(my + 4 * sy + 2);     // w_vv, w_mv | w_vm, w_mm
+        const double2 x0 = *reinterpret_cast<const double2 *>(mx + 4 * sx), x1 = *reinterpret_cast<const double2 *>(mx + 4 * sx + 2);
+        // transposed mix of y: class value = w_.v mode(v) + w_.m mode(m), column by column
+        const double av_v = fma(y0.x, stage[u][0], y1.x * stage[u][2]), am_v = fma(y0.y, stage[u][0], y1.y * stage[u][2]);       // x slot of the vertex class
+        const double av_m = fma(y0.x, stage[u][1], y1.x * stage[u][3]), am_m = fma(y0.y, stage[u][1], y1.y * stage[u][3]);       // x slot of the midpoint class
+        // then of x, row by row
+        L[sy * LD1 + sx] = fma(x0.x, av_v, x1.x * av_m); L[sy * LD1 + H + sx] = fma(x0.y, av_v, x1.y * av_m);
+        L[(H + sy) * LD1 + sx] = fma(x0.x, am_v, x1.x * am_m); L[(H + sy) * LD1 + H + sx] = fma(x0.y, am_v, x1.y * am_m);
+      }
+    }
+  }
+  // ---- who computes what.  The result of a GEMM is NCT class-tile pairs x NB batch tiles; a wave holds some of them, both classes of a pair side by side in accv / accm.
+  //   role A: the wave owns class tile `fixed` over batch tiles 0 .. NA-1 (one fragment of each class transform per k-step, NA data fragments);
+  //   role B: the wave owns batch tile `fixed` over all NCT class tiles (NCT fragments of each class transform per k-step, one data fragment).
+  // NT != 5: NCT waves, all role A over all batch tiles.  NT = 5 (QUAD; 3 class tiles, 5 batch tiles - 4 in pass 2): FOUR waves, one per SIMD, as for the dense pass
+  // (profiles/r03_lds_residency.txt): passes 1 / 3: waves 0-2 role A over batch tiles 0-3, wave 3 role B on batch tile 4 (4 + 4 + 4 + 3 pair tiles); pass 2: every
+  // wave role B on batch tile w (3 pair tiles each)
+  constexpr int NA = QUAD ? 4 : NB, NACC = (QUAD && MODE == 1) ? NCT : NA, NTF = QUAD ? NCT : 1;
+  const bool roleB = QUAD && (MODE == 1 || w == NW - 1);
+  const int fixed = roleB ? (MODE == 1 ? w : NB - 1) : w;
+  auto tile_of = [&](int a, int &ct, int &bt) { ct = roleB ? a : fixed; bt = roleB ? fixed : a; return a < (roleB ? NCT : NA); };
+  // class-transform fragments in two rotating register buffers of CHK k-steps, as in k_fdmo_pass: the 2 NCH chunks of the two GEMMs form one sequence, and
+  // a buffer is refilled with the chunk after next as soon as the MFMAs that used it have been issued
+  constexpr int CHK = 2, NCH = KK / CHK;
+  const double *__restrict__ T1v = P.Tv[0][c][p1] + lane, *__restrict__ T1m = P.Tm[0][c][p1] + lane, *__restrict__ T2v = P.Tv[1][c][p2] + lane, *__restrict__ T2m = P.Tm[1][c][p2] + lane;
+  double tf[2][2][CHK][NTF];
+  auto load_chunk = [&](auto role_c, int buf, int step) {    // step < NCH: chunk `step` of GEMM 1, else chunk step - NCH of GEMM 2
+    constexpr bool RB = decltype(role_c)::value;
+    const double *__restrict__ Tv = step < NCH ? T1v : T2v, *__restrict__ Tm = step < NCH ? T1m : T2m; const int ch = step < NCH ? step : step - NCH;
+#pragma unroll
+    for (int k = 0; k < CHK; ++k) {
+#pragma unroll
+      for (int f = 0; f < (RB ? NCT : 1); ++f) { const int ct = RB ? f : fixed; tf[buf][0][k][f] = Tv[((int64_t)ct * KK + CHK * ch + k) * 64]; tf[buf][1][k][f] = Tm[((int64_t)ct * KK + CHK * ch + k) * 64]; }
+    }
+  };
+  v4d accv[NACC], accm[NACC];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int t = 0; t < NACC; ++t) { accv[t] = v4d{0, 0, 0, 0}; accm[t] = v4d{0, 0, 0, 0}; }
+  };
+  // contract columns: tile (bt, ct) = sum_k data(rows of batch tile bt, k) T(rows of class tile ct, k); contract rows: tile (ct, bt) = sum_k T(rows of class tile ct, k) data(k, columns of batch tile bt);
+  // k runs over the class region (offset H for the midpoint class), whole trailing k-steps are skipped (wave-uniform)
+  auto gemm = [&](auto role_c, auto contract_cols, auto ld_c, auto first_step_c, int kkv, int kkm) {
+    constexpr bool RB = decltype(role_c)::value, kCols = decltype(contract_cols)::value; constexpr int LD = decltype(ld_c)::value, S0 = decltype(first_step_c)::value;
+    constexpr int ND = RB ? 1 : NA, NF = RB ? NCT : 1;          // data fragments / transform fragments per class and k-step
+    const double *La = (kCols ? L + j * LD + kq : L + kq * LD + j) + (RB ? (kCols ? 16 * fixed * LD : 16 * fixed) : 0);
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+      const int buf = (S0 + kk / CHK) & 1;
+#pragma unroll
+      for (int cls = 0; cls < 2; ++cls) {
+        if (kk < (cls ? kkm : kkv)) {
+          double d[ND];
+#pragma unroll
+          for (int t = 0; t < ND; ++t) d[t] = kCols ? La[16 * t * LD + cls * H + 4 * kk] : La[(cls * H + 4 * kk) * LD + 16 * t];
+#pragma unroll
+          for (int a = 0; a < (RB ? NF : ND); ++a) {
+            const double dv = d[RB ? 0 : a], tv = tf[buf][cls][kk % CHK][RB ? a : 0];
+            v4d &acc = cls ? accm[a] : accv[a];
+            acc = kCols ? __builtin_amdgcn_mfma_f64_16x16x4f64(dv, tv, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(tv, dv, acc, 0, 0, 0);
+          }
+        }
+      }
+      // (pass 2: GEMM 2's first chunks are requested behind the epilogue instead - held across its reciprocal sequences they cost the third wave per SIMD)
+      if (kk % CHK == CHK - 1 && S0 + kk / CHK + 2 < ((MODE == 1 && S0 == 0) ? NCH : 2 * NCH)) load_chunk(role_c, buf, S0 + kk / CHK + 2);
+    }
+  };
+  // the role is wave-uniform; both bodies are branch-free instruction streams
+  auto by_role = [&](auto f) {
+    if constexpr (!QUAD) f(std::false_type{});
+    else if constexpr (MODE == 1) f(std::true_type{});
+    else { if (roleB) f(std::true_type{}); else f(std::false_type{}); }
+  };
+  typedef std::integral_constant<bool, kColsFirst> CF; typedef std::integral_constant<int, LD1> L1c;
+  typedef std::integral_constant<bool, kColsSecond> CS; typedef std::integral_constant<int, LD2> L2c;
+  typedef std::integral_constant<int, 0> S0c; typedef std::integral_constant<int, NCH> S1c;
+  by_role([&](auto r) { load_chunk(r, 0, 0); load_chunk(r, 1, 1); });
+  zero_acc();
+  __syncthreads();
+  by_role([&](auto r) { gemm(r, CF{}, L1c{}, S0c{}, P.kkv[0], P.kkm[0]); });
+  __syncthreads();                                   // everybody has finished reading the input block
+  // ---- first result -> LDS in the layout of the second GEMM ----
+  if constexpr (MODE == 0) {           // tile (bt, ct): (y line index 16 bt + 4 q + kq, x slot 16 ct + j): mix of x with the lane's four coefficients
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+      const int s = 16 * ct + j;
+      const double *__restrict__ m1 = P.mix[0][c][p1] + 4 * s;
+      const double2 w0 = *reinterpret_cast<const double2 *>(m1), w1 = *reinterpret_cast<const double2 *>(m1 + 2);
+      if (s < H) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double av = accv[a][q], bb = accm[a][q]; const int row = 16 * bt + 4 * q + kq;
+          L[row * LD2 + s] = fma(w0.x, av, w0.y * bb); L[row * LD2 + H + s] = fma(w1.x, av, w1.y * bb);
+        }
+      }
+    }
+  } else if constexpr (MODE == 2) {    // tile (ct, bt): (y position 16 ct + 4 q + kq, x slot region column 16 bt + j): the mixes are done
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int p = 16 * ct + 4 * q + kq;
+        if (p < H) { L[p * LD2 + 16 * bt + j] = accv[a][q]; L[(H + p) * LD2 + 16 * bt + j] = accm[a][q]; }
+      }
+    }
+  } else {                             // tile (ct, bt): (z slot 16 ct + 4 q + kq, column 16 bt + j): mix, divide by the eigenvalue sums, transposed mix
+    const double *__restrict__ lamz = P.lam_z[c][p1], *__restrict__ m1 = P.mix[0][c][p1];
+    const double *bx = P.bxy + (int64_t)(4 * c + (o & 3)) * P.pl; const double czc = P.cz[c];
+    double gz = 0;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+      const double bxy = bx[min(b * P.C + 16 * bt + j, P.pl - 1)];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int s = 16 * ct + 4 * q + kq;
+        const double2 w0 = *reinterpret_cast<const double2 *>(m1 + 4 * s), w1 = *reinterpret_cast<const double2 *>(m1 + 4 * s + 2);
+        const double lzv = lamz[s], lzm = lamz[64 + s];
+        const double av = accv[a][q], bb = accm[a][q];
+        const double gv = fma(w0.x, av, w0.y * bb), gm = fma(w1.x, av, w1.y * bb);
+        // reciprocal by v_rcp_f64 + one Newton step; modes that do not exist carry lam = inf and give exactly 0
+        const double dv = fma(czc, lzv, bxy), dm = fma(czc, lzm, bxy);
+        double rv = __builtin_amdgcn_rcp(dv), rm = __builtin_amdgcn_rcp(dm);
+        rv = dv < 1e300 ? fma(rv, fma(-dv, rv, 1.0), rv) : 0.0; rm = dm < 1e300 ? fma(rm, fma(-dm, rm, 1.0), rm) : 0.0;
+        const double zv = gv * rv, zm = gm * rm;
+        if constexpr (GZ) gz = fma(gm, zm, fma(gv, zv, gz));
+        if (s < H) { L[s * LD2 + 16 * bt + j] = fma(w0.x, zv, w1.x * zm); L[(H + s) * LD2 + 16 * bt + j] = fma(w0.y, zv, w1.y * zm); }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr (GZ) {                 // wave sums -> LDS; the barrier in front of the second GEMM publishes them
+      gz = wave_sum(gz);
+      if (lane == 0) gz_wave[w] = gz;
+    }
+  }
+  if constexpr (MODE == 1) by_role([&](auto r) { load_chunk(r, NCH & 1, NCH); load_chunk(r, (NCH + 1) & 1, NCH + 1); });
+  zero_acc();
+  __syncthreads();
+  if constexpr (GZ) {
+    if (tid == 0) { double t = 0; for (int k = 0; k < NW; ++k) t += gz_wave[k]; P.gz_part[blockIdx.x] = t; }   // fixed order: bitwise reproducible
+  }
+  by_role([&](auto r) { gemm(r, CS{}, L2c{}, S1c{}, P.kkv[1], P.kkm[1]); });
+  // ---- store ----
+  if constexpr (MODE == 0) {           // tile (ct, bt): (y slot 16 ct + 4 q + kq, x slot region column 16 bt + j): mix of y, then the compact class-major order; every entry of the plane is written, the pad column too
+    const double *__restrict__ m2 = P.mix[1][c][p2];
+    const int nvx = P.nvx, nvy = P.nvy, nmy = P.nmy;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+      const int cpos = 16 * bt + j, col = cpos < H ? (cpos < nvx ? cpos : -1) : (cpos - H < C - nvx ? nvx + cpos - H : -1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int s = 16 * ct + 4 * q + kq;
+        const double2 w0 = *reinterpret_cast<const double2 *>(m2 + 4 * s), w1 = *reinterpret_cast<const double2 *>(m2 + 4 * s + 2);
+        const double av = accv[a][q], bb = accm[a][q];
+        if (col >= 0 && s < nvy) out[base + (int64_t)s * P.row_stride + col] = fma(w0.x, av, w0.y * bb);
+        if (col >= 0 && s < nmy) out[base + (int64_t)(nvy + s) * P.row_stride + col] = fma(w1.x, av, w1.y * bb);
+      }
+    }
+  } else if constexpr (MODE == 2) {    // tile (bt, ct): (y line index 16 bt + 4 q + kq, x position 16 ct + j): nodes 2 p and 2 p + 1 of the row in one 16-byte store
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+      const int px = 16 * ct + j;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int rn = node_of(16 * bt + 4 * q + kq);
+        if (px < H && rn < R && 2 * px < C) *reinterpret_cast<double2 *>(out + base + (int64_t)rn * P.row_stride + 2 * px) = double2{accv[a][q], accm[a][q]};
+      }
+    }
+  } else {                             // tile (ct, bt): (z position 16 ct + 4 q + kq, column 16 bt + j): rows 2 p and 2 p + 1
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      int ct, bt; if (!tile_of(a, ct, bt)) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int p = 16 * ct + 4 * q + kq, cc = 16 * bt + j;
+        if (p < H && cc < C) {
+          if (2 * p < R) out[base + (int64_t)(2 * p) * P.row_stride + cc] = accv[a][q];
+          if (2 * p + 1 < R) out[base + (int64_t)(2 * p + 1) * P.row_stride + cc] = accm[a][q];
+        }
+      }
+    }
+  }
+}
+
 // ---- the strip form of the scalar passes (one rank, the flags of the General variant without the slab extras) ------------------------------------------------------------
 // A scalar Q1 system has one block per z plane (passes 1 / 3) and a few dozen chunks (pass 2): k_fdmo_pass starts far fewer workgroups than the chip has CUs, and a launch
 // lasts as long as ONE workgroup needs for its two chained GEMMs.  Here a block is shared out over NT workgroups of NT waves, one tile per wave and GEMM:
@@ -1164,6 +1445,32 @@ void launch_pass_nt(hipStream_t s, int nt, PassVariant v, const OctPass &P, int 
     default: throw Error("fdmo: half lines of more than 128 entries");
   }
 }
+// class-split passes: the same block, grid and LDS size as the dense octant pass of that tile count
+template <int NT> void launch_vm(hipStream_t s, const OctPassVM &P, int n_items, const double *in, double *out, hipEvent_t e0, hipEvent_t e1) {
+  constexpr unsigned lds = (unsigned)(PassGeom<NT>::PADN * PassGeom<NT>::LDMAX * sizeof(double));
+  auto go = [&](auto kernel) {
+    if (lds > 64 * 1024) {
+      static std::mutex mu; static std::set<std::pair<int, const void *>> done; int dev = 0; PORO_HIP(hipGetDevice(&dev));
+      std::lock_guard<std::mutex> lk(mu);
+      if (!done.count({dev, reinterpret_cast<const void *>(kernel)})) { PORO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done.insert({dev, reinterpret_cast<const void *>(kernel)}); }
+    }
+    hipExtLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(64 * vm_waves<NT>()), lds, s, e0, e1, 0, P, in, out);
+  };
+  if (P.mode == 0) go(k_fdmo_pass_vm<NT, 0>); else if (P.mode == 2) go(k_fdmo_pass_vm<NT, 2>); else if (P.gz_part) go(k_fdmo_pass_vm<NT, 1, true>); else go(k_fdmo_pass_vm<NT, 1>);
+}
+void launch_vm_nt(hipStream_t s, int nt, const OctPassVM &P, int n_items, const double *in, double *out, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  switch (nt) {
+    case 1: launch_vm<1>(s, P, n_items, in, out, e0, e1); break;
+    case 2: launch_vm<2>(s, P, n_items, in, out, e0, e1); break;
+    case 3: launch_vm<3>(s, P, n_items, in, out, e0, e1); break;
+    case 4: launch_vm<4>(s, P, n_items, in, out, e0, e1); break;
+    case 5: launch_vm<5>(s, P, n_items, in, out, e0, e1); break;
+    case 6: launch_vm<6>(s, P, n_items, in, out, e0, e1); break;
+    case 7: launch_vm<7>(s, P, n_items, in, out, e0, e1); break;
+    case 8: launch_vm<8>(s, P, n_items, in, out, e0, e1); break;
+    default: throw Error("fdmo: half lines of more than 128 entries");
+  }
+}
 // columns of a pass-2 chunk: one 16-wide tile per wave (NT = 5: four waves)
 inline int pass2_chunk(int nt) { return nt == 5 ? 64 : 16 * nt; }
 inline int pass2_chunks(int pl, int nt) { return (pl + pass2_chunk(nt) - 1) / pass2_chunk(nt); }   // chunks of a plane of pl positions = workgroups of pass 2 per block (one rank)
@@ -1234,6 +1541,22 @@ OctPass plan_pass(const Form &F, int pass) {
   }
   return P;
 }
+// the class-split passes of the single-rank octant form: the dense plan's blocks and grids, the class tables of fdmo_upload_dir_classes
+OctPassVM plan_vm(const FdmOct &O, const OctPass &D, int pass) {
+  OctPassVM P{};
+  P.mode = D.mode; P.R = D.R; P.C = D.C; P.nblk = D.nblk; P.pl = D.pl; P.co_stride = D.co_stride; P.blk_stride = D.blk_stride; P.row_stride = D.row_stride; P.bit1 = D.bit1; P.bit2 = D.bit2;
+  const int dir[2] = {pass == 1 ? 0 : pass == 2 ? 2 : 1, pass == 1 ? 1 : pass == 2 ? 2 : 0}; const bool back[2] = {pass == 3, pass != 1};
+  for (int g = 0; g < 2; ++g) {
+    const int h = O.h[dir[g]]; P.kkv[g] = ((h + 1) / 2 + 3) / 4; P.kkm[g] = (h / 2 + 3) / 4;
+    for (int c = 0; c < 3; ++c) for (int p = 0; p < 2; ++p) {
+      P.Tv[g][c][p] = (back[g] ? O.cbwd : O.cfwd)[c][dir[g]][p][0].p; P.Tm[g][c][p] = (back[g] ? O.cbwd : O.cfwd)[c][dir[g]][p][1].p; P.mix[g][c][p] = O.cmix[c][dir[g]][p].p;
+    }
+  }
+  P.nvx = (O.h[0] + 1) / 2; P.nvy = (O.h[1] + 1) / 2; P.nmy = O.h[1] / 2;
+  for (int c = 0; c < 3; ++c) { P.cz[c] = O.coef[c][2]; for (int p = 0; p < 2; ++p) P.lam_z[c][p] = O.clam[c][2][p].p; }
+  P.bxy = O.bxy_vm.p;
+  return P;
+}
 // slab form: the same plan + where the pass meets the exchange buffer (see OctPass): pass 1 stores into it, pass 3 loads from it, pass 2 gathers whole lines from it
 OctPass plan_slab_pass(const Form &F, int pass) {
   const auto &S = F.O.slab;
@@ -1292,7 +1615,7 @@ void slab_prologue(FdmOct &O, const int nn[3], int rank, const std::vector<int> 
 }  // namespace
 
 // everything of the three passes of a displacement form that does not change from one application to the next: [fp64 / fp32 fragments][pass]
-struct FdmoPlans { OctPass pass[2][3]; int n_items[3]; };
+struct FdmoPlans { OctPass pass[2][3]; int n_items[3]; OctPassVM vm[3]; };
 
 bool fdmo_usable(int dim, const int nn[3]) {
   if (dim != 3) return false;
@@ -1401,8 +1724,32 @@ void fdmo_upload_dir(FdmOct &O, int comp, int dir, const LineTables &T) {
   }
 }
 
+void fdmo_upload_dir_classes(FdmOct &O, int comp, int dir, const ClassSplitTables &T) {
+  if (!O.class_split || O.per_dir || O.slab.on || O.planar) throw Error("fdmo_upload_dir_classes: the class-split passes exist for the single-rank octant form only");
+  if (!T.ok || T.n != O.n[dir]) throw Error("fdmo_upload_dir_classes: a line that is not class-split");      // (the caller decides from ClassSplitTables::ok before any upload)
+  const int nt = O.nt, tiles = (nt + 1) / 2, ksteps = 2 * nt, h = O.h[dir]; const double inf = std::numeric_limits<double>::infinity();
+  for (int p = 0; p < 2; ++p) {
+    const ClassSplitGroup &G = T.grp[p];
+    if (G.nv != (h + 1) / 2 || G.nm != h / 2 || G.nv > 8 * nt || G.slots > 8 * nt || G.slots > 64) throw Error("fdmo_upload_dir_classes: class sizes do not fit the pass kernel");
+    for (int cls = 0; cls < 2; ++cls) { O.cfwd[comp][dir][p][cls].upload(class_fragments(G, cls, tiles, ksteps, false)); O.cbwd[comp][dir][p][cls].upload(class_fragments(G, cls, tiles, ksteps, true)); }
+    std::vector<double> mix(4 * 64, 0.0), lam(2 * 64, inf);
+    for (int s = 0; s < G.slots; ++s) { for (int e = 0; e < 4; ++e) mix[4 * s + e] = G.mix[4 * s + e]; lam[s] = G.lam_v[s]; lam[64 + s] = G.lam_m[s]; }
+    O.cmix[comp][dir][p].upload(mix); O.clam[comp][dir][p].upload(lam); O.h_clam[comp][dir][p] = lam;
+  }
+}
+bool fdmo_class_split_runs(const FdmOct &O, int precision) { return O.class_split && precision != PORO_FDM_FP32 && !O.per_dir && !O.slab.on && !O.planar; }
+
 void fdmo_finalize(FdmOct &O) {
   const int hx = O.h[0], hy = O.h[1], hxp = O.hxp; const size_t pl = (size_t)hxp * hy;
+  if (O.class_split) {      // the x / y share of the eigenvalue sums in the class-major mode order of the plane: index s of the vertex class, nv + s of the midpoint class
+    const int nvx = (hx + 1) / 2, nvy = (hy + 1) / 2;
+    std::vector<double> B((size_t)12 * pl, 1.0);
+    for (int c = 0; c < 3; ++c) for (int q = 0; q < 4; ++q) for (int my = 0; my < hy; ++my) for (int mx = 0; mx < hx; ++mx) {
+      const std::vector<double> &lx = O.h_clam[c][0][q & 1], &ly = O.h_clam[c][1][q >> 1];
+      B[(size_t)(4 * c + q) * pl + (size_t)my * hxp + mx] = O.coef[c][0] * (mx < nvx ? lx[mx] : lx[64 + mx - nvx]) + O.coef[c][1] * (my < nvy ? ly[my] : ly[64 + my - nvy]);
+    }
+    O.bxy_vm.upload(B);
+  }
   // planes per component: one per parity combination of x and y (per-direction form: of those of the two that are split, x in the lowest bit)
   const int sx = O.per_dir ? (O.split_mask & 1) : 1, sy = O.per_dir ? ((O.split_mask >> 1) & 1) : 1, cmul = 1 << (sx + sy);
   std::vector<double> B((size_t)3 * cmul * pl, 1.0);             // (row pads: any finite non-zero value, their data are zeros)
@@ -1417,6 +1764,7 @@ void fdmo_finalize(FdmOct &O) {
     plans->pass[f32][k] = O.slab.on ? plan_slab_pass(F, k + 1) : plan_pass(F, k + 1);
     plans->n_items[k] = F.blocks * plans->pass[f32][k].nblk;
   }
+  if (O.class_split) for (int k = 0; k < 3; ++k) plans->vm[k] = plan_vm(O, plans->pass[0][k], k + 1);
   O.plans = plans;
 }
 
@@ -1434,6 +1782,13 @@ void fdmo_apply(hipStream_t s, const FdmOct &O, const double *g_oct, double *z_o
   if (f32 && !scratch) throw Error("fdmo_apply: the fp32 transforms need the scratch array");
   double *const mid = scratch ? scratch : z_oct;
   const double *const in[3] = {g_oct, mid, mid}; double *const out[3] = {mid, mid, z_oct};      // (pass 2 works in place)
+  if (fdmo_class_split_runs(O, precision)) {        // the same three launches with the class-split kernels (no stamps: the diagnostic belongs to k_fdmo_pass)
+    for (int k = 0; k < 3; ++k) {
+      OctPassVM V = O.plans->vm[k]; V.gate = gate; if (k == 1) V.gz_part = gz_part; if (k == 0) V.stop = stop;
+      launch_vm_nt(s, O.nt, V, n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
+    }
+    return;
+  }
   for (int k = 0; k < 3; ++k) launch_pass_nt(s, k == 1 ? O.nt_z : O.nt, f32 ? PassVariant::OctantF32 : O.per_dir ? PassVariant::PerDirection : PassVariant::Octant, P[k], n_items[k], in[k], out[k], ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr);
   stamps.dump(s);
 }
