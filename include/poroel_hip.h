@@ -581,6 +581,44 @@ int  poro_ctx_set_cell_density(poro_ctx *ctx, const double *rho /* [n_cells], NU
 int  poro_ctx_get_cell_density(poro_ctx *ctx, double *out /* [n_cells], may be NULL */, int64_t n_cells, int32_t *kind);
 int  poro_get_gravity_vectors(poro_ctx *ctx, double *body_u /* [n_dofs_u] or NULL */, double *flux_p /* [n_dofs_p] or NULL */);
 
+/* Darcy velocity, boundary discharge and fluid mass balance (appended entry points, no struct of the existing ABI changes: PORO_ABI_VERSION stays 4).  Pure
+ * post-processing: the calls synchronise (they return host data), leave every PORO_VEC_* vector unchanged, work in both operator modes and on every single-rank mesh
+ * (box-tagged, tensor, refined with hanging nodes, Gmsh; 2D and 3D) and read the permeability and the gravity the context holds AT THE TIME OF THE CALL.  A vector that
+ * is not in the pressure space, a partitioned context (n_ranks > 1) and time_step <= 0 return < 0 with a message.  Timer families: "darcy", "flow_balance"
+ * (inside them, for measurements: "darcy_bfaces", "darcy_label_sums", "flow_balance_sums" bracket those kernels alone).
+ * THE DEFINITIONS BELOW ARE THIS PROJECT'S (the reference computes no flow); this text is what the tests pin.
+ *   kappa_c = what the context holds for cell c: poro_material.k_over_mu, the per-cell k / mu, or its per-cell diagonal tensor (products then componentwise).
+ *   rho_f g = the gravity term of Darcy's law; zero unless gravity is on with a fluid density - exactly the condition under which the residual carries the gravity flux.
+ * Cell velocity (poro_pres_darcy_velocity): q_c = -kappa_c (grad p_h(x_c) - rho_f g), p_h the Q1 function of the pressure-space vector `which_vec`, x_c the image of
+ *   the reference centre (1/2, ..., 1/2) under MappingQ1.  q_host[n_cells][dim], cells in the descriptor's order.
+ * Face discharge (poro_pres_boundary_discharge): for entry b of the boundary-face list (local face f = 2 d + side of its cell)
+ *   Q_b = int_F q . n dS with the tensorised Gauss(2) rule on the face, q = -kappa_c (grad p_h - rho_f g) evaluated from the face's own cell at the face points, n dS
+ *   from the face's own map (column d of det(J) J^-T with the sign of the side: the convention of the Neumann term and of the Kelly indicator).  n is outward: positive
+ *   means fluid leaving.  Q_face_host[n_bfaces] (may be NULL).
+ * Label sums: Q_label_host[l] = the sum of Q_b over the faces with bface_id == labels[l], in list order per lane (a fixed face-to-lane assignment and a fixed-order
+ *   block sum: no float atomics, the same bits from call to call); a label no face carries gives exactly 0.  labels may be NULL with n_labels = 0.
+ * Discrete balance (poro_pres_flow_balance): let r = M t + kappa K p + src be the pressure residual's own vector before any sign, condensation or masking,
+ *   t = alpha (eps_v - eps_v0) / dt + (p - p_old) / (M_b dt) from PORO_VEC_{EPSV, EPSV0, P, P_OLD}, src what poro_pres_assemble_residual uses (the well alone, or well
+ *   plus gravity flux), Rt = C^T(-r) the condensed residual BEFORE the prescribed rows are zeroed, and m_j = sum_i M_ij = int phi_j the lumped mass (built once per
+ *   context from its own mass matrix).  Reported:
+ *     storage_rate_strain   = sum_j m_j alpha (eps_v - eps_v0)_j / dt
+ *     storage_rate_pressure = sum_j m_j (p - p_old)_j / (M_b dt)
+ *     source_sum            = sum_i src_i   (negative for an injecting well)
+ *     outflow_prescribed    = sum of Rt_i over the prescribed-pressure rows: since -r_i = int_Gamma phi_i q . n there, the conservative discharge through the drained boundary
+ *     free_row_sum          = sum of Rt_i over all other rows
+ *     residual_l2           = sqrt(sum over the other rows of Rt_i^2), the number poro_pres_assemble_residual returns
+ *   and optionally Rt_i for every prescribed dof in the order of poro_desc.dirichlet_dof_p (outflow_dof_host[n_dirichlet_p]).  Algebraic identity, on every mesh and with
+ *   every permeability form (the columns of K sum to zero, the gravity flux vector sums to zero, hanging-node weights sum to one):
+ *     outflow_prescribed + free_row_sum = -(storage_rate_strain + storage_rate_pressure + source_sum).
+ *   |free_row_sum| <= sqrt(n_dofs_p) residual_l2 (Cauchy-Schwarz): a step whose pressure loop converged closes its balance to sqrt(n_dofs_p) * its tolerance.
+ *   CAVEAT: with the reference's loop as committed (storage against the eps_v0 of the run's START) storage_rate_strain is the discrete system's term, not a physical
+ *   rate; it is physical where eps_v0 is the previous step's strain (the host layer's incremental_strain switch).
+ *   Rt is assembled into scratch by the calls poro_pres_assemble_residual makes; PORO_VEC_RESIDUAL_P is not touched. */
+typedef struct poro_flow_balance_terms { double storage_rate_strain, storage_rate_pressure, source_sum, outflow_prescribed, free_row_sum, residual_l2; } poro_flow_balance_terms;
+int  poro_pres_darcy_velocity(poro_ctx *ctx, int which_vec, double *q_host /* [n_cells][dim] */);
+int  poro_pres_boundary_discharge(poro_ctx *ctx, int which_vec, double *Q_face_host /* [n_bfaces] or NULL */, const int32_t *labels, int32_t n_labels, double *Q_label_host /* [n_labels] or NULL */);
+int  poro_pres_flow_balance(poro_ctx *ctx, double time_step, poro_flow_balance_terms *out, double *outflow_dof_host /* [n_dirichlet_p] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,14 @@ class SolveInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class FlowBalanceTerms(C.Structure):
+    """poro_flow_balance_terms (include/poroel_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("storage_rate_strain", "storage_rate_pressure", "source_sum", "outflow_prescribed", "free_row_sum", "residual_l2")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RunOptions(C.Structure):
     """poro_host_run_options (host/run_controls.hpp), member by member; tests/test_run_options_cpu.py holds the two layouts against each other"""
     _fields_ = [("p_init", C.c_double), ("time_step", C.c_double), ("n_steps", C.c_int32), ("fss_tol", C.c_double), ("pressure_tol", C.c_double),
@@ -124,7 +132,8 @@ HIP_SYMBOLS = [
     "poro_ctx_set_cell_permeability_tensor", "poro_ctx_get_cell_permeability_tensor",
     "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli",
     "poro_ctx_set_moduli_operator", "poro_ctx_get_moduli_operator",
-    "poro_ctx_set_gravity", "poro_ctx_get_gravity", "poro_ctx_set_cell_density", "poro_ctx_get_cell_density", "poro_get_gravity_vectors"]
+    "poro_ctx_set_gravity", "poro_ctx_get_gravity", "poro_ctx_set_cell_density", "poro_ctx_get_cell_density", "poro_get_gravity_vectors",
+    "poro_pres_darcy_velocity", "poro_pres_boundary_discharge", "poro_pres_flow_balance"]
 
 _hip = None
 _host = None
@@ -203,6 +212,9 @@ def load_hip():
         L.poro_ctx_set_cell_density.argtypes = [C.c_void_p, _dp, C.c_int64]
         L.poro_ctx_get_cell_density.argtypes = [C.c_void_p, _dp, C.c_int64, _ip]
         L.poro_get_gravity_vectors.argtypes = [C.c_void_p, _dp, _dp]
+        L.poro_pres_darcy_velocity.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.poro_pres_boundary_discharge.argtypes = [C.c_void_p, C.c_int, _dp, _ip, C.c_int32, _dp]
+        L.poro_pres_flow_balance.argtypes = [C.c_void_p, C.c_double, C.POINTER(FlowBalanceTerms), _dp]
         _hip = L
     return _hip
 
@@ -287,6 +299,11 @@ def load_host():
         L.poro_host_runner_work.restype = None
         L.poro_host_runner_postprocess.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.poro_host_runner_state.argtypes = [C.c_void_p, C.c_int]
+        L.poro_host_runner_postprocess_darcy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
+        L.poro_host_runner_track_flow.argtypes = [C.c_void_p, C.c_int]
+        L.poro_host_runner_flow_balance.argtypes = [C.c_void_p, _dp, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp]
+        L.poro_host_pressure_bc_labels.restype = C.c_int64
+        L.poro_host_pressure_bc_labels.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.restype = None
         L.poro_host_runner_free.argtypes = [C.c_void_p]
@@ -496,6 +513,13 @@ class Problem:
         self._host("set_pressure_bc", len(conditions), pl, pv)
         self.desc = self.desc_ptr.contents
         return self
+
+    def pressure_bc_labels(self):
+        """per entry of desc.dirichlet_dof_p the boundary label that prescribed it; on an edge shared by two labelled faces the first condition of set_pressure_bc wins"""
+        H = load_host()
+        out = np.zeros(H.poro_host_pressure_bc_labels(self.handle, None), dtype=np.int32)
+        H.poro_host_pressure_bc_labels(self.handle, out.ctypes.data_as(_ip))
+        return out
 
     def _host(self, name, *args):
         """poro_host_<name>(handle, *args); raises what the host layer reports"""
@@ -852,6 +876,27 @@ class Context:
         self._chk(self.L.poro_pres_estimate_error(self.ptr, int(which), eta.ctypes.data_as(_dp)))
         return eta
 
+    def darcy_velocity(self, which=VEC_P):
+        """q_c = -kappa_c (grad p_h(x_c) - rho_f g) at the cell centres, [n_cells][dim] (definition: include/poroel_hip.h)"""
+        q = np.empty((self.problem.desc.n_cells, self.dim))
+        self._chk(self.L.poro_pres_darcy_velocity(self.ptr, int(which), q.ctypes.data_as(_dp)))
+        return q
+
+    def boundary_discharge(self, labels=None, which=VEC_P):
+        """(Q_face[n_bfaces], Q_label[len(labels)]): int_F q . n dS per boundary face, outward positive, and its deterministic sums over the faces of each label"""
+        Q = np.empty(self.problem.desc.n_bfaces)
+        lab, pl = _arr_i([] if labels is None else labels)
+        Ql = np.empty(lab.size)
+        self._chk(self.L.poro_pres_boundary_discharge(self.ptr, int(which), Q.ctypes.data_as(_dp), pl if lab.size else None, int(lab.size), Ql.ctypes.data_as(_dp) if lab.size else None))
+        return Q, Ql
+
+    def flow_balance(self, dt):
+        """(terms, outflow_dof): the terms of the discrete fluid balance as a dict and C^T(-r) on the prescribed-pressure dofs in the order of dirichlet_dof_p"""
+        t = FlowBalanceTerms()
+        out = np.empty(self.problem.desc.n_dirichlet_p)
+        self._chk(self.L.poro_pres_flow_balance(self.ptr, float(dt), C.byref(t), out.ctypes.data_as(_dp) if out.size else None))
+        return t.as_dict(), out
+
     def transfer_p_from(self, other, rows):
         """VEC_P, VEC_EPSV, VEC_EPSV0 of `other` (the context of the previous mesh) -> this context through rows = (ptr, node, weight), e.g. other.problem.transfer_rows_p(self.problem)"""
         ptr = np.ascontiguousarray(rows[0], dtype=np.int64)
@@ -1110,10 +1155,42 @@ class Runner:
         if self.H.poro_host_runner_state(self.h, 1) != 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
 
-    def postprocess(self, output_dir=None, corrected=False):
-        """PoroelasticityFSS.h:409-411: shear strains, effective stresses (PORO_VEC_STRESS0+e) and, with a directory, solution-NNNN.vtk"""
-        if self.H.poro_host_runner_postprocess(self.h, output_dir.encode() if output_dir else None, int(corrected)) < 0:
+    def postprocess(self, output_dir=None, corrected=False, darcy=False):
+        """PoroelasticityFSS.h:409-411: shear strains, effective stresses (PORO_VEC_STRESS0+e) and, with a directory, solution-NNNN.vtk; darcy=True appends the Darcy
+        velocity per cell (CELL_DATA / VECTORS darcy_velocity) to the file"""
+        d = output_dir.encode() if output_dir else None
+        rc = self.H.poro_host_runner_postprocess_darcy(self.h, d, int(corrected), 1) if darcy else self.H.poro_host_runner_postprocess(self.h, d, int(corrected))
+        if rc < 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
+
+    def darcy_velocity(self):
+        """q_c = -kappa_c (grad p_h(x_c) - rho_f g) of the present pressure, [n_cells][dim] (Context.darcy_velocity)"""
+        return self.ctx.darcy_velocity()
+
+    def track_flow_balance(self, on=True):
+        """while on, every step() adds dt * the terms of its fluid balance to the cumulative volumes flow_balance() reports; initialize() resets them, adapt() keeps them"""
+        if self.H.poro_host_runner_track_flow(self.h, int(bool(on))) != 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
+
+    def flow_balance(self):
+        """The discrete fluid balance of the present state (include/poroel_hip.h, poro_pres_flow_balance): the six terms; `labels` = the prescribed-pressure labels;
+        outflow_by_label = the conservative discharge C^T(-r) summed over the dofs each label prescribed; discharge_by_label = the face integrals of q . n;
+        `cumulative` = the time integrals over the steps taken since track_flow_balance(): steps, storage_strain, storage_pressure, source (injected volume, negative
+        for an injecting well), outflow, free_rows, bound (sum of dt sqrt(n_dofs_p) residual_l2), outflow_by_label, discharge_by_label"""
+        cap = 64
+        terms = np.zeros(6); totals = np.zeros(8)
+        labels = np.zeros(cap, dtype=np.int32); out, dis, tout, tdis = (np.zeros(cap) for _ in range(4))
+        n = self.H.poro_host_runner_flow_balance(self.h, terms.ctypes.data_as(_dp), labels.ctypes.data_as(_ip), out.ctypes.data_as(_dp), dis.ctypes.data_as(_dp), cap,
+                                                 totals.ctypes.data_as(_dp), tout.ctypes.data_as(_dp), tdis.ctypes.data_as(_dp))
+        if n < 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
+        res = dict(zip([f[0] for f in FlowBalanceTerms._fields_], terms.tolist()))
+        lab = [int(l) for l in labels[:n]]
+        res.update(labels=lab, outflow_by_label=dict(zip(lab, out[:n].tolist())), discharge_by_label=dict(zip(lab, dis[:n].tolist())))
+        nt = int(totals[7])
+        res["cumulative"] = dict(steps=int(totals[0]), storage_strain=totals[1], storage_pressure=totals[2], source=totals[3], outflow=totals[4], free_rows=totals[5], bound=totals[6],
+                                 outflow_by_label=dict(zip(lab[:nt], tout[:nt].tolist())), discharge_by_label=dict(zip(lab[:nt], tdis[:nt].tolist())))
+        return res
 
     def preconditioners(self):
         """(displacement, pressure, projection): the PREC_* the driver chose for the current context (made in initialize(), and again after every adapt())"""

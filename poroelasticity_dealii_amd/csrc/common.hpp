@@ -350,6 +350,10 @@ struct poro_ctx {
     poro::DevBuf<double> body_u, flux_p, src_p;
     bool flux_on() const { return on && rho_f != 0; }
   } grav;
+  // Flow post-processing (ctx_flux.hip, kernels_darcy.hip), allocated at the first call: q [n_cells][dim], Qf [n_bfaces], the scratch of the balance (t = the residual's
+  // storage term, rt = C^T(-r), out = rt on the prescribed dofs), m = the lumped pressure mass M 1 (built once), pdir_dof = the prescribed dofs in the descriptor's order
+  struct Flux { bool built = false; poro::DevBuf<double> q, Qf, Ql, m, t, rt, out, sums; poro::DevBuf<int32_t> labels, pdir_dof; } flux;
+  std::vector<int32_t> h_pdir_dof;   // poro_desc.dirichlet_dof_p as given
 };
 
 namespace poro {
@@ -439,6 +443,19 @@ void kelly_faces(hipStream_t s, int dim, int64_t n_faces, const int32_t *cell_a,
                  const double *p, double *jump);
 void kelly_cells(hipStream_t s, int dim, int64_t n_cells, const int64_t *ent_ptr, const int32_t *ent_face, const int32_t *ent_hcell, const double *cell_X, const double *jump, double *eta);
 void transfer_rows3(hipStream_t s, int64_t n_rows, const int64_t *ptr, const int32_t *col, const double *w, const double *const in[3], double *const out[3]);
+
+// ---- kernels_darcy.hip: Darcy velocity, boundary discharge, fluid mass balance ----
+struct DarcyGravity { double v[3]; };   // rho_f g, zeros unless Gravity::flux_on()
+// kappa_c: ncomp = 0 the scalar `kappa`; 1: perm_cell[n_cells]; dim: perm_cell[n_cells][dim] (poro_ctx::Perm::cell)
+struct DarcyArgs { int dim, ncomp; int64_t n_cells; const double *cell_X; const int32_t *cell_dofs_p; const double *p; double kappa; const double *perm_cell; DarcyGravity rg; };
+void darcy_cells(hipStream_t s, const DarcyArgs &a, double *q /* [n_cells][dim] */);
+void darcy_bfaces(hipStream_t s, const DarcyArgs &a, int64_t n_bfaces, const int32_t *bface_cell, const int32_t *bface_local, double *Q /* [n_bfaces] */);
+void darcy_label_sums(hipStream_t s, int64_t n_bfaces, const int32_t *bface_id, const double *Q, const int32_t *labels, int32_t n_labels, double *out /* [n_labels] */);
+// sums over the n pressure dofs, one slab of kMaxPartials block partials each: 0 m c_strain (ev - ev0), 1 m c_pres (p - p_old), 2 src, 3 Rt on the rows of pdir_mask (nullable),
+// 4 Rt on the other rows, 5 Rt^2 on the other rows
+struct FlowBalanceArgs { int64_t n; const double *p, *p_old, *ev, *ev0, *m, *src, *Rt; const uint8_t *pdir_mask; double c_strain, c_pres; };
+void flow_balance_partials(hipStream_t s, const FlowBalanceArgs &A, double *partials /* [6][kMaxPartials] */);
+void darcy_gather(hipStream_t s, int64_t n, const int32_t *idx, const double *src, double *dst);   // dst[i] = src[idx[i]]
 
 // ---- kernels_asm.hip ----------------------------------------------------------------------------
 struct AsmArgs {

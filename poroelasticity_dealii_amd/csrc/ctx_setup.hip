@@ -300,7 +300,7 @@ void setup(poro_ctx *c, const poro_desc *d) {
       std::vector<uint8_t> pm(c->n_p, 0); std::vector<double> pv(c->n_p, 0.0);
       if (d->n_dirichlet_p < 0 || (d->n_dirichlet_p && (!d->dirichlet_dof_p || !d->dirichlet_value_p))) throw Error("bad prescribed-pressure list");
       for (int64_t i = 0; i < d->n_dirichlet_p; ++i) { const int32_t dof = d->dirichlet_dof_p[i]; if (dof < 0 || dof >= c->n_p) throw Error("dirichlet_dof_p out of range"); pm[dof] = 1; pv[dof] = d->dirichlet_value_p[i]; }
-      c->n_pdir = d->n_dirichlet_p;
+      c->n_pdir = d->n_dirichlet_p; c->h_pdir_dof.assign(d->dirichlet_dof_p, d->dirichlet_dof_p + d->n_dirichlet_p);
       if (c->n_pdir) { if (c->comm.part.n_ranks > 1) throw Error("prescribed pressures are implemented for one rank (there: PORO_PREC_JACOBI for any set, PORO_PREC_FDM where they cover whole faces of a uniform box or tensor-product grid)"); c->pdir_mask.upload(pm); c->pdir_val.upload(pv); }
       // both lists at once (a drained face on a locally refined mesh): analysed together, see upload_constraints.  cons_p.inert is then the union of the two sets
       upload_constraints(c->cons_p, d->cons_p, c->n_p, &pm, "cons_p", c->n_pdir ? &pv : nullptr);

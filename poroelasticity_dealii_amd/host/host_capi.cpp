@@ -230,6 +230,12 @@ int poro_host_set_pressure_bc(void *h, int n, const int32_t *labels, const doubl
     return 0;
   } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+// per entry of poro_desc.dirichlet_dof_p the boundary label that prescribed it (first condition in list order on shared edges); returns the length, copies when out != NULL
+int64_t poro_host_pressure_bc_labels(void *h, int32_t *out) {
+  const auto &v = static_cast<ProblemData *>(h)->dirichlet_label_p;
+  if (out && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
+  return (int64_t)v.size();
+}
 // extension: rigid frictionless plates - component `components[i]` of the displacement takes ONE (unknown) value on the boundary `labels[i]` (before the context is created)
 int poro_host_tie_boundary(void *h, int n, const int32_t *labels, const int32_t *components) {
   try {
@@ -386,6 +392,36 @@ int poro_host_runner_restore_and_step(void *r, double *trace, int max_rows, int6
 // tail of the time loop body (PoroelasticityFSS.h:409-411): shear strains, effective stresses and, with a directory, solution-NNNN.vtk
 int poro_host_runner_postprocess(void *r, const char *output_dir, int corrected) {
   return try_on_runner(r, [&](auto &prob, RunControls rc) { rc.output_dir = output_dir ? output_dir : ""; rc.corrected_postprocessing = corrected != 0; prob.postprocess(rc); });
+}
+// the same with the Darcy velocity per cell appended to the file (CELL_DATA / VECTORS darcy_velocity) when darcy != 0
+int poro_host_runner_postprocess_darcy(void *r, const char *output_dir, int corrected, int darcy) {
+  return try_on_runner(r, [&](auto &prob, RunControls rc) { rc.output_dir = output_dir ? output_dir : ""; rc.corrected_postprocessing = corrected != 0;
+    const bool was = prob.flow_controls.darcy_output; prob.flow_controls.darcy_output = darcy != 0;
+    try { prob.postprocess(rc); } catch (...) { prob.flow_controls.darcy_output = was; throw; }
+    prob.flow_controls.darcy_output = was; });
+}
+// Flow accounting (PoroElasticProblem::flow_balance / flow_totals).  poro_host_runner_track_flow: flow_controls.flow_balance of the runner's problem - while on, every step adds dt * its
+// terms to the totals.  poro_host_runner_flow_balance: the balance of the PRESENT state (nothing is accumulated by the call): terms[6] in the order of
+// poro_flow_balance_terms; per prescribed label (at most max_labels) the label, the conservative outflow and the face-integrated discharge; totals[8] = steps accounted,
+// the time integrals of storage_rate_strain, storage_rate_pressure, source_sum, outflow_prescribed, free_row_sum, the summed bounds dt sqrt(n) residual_l2, and the number
+// of labels of the totals; total_outflow / total_discharge per label (same order).  Returns the number of labels, < 0 on error
+int poro_host_runner_track_flow(void *r, int on) { return try_on_runner(r, [&](auto &prob, const RunControls &) { prob.flow_controls.flow_balance = on != 0; }); }
+int poro_host_runner_flow_balance(void *r, double *terms, int32_t *labels, double *outflow, double *discharge, int max_labels, double *totals, double *total_outflow, double *total_discharge) {
+  try {
+    return on_runner(r, [&](auto &prob, const RunControls &rc) {
+      const auto B = prob.flow_balance(rc);
+      const poro_flow_balance_terms &t = B.terms;
+      const double all[6] = {t.storage_rate_strain, t.storage_rate_pressure, t.source_sum, t.outflow_prescribed, t.free_row_sum, t.residual_l2};
+      if (terms) std::copy(all, all + 6, terms);
+      const int n = (int)B.labels.size();
+      if (n > max_labels) throw std::runtime_error("runner_flow_balance: more prescribed labels than the caller has room for");
+      for (int k = 0; k < n; ++k) { if (labels) labels[k] = B.labels[k]; if (outflow) outflow[k] = B.outflow_by_label[k]; if (discharge) discharge[k] = B.discharge_by_label[k]; }
+      const auto &T = prob.flow_totals;
+      if (totals) { const double tt[8] = {(double)T.steps, T.storage_strain, T.storage_pressure, T.source, T.outflow, T.free_rows, T.bound, (double)T.labels.size()}; std::copy(tt, tt + 8, totals); }
+      for (size_t k = 0; k < T.labels.size() && (int)k < max_labels; ++k) { if (total_outflow) total_outflow[k] = T.outflow_by_label[k]; if (total_discharge) total_discharge[k] = T.discharge_by_label[k]; }
+      return n;
+    });
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 // cumulative work counters since creation (same layout as poro_host_runner_step's `work`)
 void poro_host_runner_work(void *r, int64_t *work) { on_runner(r, [&](auto &prob, const RunControls &) { fill_work(prob.work, work); }); }

@@ -403,17 +403,18 @@ inline RefinedBox make_refined_box(int dim, const int n[3], const double origin[
 }
 
 // extension: prescribed pressure on the faces carrying the given labels (first condition wins, like the displacement conditions)
-inline void make_dirichlet_p(const Mesh &m, const DoFs &D, const BoundaryConditions &bc, std::vector<int32_t> &dofs, std::vector<double> &values) {
+// labels (optional): for every listed dof the label of the condition that prescribed it - on an edge shared by two labelled faces the first condition in list order
+inline void make_dirichlet_p(const Mesh &m, const DoFs &D, const BoundaryConditions &bc, std::vector<int32_t> &dofs, std::vector<double> &values, std::vector<int32_t> *labels = nullptr) {
   const int dim = m.dim, nv = 1 << dim;
-  std::map<int32_t, double> cons;
+  std::map<int32_t, std::pair<double, int32_t>> cons;
   for (size_t cond = 0; cond < bc.pressure_labels.size(); ++cond)
     for (size_t bf = 0; bf < m.bface_cell.size(); ++bf) {
       if (m.bface_id[bf] != bc.pressure_labels[cond]) continue;
       const int64_t c = m.bface_cell[bf]; const int f = m.bface_local[bf], nd = f / 2, side = f % 2;
-      for (int v = 0; v < nv; ++v) if (((v >> nd) & 1) == side) cons.emplace(D.cell_p[c * nv + v], bc.pressure_values[cond]);
+      for (int v = 0; v < nv; ++v) if (((v >> nd) & 1) == side) cons.emplace(D.cell_p[c * nv + v], std::make_pair(bc.pressure_values[cond], bc.pressure_labels[cond]));
     }
-  dofs.clear(); values.clear();
-  for (auto &kv : cons) { dofs.push_back(kv.first); values.push_back(kv.second); }
+  dofs.clear(); values.clear(); if (labels) labels->clear();
+  for (auto &kv : cons) { dofs.push_back(kv.first); values.push_back(kv.second.first); if (labels) labels->push_back(kv.second.second); }
 }
 
 // Everything poro_desc points at, owned in one place.
@@ -421,6 +422,7 @@ struct ProblemData {
   Mesh mesh; DoFs dofs; FETables fe; BoundaryConditions bc;
   std::vector<int32_t> dirichlet_dof; std::vector<double> dirichlet_value;
   std::vector<int32_t> dirichlet_dof_p; std::vector<double> dirichlet_value_p;
+  std::vector<int32_t> dirichlet_label_p;   // per entry of dirichlet_dof_p the boundary label that prescribed it (empty where the list was given by the caller)
   poro_material mat{}; poro_partition part{};
   ConstraintList cons_u, cons_p;      // hanging-node constraints (locally refined meshes)
   // general partition (partition_problem): interface lists and the local -> global maps of the piece
@@ -656,7 +658,7 @@ struct ProblemData {
   // ids no face of the mesh carries go to ids the auxiliary box does not have
   void translate_to_coarse(std::vector<int32_t> &labels) const { for (auto &l : labels) { auto it = coarse_side_of_id.find(l); l = it == coarse_side_of_id.end() ? -1 - l : it->second; } }
   void set_pressure_bc() {
-    if (!dirichlet_given) make_dirichlet_p(mesh, dofs, bc, dirichlet_dof_p, dirichlet_value_p);
+    if (!dirichlet_given) make_dirichlet_p(mesh, dofs, bc, dirichlet_dof_p, dirichlet_value_p, &dirichlet_label_p);
     d.n_dirichlet_p = (int64_t)dirichlet_dof_p.size(); d.dirichlet_dof_p = dirichlet_dof_p.data(); d.dirichlet_value_p = dirichlet_value_p.data();
     // the coarse space of the two-level preconditioner carries the same condition (a refined box's coarse problem has the mesh's own labels, an auxiliary box its own
     // ids): a coarse problem built before the condition was set learns of it here.  Pieces of a partition: their copy of the coarse problem has its lists given

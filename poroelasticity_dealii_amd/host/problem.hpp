@@ -4,6 +4,7 @@
 // forwarding to the C-ABI of include/poroel_hip.h.  deal.II Vector<double> members become handles to
 // device-resident vectors; nothing here computes on the CPU.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <stdexcept>
@@ -241,7 +242,7 @@ template <int dim> class PoroElasticProblem {
   void get_effective_stresses() { check(poro_get_effective_stresses(ctx), "get_effective_stresses"); }   // :189-224
   // :227-291: legacy-VTK file of u, p, strains and stresses, one patch per cell with its 2^dim vertices (build_patches(min degree) = 1
   // subdivision), fields in the reference's order.  2D quirk: the reference writes stresses[0] under the name "sigma_yy" (:257-258).
-  void output_results(unsigned int step, const std::string &dir, bool corrected = false) {
+  void output_results(unsigned int step, const std::string &dir, bool corrected = false, bool darcy = false) {
     const ProblemData &P = *pd; const int nv = 1 << dim, k = P.d.degree_u, n1 = k + 1, ns = P.d.fe.ns_u;
     const int64_t nc = P.d.n_cells, npts = nc * nv;
     std::vector<double> u, p; displacement_solver.solution.get(u, P.d.n_dofs_u); pressure_solver.solution.get(p, P.d.n_dofs_p);
@@ -284,13 +285,58 @@ template <int dim> class PoroElasticProblem {
       scalar("eps_xy", eps[1]); scalar("eps_xz", eps[2]); scalar("eps_yy", eps[3]); scalar("eps_yz", eps[4]); scalar("eps_zz", eps[5]);
       scalar("sigma_xy", sig[1]); scalar("sigma_xz", sig[2]); scalar("sigma_yy", sig[3]); scalar("sigma_yz", sig[4]); scalar("sigma_zz", sig[5]);
     }
+    if (darcy) {                                           // (extension, only on request: the file is otherwise what it was) one Darcy velocity per cell
+      const std::vector<double> q = darcy_velocity();
+      out << "CELL_DATA " << nc << "\nVECTORS darcy_velocity double\n";
+      for (int64_t c = 0; c < nc; ++c) out << q[c * dim] << ' ' << q[c * dim + 1] << ' ' << (dim == 3 ? q[c * dim + 2] : 0.0) << '\n';
+    }
   }
   // the tail of the time loop body (:409-411)
   void postprocess(const RunControls &rc) {
     get_shear_strain_components(rc.corrected_postprocessing);
     get_effective_stresses();
-    if (!rc.output_dir.empty()) output_results((unsigned)time_step_number, rc.output_dir, rc.corrected_postprocessing);
+    if (!rc.output_dir.empty()) output_results((unsigned)time_step_number, rc.output_dir, rc.corrected_postprocessing, flow_controls.darcy_output);
   }
+
+  // ---- flow post-processing (extension; definitions: include/poroel_hip.h) ----
+  // The two switches, set by the command line (poro_run --flow-balance, --darcy-output) and by the Runner's methods.  They live here and not in RunControls, whose
+  // member list is pinned together with poro_host_run_options (tests/run_options_check.cpp).  flow_balance: after every time step the terms of the discrete fluid
+  // balance go into flow_history and, times dt, into flow_totals.  darcy_output: output_results appends CELL_DATA / VECTORS darcy_velocity.  Both off: nothing changes
+  struct FlowControls { bool flow_balance = false, darcy_output = false; } flow_controls;
+  // q_c = -kappa_c (grad p_h(x_c) - rho_f g) of the present pressure, [n_cells][dim]
+  std::vector<double> darcy_velocity() {
+    std::vector<double> q((size_t)pd->d.n_cells * dim);
+    check(poro_pres_darcy_velocity(ctx, PORO_VEC_P, q.data()), "pres_darcy_velocity");
+    return q;
+  }
+  // The terms of the discrete fluid balance of the present state, and per prescribed label (in the order of bc.pressure_labels, every label once) the conservative
+  // outflow - the sum of C^T(-r) over the dofs the label prescribed, ProblemData::dirichlet_label_p - and the face-integrated discharge
+  struct FlowBalance {
+    poro_flow_balance_terms terms{};
+    std::vector<int32_t> labels; std::vector<double> outflow_by_label, discharge_by_label;
+    // what the identity leaves: storage + source + outflow = -free_row_sum up to rounding, and |free_row_sum| <= sqrt(n) residual_l2
+    double imbalance() const { return terms.storage_rate_strain + terms.storage_rate_pressure + terms.source_sum + terms.outflow_prescribed; }
+  };
+  FlowBalance flow_balance(const RunControls &rc) {
+    const ProblemData &P = *pd;
+    FlowBalance B;
+    for (int32_t l : P.bc.pressure_labels) if (std::find(B.labels.begin(), B.labels.end(), l) == B.labels.end()) B.labels.push_back(l);
+    std::vector<double> per_dof((size_t)P.d.n_dirichlet_p);
+    check(poro_pres_flow_balance(ctx, rc.time_step, &B.terms, per_dof.empty() ? nullptr : per_dof.data()), "pres_flow_balance");
+    B.outflow_by_label.assign(B.labels.size(), 0.0); B.discharge_by_label.assign(B.labels.size(), 0.0);
+    if (P.dirichlet_label_p.size() == per_dof.size())
+      for (size_t i = 0; i < per_dof.size(); ++i)
+        for (size_t k = 0; k < B.labels.size(); ++k) if (B.labels[k] == P.dirichlet_label_p[i]) B.outflow_by_label[k] += per_dof[i];
+    if (!B.labels.empty()) check(poro_pres_boundary_discharge(ctx, PORO_VEC_P, nullptr, B.labels.data(), (int32_t)B.labels.size(), B.discharge_by_label.data()), "pres_boundary_discharge");
+    return B;
+  }
+  // time integrals of the terms over the steps taken while flow_controls.flow_balance was set (dt * each term, per step): cumulative storage change, injected volume
+  // (source), drained volume in total and per label.  Reset by initialize, carried across refine_mesh like the work counters
+  struct FlowTotals {
+    int steps = 0; double storage_strain = 0, storage_pressure = 0, source = 0, outflow = 0, free_rows = 0, bound = 0 /* sum of dt sqrt(n) residual_l2 */;
+    std::vector<int32_t> labels; std::vector<double> outflow_by_label, discharge_by_label;
+  } flow_totals;
+  std::vector<FlowBalance> flow_history;                   // one entry per such step (the driver's log)
 
   // work counters of the metric "DoF-updates in assemble + SpMV" (SURVEY 8d): operator applications and assembly passes
   struct Work { int64_t apply_u = 0, apply_p = 0, asm_rhs_u = 0, asm_matrix_u = 0, residual_p = 0, jacobian_p = 0, proj_rhs = 0;
@@ -343,6 +389,7 @@ template <int dim> class PoroElasticProblem {
     get_volumetric_strain();                               // :316
     initial_volumetric_strain = volumetric_strain;         // :317
     time_step_number = 0;
+    flow_totals = FlowTotals(); flow_history.clear();
   }
   // one pass of the time loop body (:328-407); returns the number of trace rows written (= FSS iterations)
   int time_step(const RunControls &rc, double *trace, int max_rows) {
@@ -381,6 +428,7 @@ template <int dim> class PoroElasticProblem {
       pressure_error = pressure_solver.residual_l2;        // :405
       if (rows < max_rows) { double *r = trace + 8 * rows++; r[0] = time_step_number; r[1] = fss_iteration; r[2] = pressure_iteration - 1; r[3] = inner; r[4] = pinf; r[5] = pressure_error; r[6] = displacement_solver.last.iterations; r[7] = pcg; }
     }
+    if (flow_controls.flow_balance) account_flow(rc);
     return rows;
   }
   // device-side snapshot / rollback of the whole solver state (retry or repeat a time step)
@@ -411,6 +459,16 @@ template <int dim> class PoroElasticProblem {
   }
   void normal_strains() {
     get_normal_strain_components(); work.proj_rhs++;
+  }
+  // the balance of the step just taken (the state the step's last residual saw) into flow_history and, times dt, into flow_totals
+  void account_flow(const RunControls &rc) {
+    const FlowBalance B = flow_balance(rc);
+    FlowTotals &T = flow_totals; const double dt = rc.time_step;
+    if (T.labels != B.labels) { T.labels = B.labels; T.outflow_by_label.assign(B.labels.size(), 0.0); T.discharge_by_label.assign(B.labels.size(), 0.0); }
+    T.steps++; T.storage_strain += dt * B.terms.storage_rate_strain; T.storage_pressure += dt * B.terms.storage_rate_pressure; T.source += dt * B.terms.source_sum;
+    T.outflow += dt * B.terms.outflow_prescribed; T.free_rows += dt * B.terms.free_row_sum; T.bound += dt * std::sqrt((double)pd->d.n_dofs_p) * B.terms.residual_l2;
+    for (size_t k = 0; k < B.labels.size(); ++k) { T.outflow_by_label[k] += dt * B.outflow_by_label[k]; T.discharge_by_label[k] += dt * B.discharge_by_label[k]; }
+    flow_history.push_back(B);
   }
   // the problem and its solver members move to another context (refine_mesh); the caller looks after the context left behind
   void rebind(poro_ctx *c) {

@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR] [--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR [--darcy-output]] [--corrected-output] [--flow-balance] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -13,6 +13,10 @@
 // --moduli-layers TOP=YOUNG:POISSON[,TOP=YOUNG:POISSON...] (an extension likewise) sets Young's modulus and Poisson's ratio layer by layer along the slowest direction, the
 // layers chosen by cell centres in the same way; lambda and G follow by the parameter file's formulas.  On a box the displacement operator then runs the general cell loop;
 // --fastest takes the fast diagonalisation (line-solve form) on boxes and Chebyshev elsewhere; the run prints the field's kind and the choice, also after every adapt.
+// --flow-balance (an extension: the reference computes no flow) prints after the log of every step one line with the six terms of the discrete fluid balance
+// (include/poroel_hip.h, poro_pres_flow_balance), the conservative outflow and the face-integrated discharge per prescribed label and the imbalance against its bound
+// sqrt(n) * residual_l2, and at the end the cumulative volumes.  --darcy-output (with --output) appends the Darcy velocity per cell to every VTK file.  Without the two
+// options the log and the files are what they were.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <algorithm>
@@ -29,8 +33,8 @@
 
 using namespace poro_host;
 
-static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR] "
-                                  "[--corrected-output] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
+static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR [--darcy-output]] "
+                                  "[--corrected-output] [--flow-balance] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
                                   "[--gravity GX,GY[,GZ]] [--fluid-density RHO] [--density-layers TOP=RHO[,TOP=RHO...]] [--hydrostatic-init] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
@@ -60,6 +64,7 @@ int main(int argc, char **argv) {
   std::vector<double> tensor_top, tensor_k[3];
   std::vector<double> moduli_top, moduli_young, moduli_poisson;
   std::vector<double> gravity, density_top, density_value; double fluid_density = 0; bool hydrostatic_init = false;
+  bool flow_balance = false, darcy_output = false;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -68,6 +73,8 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--matrix-free")) op = PORO_OP_MATRIX_FREE;
     else if (!std::strcmp(argv[i], "--output") && i + 1 < argc) rc.output_dir = argv[++i];
     else if (!std::strcmp(argv[i], "--corrected-output")) rc.corrected_postprocessing = true;
+    else if (!std::strcmp(argv[i], "--darcy-output")) darcy_output = true;       // with --output: one Darcy velocity per cell appended to every file (CELL_DATA / VECTORS darcy_velocity)
+    else if (!std::strcmp(argv[i], "--flow-balance")) flow_balance = true;       // one line per step with the terms of the discrete fluid balance, the cumulative volumes at the end
     else if (!std::strcmp(argv[i], "--incremental-strain")) rc.incremental_strain = true;   // storage term against the previous step instead of the initial state
     else if (!std::strcmp(argv[i], "--coupled-fss")) rc.coupled_fss = true;    // restore get_volumetric_strain() inside the fixed-stress loop (:399)
     else if (!std::strcmp(argv[i], "--ssor")) rc.preconditioner = PORO_PREC_SSOR;   // the reference's PreconditionSSOR instead of Jacobi
@@ -171,6 +178,7 @@ int main(int argc, char **argv) {
     rc.n_steps = steps >= 0 ? steps : n_steps;
     std::vector<double> trace(8 * (size_t)(1 + rc.n_steps * rc.max_fss_iterations));
     int rows;
+    std::vector<std::string> flow_lines;      // --flow-balance: one line per step, then the totals
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
     static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
     auto go = [&](auto &prob) {
@@ -204,7 +212,27 @@ int main(int argc, char **argv) {
                     << " dofs; pressure preconditioner: " << prec_name[prob.pressure_solver.control.preconditioner] << ", projection preconditioner: "
                     << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
         };
+      prob.flow_controls.flow_balance = flow_balance; prob.flow_controls.darcy_output = darcy_output;
       rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
+      if (flow_balance) {                // (only with the option) the per-step lines, printed with the steps below, and the totals
+        char buf[256];
+        const double sqrt_n = std::sqrt((double)prob.problem()->d.n_dofs_p);
+        for (size_t s = 0; s < prob.flow_history.size(); ++s) {
+          const auto &B = prob.flow_history[s]; const poro_flow_balance_terms &t = B.terms;
+          std::snprintf(buf, sizeof buf, "flow balance step %zu: storage_strain %.9e storage_pressure %.9e source %.9e outflow %.9e free_rows %.9e residual_l2 %.9e;", s + 1,
+                        t.storage_rate_strain, t.storage_rate_pressure, t.source_sum, t.outflow_prescribed, t.free_row_sum, t.residual_l2);
+          std::string line = buf;
+          for (size_t k = 0; k < B.labels.size(); ++k) { std::snprintf(buf, sizeof buf, " label %d outflow %.9e discharge %.9e;", (int)B.labels[k], B.outflow_by_label[k], B.discharge_by_label[k]); line += buf; }
+          std::snprintf(buf, sizeof buf, " imbalance %.3e bound %.3e", B.imbalance(), sqrt_n * t.residual_l2); line += buf;
+          flow_lines.push_back(line);
+        }
+        const auto &T = prob.flow_totals;
+        std::snprintf(buf, sizeof buf, "flow balance totals over %d steps: storage_strain %.9e storage_pressure %.9e injected %.9e drained %.9e;", T.steps, T.storage_strain, T.storage_pressure, -T.source, T.outflow);
+        std::string line = buf;
+        for (size_t k = 0; k < T.labels.size(); ++k) { std::snprintf(buf, sizeof buf, " label %d drained %.9e face-integrated %.9e;", (int)T.labels[k], T.outflow_by_label[k], T.discharge_by_label[k]); line += buf; }
+        std::snprintf(buf, sizeof buf, " imbalance %.3e bound %.3e", T.storage_strain + T.storage_pressure + T.source + T.outflow, T.bound); line += buf;
+        flow_lines.push_back(line);
+      }
       if (rc.fdm_per_direction) {           // (only with the option, so the reference's log stays as it is)
         static const char *const runs[] = {"nodal kernels", "octant form", "per-direction form", "slab form", "planar form"};
         int32_t req = 0, eff = 0, split[3] = {0, 0, 0};
@@ -232,7 +260,10 @@ int main(int argc, char **argv) {
       std::cout << "        pressure converged; iterations: " << (int)t[2] << std::endl;        // :367-369
       std::cout << "Solution limits: " << t[4] << "\t" << std::endl;                             // :387-389
       std::cout << "        Error: " << t[5] << std::endl;                                       // :406
+      const size_t step = (size_t)t[0];           // --flow-balance: the step's line behind its last coupling iteration
+      if (step >= 1 && step + 1 <= flow_lines.size() && (r + 1 == rows || trace[8 * (r + 1)] != t[0])) std::cout << flow_lines[step - 1] << std::endl;
     }
+    if (!flow_lines.empty()) std::cout << flow_lines.back() << std::endl;
   } catch (std::exception &exc) {   // PoroelasticityFSS.h:512-523
     std::cerr << std::endl << "----------------------------------------------------" << std::endl
               << "Exception on processing: " << std::endl << exc.what() << std::endl << "Aborting!" << std::endl
