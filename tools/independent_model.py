@@ -6,7 +6,11 @@ Where the oracle (and the reference) loop over cells and quadrature points, this
   projection right-hand sides r_cc = G_c^T u_c,  well source = the reference's QGauss(2) quadrature of the cylinder indicator (right_hand_side.h:99-116),
 and solves every sub-problem with a sparse DIRECT solver.  It then walks PoroElasticProblem<dim>::run() (PoroelasticityFSS.h:308-407, quirks Q1 / Q2 / Q7).
 Used to generate tests/golden/independent_traces.json (python tools/independent_model.py --write), against which both the oracle (CPU suite) and the HIP
-path (GPU suite) are checked: a cross-implementation golden instead of the oracle's own output."""
+path (GPU suite) are checked: a cross-implementation golden instead of the oracle's own output.
+
+This model knows uniform boxes, one k / mu, one (lambda, G), no gravity, no prescribed pressures and no tractions.  tests/step_reference.py is the model of the time step
+with every field on (a cell loop over the descriptor's mesh arrays, any MappingQ1 mesh, hanging nodes, both flavours of the loop and the monolithic Biot system);
+tests/test_step_reference_cpu.py holds it against the goldens written here."""
 import json
 import os
 import sys
