@@ -619,6 +619,57 @@ int  poro_pres_darcy_velocity(poro_ctx *ctx, int which_vec, double *q_host /* [n
 int  poro_pres_boundary_discharge(poro_ctx *ctx, int which_vec, double *Q_face_host /* [n_bfaces] or NULL */, const int32_t *labels, int32_t n_labels, double *Q_label_host /* [n_labels] or NULL */);
 int  poro_pres_flow_balance(poro_ctx *ctx, double time_step, poro_flow_balance_terms *out, double *outflow_dof_host /* [n_dirichlet_p] or NULL */);
 
+/* Cell stresses, failure measures and support reactions (appended entry points, no struct of the existing ABI changes: PORO_ABI_VERSION stays 4).  Pure post-processing,
+ * the mechanical twin of the flow calls above: the calls synchronise (they return host data), leave every PORO_VEC_* vector unchanged, work in both operator modes and on
+ * every single-rank mesh (box-tagged, tensor, refined with hanging nodes, Gmsh; 2D and 3D; Q1 and Q2 displacements).  A partitioned context (n_ranks > 1), a vector of the
+ * wrong space, a friction angle outside [0, pi/2) and a cohesion < 0 return < 0 with a message.  Timer families: "cell_stress", "cell_measures", "force_balance".
+ * THE DEFINITIONS BELOW ARE THIS PROJECT'S (the reference computes none of this); this text is what the tests pin.
+ *   Sign: tension is positive, as in sigma' = C : eps everywhere in the code.
+ *   Packed symmetric order: the one of PORO_VEC_STRAIN0 + e - 2D: xx, xy, yy; 3D: xx, xy, xz, yy, yz, zz.
+ *   lambda_c, G_c = what the context holds for cell c AT THE TIME OF THE CALL: the scalars of poro_material, or the cell's own pair of poro_ctx_set_cell_moduli - never a
+ *   nodal mean (poro_get_effective_stresses multiplies by nodal means and is left as it is).  alpha = mat.biot_alpha.  u_h = the FE_Q(k)^dim function of a
+ *   displacement-space vector, p_h = the Q1 function of a pressure-space vector, x_c = the image of the reference centre (1/2, ..., 1/2) under MappingQ1 - the point of
+ *   poro_pres_darcy_velocity, so the cell data are co-located.
+ * Cell stress (poro_disp_cell_stress):
+ *   eps_c    = sym grad u_h(x_c), from the cell's own dofs and the true J^-1 at the centre (non-affine cells included)
+ *   sigma'_c = lambda_c tr(eps_c) I + 2 G_c eps_c
+ *   sigma_c  = sigma'_c - alpha p_h(x_c) I;   which_p = -1: no pressure, sigma = sigma'
+ *   Each output is [n_cells][n_sym], cells in the descriptor's order, and may be NULL.
+ * Cell measures (poro_disp_cell_measures): from the 3 x 3 EFFECTIVE stress.  In 2D that is plane strain: the in-plane block plus sigma'_zz = lambda_c tr(eps_c), which can
+ *   be the largest, the middle or the smallest principal value.  measures_host[n_cells][6] (may be NULL): s1 >= s2 >= s3 (principal effective stresses), the mean tr / 3,
+ *   von Mises sqrt(3 J2), and the Mohr-Coulomb function f = (s1 - s3) / 2 + (s1 + s3) / 2 * sin(phi) - c * cos(phi); f >= 0: the envelope is reached.
+ *   mc = {cohesion c >= 0, friction angle phi in radians, 0 <= phi < pi/2}; mc = NULL: f = 0 and a summary of zeros.
+ *   summary (may be NULL) = {max_f, argmax_cell, n_failing = the number of cells with f >= 0}, computed on the device in fixed order (per-block partials, finished in one
+ *   block; a tie goes to the lowest cell index; no float atomics: the same bits from call to call).
+ *   which_p must be -1 or a pressure-space vector and is otherwise IGNORED: the measures are those of the effective stress (one signature for both calls).
+ *   The eigenvalues come from a fixed number of cyclic Jacobi sweeps (csrc/stress_measures.hpp): accurate for repeated and nearly repeated principal stresses.
+ * Force balance (poro_disp_force_balance): let b = b_cpl + b_neu + b_body be the three parts of the displacement right-hand side on ALL rows, without Dirichlet masking
+ *   and without lifting: b_cpl,i = alpha int p_h div(phi_i) with the current PORO_VEC_P, b_neu = the Neumann (traction) vector, b_body = the gravity body force or zero;
+ *   r = A_full u - b with A_full the unconstrained operator (the one the lifting is built with) and u = PORO_VEC_U; Rt = C^T r the residual condensed through cons_u
+ *   (hanging nodes, rigid-plate ties) BEFORE the Dirichlet rows are touched.  Per component k < dim (arrays of 3, unused entries 0; the component of a dof is its local
+ *   index s * dim + comp in cell_dofs_u, tabulated once per context):
+ *     reaction_sum[k] = sum of Rt_i over the Dirichlet rows of component k: the force the supports exert on the body.  One addition keeps this complete on meshes whose
+ *                       hanging nodes lie on a supported face: the host provider closes its lists, i.e. a hanging row h whose masters are prescribed no longer names them
+ *                       and its weights sum to less than one.  The share (1 - sum_m w_hm) r_h that those masters' rows would have received is added to the sum of its
+ *                       component (it is exactly 0.0 for every other row and for every tie).  reaction_dof_host cannot attribute it to a dof and leaves it out
+ *     free_row_sum[k] = sum of Rt_i over all other rows of component k
+ *     traction_sum[k] = sum over the component-k rows of b_neu,i;   body_sum[k] = ... of b_body,i;   coupling_sum[k] = ... of b_cpl,i
+ *     residual_l2     = the 2-norm of Rt over the non-Dirichlet rows
+ *   Identity (the shape functions of one component sum to one, so the component-k rows of A_full sum to zero; it holds wherever every constraint row has masters of
+ *   its own component and weights that sum to one - or to less than one only because prescribed masters were eliminated, see reaction_sum - which covers every list the
+ *   host provider builds):
+ *     reaction_sum[k] + free_row_sum[k] = -(traction_sum[k] + body_sum[k] + coupling_sum[k]),
+ *   coupling_sum[k] itself being zero to rounding (it is alpha int p d_k(1)).  |free_row_sum[k]| <= sqrt(n_dofs_u) residual_l2: the supports of a converged step carry
+ *   exactly the applied load.  reaction_dof_host (optional) receives Rt_i for every Dirichlet dof in the order of poro_desc.dirichlet_dof.
+ *   Everything is assembled in scratch: PORO_VEC_RHS_U and every other vector are untouched. */
+typedef struct poro_mohr_coulomb { double cohesion, friction_angle /* radians */; } poro_mohr_coulomb;
+typedef struct poro_failure_summary { double max_f; int64_t argmax_cell, n_failing; } poro_failure_summary;
+typedef struct poro_force_balance_terms { double reaction_sum[3], free_row_sum[3], traction_sum[3], body_sum[3], coupling_sum[3], residual_l2; } poro_force_balance_terms;
+int  poro_disp_cell_stress(poro_ctx *ctx, int which_u, int which_p /* -1: none */, double *strain_host, double *stress_eff_host, double *stress_tot_host /* [n_cells][n_sym] each, or NULL */);
+int  poro_disp_cell_measures(poro_ctx *ctx, int which_u, int which_p /* -1 or a pressure-space vector; ignored */, const poro_mohr_coulomb *mc /* or NULL */,
+                             double *measures_host /* [n_cells][6] or NULL */, poro_failure_summary *summary /* or NULL */);
+int  poro_disp_force_balance(poro_ctx *ctx, poro_force_balance_terms *out, double *reaction_dof_host /* [n_dirichlet] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

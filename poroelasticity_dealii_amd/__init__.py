@@ -97,6 +97,24 @@ class FlowBalanceTerms(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MohrCoulomb(C.Structure):
+    """poro_mohr_coulomb (include/poroel_hip.h): cohesion and friction angle in radians"""
+    _fields_ = [("cohesion", C.c_double), ("friction_angle", C.c_double)]
+
+
+class FailureSummary(C.Structure):
+    """poro_failure_summary (include/poroel_hip.h)"""
+    _fields_ = [("max_f", C.c_double), ("argmax_cell", C.c_int64), ("n_failing", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ForceBalanceTerms(C.Structure):
+    """poro_force_balance_terms (include/poroel_hip.h)"""
+    _fields_ = [(n, C.c_double * 3) for n in ("reaction_sum", "free_row_sum", "traction_sum", "body_sum", "coupling_sum")] + [("residual_l2", C.c_double)]
+
+
 class RunOptions(C.Structure):
     """poro_host_run_options (host/run_controls.hpp), member by member; tests/test_run_options_cpu.py holds the two layouts against each other"""
     _fields_ = [("p_init", C.c_double), ("time_step", C.c_double), ("n_steps", C.c_int32), ("fss_tol", C.c_double), ("pressure_tol", C.c_double),
@@ -133,7 +151,8 @@ HIP_SYMBOLS = [
     "poro_ctx_set_cell_moduli", "poro_ctx_get_cell_moduli",
     "poro_ctx_set_moduli_operator", "poro_ctx_get_moduli_operator",
     "poro_ctx_set_gravity", "poro_ctx_get_gravity", "poro_ctx_set_cell_density", "poro_ctx_get_cell_density", "poro_get_gravity_vectors",
-    "poro_pres_darcy_velocity", "poro_pres_boundary_discharge", "poro_pres_flow_balance"]
+    "poro_pres_darcy_velocity", "poro_pres_boundary_discharge", "poro_pres_flow_balance",
+    "poro_disp_cell_stress", "poro_disp_cell_measures", "poro_disp_force_balance"]
 
 _hip = None
 _host = None
@@ -215,6 +234,9 @@ def load_hip():
         L.poro_pres_darcy_velocity.argtypes = [C.c_void_p, C.c_int, _dp]
         L.poro_pres_boundary_discharge.argtypes = [C.c_void_p, C.c_int, _dp, _ip, C.c_int32, _dp]
         L.poro_pres_flow_balance.argtypes = [C.c_void_p, C.c_double, C.POINTER(FlowBalanceTerms), _dp]
+        L.poro_disp_cell_stress.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
+        L.poro_disp_cell_measures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MohrCoulomb), _dp, C.POINTER(FailureSummary)]
+        L.poro_disp_force_balance.argtypes = [C.c_void_p, C.POINTER(ForceBalanceTerms), _dp]
         _hip = L
     return _hip
 
@@ -301,9 +323,15 @@ def load_host():
         L.poro_host_runner_state.argtypes = [C.c_void_p, C.c_int]
         L.poro_host_runner_postprocess_darcy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
         L.poro_host_runner_track_flow.argtypes = [C.c_void_p, C.c_int]
+        L.poro_host_runner_postprocess_fields.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+        L.poro_host_runner_mohr_coulomb.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        L.poro_host_runner_track_force.argtypes = [C.c_void_p, C.c_int]
+        L.poro_host_runner_force_history.argtypes = [C.c_void_p, C.c_int, _dp]
         L.poro_host_runner_flow_balance.argtypes = [C.c_void_p, _dp, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp]
         L.poro_host_pressure_bc_labels.restype = C.c_int64
         L.poro_host_pressure_bc_labels.argtypes = [C.c_void_p, _ip]
+        L.poro_host_displacement_bc_labels.restype = C.c_int64
+        L.poro_host_displacement_bc_labels.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.restype = None
         L.poro_host_runner_free.argtypes = [C.c_void_p]
@@ -519,6 +547,15 @@ class Problem:
         H = load_host()
         out = np.zeros(H.poro_host_pressure_bc_labels(self.handle, None), dtype=np.int32)
         H.poro_host_pressure_bc_labels(self.handle, out.ctypes.data_as(_ip))
+        return out
+
+    def displacement_bc_labels(self):
+        """[n_dirichlet, 2]: per entry of desc.dirichlet_dof the (boundary label, component) of the displacement condition that prescribed it; where two conditions
+        meet in a dof the first one of the list wins, as for the values.  Empty where the Dirichlet list was given by the caller (pieces of a partition)"""
+        H = load_host()
+        out = np.zeros((H.poro_host_displacement_bc_labels(self.handle, None), 2), dtype=np.int32)
+        if out.size:
+            H.poro_host_displacement_bc_labels(self.handle, out.ctypes.data_as(_ip))
         return out
 
     def _host(self, name, *args):
@@ -897,6 +934,50 @@ class Context:
         self._chk(self.L.poro_pres_flow_balance(self.ptr, float(dt), C.byref(t), out.ctypes.data_as(_dp) if out.size else None))
         return t.as_dict(), out
 
+    def cell_stress(self, which_u=VEC_U, which_p=VEC_P):
+        """(strain, effective, total), [n_cells][n_sym] each: eps_c = sym grad u_h(x_c), sigma'_c = lambda_c tr(eps_c) I + 2 G_c eps_c with the cell's OWN moduli,
+        sigma_c = sigma'_c - alpha p_h(x_c) I at the cell centres; which_p=None (or -1): no pressure, total = effective (definition: include/poroel_hip.h)"""
+        nc, ns = self.problem.desc.n_cells, self.dim * (self.dim + 1) // 2
+        e, se, st = (np.empty((nc, ns)) for _ in range(3))
+        self._chk(self.L.poro_disp_cell_stress(self.ptr, int(which_u), -1 if which_p is None else int(which_p), e.ctypes.data_as(_dp), se.ctypes.data_as(_dp), st.ctypes.data_as(_dp)))
+        return e, se, st
+
+    def cell_measures(self, which_u=VEC_U, which_p=VEC_P, cohesion=None, friction_angle=None):
+        """(measures [n_cells][6], summary): per cell s1 >= s2 >= s3, mean, von Mises and the Mohr-Coulomb function f of the 3 x 3 EFFECTIVE stress (2D: plane strain);
+        summary = {max_f, argmax_cell, n_failing} from the device.  cohesion and friction_angle (radians) both None: f = 0 and a summary of zeros.  which_p is checked
+        and ignored (include/poroel_hip.h)"""
+        if (cohesion is None) != (friction_angle is None):
+            raise ValueError("cell_measures: give both cohesion and friction_angle, or neither")
+        m = np.empty((self.problem.desc.n_cells, 6))
+        mc = None if cohesion is None else MohrCoulomb(float(cohesion), float(friction_angle))
+        summ = FailureSummary()
+        self._chk(self.L.poro_disp_cell_measures(self.ptr, int(which_u), -1 if which_p is None else int(which_p), None if mc is None else C.byref(mc), m.ctypes.data_as(_dp), C.byref(summ)))
+        return m, summ.as_dict()
+
+    def force_balance(self):
+        """The force balance of the displacement system at the present PORO_VEC_U / PORO_VEC_P (include/poroel_hip.h, poro_disp_force_balance): per component the arrays
+        reaction_sum, free_row_sum, traction_sum, body_sum, coupling_sum [dim] and residual_l2; reaction_dof = C^T r on the Dirichlet dofs in the order of
+        desc.dirichlet_dof; reaction_by_label[(label, component)] = its sums over the dofs each displacement condition prescribed (Problem.displacement_bc_labels;
+        empty where the problem has no such record)"""
+        t = ForceBalanceTerms()
+        nd = self.problem.desc.n_dirichlet
+        per_dof = np.empty(nd)
+        self._chk(self.L.poro_disp_force_balance(self.ptr, C.byref(t), per_dof.ctypes.data_as(_dp) if nd else None))
+        res = {n: np.array(getattr(t, n)[:self.dim]) for n in ("reaction_sum", "free_row_sum", "traction_sum", "body_sum", "coupling_sum")}
+        res["residual_l2"] = t.residual_l2
+        res["reaction_dof"] = per_dof
+        by = {}
+        if getattr(self, "_bc_pairs", None) is None:             # (the record belongs to the problem the context was made from: read once)
+            owner = self.problem if hasattr(self.problem, "displacement_bc_labels") else getattr(self.problem, "source", None)      # (a descriptor copy keeps its source's dofs)
+            labels = owner.displacement_bc_labels() if hasattr(owner, "displacement_bc_labels") else np.zeros((0, 2), dtype=np.int32)
+            self._bc_pairs = np.unique(labels, axis=0, return_inverse=True) if len(labels) else (labels, np.zeros(0, dtype=np.int64))
+        pairs, inverse = self._bc_pairs
+        if len(inverse) == nd and nd:
+            sums = np.bincount(np.asarray(inverse).ravel(), weights=per_dof, minlength=len(pairs))      # in the order of the dof list
+            by = {(int(l), int(c)): float(v) for (l, c), v in zip(pairs.tolist(), sums.tolist())}
+        res["reaction_by_label"] = by
+        return res
+
     def transfer_p_from(self, other, rows):
         """VEC_P, VEC_EPSV, VEC_EPSV0 of `other` (the context of the previous mesh) -> this context through rows = (ptr, node, weight), e.g. other.problem.transfer_rows_p(self.problem)"""
         ptr = np.ascontiguousarray(rows[0], dtype=np.int64)
@@ -1155,13 +1236,52 @@ class Runner:
         if self.H.poro_host_runner_state(self.h, 1) != 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
 
-    def postprocess(self, output_dir=None, corrected=False, darcy=False):
+    def postprocess(self, output_dir=None, corrected=False, darcy=False, stress=False, cohesion=None, friction_angle=None):
         """PoroelasticityFSS.h:409-411: shear strains, effective stresses (PORO_VEC_STRESS0+e) and, with a directory, solution-NNNN.vtk; darcy=True appends the Darcy
-        velocity per cell (CELL_DATA / VECTORS darcy_velocity) to the file"""
+        velocity per cell (CELL_DATA / VECTORS darcy_velocity) to the file; stress=True appends behind it the cell stresses and two failure measures (TENSORS
+        effective_stress, TENSORS total_stress, SCALARS mohr_coulomb - with cohesion and friction_angle in radians, 0 without - and SCALARS von_mises)"""
         d = output_dir.encode() if output_dir else None
-        rc = self.H.poro_host_runner_postprocess_darcy(self.h, d, int(corrected), 1) if darcy else self.H.poro_host_runner_postprocess(self.h, d, int(corrected))
+        if stress:
+            if (cohesion is None) != (friction_angle is None):
+                raise ValueError("postprocess: give both cohesion and friction_angle, or neither")
+            rc = self.H.poro_host_runner_mohr_coulomb(self.h, int(cohesion is not None), float(cohesion or 0.0), float(friction_angle or 0.0))
+            if rc == 0:
+                rc = self.H.poro_host_runner_postprocess_fields(self.h, d, int(corrected), int(darcy), 1)
+        else:
+            rc = self.H.poro_host_runner_postprocess_darcy(self.h, d, int(corrected), 1) if darcy else self.H.poro_host_runner_postprocess(self.h, d, int(corrected))
         if rc < 0:
             raise RuntimeError(self.H.poro_host_last_error().decode())
+
+    def cell_stress(self):
+        """(strain, effective, total) per cell of the present state (Context.cell_stress)"""
+        return self.ctx.cell_stress()
+
+    def cell_measures(self, cohesion=None, friction_angle=None):
+        """(measures [n_cells][6], summary) of the present effective stress (Context.cell_measures)"""
+        return self.ctx.cell_measures(cohesion=cohesion, friction_angle=friction_angle)
+
+    def track_force_balance(self, on=True):
+        """while on, every step() appends its force balance to the records force_balance() returns under `history`; initialize() clears them"""
+        if self.H.poro_host_runner_track_force(self.h, int(bool(on))) != 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
+
+    def force_balance(self):
+        """The force balance of the present state (Context.force_balance: the terms per component, reaction_dof, reaction_by_label[(label, component)]) and `history`:
+        one dict of the terms per step taken since track_force_balance()"""
+        res = self.ctx.force_balance()
+        n = self.H.poro_host_runner_force_history(self.h, 0, None)
+        if n < 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
+        dim, hist = self.ctx.dim, []
+        for s in range(n):
+            t = np.zeros(16)
+            if self.H.poro_host_runner_force_history(self.h, s, t.ctypes.data_as(_dp)) < 0:
+                raise RuntimeError(self.H.poro_host_last_error().decode())
+            rec = {name: t[3 * i:3 * i + dim].copy() for i, name in enumerate(("reaction_sum", "free_row_sum", "traction_sum", "body_sum", "coupling_sum"))}
+            rec["residual_l2"] = float(t[15])
+            hist.append(rec)
+        res["history"] = hist
+        return res
 
     def darcy_velocity(self):
         """q_c = -kappa_c (grad p_h(x_c) - rho_f g) of the present pressure, [n_cells][dim] (Context.darcy_velocity)"""

@@ -354,6 +354,11 @@ struct poro_ctx {
   // storage term, rt = C^T(-r), out = rt on the prescribed dofs), m = the lumped pressure mass M 1 (built once), pdir_dof = the prescribed dofs in the descriptor's order
   struct Flux { bool built = false; poro::DevBuf<double> q, Qf, Ql, m, t, rt, out, sums; poro::DevBuf<int32_t> labels, pdir_dof; } flux;
   std::vector<int32_t> h_pdir_dof;   // poro_desc.dirichlet_dof_p as given
+  // Mechanical post-processing (ctx_stress.hip, kernels_stress.hip), allocated at the first call of each kind: strain / eff / tot [n_cells][n_sym], measures [n_cells][6];
+  // the scratch of the force balance (au = A_full u, then Rt; cpl, neu = the coupling and traction vectors on all rows; zero_u / zero_mask = what the box kernel of the
+  // coupling takes for lifting, loads and mask; out = Rt on the Dirichlet dofs), comp = the component of every displacement dof (built once)
+  struct Stress { bool cells_built = false, balance_built = false; poro::DevBuf<double> strain, eff, tot, measures, summary, partials, au, cpl, neu, zero_u, out, sums;
+                  poro::DevBuf<uint8_t> comp, zero_mask; } stress;
 };
 
 namespace poro {
@@ -456,6 +461,22 @@ void darcy_label_sums(hipStream_t s, int64_t n_bfaces, const int32_t *bface_id, 
 struct FlowBalanceArgs { int64_t n; const double *p, *p_old, *ev, *ev0, *m, *src, *Rt; const uint8_t *pdir_mask; double c_strain, c_pres; };
 void flow_balance_partials(hipStream_t s, const FlowBalanceArgs &A, double *partials /* [6][kMaxPartials] */);
 void darcy_gather(hipStream_t s, int64_t n, const int32_t *idx, const double *src, double *dst);   // dst[i] = src[idx[i]]
+
+// ---- kernels_stress.hip: cell strains and stresses, failure measures, force balance ----
+// cell_mod: [n_cells][2] = (lambda, G) or null: lam, G; p null: no pressure (total = effective)
+struct StressArgs { int dim, k_u; int64_t n_cells; const double *cell_X; const int32_t *cell_dofs_u, *cell_dofs_p; const double *u, *p; double lam, G, alpha; const double *cell_mod; };
+void stress_cells(hipStream_t s, const StressArgs &a, double *strain, double *eff, double *tot /* [n_cells][n_sym] each */);
+// measures[n_cells][6] from strain / eff as stress_cells left them; with_mc: also summary[3] = max f, its lowest cell, the number of cells with f >= 0 (through `partials`, 3 slabs)
+void stress_measures_cells(hipStream_t s, int dim, int64_t n_cells, const double *strain, const double *eff, double lam0, const double *cell_mod, bool with_mc, double sin_phi,
+                           double c_cos_phi, double *measures, double *partials, double *summary);
+void dof_components(hipStream_t s, int64_t n_entries, int dim, const int32_t *cell_dofs_u, uint8_t *comp /* [n_u] */);
+void force_residual(hipStream_t s, int64_t n, const double *Au, const double *cpl, const double *neu, const double *body /* nullable */, double *r);   // r = A u - (cpl + neu + body)
+// sums over the n displacement dofs, one slab of kMaxPartials block partials each: 5 k + {0 Rt on the Dirichlet rows, 1 Rt on the other rows, 2 neu, 3 body (nullable), 4 cpl} of
+// component k = comp[i], then 5 dim: Rt^2 on the non-Dirichlet rows
+// out[k < dim] = sum over the constraint rows h of component k of (1 - sum of the row's weights) r_h (r BEFORE la_cons_reduce); one block, fixed order
+void force_deficit(hipStream_t s, int dim, const ConsDev &C, const double *r, const uint8_t *comp, double *out /* [dim] */);
+struct ForceBalanceArgs { int64_t n; const uint8_t *comp, *dir_mask; const double *Rt, *neu, *body, *cpl; };
+void force_balance_partials(hipStream_t s, int dim, const ForceBalanceArgs &A, double *partials /* [5 dim + 1][kMaxPartials] */);
 
 // ---- kernels_asm.hip ----------------------------------------------------------------------------
 struct AsmArgs {

@@ -236,6 +236,13 @@ int64_t poro_host_pressure_bc_labels(void *h, int32_t *out) {
   if (out && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
   return (int64_t)v.size();
 }
+// per entry of poro_desc.dirichlet_dof the (boundary label, component) of the displacement condition that prescribed it (first condition in list order), two entries per
+// dof; returns the number of dofs, copies when out != NULL.  0 where the list was given by the caller (pieces of a partition)
+int64_t poro_host_displacement_bc_labels(void *h, int32_t *out) {
+  const auto &v = static_cast<ProblemData *>(h)->dirichlet_label_u;
+  if (out && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
+  return (int64_t)(v.size() / 2);
+}
 // extension: rigid frictionless plates - component `components[i]` of the displacement takes ONE (unknown) value on the boundary `labels[i]` (before the context is created)
 int poro_host_tie_boundary(void *h, int n, const int32_t *labels, const int32_t *components) {
   try {
@@ -399,6 +406,36 @@ int poro_host_runner_postprocess_darcy(void *r, const char *output_dir, int corr
     const bool was = prob.flow_controls.darcy_output; prob.flow_controls.darcy_output = darcy != 0;
     try { prob.postprocess(rc); } catch (...) { prob.flow_controls.darcy_output = was; throw; }
     prob.flow_controls.darcy_output = was; });
+}
+// the same with the switches of both post-processing families: darcy != 0 appends the Darcy velocity, stress != 0 behind it the cell stresses (CELL_DATA / TENSORS
+// effective_stress, TENSORS total_stress, SCALARS mohr_coulomb, SCALARS von_mises; the criterion of poro_host_runner_mohr_coulomb, f = 0 without one)
+int poro_host_runner_postprocess_fields(void *r, const char *output_dir, int corrected, int darcy, int stress) {
+  return try_on_runner(r, [&](auto &prob, RunControls rc) { rc.output_dir = output_dir ? output_dir : ""; rc.corrected_postprocessing = corrected != 0;
+    const bool was_d = prob.flow_controls.darcy_output, was_s = prob.stress_controls.stress_output;
+    prob.flow_controls.darcy_output = darcy != 0; prob.stress_controls.stress_output = stress != 0;
+    try { prob.postprocess(rc); } catch (...) { prob.flow_controls.darcy_output = was_d; prob.stress_controls.stress_output = was_s; throw; }
+    prob.flow_controls.darcy_output = was_d; prob.stress_controls.stress_output = was_s; });
+}
+// Mechanical accounting (PoroElasticProblem::force_balance / force_history).  poro_host_runner_mohr_coulomb: the criterion of the runner's measures (on = 0: none).
+// poro_host_runner_track_force: while on, every step appends its force balance to the history (initialize clears it).  poro_host_runner_force_history: record s of the
+// history as 16 doubles in the order of poro_force_balance_terms (out may be NULL); returns the number of records, < 0 on error
+int poro_host_runner_mohr_coulomb(void *r, int on, double cohesion, double friction_angle) {
+  return try_on_runner(r, [&](auto &prob, const RunControls &) { prob.stress_controls.mohr_coulomb = on != 0; prob.stress_controls.cohesion = cohesion; prob.stress_controls.friction_angle = friction_angle; });
+}
+int poro_host_runner_track_force(void *r, int on) { return try_on_runner(r, [&](auto &prob, const RunControls &) { prob.stress_controls.force_balance = on != 0; }); }
+int poro_host_runner_force_history(void *r, int s, double *out) {
+  try {
+    return on_runner(r, [&](auto &prob, const RunControls &) {
+      const int n = (int)prob.force_history.size();
+      if (out) {
+        if (s < 0 || s >= n) throw std::runtime_error("runner_force_history: no such record");
+        const poro_force_balance_terms &t = prob.force_history[s].terms;
+        for (int k = 0; k < 3; ++k) { out[k] = t.reaction_sum[k]; out[3 + k] = t.free_row_sum[k]; out[6 + k] = t.traction_sum[k]; out[9 + k] = t.body_sum[k]; out[12 + k] = t.coupling_sum[k]; }
+        out[15] = t.residual_l2;
+      }
+      return n;
+    });
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 // Flow accounting (PoroElasticProblem::flow_balance / flow_totals).  poro_host_runner_track_flow: flow_controls.flow_balance of the runner's problem - while on, every step adds dt * its
 // terms to the totals.  poro_host_runner_flow_balance: the balance of the PRESENT state (nothing is accumulated by the call): terms[6] in the order of

@@ -224,10 +224,13 @@ struct BoundaryConditions {  // BoundaryConditions.h:6-62
 // VectorTools::interpolate_boundary_values(label, ConstantFunction(value), constraints, mask[component])
 // in the order of the conditions; an already constrained dof keeps its first value
 // (PoroElasticDisplacementSolver.h:117-136).
+// labels (optional): for every listed dof the (label, component) pair of the condition that prescribed it, two entries per dof - the first condition in list order,
+// as for the values
 inline void make_dirichlet(const Mesh &m, const DoFs &D, const BoundaryConditions &bc,
-                           std::vector<int32_t> &dofs, std::vector<double> &values) {
+                           std::vector<int32_t> &dofs, std::vector<double> &values, std::vector<int32_t> *labels = nullptr) {
   const int dim = m.dim, n1 = D.k_u + 1, ns = ipow(n1, dim);
   std::map<int32_t, double> cons;
+  std::map<int32_t, std::pair<int32_t, int32_t>> who;
   for (size_t cond = 0; cond < bc.dirichlet_labels.size(); ++cond) {
     const int comp = bc.dirichlet_components[cond];
     for (size_t bf = 0; bf < m.bface_cell.size(); ++bf) {
@@ -239,11 +242,12 @@ inline void make_dirichlet(const Mesh &m, const DoFs &D, const BoundaryCondition
         if (idx[nd] != side * D.k_u) continue;
         const int32_t dof = D.cell_u[(c * ns + s) * dim + comp];
         cons.emplace(dof, bc.dirichlet_values[cond]);
+        if (labels) who.emplace(dof, std::make_pair(bc.dirichlet_labels[cond], (int32_t)comp));
       }
     }
   }
-  dofs.clear(); values.clear();
-  for (auto &kv : cons) { dofs.push_back(kv.first); values.push_back(kv.second); }
+  dofs.clear(); values.clear(); if (labels) labels->clear();
+  for (auto &kv : cons) { dofs.push_back(kv.first); values.push_back(kv.second); if (labels) { const auto &w = who.at(kv.first); labels->push_back(w.first); labels->push_back(w.second); } }
 }
 
 // ---- locally refined box: hanging nodes ---------------------------------------------------------------------------------------------
@@ -422,6 +426,7 @@ struct ProblemData {
   Mesh mesh; DoFs dofs; FETables fe; BoundaryConditions bc;
   std::vector<int32_t> dirichlet_dof; std::vector<double> dirichlet_value;
   std::vector<int32_t> dirichlet_dof_p; std::vector<double> dirichlet_value_p;
+  std::vector<int32_t> dirichlet_label_u;   // per entry of dirichlet_dof the (label, component) that prescribed it, two entries each (empty where the list was given by the caller)
   std::vector<int32_t> dirichlet_label_p;   // per entry of dirichlet_dof_p the boundary label that prescribed it (empty where the list was given by the caller)
   poro_material mat{}; poro_partition part{};
   ConstraintList cons_u, cons_p;      // hanging-node constraints (locally refined meshes)
@@ -606,8 +611,11 @@ struct ProblemData {
       out.inhom.push_back(b); out.ptr.push_back((int64_t)out.master.size());
     }
     cons_u = out;
-    dirichlet_dof.clear(); dirichlet_value.clear();
-    for (auto &kv : dir) { dirichlet_dof.push_back(kv.first); dirichlet_value.push_back(kv.second); }
+    std::map<int32_t, std::pair<int32_t, int32_t>> who;        // (the labels follow the dofs that stay in the list)
+    if (dirichlet_label_u.size() == 2 * dirichlet_dof.size()) for (size_t i = 0; i < dirichlet_dof.size(); ++i) who[dirichlet_dof[i]] = {dirichlet_label_u[2 * i], dirichlet_label_u[2 * i + 1]};
+    dirichlet_dof.clear(); dirichlet_value.clear(); dirichlet_label_u.clear();
+    for (auto &kv : dir) { dirichlet_dof.push_back(kv.first); dirichlet_value.push_back(kv.second);
+                           if (!who.empty()) { const auto &w = who.at(kv.first); dirichlet_label_u.push_back(w.first); dirichlet_label_u.push_back(w.second); } }
   }
   // extension: rigid-plate conditions.  All dofs of component comp on the faces labelled `label` that carry no boundary value are tied to the first of them
   // (an ordinary entry of the constraint list: x[dof] = 1 * x[master]); the tractions of the tied rows then add up on the master (C^T b)
@@ -631,7 +639,7 @@ struct ProblemData {
   void finalize(int k_u, bool have_dofs = false) {
     if (!have_dofs) dofs = distribute_dofs(mesh, k_u);
     fe.build(mesh.dim, k_u);
-    if (!dirichlet_given) make_dirichlet(mesh, dofs, bc, dirichlet_dof, dirichlet_value);
+    if (!dirichlet_given) make_dirichlet(mesh, dofs, bc, dirichlet_dof, dirichlet_value, &dirichlet_label_u);
     if (!ties_added && !bc.tie_labels.empty()) { add_ties(); ties_added = true; }
     close_constraints();
     d = poro_desc{};

@@ -242,7 +242,7 @@ template <int dim> class PoroElasticProblem {
   void get_effective_stresses() { check(poro_get_effective_stresses(ctx), "get_effective_stresses"); }   // :189-224
   // :227-291: legacy-VTK file of u, p, strains and stresses, one patch per cell with its 2^dim vertices (build_patches(min degree) = 1
   // subdivision), fields in the reference's order.  2D quirk: the reference writes stresses[0] under the name "sigma_yy" (:257-258).
-  void output_results(unsigned int step, const std::string &dir, bool corrected = false, bool darcy = false) {
+  void output_results(unsigned int step, const std::string &dir, bool corrected = false, bool darcy = false, bool stress = false) {
     const ProblemData &P = *pd; const int nv = 1 << dim, k = P.d.degree_u, n1 = k + 1, ns = P.d.fe.ns_u;
     const int64_t nc = P.d.n_cells, npts = nc * nv;
     std::vector<double> u, p; displacement_solver.solution.get(u, P.d.n_dofs_u); pressure_solver.solution.get(p, P.d.n_dofs_p);
@@ -290,12 +290,29 @@ template <int dim> class PoroElasticProblem {
       out << "CELL_DATA " << nc << "\nVECTORS darcy_velocity double\n";
       for (int64_t c = 0; c < nc; ++c) out << q[c * dim] << ' ' << q[c * dim + 1] << ' ' << (dim == 3 ? q[c * dim + 2] : 0.0) << '\n';
     }
+    if (stress) {                                          // (extension, only on request, after whatever `darcy` appends) the cell stresses and two failure measures
+      const CellStress S = cell_stress();
+      const CellMeasures M = cell_measures();
+      if (!darcy) out << "CELL_DATA " << nc << '\n';
+      static const int at2[3][3] = {{0, 1, -1}, {1, 2, -1}, {-1, -1, -1}}, at3[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};   // packed index of entry (a, b)
+      auto tensors = [&](const char *nm, const std::vector<double> &t) {
+        out << "TENSORS " << nm << " double\n";
+        for (int64_t c = 0; c < nc; ++c) { for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) { const int e = dim == 2 ? at2[a][b] : at3[a][b]; out << (e < 0 ? 0.0 : t[(size_t)c * n_sym + e]) << (b < 2 ? ' ' : '\n'); } } out << '\n'; }
+      };
+      tensors("effective_stress", S.effective); tensors("total_stress", S.total);
+      auto cells = [&](const char *nm, int col) {
+        out << "SCALARS " << nm << " double 1\nLOOKUP_TABLE default\n";
+        for (int64_t c = 0; c < nc; ++c) out << M.values[(size_t)c * 6 + col] << ' ';
+        out << '\n';
+      };
+      cells("mohr_coulomb", 5); cells("von_mises", 4);
+    }
   }
   // the tail of the time loop body (:409-411)
   void postprocess(const RunControls &rc) {
     get_shear_strain_components(rc.corrected_postprocessing);
     get_effective_stresses();
-    if (!rc.output_dir.empty()) output_results((unsigned)time_step_number, rc.output_dir, rc.corrected_postprocessing, flow_controls.darcy_output);
+    if (!rc.output_dir.empty()) output_results((unsigned)time_step_number, rc.output_dir, rc.corrected_postprocessing, flow_controls.darcy_output, stress_controls.stress_output);
   }
 
   // ---- flow post-processing (extension; definitions: include/poroel_hip.h) ----
@@ -337,6 +354,53 @@ template <int dim> class PoroElasticProblem {
     std::vector<int32_t> labels; std::vector<double> outflow_by_label, discharge_by_label;
   } flow_totals;
   std::vector<FlowBalance> flow_history;                   // one entry per such step (the driver's log)
+
+  // ---- mechanical post-processing (extension; definitions: include/poroel_hip.h) ----
+  // The switches, set by the command line (poro_run --stress-output, --mohr-coulomb, --force-balance) and by the Runner's methods; here and not in RunControls for the
+  // reason given at FlowControls.  stress_output: output_results appends the cell stresses and two failure measures.  mohr_coulomb: the criterion of cell_measures
+  // (off: f = 0).  force_balance / failure_log: after every time step the force balance / the failure summary goes into force_history / failure_history.  All off:
+  // nothing changes
+  struct StressControls { bool stress_output = false, force_balance = false, failure_log = false, mohr_coulomb = false; double cohesion = 0, friction_angle = 0; } stress_controls;
+  struct CellStress { std::vector<double> strain, effective, total; };       // [n_cells][n_sym] each
+  CellStress cell_stress() {
+    const size_t n = (size_t)pd->d.n_cells * (dim * (dim + 1) / 2);
+    CellStress S; S.strain.resize(n); S.effective.resize(n); S.total.resize(n);
+    check(poro_disp_cell_stress(ctx, PORO_VEC_U, PORO_VEC_P, S.strain.data(), S.effective.data(), S.total.data()), "disp_cell_stress");
+    return S;
+  }
+  struct CellMeasures { std::vector<double> values; poro_failure_summary summary{}; };   // [n_cells][6]
+  CellMeasures cell_measures() {
+    CellMeasures M; M.values.resize((size_t)pd->d.n_cells * 6);
+    const poro_mohr_coulomb mc{stress_controls.cohesion, stress_controls.friction_angle};
+    check(poro_disp_cell_measures(ctx, PORO_VEC_U, -1, stress_controls.mohr_coulomb ? &mc : nullptr, M.values.data(), &M.summary), "disp_cell_measures");
+    return M;
+  }
+  // The force balance of the present state and, per displacement condition (label, component) in the order of the conditions, every pair once, the reaction: the sum of
+  // C^T r over the dofs the condition prescribed (ProblemData::dirichlet_label_u)
+  struct ForceBalance {
+    poro_force_balance_terms terms{};
+    std::vector<int32_t> labels, components; std::vector<double> reaction_by_label;
+    // what the identity leaves per component: reaction + traction + body + coupling = -free_row_sum up to rounding, and |free_row_sum| <= sqrt(n) residual_l2
+    double imbalance(int k) const { return terms.reaction_sum[k] + terms.traction_sum[k] + terms.body_sum[k] + terms.coupling_sum[k]; }
+  };
+  ForceBalance force_balance() {
+    const ProblemData &P = *pd;
+    ForceBalance B;
+    for (size_t i = 0; i < P.bc.dirichlet_labels.size(); ++i) {
+      bool seen = false;
+      for (size_t k = 0; k < B.labels.size(); ++k) seen = seen || (B.labels[k] == P.bc.dirichlet_labels[i] && B.components[k] == P.bc.dirichlet_components[i]);
+      if (!seen) { B.labels.push_back(P.bc.dirichlet_labels[i]); B.components.push_back(P.bc.dirichlet_components[i]); }
+    }
+    std::vector<double> per_dof((size_t)P.d.n_dirichlet);
+    check(poro_disp_force_balance(ctx, &B.terms, per_dof.empty() ? nullptr : per_dof.data()), "disp_force_balance");
+    B.reaction_by_label.assign(B.labels.size(), 0.0);
+    if (P.dirichlet_label_u.size() == 2 * per_dof.size())
+      for (size_t i = 0; i < per_dof.size(); ++i)
+        for (size_t k = 0; k < B.labels.size(); ++k) if (B.labels[k] == P.dirichlet_label_u[2 * i] && B.components[k] == P.dirichlet_label_u[2 * i + 1]) B.reaction_by_label[k] += per_dof[i];
+    return B;
+  }
+  std::vector<ForceBalance> force_history;                 // one entry per step taken while stress_controls.force_balance was set; reset by initialize
+  std::vector<poro_failure_summary> failure_history;       // likewise for stress_controls.failure_log
 
   // work counters of the metric "DoF-updates in assemble + SpMV" (SURVEY 8d): operator applications and assembly passes
   struct Work { int64_t apply_u = 0, apply_p = 0, asm_rhs_u = 0, asm_matrix_u = 0, residual_p = 0, jacobian_p = 0, proj_rhs = 0;
@@ -389,7 +453,7 @@ template <int dim> class PoroElasticProblem {
     get_volumetric_strain();                               // :316
     initial_volumetric_strain = volumetric_strain;         // :317
     time_step_number = 0;
-    flow_totals = FlowTotals(); flow_history.clear();
+    flow_totals = FlowTotals(); flow_history.clear(); force_history.clear(); failure_history.clear();
   }
   // one pass of the time loop body (:328-407); returns the number of trace rows written (= FSS iterations)
   int time_step(const RunControls &rc, double *trace, int max_rows) {
@@ -429,6 +493,8 @@ template <int dim> class PoroElasticProblem {
       if (rows < max_rows) { double *r = trace + 8 * rows++; r[0] = time_step_number; r[1] = fss_iteration; r[2] = pressure_iteration - 1; r[3] = inner; r[4] = pinf; r[5] = pressure_error; r[6] = displacement_solver.last.iterations; r[7] = pcg; }
     }
     if (flow_controls.flow_balance) account_flow(rc);
+    if (stress_controls.force_balance) force_history.push_back(force_balance());
+    if (stress_controls.failure_log) failure_history.push_back(cell_measures().summary);
     return rows;
   }
   // device-side snapshot / rollback of the whole solver state (retry or repeat a time step)

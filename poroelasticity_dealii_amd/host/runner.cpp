@@ -1,4 +1,4 @@
-// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR [--darcy-output]] [--corrected-output] [--flow-balance] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
+// Driver executable: `poro_run input.data [--mesh domain.msh] [--degree 1|2] [--matrix-free] [--ssor | --chebyshev | --block-fdm] [--steps N] [--output DIR [--darcy-output] [--stress-output]] [--corrected-output] [--flow-balance] [--force-balance] [--mohr-coulomb COHESION,FRICTION_DEG] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] [--refine-every N [--refine-fraction f] [--coarsen-fraction f]]`.
 // Stands in for the reference's missing code/source/Runner.cpp (code/CMakeLists.txt:8): argv[1] is the
 // parameter file (parse_command_line.h:5-27); the mesh is create_mesh()'s colorized box refined
 // `Initial refinement level` times (PoroelasticityFSS.h:418-435) unless --mesh names a Gmsh file
@@ -17,6 +17,10 @@
 // (include/poroel_hip.h, poro_pres_flow_balance), the conservative outflow and the face-integrated discharge per prescribed label and the imbalance against its bound
 // sqrt(n) * residual_l2, and at the end the cumulative volumes.  --darcy-output (with --output) appends the Darcy velocity per cell to every VTK file.  Without the two
 // options the log and the files are what they were.
+// --stress-output (with --output; an extension likewise) appends to every VTK file, behind what --darcy-output appends, the effective and the total stress per cell and the
+// Mohr-Coulomb function and von Mises stress (include/poroel_hip.h, poro_disp_cell_stress / poro_disp_cell_measures).  --mohr-coulomb COHESION,FRICTION_DEG sets the
+// criterion (without it f = 0) and prints after every step's log max f, its cell and the number of failing cells.  --force-balance prints after every step's log one line
+// with the reaction per displacement condition, per component the reaction, the applied loads and the closure against its bound sqrt(n) * residual_l2.
 // --refine-every N adapts the mesh every N-th step like refine_mesh (:333-340, :447-498; the reference hard-wires N = 5) on the box with ONE level of refinement
 // (the analogue of `Max refinement level = 1`): the box is then built as a refined box with an empty mask, i.e. as a general mesh with the two-level coarse space.
 #include <algorithm>
@@ -33,8 +37,8 @@
 
 using namespace poro_host;
 
-static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR [--darcy-output]] "
-                                  "[--corrected-output] [--flow-balance] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
+static const char *const kUsage = "usage: poro_run input.data [--mesh domain.msh] [--degree 1|2] [--device N] [--matrix-free] [--ssor | --chebyshev | --block-fdm | --two-level | --fastest] [--steps N] [--output DIR [--darcy-output] [--stress-output]] "
+                                  "[--corrected-output] [--flow-balance] [--force-balance] [--mohr-coulomb COHESION,FRICTION_DEG] [--coupled-fss] [--incremental-strain] [--pressure-bc LABEL=VALUE ...] [--permeability-layers TOP=VALUE[,TOP=VALUE...]] [--permeability-tensor-layers TOP=KX:KY[:KZ][,...]] [--moduli-layers TOP=YOUNG:POISSON[,...]] [--atomic-scatter] [--hybrid-operator] [--fdm-fp32] [--fdm-per-direction] [--moduli-structured] "
                                   "[--gravity GX,GY[,GZ]] [--fluid-density RHO] [--density-layers TOP=RHO[,TOP=RHO...]] [--hydrostatic-init] "
                                   "[--refine-every N [--refine-fraction f] [--coarsen-fraction f]]";
 
@@ -65,6 +69,7 @@ int main(int argc, char **argv) {
   std::vector<double> moduli_top, moduli_young, moduli_poisson;
   std::vector<double> gravity, density_top, density_value; double fluid_density = 0; bool hydrostatic_init = false;
   bool flow_balance = false, darcy_output = false;
+  bool force_balance = false, stress_output = false, mohr_coulomb = false; double mc_cohesion = 0, mc_friction_deg = 0;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
     else if (!std::strcmp(argv[i], "--degree") && i + 1 < argc) degree = std::atoi(argv[++i]);
@@ -74,6 +79,16 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--output") && i + 1 < argc) rc.output_dir = argv[++i];
     else if (!std::strcmp(argv[i], "--corrected-output")) rc.corrected_postprocessing = true;
     else if (!std::strcmp(argv[i], "--darcy-output")) darcy_output = true;       // with --output: one Darcy velocity per cell appended to every file (CELL_DATA / VECTORS darcy_velocity)
+    else if (!std::strcmp(argv[i], "--stress-output")) stress_output = true;     // with --output: effective / total stress, Mohr-Coulomb function and von Mises stress per cell appended to every file
+    else if (!std::strcmp(argv[i], "--force-balance")) force_balance = true;     // one line per step with the support reactions, the loads and the closure
+    else if (!std::strcmp(argv[i], "--mohr-coulomb") && i + 1 < argc) {          // COHESION,FRICTION_DEG: the criterion of the failure measure; one line per step with max f, its cell, the failing cells
+      const char *arg = argv[++i], *comma = std::strchr(arg, ','); char *end = nullptr, *end2 = nullptr;
+      mc_cohesion = std::strtod(arg, &end); mc_friction_deg = comma ? std::strtod(comma + 1, &end2) : 0.0;
+      if (!comma || end != comma || comma == arg || !end2 || end2 == comma + 1 || *end2 || !(mc_cohesion >= 0) || !(mc_friction_deg >= 0 && mc_friction_deg < 90)) {
+        std::cerr << "--mohr-coulomb needs COHESION,FRICTION_DEG with COHESION >= 0 and 0 <= FRICTION_DEG < 90, got " << arg << std::endl; return 1;
+      }
+      mohr_coulomb = true;
+    }
     else if (!std::strcmp(argv[i], "--flow-balance")) flow_balance = true;       // one line per step with the terms of the discrete fluid balance, the cumulative volumes at the end
     else if (!std::strcmp(argv[i], "--incremental-strain")) rc.incremental_strain = true;   // storage term against the previous step instead of the initial state
     else if (!std::strcmp(argv[i], "--coupled-fss")) rc.coupled_fss = true;    // restore get_volumetric_strain() inside the fixed-stress loop (:399)
@@ -179,6 +194,7 @@ int main(int argc, char **argv) {
     std::vector<double> trace(8 * (size_t)(1 + rc.n_steps * rc.max_fss_iterations));
     int rows;
     std::vector<std::string> flow_lines;      // --flow-balance: one line per step, then the totals
+    std::vector<std::string> force_lines, failure_lines;   // --force-balance, --mohr-coulomb: one line per step
     std::cout << "starting time loop" << std::endl << "time max " << data.t_max << std::endl;   // :325-326
     static const char *const prec_name[] = {"none", "Jacobi", "SSOR", "FDM", "ILU0", "Chebyshev", "two-level"};
     auto go = [&](auto &prob) {
@@ -213,7 +229,34 @@ int main(int argc, char **argv) {
                     << prec_name[prob.strain_projector.control.preconditioner] << std::endl;
         };
       prob.flow_controls.flow_balance = flow_balance; prob.flow_controls.darcy_output = darcy_output;
+      prob.stress_controls.stress_output = stress_output; prob.stress_controls.force_balance = force_balance; prob.stress_controls.failure_log = mohr_coulomb;
+      prob.stress_controls.mohr_coulomb = mohr_coulomb; prob.stress_controls.cohesion = mc_cohesion; prob.stress_controls.friction_angle = mc_friction_deg * 3.14159265358979323846 / 180.0;
       rows = prob.run(rc, trace.data(), (int)trace.size() / 8);
+      if (force_balance) {               // (only with the option)
+        char buf[256];
+        const int dm = prob.problem()->d.dim; const double sqrt_n = std::sqrt((double)prob.problem()->d.n_dofs_u);
+        for (size_t s = 0; s < prob.force_history.size(); ++s) {
+          const auto &B = prob.force_history[s]; const poro_force_balance_terms &t = B.terms;
+          std::snprintf(buf, sizeof buf, "force balance step %zu:", s + 1);
+          std::string line = buf;
+          for (size_t k = 0; k < B.labels.size(); ++k) { std::snprintf(buf, sizeof buf, " label %d component %d reaction %.9e;", (int)B.labels[k], (int)B.components[k], B.reaction_by_label[k]); line += buf; }
+          for (int k = 0; k < dm; ++k) {
+            std::snprintf(buf, sizeof buf, " component %d: reaction %.9e traction %.9e body %.9e coupling %.3e free_rows %.3e closure %.3e bound %.3e;", k, t.reaction_sum[k], t.traction_sum[k], t.body_sum[k],
+                          t.coupling_sum[k], t.free_row_sum[k], B.imbalance(k), sqrt_n * t.residual_l2);
+            line += buf;
+          }
+          std::snprintf(buf, sizeof buf, " residual_l2 %.9e", t.residual_l2); line += buf;
+          force_lines.push_back(line);
+        }
+      }
+      if (mohr_coulomb) {
+        char buf[256];
+        for (size_t s = 0; s < prob.failure_history.size(); ++s) {
+          const poro_failure_summary &f = prob.failure_history[s];
+          std::snprintf(buf, sizeof buf, "mohr-coulomb step %zu: max f %.9e in cell %lld, %lld failing cells", s + 1, f.max_f, (long long)f.argmax_cell, (long long)f.n_failing);
+          failure_lines.push_back(buf);
+        }
+      }
       if (flow_balance) {                // (only with the option) the per-step lines, printed with the steps below, and the totals
         char buf[256];
         const double sqrt_n = std::sqrt((double)prob.problem()->d.n_dofs_p);
@@ -262,6 +305,10 @@ int main(int argc, char **argv) {
       std::cout << "        Error: " << t[5] << std::endl;                                       // :406
       const size_t step = (size_t)t[0];           // --flow-balance: the step's line behind its last coupling iteration
       if (step >= 1 && step + 1 <= flow_lines.size() && (r + 1 == rows || trace[8 * (r + 1)] != t[0])) std::cout << flow_lines[step - 1] << std::endl;
+      if (step >= 1 && (r + 1 == rows || trace[8 * (r + 1)] != t[0])) {     // --force-balance, --mohr-coulomb: the step's lines behind its last coupling iteration
+        if (step <= force_lines.size()) std::cout << force_lines[step - 1] << std::endl;
+        if (step <= failure_lines.size()) std::cout << failure_lines[step - 1] << std::endl;
+      }
     }
     if (!flow_lines.empty()) std::cout << flow_lines.back() << std::endl;
   } catch (std::exception &exc) {   // PoroelasticityFSS.h:512-523
