@@ -398,6 +398,29 @@ int  poro_pres_solve(poro_ctx *ctx, const poro_solver_opts *opts, poro_solve_inf
 /* PoroElasticPressureSolver<dim>::update_volumetric_strain (:187-194): eps_v += (alpha/K) dp */
 int  poro_pres_update_volumetric_strain(poro_ctx *ctx);
 
+/* The pressure Newton loop of one fixed-stress iteration (PoroelasticityFSS.h:358-380) in one call:
+ *   while (it < max_iterations) { ++it; update_volumetric_strain; assemble_residual; if (l2 < pressure_tol) break; assemble_jacobian; solve; p += dp; }   pinf = |p|_inf
+ * enqueued as gated batches of iterations - a device-side test closes a gate where the per-call loop would have left, and every later kernel of the batch returns at once -
+ * so that the host waits once per batch (normally once per call) instead of once per residual, check and norm.  The kernels of the per-call sequence in its order (p += dp
+ * and the next iteration's strain update share a launch): every vector and every recorded number is what that sequence gives, bit for bit.
+ * Eligible (poro_supports_pres_newton_loop): one rank, PORO_OP_MATRIX_FREE on a 3D box with the constant-coefficient pressure stencil (no per-cell permeability or moduli),
+ * no hanging or prescribed pressure dofs, opts->preconditioner == PORO_PREC_FDM with the direct solve first (PORO_STOP_RHS).  PORO_PRES_HOST_LOOP in the environment when
+ * the context is made: never eligible (A/B hook).
+ * hint_slot (0..7, else none): which call of the time step this is; the length of the first batch comes from the count the same slot took last time.
+ * record: iterations = residuals evaluated (= pressure_iteration), solves = direct solves whose check held, outcome PORO_NEWTON_*; l2[i] of iteration i + 1; res[k], bn[k]
+ * of the k-th check (final and initial residual of that solve).  Arrays of max_iterations entries each, the caller's.
+ * PORO_NEWTON_FALLBACK: the check of the direct solve of iteration `iterations` failed; PORO_VEC_DP holds the direct result, PORO_VEC_P is not yet updated, exactly the
+ * state in which poro_pres_solve goes on to CG: the caller calls poro_pres_solve (which repeats the direct solve, same bits), updates p and runs the rest per call.
+ * pinf is not set then.  The timer family "pressure_newton_batched" counts the calls with hint_slot == 0, that is the time steps whose loops ran this way (a count, no time). */
+enum { PORO_NEWTON_CAP = 0, PORO_NEWTON_CONVERGED = 1, PORO_NEWTON_FALLBACK = 2 };
+typedef struct poro_newton_record {
+  int32_t iterations, solves, outcome, batches;
+  double  pinf;
+  double *l2, *res, *bn;
+} poro_newton_record;
+int  poro_supports_pres_newton_loop(poro_ctx *ctx, const poro_solver_opts *opts);
+int  poro_pres_newton_loop(poro_ctx *ctx, double time_step, double pressure_tol, int32_t max_iterations, const poro_solver_opts *opts, int32_t hint_slot, poro_newton_record *record);
+
 /* StrainProjector<dim>::assemble_projection_matrix (:101-106) */
 int  poro_proj_assemble_matrix(poro_ctx *ctx);
 /* StrainProjector<dim>::assemble_projection_rhs (:109-198); tensor_components are full indices a*dim+b */

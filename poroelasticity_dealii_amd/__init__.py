@@ -81,6 +81,11 @@ class SolverOpts(C.Structure):
                 ("stop_rule", C.c_int32), ("poly_degree", C.c_int32)]
 
 
+class NewtonRecord(C.Structure):      # poro_newton_record
+    _fields_ = [("iterations", C.c_int32), ("solves", C.c_int32), ("outcome", C.c_int32), ("batches", C.c_int32), ("pinf", C.c_double),
+                ("l2", C.POINTER(C.c_double)), ("res", C.POINTER(C.c_double)), ("bn", C.POINTER(C.c_double))]
+
+
 class SolveInfo(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("initial_residual", C.c_double), ("final_residual", C.c_double),
                 ("seconds", C.c_double), ("operator_applications", C.c_int64)]
@@ -142,7 +147,7 @@ HIP_SYMBOLS = [
     "poro_last_error", "poro_abi_version", "poro_ctx_create", "poro_ctx_destroy", "poro_ctx_synchronize", "poro_ctx_set_scatter_mode", "poro_ctx_get_scatter_mode", "poro_ctx_set_operator_form", "poro_ctx_get_operator_form", "poro_ctx_set_fdm_precision", "poro_ctx_get_fdm_precision", "poro_comm_unique_id", "poro_ctx_comm_init_rccl",
     "poro_ctx_comm_init_callbacks", "poro_vec_set", "poro_vec_get", "poro_vec_fill", "poro_vec_copy", "poro_vec_axpy", "poro_vec_norm",
     "poro_state_save", "poro_state_restore", "poro_disp_assemble_system", "poro_disp_solve", "poro_supports_preconditioner", "poro_pres_assemble_residual", "poro_pres_apply_boundary_values", "poro_pres_assemble_jacobian", "poro_pres_solve",
-    "poro_pres_update_volumetric_strain", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
+    "poro_pres_update_volumetric_strain", "poro_supports_pres_newton_loop", "poro_pres_newton_loop", "poro_proj_assemble_matrix", "poro_proj_assemble_rhs", "poro_proj_solve", "poro_proj_solve_many", "poro_get_volumetric_strain", "poro_get_effective_stresses",
     "poro_pres_estimate_error", "poro_state_transfer_p",
     "poro_export_csr_size", "poro_export_csr", "poro_apply_operator", "poro_apply_preconditioner_u", "poro_bench_operator", "poro_timers_reset", "poro_timers_enable", "poro_timers_get",
     "poro_ctx_set_fdm_form", "poro_ctx_get_fdm_form",
@@ -203,6 +208,8 @@ def load_hip():
         L.poro_pres_apply_boundary_values.argtypes = [C.c_void_p]
         L.poro_pres_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]
         L.poro_pres_update_volumetric_strain.argtypes = [C.c_void_p]
+        L.poro_supports_pres_newton_loop.argtypes = [C.c_void_p, C.c_void_p]
+        L.poro_pres_newton_loop.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.poro_proj_assemble_matrix.argtypes = [C.c_void_p]
         L.poro_proj_assemble_rhs.argtypes = [C.c_void_p, _ip, C.c_int32]
         L.poro_proj_solve.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]
@@ -334,6 +341,7 @@ def load_host():
         L.poro_host_displacement_bc_labels.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.argtypes = [C.c_void_p, _ip]
         L.poro_host_runner_preconditioners.restype = None
+        L.poro_host_runner_pressure_solver_tolerances.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.poro_host_runner_free.argtypes = [C.c_void_p]
         L.poro_host_runner_free.restype = None
         _host = L
@@ -1032,6 +1040,18 @@ class Context:
     def pres_update_volumetric_strain(self):
         self._chk(self.L.poro_pres_update_volumetric_strain(self.ptr))
 
+    def supports_pres_newton_loop(self, abs_tol=0.0, rel_tol=1e-8, max_iter=1000, prec=PREC_FDM):
+        return bool(self.L.poro_supports_pres_newton_loop(self.ptr, C.byref(self._opts(abs_tol, rel_tol, max_iter, prec, 1.0))))
+
+    def pres_newton_loop(self, dt, pressure_tol, max_iterations, abs_tol=0.0, rel_tol=1e-8, max_iter=1000, prec=PREC_FDM, hint_slot=-1):
+        """poro_pres_newton_loop (include/poroel_hip.h): the pressure Newton loop of one fixed-stress iteration as gated batches.  Returns a dict: iterations, solves,
+        outcome (0 cap, 1 converged, 2 fallback), batches, pinf, l2[iterations], res / bn of every check that ran"""
+        l2, res, bn = (np.zeros(max_iterations) for _ in range(3))
+        rec = NewtonRecord(l2=l2.ctypes.data_as(_dp), res=res.ctypes.data_as(_dp), bn=bn.ctypes.data_as(_dp))
+        self._chk(self.L.poro_pres_newton_loop(self.ptr, dt, pressure_tol, max_iterations, C.byref(self._opts(abs_tol, rel_tol, max_iter, prec, 1.0)), hint_slot, C.byref(rec)))
+        checks = rec.solves + (1 if rec.outcome == 2 else 0)
+        return dict(iterations=rec.iterations, solves=rec.solves, outcome=rec.outcome, batches=rec.batches, pinf=rec.pinf, l2=l2[:rec.iterations].copy(), res=res[:checks].copy(), bn=bn[:checks].copy())
+
     def proj_assemble_matrix(self):
         self._chk(self.L.poro_proj_assemble_matrix(self.ptr))
 
@@ -1317,6 +1337,11 @@ class Runner:
         out = (C.c_int32 * 3)()
         self.H.poro_host_runner_preconditioners(self.h, out)
         return tuple(out)
+
+    def set_pressure_solver_tolerances(self, abs_tol=0.0, rel_tol=1e-8):
+        """the stopping rule of the pressure solve, ||g|| <= max(abs_tol, rel_tol ||R||) (the reference's: 0, 1e-8); kept over initialize() and adapt()"""
+        if self.H.poro_host_runner_pressure_solver_tolerances(self.h, abs_tol, rel_tol) != 0:
+            raise RuntimeError(self.H.poro_host_last_error().decode())
 
     def work(self):
         """cumulative work counters since creation"""

@@ -14,6 +14,7 @@
 #include "../../include/poroel_hip.h"
 #include "fdm_tables.hpp"      // poro::Error (declared there: that header compiles without this one) and LineTables, the 1D tables of a grid line
 #include "cell_field.hpp"      // poro::CellField, the host state of a per-cell coefficient field
+#include "newton_record.hpp"   // the record of the pressure Newton loop's batches (host-only)
 
 namespace poro {
 
@@ -318,6 +319,9 @@ struct poro_ctx {
   // timing
   bool timing = false; std::map<std::string, poro::Timer> timers; std::vector<hipEvent_t> event_pool;
   double jac_dt = -1;
+  // the pressure Newton loop (ctx.hip): pres_host_loop = PORO_PRES_HOST_LOOP was set when the context was made (the per-call loop, A/B hook); the gate and the record of a
+  // batch; per call slot of a time step the residual evaluations that call took last time (0 = unknown; cleared by poro_state_restore like the iteration-count hints)
+  bool pres_host_loop = false; poro::DevBuf<poro::PcgScalars> newton_gate; poro::DevBuf<double> newton_rec; int newton_hint[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   poro::KellyDev kelly;
   // The per-cell coefficient fields (ctx_fields.hip; one rank).  Both are a poro::CellField (cell_field.hpp): kind 0 none, 1 layered along the slowest direction of
   // `lines`, 2 general; host[a]: the caller's arrays; layer[a]: per cell layer of that direction the value (kind 1) or the arithmetic mean (kind 2) - the coefficients of
@@ -387,6 +391,13 @@ void la_reduce_post(hipStream_t s, const double *partials, int n_sets, double *r
 void la_copy(hipStream_t s, double *y, const double *x, int64_t n);
 void la_axpy(hipStream_t s, double *y, double a, const double *x, int64_t n);
 void la_add_range(hipStream_t s, double *y, const double *x, int64_t n);
+// the pressure Newton loop as a gated batch (poro_pres_newton_loop): gate->done != 0 makes every one of these but la_newton_reset / la_newton_post a no-op
+void la_axpy_gated(hipStream_t s, double *y, double a, const double *x, int64_t n, const PcgScalars *gate);
+void la_newton_update(hipStream_t s, double *p, double *ev, double c, const double *dp, int64_t n, const PcgScalars *gate);      // p += dp, ev += c dp
+void la_newton_reset(hipStream_t s, PcgScalars *gate, double *rec /*[kNewtonRecord]*/);
+void la_newton_residual_test(hipStream_t s, const double *partials, double tol, int slot, PcgScalars *gate, double *rec);
+void la_newton_check_test(hipStream_t s, const double *partials /*[2 kMaxPartials]*/, double abs_tol, double rel_tol, int slot, PcgScalars *gate, double *rec);
+void la_newton_post(hipStream_t s, const double *partials_inf, double *rec, Mailbox *mb, unsigned long long seq);
 void la_add_two_ranges(hipStream_t s, double *y0, const double *x0, double *y1, const double *x1, int64_t n);
 // partials-based reductions; results land in red[slot..] after la_reduce_finish
 void la_dot_partials(hipStream_t s, const double *a, const double *b, int64_t n, double *partials /*[kMaxPartials]*/, const PcgScalars *gate = nullptr /* no-op once gate->done / finishing */);
@@ -396,7 +407,7 @@ void la_csr_spmv(hipStream_t s, const CsrDev &A, const double *val, const double
 // R = -(M t + kappa K p + src)
 void la_csr_residual(hipStream_t s, const CsrDev &A, const double *M, const double *K, double kappa, const double *t, const double *p,
                      const double *src, double *R);
-void la_pressure_tmp(hipStream_t s, double *t, const double *ev, const double *ev0, const double *p, const double *p_old, double c1, double c2, int64_t n);
+void la_pressure_tmp(hipStream_t s, double *t, const double *ev, const double *ev0, const double *p, const double *p_old, double c1, double c2, int64_t n, const PcgScalars *gate = nullptr);
 void la_jacobian(hipStream_t s, double *J, const double *M, const double *K, double a, double kappa, int64_t nnz);
 void la_ifc_pack(hipStream_t s, const IfcDev &I, const double *v);
 void la_ifc_sum(hipStream_t s, const IfcDev &I, double *v);
@@ -521,8 +532,8 @@ struct MfArgs { int dim, k_u; BoxDev box; const double *Ke; const uint8_t *mask;
 void mf_apply(hipStream_t s, const MfArgs &a, const double *x, double *y, bool constrained, double *dot_partials = nullptr);
 void mf_diag(hipStream_t s, const MfArgs &a, double *diag);
 // y = (a M + kappa K) x for the Q1 pressure space of a uniform box (constant-coefficient 3^dim-point stencil)
-void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y);
-void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R);
+void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y, const PcgScalars *gate = nullptr);      // gate: a no-op once gate->done (the pressure Newton loop's batch)
+void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R, const PcgScalars *gate = nullptr);
 // the same with a per-cell coefficient: y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q).  kap holds ncomp planes of n_cells weights in lattice cell order, ncomp = 1
 // (one k / mu per cell) or dim (component d weights the derivatives along direction d, K_e = kx k(x)m(x)m + ky m(x)k(x)m + kz m(x)m(x)k)
 void p_stencil_apply_var(hipStream_t s, int dim, const BoxDev &box, double a, const double *kap, int ncomp, const double *x, double *y);
@@ -586,7 +597,7 @@ int fdmo_scalar_apply(hipStream_t s, FdmOct &O, double a, double kappa, const do
 int fdmo_scalar_apply_many(hipStream_t s, FdmOct &O, double a, double kappa, int nb, const double *const *g, double *const *z, const PcgScalars *gate = nullptr);   // up to 3 right-hand sides in one set of launches
 // block partials of |y_e - b_e|^2 and |b_e|^2 for up to three (y, b) pairs: sets 2e and 2e + 1 of `partials`
 // mask != null: rows with mask[i] != 0 count in neither norm (prescribed rows of a system solved on its free rows)
-void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask = nullptr);
+void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask = nullptr, const PcgScalars *gate = nullptr);
 // slab partitions: nn = LOCAL vertices, the last direction's matrices are uploaded for the GLOBAL line; the three sweeps separately (all-to-alls in between, ctx_prec.hip)
 void fdmo_scalar_init_slab(FdmOct &O, const int nn[3], int rank, const std::vector<int> &node_layers, hipStream_t s);
 void fdmo_scalar_slab_pass(hipStream_t s, FdmOct &O, int pass, double a, double kappa, const double *in, double *out);

@@ -541,6 +541,8 @@ int poro_ctx_create(const poro_desc *desc, int device, int operator_mode, poro_c
     kron_lm_prepare_device();
     { void *mbp = nullptr; PORO_HIP(hipHostMalloc(&mbp, sizeof(Mailbox), hipHostMallocDefault)); std::memset(mbp, 0, sizeof(Mailbox)); c->mailbox = static_cast<Mailbox *>(mbp); }
     setup(c.get(), desc);
+    c->pres_host_loop = std::getenv("PORO_PRES_HOST_LOOP") != nullptr;      // A/B hook, read once per context: the pressure Newton loop call by call (poro_pres_newton_loop refuses)
+    c->newton_gate.alloc(1); c->newton_gate.zero(c->stream); c->newton_rec.alloc(kNewtonRecord); c->newton_rec.zero(c->stream);
     if (desc->coarse.enabled) {
       // two-level preconditioner: the underlying uniform box becomes a context of its own on this context's stream
       if (!desc->coarse.box_problem || !desc->coarse.ptr || !desc->coarse.node || !desc->coarse.weight) throw Error("poro_desc.coarse: box_problem / ptr / node / weight missing");
@@ -830,6 +832,7 @@ int poro_state_restore(poro_ctx *c) {
     la_copy_many(c->stream, (int)dst.size(), dst.data(), src.data(), len.data());      // (one launch instead of two dozen)
     // the solves that follow repeat earlier ones: forget the iteration-count history, so that a measurement of a repeated step cannot profit from a perfect prediction
     for (int *h : {c->pcg_hint_u, c->pcg_hint_fdm_u, c->pcg_hint_cheb_u, c->pcg_hint_p, c->pcg_hint_proj}) h[0] = h[1] = 0;
+    for (int &h : c->newton_hint) h = 0;
     return 0;
   });
 }
@@ -974,22 +977,22 @@ int poro_pres_apply_boundary_values(poro_ctx *c) {
   });
 }
 
+// J = M/(M_b dt) + (k/mu) K depends on dt only (the reference recomputes it every pressure iteration): same dt, same matrix
+static int form_jacobian(poro_ctx *c, double dt) {
+  if (c->jac_dt == dt) return 0;
+  Timed tm(c, "pressure_jacobian");
+  la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->Ap.nnz);   // (per-cell k / mu: Kp holds K_kappa)
+  la_csr_diag(c->stream, c->Ap, c->Jp.p, c->diag_J.p);
+  exchange_add(c, c->diag_J.p, c->n_p, c->comm.part.plane_p);
+  if (!c->dinv_J.p) c->dinv_J.alloc(c->n_p);
+  la_reciprocal(c->stream, c->dinv_J.p, c->diag_J.p, c->n_p);
+  if (c->cons_p.n || c->n_pdir) la_mask_zero(c->stream, c->dinv_J.p, c->cons_p.inert.p, c->n_p);
+  c->ilu_J_valid = false;
+  c->jac_dt = dt;
+  return 0;
+}
 int poro_pres_assemble_jacobian(poro_ctx *c, double dt) {
-  return guarded([&] {
-    PORO_HIP(hipSetDevice(c->device));
-    // J = M/(M_b dt) + (k/mu) K depends on dt only (the reference recomputes it every pressure iteration): same dt, same matrix
-    if (c->jac_dt == dt) return 0;
-    Timed tm(c, "pressure_jacobian");
-    la_jacobian(c->stream, c->Jp.p, c->Mp.p, c->Kp.p, 1. / c->mat.biot_M / dt, c->perm.kind ? 1.0 : c->mat.k_over_mu, c->Ap.nnz);   // (per-cell k / mu: Kp holds K_kappa)
-    la_csr_diag(c->stream, c->Ap, c->Jp.p, c->diag_J.p);
-    exchange_add(c, c->diag_J.p, c->n_p, c->comm.part.plane_p);
-    if (!c->dinv_J.p) c->dinv_J.alloc(c->n_p);
-    la_reciprocal(c->stream, c->dinv_J.p, c->diag_J.p, c->n_p);
-    if (c->cons_p.n || c->n_pdir) la_mask_zero(c->stream, c->dinv_J.p, c->cons_p.inert.p, c->n_p);
-    c->ilu_J_valid = false;
-    c->jac_dt = dt;
-    return 0;
-  });
+  return guarded([&] { PORO_HIP(hipSetDevice(c->device)); return form_jacobian(c, dt); });
 }
 
 int poro_pres_solve(poro_ctx *c, const poro_solver_opts *opts, poro_solve_info *info) {
@@ -1040,6 +1043,84 @@ int poro_pres_update_volumetric_strain(poro_ctx *c) {
   return guarded([&] { PORO_HIP(hipSetDevice(c->device)); if (c->mod.kind) la_strain_update_nodal(c->stream, vec(c, PORO_VEC_EPSV), vec(c, PORO_VEC_DP), c->mat.biot_alpha, c->mod.node.p, c->n_p);   // per-cell moduli: K = lambda + 2 G / 3 from the nodal means
                          else la_axpy(c->stream, vec(c, PORO_VEC_EPSV), c->mat.biot_alpha / c->mat.bulk_K, vec(c, PORO_VEC_DP), c->n_p);
                          return 0; });
+}
+
+// ---- the pressure Newton loop as gated batches (include/poroel_hip.h: poro_pres_newton_loop; newton_record.hpp) ---------------------------------------------------
+static bool newton_loop_supported(poro_ctx *c, const poro_solver_opts *opts) {
+  static const bool iterative = std::getenv("PORO_PRES_ITERATIVE") != nullptr;
+  if (!c || !opts || c->pres_host_loop || iterative) return false;
+  // the constant-coefficient box stencil on one rank without constraint lists: nothing stands between the residual kernel and its norm, or between the stencil and its check
+  if (c->operator_mode != PORO_OP_MATRIX_FREE || !c->box.enabled || c->perm.kind || c->cons_p.n || c->n_pdir || c->comm.multi() || c->mod.kind || c->dim != 3) return false;
+  if (opts->preconditioner != PORO_PREC_FDM || opts->stop_rule != PORO_STOP_RHS || prec_refusal(c, 1, PORO_PREC_FDM, true)) return false;
+  build_fdm_q1(c, Q1Set::free_ends);
+  return c->q1_free.fused.built && !c->q1_free.fused.slab.on;
+}
+int poro_supports_pres_newton_loop(poro_ctx *c, const poro_solver_opts *opts) {
+  int yes = 0;
+  const int rc = guarded([&] { PORO_HIP(hipSetDevice(c->device)); yes = newton_loop_supported(c, opts) ? 1 : 0; return 0; });
+  return rc == 0 ? yes : 0;
+}
+int poro_pres_newton_loop(poro_ctx *c, double dt, double pressure_tol, int32_t max_iterations, const poro_solver_opts *opts, int32_t hint_slot, poro_newton_record *out) {
+  return guarded([&] {
+    PORO_HIP(hipSetDevice(c->device));
+    if (!out || !out->l2 || !out->res || !out->bn) throw Error("pres_newton_loop: no record");
+    if (max_iterations < 1) throw Error("pres_newton_loop: max_iterations < 1");
+    if (!newton_loop_supported(c, opts)) throw Error("pres_newton_loop: not supported on this context with these options (poro_supports_pres_newton_loop tells)");
+    hipStream_t s = c->stream;
+    form_jacobian(c, dt);      // (only where dt changed; before the batch, which cannot stop for it)
+    const double a = 1. / c->mat.biot_M / c->jac_dt, kappa = c->mat.k_over_mu, strain = c->mat.biot_alpha / c->mat.bulk_K;
+    double *const p = vec(c, PORO_VEC_P), *const dp = vec(c, PORO_VEC_DP), *const R = vec(c, PORO_VEC_RESIDUAL_P), *const ev = vec(c, PORO_VEC_EPSV), *const y = c->wh_p.p;
+    const double *const src = c->grav.flux_on() ? c->grav.src_p.p : c->src_local.p;
+    PcgScalars *const gate = c->newton_gate.p; double *const rec = c->newton_rec.p;
+    const int predicted = hint_slot >= 0 && hint_slot < 8 ? c->newton_hint[hint_slot] : 0;
+    NewtonState S; int batches = 0;
+    while (!S.finished) {
+      const NewtonBatch B = newton_plan_batch(S, max_iterations, predicted);
+      if (B.slots < 1) throw Error("pres_newton_loop: empty batch");
+      la_newton_reset(s, gate, rec);
+      for (int j = 0; j < B.slots; ++j) {
+        const bool solve_here = j + 1 < B.slots || B.last_solve, solved_before = j > 0;     // (a slot behind another one follows that one's solve part)
+        if (j > 0 || B.first_residual) {
+          if (!solved_before) la_axpy_gated(s, ev, strain, dp, c->n_p, gate);               // update_volumetric_strain (:360); behind a solve part: done with its p += dp
+          {
+            Timed tm(c, "pressure_residual");                                               // assemble_residual (:361-363), the kernels of poro_pres_assemble_residual
+            la_pressure_tmp(s, c->tmp_p.p, ev, vec(c, PORO_VEC_EPSV0), p, vec(c, PORO_VEC_P_OLD), c->mat.biot_alpha / dt, 1. / c->mat.biot_M / dt, c->n_p, gate);
+            p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, c->tmp_p.p, p, src, R, gate);
+          }
+          la_dot_partials(s, R, R, c->n_p, c->partials.p, gate);
+          la_newton_residual_test(s, c->partials.p, pressure_tol, j, gate, rec);            // l2 < pressure_tol (:366)
+        }
+        if (solve_here) {
+          {
+            Timed tm(c, "precondition_p_fdm");                                              // solve (:378): dp = J^-1 R ...
+            count_strip_launches(c, fdmo_scalar_apply(s, c->q1_free.fused, a, kappa, R, dp, gate));
+          }
+          {
+            Timed tm(c, "apply_p_stencil");                                                 // ... checked against the reference's stopping rule (solve_q1_direct)
+            p_stencil_apply(s, c->dim, c->box, a, kappa, dp, y, gate);
+          }
+          const double *ys[1] = {y}, *bs[1] = {R};
+          la_residual_norms_many(s, 1, ys, bs, c->n_p, c->partials.p, nullptr, gate);
+          la_newton_check_test(s, c->partials.p, opts->abs_tol, opts->rel_tol, j, gate, rec);
+          if (j + 1 < B.slots) la_newton_update(s, p, ev, strain, dp, c->n_p, gate);        // p += dp (:379) and the next iteration's update_volumetric_strain (:360)
+          else la_axpy_gated(s, p, 1.0, dp, c->n_p, gate);                                  // p += dp (:379)
+        }
+      }
+      // (the sums of a batch go to its record alone: c->red, where k_reduce_post leaves a copy of what it publishes, has no reader behind these calls)
+      la_norm_partials(s, p, c->n_p, c->partials.p, c->partials.p + kMaxPartials);          // |p|_inf (:387-389), whatever the gate says
+      newton_post_and_wait(c, c->partials.p + kMaxPartials);
+      double r[kNewtonRecord];
+      for (int k = 0; k < kNewtonRecord; ++k) r[k] = c->mailbox->vals[k];
+      if (!newton_absorb(S, B, r, max_iterations)) throw Error("pres_newton_loop: the record of a batch contradicts what was enqueued");
+      ++batches;
+    }
+    if (hint_slot >= 0 && hint_slot < 8) c->newton_hint[hint_slot] = S.entered;
+    if (hint_slot == 0) c->timers["pressure_newton_batched"].enqueued++;      // (a count, no time: the time steps whose loop ran as batches - slot 0 is a step's first call)
+    out->iterations = S.entered; out->solves = S.solves; out->outcome = S.code; out->batches = batches; out->pinf = S.pinf;
+    for (size_t i = 0; i < S.l2.size(); ++i) out->l2[i] = S.l2[i];
+    for (size_t i = 0; i < S.res.size(); ++i) { out->res[i] = S.res[i]; out->bn[i] = S.bn[i]; }
+    return 0;
+  });
 }
 
 int poro_proj_assemble_matrix(poro_ctx *c) {

@@ -95,6 +95,12 @@ void post_sums_and_wait(poro_ctx *c, const double *partials, int n_sets, int max
   la_reduce_post(c->stream, partials, n_sets, c->red.p, max_mask, c->mailbox, want);
   mailbox_wait(c, want);
 }
+// the end of a batch of the pressure Newton loop: max |p| from the partials of la_norm_partials and the batch's record go to the mailbox in one launch; one wait
+void newton_post_and_wait(poro_ctx *c, const double *partials_inf) {
+  const unsigned long long want = ++c->mb_seq;
+  la_newton_post(c->stream, partials_inf, c->newton_rec.p, c->mailbox, want);
+  mailbox_wait(c, want);
+}
 static void mailbox_wait(poro_ctx *c, unsigned long long want) {
   PORO_HIP(hipGetLastError());
   const auto t0 = std::chrono::steady_clock::now(); unsigned spins = 0;

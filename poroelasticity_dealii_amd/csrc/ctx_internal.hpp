@@ -72,6 +72,7 @@ struct EventPair {
 // device -> host scalars through the pinned mailbox (no copy engine, no stream synchronisation)
 void post_and_wait(poro_ctx *c, const double *dev_src, int n, const PcgScalars *sc = nullptr);
 void post_sums_and_wait(poro_ctx *c, const double *partials, int n_sets, int max_mask, int n_allreduce);
+void newton_post_and_wait(poro_ctx *c, const double *partials_inf);      // one rank: c->newton_rec + max |p| -> mailbox->vals[0 .. kNewtonRecord)
 void count_strip_launches(poro_ctx *c, int n);      // ctx_prec.hip
 
 // ---- communication (ctx_comm.hip) ---------------------------------------------------------------------------------------------------

@@ -67,6 +67,66 @@ __global__ void k_reduce_post(const double *partials, int n_sets, double *red, i
   if (threadIdx.x == 0) __hip_atomic_store(const_cast<unsigned long long *>(&mb->seq), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- the pressure Newton loop as one gated batch (ctx.hip: poro_pres_newton_loop) ----------------------------------------------------------------------------------
+// The gate is a PcgScalars of its own whose `done` holds the loop's code (newton_record.hpp: 0 open, 1 converged, 2 fallback): every kernel of the batch tests it the way
+// the launches of a CG iteration test theirs.  rec[kNewtonRecord] is the batch's record, which the last kernel copies to the mailbox
+__global__ void k_newton_reset(PcgScalars *gate, double *rec) {
+  if (threadIdx.x < kNewtonRecord) rec[threadIdx.x] = 0.0;
+  if (threadIdx.x == 32) { gate->done = 0; gate->finishing = 0; gate->stop = 0; }
+}
+__global__ void k_axpy_gated(double *y, double a, const double *x, int64_t n, const PcgScalars *gate) {
+  if (pcg_gate_closed(gate)) return;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) y[i] += a * x[i];
+}
+// p += dp of one iteration and eps_v += c dp of the next in one launch (two k_axpy's statements on independent vectors, dp read once)
+__global__ void k_newton_update(double *p, double *ev, double c, const double *dp, int64_t n, const PcgScalars *gate) {
+  if (pcg_gate_closed(gate)) return;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) { const double d = dp[i]; p[i] += d; ev[i] += c * d; }      // (k_axpy with a = 1: fma(1, d, p) = p + d)
+}
+// one block: R . R from the partials of la_dot_partials (k_reduce_post's additions), into the record; closes the gate when sqrt(R . R) < tol
+__global__ void k_newton_residual_test(const double *partials, double tol, int slot, PcgScalars *gate, double *rec) {
+  __shared__ double sh[4];
+  if (pcg_gate_closed(gate)) return;
+  double v = 0;
+  for (int i = threadIdx.x; i < kMaxPartials; i += kBlock) v = v + partials[i];
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) {
+    rec[kNewtonHead + 3 * slot] = v; rec[0] += 1.0;
+    if (sqrt(v) < tol) { rec[2] = 1.0; gate->done = 1; }
+  }
+}
+// one block: the two sums of the direct solve's check (la_residual_norms_many + k_reduce_post) into the record; the reference's stopping rule (solve_q1_direct) either
+// counts the solve or closes the gate with the fallback code, p not yet updated
+__global__ void k_newton_check_test(const double *partials, double abs_tol, double rel_tol, int slot, PcgScalars *gate, double *rec) {
+  __shared__ double sh[4];
+  if (pcg_gate_closed(gate)) return;
+  double s[2];
+  for (int k = 0; k < 2; ++k) {
+    double v = 0;
+    for (int i = threadIdx.x; i < kMaxPartials; i += kBlock) v = v + partials[k * kMaxPartials + i];
+    s[k] = block_sum(v, sh);
+  }
+  if (threadIdx.x == 0) {
+    rec[kNewtonHead + 3 * slot + 1] = s[0]; rec[kNewtonHead + 3 * slot + 2] = s[1];
+    const double res = sqrt(s[0]), bn = sqrt(s[1]);
+    if (res <= fmax(abs_tol, rel_tol * bn)) rec[1] += 1.0;
+    else { rec[2] = 2.0; gate->done = 2; }
+  }
+}
+// one block, never gated: max |p| from k_norm's partials into the record, the record to the mailbox, then the sequence number (k_reduce_post's publication)
+__global__ void k_newton_post(const double *partials_inf, double *rec, Mailbox *mb, unsigned long long seq) {
+  __shared__ double sh[4], pinf;
+  double v = 0;
+  for (int i = threadIdx.x; i < kMaxPartials; i += kBlock) v = fmax(v, partials_inf[i]);
+  v = block_max(v, sh);
+  if (threadIdx.x == 0) pinf = v;
+  __syncthreads();
+  if (threadIdx.x < kNewtonRecord) mb->vals[threadIdx.x] = threadIdx.x == 3 ? pinf : rec[threadIdx.x];
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(const_cast<unsigned long long *>(&mb->seq), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <int L> __global__ void k_spmv(int64_t n, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
                                         const double *__restrict__ x, double *__restrict__ y) {
   const int lane = threadIdx.x % L;
@@ -109,7 +169,8 @@ template <int L> __global__ void k_residual(int64_t n, const int64_t *__restrict
   // same association as the reference: residual = M t; tmp = (K p) * kappa; residual += tmp; += source; *= -1
   if (lane == 0) R[row] = -((s1 + s2 * kappa) + src[row]);
 }
-__global__ void k_pressure_tmp(double *t, const double *ev, const double *ev0, const double *p, const double *po, double c1, double c2, int64_t n) {
+__global__ void k_pressure_tmp(double *t, const double *ev, const double *ev0, const double *p, const double *po, double c1, double c2, int64_t n, const PcgScalars *gate) {
+  if (pcg_gate_closed(gate)) return;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) t[i] = (ev[i] - ev0[i]) * c1 + (p[i] - po[i]) * c2;
 }
 __global__ void k_jacobian(double *J, const double *M, const double *K, double a, double kappa, int64_t nnz) {
@@ -463,8 +524,9 @@ void la_two_level_combine(hipStream_t s, const int64_t *ptr, const int32_t *col,
 }
 struct ManyPairs { const double *y[3], *b[3]; };
 // MASKED: rows with mask[i] != 0 are left out of both sums (same partials layout)
-template <bool MASKED> __global__ void __launch_bounds__(kBlock) k_residual_norms_many(ManyPairs V, int nb, int64_t n, double *partials, const uint8_t *__restrict__ mask) {
+template <bool MASKED> __global__ void __launch_bounds__(kBlock) k_residual_norms_many(ManyPairs V, int nb, int64_t n, double *partials, const uint8_t *__restrict__ mask, const PcgScalars *gate) {
   __shared__ double sh[5];
+  if (pcg_gate_closed(gate)) return;
   for (int e = 0; e < nb; ++e) {
     double rr = 0, bb = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
@@ -475,10 +537,10 @@ template <bool MASKED> __global__ void __launch_bounds__(kBlock) k_residual_norm
     store_partial(partials + (size_t)(2 * e) * kMaxPartials, rr); store_partial(partials + (size_t)(2 * e + 1) * kMaxPartials, bb);
   }
 }
-void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask) {
+void la_residual_norms_many(hipStream_t s, int nb, const double *const *y, const double *const *b, int64_t n, double *partials, const uint8_t *mask, const PcgScalars *gate) {
   ManyPairs V{}; for (int e = 0; e < nb; ++e) { V.y[e] = y[e]; V.b[e] = b[e]; }
-  if (mask) hipLaunchKernelGGL(k_residual_norms_many<true>, reduce_grid(n), kBlock, 0, s, V, nb, n, partials, mask);
-  else hipLaunchKernelGGL(k_residual_norms_many<false>, reduce_grid(n), kBlock, 0, s, V, nb, n, partials, mask);
+  if (mask) hipLaunchKernelGGL(k_residual_norms_many<true>, reduce_grid(n), kBlock, 0, s, V, nb, n, partials, mask, gate);
+  else hipLaunchKernelGGL(k_residual_norms_many<false>, reduce_grid(n), kBlock, 0, s, V, nb, n, partials, mask, gate);
 }
 void la_post(hipStream_t s, Mailbox *mb, unsigned long long seq, const double *src, int n, const PcgScalars *sc) { hipLaunchKernelGGL(k_post, 1, 64, 0, s, mb, seq, src, n, sc); }
 void la_reduce_post(hipStream_t s, const double *partials, int n_sets, double *red, int max_mask, Mailbox *mb, unsigned long long seq) {
@@ -517,6 +579,14 @@ void la_copy_many(hipStream_t s, int count, double *const *dst, const double *co
   }
 }
 void la_axpy(hipStream_t s, double *y, double a, const double *x, int64_t n) { if (n) hipLaunchKernelGGL(k_axpy, grid_for(n), kBlock, 0, s, y, a, x, n); }
+void la_axpy_gated(hipStream_t s, double *y, double a, const double *x, int64_t n, const PcgScalars *gate) { if (n) hipLaunchKernelGGL(k_axpy_gated, grid_for(n), kBlock, 0, s, y, a, x, n, gate); }
+void la_newton_update(hipStream_t s, double *p, double *ev, double c, const double *dp, int64_t n, const PcgScalars *gate) { if (n) hipLaunchKernelGGL(k_newton_update, grid_for(n), kBlock, 0, s, p, ev, c, dp, n, gate); }
+void la_newton_reset(hipStream_t s, PcgScalars *gate, double *rec) { hipLaunchKernelGGL(k_newton_reset, 1, 64, 0, s, gate, rec); }
+void la_newton_residual_test(hipStream_t s, const double *partials, double tol, int slot, PcgScalars *gate, double *rec) { hipLaunchKernelGGL(k_newton_residual_test, 1, kBlock, 0, s, partials, tol, slot, gate, rec); }
+void la_newton_check_test(hipStream_t s, const double *partials, double abs_tol, double rel_tol, int slot, PcgScalars *gate, double *rec) {
+  hipLaunchKernelGGL(k_newton_check_test, 1, kBlock, 0, s, partials, abs_tol, rel_tol, slot, gate, rec);
+}
+void la_newton_post(hipStream_t s, const double *partials_inf, double *rec, Mailbox *mb, unsigned long long seq) { hipLaunchKernelGGL(k_newton_post, 1, kBlock, 0, s, partials_inf, rec, mb, seq); }
 void la_add_range(hipStream_t s, double *y, const double *x, int64_t n) { la_axpy(s, y, 1.0, x, n); }
 // both interface planes of a slab in one launch (either pair may be null)
 __global__ void k_add_two_ranges(double *y0, const double *x0, double *y1, const double *x1, int64_t n) {
@@ -551,8 +621,8 @@ void la_csr_residual(hipStream_t s, const CsrDev &A, const double *M, const doub
     hipLaunchKernelGGL(k_residual<l>, (unsigned)grid, kBlock, 0, s, A.n, A.rp.p, A.col.p, M, K, kappa, t, p, src, R);
   });
 }
-void la_pressure_tmp(hipStream_t s, double *t, const double *ev, const double *ev0, const double *p, const double *po, double c1, double c2, int64_t n) {
-  hipLaunchKernelGGL(k_pressure_tmp, grid_for(n), kBlock, 0, s, t, ev, ev0, p, po, c1, c2, n);
+void la_pressure_tmp(hipStream_t s, double *t, const double *ev, const double *ev0, const double *p, const double *po, double c1, double c2, int64_t n, const PcgScalars *gate) {
+  hipLaunchKernelGGL(k_pressure_tmp, grid_for(n), kBlock, 0, s, t, ev, ev0, p, po, c1, c2, n, gate);
 }
 void la_jacobian(hipStream_t s, double *J, const double *M, const double *K, double a, double kappa, int64_t nnz) {
   hipLaunchKernelGGL(k_jacobian, grid_for(nnz), kBlock, 0, s, J, M, K, a, kappa, nnz);

@@ -13,6 +13,7 @@
 // Constrained rows return diag_i x_i (ConstraintMatrix elimination).
 #include "common.hpp"
 #include "p_stencil.hpp"
+#include "device_reduce.hpp"
 
 namespace poro {
 namespace {
@@ -191,7 +192,8 @@ void dispatch(hipStream_t s, const MfArgs &a, const double *x, double *y, bool c
 // Q1 matrices M1 = h/6 (1,4,1), K1 = 1/h (-1,2,-1) (boundary rows: h/6 (2,1), 1/h (1,-1)): a 3^DIM-point constant-coefficient
 // stencil.  One thread per node; the 3 MB vector stays in L2, so the kernel costs microseconds where the CSR form streams 125 MB.
 template <int DIM> __global__ void __launch_bounds__(256)
-k_p_stencil(int n0, int n1, int n2, double h0, double h1, double h2, double a, double kappa, const double *__restrict__ x, double *__restrict__ y) {
+k_p_stencil(int n0, int n1, int n2, double h0, double h1, double h2, double a, double kappa, const double *__restrict__ x, double *__restrict__ y, const PcgScalars *gate) {
+  if (pcg_gate_closed(gate)) return;      // (a launch of the pressure Newton loop's batch whose gate is closed; null elsewhere)
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nn = (int64_t)n0 * n1 * n2;
   if (node >= nn) return;
@@ -201,7 +203,8 @@ k_p_stencil(int n0, int n1, int n2, double h0, double h1, double h2, double a, d
 // K-res-p on a uniform box: R = -((M t + kappa (K p)) + q), same association as k_residual / the reference (PoroElasticPressureSolver.h:113-155)
 template <int DIM> __global__ void __launch_bounds__(256)
 k_p_residual_stencil(int n0, int n1, int n2, double h0, double h1, double h2, double kappa, const double *__restrict__ t, const double *__restrict__ p,
-                     const double *__restrict__ src, double *__restrict__ R) {
+                     const double *__restrict__ src, double *__restrict__ R, const PcgScalars *gate) {
+  if (pcg_gate_closed(gate)) return;
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= (int64_t)n0 * n1 * n2) return;
   PStencilTaps<DIM> Tt, Tp;               // the loads of both stencils are in flight before either is summed
@@ -209,19 +212,19 @@ k_p_residual_stencil(int n0, int n1, int n2, double h0, double h1, double h2, do
   const double s1 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 1.0, 0.0, node, Tt), s2 = p_stencil_sum<DIM>(n0, n1, n2, h0, h1, h2, 0.0, 1.0, node, Tp);
   R[node] = -((s1 + s2 * kappa) + src[node]);
 }
-void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R) {
+void p_residual_stencil(hipStream_t s, int dim, const BoxDev &box, double kappa, const double *t, const double *p, const double *src, double *R, const PcgScalars *gate) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const unsigned grid = (unsigned)(((int64_t)n0 * n1 * n2 + 255) / 256);
-  if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kappa, t, p, src, R);
-  else hipLaunchKernelGGL(k_p_residual_stencil<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kappa, t, p, src, R);
+  if (dim == 2) hipLaunchKernelGGL(k_p_residual_stencil<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, kappa, t, p, src, R, gate);
+  else hipLaunchKernelGGL(k_p_residual_stencil<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], kappa, t, p, src, R, gate);
 }
 
-void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y) {
+void p_stencil_apply(hipStream_t s, int dim, const BoxDev &box, double a, double kappa, const double *x, double *y, const PcgScalars *gate) {
   const int n0 = box.n[0] + 1, n1 = box.n[1] + 1, n2 = dim == 3 ? box.n[2] + 1 : 1;
   const int64_t nn = (int64_t)n0 * n1 * n2;
   const unsigned grid = (unsigned)((nn + 255) / 256);
-  if (dim == 2) hipLaunchKernelGGL(k_p_stencil<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kappa, x, y);
-  else hipLaunchKernelGGL(k_p_stencil<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kappa, x, y);
+  if (dim == 2) hipLaunchKernelGGL(k_p_stencil<2>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], 1.0, a, kappa, x, y, gate);
+  else hipLaunchKernelGGL(k_p_stencil<3>, grid, 256, 0, s, n0, n1, n2, box.h[0], box.h[1], box.h[2], a, kappa, x, y, gate);
 }
 
 // ---- the same two kernels with a per-cell coefficient: y = (a M + K_kappa) x, R = -((M t + K_kappa p) + q); kap = NK planes of lattice-ordered weights, NK = 1

@@ -466,6 +466,12 @@ void poro_host_runner_work(void *r, int64_t *work) { on_runner(r, [&](auto &prob
 void poro_host_runner_preconditioners(void *r, int32_t *out) {
   on_runner(r, [&](auto &p, const RunControls &) { out[0] = p.displacement_solver.control.preconditioner; out[1] = p.pressure_solver.control.preconditioner; out[2] = p.strain_projector.control.preconditioner; });
 }
+// the stopping rule of the pressure solve (PoroElasticPressureSolver.h:175: SolverControl(1000, 1e-8 * |R|)): ||g|| <= max(abs_tol, rel_tol ||R||).  Kept over initialize() and adapt()
+int poro_host_runner_pressure_solver_tolerances(void *r, double abs_tol, double rel_tol) {
+  if (!(abs_tol >= 0) || !(rel_tol >= 0)) { g_err = "pressure_solver_tolerances: tolerances must be >= 0"; return -1; }
+  on_runner(r, [&](auto &p, const RunControls &) { p.pressure_solver.control.abs_tol = abs_tol; p.pressure_solver.control.rel_tol = rel_tol; });
+  return 0;
+}
 void poro_host_runner_free(void *r) { delete static_cast<HostRunner *>(r); }
 
 }  // extern "C"

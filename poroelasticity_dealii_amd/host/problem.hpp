@@ -95,8 +95,21 @@ template <int dim> class PoroElasticPressureSolver {
     poro_host::check(rc, "pres_solve");
     if (rc > 0) throw poro_host::NoConvergence("PoroElasticPressureSolver::solve", last.iterations, last.final_residual);
   }
+  // The whole Newton loop of one fixed-stress iteration (:358-380) as gated batches, where the context supports it (poro_pres_newton_loop): the host waits once.
+  // The record holds what the per-call loop would have produced; `last` is the info of the last solve whose check held
+  bool newton_loop_supported() { return poro_supports_pres_newton_loop(ctx, &control) != 0; }
+  const poro_newton_record &newton_loop(double time_step, double pressure_tol, int max_iterations, int hint_slot) {
+    rec_l2.assign(max_iterations, 0.0); rec_res.assign(max_iterations, 0.0); rec_bn.assign(max_iterations, 0.0);
+    record = poro_newton_record{}; record.l2 = rec_l2.data(); record.res = rec_res.data(); record.bn = rec_bn.data();
+    poro_host::check(poro_pres_newton_loop(ctx, time_step, pressure_tol, max_iterations, &control, hint_slot, &record), "pres_newton_loop");
+    if (record.solves > 0) {
+      last = poro_solve_info{}; last.iterations = 0; last.converged = 1; last.initial_residual = rec_bn[record.solves - 1]; last.final_residual = rec_res[record.solves - 1]; last.operator_applications = 1;
+    }
+    return record;
+  }
   double residual_l2 = 0;   // residual.l2_norm() of the last assemble_residual, computed on device in the same pass
  private:
+  poro_newton_record record{}; std::vector<double> rec_l2, rec_res, rec_bn;
   poro_ctx *ctx;
 };
 }  // namespace solvers
@@ -429,6 +442,7 @@ template <int dim> class PoroElasticProblem {
     const int64_t n_dofs_p = pd->n_dofs_p_global > 0 ? pd->n_dofs_p_global : pd->d.n_dofs_p;
     if (rc.preconditioner != PORO_PREC_SSOR && rc.preconditioner_p < 0 && pressure_solver.control.preconditioner == PORO_PREC_JACOBI && n_dofs_p >= 4096 && poro_supports_preconditioner(context(), 1, PORO_PREC_TWO_LEVEL))
       pressure_solver.control.preconditioner = PORO_PREC_TWO_LEVEL;
+    pressure_newton_batched = pressure_solver.newton_loop_supported();      // fixed per context and preconditioner: asked once, here
   }
   // trace rows: [step, fss_iteration, pressure_iterations, inner pressure error, |p|_inf, error after displacement, u CG its, p CG its]
   void initialize(const RunControls &rc) {
@@ -470,20 +484,36 @@ template <int dim> class PoroElasticProblem {
       fss_iteration++;
       int pressure_iteration = 0, pcg = 0; double inner = 0;
       pressure_solver.solution_update = 0.0;               // :356
-      while (pressure_iteration < rc.max_pressure_iterations) {   // :358
-        pressure_iteration++;
-        pressure_solver.update_volumetric_strain(volumetric_strain);   // :360
-        pressure_solver.assemble_residual(rc.time_step, volumetric_strain, initial_volumetric_strain); work.residual_p++;   // :361-363
-        pressure_error = pressure_solver.residual_l2;      // :364
-        inner = pressure_error;
-        if (pressure_error < rc.pressure_tol) break;       // :366-371
+      // :358-380 and :387-389 in one call where the context can run the loop as gated batches: same numbers, one wait.  A failed check of a direct solve hands the
+      // loop back at that iteration's solve (resume_at_solve), and the rest of it runs per call
+      bool resume_at_solve = false, have_pinf = false; double pinf = 0;
+      const bool batched = rc.max_pressure_iterations >= 1 && pressure_newton_batched;
+      if (batched) {
+        const poro_newton_record &N = pressure_solver.newton_loop(rc.time_step, rc.pressure_tol, rc.max_pressure_iterations, fss_iteration - 1);
+        pressure_iteration = N.iterations; work.residual_p += N.iterations;      // :359-363
+        pressure_error = inner = N.l2[N.iterations - 1];                         // :364
+        work.apply_p += N.solves;                                                // :378 (direct solves: no CG iterations, one operator application each)
+        if (N.solves > 0 && rc.time_step != jacobian_dt) { work.jacobian_p++; jacobian_dt = rc.time_step; }   // :377
+        if (N.outcome == PORO_NEWTON_FALLBACK) resume_at_solve = true;
+        else { pinf = N.pinf; have_pinf = true; }                                // :387-389
+      }
+      while (resume_at_solve || (!have_pinf && pressure_iteration < rc.max_pressure_iterations)) {   // :358 (have_pinf: the batches ran the loop to its end)
+        if (!resume_at_solve) {
+          pressure_iteration++;
+          pressure_solver.update_volumetric_strain(volumetric_strain);   // :360
+          pressure_solver.assemble_residual(rc.time_step, volumetric_strain, initial_volumetric_strain); work.residual_p++;   // :361-363
+          pressure_error = pressure_solver.residual_l2;      // :364
+          inner = pressure_error;
+          if (pressure_error < rc.pressure_tol) break;       // :366-371
+        }
+        resume_at_solve = false;
         pressure_solver.assemble_jacobian(rc.time_step);                       // :377
         if (rc.time_step != jacobian_dt) { work.jacobian_p++; jacobian_dt = rc.time_step; }   // the library re-forms J only when dt changed
         pressure_solver.solve();                           // :378
         pcg += pressure_solver.last.iterations; work.cg_p += pressure_solver.last.iterations; work.apply_p += pressure_solver.last.operator_applications;
         pressure_solver.solution += pressure_solver.solution_update;   // :379
       }
-      const double pinf = pressure_solver.solution.linfty_norm();   // :387-389
+      if (!have_pinf) pinf = pressure_solver.solution.linfty_norm();   // :387-389
       assemble_displacement();                             // :395
       solve_displacement();                                // :396
       normal_strains();                                    // :398  (get_volumetric_strain() stays commented out, :399)
@@ -541,6 +571,7 @@ template <int dim> class PoroElasticProblem {
     ctx = c; pressure_solver.rebind(c); displacement_solver.rebind(c); strain_projector.set_solvers(c);
     volumetric_strain.ctx = initial_volumetric_strain.ctx = c;
   }
+  bool pressure_newton_batched = false;   // the context runs the pressure Newton loop as gated batches (choose_preconditioners)
   bool first_assembly = true; int time_step_number = 0, saved_step_number = 0; double jacobian_dt = -1;
   const ProblemData *pd; int device_, operator_mode_;
   std::unique_ptr<ProblemData> adapted;   // the mesh the last refine_mesh built (the first mesh belongs to the caller)
