@@ -319,7 +319,7 @@ struct poro_ctx {
   // timing
   bool timing = false; std::map<std::string, poro::Timer> timers; std::vector<hipEvent_t> event_pool;
   double jac_dt = -1;
-  // the pressure Newton loop (ctx.hip): pres_host_loop = PORO_PRES_HOST_LOOP was set when the context was made (the per-call loop, A/B hook); the gate and the record of a
+  // the pressure Newton loop (ctx_pressure.hip): pres_host_loop = PORO_PRES_HOST_LOOP was set when the context was made (the per-call loop, A/B hook); the gate and the record of a
   // batch; per call slot of a time step the residual evaluations that call took last time (0 = unknown; cleared by poro_state_restore like the iteration-count hints)
   bool pres_host_loop = false; poro::DevBuf<poro::PcgScalars> newton_gate; poro::DevBuf<double> newton_rec; int newton_hint[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   poro::KellyDev kelly;

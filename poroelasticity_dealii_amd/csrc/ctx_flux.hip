@@ -9,16 +9,6 @@ using namespace poro;
 using namespace poro::ctx_detail;
 
 namespace {
-void check_flux_call(poro_ctx *c, const char *name) {
-  if (!c) throw Error("null argument");
-  if (c->comm.part.n_ranks > 1) throw Error(std::string(name) + ": not implemented on partitioned contexts (n_ranks > 1)");
-}
-const double *pressure_space_vector(poro_ctx *c, int which, const char *name) {
-  auto it = c->vec.find(which);
-  if (it == c->vec.end()) throw Error("unknown vector id " + std::to_string(which));
-  if (is_u_vec(which) || (int64_t)it->second.n != c->n_p) throw Error(std::string(name) + ": vector " + std::to_string(which) + " is not a pressure-space vector");
-  return it->second.p;
-}
 // what the context holds now: the permeability form and rho_f g under the residual's own condition
 DarcyArgs darcy_args(poro_ctx *c, const double *p) {
   DarcyArgs a{};
@@ -45,9 +35,9 @@ extern "C" {
 
 int poro_pres_darcy_velocity(poro_ctx *c, int which_vec, double *q_host) {
   return guarded([&] {
-    check_flux_call(c, "poro_pres_darcy_velocity");
+    require_single_rank(c, "poro_pres_darcy_velocity");
     if (!q_host) throw Error("null argument");
-    const double *p = pressure_space_vector(c, which_vec, "poro_pres_darcy_velocity");
+    const double *p = space_vector(c, which_vec, false, "poro_pres_darcy_velocity");
     PORO_HIP(hipSetDevice(c->device));
     build_flux(c);
     { Timed tm(c, "darcy"); darcy_cells(c->stream, darcy_args(c, p), c->flux.q.p); }
@@ -59,9 +49,9 @@ int poro_pres_darcy_velocity(poro_ctx *c, int which_vec, double *q_host) {
 
 int poro_pres_boundary_discharge(poro_ctx *c, int which_vec, double *Q_face_host, const int32_t *labels, int32_t n_labels, double *Q_label_host) {
   return guarded([&] {
-    check_flux_call(c, "poro_pres_boundary_discharge");
+    require_single_rank(c, "poro_pres_boundary_discharge");
     if (n_labels < 0 || (n_labels && (!labels || !Q_label_host))) throw Error("poro_pres_boundary_discharge: labels without a list or without a place for their sums");
-    const double *p = pressure_space_vector(c, which_vec, "poro_pres_boundary_discharge");
+    const double *p = space_vector(c, which_vec, false, "poro_pres_boundary_discharge");
     PORO_HIP(hipSetDevice(c->device));
     build_flux(c);
     poro_ctx::Flux &F = c->flux;
@@ -81,7 +71,7 @@ int poro_pres_boundary_discharge(poro_ctx *c, int which_vec, double *Q_face_host
 
 int poro_pres_flow_balance(poro_ctx *c, double dt, poro_flow_balance_terms *out, double *outflow_dof_host) {
   return guarded([&] {
-    check_flux_call(c, "poro_pres_flow_balance");
+    require_single_rank(c, "poro_pres_flow_balance");
     if (!out) throw Error("null argument");
     if (!(dt > 0) || !std::isfinite(dt)) throw Error("poro_pres_flow_balance: time_step must be finite and > 0");
     PORO_HIP(hipSetDevice(c->device));
@@ -89,18 +79,13 @@ int poro_pres_flow_balance(poro_ctx *c, double dt, poro_flow_balance_terms *out,
     poro_ctx::Flux &F = c->flux;
     hipStream_t s = c->stream;
     const double *p = vec(c, PORO_VEC_P), *p_old = vec(c, PORO_VEC_P_OLD), *ev = vec(c, PORO_VEC_EPSV), *ev0 = vec(c, PORO_VEC_EPSV0);
-    const double *src = c->grav.flux_on() ? c->grav.src_p.p : c->src_local.p;
-    const double c_strain = c->mat.biot_alpha / dt, c_pres = 1. / c->mat.biot_M / dt;
+    const PressureCoeffs k = pressure_coeffs(c, dt);
     {
       Timed tm(c, "flow_balance");
-      // Rt = C^T(-r) by the calls of poro_pres_assemble_residual up to and including la_cons_reduce, into scratch
-      la_pressure_tmp(s, F.t.p, ev, ev0, p, p_old, c_strain, c_pres, c->n_p);
-      if (c->operator_mode == PORO_OP_MATRIX_FREE && c->box.enabled) {
-        if (c->perm.kind) p_residual_stencil_var(s, c->dim, c->box, c->perm.lattice.p, c->perm.ncomp, F.t.p, p, src, F.rt.p);
-        else p_residual_stencil(s, c->dim, c->box, c->mat.k_over_mu, F.t.p, p, src, F.rt.p);
-      } else la_csr_residual(s, c->Ap, c->Mp.p, c->Kp.p, c->perm.kind ? 1.0 : c->mat.k_over_mu, F.t.p, p, src, F.rt.p);
+      // Rt = C^T(-r): the rows of poro_pres_assemble_residual and its la_cons_reduce, into scratch
+      pressure_residual_rows(c, k, F.t.p, F.rt.p);
       la_cons_reduce(s, c->cons_p, F.rt.p);
-      FlowBalanceArgs A{c->n_p, p, p_old, ev, ev0, F.m.p, src, F.rt.p, c->n_pdir ? c->pdir_mask.p : nullptr, c_strain, c_pres};
+      FlowBalanceArgs A{c->n_p, p, p_old, ev, ev0, F.m.p, k.src, F.rt.p, c->n_pdir ? c->pdir_mask.p : nullptr, k.c_strain, k.c_pres};
       { Timed t1(c, "flow_balance_sums"); flow_balance_partials(s, A, c->partials.p); la_reduce_finish(s, c->partials.p, 6, F.sums.p, 0); }   // (the one pass and its finish alone)
       if (outflow_dof_host && c->n_pdir) darcy_gather(s, c->n_pdir, F.pdir_dof.p, F.rt.p, F.out.p);
     }

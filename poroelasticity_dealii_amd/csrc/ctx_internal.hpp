@@ -96,6 +96,19 @@ void count_mfg_launches(poro_ctx *c, int n);                                   /
 double *vec(poro_ctx *c, int which);
 int64_t vec_len(poro_ctx *c, int which);
 bool is_u_vec(int which);
+// the device vector `which` where it belongs to the displacement (or the pressure) space; throws otherwise, in the name of the entry point
+inline const double *space_vector(poro_ctx *c, int which, bool displacement, const char *name) {
+  auto it = c->vec.find(which);
+  if (it == c->vec.end()) throw Error("unknown vector id " + std::to_string(which));
+  const bool ok = displacement ? is_u_vec(which) && (int64_t)it->second.n == c->n_u : !is_u_vec(which) && (int64_t)it->second.n == c->n_p;
+  if (!ok) throw Error(std::string(name) + ": vector " + std::to_string(which) + (displacement ? " is not a displacement-space vector" : " is not a pressure-space vector"));
+  return it->second.p;
+}
+// the post-processing entry points (ctx_flux.hip, ctx_stress.hip) run on one rank
+inline void require_single_rank(poro_ctx *c, const char *name) {
+  if (!c) throw Error("null argument");
+  if (c->comm.part.n_ranks > 1) throw Error(std::string(name) + ": not implemented on partitioned contexts (n_ranks > 1)");
+}
 bool apply_A_u(poro_ctx *c, const double *x, double *y, int mode, double *dot_partials = nullptr, bool fix_rows = true, const PcgScalars *pcg_state = nullptr,
                bool exchange = true /* false: leave the rank's partial product (the caller folds constrained rows first) */);
 
@@ -114,7 +127,7 @@ struct PrecCall {
 enum class GzLeft { nowhere, in_partials /* PrecCall::gz_partials */, in_octant_form /* FdmOct::gz_part, which k_fdmo_update_d reads */ };   // where a call left g . z; nowhere: the driver runs a dot kernel
 typedef std::function<GzLeft(const double *g, double *z, const PrecCall &)> PrecFn;
 
-// One linear system A x = b as the three drivers see it; filled once per solve (ctx.hip: krylov_u and solve_q1 fill what is common to a space)
+// One linear system A x = b as the three drivers see it; filled once per solve (ctx.hip: krylov_u, ctx_pressure.hip: solve_q1 fill what is common to a space)
 struct KrylovSystem {
   int64_t n = 0, plane = 0;            // local length; dofs of one shared plane (slab partitions)
   double *x = nullptr; const double *b = nullptr;
@@ -166,6 +179,15 @@ void build_fdm_u(poro_ctx *c);
 FdmuLineArgs fdmu_line_args(poro_ctx *c);   // per-cell moduli, after build_fdm_u: the arguments of the line-solve kernels (kernels_fdmu_line.hip)
 void release_fdm_u(poro_ctx *c);   // frees what build_fdm_u made; the next use builds again (a change of the requested form)
 void fdm_precondition_u(poro_ctx *c, const double *g, double *z);
+
+// ---- pressure and projection systems (ctx_pressure.hip) ------------------------------------------------------------------------------------
+// The numbers of the pressure equation at one time step: the residual's storage term is c_strain (ev - ev0) + c_pres (p - p_old), its flux term kappa K p (a per-cell k / mu:
+// kappa = 1 and the field sits in Kp / the stencil), src the right-hand side vector (the well, + the Darcy gravity flux while that is on); strain_update: d eps_v = strain_update dp
+struct PressureCoeffs { double c_strain, c_pres, kappa, strain_update; const double *src; };
+PressureCoeffs pressure_coeffs(poro_ctx *c, double dt);
+// rows = the uncondensed, rank-partial residual rows of PORO_VEC_P / P_OLD / EPSV / EPSV0 in the context's form (constant stencil, per-cell stencil or CSR); tmp: scratch of n_p.
+// No timer scope of its own.  gate: the constant stencil alone, throws on the other two
+void pressure_residual_rows(poro_ctx *c, const PressureCoeffs &k, double *tmp, double *rows, const PcgScalars *gate = nullptr);
 
 // ---- mesh adaptation (ctx_adapt.hip) ------------------------------------------------------------------------------------------------------
 // rows a caller hands in (interpolation / transfer): ptr[0] == 0, ptr ascending over n_rows rows, every column in [0, n_cols); throws before anything is uploaded

@@ -12,17 +12,6 @@ using namespace poro::ctx_detail;
 namespace {
 constexpr double kHalfPi = 1.57079632679489661923;
 
-void check_stress_call(poro_ctx *c, const char *name) {
-  if (!c) throw Error("null argument");
-  if (c->comm.part.n_ranks > 1) throw Error(std::string(name) + ": not implemented on partitioned contexts (n_ranks > 1)");
-}
-const double *space_vector(poro_ctx *c, int which, bool displacement, const char *name) {
-  auto it = c->vec.find(which);
-  if (it == c->vec.end()) throw Error("unknown vector id " + std::to_string(which));
-  const bool ok = displacement ? is_u_vec(which) && (int64_t)it->second.n == c->n_u : !is_u_vec(which) && (int64_t)it->second.n == c->n_p;
-  if (!ok) throw Error(std::string(name) + ": vector " + std::to_string(which) + (displacement ? " is not a displacement-space vector" : " is not a pressure-space vector"));
-  return it->second.p;
-}
 int n_sym(const poro_ctx *c) { return c->dim * (c->dim + 1) / 2; }
 
 void build_cells(poro_ctx *c) {
@@ -70,7 +59,7 @@ extern "C" {
 
 int poro_disp_cell_stress(poro_ctx *c, int which_u, int which_p, double *strain_host, double *stress_eff_host, double *stress_tot_host) {
   return guarded([&] {
-    check_stress_call(c, "poro_disp_cell_stress");
+    require_single_rank(c, "poro_disp_cell_stress");
     const double *u = space_vector(c, which_u, true, "poro_disp_cell_stress");
     const double *p = which_p == -1 ? nullptr : space_vector(c, which_p, false, "poro_disp_cell_stress");
     PORO_HIP(hipSetDevice(c->device));
@@ -89,7 +78,7 @@ int poro_disp_cell_stress(poro_ctx *c, int which_u, int which_p, double *strain_
 
 int poro_disp_cell_measures(poro_ctx *c, int which_u, int which_p, const poro_mohr_coulomb *mc, double *measures_host, poro_failure_summary *summary) {
   return guarded([&] {
-    check_stress_call(c, "poro_disp_cell_measures");
+    require_single_rank(c, "poro_disp_cell_measures");
     const double *u = space_vector(c, which_u, true, "poro_disp_cell_measures");
     if (which_p != -1) space_vector(c, which_p, false, "poro_disp_cell_measures");       // checked, then ignored: the measures are of the effective stress
     if (mc && !(mc->cohesion >= 0 && std::isfinite(mc->cohesion))) throw Error("poro_disp_cell_measures: the cohesion must be finite and >= 0");
@@ -115,7 +104,7 @@ int poro_disp_cell_measures(poro_ctx *c, int which_u, int which_p, const poro_mo
 
 int poro_disp_force_balance(poro_ctx *c, poro_force_balance_terms *out, double *reaction_dof_host) {
   return guarded([&] {
-    check_stress_call(c, "poro_disp_force_balance");
+    require_single_rank(c, "poro_disp_force_balance");
     if (!out) throw Error("null argument");
     PORO_HIP(hipSetDevice(c->device));
     build_balance(c);

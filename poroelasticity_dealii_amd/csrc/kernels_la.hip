@@ -67,7 +67,7 @@ __global__ void k_reduce_post(const double *partials, int n_sets, double *red, i
   if (threadIdx.x == 0) __hip_atomic_store(const_cast<unsigned long long *>(&mb->seq), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// ---- the pressure Newton loop as one gated batch (ctx.hip: poro_pres_newton_loop) ----------------------------------------------------------------------------------
+// ---- the pressure Newton loop as one gated batch (ctx_pressure.hip: poro_pres_newton_loop) ----------------------------------------------------------------------------------
 // The gate is a PcgScalars of its own whose `done` holds the loop's code (newton_record.hpp: 0 open, 1 converged, 2 fallback): every kernel of the batch tests it the way
 // the launches of a CG iteration test theirs.  rec[kNewtonRecord] is the batch's record, which the last kernel copies to the mailbox
 __global__ void k_newton_reset(PcgScalars *gate, double *rec) {

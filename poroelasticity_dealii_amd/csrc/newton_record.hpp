@@ -1,4 +1,4 @@
-// Host-only: the record of the pressure Newton loop's gated batches (ctx.hip: poro_pres_newton_loop) and what the host rebuilds from it.  Free of HIP and of project
+// Host-only: the record of the pressure Newton loop's gated batches (ctx_pressure.hip: poro_pres_newton_loop) and what the host rebuilds from it.  Free of HIP and of project
 // headers: the library plans its batches and reads their records with these functions, and tests/newton_record_check.cpp runs them under the sanitizers.
 //
 // A batch is a run of up to kNewtonSlots pressure iterations enqueued without a wait.  Slot j holds the two parts of one iteration of PoroelasticityFSS.h:358-380:
